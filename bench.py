@@ -331,6 +331,63 @@ def make_results(ctx, pg, colsums, per_genome, piece_tiles):
     return [r], merged
 
 
+DUMP_CAPS = {"bitmap1": 22 << 20, "bitmap100": 22 << 20, "bins": 8 << 20, "colsums": 8 << 20}  # bytes per kind, 60 MB in all
+DUMP_SEED = 20240607  # the sampled positions depend on the output shapes and this seed only
+
+
+def dump_outputs(out_dir, results, colsums):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step, as .npy files (float32 where exact,
+    float64 otherwise), for comparing two builds output for output.  Contigs in launch order (genome-major), numbered
+    across ``results``; where a kind is larger than its share of DUMP_CAPS, a fixed seeded sample of its rows is written
+    with the rows' global indices (``<kind>_index``).
+      bitmap1    [n, nbytes]   bitmap.1 rows (presence bytes, bit g = genome g) at sampled k-mer positions
+      bitmap100  [n, nbytes]   bitmap.100 rows (every 100th position)
+      bins       [n, G + 1]    bin histograms (bitsum.bins.tsv), all contigs' bins one after the other
+      colsums    [contigs, G]  per-contig column sums (with colsums on)
+    Every contig's rows are copied to the host once, outside the timed region.  Returns {name: shape} of what was written."""
+    os.makedirs(out_dir, exist_ok=True)
+    contigs = [(r, i) for r in results for i in range(len(r.seqs.lens))]
+    infos = [r.contig_info(i) for r, i in contigs]
+    nb, G = results[0].nbytes, results[0].ngenomes
+    counts = {"bitmap1": [x["nkmers"] for x in infos], "bitmap100": [x["nrows100"] for x in infos],
+              "bins": [x["nbins"] for x in infos]}
+    row_bytes = {"bitmap1": 4 * nb, "bitmap100": 4 * nb, "bins": 4 * (G + 1)}
+    rng = np.random.default_rng(DUMP_SEED)
+    picks, starts = {}, {}
+    for kind, cnt in counts.items():
+        starts[kind] = np.concatenate([[0], np.cumsum(cnt, dtype=np.int64)])
+        total = int(starts[kind][-1])
+        n = DUMP_CAPS[kind] // row_bytes[kind]
+        if total > n:  # (the index costs 8 bytes per row more)
+            n = DUMP_CAPS[kind] // (row_bytes[kind] + 8)
+            picks[kind] = np.unique(rng.integers(0, total, n, dtype=np.int64))
+        else:
+            picks[kind] = None
+    parts = {kind: [] for kind in counts}
+    for c, (r, i) in enumerate(contigs):
+        got = dict(zip(("bitmap1", "bitmap100", "bins"), r.download(i)[:3]))
+        for kind, a in got.items():
+            lo, hi = int(starts[kind][c]), int(starts[kind][c + 1])
+            if picks[kind] is not None:
+                p = picks[kind]
+                a = a[p[np.searchsorted(p, lo):np.searchsorted(p, hi)] - lo]
+            parts[kind].append(a.astype(np.float32))
+    arrays = {kind: np.concatenate(v) if v else np.zeros((0, row_bytes[kind] // 4), np.float32) for kind, v in parts.items()}
+    for kind, p in picks.items():
+        if p is not None:
+            arrays[kind + "_index"] = p.astype(np.float64)
+    if colsums:
+        cs = np.concatenate([r.contig_colsums(0) for r in results]).astype(np.float64)
+        if cs.nbytes > DUMP_CAPS["colsums"]:
+            p = np.unique(rng.integers(0, len(cs), DUMP_CAPS["colsums"] // (8 * G + 8), dtype=np.int64))
+            cs, arrays["colsums_index"] = cs[p], p.astype(np.float64)
+        arrays["colsums"] = cs
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 KERNEL_SOURCES = ("pg_anchor.hip", "pg_device.h", "pg_kernels.h", "pg_kernels.hip", "pg_api.hip")  # what k_probe / k_epilogue are compiled from, and what picks the table layout and window they run with (geom_for, k_table_init)
 
 
@@ -1096,7 +1153,7 @@ def plant_like_pangenome(dev, G, C, L, d, seed, families=30, repeat_share=0.5):
     return genomes, what
 
 
-def sharded_leg(ctx, dev, args, rank, world, dist, steps, warmup, nblocks=None):
+def sharded_leg(ctx, dev, args, rank, world, dist, steps, warmup, nblocks=None, dump_dir=None):
     """The genome-sharded pipeline (panagram_amd.distributed.ShardedAnchoring — what Index.run() uses when the
     table exceeds one GPU) on the configs[1] pangenome: rank r holds the table of genome block r only, every rank
     probes all anchor positions; extract + all-gather (RCCL over xGMI) + merge + statistics are all timed."""
@@ -1125,6 +1182,7 @@ def sharded_leg(ctx, dev, args, rank, world, dist, steps, warmup, nblocks=None):
     dt = timed_steps(step, steps, warmup, world, dev, dist)
     pos = sum(pg.pos_per_genome)
     mine = [a for a in names if writer[a] == rank]
+    dumped = dump_outputs(dump_dir, [sh.full[a] for a in mine], True) if dump_dir and rank == 0 else None
     if mine and not emulated:  # the writer's completed rows: the anchor holds all of its own k-mers
         cs = sh.full[mine[0]].colsums()
         assert int(cs[names.index(mine[0])]) == pg.pos_per_genome[names.index(mine[0])]
@@ -1144,6 +1202,8 @@ def sharded_leg(ctx, dev, args, rank, world, dist, steps, warmup, nblocks=None):
                         f"columns sent to the anchors' writers, rows merged + statistics there"),
         "columns_from_the_probe": bool(getattr(sh, "_direct", False)),
     }
+    if dumped is not None:
+        out["dump_outputs"] = {"dir": dump_dir, "arrays": dumped, "anchors": mine}
     sh.close()
     pg.close()
     ctx.trim()
@@ -1209,12 +1269,17 @@ def main():
     ap.add_argument("--no-config5", action="store_true", help="skip the BASELINE configs[4] leg (8 x 3 Gb, d=0.05, 8 genome blocks as passes on this GPU)")
     ap.add_argument("--settle-s", type=float, default=0.4, help="seconds of untimed steps before the warm-up steps (the shader clock settles; 0: none)")
     ap.add_argument("--cpu-sample-mb", type=float, default=20.0, help="bases per thread of the CPU baseline leg (about 12 s of CPU work)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0's share) as "
+                         "DIR/<name>.npy, at most 64 MB (a fixed seeded sample of the rows): see dump_outputs")
     ap.add_argument("--e2e-config4-child", default="", metavar="write:DIR|run:DIR", help=argparse.SUPPRESS)  # (baseline_config_legs' files -> files leg, in processes of its own)
     ap.add_argument("--emulate-rank", type=str, default="", metavar="R/N",
                     help="one process plays rank R of an N-rank contig-sharded run (no collective): the N x longer "
                          "pangenome, the replicated table and rank R's contig group, for checking the multi-GPU "
                          "set-up on a one-GPU box; the reported value is this rank's alone")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.e2e_config4_child:
         mode, d = args.e2e_config4_child.split(":", 1)
@@ -1272,7 +1337,7 @@ def main():
     default_shape = (G, round(args.genome_mb), k, C, args.d) == (8, 100, 21, 5, 0.01)
 
     if args.mode == "genome-sharded":
-        leg = sharded_leg(ctx, dev, args, rank, world, dist, args.steps, args.warmup, args.blocks)
+        leg = sharded_leg(ctx, dev, args, rank, world, dist, args.steps, args.warmup, args.blocks, dump_dir=args.dump_outputs or None)
         out = {"metric": "anchored k-mers/sec building pan-kmer bitmap", "value": leg["value"], "unit": "k-mers/s",
                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": leg["ms_per_step"],
                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
@@ -1337,6 +1402,7 @@ def main():
     avg_epi_s = float(np.mean([t[1] for t in tm])) / 1e3
     nruns = int(sum(t[2] for t in tm))
     pos_per_launch = pos_per_step / len(results)
+    dumped = dump_outputs(args.dump_outputs, results, not args.no_colsums) if args.dump_outputs and rank == 0 else None
 
     def genome_rows(g, n):  # first n rows of genome g's first contig
         r, ci = (results[g], 0) if args.per_genome_launches else (results[0], g * C)
@@ -1407,6 +1473,7 @@ def main():
         "dtype": "u64",
         "data": "synthetic",
         "ranks_observed": ranks_observed,
+        "dump_outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped is not None else None,
         "config": {
             "workload": workload,
             "positions_per_step_per_gpu": pos_per_step,

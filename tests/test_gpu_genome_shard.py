@@ -144,14 +144,14 @@ def _check_tree(out, fx, gzi_like_reference=True):
 def test_index_run_genome_sharded_on_one_gpu(name, nblocks, chunk, direct, tmp_path, monkeypatch):
     """Index.run() in the genome-sharded mode: one GPU works the genome blocks off as passes.  ("n8_k21", 8): one
     genome per block — config 5's layout; chunk: positions per exchanged chunk, small ones make every anchor
-    several chunks (double-buffered pipeline) whose last ones are short."""
+    several chunks (double-buffered pipeline) whose last ones are short.  direct: PG_COLUMNS_DIRECT on — one-genome
+    blocks get their bit columns straight from the probe; wider blocks do not qualify, and the pipeline must fall
+    back to extracting the columns from narrow rows with the same tree."""
     from panagram_amd import distributed as pdist
     from panagram_amd import index as pidx
     fx = H.load_case(name)
     s = _write_case(tmp_path, fx)
     out = tmp_path / "idx"
-    if direct and (name, nblocks) not in (("n8_k21", 8), ("n2_k21", 2)):
-        pytest.skip("columns straight from the probe only exist for one-genome blocks")
     from panagram_amd import engine
     monkeypatch.setattr(engine, "COLUMNS_DIRECT", direct)  # (PG_COLUMNS_DIRECT: off by default)
     monkeypatch.setattr(pdist, "CHUNK_POSITIONS", chunk)
@@ -351,11 +351,10 @@ def test_two_processes_on_one_gpu(name, shard, nblocks, chunk, exchange, tmp_pat
     """("n8_k21", genome, 2): one pass, each rank one block of 4 genomes; (…, 8): four passes of one-genome blocks
     (config 5's layout; columns straight from the probe); ("n9_k21", 4): blocks of 3, 3, 3 on two ranks — the second
     pass has an idle rank; replicated: pieces of homology classes dealt to the two ranks (both anchor every genome's
-    share, co-scheduled), fragments assembled by whoever finds a genome complete, no collective."""
+    share, co-scheduled), fragments assembled by whoever finds a genome complete, no collective — PG_SHARD_EXCHANGE
+    ("host" or "rccl") must then change nothing."""
     import torch.multiprocessing as mp
     import os
-    if exchange == "host" and shard == "replicated":
-        pytest.skip("no exchange step in the contig-sharded mode")
     # ("host": the two ranks' columns go GPU -> pinned host -> gloo all-gather -> GPU, PG_SHARD_EXCHANGE's fallback route;
     # "rccl" here hands the CUDA tensors to the gloo group of this one-GPU set-up, see above)
     monkeypatch.setenv("PG_SHARD_EXCHANGE", exchange)
@@ -368,15 +367,17 @@ def test_two_processes_on_one_gpu(name, shard, nblocks, chunk, exchange, tmp_pat
     _check_tree(out, fx, gzi_like_reference=shard != "replicated")
 
 
-@pytest.mark.parametrize("shard,nblocks,chunk", [("genome", 8, 1500), ("replicated", 0, 1 << 27)])
-def test_eight_processes_on_one_gpu(shard, nblocks, chunk, tmp_path, monkeypatch):
-    """An 8-rank dress rehearsal on the one device — the first contact with an 8-GPU node should not be the first time
-    anything runs at world = 8.  genome / 8 blocks on "n8_k21" is BASELINE.json configs[4]'s layout exactly: EIGHT real-engine
-    processes, one genome's table each, every rank probing every anchor position (several chunk groups per anchor), the 8
-    bit columns exchanged per group and merged on the anchors' writers, ONE pass.  RCCL refuses several ranks on one device,
-    so the exchange takes the product's host route (PG_SHARD_EXCHANGE=host: columns to pinned memory, all-gather over gloo,
-    back to the GPU) — what that route is for.  replicated: pieces of homology classes dealt to 8 ranks, fragments assembled
-    without a rendezvous.  Both trees equal the reference binary's golden outputs (cpp/anchor.cpp:139-164, 217-223)."""
+@pytest.mark.parametrize("shard,nblocks,chunk", [("genome", 4, 1500), ("genome", 8, 1500), ("replicated", 0, 1 << 27)])
+def test_four_processes_on_one_gpu(shard, nblocks, chunk, tmp_path, monkeypatch):
+    """A multi-rank dress rehearsal on the one device beyond two ranks: FOUR real-engine processes (with this one, five
+    processes hold the GPU — no more than a shared device should carry at once; the 8-rank control flow runs on CPU in
+    test_distributed_cpu).  genome / 4 blocks on "n8_k21": one pass, each rank one block of two genomes, every rank
+    probing every anchor position (several chunk groups per anchor), the bit columns exchanged per group and merged on
+    the anchors' writers.  genome / 8 blocks: BASELINE.json configs[4]'s layout of one genome per block (columns of
+    width 1), two passes of four blocks.  RCCL refuses several ranks on one device, so the exchange takes the product's
+    host route (PG_SHARD_EXCHANGE=host: columns to pinned memory, all-gather over gloo, back to the GPU) — what that route
+    is for.  replicated: pieces of homology classes dealt to 4 ranks, fragments assembled without a rendezvous.  All
+    trees equal the reference binary's golden outputs (cpp/anchor.cpp:139-164, 217-223)."""
     import torch.multiprocessing as mp
     import os
     monkeypatch.setenv("PG_SHARD_EXCHANGE", "host")
@@ -385,8 +386,8 @@ def test_eight_processes_on_one_gpu(shard, nblocks, chunk, tmp_path, monkeypatch
     s = _write_case(tmp_path, fx)
     out = tmp_path / "idx"
     port = 29600 + (os.getpid() % 2000)
-    mp.spawn(_two_rank_worker, args=(8, port, str(s), str(out), int(fx["k"]), [f"g{g}" for g in fx["anchors"]], shard, nblocks, chunk),
-             nprocs=8, join=True)
+    mp.spawn(_two_rank_worker, args=(4, port, str(s), str(out), int(fx["k"]), [f"g{g}" for g in fx["anchors"]], shard, nblocks, chunk),
+             nprocs=4, join=True)
     _check_tree(out, fx, gzi_like_reference=shard != "replicated")
 
 
@@ -415,18 +416,17 @@ def _real_gpu_worker(rank, world, port, samples, out, k, anchors, shard, nblocks
 @pytest.mark.parametrize("name,shard,nblocks,chunk", [("n9_k21", "replicated", 0, 1 << 27), ("n8_k21", "genome", 0, 1500),
                                                       ("n8_k21", "genome", 8, 1 << 27)])
 def test_real_gpus_over_rccl_give_the_one_rank_tree(name, shard, nblocks, chunk, tmp_path, monkeypatch):
-    """SURVEY section 4's "1 vs N GPUs produce identical payload bytes", on REAL GPUs: Index.run() on min(8, device_count)
-    ranks, one process per GPU, torch.distributed backend "nccl" (= RCCL over xGMI) — the contig-sharded mode ("replicated":
+    """SURVEY section 4's "1 vs N GPUs produce identical payload bytes", on REAL GPUs: Index.run() on min(4, device_count)
+    ranks (with this process, at most five hold a GPU at once), one process per GPU, torch.distributed backend "nccl" (= RCCL over xGMI) — the contig-sharded mode ("replicated":
     pieces of homology classes dealt to the ranks, no collective; cpp/anchor.cpp:217-223 is the axis) and the genome-sharded
     mode (one genome block per GPU, or 8 one-genome blocks as passes: the bit columns cross xGMI) — against the reference
-    binary's golden outputs AND against the tree one rank writes on its own.  Skipped on a one-GPU box (there the same
-    code runs with several processes on the one device over gloo: test_two/eight_processes_on_one_gpu)."""
+    binary's golden outputs AND against the tree one rank writes on its own.  On a one-GPU box: ONE rank in an RCCL
+    group of one (RCCL refuses several ranks on one device; the several-rank code runs there over gloo in
+    test_two/four_processes_on_one_gpu) — the launcher's set-up and Index.run() under it, against the same trees."""
     import os
     import torch.multiprocessing as mp
     ngpu = torch.cuda.device_count()
-    if ngpu < 2:
-        pytest.skip("needs at least two GPUs (RCCL refuses several ranks on one device)")
-    world = min(8, ngpu)
+    world = min(4, ngpu)
     monkeypatch.setenv("PG_MIN_PIECE", "500")  # (the fixture's contigs are a few kb: cut them all the same)
     fx = H.load_case(name)
     s = _write_case(tmp_path, fx)

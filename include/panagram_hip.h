@@ -172,6 +172,28 @@ int pg_sketch_estimate_registers(const uint8_t *regs65536, uint64_t *distinct);
 int pg_sketch_reset(pg_sketch *sk);
 int pg_sketch_destroy(pg_sketch *sk);
 
+/* MinHash sketch of a sample (genome_dist.tsv): the s smallest distinct h1 of MurmurHash3_x64_128(seed) over the ASCII
+ * bytes of its canonical k-mers (k = 21, the lexicographically smaller of a k-mer and its reverse complement, k-mers
+ * with a base other than ACGT skipped) — the sketch of the reference workflow's `mash sketch -s 10000`
+ * (panagram/workflow/Snakefile:124-149).  The GPU hashes every k-mer and keeps those below a threshold tau as
+ * candidates, tau = 2^64 * min(1, 4 s / expected_distinct) (expected_distinct 0: the seqset's k-mer positions); fewer
+ * than s distinct candidates below tau < 2^64 reruns with 4 tau, more candidates than the buffer holds with a 4x
+ * buffer.  tau / capacity other than 0 replace the automatic choices (tests: both fallbacks).  Several seqsets added
+ * make one sketch (their union); bases: the ACGT bases added; passes: the kernel launches since create / reset. */
+typedef struct pg_minhash pg_minhash;
+int pg_minhash_create(pg_ctx *ctx, int k, uint32_t s, uint32_t seed, uint64_t tau, uint64_t capacity, pg_minhash **out);
+int pg_minhash_add_seqset(pg_minhash *mh, const pg_seqset *seqs, uint64_t expected_distinct);
+/* the sketch, ascending, into hashes (room for s): *count values */
+int pg_minhash_result(pg_minhash *mh, uint64_t *hashes, uint32_t *count, uint64_t *bases, uint32_t *passes);
+int pg_minhash_reset(pg_minhash *mh);
+int pg_minhash_destroy(pg_minhash *mh);
+/* host only (no device): every pair i < j of n sketches — sketch i = hashes[offsets[i], offsets[i + 1]), ascending —
+ * in the order (0,1) (0,2) .. (0,n-1) (1,2) ..: mash's merge (common / denom of the s smallest of the union), the
+ * distance -ln(2J / (1 + J)) / k (J = common / denom; 1 when nothing is shared, at most 1) and, when bases (ACGT bases
+ * per sample) is not NULL, the p-value P[Binomial(denom, r) >= common] of mash's model (pvalue may be NULL) */
+int pg_minhash_distances(const uint64_t *hashes, const uint64_t *offsets, uint32_t n, uint32_t s, int k, const uint64_t *bases,
+                         double *dist, double *pvalue, uint32_t *common, uint32_t *denom);
+
 /* re-hash into the smallest table whose mean occupancy is <= keys_per_bucket keys per 128 bytes;
  * also settles the minimizer length for the keys actually present */
 int pg_table_rehash(pg_table *tbl, double keys_per_bucket);

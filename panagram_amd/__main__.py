@@ -20,6 +20,10 @@ def main(argv=None):
     ix.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     ix.add_argument("--export_kmc", action="store_true", help="also write kmc/bitvec{i} (KMC1 layout)")
     ix.add_argument("--kmc.use_existing", dest="use_existing", action="store_true")
+    ix.add_argument("--genome_dist", action="store_true", help="also write genome_dist.tsv (MinHash distances, for panagram view)")
+    ds = sub.add_parser("dist", help="write genome_dist.tsv of an existing index (MinHash sketches on the GPU)")
+    ds.add_argument("index_dir")
+    ds.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     ra = sub.add_parser("run_anchor", help="argv-compatible with the reference's cpp/run_anchor")
     ra.add_argument("args", nargs="+")
     ra.add_argument("--device", type=int, default=0)
@@ -28,8 +32,16 @@ def main(argv=None):
         from .index import KMC, Index
         idx = Index(a.input, prefix=a.prefix, k=a.k, cores=a.cores, prepare=a.prepare,
                     anchor_genomes=a.anchor_genomes, device=a.device, export_kmc=a.export_kmc,
-                    kmc=KMC(use_existing=a.use_existing))
+                    kmc=KMC(use_existing=a.use_existing), genome_dist=a.genome_dist)
         idx.run()
+        return 0
+    if a.cmd == "dist":
+        from .index import Index
+        idx = Index(a.index_dir, mode="r", device=a.device)
+        try:
+            print("Wrote", idx.write_genome_dist())
+        finally:
+            idx.close()
         return 0
     from .index import run_anchor_cli
     return run_anchor_cli(a.args, a.device)

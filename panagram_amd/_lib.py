@@ -66,6 +66,12 @@ PROTOTYPES = {
     "pg_sketch_reset": (C.c_int, [_vp]),
     "pg_table_bytes_for": (C.c_int, [C.c_int, C.c_int, C.c_uint64, _u64p]),
     "pg_sketch_destroy": (C.c_int, [_vp]),
+    "pg_minhash_create": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, _vpp]),
+    "pg_minhash_add_seqset": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "pg_minhash_result": (C.c_int, [_vp, _vp, _u32p, _u64p, _u32p]),
+    "pg_minhash_reset": (C.c_int, [_vp]),
+    "pg_minhash_destroy": (C.c_int, [_vp]),
+    "pg_minhash_distances": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "pg_table_export": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint64, _u64p]),
     "pg_table_k": (C.c_int, [_vp]),
     "pg_table_ngenomes": (C.c_int, [_vp]),

@@ -82,6 +82,14 @@ hipError_t launch_sketch(hipStream_t st, int k, const uint64_t *seqw, const uint
 constexpr uint32_t SKETCH_JOB = 1u << 16;
 hipError_t launch_sketch_set(hipStream_t st, int k, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint64_t *seqw,
                              const uint32_t *nmw, const uint32_t *has_n, uint32_t *regs);
+// MinHash candidates of a seqset (pg_minhash.hip): canonical 21-mers (mash's default k) hashed with MurmurHash3_x64_128;
+// h1 <= limit goes to cand (slots >= cap only counted in *count).  jobs[j] = (contig, chunk): BASES [chunk, chunk + 1) x
+// MINHASH_JOB — every contig with a base has jobs (*bases += its ACGT bases), the k-mers starting there are hashed
+constexpr int MINHASH_K = 21;
+constexpr uint32_t MINHASH_JOB = 1u << 16;
+hipError_t launch_minhash(hipStream_t st, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint64_t *seqw,
+                          const uint32_t *nmw, const uint32_t *has_n, uint64_t limit, uint32_t seed, uint64_t *cand, uint64_t cap,
+                          unsigned long long *count, unsigned long long *bases);
 hipError_t launch_insert_seq(hipStream_t st, const SubTable &t, int w, uint32_t bits, int k,
                              const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n,
                              uint64_t nkmers, unsigned long long *counters, uint32_t max_probe, int count_mode = 0);

@@ -377,6 +377,72 @@ class KmerSketch:
             pass
 
 
+class MinHashSketch:
+    """Bottom-s MinHash sketch of a sample on the GPU — the s smallest distinct h1 of MurmurHash3_x64_128 (seed 42) over
+    the canonical 21-mers, what `mash sketch -s 10000` keeps (the reference workflow's genome_dist.tsv,
+    panagram/workflow/Snakefile:124-149).  ``distinct``: the sample's distinct k-mer estimate (KmerSketch), which sets the
+    candidate threshold; ``tau`` / ``capacity`` (0: automatic) force the threshold and the candidate buffer (tests of
+    the reruns).  Several ``add`` calls make one sketch of their union."""
+
+    K, S, SEED = 21, 10000, 42
+
+    def __init__(self, ctx: Context, k: int = K, s: int = S, seed: int = SEED, tau: int = 0, capacity: int = 0):
+        self.ctx, self._lib, self.k, self.s = ctx, ctx._lib, k, s
+        h = C.c_void_p()
+        check(self._lib.pg_minhash_create(ctx._h, k, s, seed, tau, capacity, C.byref(h)))
+        self._h = h
+        ctx._adopt(self)
+
+    def add(self, seqs: SeqSet, distinct: int = 0) -> None:
+        check(self._lib.pg_minhash_add_seqset(self._h, seqs._h, int(distinct)))
+
+    def result(self) -> Tuple[np.ndarray, int]:
+        """(the sketch: ascending uint64, at most s values; ACGT bases added)"""
+        out = np.empty(self.s, np.uint64)
+        n, bases = C.c_uint32(), C.c_uint64()
+        check(self._lib.pg_minhash_result(self._h, _ptr(out), C.byref(n), C.byref(bases), None))
+        return out[:n.value].copy(), int(bases.value)
+
+    def passes(self) -> int:
+        """kernel launches since creation / reset (1 per sample unless a rerun was needed)"""
+        n, p = C.c_uint32(), C.c_uint32()
+        check(self._lib.pg_minhash_result(self._h, None, C.byref(n), None, C.byref(p)))
+        return int(p.value)
+
+    def reset(self) -> None:
+        check(self._lib.pg_minhash_reset(self._h))
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.pg_minhash_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def minhash_distances(sketches: Sequence[np.ndarray], bases: Optional[Sequence[int]] = None, s: int = MinHashSketch.S,
+                      k: int = MinHashSketch.K):
+    """Every pair i < j of sketches, in the order (0,1) (0,2) .. (1,2) ..: (distance, p-value, common, denom) arrays —
+    mash's compareSketches (host only, no device).  ``bases``: ACGT bases per sample for the p-values (None: all 1)."""
+    n = len(sketches)
+    offsets = np.zeros(n + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(x) for x in sketches])
+    hashes = np.ascontiguousarray(np.concatenate([np.asarray(x, np.uint64) for x in sketches]) if n else np.zeros(0, np.uint64))
+    npairs = n * (n - 1) // 2
+    dist, pval = np.empty(npairs, np.float64), np.empty(npairs, np.float64)
+    common, denom = np.empty(npairs, np.uint32), np.empty(npairs, np.uint32)
+    b = None if bases is None else np.ascontiguousarray(bases, np.uint64)
+    if b is not None and b.size != n:
+        raise ValueError("one base count per sketch")
+    check(_lib.load().pg_minhash_distances(_ptr(hashes), _ptr(offsets), n, s, k, _ptr(b), _ptr(dist), _ptr(pval), _ptr(common),
+                                           _ptr(denom)))
+    return dist, pval, common, denom
+
+
 class PanTable(_Owner):
     """GPU-resident k-mer -> genome-mask table (replaces kmc/bitvec{i})."""
 

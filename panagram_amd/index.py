@@ -19,7 +19,10 @@ Output tree (identical to the reference's):
     <prefix>/anchor/<name>/bitmap.1.gz(.gzi) bitmap.100.gz(.gzi) bitsum.bins.tsv chrs.tsv
                            total_paircounts.csv
 
-Out of scope here: GFF annotation, UMAPs, mash distances, the viewer.
+    <prefix>/genome_dist.tsv       (opt-in: ``genome_dist=True`` / ``index --genome_dist`` / the ``dist`` command;
+                                    MinHash sketches taken on the GPU in place of `mash sketch` + `mash triangle`)
+
+Out of scope here: GFF annotation, UMAPs, mash's own .msh files, the viewer.
 """
 from __future__ import annotations
 
@@ -298,8 +301,10 @@ class Index:
     genome_blocks: int = dataclasses.field(default_factory=lambda: int(os.environ.get("PG_GENOME_BLOCKS", "0")))
     # build the replicated table from the genomes this process anchors, the other samples only set bits (PG_FULL_TABLE=1: all k-mers)
     filtered_table: bool = dataclasses.field(default_factory=lambda: os.environ.get("PG_FULL_TABLE", "") in ("", "0"))
+    # also write genome_dist.tsv (write_genome_dist): off by default, so that the default tree and config.yaml stay as they were
+    genome_dist: bool = False
 
-    _EXTRA = ("device", "export_kmc", "rank", "world", "shard", "genome_blocks", "filtered_table")
+    _EXTRA = ("device", "export_kmc", "rank", "world", "shard", "genome_blocks", "filtered_table", "genome_dist")
     # keys of config.yaml that describe one invocation, not the index: not taken over when a directory is re-opened
     # (`prepare` is written for schema compatibility, but a later `index <dir>` run must not stop at "Prepared")
     _NOT_IN_CONFIG = ("input", "mode", "prefix", "prepare")
@@ -324,6 +329,7 @@ class Index:
         self._table_scope = "all"
         self.timings: Dict[str, float] = {}  # seconds spent in load_inputs / build_table (host wall clock), for reports
         self._seqsets: Dict[str, engine.SeqSet] = {}
+        self._minhash: Dict[str, Tuple[np.ndarray, int]] = {}  # name -> (MinHash sketch, ACGT bases): write_genome_dist
 
     def _reopen_prepared(self):
         self.prefix = self.input
@@ -382,6 +388,10 @@ class Index:
     @property
     def samples_fname(self):
         return os.path.join(self.prefix, "samples.tsv")
+
+    @property
+    def genome_dist_fname(self):
+        return os.path.join(self.prefix, "genome_dist.tsv")
 
     def get_subdir(self, name):
         return os.path.join(self.prefix, name)
@@ -514,6 +524,8 @@ class Index:
         t_start = time.perf_counter()
         inputs = []
         sketch = engine.KmerSketch(self.context, self.k)
+        # genome_dist.tsv: each sample's MinHash sketch while its sequence is resident (only the writing rank needs them)
+        minhash = engine.MinHashSketch(self.context) if self.genome_dist and self.rank == 0 else None
         # the FASTA files are read a few ahead by host threads while the GPU parses and sketches — plain files straight into a
         # small pool of page-locked buffers (engine.HostBuffer) that go round: the text then goes up by DMA instead of through
         # the runtime's staging copy of pageable memory, and a file costs neither 50 000 page faults nor their unmapping
@@ -557,10 +569,16 @@ class Index:
             sketch.add(ss)
             inputs.append((name, g, ss, min_count, sketch.registers()))
             self.timings["load_sketch_s"] = self.timings.get("load_sketch_s", 0.0) + time.perf_counter() - t0
+            if minhash is not None and name not in self._minhash:
+                t0 = time.perf_counter()
+                self._minhash[name] = self._minhash_of(minhash, ss, engine.KmerSketch.estimate_registers(inputs[-1][4]))
+                self.timings["load_minhash_s"] = self.timings.get("load_minhash_s", 0.0) + time.perf_counter() - t0
         if pool is not None:
             reader.submit(pool.close)  # (unlocking the memory costs as much as locking it, 40 ms per GB: beside the table build)
         reader.shutdown(wait=False)
         sketch.close()
+        if minhash is not None:
+            minhash.close()
         self.context.trim()  # (the FASTA text buffer the parser kept for the next file)
         self._inputs = inputs
         self.timings["load_inputs_s"] = self.timings.get("load_inputs_s", 0.0) + time.perf_counter() - t_start
@@ -698,6 +716,65 @@ class Index:
         self._table, self._table_scope = tbl, scope
         return tbl
 
+    # ---- genome_dist.tsv: rule `mash` of the reference workflow (workflow/Snakefile:124-149) ----
+    @staticmethod
+    def _minhash_of(minhash: "engine.MinHashSketch", ss: "engine.SeqSet", distinct: int = 0) -> Tuple[np.ndarray, int]:
+        minhash.reset()
+        minhash.add(ss, distinct)
+        return minhash.result()
+
+    def write_genome_dist(self) -> str:
+        """Write ``genome_dist.tsv`` — what the reference's workflow makes with ``mash sketch -r -s 10000`` and ``mash
+        triangle -E`` (workflow/Snakefile:124-149) and ``panagram view`` reads at start-up (figs.py:50-59): one line per
+        pair of samples in sample order, ``name_a, name_b, distance, p-value, common/denom``, numbers as %.6g.
+
+        The sketches (engine.MinHashSketch: the 10 000 smallest MurmurHash3 values of the canonical 21-mers, seed 42, mash's
+        defaults whatever this index's k) come from ``load_inputs`` when ``genome_dist`` was set; the samples without one
+        are read, sketched and freed one at a time.  Distances: mash's merge and formula (engine.minhash_distances).  The
+        p-value uses each sample's ACGT bases where mash under ``-r`` estimates a genome size, so that column can differ
+        from mash's; the viewer reads only the names and the distance.  Byte-for-byte agreement with mash 2.3 is the intent,
+        not a tested claim.  Returns the file's path."""
+        names = [str(n) for n in self.genome_names]
+        todo = [n for n in names if n not in self._minhash]
+        if todo:
+            minhash = engine.MinHashSketch(self.context)
+            hll = engine.KmerSketch(self.context, engine.MinHashSketch.K)
+            try:
+                for name in todo:
+                    g = self.genomes[name]
+                    if pd.isna(g.fasta):
+                        self._minhash[name] = (np.zeros(0, np.uint64), 0)
+                        continue
+                    resident = self._seqsets.get(name)
+                    if resident is not None:
+                        ss = resident
+                    elif is_fastq(g.fasta):
+                        ss = engine.SeqSet.from_host(self.context, [read_fastq_joined(g.fasta)])
+                    else:
+                        ss = engine.SeqSet.from_fasta(self.context, g.fasta)
+                    hll.reset()
+                    hll.add(ss)
+                    self._minhash[name] = self._minhash_of(minhash, ss, hll.estimate())
+                    if ss is not resident:
+                        ss.close()
+            finally:
+                hll.close()
+                minhash.close()
+        sketches = [self._minhash[n][0] for n in names]
+        bases = [self._minhash[n][1] for n in names]
+        dist, pval, common, denom = engine.minhash_distances(sketches, bases)
+        lines, t = [], 0
+        for i in range(len(names)):
+            for j in range(i + 1, len(names)):
+                lines.append(f"{names[i]}\t{names[j]}\t{dist[t]:.6g}\t{pval[t]:.6g}\t{common[t]}/{denom[t]}\n")
+                t += 1
+
+        def write(tmp):
+            with open(tmp, "w") as f:
+                f.write("".join(lines))
+        self._write_atomically(self.genome_dist_fname, write)
+        return self.genome_dist_fname
+
     def seqset_for(self, name: str) -> engine.SeqSet:
         """The genome's FASTA, parsed and 2-bit packed in HBM (0.375 byte per base), cached."""
         ss = self._seqsets.get(name)
@@ -825,6 +902,9 @@ class Index:
         own_group = self._ensure_process_group()
         try:
             self._run_planned(ThreadPoolExecutor)
+            if self.genome_dist and self.rank == 0:  # (one writer in a multi-rank run)
+                self.write_genome_dist()
+                self.close()
         finally:
             if own_group:
                 self._dist().destroy_process_group()

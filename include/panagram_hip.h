@@ -459,6 +459,28 @@ int pg_bgzf_write(pg_bgzf *w, const void *data, size_t len);
 /* writes the EOF block, closes the file and, if gzi_path != NULL, the index */
 int pg_bgzf_close(pg_bgzf *w, const char *gzi_path);
 
+/* ---- BGZF inflated on the GPU (k_bgzf_inflate, pg_inflate.hip) -------
+ * Reference: the block-by-block host inflate of Bio.bgzf's BgzfReader (index.py:615-651, 827-845) and of
+ * `panagram annotate` reading bitmap.1.gz back (index.py:971-1010).  One workgroup inflates one BGZF block: full RFC 1951
+ * (stored, fixed and dynamic Huffman blocks, several per member, the empty EOF member), CRC32 and ISIZE checked on the
+ * device.  Every input byte is untrusted: a malformed block returns PG_E_FORMAT, pg_last_error() names its file offset
+ * (the first bad block), and the context stays usable.
+ *
+ * pg_bgzf_inflate: whole blocks held in host memory -> d_out (device memory, out_bytes).  coffs / roffs (nblocks + 1 entries
+ * each: compressed offsets into comp, payload offsets; roffs may be NULL): block i = comp[coffs[i], coffs[i+1]), its payload
+ * at d_out + roffs[i].  coffs == NULL: the blocks are found by walking BSIZE and ISIZE through all comp_bytes (nblocks and
+ * roffs unused).  *raw_bytes (may be NULL) = payload bytes written.  Synchronises. */
+int pg_bgzf_inflate(pg_ctx *ctx, const void *comp, uint64_t comp_bytes, uint32_t nblocks, const uint64_t *coffs,
+                    const uint64_t *roffs, void *d_out, uint64_t out_bytes, uint64_t *raw_bytes);
+/* the rows of contigs first_contig .. first_contig+ncontigs-1 of a result (a rows container: pg_seqset_create from lengths +
+ * pg_result_create_rows) read back from a bitmap.<step>.gz: the result's contig 0 starts at row file_row0 of the file's
+ * payload (0 when the result holds the file's contigs from the first one), so that a long anchor can be read in batches of
+ * chromosomes.  gzi_path (may be NULL) says where to start reading; the blocks are walked from there and checked against it.
+ * Each contig's rows land at its own place in the (padded) row buffer.  Afterwards pg_result_window_stats works on the rows.
+ * Reads the file in pieces of 64 MiB; synchronises. */
+int pg_result_inflate_bgzf(pg_result *r, int step, const char *gz_path, const char *gzi_path, uint32_t first_contig,
+                           uint32_t ncontigs, uint64_t file_row0);
+
 /* bitsum.bins.tsv as KMCdb::anchor_fasta / write_bits write it (cpp/anchor.cpp:57-69,184-189): the header line
  * "chr\tstart\t0\t1...\tN", then for contig c (numbered from 0) and bin b the line
  * "c\t(b * binlen[c])\tcount_0...\tcount_N"; bins = the contigs' rows back to back, ngenomes + 1 counts each.

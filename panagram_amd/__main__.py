@@ -21,9 +21,16 @@ def main(argv=None):
     ix.add_argument("--export_kmc", action="store_true", help="also write kmc/bitvec{i} (KMC1 layout)")
     ix.add_argument("--kmc.use_existing", dest="use_existing", action="store_true")
     ix.add_argument("--genome_dist", action="store_true", help="also write genome_dist.tsv (MinHash distances, for panagram view)")
+    ix.add_argument("--annotate", action="store_true", help="also write the gene / annotation tracks of annotated anchor genomes")
     ds = sub.add_parser("dist", help="write genome_dist.tsv of an existing index (MinHash sketches on the GPU)")
     ds.add_argument("index_dir")
     ds.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    an = sub.add_parser("annotate", help="(Re-)annotate an existing anchored genome using a GFF file")
+    an.add_argument("index_dir")
+    an.add_argument("genome")
+    an.add_argument("gff_file")
+    an.add_argument("--nogene", action="store_true")
+    an.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     ra = sub.add_parser("run_anchor", help="argv-compatible with the reference's cpp/run_anchor")
     ra.add_argument("args", nargs="+")
     ra.add_argument("--device", type=int, default=0)
@@ -32,7 +39,7 @@ def main(argv=None):
         from .index import KMC, Index
         idx = Index(a.input, prefix=a.prefix, k=a.k, cores=a.cores, prepare=a.prepare,
                     anchor_genomes=a.anchor_genomes, device=a.device, export_kmc=a.export_kmc,
-                    kmc=KMC(use_existing=a.use_existing), genome_dist=a.genome_dist)
+                    kmc=KMC(use_existing=a.use_existing), genome_dist=a.genome_dist, annotate=a.annotate)
         idx.run()
         return 0
     if a.cmd == "dist":
@@ -40,6 +47,14 @@ def main(argv=None):
         idx = Index(a.index_dir, mode="r", device=a.device)
         try:
             print("Wrote", idx.write_genome_dist())
+        finally:
+            idx.close()
+        return 0
+    if a.cmd == "annotate":
+        from .index import Index
+        idx = Index(a.index_dir, mode="r", device=a.device)
+        try:
+            idx[a.genome].run_annotate(a.gff_file, nogene=a.nogene)
         finally:
             idx.close()
         return 0

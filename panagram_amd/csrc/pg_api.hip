@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <system_error>
@@ -3473,5 +3474,263 @@ extern "C" int pg_counters_for_read(pg_table *t, int db_idx, const char *ascii, 
     if (d_out) hipFree(d_out);
     pg_seqset_destroy(sq);
     return rc;
+    PG_API_END
+}
+
+// ---------------------------------------------------------------------------
+// BGZF inflated on the GPU (pg_inflate.hip): the host finds the blocks (BSIZE / ISIZE, or the .gzi), uploads their
+// compressed bytes piece by piece and k_bgzf_inflate writes the payload into device memory through a segment map.
+// ---------------------------------------------------------------------------
+static constexpr uint64_t INF_PIECE_BYTES = 64ull << 20;  // compressed bytes per launch
+static constexpr uint32_t INF_PIECE_BLOCKS = 1u << 18;
+
+static const char *inf_what(uint32_t code) {
+    switch (code) {
+    case INF_E_HEADER: return "bad header";
+    case INF_E_TYPE: return "reserved block type";
+    case INF_E_STORED: return "stored block LEN / NLEN mismatch";
+    case INF_E_CODES: return "over-subscribed or incomplete Huffman code";
+    case INF_E_SYMBOL: return "invalid Huffman symbol";
+    case INF_E_DISTANCE: return "distance reaches back past the start of the output";
+    case INF_E_OVERRUN: return "output overruns ISIZE";
+    case INF_E_INPUT: return "deflate data overruns BSIZE";
+    case INF_E_ISIZE: return "ISIZE mismatch";
+    case INF_E_CRC: return "CRC32 mismatch";
+    default: return "malformed";
+    }
+}
+
+// the gzip header of a BGZF block at p (avail bytes from there): header length, BSIZE + 1, ISIZE.  0 when well formed
+static bool bgzf_header(const uint8_t *p, uint64_t avail, uint32_t *hlen, uint32_t *csize, uint32_t *isize) {
+    if (avail < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || p[3] != 4) return false;
+    const uint32_t xlen = p[10] | (p[11] << 8);
+    if (12ull + xlen > avail) return false;
+    uint32_t bsize = 0;
+    bool found = false;
+    for (uint32_t i = 12; i + 4 <= 12 + xlen;) {
+        const uint32_t slen = p[i + 2] | (p[i + 3] << 8);
+        if (p[i] == 'B' && p[i + 1] == 'C' && slen == 2 && i + 6 <= 12 + xlen) {
+            bsize = p[i + 4] | (p[i + 5] << 8);
+            found = true;
+        }
+        i += 4 + slen;
+    }
+    if (!found) return false;
+    *hlen = 12 + xlen;
+    *csize = bsize + 1;
+    if (*csize < *hlen + 8 + 2 || *csize > avail) return false;
+    const uint8_t *f = p + *csize - 4;
+    *isize = (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16) | ((uint32_t)f[3] << 24);
+    return *isize <= 65536;
+}
+
+// blocks[] (coff relative to comp; file offset = file_base + coff) -> d_dst through segs, in launches of whole pieces
+static int inflate_blocks(pg_ctx *ctx, const uint8_t *comp, uint64_t file_base, std::vector<InflBlock> &blocks,
+                          const std::vector<PaySeg> &segs, uint8_t *d_dst) {
+    if (blocks.empty()) return PG_OK;
+    hipStream_t st = ctx->stream;
+    uint32_t *d_comp = nullptr, *d_status = nullptr, *d_crc = nullptr;
+    InflBlock *d_blocks = nullptr;
+    PaySeg *d_segs = nullptr;
+    hipError_t e = hipSuccess;
+    auto ok = [&](hipError_t x) {
+        if (e == hipSuccess) e = x;
+        return e == hipSuccess;
+    };
+    uint64_t span_max = 0;
+    size_t nb_max = 0;
+    for (size_t b0 = 0, b1; b0 < blocks.size(); b0 = b1) {  // piece geometry first: one allocation for every piece
+        for (b1 = b0 + 1; b1 < blocks.size() && b1 - b0 < INF_PIECE_BLOCKS &&
+                          blocks[b1].coff + blocks[b1].csize - blocks[b0].coff <= INF_PIECE_BYTES; ++b1) {
+        }
+        span_max = std::max<uint64_t>(span_max, blocks[b1 - 1].coff + blocks[b1 - 1].csize - blocks[b0].coff);
+        nb_max = std::max(nb_max, b1 - b0);
+    }
+    ok(hipMalloc(reinterpret_cast<void **>(&d_comp), (span_max + 3) / 4 * 4 + 16));
+    ok(hipMalloc(reinterpret_cast<void **>(&d_blocks), nb_max * sizeof(InflBlock)));
+    ok(hipMalloc(reinterpret_cast<void **>(&d_status), nb_max * 4));
+    ok(hipMalloc(reinterpret_cast<void **>(&d_crc), CRC_TAB_WORDS * 4));
+    ok(hipMalloc(reinterpret_cast<void **>(&d_segs), segs.size() * sizeof(PaySeg)));
+    ok(hipMemcpyAsync(d_crc, crc_tables_host(), CRC_TAB_WORDS * 4, hipMemcpyHostToDevice, st));
+    ok(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(PaySeg), hipMemcpyHostToDevice, st));
+    std::vector<uint32_t> status;
+    int rc = PG_OK;
+    for (size_t b0 = 0, b1; e == hipSuccess && rc == PG_OK && b0 < blocks.size(); b0 = b1) {
+        for (b1 = b0 + 1; b1 < blocks.size() && b1 - b0 < INF_PIECE_BLOCKS &&
+                          blocks[b1].coff + blocks[b1].csize - blocks[b0].coff <= INF_PIECE_BYTES; ++b1) {
+        }
+        const uint64_t c0 = blocks[b0].coff, span = blocks[b1 - 1].coff + blocks[b1 - 1].csize - c0;
+        const uint32_t nb = (uint32_t)(b1 - b0);
+        std::vector<InflBlock> piece(blocks.begin() + b0, blocks.begin() + b1);
+        for (auto &b : piece) b.coff -= c0;
+        ok(hipMemcpyAsync(d_comp, comp + c0, span, hipMemcpyHostToDevice, st));
+        ok(hipMemcpyAsync(d_blocks, piece.data(), nb * sizeof(InflBlock), hipMemcpyHostToDevice, st));
+        ok(hipMemsetAsync(d_status, 0, (size_t)nb * 4, st));
+        if (e == hipSuccess)
+            ok(launch_bgzf_inflate(st, d_comp, (span + 3) / 4, d_blocks, nb, d_segs, (uint32_t)segs.size() - 1, d_dst, d_crc, d_status));
+        status.resize(nb);
+        ok(hipMemcpyAsync(status.data(), d_status, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        ok(hipStreamSynchronize(st));
+        if (e != hipSuccess) break;
+        for (uint32_t i = 0; i < nb; ++i)
+            if (status[i]) {
+                rc = fail(PG_E_FORMAT, "BGZF block at file offset %llu: %s", (unsigned long long)(file_base + blocks[b0 + i].coff),
+                          inf_what(status[i]));
+                break;
+            }
+    }
+    if (e != hipSuccess) rc = fail(PG_E_HIP, "BGZF inflate: %s", hipGetErrorString(e));
+    hipFree(d_comp);
+    hipFree(d_blocks);
+    hipFree(d_status);
+    hipFree(d_crc);
+    hipFree(d_segs);
+    return rc;
+}
+
+extern "C" int pg_bgzf_inflate(pg_ctx *ctx, const void *comp_, uint64_t comp_bytes, uint32_t nblocks, const uint64_t *coffs,
+                               const uint64_t *roffs, void *d_out, uint64_t out_bytes, uint64_t *raw_bytes) {
+    PG_API_BEGIN
+    if (!ctx || (comp_bytes && !comp_) || (!coffs && roffs)) return fail(PG_E_INVALID, "pg_bgzf_inflate: bad arguments");
+    const uint8_t *comp = static_cast<const uint8_t *>(comp_);
+    std::vector<InflBlock> blocks;
+    uint64_t roff = 0;
+    if (!coffs) {  // walk BSIZE / ISIZE through the whole buffer
+        for (uint64_t off = 0; off < comp_bytes;) {
+            InflBlock b{};
+            if (!bgzf_header(comp + off, comp_bytes - off, &b.hlen, &b.csize, &b.isize))
+                return fail(PG_E_FORMAT, "BGZF block at file offset %llu: bad header", (unsigned long long)off);
+            b.coff = off;
+            b.roff = roff;
+            roff += b.isize;
+            off += b.csize;
+            blocks.push_back(b);
+        }
+    } else {
+        if (coffs[nblocks] > comp_bytes) return fail(PG_E_INVALID, "pg_bgzf_inflate: block offsets beyond the buffer");
+        for (uint32_t i = 0; i < nblocks; ++i) {
+            InflBlock b{};
+            if (coffs[i + 1] < coffs[i] || !bgzf_header(comp + coffs[i], coffs[i + 1] - coffs[i], &b.hlen, &b.csize, &b.isize) ||
+                b.csize != coffs[i + 1] - coffs[i])
+                return fail(PG_E_FORMAT, "BGZF block at file offset %llu: bad header", (unsigned long long)coffs[i]);
+            b.coff = coffs[i];
+            if (roffs) {  // the caller's raw offsets: the device checks the footer's ISIZE against them
+                if (roffs[i + 1] < roffs[i] || roffs[i + 1] - roffs[i] > 65536)
+                    return fail(PG_E_FORMAT, "BGZF block at file offset %llu: ISIZE mismatch", (unsigned long long)coffs[i]);
+                b.isize = (uint32_t)(roffs[i + 1] - roffs[i]);
+                roff = roffs[i];
+            }
+            b.roff = roff;
+            roff += b.isize;
+            blocks.push_back(b);
+        }
+    }
+    if (roff > out_bytes) return fail(PG_E_INVALID, "pg_bgzf_inflate: %llu payload bytes do not fit %llu", (unsigned long long)roff,
+                                      (unsigned long long)out_bytes);
+    if (roff && !d_out) return fail(PG_E_INVALID, "pg_bgzf_inflate: NULL output");
+    if (int x = use_device(ctx)) return x;
+    std::vector<PaySeg> segs = {{0, 0}, {roff, 0}};
+    if (int x = inflate_blocks(ctx, comp, 0, blocks, segs, static_cast<uint8_t *>(d_out))) return x;
+    if (raw_bytes) *raw_bytes = roff;
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_result_inflate_bgzf(pg_result *r, int step, const char *gz_path, const char *gzi_path, uint32_t first_contig,
+                                      uint32_t ncontigs, uint64_t file_row0) {
+    PG_API_BEGIN
+    if (!r || !gz_path) return fail(PG_E_INVALID, "pg_result_inflate_bgzf: NULL argument");
+    if ((uint64_t)first_contig + ncontigs > r->ad.size())
+        return fail(PG_E_INVALID, "contigs %u..%u out of range", first_contig, first_contig + ncontigs);
+    if (step != 1 && step != 100 && (uint32_t)step != r->lowres_step)
+        return fail(PG_E_INVALID, "step must be 1 or the result's low-resolution step (%u; 100 is accepted as its alias)", r->lowres_step);
+    if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
+    const uint64_t nbytes = (r->N + 7) / 8;
+    // the payload range of the contigs and where each one's rows live in the result
+    std::vector<PaySeg> segs;
+    uint64_t row = file_row0;
+    for (uint32_t c = 0; c < first_contig; ++c) row += step == 1 ? r->ad[c].nkmers : r->nrows100[c];
+    for (uint32_t c = first_contig; c < first_contig + ncontigs; ++c) {
+        segs.push_back({row * nbytes, step == 1 ? r->ad[c].out_off : r->ad[c].out100_off});
+        row += step == 1 ? r->ad[c].nkmers : r->nrows100[c];
+    }
+    const uint64_t R0 = segs.empty() ? row * nbytes : segs[0].lstart, R1 = row * nbytes;
+    segs.push_back({R1, 0});
+    FILE *f = fopen(gz_path, "rb");
+    if (!f) return fail(PG_E_IO, "cannot open %s", gz_path);
+    std::unique_ptr<FILE, int (*)(FILE *)> fguard(f, fclose);
+    fseeko(f, 0, SEEK_END);
+    const uint64_t fsize = (uint64_t)ftello(f);
+    // where to start: the last block at or before R0 (the .gzi: u64 n, then n x (compressed, raw) of blocks 1..n)
+    uint64_t cpos = 0, rpos = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> gzi;
+    if (gzi_path) {
+        FILE *g = fopen(gzi_path, "rb");
+        if (!g) return fail(PG_E_IO, "cannot open %s", gzi_path);
+        uint64_t n = 0;
+        bool good = fread(&n, 8, 1, g) == 1 && n < (1ull << 32);
+        if (good) {
+            gzi.resize(n);
+            for (uint64_t i = 0; good && i < n; ++i) good = fread(&gzi[i].first, 8, 1, g) == 1 && fread(&gzi[i].second, 8, 1, g) == 1;
+        }
+        fclose(g);
+        if (!good) return fail(PG_E_FORMAT, "%s: truncated .gzi", gzi_path);
+        for (size_t i = 1; i < gzi.size(); ++i)
+            if (gzi[i].first <= gzi[i - 1].first || gzi[i].second < gzi[i - 1].second)
+                return fail(PG_E_FORMAT, "%s: offsets not increasing at entry %zu", gzi_path, i);
+        auto it = std::upper_bound(gzi.begin(), gzi.end(), R0, [](uint64_t v, const std::pair<uint64_t, uint64_t> &p) { return v < p.second; });
+        if (it != gzi.begin()) {
+            --it;
+            cpos = it->first;
+            rpos = it->second;
+        }
+    }
+    if (int x = use_device(r->ctx)) return x;
+    if (int x = join_result(r)) return x;
+    uint8_t *dst = step == 1 ? r->d_out1 : r->d_out100;
+    uint8_t *h = nullptr;
+    if (hipHostMalloc(reinterpret_cast<void **>(&h), INF_PIECE_BYTES, hipHostMallocDefault) != hipSuccess)
+        return fail(PG_E_HIP, "pg_result_inflate_bgzf: no pinned staging buffer");
+    std::unique_ptr<uint8_t, hipError_t (*)(void *)> hguard(h, hipHostFree);
+    size_t gi = 0;  // next .gzi entry to compare the walk with
+    int rc = PG_OK;
+    uint64_t prev_coff = UINT64_MAX;
+    while (rc == PG_OK && rpos < R1) {
+        if (cpos >= fsize) return fail(PG_E_FORMAT, "%s ends at payload byte %llu, before byte %llu", gz_path, (unsigned long long)rpos,
+                                       (unsigned long long)R1);
+        const uint64_t want = std::min<uint64_t>(INF_PIECE_BYTES, fsize - cpos);
+        if (fseeko(f, (off_t)cpos, SEEK_SET) != 0 || fread(h, 1, want, f) != want) return fail(PG_E_IO, "short read of %s", gz_path);
+        std::vector<InflBlock> blocks;
+        uint64_t off = 0;
+        while (off < want && rpos < R1) {
+            InflBlock b{};
+            if (!bgzf_header(h + off, want - off, &b.hlen, &b.csize, &b.isize)) {
+                if (want - off < 65536 + 8 && cpos + want < fsize) break;  // the block continues in the next piece
+                return fail(PG_E_FORMAT, "BGZF block at file offset %llu: bad header", (unsigned long long)(cpos + off));
+            }
+            // the walk against the .gzi: a block it lists must start at the raw offset it gives
+            while (gi < gzi.size() && gzi[gi].first < cpos + off) ++gi;
+            if (gi < gzi.size() && gzi[gi].first == cpos + off && gzi[gi].second != rpos)
+                return fail(PG_E_FORMAT, "BGZF block at file offset %llu: ISIZE mismatch (the .gzi places the next block at %llu)",
+                            (unsigned long long)(prev_coff == UINT64_MAX ? cpos + off : prev_coff), (unsigned long long)gzi[gi].second);
+            b.coff = off;
+            b.roff = rpos;
+            prev_coff = cpos + off;
+            rpos += b.isize;
+            off += b.csize;
+            if (rpos > R0) blocks.push_back(b);  // (blocks wholly before the range: walked, not inflated)
+        }
+        if (off == 0) return fail(PG_E_FORMAT, "BGZF block at file offset %llu: bad header", (unsigned long long)cpos);
+        rc = inflate_blocks(r->ctx, h, cpos, blocks, segs, dst);
+        cpos += off;
+    }
+    if (rc) return rc;
+    // the rows are there: readers of the result (pg_result_window_stats, ...) may go
+    if (int x = next_events(r, false)) return x;
+    HIP_TRY(hipEventRecord(r->ev[0], r->ctx->stream));
+    HIP_TRY(hipEventRecord(r->ev[1], r->ctx->stream));
+    r->ev_ok = true;
+    r->rows_valid = true;
+    return PG_OK;
     PG_API_END
 }

@@ -177,6 +177,20 @@ hipError_t launch_deflate_code(hipStream_t st, const uint8_t *base, const PaySeg
 hipError_t launch_row_deflate(hipStream_t st, const uint8_t *base, const PaySeg *segs, uint32_t nseg, uint64_t total,
                               uint64_t first_block, uint32_t nblocks, uint32_t row, const uint32_t *crc_tabs, const void *code,
                               uint8_t *slots, uint32_t *sizes, uint32_t force_stored, uint32_t *offs, uint8_t *packed);
+// GPU-side BGZF inflate (pg_inflate.hip): block i = bytes [coff, coff + csize) of the compressed buffer, its deflate data
+// behind an hlen-byte gzip header, isize payload bytes that belong at payload offset roff; segs map the payload to device
+// memory as above (bytes outside [segs[0].lstart, segs[nseg].lstart) are not written).  status[i] (zeroed by the caller)
+// receives an INF_E_* code when block i is malformed.
+struct InflBlock {
+    uint64_t coff, roff;
+    uint32_t hlen, csize, isize, pad;
+};
+enum : uint32_t {
+    INF_E_HEADER = 1, INF_E_TYPE, INF_E_STORED, INF_E_CODES, INF_E_SYMBOL, INF_E_DISTANCE, INF_E_OVERRUN, INF_E_INPUT,
+    INF_E_ISIZE, INF_E_CRC
+};
+hipError_t launch_bgzf_inflate(hipStream_t st, const uint32_t *comp, uint64_t comp_words, const InflBlock *blocks, uint32_t nblocks,
+                               const PaySeg *segs, uint32_t nseg, uint8_t *dst, const uint32_t *crc_tabs, uint32_t *status);
 hipError_t launch_window_stats(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint64_t nrows, uint32_t nwin,
                                uint32_t pieces, const uint64_t *starts, const uint64_t *ends, unsigned long long *hist,
                                unsigned long long *cs);

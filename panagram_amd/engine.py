@@ -828,6 +828,35 @@ class AnchorResult:
         check(self._lib.pg_result_write_bgzf_range(self._h, step, first_contig, n, os.fsencode(gz_path),
                                                    os.fsencode(gzi_path) if gzi_path else None, level, threads))
 
+    def inflate_bgzf(self, step: int, gz_path: str, gzi_path: Optional[str] = None, first_contig: int = 0,
+                     ncontigs: Optional[int] = None, file_row0: int = 0) -> None:
+        """Fill the rows of contigs [first_contig, first_contig + ncontigs) (default: all) from a bitmap.<step>.gz, inflated
+        on the GPU (k_bgzf_inflate); the result's contig 0 is row ``file_row0`` of the file's payload.  Afterwards
+        ``window_stats`` reads them.  A malformed block raises PanagramHipError (PG_E_FORMAT) naming its file offset."""
+        n = len(self.seqs.lens) - first_contig if ncontigs is None else ncontigs
+        check(self._lib.pg_result_inflate_bgzf(self._h, step, os.fsencode(gz_path), os.fsencode(gzi_path) if gzi_path else None,
+                                               first_contig, n, int(file_row0)))
+
+    @classmethod
+    def from_bgzf(cls, ctx: Context, k: int, ngenomes: int, nkmers: Sequence[int], gz_path: str,
+                  gzi_path: Optional[str] = None, file_row0: int = 0, step: int = 1) -> "AnchorResult":
+        """A rows container over contigs of ``nkmers`` rows each (contig lengths nkmers + k - 1; k - 1 for a contig without
+        rows) whose bitmap.<step> rows are read back from ``gz_path`` starting at payload row ``file_row0``."""
+        nk = np.asarray(nkmers, np.int64)
+        ss = SeqSet(ctx, np.where(nk > 0, nk + k - 1, k - 1).astype(np.uint64))
+        try:
+            r = cls.rows_container(ctx, k, ngenomes, ss, colsums=False)
+        except Exception:
+            ss.close()
+            raise
+        r._own_seqs = ss
+        try:
+            r.inflate_bgzf(step, gz_path, gzi_path, file_row0=file_row0)
+        except Exception:
+            r.close()
+            raise
+        return r
+
     def download(self, idx: int, want_bitmap1: bool = True, want_bitmap100: bool = True):
         info = self.contig_info(idx)
         nb = self.nbytes
@@ -864,12 +893,38 @@ class AnchorResult:
         if self._h:
             self._lib.pg_result_destroy(self._h)
             self._h = None
+        own = getattr(self, "_own_seqs", None)
+        if own is not None:
+            self._own_seqs = None
+            own.close()
 
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+def bgzf_inflate(ctx: Context, comp, coffs=None, roffs=None, out_bytes: Optional[int] = None) -> bytes:
+    """Whole BGZF blocks held in host memory inflated on the GPU (k_bgzf_inflate) and brought back: ``coffs`` / ``roffs``
+    (nblocks + 1 offsets each, ``roffs`` optional) place the blocks; without them the blocks are found from BSIZE / ISIZE.
+    A malformed block raises PanagramHipError (PG_E_FORMAT) naming its offset."""
+    buf = np.frombuffer(bytes(comp), np.uint8)
+    co = None if coffs is None else np.ascontiguousarray(coffs, np.uint64)
+    ro = None if roffs is None else np.ascontiguousarray(roffs, np.uint64)
+    nblocks = 0 if co is None else len(co) - 1
+    if out_bytes is None:  # (the footers' ISIZE, walked here only to size the buffer; the library walks and checks again)
+        out_bytes, off = 0, 0
+        while ro is None and off + 18 <= len(buf):
+            off += int(buf[off + 16]) + 256 * int(buf[off + 17]) + 1
+            out_bytes += int(buf[off - 4:off].view("<u4")[0]) if 4 <= off <= len(buf) else 0
+        out_bytes = int(ro[-1]) if ro is not None else out_bytes
+    import torch  # the payload lands in a torch tensor (the library and torch share one HIP runtime) and comes home by .cpu()
+    dev = torch.empty(max(16, out_bytes), dtype=torch.uint8, device=f"cuda:{ctx.device}")
+    raw = C.c_uint64()
+    check(ctx._lib.pg_bgzf_inflate(ctx._h, _ptr(buf), len(buf), nblocks, _ptr(co), _ptr(ro), C.c_void_p(dev.data_ptr()),
+                                   out_bytes, C.byref(raw)))
+    return dev[:raw.value].cpu().numpy().tobytes()
 
 
 class SmallOutputs:

@@ -21,8 +21,11 @@ Output tree (identical to the reference's):
 
     <prefix>/genome_dist.tsv       (opt-in: ``genome_dist=True`` / ``index --genome_dist`` / the ``dist`` command;
                                     MinHash sketches taken on the GPU in place of `mash sketch` + `mash triangle`)
+    <prefix>/anchor/<name>/gene.bed.gz(.csi) anno.bed.gz(.csi) anno_types.txt
+                                   (opt-in: ``annotate=True`` / ``index --annotate`` / the ``annotate`` command:
+                                    ``Genome.run_annotate``, index.py:971-1010; bitmap.1.gz inflated on the GPU)
 
-Out of scope here: GFF annotation, UMAPs, mash's own .msh files, the viewer.
+Out of scope here: UMAPs, mash's own .msh files, the viewer.
 """
 from __future__ import annotations
 
@@ -303,8 +306,11 @@ class Index:
     filtered_table: bool = dataclasses.field(default_factory=lambda: os.environ.get("PG_FULL_TABLE", "") in ("", "0"))
     # also write genome_dist.tsv (write_genome_dist): off by default, so that the default tree and config.yaml stay as they were
     genome_dist: bool = False
+    # run Genome.run_annotate() for every annotated anchor genome this process completes (off by default: the default tree
+    # stays as it was)
+    annotate: bool = False
 
-    _EXTRA = ("device", "export_kmc", "rank", "world", "shard", "genome_blocks", "filtered_table", "genome_dist")
+    _EXTRA = ("device", "export_kmc", "rank", "world", "shard", "genome_blocks", "filtered_table", "genome_dist", "annotate")
     # keys of config.yaml that describe one invocation, not the index: not taken over when a directory is re-opened
     # (`prepare` is written for schema compatibility, but a later `index <dir>` run must not stop at "Prepared")
     _NOT_IN_CONFIG = ("input", "mode", "prefix", "prepare")
@@ -330,6 +336,7 @@ class Index:
         self.timings: Dict[str, float] = {}  # seconds spent in load_inputs / build_table (host wall clock), for reports
         self._seqsets: Dict[str, engine.SeqSet] = {}
         self._minhash: Dict[str, Tuple[np.ndarray, int]] = {}  # name -> (MinHash sketch, ACGT bases): write_genome_dist
+        self._completed: List[str] = []  # anchor genomes whose files this process completed (Genome._write_tables)
 
     def _reopen_prepared(self):
         self.prefix = self.input
@@ -902,6 +909,11 @@ class Index:
         own_group = self._ensure_process_group()
         try:
             self._run_planned(ThreadPoolExecutor)
+            if self.annotate:  # (every mode: the process that completed a genome's files annotates it)
+                for name in list(self._completed):
+                    if self.genomes[name].annotated:
+                        self.genomes[name].run_annotate()
+                self.close()
             if self.genome_dist and self.rank == 0:  # (one writer in a multi-rank run)
                 self.write_genome_dist()
                 self.close()
@@ -1132,6 +1144,15 @@ class Index:
         N = self.ngenomes
         flat = np.bincount(inv * (N + 1) + pancnts.to_numpy().astype(np.int64), minlength=len(ub) * (N + 1))
         return pd.DataFrame(flat.reshape(len(ub), N + 1).T, index=self.bitsum_index, columns=ub)
+
+    def query_genes(self, genome, chrom=None, start=None, end=None) -> pd.DataFrame:
+        """the gene track's rows of ``genome`` overlapping the region (index.py:865-889): chr start end name, then the
+        gene's positions held by 1 genome and by all N"""
+        return self.genomes[genome].query_genes(chrom, start, end)
+
+    def query_anno(self, genome, chrom, start, end) -> pd.DataFrame:
+        """the annotation track's rows of ``genome`` overlapping the region (index.py:891-920), with ``type_id``"""
+        return self.genomes[genome].query_anno(chrom, start, end)
 
     def query_bitmap(self, genome, chrom, start=None, end=None, step=1):
         return self.genomes[genome].query(chrom, start, end, step)
@@ -1416,8 +1437,7 @@ class Genome:
             with open(self.bins_fname, "w") as f:
                 f.writelines(bins_rows)
         if gene_hists is not None:  # bitsum.genes.tsv: one row per annotated chromosome (index.py:1079-1082)
-            pd.DataFrame([h for _, h in gene_hists.values()], index=pd.Index(list(gene_hists), name="chr"),
-                         columns=range(N + 1)).to_csv(self.chr_genes_fname, sep="\t")
+            self._write_gene_sums(self.chr_genes_fname, gene_hists)
         # total_paircounts.csv (index.py:1068-1074): count[g] = positions holding genome g's bit
         counts = pd.Series(np.asarray(paircount_sums, dtype=np.int64), index=self.index.genome_names)
         pd.DataFrame({"count": counts, "frac": counts / counts[self.name]}).to_csv(
@@ -1426,6 +1446,144 @@ class Genome:
         self.set_chrs(chrs)
         self.write_benchmark()
         self.chrs.to_csv(self.chrs_fname, sep="\t")  # written last: it is the rule's completion marker
+        self.index._completed.append(self.name)
+
+    def _write_gene_sums(self, path: str, gene_hists) -> None:
+        pd.DataFrame([h for _, h in gene_hists.values()], index=pd.Index(list(gene_hists), name="chr"),
+                     columns=range(self.ngenomes + 1)).to_csv(path, sep="\t")
+
+    # ---- ANNOTATE: gene and annotation tracks of an anchored genome (index.py:615-651, 663-791, 971-1010) ----
+    def tabix_fname(self, typ: str) -> str:
+        return os.path.join(self.prefix, f"{typ}.bed.gz")
+
+    def tabix_idx_fname(self, typ: str) -> str:
+        return self.tabix_fname(typ) + ".csi"
+
+    @property
+    def anno_types_fname(self):
+        return os.path.join(self.prefix, "anno_types.txt")
+
+    annotate_budget = 8 << 30  # bitmap.1 payload bytes of one batch of chromosomes read back into HBM
+
+    def run_annotate(self, gff=None, nogene=False) -> None:
+        """Counterpart of ``Genome.run_annotate(gff_file, nogene=...)`` (index.py:971-1010): the GFF (default: the sample's
+        own) -> anno.bed.gz(.csi) and anno_types.txt, and unless ``nogene``, per-gene occupancy from bitmap.1.gz inflated on
+        the GPU -> gene.bed.gz(.csi), bitsum.genes.tsv and the ``gene_count`` column of chrs.tsv.  Every file is written to a
+        temporary and renamed."""
+        from . import annotation as an
+        gff = self.gff if gff is None else gff
+        if gff is None or (not isinstance(gff, str) and pd.isna(gff)):
+            raise ValueError(f"{self.name}: no GFF to annotate with")
+        idx = self.index
+        genes, annos, types = an.gff_records(gff, idx.gff_gene_types, idx.gff_anno_types, idx.gff_name)
+        an.write_track(self.tabix_fname("anno"), annos)
+        self._write_text(self.anno_types_fname, "".join(f"{t}\n" for t in types))
+        if nogene:
+            return
+        self.load_chrs()
+        N = self.ngenomes
+        occ = np.zeros((len(genes), N + 1), np.int64)  # each gene's own histogram (0 when skipped)
+        gene_hists = {}
+        grouped = {chrom: grp.index.to_numpy() for chrom, grp in genes.groupby("chr", sort=True)}
+        work = []  # (chrom, gene rows, starts, ends) of the genes inside their chromosome
+        for chrom, rows in grouped.items():
+            gene_hists[chrom] = (len(rows), np.zeros(N + 1, np.int64))
+            if chrom not in self.chrs.index:
+                self.log.warning(f"Skipping {len(rows)} gene(s) on {chrom}: chromosome not found")
+                logger.warning(f"{self.name}: skipping {len(rows)} gene(s) on {chrom}: chromosome not found")
+                continue
+            size = int(self.chrs.loc[chrom, "size"])
+            st, en = genes.loc[rows, "start"].to_numpy(np.int64), genes.loc[rows, "end"].to_numpy(np.int64)
+            ok = (en > st) & (st >= 0) & (en <= size)
+            for s_, e_ in zip(st[~ok], en[~ok]):
+                self.log.warning(f"Skipping gene at {chrom}:{s_}-{e_}, coordinates out-of-bounds")
+            if ok.any():
+                work.append((chrom, rows[ok], st[ok], en[ok]))
+        for batch in self._annotate_batches([w[0] for w in work]):
+            res = self._rows_from_disk(batch)
+            try:
+                for ci, chrom in enumerate(batch):
+                    _, rows, st, en = next(w for w in work if w[0] == chrom)
+                    h, _ = res.window_stats(ci, st, en, step=1, colsums=False)
+                    occ[rows] = h.astype(np.int64)
+                    gene_hists[chrom] = (gene_hists[chrom][0], occ[rows].sum(axis=0))
+                    self.log.info(f"Annotated {chrom}")
+            finally:
+                res.close()
+        an_genes = an.gene_track(genes, occ[:, 1], occ[:, N], N)
+        an.write_track(self.tabix_fname("gene"), an_genes)
+        self._write_gene_sums(self.chr_genes_fname + ".tmp", gene_hists)
+        os.replace(self.chr_genes_fname + ".tmp", self.chr_genes_fname)
+        counts = pd.Series({c: n for c, (n, _) in gene_hists.items()}, dtype=np.int64)
+        self.chrs["gene_count"] = counts.reindex(self.chrs.index, fill_value=0).astype(np.int64).to_numpy()
+        self.chrs.to_csv(self.chrs_fname + ".tmp", sep="\t")
+        os.replace(self.chrs_fname + ".tmp", self.chrs_fname)
+
+    @staticmethod
+    def _write_text(path: str, text: str) -> None:
+        with open(path + ".tmp", "w") as f:
+            f.write(text)
+        os.replace(path + ".tmp", path)
+
+    def _annotate_batches(self, chroms: List[str]) -> List[List[str]]:
+        """runs of chromosomes that are neighbours in the file, each run's rows within annotate_budget (a longer
+        chromosome is a run of its own)"""
+        order = {c: i for i, c in enumerate(self.chrs.index)}
+        chroms = sorted(chroms, key=order.get)
+        nb = self.nbytes
+        out, cur, cur_bytes = [], [], 0
+        for c in chroms:
+            b = int(self.chrs.loc[c, "size"]) * nb
+            if cur and (order[c] != order[cur[-1]] + 1 or cur_bytes + b > self.annotate_budget):
+                out.append(cur)
+                cur, cur_bytes = [], 0
+            cur.append(c)
+            cur_bytes += b
+        if cur:
+            out.append(cur)
+        return out
+
+    def _rows_from_disk(self, chroms: List[str]) -> "engine.AnchorResult":
+        """a rows result over consecutive chromosomes of chrs.tsv, filled from bitmap.1.gz on the GPU"""
+        sizes = [int(self.chrs.loc[c, "size"]) for c in chroms]
+        row0 = int(self.chrs["size"].cumsum().shift(fill_value=0).loc[chroms[0]])
+        return engine.AnchorResult.from_bgzf(self.index.context, int(self.index.k), self.ngenomes, sizes, self.bitmap_gz_fname(1),
+                                             self.bitmap_gzi_fname(1), file_row0=row0)
+
+    def _tabix(self, typ: str):
+        from . import annotation as an
+        cache = self.__dict__.setdefault("_tabix_cache", {})
+        if typ not in cache:
+            path = self.tabix_fname(typ)
+            cache[typ] = an.TabixTrack(path) if os.path.exists(path) else None
+        return cache[typ]
+
+    def query_genes(self, chrom=None, start=None, end=None) -> pd.DataFrame:
+        from . import annotation as an
+        cols = an.GENE_COLS + [1, self.ngenomes]
+        tbx = self._tabix("gene")
+        rows = tbx.fetch(chrom, start, end) if tbx is not None else []
+        types = {"start": int, "end": int, 1: int, self.ngenomes: int}
+        return pd.DataFrame(rows, columns=cols).astype(types)
+
+    def query_anno(self, chrom, start, end) -> pd.DataFrame:
+        from . import annotation as an
+        tbx = self._tabix("anno")
+        if tbx is None:
+            return pd.DataFrame(columns=an.TABIX_COLS)
+        df = pd.DataFrame(tbx.fetch(chrom, start, end), columns=an.TABIX_COLS).astype(an.TABIX_TYPES)
+        df["type_id"] = self.anno_type_ids[df["type"]].to_numpy()
+        return df
+
+    @property
+    def anno_type_ids(self) -> pd.Series:
+        """type -> id as the viewer numbers them (index.py:705-727): ``exon`` first (id 0) when present, else from 1"""
+        with open(self.anno_types_fname) as f:
+            types = [t.strip() for t in f if t.strip()]
+        if "exon" in types:
+            types = ["exon"] + [t for t in types if t != "exon"]
+        id0 = 0 if "exon" in types else 1
+        return pd.Series({t: id0 + i for i, t in enumerate(types)}, dtype=np.int64)
 
     def run_anchor(self, table: engine.PanTable, logfile: Optional[str] = None, bgzf_threads: Optional[int] = None):
         """Counterpart of ``Genome.run_anchor(bitvecs, logfile)`` (index.py:1012-1097) and of

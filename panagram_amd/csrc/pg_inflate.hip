@@ -15,8 +15,8 @@
 //   - the finished bytes go out through the caller's segment map (PaySeg: payload offset -> device offset), so that a
 //     block that straddles two contigs of a padded row buffer lands in both; bytes outside the map are dropped
 // Every input byte is untrusted: reads stay inside the block's deflate bytes (the word loads are clamped to the buffer and
-// the consumed bit count is checked after every symbol), writes inside ISIZE; a malformed block sets its status word
-// (INF_E_*) and its workgroup stops.
+// the consumed bit count is checked before anything read is acted on: a stream cut short fails as INF_E_INPUT, whatever
+// the bits behind it say), writes inside ISIZE; a malformed block sets its status word (INF_E_*) and its workgroup stops.
 #include "pg_kernels.h"
 
 namespace pg {
@@ -202,6 +202,10 @@ __global__ __launch_bounds__(INF_THREADS) void k_bgzf_inflate(const uint32_t *__
         in.refill();
         last = in.bits(1);
         const uint32_t type = in.bits(2);
+        if (in.over()) {  // (a block header behind the data: the stream was cut short)
+            fail(INF_E_INPUT);
+            return;
+        }
         if (type == 0) {  // stored: to the byte boundary, LEN, NLEN, the bytes
             in.drop((8u - (uint32_t)(in.used & 7u)) & 7u);
             in.refill();
@@ -255,6 +259,10 @@ __global__ __launch_bounds__(INF_THREADS) void k_bgzf_inflate(const uint32_t *__
             nlen = (int)in.bits(5) + 257;
             ndist = (int)in.bits(5) + 1;
             const int ncl = (int)in.bits(4) + 4;
+            if (in.over()) {
+                fail(INF_E_INPUT);
+                return;
+            }
             if (nlen > 286 || ndist > 30) {
                 fail(INF_E_CODES);
                 return;
@@ -268,6 +276,10 @@ __global__ __launch_bounds__(INF_THREADS) void k_bgzf_inflate(const uint32_t *__
                 if (lane == 0) cl[INF_CL_ORDER[i]] = (uint8_t)v;
             }
             __syncthreads();
+            if (in.over()) {
+                fail(INF_E_INPUT);
+                return;
+            }
             Code CL{ll_cnt, ll_sym, ll_lut, 7};
             if (build_code(cl, 19, CL) != 0) {  // the code-length code must be complete
                 fail(INF_E_CODES);
@@ -299,6 +311,10 @@ __global__ __launch_bounds__(INF_THREADS) void k_bgzf_inflate(const uint32_t *__
                     rep = 3 + in.bits(3);
                 } else {
                     rep = 11 + in.bits(7);
+                }
+                if (in.over()) {
+                    fail(INF_E_INPUT);
+                    return;
                 }
                 if (i + (int)rep > nlen + ndist) {
                     fail(INF_E_CODES);
@@ -342,6 +358,10 @@ __global__ __launch_bounds__(INF_THREADS) void k_bgzf_inflate(const uint32_t *__
                 return;
             }
             if (s < 256) {
+                if (in.over()) {
+                    fail(INF_E_INPUT);
+                    return;
+                }
                 if (pos >= isize) {
                     fail(INF_E_OVERRUN);
                     return;
@@ -353,17 +373,21 @@ __global__ __launch_bounds__(INF_THREADS) void k_bgzf_inflate(const uint32_t *__
             } else {
                 const int ls = s - 257;
                 if (ls >= 29) {
-                    fail(INF_E_SYMBOL);
+                    fail(in.over() ? INF_E_INPUT : INF_E_SYMBOL);
                     return;
                 }
                 const uint32_t len = INF_LEN_BASE[ls] + in.bits(INF_LEN_EXTRA[ls]);
                 in.refill();
                 const int ds = decode(in, D);
                 if (ds < 0 || ds >= 30) {
-                    fail(INF_E_SYMBOL);
+                    fail(in.over() ? INF_E_INPUT : INF_E_SYMBOL);
                     return;
                 }
                 const uint32_t dist = INF_DIST_BASE[ds] + in.bits(INF_DIST_EXTRA[ds]);
+                if (in.over()) {
+                    fail(INF_E_INPUT);
+                    return;
+                }
                 if (dist > pos) {
                     fail(INF_E_DISTANCE);
                     return;
@@ -384,10 +408,6 @@ __global__ __launch_bounds__(INF_THREADS) void k_bgzf_inflate(const uint32_t *__
                     for (uint32_t j = lane; j < len; j += INF_THREADS) out[pos + j] = out[src + j % dist];
                 }
                 pos += len;
-            }
-            if (in.over()) {
-                fail(INF_E_INPUT);
-                return;
             }
         }
         if (in.over()) {

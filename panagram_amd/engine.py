@@ -905,6 +905,35 @@ class AnchorResult:
             pass
 
 
+def _bgzf_bsize(buf: np.ndarray, off: int) -> Optional[int]:
+    """BSIZE of the BGZF block at ``off``: the BC subfield found among the gzip extra subfields (any number, any order,
+    as the library's header walk reads them); None when there is none"""
+    xlen = int(buf[off + 10]) | int(buf[off + 11]) << 8
+    end = off + 12 + xlen
+    if end > len(buf):
+        return None
+    i, bsize = off + 12, None
+    while i + 4 <= end:
+        slen = int(buf[i + 2]) | int(buf[i + 3]) << 8
+        if buf[i] == ord("B") and buf[i + 1] == ord("C") and slen == 2 and i + 6 <= end:
+            bsize = int(buf[i + 4]) | int(buf[i + 5]) << 8
+        i += 4 + slen
+    return bsize
+
+
+def _bgzf_payload_bytes(buf: np.ndarray) -> int:
+    """the ISIZEs of the BGZF blocks in ``buf`` summed, walking BSIZE from the first block; the walk stops at a block without
+    a BC subfield"""
+    total, off = 0, 0
+    while off + 18 <= len(buf):
+        bsize = _bgzf_bsize(buf, off)
+        if bsize is None:  # (the library names the bad header)
+            break
+        off += bsize + 1
+        total += int(buf[off - 4:off].view("<u4")[0]) if 4 <= off <= len(buf) else 0
+    return total
+
+
 def bgzf_inflate(ctx: Context, comp, coffs=None, roffs=None, out_bytes: Optional[int] = None) -> bytes:
     """Whole BGZF blocks held in host memory inflated on the GPU (k_bgzf_inflate) and brought back: ``coffs`` / ``roffs``
     (nblocks + 1 offsets each, ``roffs`` optional) place the blocks; without them the blocks are found from BSIZE / ISIZE.
@@ -914,11 +943,7 @@ def bgzf_inflate(ctx: Context, comp, coffs=None, roffs=None, out_bytes: Optional
     ro = None if roffs is None else np.ascontiguousarray(roffs, np.uint64)
     nblocks = 0 if co is None else len(co) - 1
     if out_bytes is None:  # (the footers' ISIZE, walked here only to size the buffer; the library walks and checks again)
-        out_bytes, off = 0, 0
-        while ro is None and off + 18 <= len(buf):
-            off += int(buf[off + 16]) + 256 * int(buf[off + 17]) + 1
-            out_bytes += int(buf[off - 4:off].view("<u4")[0]) if 4 <= off <= len(buf) else 0
-        out_bytes = int(ro[-1]) if ro is not None else out_bytes
+        out_bytes = int(ro[-1]) if ro is not None else _bgzf_payload_bytes(buf)
     import torch  # the payload lands in a torch tensor (the library and torch share one HIP runtime) and comes home by .cpu()
     dev = torch.empty(max(16, out_bytes), dtype=torch.uint8, device=f"cuda:{ctx.device}")
     raw = C.c_uint64()

@@ -7,8 +7,13 @@ pan-kmer table and its presence row / 1-in-100 row / bin histogram / column sums
 (device-resident inputs and outputs; BASELINE.json configs[1]: 8 synthetic 100 Mb
 genomes, k=21, one GPU, all tables resident).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline needs and no more: it builds the pangenome and its table, warms up, times the K steps,
+writes --dump-outputs if asked and prints the line.  --full also runs every further leg, all outside the timed region:
+the one-launch-per-genome comparison, the CPU baseline, files -> files through Index.run(), the genome-sharded pipeline,
+the robustness inputs, the north-star / wide / BASELINE configs[2..4] shapes (each of those legs with a --no-* switch).
 
 Multi-GPU (one process per GPU):
   --mode contig-sharded (default)  the path shards by anchor contig with a replicated table and NO data-path
@@ -18,8 +23,8 @@ Multi-GPU (one process per GPU):
   --mode genome-sharded            the table is cut into genome blocks, rank r holds block r; every rank probes every
         anchor position; the blocks' bit columns are all-gathered over RCCL/xGMI and merged on the anchor's writer
         (panagram_amd.distributed.ShardedAnchoring — the product's pipeline), all inside the timed region.
-  With N > 1 the default mode also times the genome-sharded pipeline once, untimed-region-outside, and reports it
-  as config.genome_sharded_leg (collective bytes included).
+  With N > 1 and --full the default mode also times the genome-sharded pipeline once, untimed-region-outside, and reports
+  it as config.genome_sharded_leg (collective bytes included).
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -1229,6 +1234,72 @@ def spawn_ranks(n):
     return subprocess.call(cmd, env=env)
 
 
+def further_legs(ctx, dev, args, out, rank, world, dist, default_shape, e2e_first):
+    """--full: every leg besides the headline, outside the timed region of `value`; their results go into ``out``
+    (the line main() prints).  Each leg catches its own failure, so that the measured line stands whatever happens here."""
+    # (the line so far goes to stderr first: should a further leg die, the measured value is still on record; stdout
+    # carries the ONE complete line at the end)
+    if rank == 0:
+        print("[bench] timed region done, before the further legs: " + json.dumps(out), file=sys.stderr, flush=True)
+    # With more than one rank the further leg has a collective in it, and a rank that dies or stalls there would leave
+    # the others waiting inside RCCL for ever — and the measured line unprinted.  A watchdog per rank: if the leg has not
+    # come back after LEG_TIMEOUT_S, rank 0 prints the line as it stands (the leg marked as timed out) and every rank
+    # leaves with exit code 0.
+    watchdog = None
+    if world > 1:
+        def give_up():
+            if rank == 0:
+                out["config"].setdefault("genome_sharded_leg", {"error": f"no result after {LEG_TIMEOUT_S} s (watchdog): the measured line stands"})
+                print(json.dumps(out), flush=True)
+            print(f"[bench] rank {rank}: further leg timed out, leaving", file=sys.stderr, flush=True)
+            os._exit(0)
+        watchdog = threading.Timer(LEG_TIMEOUT_S, give_up)
+        watchdog.daemon = True
+        watchdog.start()
+    if not args.no_sharded_leg and (world > 1 or default_shape):
+        # the one mode with a data-path collective (BASELINE.json configs[4]); with one rank: the pipeline's own cost
+        try:
+            out["config"]["genome_sharded_leg"] = sharded_leg(ctx, dev, args, rank, world, dist, 3, 1, args.blocks)
+        except Exception as e:  # a failed extra leg must not take the measured line with it
+            out["config"]["genome_sharded_leg"] = {"error": f"{type(e).__name__}: {e}"}
+    if e2e_first is not None:
+        out["e2e"] = e2e_first
+    if world == 1 and default_shape and not args.no_robustness:
+        try:
+            out["robustness"] = robustness_legs(ctx, dev, args, args.k)
+            out["robustness"]["per_genome_launches_value_on_the_headline_workload"] = out["config"].get("per_genome_launches_value")
+        except Exception as e:
+            out["robustness"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and default_shape and not args.no_other_shapes:
+        try:
+            out["config"]["other_shapes"] = [north_star_leg(ctx, dev, args)]
+        except Exception as e:
+            out["config"]["other_shapes"] = [{"error": f"{type(e).__name__}: {e}"}]
+    if world == 1 and default_shape and not args.no_other_shapes:
+        try:
+            out["config"]["wide_shapes"] = wide_legs(ctx, dev, args)
+        except Exception as e:
+            out["config"]["wide_shapes"] = [{"error": f"{type(e).__name__}: {e}"}]
+    if world == 1 and default_shape and not args.no_other_shapes and not args.no_baseline_configs:
+        try:
+            out["config"]["baseline_configs"], out["e2e_config4"] = baseline_config_legs(ctx, dev, args)
+        except Exception as e:
+            out["config"]["baseline_configs"] = [{"error": f"{type(e).__name__}: {e}"}]
+    if world == 1 and default_shape and not args.no_config5:
+        try:
+            out["config"]["config5_leg"] = config5_leg(ctx, dev, args)
+        except Exception as e:
+            out["config"]["config5_leg"] = {"error": f"{type(e).__name__}: {e}"}
+        ctx.trim()
+        torch.cuda.empty_cache()
+        try:  # what Index.plan_sharding chooses on one GPU since round 6: two genomes per block in a denser table, half the passes
+            out["config"]["config5_leg_two_genome_blocks"] = config5_leg(ctx, dev, args, per=2, keys_per_line="auto")
+        except Exception as e:
+            out["config"]["config5_leg_two_genome_blocks"] = {"error": f"{type(e).__name__}: {e}"}
+    if watchdog is not None:
+        watchdog.cancel()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1259,6 +1330,9 @@ def main():
     ap.add_argument("--per-genome-launches", action="store_true",
                     help="one launch per anchor genome instead of one co-scheduled launch over all of them")
     ap.add_argument("--piece-tiles", type=int, default=0, help="co-scheduling granularity in tiles of 1024 positions (0: library default, 64 down to 8 by genome count)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every further leg the --no-* switches below name (off: the line carries the "
+                         "headline and what its timed steps measured, nothing that takes runs of its own)")
     ap.add_argument("--no-compare", action="store_true", help="skip the untimed one-launch-per-genome comparison run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-shapes", action="store_true", help="skip the north-star-shape leg (64 x 200 Mb, k=21)")
@@ -1355,7 +1429,7 @@ def main():
     # shape in a process that has not yet freed tens of GB — hipFree's cost is paid inside the NEXT large hipMalloc on this stack
     # (40 ms per GB), and behind the legs below it landed in this leg's table build (1.5-1.9 s instead of 0.02)
     e2e_first = None
-    if world == 1 and (default_shape or os.environ.get("PG_BENCH_E2E_ANY")) and not args.no_e2e:  # (PG_BENCH_E2E_ANY: experiments on other shapes)
+    if args.full and world == 1 and (default_shape or os.environ.get("PG_BENCH_E2E_ANY")) and not args.no_e2e:  # (PG_BENCH_E2E_ANY: experiments on other shapes)
         try:
             e2e_first = e2e_leg(dev, args, G, contig_lens, k)
         except Exception as e:
@@ -1364,6 +1438,8 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- k-mer set construction on the GPU (replaces kmc + kmc_tools; timed separately) ----
+    # (the ASCII copy is for the CPU baseline of --full; a plain run keeps it as well, because the table's density is chosen with
+    # it in HBM: without --full the timed steps run against the very table a --full run measures)
     keep_ascii = rank == 0 and world == 1 and not args.no_cpu_baseline
     strong = args.scaling == "strong" and (world > 1 or bool(args.emulate_rank))
     if strong:
@@ -1493,7 +1569,7 @@ def main():
                                    bound="hbm" if args.per_genome_launches else "issue"),
     }
 
-    if world == 1 and not args.per_genome_launches and not args.no_compare:
+    if args.full and world == 1 and not args.per_genome_launches and not args.no_compare:
         # for comparison only (outside the timed region): the same work as one launch per genome — what a single-anchor
         # Index.run(), the run_anchor CLI with one FASTA or unrelated sequences get — against the table the product builds
         # for THAT mode (PanTable(coscheduled=1): how a table will be probed decides its minimizer window)
@@ -1539,7 +1615,7 @@ def main():
         if pg1 is not pg:
             pg1.table.close()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         nthreads = min(G, engine.usable_cpus())
         sample = int(args.cpu_sample_mb * 1e6)
         cache = {}
@@ -1569,68 +1645,8 @@ def main():
     pg.close()
     ctx.trim()
 
-    # ---- further legs, outside the timed region of `value` ----
-    # (the line so far goes to stderr first: should a further leg die, the measured value is still on record; stdout
-    # carries the ONE complete line at the end)
-    if rank == 0:
-        print("[bench] timed region done, before the further legs: " + json.dumps(out), file=sys.stderr, flush=True)
-    # With more than one rank the further leg has a collective in it, and a rank that dies or stalls there would leave
-    # the others waiting inside RCCL for ever — and the measured line unprinted.  A watchdog per rank: if the leg has not
-    # come back after LEG_TIMEOUT_S, rank 0 prints the line as it stands (the leg marked as timed out) and every rank
-    # leaves with exit code 0.
-    watchdog = None
-    if world > 1:
-        def give_up():
-            if rank == 0:
-                out["config"].setdefault("genome_sharded_leg", {"error": f"no result after {LEG_TIMEOUT_S} s (watchdog): the measured line stands"})
-                print(json.dumps(out), flush=True)
-            print(f"[bench] rank {rank}: further leg timed out, leaving", file=sys.stderr, flush=True)
-            os._exit(0)
-        watchdog = threading.Timer(LEG_TIMEOUT_S, give_up)
-        watchdog.daemon = True
-        watchdog.start()
-    if not args.no_sharded_leg and (world > 1 or default_shape):
-        # the one mode with a data-path collective (BASELINE.json configs[4]); with one rank: the pipeline's own cost
-        try:
-            out["config"]["genome_sharded_leg"] = sharded_leg(ctx, dev, args, rank, world, dist, 3, 1, args.blocks)
-        except Exception as e:  # a failed extra leg must not take the measured line with it
-            out["config"]["genome_sharded_leg"] = {"error": f"{type(e).__name__}: {e}"}
-    if e2e_first is not None:
-        out["e2e"] = e2e_first
-    if world == 1 and default_shape and not args.no_robustness:
-        try:
-            out["robustness"] = robustness_legs(ctx, dev, args, k)
-            out["robustness"]["per_genome_launches_value_on_the_headline_workload"] = out["config"].get("per_genome_launches_value")
-        except Exception as e:
-            out["robustness"] = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and default_shape and not args.no_other_shapes:
-        try:
-            out["config"]["other_shapes"] = [north_star_leg(ctx, dev, args)]
-        except Exception as e:
-            out["config"]["other_shapes"] = [{"error": f"{type(e).__name__}: {e}"}]
-    if world == 1 and default_shape and not args.no_other_shapes:
-        try:
-            out["config"]["wide_shapes"] = wide_legs(ctx, dev, args)
-        except Exception as e:
-            out["config"]["wide_shapes"] = [{"error": f"{type(e).__name__}: {e}"}]
-    if world == 1 and default_shape and not args.no_other_shapes and not args.no_baseline_configs:
-        try:
-            out["config"]["baseline_configs"], out["e2e_config4"] = baseline_config_legs(ctx, dev, args)
-        except Exception as e:
-            out["config"]["baseline_configs"] = [{"error": f"{type(e).__name__}: {e}"}]
-    if world == 1 and default_shape and not args.no_config5:
-        try:
-            out["config"]["config5_leg"] = config5_leg(ctx, dev, args)
-        except Exception as e:
-            out["config"]["config5_leg"] = {"error": f"{type(e).__name__}: {e}"}
-        ctx.trim()
-        torch.cuda.empty_cache()
-        try:  # what Index.plan_sharding chooses on one GPU since round 6: two genomes per block in a denser table, half the passes
-            out["config"]["config5_leg_two_genome_blocks"] = config5_leg(ctx, dev, args, per=2, keys_per_line="auto")
-        except Exception as e:
-            out["config"]["config5_leg_two_genome_blocks"] = {"error": f"{type(e).__name__}: {e}"}
-    if watchdog is not None:
-        watchdog.cancel()
+    if args.full:
+        further_legs(ctx, dev, args, out, rank, world, dist, default_shape, e2e_first)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -2,7 +2,7 @@
 # the files-to-files leg (Index.run()) by genome count: seconds, and the anchor + write part as GB of rows per second
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 for A in "--genomes 8 --genome-mb 40" "--genomes 12 --genome-mb 40" "--genomes 20 --genome-mb 40" "--genomes 27 --genome-mb 40" "--genomes 40 --genome-mb 40" "--genomes 56 --genome-mb 40" "--genomes 64 --genome-mb 40" "--genomes 72 --genome-mb 20" "--genomes 100 --genome-mb 20" "--genomes 128 --genome-mb 20"; do
-  PG_BENCH_E2E_ANY=1 timeout 900 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-compare --no-other-shapes --no-sharded-leg --no-robustness $A 2>gpurun_out/ab.err | python -c "
+  PG_BENCH_E2E_ANY=1 timeout 900 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-compare --no-other-shapes --no-sharded-leg --no-robustness $A 2>"${TMPDIR:-/tmp}/ab.err" | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); e=d['e2e']; nb=d['config']['nbytes']
 rows=e['positions']*nb

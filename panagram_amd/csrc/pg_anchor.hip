@@ -2149,6 +2149,18 @@ __device__ __forceinline__ void hist_position(bool active, uint32_t pos, uint32_
     }
 }
 
+// Every lane adds its own value to the LDS counter p (one ds_add per lane).  With an address the compiler sees as uniform,
+// its atomic optimizer sums the lanes first in a SCALAR loop over the active lanes (s_ff1 / v_readlane / s_add ..., seven
+// scalar instructions per lane and a dependent chain through all 64): k_epilogue<0,1>'s end-of-bin and end-of-range
+// reductions (9 + 8 counters) came to most of the pass's SQ_INSTS_SALU, and their chains were most of its fixed cost
+// (profiles/r7_stats_fixed_cost.md).  The zero comes out of inline assembly, so that the address stays per lane; the LDS
+// works the same-address lanes off one after the other, about 64 cycles per instruction.
+__device__ __forceinline__ void lds_add_lanes(uint32_t *p, uint32_t v) {
+    uint32_t z;
+    asm("v_mov_b32 %0, 0" : "=v"(z));
+    atomicAdd(p + z, v);
+}
+
 // four consecutive rows of NB bytes = NB aligned 32-bit words (a thread's first row starts at a
 // multiple of 4 rows): load the words (all in flight together), cut the rows out with static shifts
 template <int NB>
@@ -2471,7 +2483,7 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
         for (int v = 0; v < 8; ++v) thr[v] = 0;
 #pragma unroll
         for (int v = 0; v < 9; ++v)
-            if ((uint32_t)v <= N && hc[v]) atomicAdd(&hist[v], hc[v]);
+            if ((uint32_t)v <= N && hc[v]) lds_add_lanes(&hist[v], hc[v]);
     };
 
     // column sums are kept per contig (colsums[contig][N]): register / LDS accumulators are emptied
@@ -2480,7 +2492,7 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
         if constexpr (MODE == 0) {
 #pragma unroll
             for (int gb = 0; gb < 8; ++gb) {
-                if ((uint32_t)gb < N && cacc[gb]) atomicAdd(&cs[gb], cacc[gb]);
+                if ((uint32_t)gb < N && cacc[gb]) lds_add_lanes(&cs[gb], cacc[gb]);
                 cacc[gb] = 0;
             }
         }

@@ -373,6 +373,15 @@ int pg_result_contig_info(const pg_result *r, uint32_t idx, uint64_t *nkmers, ui
  * (index.py:1169-1183) and bitmap_to_bins / paircount bins (index.py:438-449).  Synchronises. */
 int pg_result_window_stats(pg_result *r, uint32_t idx, int step, uint32_t nwin, const uint64_t *starts,
                            const uint64_t *ends, uint64_t *hist, uint64_t *colsums);
+/* masked per-bin column sums of the introgression caller's binning step (call_introgressions.py: bitmap_to_bins):
+ * bin i = SAMPLED rows [starts[i], ends[i]) of contig contig[i]'s bitmap.<step> rows in HBM, sampled row j being row
+ * j * stride.  Per row: if none of the keep_words bits is set (ceil(ngenomes / 32) words, bits past ngenomes ignored; NULL:
+ * no mask), they are ORed in (--rmu); then with omit_fixed a row whose ngenomes bits are all set is dropped (--rmf).
+ * cs_out[i*ngenomes + g] = rows left holding genome g's bit, kept_out[i] = rows left.  Every sampled row must lie inside
+ * its contig.  One launch for all bins (k_bin_colsums); synchronises. */
+int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, uint32_t nbins, const uint32_t *contig,
+                          const uint64_t *starts, const uint64_t *ends, const uint32_t *keep_words, int omit_fixed,
+                          uint64_t *cs_out, uint64_t *kept_out);
 /* stream the whole bitmap.1 (step 1) or bitmap.100 (step 100) payload of the result — every
  * contig, in order — from HBM into a BGZF file + .gzi index (gzi_path may be NULL): D2H through
  * pinned double buffers on a private stream overlapped with multi-threaded deflate.  Replaces

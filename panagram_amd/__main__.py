@@ -7,6 +7,10 @@ import sys
 
 
 def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    if argv and argv[0] == "intros":  # (its own two forms: `intros call ...` and `intros <config.yaml>`)
+        from . import introgressions
+        return introgressions.main(argv[1:])
     ap = argparse.ArgumentParser(prog="panagram_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
     ix = sub.add_parser("index", help="Anchor k-mer bitvectors to reference FASTA files to create pan-kmer bitmap")
@@ -31,6 +35,9 @@ def main(argv=None):
     an.add_argument("gff_file")
     an.add_argument("--nogene", action="store_true")
     an.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    it = sub.add_parser("intros", help="call introgressions from k-mer similarity binned on the GPU: `intros call [flags]` "
+                                       "(call_introgressions.py's flags) or `intros <config.yaml> [--sweep]`", add_help=False)
+    it.add_argument("args", nargs=argparse.REMAINDER)
     ra = sub.add_parser("run_anchor", help="argv-compatible with the reference's cpp/run_anchor")
     ra.add_argument("args", nargs="+")
     ra.add_argument("--device", type=int, default=0)

@@ -3322,6 +3322,77 @@ extern "C" int pg_result_window_stats(pg_result *r, uint32_t idx, int step, uint
     PG_API_END
 }
 
+// masked per-bin column sums over sampled rows (call_introgressions.py: bitmap_to_bins): one launch for bins of any of
+// the result's contigs
+extern "C" int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, uint32_t nbins, const uint32_t *contig,
+                                     const uint64_t *starts, const uint64_t *ends, const uint32_t *keep_words, int omit_fixed,
+                                     uint64_t *cs_out, uint64_t *kept_out) {
+    PG_API_BEGIN
+    if (!r || (nbins && (!contig || !starts || !ends || !cs_out || !kept_out)))
+        return fail(PG_E_INVALID, "pg_result_bin_colsums: NULL argument");
+    if (step != 1 && step != 100 && (uint32_t)step != r->lowres_step)
+        return fail(PG_E_INVALID, "step must be 1 or the result's low-resolution step (%u; 100 is accepted as its alias)", r->lowres_step);
+    if (stride < 1) return fail(PG_E_INVALID, "pg_result_bin_colsums: stride must be >= 1");
+    if (nbins > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_bin_colsums: %u bins (at most 2^31 - 1 per call)", nbins);
+    const uint32_t N = r->N;
+    if (N < 1 || N > 4096) return fail(PG_E_INVALID, "pg_result_bin_colsums: %u genomes (1 to 4096)", N);
+    if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
+    if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
+    if (step != 1 && (r->flags & PG_ANCHOR_ROWS_ONLY) && !r->ev_epi && !r->rows_valid)
+        return fail(PG_E_INVALID, "rows-only result: the low-resolution rows need pg_rows_epilogue first");
+    const uint32_t ndw = (N + 31) / 32;
+    // bin i: device byte offset of its contig's rows, then [start, end) in sampled rows
+    std::vector<uint64_t> se((size_t)nbins * 3);
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < nbins; ++i) {
+        if (contig[i] >= r->ad.size()) return fail(PG_E_INVALID, "bin %u: contig %u out of range", i, contig[i]);
+        const AnchorDesc &a = r->ad[contig[i]];
+        const uint64_t nrows = step == 1 ? (uint64_t)a.nkmers : r->nrows100[contig[i]];
+        if (starts[i] > ends[i]) return fail(PG_E_INVALID, "bin %u: start %llu past end %llu", i, (unsigned long long)starts[i],
+                                             (unsigned long long)ends[i]);
+        if (ends[i] > starts[i] && (nrows == 0 || ends[i] - 1 > (nrows - 1) / stride))
+            return fail(PG_E_INVALID, "bin %u: sampled row %llu (x %u) past the %llu rows of contig %u", i,
+                        (unsigned long long)(ends[i] - 1), stride, (unsigned long long)nrows, contig[i]);
+        se[i] = step == 1 ? a.out_off : a.out100_off;
+        se[nbins + i] = starts[i];
+        se[2 * (size_t)nbins + i] = ends[i];
+        longest = std::max(longest, ends[i] - starts[i]);
+    }
+    std::vector<uint32_t> kw(ndw, 0);
+    if (keep_words)
+        for (uint32_t d = 0; d < ndw; ++d) kw[d] = keep_words[d] & (N - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (N - 32 * d)) - 1u);
+    if (nbins == 0) return PG_OK;
+    if (int e = use_device(r->ctx)) return e;
+    if (int e = join_result(r)) return e;
+    hipStream_t st = r->ctx->stream;
+    // pieces: about 32 K sampled rows each for the longest bin, and enough blocks to fill the device
+    uint32_t pieces = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, longest / 32768));
+    while (pieces < 256 && (uint64_t)nbins * pieces < 4096 && (uint64_t)pieces * 4096 < longest) pieces *= 2;
+    uint64_t *d_se = nullptr;
+    uint32_t *d_kw = nullptr;
+    unsigned long long *d_out = nullptr;
+    const size_t nc = (size_t)nbins * N;
+    int rc = PG_OK;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_se), se.size() * 8);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_kw), (size_t)ndw * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), (nc + nbins) * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se, se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_kw, kw.data(), (size_t)ndw * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (nc + nbins) * 8, st);
+    if (e == hipSuccess)
+        e = launch_bin_colsums(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nbins, pieces, d_se, d_se + nbins,
+                               d_se + 2 * (size_t)nbins, d_kw, omit_fixed ? 1u : 0u, d_out, d_out + nc);
+    if (e == hipSuccess) e = hipMemcpyAsync(cs_out, d_out, nc * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(kept_out, d_out + nc, (size_t)nbins * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_result_bin_colsums: %s", hipGetErrorString(e));
+    if (d_se) hipFree(d_se);
+    if (d_kw) hipFree(d_kw);
+    if (d_out) hipFree(d_out);
+    return rc;
+    PG_API_END
+}
+
 extern "C" int pg_result_contig_info(const pg_result *r, uint32_t idx, uint64_t *nkmers, uint64_t *nrows100,
                                      uint32_t *nbins, uint32_t *binlen) {
     PG_API_BEGIN

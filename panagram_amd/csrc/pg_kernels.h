@@ -194,6 +194,12 @@ hipError_t launch_bgzf_inflate(hipStream_t st, const uint32_t *comp, uint64_t co
 hipError_t launch_window_stats(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint64_t nrows, uint32_t nwin,
                                uint32_t pieces, const uint64_t *starts, const uint64_t *ends, unsigned long long *hist,
                                unsigned long long *cs);
+// masked per-bin column sums (pg_bins.hip): bin i = sampled rows [starts[i], ends[i]) of the rows at rows + base[i], sampled
+// row j being row j * stride; keep: ceil(N / 32) words (bits past N zero).  cs ([nbins][N]) and kept ([nbins]) are zeroed
+// by the caller and accumulated into.
+hipError_t launch_bin_colsums(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, uint32_t nbins,
+                              uint32_t pieces, const uint64_t *base, const uint64_t *starts, const uint64_t *ends,
+                              const uint32_t *keep, uint32_t omit_fixed, unsigned long long *cs, unsigned long long *kept);
 hipError_t launch_rows_epilogue(hipStream_t st, uint32_t ngenomes, const AnchorDesc *ad, const uint32_t *tile_contig,
                                 uint32_t ntiles, const uint8_t *out1, uint8_t *out100, uint32_t *bins,
                                 unsigned long long *colsums, uint32_t flags, const uint2 *d_ranges = nullptr,

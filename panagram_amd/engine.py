@@ -819,6 +819,27 @@ class AnchorResult:
         check(self._lib.pg_result_window_stats(self._h, idx, step, n, _ptr(starts), _ptr(ends), _ptr(hist), _ptr(cs)))
         return hist, cs
 
+    def bin_colsums(self, contigs, starts, ends, step: int = 1, stride: int = 1, keep_words=None, omit_fixed: bool = False):
+        """(cs [nbins, N] uint64, kept [nbins] uint64): bin i = sampled rows [starts[i], ends[i]) of contig contigs[i]'s
+        bitmap.<step> rows, sampled row j = row j * stride; rows without any ``keep_words`` bit get them ORed in, and with
+        ``omit_fixed`` rows whose N bits are then all set are dropped (k_bin_colsums, one launch)"""
+        contigs = np.ascontiguousarray(contigs, np.uint32)
+        starts = np.ascontiguousarray(starts, np.uint64)
+        ends = np.ascontiguousarray(ends, np.uint64)
+        n, N = len(starts), self.ngenomes
+        if len(contigs) != n or len(ends) != n:
+            raise ValueError("contigs, starts and ends need one entry per bin")
+        kw = None
+        if keep_words is not None:
+            kw = np.zeros((N + 31) // 32, np.uint32)
+            given = np.asarray(keep_words, np.uint32).ravel()
+            kw[:min(len(kw), len(given))] = given[:len(kw)]
+        cs = np.zeros((n, N), np.uint64)
+        kept = np.zeros(n, np.uint64)
+        check(self._lib.pg_result_bin_colsums(self._h, int(step), int(stride), n, _ptr(contigs), _ptr(starts), _ptr(ends),
+                                              _ptr(kw), 1 if omit_fixed else 0, _ptr(cs), _ptr(kept)))
+        return cs, kept
+
     def write_bgzf(self, step: int, gz_path: str, gzi_path: Optional[str] = None, level: int = 6,
                    threads: int = 1, first_contig: int = 0, ncontigs: Optional[int] = None) -> None:
         """Stream the bitmap.<step> payload of contigs [first_contig, first_contig + ncontigs) (default:
@@ -839,13 +860,14 @@ class AnchorResult:
 
     @classmethod
     def from_bgzf(cls, ctx: Context, k: int, ngenomes: int, nkmers: Sequence[int], gz_path: str,
-                  gzi_path: Optional[str] = None, file_row0: int = 0, step: int = 1) -> "AnchorResult":
+                  gzi_path: Optional[str] = None, file_row0: int = 0, step: int = 1, lowres_step: int = 100) -> "AnchorResult":
         """A rows container over contigs of ``nkmers`` rows each (contig lengths nkmers + k - 1; k - 1 for a contig without
-        rows) whose bitmap.<step> rows are read back from ``gz_path`` starting at payload row ``file_row0``."""
+        rows) whose bitmap.<step> rows are read back from ``gz_path`` starting at payload row ``file_row0`` (rows of that
+        file: for the low-resolution bitmap, ``step`` = ``lowres_step``, the index's low-resolution step)."""
         nk = np.asarray(nkmers, np.int64)
         ss = SeqSet(ctx, np.where(nk > 0, nk + k - 1, k - 1).astype(np.uint64))
         try:
-            r = cls.rows_container(ctx, k, ngenomes, ss, colsums=False)
+            r = cls.rows_container(ctx, k, ngenomes, ss, colsums=False, lowres_step=lowres_step)
         except Exception:
             ss.close()
             raise

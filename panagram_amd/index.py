@@ -1525,16 +1525,18 @@ class Genome:
             f.write(text)
         os.replace(path + ".tmp", path)
 
-    def _annotate_batches(self, chroms: List[str]) -> List[List[str]]:
-        """runs of chromosomes that are neighbours in the file, each run's rows within annotate_budget (a longer
-        chromosome is a run of its own)"""
+    def _annotate_batches(self, chroms: List[str], budget: Optional[int] = None) -> List[List[str]]:
+        """runs of chromosomes that are neighbours in the file, each run's bitmap.1 rows within ``budget`` (default:
+        annotate_budget; a longer chromosome is a run of its own).  bitmap.1 bytes whatever file is read: a rows container
+        holds the full-resolution rows of its chromosomes even when only the low-resolution ones are filled"""
+        budget = self.annotate_budget if budget is None else budget
         order = {c: i for i, c in enumerate(self.chrs.index)}
         chroms = sorted(chroms, key=order.get)
         nb = self.nbytes
         out, cur, cur_bytes = [], [], 0
         for c in chroms:
             b = int(self.chrs.loc[c, "size"]) * nb
-            if cur and (order[c] != order[cur[-1]] + 1 or cur_bytes + b > self.annotate_budget):
+            if cur and (order[c] != order[cur[-1]] + 1 or cur_bytes + b > budget):
                 out.append(cur)
                 cur, cur_bytes = [], 0
             cur.append(c)
@@ -1543,12 +1545,102 @@ class Genome:
             out.append(cur)
         return out
 
-    def _rows_from_disk(self, chroms: List[str]) -> "engine.AnchorResult":
-        """a rows result over consecutive chromosomes of chrs.tsv, filled from bitmap.1.gz on the GPU"""
+    def _rows_from_disk(self, chroms: List[str], step: int = 1) -> "engine.AnchorResult":
+        """a rows result over consecutive chromosomes of chrs.tsv, filled from bitmap.<step>.gz (1 or the index's
+        low-resolution step) on the GPU"""
         sizes = [int(self.chrs.loc[c, "size"]) for c in chroms]
-        row0 = int(self.chrs["size"].cumsum().shift(fill_value=0).loc[chroms[0]])
-        return engine.AnchorResult.from_bgzf(self.index.context, int(self.index.k), self.ngenomes, sizes, self.bitmap_gz_fname(1),
-                                             self.bitmap_gzi_fname(1), file_row0=row0)
+        if step == 1:
+            row0 = int(self.chrs["size"].cumsum().shift(fill_value=0).loc[chroms[0]])
+        else:
+            row0 = int(self.offsets.loc[chroms[0], step])
+        return engine.AnchorResult.from_bgzf(self.index.context, int(self.index.k), self.ngenomes, sizes, self.bitmap_gz_fname(step),
+                                             self.bitmap_gzi_fname(step), file_row0=row0, step=step,
+                                             lowres_step=int(self.index.lowres_step))
+
+    # ---- INTROGRESSIONS: binned k-mer similarity (call_introgressions.py: bitmap_to_bins) ----
+    # HBM of one batch of chromosomes read back: their bitmap.1 rows (the container holds them, and zeroes them, when the
+    # low-resolution file is read too), so a batch takes at most this much, plus 1 / lowres_step of it, whatever the step
+    similarity_budget = 8 << 30
+
+    @staticmethod
+    def similarity_bin_geometry(size: int, step: int, bin_size: int):
+        """(bin numbers, first sampled row, end sampled row) of the bins of a chromosome of ``size`` positions sampled every
+        ``step``: sampled row j is position j * step, bin b holds the rows with j * step // bin_size == b, and bins without a
+        sampled row are left out"""
+        n = -(-int(size) // int(step))  # len(range(0, size, step))
+        if n == 0:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64)
+        b = np.arange((n - 1) * step // bin_size + 1, dtype=np.int64)
+        s = -(-(b * bin_size) // step)
+        e = np.minimum(n, -(-((b + 1) * bin_size) // step))
+        ok = s < e
+        return b[ok], s[ok], e[ok]
+
+    def similarity_keep_words(self, keep) -> Optional[np.ndarray]:
+        """genome names (or column numbers) -> the keep mask's 32-bit words; None for no mask"""
+        if keep is None:
+            return None
+        names = list(self.index.genome_names)
+        words = np.zeros((self.ngenomes + 31) // 32, np.uint32)
+        for g in keep:
+            i = names.index(g) if not isinstance(g, (int, np.integer)) else int(g)
+            if not 0 <= i < self.ngenomes:
+                raise ValueError(f"keep: genome {g!r} out of range")
+            words[i // 32] |= np.uint32(1 << (i % 32))
+        return words
+
+    def kmer_similarity_bins(self, chroms=None, step: int = 100, bin_size: int = 1_000_000, omit_fixed: bool = False,
+                             keep=None) -> Dict[str, pd.DataFrame]:
+        """{chrom: DataFrame} as ``bitmap_to_bins(genome.query(chrom, 0, size, step), bin_size, ...)`` of the reference's
+        introgression caller gives it: one row per genome, one column per bin (its start position), each value the bin's
+        column sum over the largest column sum of the bin.  ``keep`` (genome names): rows holding none of their bits get them
+        (--rmu); ``omit_fixed``: rows holding every genome are dropped (--rmf).  A bin whose rows were all dropped is 1.0, a
+        bin whose sums are all zero NaN.  The rows are read back from the bitmap on the GPU (batches of neighbouring
+        chromosomes whose bitmap.1 rows fit ``similarity_budget`` bytes of HBM) and binned by k_bin_colsums, one launch per batch."""
+        step, bin_size = int(step), int(bin_size)
+        if step < 1 or bin_size < 1:
+            raise ValueError(f"step and bin_size must be positive, got {step}, {bin_size}")
+        if self.chrs is None:
+            self.load_chrs()
+        chroms = list(self.chrs.index) if chroms is None else [str(c) for c in chroms]
+        for c in chroms:
+            if c not in self.chrs.index:
+                raise KeyError(f"{self.name}: no chromosome {c!r}")
+        bstep = max(s for s in self.steps if step % s == 0)
+        stride = step // bstep
+        kw = self.similarity_keep_words(keep)
+        names = pd.Index(self.index.genome_names)
+        out: Dict[str, pd.DataFrame] = {}
+        geo = {c: self.similarity_bin_geometry(int(self.chrs.loc[c, "size"]), step, bin_size) for c in chroms}
+        todo = [c for c in dict.fromkeys(chroms) if len(geo[c][0])]
+        for c in chroms:
+            if not len(geo[c][0]):
+                out[c] = pd.DataFrame(np.zeros((self.ngenomes, 0)), index=names, columns=pd.Index([], dtype=np.int64))
+        for batch in self._annotate_batches(todo, self.similarity_budget):
+            res = self._rows_from_disk(batch, bstep)
+            try:
+                ci = np.concatenate([np.full(len(geo[c][0]), i, np.uint32) for i, c in enumerate(batch)])
+                st = np.concatenate([geo[c][1] for c in batch])
+                en = np.concatenate([geo[c][2] for c in batch])
+                cs, kept = res.bin_colsums(ci, st, en, step=bstep, stride=stride, keep_words=kw, omit_fixed=omit_fixed)
+            finally:
+                res.close()
+            at = 0
+            for c in batch:
+                nb = len(geo[c][0])
+                out[c] = self._similarity_frame(cs[at:at + nb], kept[at:at + nb], geo[c][0] * bin_size, names)
+                at += nb
+        return {c: out[c] for c in chroms}
+
+    @staticmethod
+    def _similarity_frame(cs: np.ndarray, kept: np.ndarray, starts: np.ndarray, names: pd.Index) -> pd.DataFrame:
+        """bins x genomes sums -> the genomes x bins frame of bitmap_to_bins: a bin without rows left is all 1 (its
+        reindex fill value), every bin divided by its largest sum (0 / 0: NaN)"""
+        v = cs.astype(np.float64)
+        v[kept == 0] = 1.0
+        with np.errstate(invalid="ignore", divide="ignore"):
+            v = v / v.max(axis=1, keepdims=True)
+        return pd.DataFrame(v.T, index=names, columns=pd.Index(np.asarray(starts, np.int64)))
 
     def _tabix(self, typ: str):
         from . import annotation as an

@@ -26,7 +26,8 @@
 //                rows), per-bin popcount histogram, per-contig column sums — persistent
 //                workgroups, register accumulators, one instantiation per row width (1..8 bytes;
 //                16 consecutive rows per thread over 4 full tiles of one bin).
-//   k_epilogue_chunks  the same for rows wider than 8 bytes (more than 64 genomes): a lane owns one
+//   k_epilogue_w the same for rows of 9..16 bytes (65..128 genomes): three or four words per row.
+//   k_epilogue_chunks  the same for rows wider than 16 bytes (more than 128 genomes): a lane owns one
 //                16-byte chunk of the rows it visits, one launch reads every row once.
 //   k_window_stats, k_cols_extract / k_cols_merge: side paths (gene / bin windows; the
 //                genome-sharded exchange).
@@ -87,34 +88,10 @@ constexpr int PROBE_SEQW = ((PROBE_TILE + 31) / 32 + 6 + 3) & ~3;  // staged 32-
 #ifndef PG_ABLATE
 #define PG_ABLATE 0  // timing experiments of k_probe (tools/ab_ablate.sh); 0 = the product
 #endif
-#ifndef PG_RC_LDS
-#define PG_RC_LDS 1
-#endif
-#ifndef PG_PROBE_PIPE
-#define PG_PROBE_PIPE 2  // 1: the front end of batch i + 1 ahead of the table look-up of batch i (k_probe); 2: and its fetch issued as soon as batch i's chunks are staged
-#endif
 constexpr uint32_t PROBE_SEQ_BASES = 32u * PROBE_SEQW;
 // k_probe's workgroup is ONE wave: what its lanes hand each other through LDS (the staged lines, the batch's line numbers, the
-// overflow queue) needs no barrier — a wave's LDS instructions are executed in the order they were issued, so a read issued
-// behind a write sees it.  __syncthreads() costs such a kernel an s_waitcnt lgkmcnt(0) — every LDS operation in flight drained —
-// where a wavefront-scope fence emits nothing (38 -> 31 full drains in the one-byte instantiation, the read of the batch's line
-// numbers issued right behind their write).  -DPG_WAVE_SYNC=1 builds that; measured (profiles/r6z_ab_wave_sync.txt, two rounds
-// on one box): configs[1] 3.26 / 3.18 -> 3.27 / 3.23 ms, 27 x 40 Mb 4.45 -> 4.38, 64 x 20 Mb k = 31 5.79 -> 5.79, one launch per
-// genome and d = 5 % unchanged — the round trips it takes off a wave's critical path are slots the seven other waves were already
-// using (latency is not what binds).  Off: the barriers say what is meant.
-#ifndef PG_WAVE_SYNC
-#define PG_WAVE_SYNC 0
-#endif
-#if PG_WAVE_SYNC
-#define PG_WSYNC()                                              \
-    do {                                                        \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  \
-        __builtin_amdgcn_wave_barrier();                        \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  \
-    } while (0)
-#else
-#define PG_WSYNC() __syncthreads()
-#endif
+// overflow queue) needs no barrier, and a __syncthreads() there costs an s_waitcnt lgkmcnt(0).  The barriers say what is
+// meant; wavefront-scope fences in their place changed no timing: profiles/r6z_ab_wave_sync.txt.
 // -DPG_PHASE_TIMING: a measuring build (tools/phase_timing.py) — every wave of k_probe stamps s_memtime at its phase
 // boundaries and adds the phases' cycles to pg_phase_cycles at the end of its tile: where a wave's time goes, waits for
 // the other waves of its SIMD included.  Slots: 0 prologue, 1 front end, 2 wait for the lines, 3 staging, 4 issue of the
@@ -130,33 +107,22 @@ __device__ unsigned long long pg_phase_cycles[1024 * 16];  // (1024 sets, by blo
 #define PG_PH_FLUSH
 #endif
 // (rcb = PROBE_SEQ_BASES - k, handed in: written as PROBE_SEQ_BASES - p - k the compiler adds p and k per position first)
-__device__ __forceinline__ uint64_t revcomp_window(const uint64_t *rw, uint64_t X, uint32_t p, int k, uint64_t kmask, uint32_t rcb) {
-#if PG_RC_LDS
+__device__ __forceinline__ uint64_t revcomp_window(const uint64_t *rw, uint32_t p, uint64_t kmask, uint32_t rcb) {
     return extract_bases32(reinterpret_cast<const uint32_t *>(rw), rcb - p) & kmask;
-#else
-    return revcomp_le(X, k);
-#endif
 }
 
 // scan the 8 slots of a line staged in LDS.  Lines fill front to back without holes (an insert
 // claims the first EMPTY slot and slots never revert), so "full" == last slot used.
 // returns 1 = found, 0 = absent (line not full), -1 = absent from a full line
-#ifndef PG_LDS_SOA
-#define PG_LDS_SOA 1  // staged lines keep their keys and their mask words apart in LDS (stage_chunk / scan_line_lds)
-#endif
 // A table line {key, m0, m1} x SLOTS is staged into LDS as SLOTS keys followed by SLOTS mask pairs: the scan then takes its
 // keys in SLOTS / 2 ds_read_b128 — 4 LDS cycles per 16 bytes and lane — where one ds_read2_b64 per two slots of the
 // interleaved line took 8 (MI355X_MICROARCH.md, LDS table): 16 instead of 32 LDS cycles per batch for the 8 keys, the
 // largest single item of a batch's ~95.  The staging lane's 16-byte chunk leaves as two 8-byte stores (6 + 6 cycles
 // against 13 for the one ds_write_b128).
 __device__ __forceinline__ void stage_chunk(uint4 *line, uint32_t slot, int slots, const uint4 v) {
-#if PG_LDS_SOA
     uint2 *const p = reinterpret_cast<uint2 *>(line);
     p[slot] = make_uint2(v.x, v.y);
     p[slots + slot] = make_uint2(v.z, v.w);
-#else
-    line[slot] = v;
-#endif
 }
 template <bool TWO, int SLOTS>
 __device__ __forceinline__ int scan_line_lds(const uint4 *line, uint64_t key, uint32_t &m0, uint32_t &m1) {
@@ -164,7 +130,6 @@ __device__ __forceinline__ int scan_line_lds(const uint4 *line, uint64_t key, ui
     // the scalar unit folds the masks into the three bits of the hit slot's number (at most one slot holds the
     // key), three v_cndmask turn them into the slot's byte offset, and only that slot's masks are read
     uint64_t kk[SLOTS];
-#if PG_LDS_SOA
 #pragma unroll
     for (int j = 0; j < SLOTS / 2; ++j) {
         const uint4 v = line[j];
@@ -172,11 +137,6 @@ __device__ __forceinline__ int scan_line_lds(const uint4 *line, uint64_t key, ui
         kk[2 * j + 1] = (uint64_t)v.z | ((uint64_t)v.w << 32);
     }
     constexpr uint32_t SLOT_BYTES = 8u, MASK0 = 8u * SLOTS;  // a slot's masks: MASK0 + 8 * slot
-#else
-#pragma unroll
-    for (int sl = 0; sl < SLOTS; ++sl) kk[sl] = *reinterpret_cast<const uint64_t *>(line + sl);
-    constexpr uint32_t SLOT_BYTES = 16u, MASK0 = 8u;
-#endif
     m0 = m1 = 0;
     if constexpr (SLOTS == 8) {
         // (ballot of a compare = v_cmp_eq_u64 with a scalar destination; inverse_ballot = the SGPR pair used as a
@@ -220,45 +180,7 @@ __device__ __forceinline__ int scan_line_lds(const uint4 *line, uint64_t key, ui
     }
 }
 
-// The same scan WITHOUT control flow, for the batches whose every active lane has a staged line (k_probe's cut batches): all
-// 64 lanes read and compare — a lane without a k-mer whatever its clamped run number points at — the hit slot's mask
-// word is read by every lane (slot 0's where nothing matched) and selected by `any & amask`; the lanes whose key is absent
-// from a FULL line come back as a lane mask.  No exec-mask save / restore around the scan and around the hit path, no return
-// code rebuilt through 0 / 1 / -1 and compared again: 11 scalar instructions and three branches fewer per batch.  Measured:
-// within 0.5 % of the scan with its branches — what a dummy instruction costs in the FRONT END of a batch (profiles/
-// r4e_probe_dummy_salu.txt) an instruction saved behind the fetch does not give back; PG_SCAN_FLAT stays 0.
-template <bool TWO>
-__device__ __forceinline__ unsigned long long scan_line_lds_flat(const uint4 *line, uint64_t key, unsigned long long amask, uint32_t &m0,
-                                                                 uint32_t &m1) {
-    static_assert(PG_LDS_SOA == 1, "scan_line_lds_flat reads the split staged line");
-    constexpr int SLOTS = 8;
-    uint64_t kk[SLOTS];
-#pragma unroll
-    for (int j = 0; j < SLOTS / 2; ++j) {
-        const uint4 v = line[j];
-        kk[2 * j] = (uint64_t)v.x | ((uint64_t)v.y << 32);
-        kk[2 * j + 1] = (uint64_t)v.z | ((uint64_t)v.w << 32);
-    }
-    constexpr uint32_t SLOT_BYTES = 8u, MASK0 = 8u * SLOTS;
-    unsigned long long e[8];
-#pragma unroll
-    for (int sl = 0; sl < 8; ++sl) e[sl] = __builtin_amdgcn_ballot_w64(kk[sl] == key);
-    const unsigned long long b0 = e[1] | e[3] | e[5] | e[7], b1 = e[2] | e[3] | e[6] | e[7], b2 = e[4] | e[5] | e[6] | e[7];
-    const unsigned long long any = b0 | b1 | b2 | e[0];
-    const uint32_t off = (__builtin_amdgcn_inverse_ballot_w64(b0) ? SLOT_BYTES : 0u) | (__builtin_amdgcn_inverse_ballot_w64(b1) ? 2u * SLOT_BYTES : 0u) |
-                         (__builtin_amdgcn_inverse_ballot_w64(b2) ? 4u * SLOT_BYTES : 0u);
-    const bool hit = __builtin_amdgcn_inverse_ballot_w64(any & amask);
-    if constexpr (TWO) {
-        const uint2 mk = *reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(line) + off + MASK0);
-        m0 = hit ? mk.x : 0u;
-        m1 = hit ? mk.y : 0u;
-    } else {
-        const uint32_t mk = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(line) + off + MASK0);
-        m0 = hit ? mk : 0u;
-        m1 = 0;
-    }
-    return amask & ~any & __builtin_amdgcn_ballot_w64(kk[SLOTS - 1] != EMPTY_KEY);
-}
+// (a scan without control flow was within 0.5 %: profiles/r4e_ab_probe_scalar_cuts.txt)
 
 // one line straight from global memory: the 8 slot loads are issued together (one latency)
 template <bool TWO, int SLOTS>
@@ -367,22 +289,13 @@ template <int NW>
 struct __attribute__((packed, aligned(4))) WordsN {
     uint32_t w[NW];
 };
-#ifndef PG_ROW12_NT
-#define PG_ROW12_NT 1  // 12-byte rows (89..96 genomes, inline layout) as one non-temporal store: 96 genomes 6.75 -> 6.12 ms (profiles/r5m_ab_row_fuse.txt)
-#endif
-#ifndef PG_ROW4_NT
-#define PG_ROW4_NT 0  // two- and four-byte rows non-temporal: 27 x 40 Mb 4.96 -> 5.59 ms, 16 x 50 Mb 3.35 -> 3.86 (profiles/r5m_ab_row_fuse.txt): not
-#endif
-#ifndef PG_NT_ROWS
-#define PG_NT_ROWS 1  // non-temporal stores for rows that ONE store instruction covers (8 and 16 bytes): see store_row
-#endif
 template <int NW, bool NT = false>
 __device__ __forceinline__ void copy_words(const uint32_t *src, uint8_t *dst, bool hit) {
     WordsN<NW> v;
 #pragma unroll
     for (int i = 0; i < NW; ++i) v.w[i] = 0;
     if (hit) v = *reinterpret_cast<const WordsN<NW> *>(src);
-    if constexpr (NW == 4 && NT && PG_NT_ROWS) {  // (non-temporal, like the 8-byte rows of store_row)
+    if constexpr (NW == 4 && NT) {  // (non-temporal, like the 8-byte rows of store_row)
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         u32x4 q = {v.w[0], v.w[1], v.w[2], v.w[3]};
         __builtin_nontemporal_store(q, reinterpret_cast<u32x4 *>(dst));
@@ -464,7 +377,7 @@ __device__ __forceinline__ void masks_inl(const uint4 *line, uint32_t S, uint32_
 // a row of 9..16 bytes out of registers (zeros for an absent key): the widest pieces the width allows, as store_row_wide
 template <int NS>
 __device__ __forceinline__ void store_words_tail(const uint32_t (&v)[4], uint8_t *dst, uint32_t tail) {
-    if (PG_ROW12_NT && NS == 3 && tail == 0) {  // (wave-uniform) a 12-byte row is one store: non-temporal
+    if (NS == 3 && tail == 0) {  // (wave-uniform) a 12-byte row is one store: non-temporal (profiles/r5m_ab_row_fuse.txt)
         typedef uint32_t u32x3 __attribute__((ext_vector_type(3), aligned(4)));
         u32x3 q = {v[0], v[1], v[2]};
         __builtin_nontemporal_store(q, reinterpret_cast<u32x3 *>(dst));
@@ -485,8 +398,7 @@ __device__ __forceinline__ void store_row_regs(uint8_t *row, uint32_t nbytes, co
     if (nbytes == 16) {  // (wave-uniform) one store covers the row: non-temporal, as store_row_wide
         typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
         u32x4 q = {w[0], w[1], w[2], w[3]};
-        if (PG_NT_ROWS) __builtin_nontemporal_store(q, reinterpret_cast<u32x4 *>(row));
-        else *reinterpret_cast<u32x4 *>(row) = q;
+        __builtin_nontemporal_store(q, reinterpret_cast<u32x4 *>(row));
     } else if (nbytes >= 12) {
         store_words_tail<3>(w, row, nbytes - 12u);
     } else {
@@ -499,18 +411,8 @@ __device__ __forceinline__ void store_row_regs(uint8_t *row, uint32_t nbytes, co
 // order, puts them right — so not for the tile's last batch (the bytes behind its last row are another wave's), and not for the
 // rows the overflow drain resolves (store_row_regs: exact).  Two stores per row at odd addresses cost the probe of 65 genomes
 // 8 % against the one store of 12-byte rows (7.6 against 7.0 ps per position).
-#ifndef PG_ROW_FUSE
-#define PG_ROW_FUSE 1
-#endif
-#ifndef PG_ROW_FUSE3
-#define PG_ROW_FUSE3 1  // three-byte rows as one unaligned dword per row (0: round 3's aligned-dword scheme)
-#endif
-#ifndef PG_ROW_FUSE_NT
-#define PG_ROW_FUSE_NT 1  // the one-store rows of 9..11 and 13..15 bytes written non-temporally (65 genomes 4.3-4.5 -> 3.98 ms, 72 x 30 Mb 14.7 -> 13.8; profiles/r5m_ab_row_fuse.txt)
-#endif
-#ifndef PG_ROW_FUSE8
-#define PG_ROW_FUSE8 1  // the same for rows of 5..7 bytes (one 8-byte store)
-#endif
+// The store is non-temporal (profiles/r5m_ab_row_fuse.txt).  Rows of three bytes (one unaligned dword) and of 5..7 bytes (one 8-byte
+// store) are written the same way: see k_probe's row store.
 // nxt: the first row word of the lane above (0 where that lane has no row), taken by the caller with every lane active
 __device__ __forceinline__ void store_row_fused(uint8_t *row, uint32_t nbytes, const uint32_t (&w)[4], uint32_t nxt) {
     const uint32_t t = nbytes & 3u;  // (wave-uniform, 1..3) bytes of the row's last word
@@ -519,12 +421,10 @@ __device__ __forceinline__ void store_row_fused(uint8_t *row, uint32_t nbytes, c
     typedef uint32_t u32x3u __attribute__((ext_vector_type(3), aligned(1)));
     if (nbytes > 12u) {
         u32x4u q = {w[0], w[1], w[2], (w[3] & keep) | (nxt << (8u * t))};
-        if (PG_ROW_FUSE_NT) __builtin_nontemporal_store(q, reinterpret_cast<u32x4u *>(row));
-        else *reinterpret_cast<u32x4u *>(row) = q;
+        __builtin_nontemporal_store(q, reinterpret_cast<u32x4u *>(row));
     } else {
         u32x3u q = {w[0], w[1], (w[2] & keep) | (nxt << (8u * t))};
-        if (PG_ROW_FUSE_NT) __builtin_nontemporal_store(q, reinterpret_cast<u32x3u *>(row));
-        else *reinterpret_cast<u32x3u *>(row) = q;
+        __builtin_nontemporal_store(q, reinterpret_cast<u32x3u *>(row));
     }
 }
 // follow a key's probe sequence through inline-layout lines in global memory (all six key words of a line in flight together)
@@ -565,16 +465,15 @@ __device__ __forceinline__ void store_row(uint8_t *row, uint32_t m0, uint32_t m1
     // ordinary stores they push table lines out of the L2 (64 x 20 Mb k=21 8.1-8.4 -> 7.8 ms, k=31 7.22 -> 6.98,
     // 128 genomes 14.0-14.7 -> 13.1-13.9; profiles/r2_ab_nt_rows.txt).  Only where ONE store instruction covers the
     // row, so that a wave writes whole lines: one- and four-byte rows lose 3-5 % that way, rows of two 16-byte pieces
-    // 25 % (256 genomes: 24.8 -> 32.2 ms — each piece leaves the L2 as a partial line).
+    // 25 % (256 genomes: 24.8 -> 32.2 ms — each piece leaves the L2 as a partial line); two- and four-byte rows lose
+    // 13-15 % (profiles/r5m_ab_row_fuse.txt).
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     if (ROWMODE == 1) {
         row[0] = (uint8_t)m0;
     } else if (ROWMODE == 4) {  // four-byte rows (25..32 genomes): one aligned dword
-        if (PG_ROW4_NT) __builtin_nontemporal_store(m0, reinterpret_cast<uint32_t *>(row));
-        else *reinterpret_cast<uint32_t *>(row) = m0;
+        *reinterpret_cast<uint32_t *>(row) = m0;
     } else if (ROWMODE == 5) {  // two-byte rows (9..16 genomes)
-        if (PG_ROW4_NT) __builtin_nontemporal_store((uint16_t)m0, reinterpret_cast<uint16_t *>(row));
-        else *reinterpret_cast<uint16_t *>(row) = (uint16_t)m0;
+        *reinterpret_cast<uint16_t *>(row) = (uint16_t)m0;
     } else if (ROWMODE == 6) {  // three-byte rows (17..24 genomes): two stores at byte alignment
         struct __attribute__((packed)) U16 { uint16_t v; };
         reinterpret_cast<U16 *>(row)->v = (uint16_t)m0;
@@ -582,8 +481,7 @@ __device__ __forceinline__ void store_row(uint8_t *row, uint32_t m0, uint32_t m1
     } else if (ROWMODE == 2 || rc.words == 4) {  // (rc.words == 4: both words at an 8-byte aligned column: one store)
         u32x2 q = {m0, m1};
         uint8_t *p = row + (ROWMODE == 2 ? 0u : rc.col0);
-        if (PG_NT_ROWS) __builtin_nontemporal_store(q, reinterpret_cast<u32x2 *>(p));
-        else *reinterpret_cast<u32x2 *>(p) = q;
+        __builtin_nontemporal_store(q, reinterpret_cast<u32x2 *>(p));
     } else if  (rc.words == 1) {  // wave-uniform
         *reinterpret_cast<uint32_t *>(row + rc.col0) = m0;
         if (rc.nb1) *reinterpret_cast<uint32_t *>(row + rc.col0 + 4) = m1;
@@ -643,7 +541,7 @@ __device__ __forceinline__ uint32_t sliding_min(uint32_t x) {
     return m;
 }
 #undef PG_DPPMIN
-// ---- batches without halo lanes (PG_PROBE_CARRY) -----------------------------------------------------------------
+// ---- batches without halo lanes -----------------------------------------------------------------------------------
 // A position's minimizer is the minimum over the W m-mers of its k-mer: its own (the last one) and the W - 1 before it,
 // which the W - 1 lanes below own.  The first W - 1 lanes of a batch have too few lanes below them; round 1-4 made them
 // HALO lanes — they only supplied m-mers, and a batch brought 64 - (W - 1) new positions (57 of 64 lanes at W = 7).
@@ -654,35 +552,7 @@ __device__ __forceinline__ uint32_t sliding_min(uint32_t x) {
 // used); their suffix minima take three row-local DPP steps there (a window of eight, cut off where the ~0 begin),
 // interleaved with the next batch's own sliding minimum, which takes them in with one v_min: up to 64 new positions
 // per batch for about eight instructions.
-#ifndef PG_RID_ADDC
-#define PG_RID_ADDC 1  // k_probe's front end: run ids by mbcnt + v_addc_co_u32 (run_ids), no test for a batch without runs
-#endif
-#ifndef PG_SCAN_FLAT
-#define PG_SCAN_FLAT 0  // 1: k_probe's slot scan without control flow (scan_line_lds_flat) — 11 scalar instructions and three branches fewer per batch, parity green, and no faster: not the default (profiles/r4e_ab_probe_scalar_cuts.txt)
-#endif
-#ifndef PG_RUNLESS_TESTS
-#define PG_RUNLESS_TESTS 0  // 1: k_probe's batches without runs skip fetch, staging and scan (rounds 1-4; see back())
-#endif
-#ifndef PG_PROBE_CARRY
-#define PG_PROBE_CARRY 1
-#endif
-// -DPG_PRIO=0xABCD: wave priorities (s_setprio) by phase of a batch, an experiment — A from the wait for the batch's lines on
-// (staging), B around the issue of the next fetch, C for slot scan / overflow entries / row store, D for the front end of
-// the batch after next; 0 = no s_setprio at all (the product; profiles/r4e_ab_setprio.txt)
-#ifndef PG_PRIO
-#define PG_PRIO 0
-#endif
-#if PG_PRIO
-#define PG_PRIO_AT(i) __builtin_amdgcn_s_setprio((PG_PRIO >> (4 * (4 - (i)))) & 3);
-#else
-#define PG_PRIO_AT(i)
-#endif
-#ifndef PG_PROBE_CUT
-#define PG_PROBE_CUT 1
-#endif
-#ifndef PG_EARLY_LINES
-#define PG_EARLY_LINES 1  // the first staging step's line numbers pass through LDS at the end of the front end (k_probe: front)
-#endif
+// (wave priorities by phase of a batch, s_setprio, changed nothing: profiles/r4e_ab_setprio.txt)
 // r[l] = min(x[l .. min(l + 7, last lane of l's row of 16)])
 __device__ __forceinline__ uint32_t suffix_min8_row(uint32_t x) {
     uint32_t r = x;
@@ -734,15 +604,11 @@ __device__ __forceinline__ uint32_t lanes_le_index(unsigned long long mask, uint
 // the set lanes BELOW (its addend -1 is an inline constant), and a lane's own bit comes in as the carry of v_addc_co_u32,
 // whose carry-in operand is a lane mask in an SGPR pair
 __device__ __forceinline__ uint32_t run_ids(unsigned long long lmask) {
-#if PG_RID_ADDC
     const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(lmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lmask, ~0u));
     uint32_t rid;
     unsigned long long carry_out;
     asm("v_addc_co_u32_e64 %0, %1, %2, 0, %3" : "=v"(rid), "=s"(carry_out) : "v"(below), "s"(lmask));
     return rid;
-#else
-    return lanes_le_index(lmask, 0u);
-#endif
 }
 // for a lane whose own bit of `mask` is set: base + its index among the set lanes = base + the set lanes BELOW it, which is
 // what mbcnt counts as it is — none of lanes_le_index's scalar shifts (a scalar instruction costs k_probe's launch what a
@@ -788,7 +654,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
     const uint32_t lbytes = INL ? st.layout * 64u : st.slots * (WIDE ? 8u : 16u);  // (= 16 * SLOTS = 128, as a run-time scalar: see k_probe)
     static_assert(LEVELS >= 1, "k_probe's entries (home line, group) are turned into (next line, step) by level 1's staged batches");
     for (int level = 1; qn > 0; ++level) {
-        PG_WSYNC();
+        __syncthreads();
         if (level > LEVELS) {
             // the few entries still unresolved (long chains) walk their sequences lane by lane:
             // 8 slot loads in flight per line, no staging overhead
@@ -823,7 +689,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
             const uint32_t pl = q_pl[ec];
             const uint64_t kmask = kmer_mask(k);
             const uint64_t X = extract_bases32(reinterpret_cast<const uint32_t *>(sw), pl) & kmask;
-            const uint64_t key = canonical_from_xb(X, revcomp_window(rw, X, pl, k, kmask, PROBE_SEQ_BASES - (uint32_t)k), k);
+            const uint64_t key = canonical_from_xb(X, revcomp_window(rw, pl, kmask, PROBE_SEQ_BASES - (uint32_t)k), k);
             const uint32_t prev_line = lane_up1(line);
             const bool leader = act && (lane == 0 || line != prev_line);
             const unsigned long long lmask = __builtin_amdgcn_ballot_w64(leader);
@@ -839,7 +705,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
                 const uint32_t nl = min((uint32_t)MAXRUN, nruns - r0);
                 if (lane < MAXRUN) lines_w[lane] = padline;
                 if (leader && rid - r0 < nl) lines_w[rid - r0] = line;
-                PG_WSYNC();
+                __syncthreads();
                 uint4 v[STAGE_ITERS];
                 uint32_t ln[STAGE_ITERS];
 #pragma unroll
@@ -852,7 +718,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
                     if constexpr (WIDE) buf[(idx / SLOTS) * LDS_LINE_U4 + (idx % SLOTS)] = v[u];  // (bare keys: as they are)
                     else stage_chunk(buf + (idx / SLOTS) * LDS_LINE_U4, idx % SLOTS, SLOTS, v[u]);
                 }
-                PG_WSYNC();
+                __syncthreads();
                 if (act && rid - r0 < nl) {
                     if constexpr (WIDE && INL) {
                         rcode = scan_keys_inl(buf + (rid - r0) * LDS_LINE_U4, key, st.slots, m1);
@@ -864,7 +730,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
                         rcode = scan_line_lds<TWO, SLOTS>(buf + (rid - r0) * LDS_LINE_U4, key, m0, m1);
                     }
                 }
-                PG_WSYNC();
+                __syncthreads();
             }
             const bool again = act && rcode < 0;
             if constexpr (WIDE && INL) {
@@ -891,7 +757,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
                 q_pl[slot] = (uint16_t)pl;
             }
             kept += (uint32_t)__popcll(kmask2);
-            PG_WSYNC();
+            __syncthreads();
         }
         qn = kept;
     }
@@ -1131,25 +997,18 @@ __device__ __forceinline__ void tile_statistics(uint32_t *H, const uint8_t *tile
 // staging geometry is the same, a line holds 16 bare keys; m0 / m1 carry the hit's line and slot + 1)
 // (probe_pipelined: the instantiations that run the skewed batch order, see the end of the kernel; they are held to the 64
 // registers of 8 waves per SIMD — the only spill that costs them sits around the queue-full call, a cold path)
-#ifndef PG_INL_WAVES8
-#define PG_INL_WAVES8 1  // the inline-layout probe held to the 64 registers of 8 waves per SIMD
-#endif
-#ifndef PG_PIPE_MORE
-#define PG_PIPE_MORE 5  // which further instantiations run the skewed order: bit 0 two-word slots, 1 split layout, 2 the 6-m-mer window, 3 generic rows
-#endif
-#ifndef PG_INL_PIPE
-#define PG_INL_PIPE 0  // 1: the inline-layout probe in the skewed batch order too (it needs 43 registers in the plain order)
-#endif
-template <int W_C, bool TWO, int ROWMODE, int SLOTS, bool WIDE, bool INL = false>
-constexpr bool probe_pipelined = PG_PROBE_PIPE && SLOTS == 8 && (ROWMODE != 3) && ((ROWMODE == 1 || ROWMODE >= 4) || (PG_PIPE_MORE & 8) || TWO || WIDE) &&
-                                 (!TWO || (PG_PIPE_MORE & 1)) && (!WIDE || (PG_PIPE_MORE & 2) || (INL && PG_INL_PIPE)) && (W_C != 6 || (PG_PIPE_MORE & 4));
+// (the skewed order runs for the one-word rows of 1..4 bytes and for two-word slots, every window; not for generic one-word rows
+// nor for the split and inline layouts: profiles/r4_ab_early_fetch.txt, r4e_ab_wide_skewed_order.txt, r5i_inline_layout.txt.  The
+// inline-layout probe is held to the 64 registers of 8 waves per SIMD all the same.)
+template <bool TWO, int ROWMODE, int SLOTS, bool WIDE>
+constexpr bool probe_pipelined = SLOTS == 8 && !WIDE && ROWMODE != 3 && (ROWMODE == 1 || ROWMODE >= 4 || TWO);
 // The scalar registers count too: a SIMD's 800 SGPRs admit floor(800 / (ceil(sgpr / 16) * 16 + 16)) waves — 8 up to 80, 7 up to
 // 96, 6 up to 112 (MI355X_MICROARCH.md) — whatever the compiler's own occupancy figure says.  Left alone the generic-row and
 // split-layout instantiations took 92 and 105 (their lane masks live on the scalar unit): 7 and 6 waves.  Held to 80, a dozen
 // masks move to vector lanes and the ninth to 63rd genome gain 3-6 % (27 x 40 Mb 140 -> 148 G k-mers/s).
 // FUSE: the tile ends with its statistics (tile_statistics above; `fo` says where they go)
 template <int W_C, bool TWO, int ROWMODE, int SLOTS, bool M64, bool WIDE = false, bool INL = false, bool FUSE = false>
-__global__ __launch_bounds__(64, ((probe_pipelined<W_C, TWO, ROWMODE, SLOTS, WIDE, INL> || (INL && PG_INL_WAVES8) || FUSE) ? 8 : 1))
+__global__ __launch_bounds__(64, ((probe_pipelined<TWO, ROWMODE, SLOTS, WIDE> || INL || FUSE) ? 8 : 1))
 __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint64_t *__restrict__ seqw,
                                               const uint32_t *__restrict__ nmw, const uint32_t *__restrict__ has_n,
                                               const SeqDesc *__restrict__ sd, const AnchorDesc *__restrict__ ad,
@@ -1159,23 +1018,16 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
     // A staged line occupies 16*SLOTS + 16 bytes of LDS: the pad keeps the lanes' ds_read_b128 of
     // "their" lines off a common bank group (a power-of-two stride would be a 32-way conflict)
     constexpr int LDS_LINE_U4 = SLOTS + 1;
-    // lines staged per step: 16, whatever the window — a batch ends in front of its 17th run (CUT below).  (While a batch
-    // was a fixed 58 - 61 positions, the 6-m-mer window — what k=21 gets on 150-570 Mb genomes, ~17 lines per batch — staged
-    // 24 to avoid a second step; with batches cut at 16 runs the smaller LDS footprint wins: 8 x 200 Mb 8.0 -> 7.6 ms,
-    // 27 x 160 Mb 21.7 -> 20.3, 64 x 160 Mb 67.3 -> 65.7; profiles/r4b_ab_w6_maxrun.txt)
-#ifndef PG_MAXRUN_W6
-#define PG_MAXRUN_W6 PROBE_MAXRUN  // (24 until batches were cut at MAXRUN runs, see below: -DPG_MAXRUN_W6=24 with -DPG_PROBE_CUT=0)
-#endif
-    constexpr int MAXRUN = W_C == 6 ? PG_MAXRUN_W6 : PROBE_MAXRUN;
+    // lines staged per step: 16, whatever the window — a batch ends in front of its 17th run (CUT below; 24 lines for the
+    // 6-m-mer window lost to the smaller LDS footprint: profiles/r4b_ab_w6_maxrun.txt)
+    constexpr int MAXRUN = PROBE_MAXRUN;
     constexpr int STAGE_ITERS = (MAXRUN * SLOTS + 63) / 64;  // 16-byte loads per lane per staging step
     // ONE block of LDS, carved up by hand, the tile's sequence words FIRST: the two-dword window reads of every batch
     // (ds_read2_b32, whose offsets reach 1020 bytes) then address them with an immediate instead of an add per window
     // (left to itself the compiler put the staging buffer first and the sequence words at 4.2-4.6 KB).
     constexpr int BUF_U4 = ((STAGE_ITERS * 64 + SLOTS - 1) / SLOTS) * LDS_LINE_U4;  // room for every staged chunk slot
     constexpr int OFF_RW = PROBE_SEQW * 8, OFF_NW = OFF_RW + (PROBE_SEQW + 1) * 8, OFF_LW = OFF_NW + PROBE_SEQW * 4;
-    // (the 6-m-mer window stages 24 lines per step: with the full queue its 5968 bytes round up to 6144 = 26 waves per CU,
-    // 6 per SIMD; 152 entries bring it to 5568 -> 5632 = 29 waves, 7 per SIMD)
-    constexpr int QCAP = (W_C == 6 && MAXRUN > PROBE_MAXRUN && PROBE_QCAP > 152) ? 152 : PROBE_QCAP;
+    constexpr int QCAP = PROBE_QCAP;
     constexpr int OFF_BUF = (OFF_LW + MAXRUN * 4 + 15) & ~15, OFF_QL = OFF_BUF + BUF_U4 * 16, OFF_QS = OFF_QL + QCAP * 4;
     constexpr int OFF_QP = OFF_QS + QCAP * 4, LDS_BYTES = OFF_QP + QCAP * 2;
     static_assert(OFF_LW <= 1020 || PROBE_TILE > 1024, "the sequence words must stay within reach of ds_read2_b32's offsets");
@@ -1214,21 +1066,19 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
         nw[i] = (hasn && wi < s.nwords) ? nmw[s.seq_off + wi] : 0u;
     }
     if (lane == 0) rw[PROBE_SEQW] = 0;  // (a window's three dwords may reach one word past the end)
-    PG_WSYNC();  // single wave: compiles to a wave-level wait, not an s_barrier
+    __syncthreads();  // single wave: compiles to a wave-level wait, not an s_barrier
 
     // (minimizer tables: k >= 20, the mask's low word is all ones — spelt out, the compiler drops the ANDs with it: two per
     // position)
     const uint64_t kmask = W_C ? (((uint64_t)(k == 32 ? ~0u : ((1u << (2 * k - 32)) - 1u)) << 32) | 0xFFFFFFFFull) : kmer_mask(k);
     const uint32_t rcb = PROBE_SEQ_BASES - (uint32_t)k;
     constexpr int HALO = W_C ? W_C - 1 : 0;  // m-mers of a window that lanes below its own supply
-    constexpr bool CARRY = PG_PROBE_CARRY && W_C >= 2;  // the first lanes' missing m-mers carried over from the batch before (sliding_min_suffix)
+    constexpr bool CARRY = W_C >= 2;  // the first lanes' missing m-mers carried over from the batch before (sliding_min_suffix)
     // CUT: a batch ends in front of its (MAXRUN + 1)-th run — the next batch starts there — so that ONE staging step takes
     // every batch: at w = 7 a quarter of the 58-position batches met more than 16 lines and paid a second, unhidden fetch
     // (not in direct mode, k < 20: every position is a run of its own there, and a batch of 16 positions would run the front
     // end four times where four staging steps share one)
-    constexpr bool CUT = PG_PROBE_CUT != 0 && W_C != 0;
-    constexpr int LHALO = CARRY ? 0 : HALO;  // lanes of a batch that only supply m-mers to their successors
-    [[maybe_unused]] constexpr int STRIDE = 64 - LHALO;  // new positions per batch (at most: CUT)
+    constexpr bool CUT = W_C != 0;
     const uint32_t m = W_C ? (uint32_t)k - W_C + 1 : 0;
     const uint64_t mm64 = (m >= 32) ? ~0ull : ((1ull << (2 * (m ? m : 1))) - 1);
     // (columns mode: `out1` is the block's column buffer, `nbytes` its width in genomes; the "rows" of the tile are
@@ -1249,14 +1099,14 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
     const uint32_t lbytes = INL ? st.layout * 64u : st.slots * (WIDE ? 8u : 16u);  // bytes per line (= 16 * SLOTS = 128), as a run-time scalar (inline layout: LAYOUT_INLINE * 64)
 
     // A batch in three parts, so that the front end of batch i + 1 can run while the table lines of batch i are on
-    // their way (PG_PROBE_PIPE): the fetch is the longest wait of a batch — a couple of thousand cycles behind a busy
+    // their way: the fetch is the longest wait of a batch — a couple of thousand cycles behind a busy
     // texture-address unit and a TLB that misses on a quarter of these random lines — and the next batch's keys,
     // minimizers and runs need nothing from it.
     struct Front {  // what the front end of a batch leaves behind: no table access so far
         uint64_t key;
         uint32_t grp, line, rid, nruns, padline;
         uint32_t adv;                            // positions the batch covers: the next one starts that many further on (wave-uniform)
-        uint32_t ln[PG_EARLY_LINES ? STAGE_ITERS : 1];  // the lines this lane fetches a chunk of in the first staging step
+        uint32_t ln[STAGE_ITERS];                // the lines this lane fetches a chunk of in the first staging step
         unsigned long long rmask, amask, lmask;  // lanes with a position / active (no N in the window) / first of a run
     };
     // ---- the carry of a batch that starts at position b0 of the tile (the tile's first, or one the tail loop starts
@@ -1275,29 +1125,23 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
         return y;
     };
     uint32_t carry = ~0u;  // (CARRY) what the next front() takes in (lanes 0 .. HALO - 1): written by carry_at or by the front() before
-    // ---- keys: lane = position b0 + lane - LHALO; it also owns m-mer number b0 + lane + (HALO - LHALO) ----
-    // FIRST: the tile's first batch, whose leading HALO lanes stand before the tile's first k-mer (pl < 0: they take
-    // their m-mers out of that k-mer, at their own offsets); in every later batch a lane's m-mer sits at the one fixed
-    // offset and its position needs no clamp — instantiated twice so that the later batches carry neither.
-    auto front = [&](auto first_tag, const uint32_t b0) __attribute__((always_inline)) {
-        constexpr bool FIRST = decltype(first_tag)::value;
+    // ---- keys: lane = position b0 + lane; it also owns m-mer number b0 + lane + HALO ----
+    auto front = [&](const uint32_t b0) __attribute__((always_inline)) {
         Front f;
-        const int32_t pl = (int32_t)(b0 + lane) - LHALO;
-        // (pl >= b0 exactly for the lanes behind the halo: a constant lane mask; a ballot straight off the compare stays
-        // a scalar mask, one of a bool that was AND-ed together first is rebuilt through 0 / 1)
-        f.rmask = __builtin_amdgcn_ballot_w64(pl < (int32_t)npos) & ~((1ull << LHALO) - 1ull);
-        const uint32_t pq = (FIRST && LHALO) ? (uint32_t)max(pl, 0) : (uint32_t)pl;
+        const int32_t pl = (int32_t)(b0 + lane);
+        // (a ballot straight off the compare stays a scalar mask)
+        f.rmask = __builtin_amdgcn_ballot_w64(pl < (int32_t)npos);
+        const uint32_t pq = (uint32_t)pl;
         const uint64_t X = extract_bases32(reinterpret_cast<const uint32_t *>(sw), pq) & kmask;
-        const uint64_t B = revcomp_window(rw, X, pq, k, kmask, rcb);
+        const uint64_t B = revcomp_window(rw, pq, kmask, rcb);
         f.key = ~(X > B ? X : B) & kmask;  // (canonical_from_xb with this kernel's mask)
         f.amask = f.rmask;
         if (hasn) f.amask &= __builtin_amdgcn_ballot_w64(extract_nmask(nw, pq, k) == 0);
         [[maybe_unused]] uint32_t own = 0;
         if (W_C) {
-            // m-mer number b0+lane is the LAST m-mer of this lane's own k-mer (the first lanes of a tile, which have no
-            // k-mer, take theirs out of the tile's first k-mer): forward strand from X, reverse complement from B — no
-            // second pass over the sequence words
-            const uint32_t off = (FIRST && LHALO) ? (uint32_t)(pl + HALO) - pq : (uint32_t)HALO;  // m-mer's offset inside the k-mer, 0..HALO
+            // m-mer number b0 + lane + HALO is the LAST m-mer of this lane's own k-mer: forward strand from X, reverse
+            // complement from B — no second pass over the sequence words
+            constexpr uint32_t off = (uint32_t)HALO;  // m-mer's offset inside the k-mer
             if constexpr (!M64) {  // m-mers of up to 32 bits: one funnel shift each, no 64-bit arithmetic
                 const uint32_t mm32 = (uint32_t)mm64;
                 const uint32_t fa = __builtin_amdgcn_alignbit((uint32_t)(X >> 32), (uint32_t)X, 2 * off) & mm32;
@@ -1317,7 +1161,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
             }
 #endif
             // sliding minimum over lanes [lane-W_C+1, lane]: m <- min(own rank, m of the lane below), W_C-1 times
-            // (the first lanes of the wave see shorter windows: they are halo lanes, never active)
+            // (the first lanes of the wave see shorter windows: the carry supplies the m-mers before them)
             if constexpr (CARRY) {
                 own = f.grp;  // (this lane's own m-mer rank: the next batch's carry is cut out of these below)
                 uint32_t suffix = __builtin_amdgcn_inverse_ballot_w64((1ull << HALO) - 1ull) ? carry : ~0u;
@@ -1342,9 +1186,9 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
             f.amask &= keep;
             f.rmask &= keep;
             f.lmask &= keep;
-            lanes_kept = (uint32_t)__popcll(keep);  // (>= MAXRUN + LHALO when anything is cut: the batch always advances)
+            lanes_kept = (uint32_t)__popcll(keep);  // (>= MAXRUN when anything is cut: the batch always advances)
         }
-        f.adv = lanes_kept - LHALO;
+        f.adv = lanes_kept;
         if constexpr (CARRY) {
             // the next batch's carry: the HALO m-mer ranks in front of its first position's own = lanes lanes_kept - HALO
             // .. lanes_kept - 1 of this batch (not needed before the next front(): the LDS crossbar's latency is hidden)
@@ -1352,7 +1196,6 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
             carry = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(((uint32_t)lane << 2) + ((lanes_kept - HALO) << 2)), (int)own);
         }
         f.nruns = (uint32_t)__popcll(f.lmask);
-#if PG_RID_ADDC
         // (a batch without runs: s_ff1 of an empty mask is -1, v_readlane takes it modulo 64 — lane 63's line, a line of the table
         // like any other, fetched and scanned by no lane: no test for the empty mask)
         // (the instruction itself, not __builtin_ctzll: ctz of 0 is undefined to the COMPILER — it may fold anything — while
@@ -1360,24 +1203,19 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
         int first_run;
         asm("s_ff1_i32_b64 %0, %1" : "=s"(first_run) : "s"(f.lmask));
         f.padline = (uint32_t)__builtin_amdgcn_readlane((int)f.line, first_run & 63);  // (wave-uniform)
-#else
-        f.padline = f.lmask ? (uint32_t)__builtin_amdgcn_readlane((int)f.line, __builtin_ctzll(f.lmask)) : 0u;  // (wave-uniform)
-#endif
 #if PG_ABLATE == 3  // (timing experiment: keys, minimizers and runs only — no table access)
         if (f.line != 0xDEADBEEFu) f.nruns = 0;
 #endif
-        if constexpr (PG_EARLY_LINES != 0) {
-            // The first staging step's line numbers go through lines_w HERE — one per run, padded with the first run's
-            // (see issue) — and every lane reads back the ones it will fetch a chunk of: two LDS round trips that used to
-            // stand between "the chunks of the batch before are staged" and this batch's fetch; the read is in flight
-            // while the caller does something else (the skewed order: the whole staging of the batch before).
-            const bool leader = __builtin_amdgcn_inverse_ballot_w64(f.lmask);
-            if (lane < MAXRUN) lines_w[0][lane] = f.padline;
-            if (leader && f.rid < (uint32_t)MAXRUN) lines_w[0][f.rid] = f.line;
-            PG_WSYNC();
+        // The first staging step's line numbers go through lines_w HERE — one per run, padded with the first run's
+        // (see issue) — and every lane reads back the ones it will fetch a chunk of: two LDS round trips that would
+        // stand between "the chunks of the batch before are staged" and this batch's fetch; the read is in flight
+        // while the caller does something else (the skewed order: the whole staging of the batch before).
+        const bool leader = __builtin_amdgcn_inverse_ballot_w64(f.lmask);
+        if (lane < MAXRUN) lines_w[0][lane] = f.padline;
+        if (leader && f.rid < (uint32_t)MAXRUN) lines_w[0][f.rid] = f.line;
+        __syncthreads();
 #pragma unroll
-            for (int it = 0; it < STAGE_ITERS; ++it) f.ln[it] = lines_w[0][it * (64 / SLOTS) + lane / SLOTS];
-        }
+        for (int it = 0; it < STAGE_ITERS; ++it) f.ln[it] = lines_w[0][it * (64 / SLOTS) + lane / SLOTS];
         return f;
     };
     // ---- the fetch of a staging step: runs r0 .. r0 + MAXRUN - 1 of the batch, MAXRUN lines = MAXRUN * SLOTS chunks of 16
@@ -1394,16 +1232,16 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
     auto issue = [&](const Front &f, const uint32_t r0) __attribute__((always_inline)) {
         Lines L;
         uint32_t ln[STAGE_ITERS];
-        if (PG_EARLY_LINES == 0 || r0 != 0u) {
+        if (r0 != 0u) {  // (the first step's line numbers are the front end's: f.ln)
             const uint32_t nl = min((uint32_t)MAXRUN, f.nruns - r0);  // (0 for a batch without runs: r0 is 0 then)
             const bool leader = __builtin_amdgcn_inverse_ballot_w64(f.lmask);
             if (lane < MAXRUN) lines_w[0][lane] = f.padline;
             if (leader && f.rid - r0 < nl) lines_w[0][f.rid - r0] = f.line;
-            PG_WSYNC();
+            __syncthreads();
         }
 #pragma unroll
         for (int it = 0; it < STAGE_ITERS; ++it) {
-            if (PG_EARLY_LINES == 0 || r0 != 0u) ln[it] = lines_w[0][it * (64 / SLOTS) + lane / SLOTS];
+            if (r0 != 0u) ln[it] = lines_w[0][it * (64 / SLOTS) + lane / SLOTS];
             else ln[it] = f.ln[it];
 #if PG_ABLATE == 1  // (timing experiment, wrong rows: every fetch a cache hit — the lines of one 64 KB window)
             ln[it] &= 511u;
@@ -1416,7 +1254,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
     // ---- the rest of the batch: its lines into LDS, every lane scans its own; overflow entries; the rows ----
     auto back = [&](const Front &f, const Lines &L, const uint32_t b0, auto &&after_staging) __attribute__((always_inline)) {
         const bool act = __builtin_amdgcn_inverse_ballot_w64(f.amask), inrange = __builtin_amdgcn_inverse_ballot_w64(f.rmask);
-        const int32_t pl = (int32_t)(b0 + lane) - LHALO;
+        const int32_t pl = (int32_t)(b0 + lane);
         uint32_t m0 = 0, m1 = 0;
         [[maybe_unused]] uint32_t rw4[4] = {0, 0, 0, 0};  // (inline layout: the row's words, zeros for an absent key)
         int rcode = 0;
@@ -1431,16 +1269,9 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
                 if constexpr (WIDE) mine[it * (64 / SLOTS) * LDS_LINE_U4 + ((uint32_t)lane % SLOTS)] = S.v[it];  // (bare keys: as they are)
                 else stage_chunk(mine + it * (64 / SLOTS) * LDS_LINE_U4, (uint32_t)lane % SLOTS, SLOTS, S.v[it]);
             }
-            PG_WSYNC();
+            __syncthreads();
         };
-        constexpr bool FLAT = PG_SCAN_FLAT && PG_ABLATE == 0 && CUT && !WIDE && SLOTS == 8;  // (CUT: an active lane's run is one of the step's)
-        unsigned long long ovf_flat = 0;
         auto scan = [&](const uint32_t r0) __attribute__((always_inline)) {
-            if constexpr (FLAT) {
-                ovf_flat = scan_line_lds_flat<TWO>(buf[0] + min(f.rid, (uint32_t)MAXRUN - 1u) * LDS_LINE_U4, f.key, f.amask, m0, m1);
-                PG_WSYNC();
-                return;
-            }
             const uint32_t nl = min((uint32_t)MAXRUN, f.nruns - r0);
 #if PG_ABLATE == 5  // (timing experiment: lines fetched and staged, no slot scan: every lane "hits" with one LDS word)
             if (act && f.rid - r0 < nl) {
@@ -1460,25 +1291,23 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
                 }
             }
 #endif
-            PG_WSYNC();
+            __syncthreads();
         };
         // The batch's lines are waited for HERE, on every path (a batch without runs has none in flight).  Left to the
         // compiler, the wait sits inside the branch below, the chunks count as possibly still on their way where the
         // paths meet, and the first instruction that re-uses one of their registers — an address of the NEXT fetch,
         // issued right behind this batch's row store — gets a vmcnt(0) that waits for that store to be acknowledged.
         PG_PH(1)
-        PG_PRIO_AT(1)
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), nothing else
         PG_PH(2)
         // (a batch without runs — a stretch of N — is not singled out: its lines_w hold line 0 throughout (padline), which is fetched,
-        // staged and scanned by no lane; three wave-uniform tests and their branches per batch were 10 scalar instructions)
-        if (PG_RUNLESS_TESTS == 0 || f.nruns) stage(L);
+        // staged and scanned by no lane; three wave-uniform tests and their branches per batch were 10 scalar instructions:
+        // profiles/r4e_ab_probe_scalar_cuts.txt)
+        stage(L);
         PG_PH(3)
-        PG_PRIO_AT(2)
         after_staging();  // (the chunks' registers are free from here on: the skewed order starts the NEXT batch's fetch now)
-        PG_PRIO_AT(3)
         PG_PH(4)
-        if (PG_RUNLESS_TESTS == 0 || f.nruns) scan(0u);
+        scan(0u);
         PG_PH(5)
         if constexpr (!CUT)
         for (uint32_t r0 = MAXRUN; r0 < f.nruns; r0 += MAXRUN) {  // (a batch with more than MAXRUN lines: a quarter of the batches at w = 7)
@@ -1490,7 +1319,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
         // ---- overflow: absent from a full line -> queue entry for the next line of its sequence ----
         // (sicmp = the compare as a lane mask, predicate 40 = signed less-than: a ballot of `rcode < 0` is sunk into the
         // blocks rcode comes from and its bool rebuilt here through 0 / 1)
-        const unsigned long long omask = FLAT ? ovf_flat : (f.amask & __builtin_amdgcn_sicmp(rcode, 0, 40));
+        const unsigned long long omask = f.amask & __builtin_amdgcn_sicmp(rcode, 0, 40);
         const bool ovf = __builtin_amdgcn_inverse_ballot_w64(omask);
         if (omask) {
             // (the entry carries the home line and the GROUP: its step and next line — two multiplies and the wrap — are
@@ -1516,7 +1345,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
         // (32-bit offset from the tile's uniform base: one store with a scalar base address)
         if constexpr (WIDE && INL) {
             // (ragged rows: one store per row — not in the tile's last batch, see store_row_fused; positions without a row hold zeros)
-            const bool fuse = PG_ROW_FUSE && (nbytes & 3u) != 0u && b0 + (uint32_t)__popcll(f.rmask) < npos;  // (wave-uniform)
+            const bool fuse = (nbytes & 3u) != 0u && b0 + (uint32_t)__popcll(f.rmask) < npos;  // (wave-uniform)
             if (fuse) {
                 const uint32_t mine = inrange ? rw4[0] : 0u;
                 const uint32_t nxt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0x130 /* wave_shl:1 */, 0xf, 0xf, true);  // (lane 63: 0)
@@ -1533,7 +1362,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
 #else
             // (rows of 13..15 bytes, W = 4: the hit's four mask words into registers and ONE 16-byte store per row, as the inline
             // layout's ragged rows — store_row_fused; not in the tile's last batch)
-            if (PG_ROW_FUSE && st.W == 4u && (nbytes & 3u) != 0u && b0 + (uint32_t)__popcll(f.rmask) < npos) {  // (wave-uniform)
+            if (st.W == 4u && (nbytes & 3u) != 0u && b0 + (uint32_t)__popcll(f.rmask) < npos) {  // (wave-uniform)
                 uint32_t v4[4] = {0, 0, 0, 0};
                 if (inrange && m1) {
                     const WordsN<4> g = *reinterpret_cast<const WordsN<4> *>(reinterpret_cast<const uint32_t *>(st.masks) + ((uint64_t)m0 * SPLIT_KEYS + (m1 - 1u)) * 4u);
@@ -1547,14 +1376,14 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
         } else if constexpr (ROWMODE == 3) {
             const uint32_t w0 = b0 >> 6, sh = b0 & 63u;
             for (uint32_t j = 0; j < rc.col0; ++j) {  // (uniform) one ballot per genome of the block
-                const unsigned long long shifted = __ballot(inrange && ((m0 >> j) & 1u)) >> LHALO;  // bit i = position b0 + i
+                const unsigned long long shifted = __ballot(inrange && ((m0 >> j) & 1u));  // bit i = position b0 + i
                 if (lane == 0 && shifted) {
                     cols[w0 * COLS_G + j] |= shifted << sh;
                     if (sh && (shifted >> (64u - sh))) cols[(w0 + 1) * COLS_G + j] |= shifted >> (64u - sh);
                 }
             }
         } else {
-            if (PG_ROW_FUSE3 && ROWMODE == 6 && b0 + (uint32_t)__popcll(f.rmask) < npos) {  // (wave-uniform; ROWMODE a constant)
+            if (ROWMODE == 6 && b0 + (uint32_t)__popcll(f.rmask) < npos) {  // (wave-uniform; ROWMODE a constant)
                 // (three-byte rows as ONE unaligned dword per row — the row and the next lane's first byte — as the
                 // 5..7-byte rows; not in the tile's last batch)
                 const uint32_t mine = inrange ? m0 : 0u;
@@ -1562,7 +1391,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
                 struct __attribute__((packed)) U32 { uint32_t v; };
                 if (inrange) reinterpret_cast<U32 *>(tile_rows + (uint32_t)pl * 3u)->v = (m0 & 0xFFFFFFu) | (nxt << 24);
             } else if constexpr (ROWMODE == 6) {
-                // Three-byte rows as ALIGNED dwords: a u16 and a u8 per lane at odd addresses cost the launch a third
+                // (the tile's last batch) Three-byte rows as ALIGNED dwords: a u16 and a u8 per lane at odd addresses cost the launch a third
                 // of its time (20 x 40 Mb: 6.7 ps per position against 5.1 with the four-byte rows of 27 genomes).
                 // The batch's rows are 3 x 58 consecutive bytes; the aligned dword that starts inside a lane's row
                 // holds the row's last 3 - j bytes and the next lane's first j + 1 (j = 0..2 by the row's address
@@ -1577,7 +1406,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
                 const uint32_t dw = __builtin_amdgcn_alignbit(nxt >> 8, lo, 8u * j);
                 const unsigned long long nextin = f.rmask >> 1;
                 const unsigned long long dmask = f.rmask & nextin & __builtin_amdgcn_ballot_w64(j != 3u);
-                const unsigned long long fmask = f.rmask & ((1ull << LHALO) | ~nextin);
+                const unsigned long long fmask = f.rmask & (1ull | ~nextin);
                 uint8_t *row = tile_rows + (uint32_t)pl * 3u;
                 if (__builtin_amdgcn_inverse_ballot_w64(dmask)) *reinterpret_cast<uint32_t *>(row + j) = dw;
                 if (__builtin_amdgcn_inverse_ballot_w64(fmask)) store_row<ROWMODE>(row, m0, m1, rc);
@@ -1587,7 +1416,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
 #else
             // (rows of 5..7 bytes, 33..56 genomes: ONE 8-byte store per row — the row and the first bytes of the next lane's, as
             // store_row_fused does for the wider ragged rows; not in the tile's last batch)
-            if (PG_ROW_FUSE8 && ROWMODE == 0 && TWO && rc.words == 3u && nbytes >= 5u && b0 + (uint32_t)__popcll(f.rmask) < npos) {  // (wave-uniform)
+            if (ROWMODE == 0 && TWO && rc.words == 3u && nbytes >= 5u && b0 + (uint32_t)__popcll(f.rmask) < npos) {  // (wave-uniform)
                 const uint32_t mine = inrange ? m0 : 0u;
                 const uint32_t nxt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)mine, 0x130 /* wave_shl:1 */, 0xf, 0xf, true);
                 if (inrange) {
@@ -1601,13 +1430,12 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
                 store_row<ROWMODE>(tile_rows + (ROWMODE == 1 ? (uint32_t)pl : ROWMODE == 4 ? (uint32_t)pl * 4u : ROWMODE == 5 ? (uint32_t)pl * 2u : ROWMODE == 6 ? (uint32_t)pl * 3u : (uint32_t)pl * nbytes), m0, m1, rc);
         }
         PG_PH(6)
-        PG_PRIO_AT(4)
     };
     // The skewed order — front end of batch i + 1 between the fetch of batch i and its use — keeps the fetched chunks
     // and two batches' keys in registers at once: it pays where that still fits 64 registers (8 waves per SIMD: this
     // kernel's speed goes with its occupancy — 7 waves cost 7 %, 5 waves 28 %), i.e. for the one-byte rows of up to 8
     // genomes (configs[1]: 4.31 -> 4.17 ms); the wider instantiations spill there and keep the plain order.
-    constexpr bool PIPE = probe_pipelined<W_C, TWO, ROWMODE, SLOTS, WIDE, INL>;
+    constexpr bool PIPE = probe_pipelined<TWO, ROWMODE, SLOTS, WIDE>;
     constexpr int LEVELS = (W_C >= 6 && !TWO && !WIDE && PROBE_STAGED_LEVELS > 1) ? 1 : PROBE_STAGED_LEVELS;  // (W_C >= 6: the wide-window tables of up to 16 genomes)
     // The batch loop runs until the tile is through OR the overflow queue could not take another full batch (tiles inside
     // a repeat family: most of their keys sit outside their home lines): the queue is drained then and the loop goes on
@@ -1627,47 +1455,36 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
         for (int it = 0; it < STAGE_ITERS; ++it) L.v[it] = make_uint4(0, 0, 0, 0);
         PG_PH(0)
         carry = carry_at(0u);
-        Front cur = front(std::true_type{}, 0u);
-        if (PG_RUNLESS_TESTS == 0 || cur.nruns) L = issue(cur, 0u);
+        Front cur = front(0u);
+        L = issue(cur, 0u);
         for (;;) {
             PG_PH(7)
             const uint32_t b1 = b0 + cur.adv;
             const bool more = b1 < npos;  // (wave-uniform)
             Front nxt = cur;
             __builtin_amdgcn_sched_barrier(0);  // (the parts stay apart: interleaved by the scheduler they keep both batches' temporaries alive)
-            if (more) nxt = front(std::false_type{}, b1);  // while the lines of `cur` are on their way
+            if (more) nxt = front(b1);  // while the lines of `cur` are on their way
             __builtin_amdgcn_sched_barrier(0);
-#if PG_PROBE_PIPE >= 2
             // the next batch's fetch goes out as soon as this batch's chunks have left their registers for LDS: it is in
             // flight during this batch's slot scan, row store and overflow entries AND the front end after next
             back(cur, L, b0, [&]() __attribute__((always_inline)) {
-                if (more && (PG_RUNLESS_TESTS == 0 || nxt.nruns)) L = issue(nxt, 0u);
+                if (more) L = issue(nxt, 0u);
             });
             __builtin_amdgcn_sched_barrier(0);
             b0 = b1;
             if (!more || qn > QROOM) break;  // (rare way out with a fetch in flight: nobody reads it; the tail starts the batch again)
             cur = nxt;
-#else
-            back(cur, L, b0, [] {});
-            __builtin_amdgcn_sched_barrier(0);
-            b0 = b1;
-            // (the room is checked AFTER a batch's look-up, which is what fills the queue: the front end of the next batch
-            // is thrown away on the rare way out — the tail starts it again)
-            if (!more || qn > QROOM) break;
-            cur = nxt;
-            if (PG_RUNLESS_TESTS == 0 || cur.nruns) L = issue(cur, 0u);
-#endif
         }
     } else {
         {
             carry = carry_at(0u);
-            const Front f = front(std::true_type{}, 0u);
+            const Front f = front(0u);
             const Lines L = issue(f, 0u);  // (also for a batch without runs — a stretch of N: line 0 is fetched and ignored)
             back(f, L, 0u, [] {});
             b0 = f.adv;
         }
         while (b0 < npos && qn <= QROOM) {
-            const Front f = front(std::false_type{}, b0);
+            const Front f = front(b0);
             const Lines L = issue(f, 0u);
             back(f, L, b0, [] {});
             b0 += f.adv;
@@ -1678,10 +1495,10 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
         drain_queue<TWO, ROWMODE, SLOTS, MAXRUN, WIDE, LEVELS, INL>(st, qn, sw, rw, q_line, q_step, q_pl, lines_w[0], buf[0], tile_rows, nbytes, rc, lane);
         qn = 0;
         if (b0 >= npos) break;
-        PG_WSYNC();
+        __syncthreads();
         carry = carry_at(b0);  // (the hot loop may have left with the front end of a batch it did not finish)
         while (b0 < npos && qn <= QROOM) {
-            const Front f = front(std::false_type{}, b0);
+            const Front f = front(b0);
             const Lines L = issue(f, 0u);
             back(f, L, b0, [] {});
             b0 += f.adv;
@@ -1734,9 +1551,6 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
 // counters[0] += newly claimed keys; counters[1] = overflow flag (a probe sequence exceeded max_probe lines).
 // ---------------------------------------------------------------------------
 constexpr int INSERT_QCAP = 256;
-#ifndef PG_INSERT_SPREAD
-#define PG_INSERT_SPREAD 1
-#endif
 
 // The claiming insert for a batch of 64 queue entries, wave-cooperative.  The protocol is lane_insert_grp's (a key may
 // be claimed in a slot only by someone who has seen every earlier slot of its sequence hold OTHER keys; slots never
@@ -1811,7 +1625,6 @@ __device__ __forceinline__ int wave_insert_batch(const SubTable &st, bool valid,
             }
         }
         if constexpr (!CLAIM) continue;  // (s is -1 or slots here: read the next line, or finished)
-#if PG_INSERT_SPREAD
         // The lanes of a run that have just read their line claim DISTINCT slots in one round: first empty slot + rank
         // in the run.  A claim made this way has not yet seen the slots below it; it sees them right after — every slot
         // of the run's range is occupied once the round is over, and what each holds comes back with its lane's CAS —
@@ -1860,7 +1673,6 @@ __device__ __forceinline__ int wave_insert_batch(const SubTable &st, bool valid,
             }
         }
         fresh = false;
-#endif
         // one compare-and-swap round among the lanes that have a slot to try
         const bool want = !done && s >= 0 && s < (int)slots;
         unsigned long long *kp = want ? key_ptr(st, b, (uint32_t)s) : nullptr;
@@ -1966,7 +1778,7 @@ __global__ __launch_bounds__(64) void k_insert_tile(const SubTable st, int w, ui
         const bool inrange = pl >= (int32_t)b && pl < (int32_t)npos;
         const uint32_t pq = (uint32_t)max(pl, 0);
         const uint64_t X = extract_bases32(reinterpret_cast<const uint32_t *>(sw), pq) & kmask;
-        const uint64_t B = revcomp_window(rw, X, pq, k, kmask, rcb);
+        const uint64_t B = revcomp_window(rw, pq, kmask, rcb);
         const uint64_t key = ~(X > B ? X : B) & kmask;
         bool act = inrange;
         if (hasn) act = act && (extract_nmask(nw, pq, k) == 0);
@@ -1992,7 +1804,7 @@ __global__ __launch_bounds__(64) void k_insert_tile(const SubTable st, int w, ui
         unsigned long long amask = __builtin_amdgcn_ballot_w64(act);  // (run starts by lane-mask arithmetic on the scalar unit, as in k_probe)
         unsigned long long lmask = amask & (~(amask << 1) | __builtin_amdgcn_ballot_w64(line != prev_line));
         const uint32_t rid = lanes_le_index(lmask, 0u);
-        if constexpr (PG_PROBE_CUT && W_C != 0) {  // one staging step per batch: the lanes behind the PROBE_MAXRUN-th run are the next batch's
+        if constexpr (W_C != 0) {  // one staging step per batch: the lanes behind the PROBE_MAXRUN-th run are the next batch's
             const unsigned long long keep = __builtin_amdgcn_sicmp((int32_t)rid, PROBE_MAXRUN, 40 /* signed < */);
             amask &= keep;
             lmask &= keep;
@@ -2233,15 +2045,6 @@ __device__ __forceinline__ EpiRange epi_range(uint32_t gt, uint32_t ntiles, cons
 // (one-byte rows: held to the registers of 7 waves per SIMD — 72 VGPRs and 20 bytes of scratch on a cold path instead of 79,
 // 96 SGPRs instead of 106: 6 -> 7 workgroups per CU, the pass 0.362 -> 0.353 ms on 8 x 10^8 rows, 0.616 -> 0.588 on
 // 1.6 x 10^9; 8 waves (64 VGPRs, 40 bytes of scratch) are slower, 0.392; profiles/r4b_ab_epilogue_waves.txt)
-#ifndef PG_EPI_HS
-#define PG_EPI_HS 1  // k_epilogue, rows of 2..8 bytes: column sums through eight counter planes behind a Harley-Seal tree
-#endif
-#ifndef PG_EPI_STREAK
-#define PG_EPI_STREAK 1  // k_epilogue, one-byte rows: the bookkeeping of whole one-bin groups once per streak (see the tile loop)
-#endif
-#ifndef PG_EPI_WAIT_HERE
-#define PG_EPI_WAIT_HERE 1  // k_epilogue, one-byte rows: see the group path's prefetch
-#endif
 #ifndef PG_EPI_WAVES0
 #define PG_EPI_WAVES0 7
 #endif
@@ -2299,20 +2102,14 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
     bool next_valid = false;
     uint4 wp_a = make_uint4(0, 0, 0, 0), wp_b = make_uint4(0, 0, 0, 0);  // ... and of 4- / 8-byte rows on the wide path
     bool wp_valid = false;
-    // wide path (8 < N <= 64): column sums in three levels, all in registers until the very end —
-    //  L1  per-thread VERTICAL counters: bit g of plane p is bit p of the number of rows seen with
-    //      genome g set; the 4 rows of a tile enter through carry-save adders (12 ALU ops per 4 rows);
-    //  L2  every 12 rows the planes are transposed into nibbles and added to byte-sliced
-    //      accumulators: byte b of bacc[w][q] counts genome 32w + 8b + q (up to 252 rows);
-    //  L3  a halving exchange over the wave (17 shuffles per word) leaves each total in one lane,
-    //      which adds it to the workgroup's LDS counters.
-#if PG_EPI_HS
-    // (round 4: L1 and L2 as in k_epilogue_chunks — EIGHT bit planes per word behind a Harley-Seal carry-save tree: four rows
-    // enter the ones / twos planes per call (9 instructions), their carry of weight 4 is held back every other call and enters
-    // the fours plane with the next one (3), likewise the eights, and every 16 rows one carry ripples through the upper four
-    // planes (8): 3.3 instructions per row and word where four planes emptied every 12 rows into byte-sliced accumulators took
-    // 8.3 — a quarter of the 22 vector instructions per row that bound the pass for rows of 2 and 3 bytes
-    // (profiles/r4e_pmc_n12_n27.txt); the planes are emptied every 240 rows straight into L3's exchange)
+    // wide path (8 < N <= 64): column sums in two levels, all in registers until the very end —
+    //  L1  per-thread VERTICAL counters: bit g of plane p is bit p of the number of rows seen with genome g set.  EIGHT bit
+    //      planes per word behind a Harley-Seal carry-save tree, as in k_epilogue_chunks: four rows enter the ones / twos
+    //      planes per call (9 instructions), their carry of weight 4 is held back every other call and enters the fours plane
+    //      with the next one (3), likewise the eights, and every 16 rows one carry ripples through the upper four planes (8):
+    //      3.3 instructions per row and word (profiles/r4e_ab_stats_harley_seal_mid.txt);
+    //  L2  every 240 rows the planes are transposed into byte counters, and a halving exchange over the wave (17 shuffles
+    //      per word) leaves each total in one lane, which adds it to the workgroup's LDS counters.
     uint32_t vp[2][8] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}}, pf[2] = {0, 0}, pe[2] = {0, 0};
     uint32_t vrows = 0;  // rows in the planes (block-uniform, a multiple of 4): the carries held back follow from it
     constexpr uint32_t VROWS_FLUSH = 240;
@@ -2349,7 +2146,7 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
         p[3] = t5 ^ c8;
         ripple(p, c16, 4);
     };
-    auto vflush = [&]() {  // L1 -> L3, wave-uniform call sites only
+    auto vflush = [&]() {  // L1 -> L2, wave-uniform call sites only
         const bool odd4 = (vrows & 4u) != 0, odd8 = (vrows & 8u) != 0;  // carries still held back (a flush between whole 16-row blocks)
         for (uint32_t ws = 0; ws < ndbs && ws < 2; ++ws) {
             if (odd4) ripple(vp[ws], pf[ws], 2);
@@ -2386,73 +2183,6 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
         }
         vrows = 0;
     };
-    [[maybe_unused]] uint32_t brounds = 0;
-    auto wave_colsums = [&]() {};
-#else
-    constexpr uint32_t VROWS_FLUSH = 12;
-    uint32_t vp[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    uint32_t bacc[2][8] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
-    uint32_t vrows = 0, brounds = 0;
-    auto vadd4 = [&](int ws, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3) {
-        const uint32_t x = vp[ws][0];
-        const uint32_t t1 = x ^ r0, s1 = t1 ^ r1, ca = (t1 & r1) | (~t1 & x);      // x + r0 + r1
-        const uint32_t t2 = s1 ^ r2, s2 = t2 ^ r3, cb = (t2 & r3) | (~t2 & s1);    // .. + r2 + r3
-        vp[ws][0] = s2;
-        const uint32_t y = vp[ws][1];
-        const uint32_t t3 = y ^ ca, cc = (t3 & cb) | (~t3 & y);                     // twos + ca + cb
-        vp[ws][1] = t3 ^ cb;
-        const uint32_t c4 = vp[ws][2] & cc;
-        vp[ws][2] ^= cc;
-        vp[ws][3] ^= c4;
-    };
-    auto wave_colsums = [&]() {  // L3, wave-uniform call sites only
-        for (uint32_t ws = 0; ws < ndbs && ws < 2; ++ws) {
-            uint32_t R[16];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                R[2 * q] = bacc[ws][q] & 0x00FF00FFu;
-                R[2 * q + 1] = (bacc[ws][q] >> 8) & 0x00FF00FFu;
-                bacc[ws][q] = 0;
-            }
-#pragma unroll
-            for (int half = 8, bit = 32; half >= 1; half >>= 1, bit >>= 1) {
-                const bool up = (lane & bit) != 0;
-#pragma unroll
-                for (int i = 0; i < half; ++i) {
-                    const uint32_t send = up ? R[i] : R[i + half];
-                    const uint32_t keep = up ? R[i + half] : R[i];
-                    R[i] = keep + (uint32_t)__shfl_xor((int)send, bit);
-                }
-            }
-            R[0] += (uint32_t)__shfl_xor((int)R[0], 2);
-            R[0] += (uint32_t)__shfl_xor((int)R[0], 1);
-            if ((lane & 3) == 0) {  // this lane holds register (lane >> 2): q = idx / 2, odd idx = bytes 1 and 3
-                const uint32_t idx = (uint32_t)lane >> 2;
-                const uint32_t g0 = 32 * ws + (idx >> 1) + ((idx & 1) ? 8u : 0u);
-                if (g0 < Nw && (R[0] & 0xFFFFu)) atomicAdd(&cs[g0], R[0] & 0xFFFFu);
-                if (g0 + 16 < Nw && (R[0] >> 16)) atomicAdd(&cs[g0 + 16], R[0] >> 16);
-            }
-        }
-        brounds = 0;
-    };
-    auto vflush = [&]() {  // L1 -> L2, wave-uniform call sites only
-        for (uint32_t ws = 0; ws < ndbs && ws < 2; ++ws) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t M = 0x11111111u;
-                const uint32_t nib = ((vp[ws][0] >> j) & M) | (((vp[ws][1] >> j) & M) << 1) |
-                                     (((vp[ws][2] >> j) & M) << 2) | (((vp[ws][3] >> j) & M) << 3);
-                bacc[ws][j] += nib & 0x0F0F0F0Fu;
-                bacc[ws][4 + j] += (nib >> 4) & 0x0F0F0F0Fu;
-            }
-#pragma unroll
-            for (int pln = 0; pln < 4; ++pln) vp[ws][pln] = 0;
-        }
-        vrows = 0;
-        if (++brounds == 21) wave_colsums();  // 21 x 12 rows: the byte counters are about to fill
-    };
-
-#endif
     auto spill = [&]() {  // the per-tile path's classes (7-bit fields of hacc) join the thresholds: thr[i] += rows of class > i
         uint32_t run = 0;
 #pragma unroll
@@ -2498,7 +2228,6 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
         }
         if constexpr (WIDE) {
             if (vrows) vflush();
-            if (brounds) wave_colsums();
         }
         __syncthreads();
         for (uint32_t i = tid; i < N; i += EPI_THREADS) {
@@ -2549,7 +2278,7 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
     int nk_kind = 0;
     for (uint32_t tile = t_begin; tile < t_end; ++tile) {
         uint32_t c = cur_c;
-        if (!(MODE == 0 && PG_EPI_STREAK && (streak || gq_valid))) {  // (a group the one before has announced lies in its contig)
+        if (!(MODE == 0 && (streak || gq_valid))) {  // (a group the one before has announced lies in its contig)
             c = tile_contig[tile];
             if (c != cur_c) {  // block-uniform; consecutive tiles nearly always share their contig
                 if (want_cs && cur_c != ~0u) flush_colsums(cur_c);
@@ -2588,8 +2317,8 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
                 if (ba == bz) return 1;
                 return (bl >= 32u && bz - ba + 1u <= MAXB) ? 2 : 0;
             };
-            const bool fast = PG_EPI_STREAK && streak != 0;  // (block-uniform) a group of a streak: whole, one bin, the bin of the group before
-            const bool known = PG_EPI_STREAK && !fast && gq_valid;  // the group before worked this one out (whole; nk_kind, nk_ba .. nk_bz) when it asked for its rows
+            const bool fast = streak != 0;  // (block-uniform) a group of a streak: whole, one bin, the bin of the group before
+            const bool known = !fast && gq_valid;  // the group before worked this one out (whole; nk_kind, nk_ba .. nk_bz) when it asked for its rows
             uint32_t grows_n = span, ba = nk_ba, bz = nk_bz;
             int kind = fast ? 1 : nk_kind;
             if (fast) {
@@ -2613,7 +2342,7 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
                         }
                         cur_row0 = row0g;
                     }
-                    if (PG_EPI_STREAK && kind == 1 && grows_n == span) {
+                    if (kind == 1 && grows_n == span) {
                         // whole groups from ts on that end inside this bin, this contig and this workgroup's range (this one included)
                         const uint64_t bin_end = min((uint64_t)(ba + 1u) * a.binlen, (uint64_t)a.nkmers);
                         streak = min((uint32_t)(bin_end - ts) / span, (t_end - tile) / 8u) - 1u;
@@ -2625,13 +2354,11 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
                 const uint4 z4 = make_uint4(0, 0, 0, 0);
                 const uint4 qa = gq_valid ? gq_next : (nv > 0u ? gg[0] : z4);
                 const uint4 qb = gq_valid ? gq_next2 : (nv > 16u ? gg[1] : z4);
-#if PG_EPI_WAIT_HERE
                 // This group's rows are waited for HERE, before the next group's loads go out.  Left to the compiler the wait sat
                 // at the rows' first use — BEHIND the prefetch — and, the paths above having merged, as vmcnt(0): it waited for
                 // the prefetch as well, so that a group's load latency and its arithmetic ran one after the other (0.35 ms for
                 // 8 x 10^8 rows where a kernel of the same geometry that only loads and counts takes 0.19).
                 __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), nothing else
-#endif
                 // prefetch the next group when this one is whole and a whole group follows right behind
                 const uint32_t tiles_here = (grows_n + PROBE_TILE - 1) / PROBE_TILE;
                 gq_valid = streak != 0;
@@ -3034,12 +2761,9 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
 // ---------------------------------------------------------------------------
 // (it runs 3-4 waves per SIMD on 104-149 VGPRs; round 4's first attempt to hold it to 5 or 6: 65-128 genomes 2.7-5.5 -> 5.0-13.9 ms,
 // profiles/r4b_ab_epilogue_waves.txt)
-template <int C_T, bool EXACT>  // chunks per row known at compile time (1..4), or 0: any
+template <int C_T, bool EXACT>  // chunks per row known at compile time (2..4), or 0: any
 // (held to the registers of 5 waves per SIMD — 96 — it still spills in the row loop: 65-128 genomes 2.67-5.23 -> 3.04-5.55 ms,
 // profiles/r4e_ab_stats_harley_seal.txt)
-#ifndef PG_EPI_REPLC
-#define PG_EPI_REPLC 1  // k_epilogue_chunks: the histogram of a tile inside one or two long bins in 8 (4) copies
-#endif
 #ifndef PG_EPI_WAVESC
 #define PG_EPI_WAVESC 1
 #endif
@@ -3169,7 +2893,6 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
     struct __attribute__((packed)) U128 { uint32_t x, y, z, w; };
     // popcount of a whole row from its lanes' chunks, valid (at least) in the row's first lane
     auto row_popc = [&](uint32_t pc) __attribute__((always_inline)) -> uint32_t {
-        if (C_T == 1) return pc;
         if (C_T == 2) return pc + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pc, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
         if (C_T == 4) {
             pc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pc, 0xB1, 0xF, 0xF, false);
@@ -3209,34 +2932,8 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
     // per-tile state (block-uniform), set when an iteration starts a tile
     uint32_t tile_start = 0, npos = 0, binlen = 1, bin0 = 0, bin0_start = 0, binv = 0, rel_base = 0;
     bool big = false, windowed = false;
-    // One LDS counter per row and (bin, class): the lanes of a wave mostly ask for the same few — on a real pangenome most rows
-    // carry ALL genomes — and the LDS works lanes that add to one word off one after the other (SQ_LDS_BANK_CONFLICT was 94 %
-    // of this pass's LDS cycles, a wave waited for the LDS 28 % of its time; d = 0.0001: +15 % on the whole pass).  While the
-    // tiles lie inside one or two long bins (any contig of more than 100 tiles) the window is therefore used as repl_n COPIES of
-    // those two bin rows, row-lane l / C adding to copy (l / C) % repl_n (copy c at c * repl_stride, an odd stride: the copies
-    // of one class sit in different banks) — k_epilogue's scheme for rows of 2..8 bytes; `unreplicate` folds the copies into
-    // the window's ordinary form, rows 0 and 1, before anything else reads or flushes it.  `repl` is block-uniform.
-    // Measured (profiles/r4e_ab_stats_hist_copies_wide.txt): core-heavy rows (d = 0.0001) 65 genomes 2.95 -> 2.73 ms, 128 genomes
-    // 6.44 -> 5.29 (89.9 -> 98.8 G k-mers/s for the step); the bench's d = 0.01 +1 %.  Rows of two or three chunks (more than
-    // 128 genomes: only every second or third lane adds) LOSE 3-6 % with it at either divergence and keep the plain window.
-    const uint32_t repl_stride = (2u * (N + 1u)) | 1u;
-    const uint32_t repl_n = 8u * repl_stride <= MAXB * (N + 1u) ? 8u : 4u;  // (MAXB >= 16: four copies always fit)
-    const uint32_t repl_off = (((uint32_t)lane / C) % repl_n) * repl_stride;
-    bool repl = false;
-    auto unreplicate = [&]() __attribute__((always_inline)) {
-        if (!repl) return;
-        __syncthreads();
-        for (uint32_t i = tid; i < 2u * (N + 1u); i += EPI_THREADS) {
-            uint32_t hv = hist[i];
-            for (uint32_t cpy = 1; cpy < repl_n; ++cpy) {
-                hv += hist[cpy * repl_stride + i];
-                hist[cpy * repl_stride + i] = 0;
-            }
-            hist[i] = hv;
-        }
-        __syncthreads();
-        repl = false;
-    };
+    // (one LDS counter per row and (bin, class), the plain window: the histogram in several copies, k_epilogue's scheme, loses 3-6 %
+    // where only every second or third lane adds: profiles/r4e_ab_stats_hist_copies_wide.txt)
     for (uint32_t it = 0; it <= nit; ++it) {  // (one more round: the last contig's column sums, flushed at ONE site)
         const bool fin = it == nit;
         if (it + 1 < nit) issue(it + 1, vn);
@@ -3259,34 +2956,19 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
             windowed = binlen >= MINBIN;
             const uint32_t last_rel = (tile_start + npos - 1 - bin0_start) / binlen;
             binv = big ? 0u : 0xFFFFFFFFu / binlen + 1u;
-            if (PG_EPI_REPLC && big && C == 1u) {  // (block-uniform) the tile's one or two bins as copies
-                if (!(repl && row0 >= cur_row0 && row0 + last_rel < cur_row0 + 2u)) {
-                    if (cur_row0 != ~0ull) {
-                        const uint32_t held = repl ? 2u : MAXB;  // (as copies the window held two rows: nothing beyond them to look at)
-                        unreplicate();
-                        __syncthreads();
-                        flush_hist(N, hist, bins, cur_row0, tid, held);
-                        __syncthreads();
-                    }
-                    cur_row0 = row0;
-                    repl = true;
+            const bool fits = cur_row0 != ~0ull && (!windowed ? row0 == cur_row0 : (row0 >= cur_row0 && row0 + last_rel < cur_row0 + MAXB));
+            if (!fits) {
+                if (cur_row0 != ~0ull) {
+                    __syncthreads();
+                    flush_hist(N, hist, bins, cur_row0, tid, MAXB);
+                    __syncthreads();
                 }
-            } else {
-                unreplicate();
-                const bool fits = cur_row0 != ~0ull && (!windowed ? row0 == cur_row0 : (row0 >= cur_row0 && row0 + last_rel < cur_row0 + MAXB));
-                if (!fits) {
-                    if (cur_row0 != ~0ull) {
-                        __syncthreads();
-                        flush_hist(N, hist, bins, cur_row0, tid, MAXB);
-                        __syncthreads();
-                    }
-                    cur_row0 = row0;
-                }
+                cur_row0 = row0;
             }
             rel_base = (uint32_t)(row0 - cur_row0);
         }
         if (r0 < npos) {  // (block-uniform)
-            uint32_t *hrow = hist + rel_base * (N + 1) + (repl ? repl_off : 0u);
+            uint32_t *hrow = hist + rel_base * (N + 1);
             const bool full = EXACT && C_T && (64 % (C_T ? C_T : 1) == 0) && r0 + iter_rows <= npos;  // (block-uniform) no row to mask
 #pragma unroll
             for (uint32_t j = 0; j < NJ; ++j) {
@@ -3337,7 +3019,6 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
 #pragma unroll
         for (uint32_t j = 0; j < NJ; ++j) v[j] = vn[j];
     }
-    unreplicate();
     __syncthreads();
     if (cur_row0 != ~0ull) flush_hist(N, hist, bins, cur_row0, tid, MAXB);
 }
@@ -3355,9 +3036,6 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
 // four rows per thread one tile at a time.  Reference: the per-bin histogram and rows of cpp/anchor.cpp:150-189,
 // index.py:1169-1183; column sums: index.py:1051,1068-1074.
 // ---------------------------------------------------------------------------
-#ifndef PG_EPI_W
-#define PG_EPI_W 1  // 0: rows of 9..16 bytes through k_epilogue_chunks (rounds 2-4)
-#endif
 #ifndef PG_EPI_W_GQ12
 #define PG_EPI_W_GQ12 2  // k_epilogue_w, rows of 9..12 bytes: tiles per group (4: 16 consecutive rows per thread, 2: 8)
 #endif
@@ -4228,7 +3906,7 @@ hipError_t launch_rows_epilogue(hipStream_t st, uint32_t ngenomes, const AnchorD
         hipLaunchKernelGGL(kern, dim3(grid), dim3(EPI_THREADS), lds, st, ngenomes, ad, tile_contig, ntiles, out1, out100, bins,
                            colsums, flags, d_ranges, wpr);
     }
-    else if (PG_EPI_W && nbytes <= 16) {  // 65..128 genomes: 16 rows per thread, three or four words per row
+    else if (nbytes <= 16) {  // 65..128 genomes: 16 rows per thread, three or four words per row
         auto kern = k_epilogue_w<16>;
         switch (nbytes) {
             case 9: kern = k_epilogue_w<9>; break;
@@ -4245,14 +3923,13 @@ hipError_t launch_rows_epilogue(hipStream_t st, uint32_t ngenomes, const AnchorD
         hipLaunchKernelGGL(kern, dim3(grid), dim3(EPI_THREADS), lds, st, ngenomes, ad, tile_contig, ntiles, out1, out100, bins,
                            colsums, flags, d_ranges, wpr);
     }
-    else {  // chunk-parallel: one launch, every row read once
-        const uint32_t C = (nbytes + 15) / 16;
+    else {  // more than 128 genomes, chunk-parallel: one launch, every row read once
+        const uint32_t C = (nbytes + 15) / 16;  // (>= 2)
         if (C > 64) return hipErrorInvalidValue;
         const size_t lds_c = (((maxb * (ngenomes + 1) + 3) & ~3u) + ((64u / C + 15u) / 16u) * 128u * C) * 4 + 16;
         const bool exact = nbytes == 16u * C;
         auto kern = k_epilogue_chunks<0, false>;  // (compile-time C: the lanes-per-row shuffles and index arithmetic unroll)
         switch (C) {
-            case 1: kern = exact ? k_epilogue_chunks<1, true> : k_epilogue_chunks<1, false>; break;
             case 2: kern = exact ? k_epilogue_chunks<2, true> : k_epilogue_chunks<2, false>; break;
             case 3: kern = k_epilogue_chunks<3, false>; break;
             case 4: kern = exact ? k_epilogue_chunks<4, true> : k_epilogue_chunks<4, false>; break;

@@ -867,13 +867,15 @@ def test_one_byte_rows_long_contigs_against_oracle(ctx, n, k, lens):
 
 
 @pytest.mark.parametrize("n,k,lens", [(65, 21, [230_000, 9_000]), (128, 31, [150_000, 2_000]), (200, 21, [120_000]),
-                                      (257, 21, [110_000, 5_000])])
+                                      (257, 21, [110_000, 5_000]), (520, 21, [105_000, 3_000])])
 def test_wide_rows_long_contigs_against_oracle(ctx, n, k, lens):
-    """more than 64 genomes on contigs whose bins are longer than a tile (nkmers / 100 = 1099 .. 2299 rows): the
-    chunk-parallel statistics pass then keeps the histogram of a tile's one or two bins in several LDS copies, folds them
-    when the window moves on (every second or third tile here) and goes back to the plain window on the short contig
-    behind.  One, two and three 16-byte chunks per row, exact and ragged.  Rows, bitmap.100, bins and per-contig column
-    sums against the oracle."""
+    """more than 64 genomes on contigs whose bins are longer than a tile (nkmers / 100 = 1049 .. 2299 rows), a short contig
+    behind them and a partial last tile: a tile's rows fall into one or two bins, and the window of bins moves on every
+    second or third tile.  n = 65 and 128 run k_epilogue_w (rows of 9 and 16 bytes: the histogram in 8 LDS copies while the
+    groups lie inside one or two long bins, the plain window on the short contig), n = 200 and 257 the chunk-parallel pass
+    with a compile-time chunk count (k_epilogue_chunks<2, false> and <3, false>), n = 520 (65-byte rows, five chunks) its
+    run-time instantiation k_epilogue_chunks<0, false>.  Rows, bitmap.100, bins and per-contig column sums against the
+    oracle."""
     from panagram_amd import engine
     rng = np.random.default_rng(n * 1000 + k)
     gen = po.synth_genomes(n, lens, 0.01, 57 + n)

@@ -235,9 +235,10 @@ extern "C" int pg_ctx_create(int device_id, pg_ctx **out) {
         delete c;
         return fail(PG_E_HIP, "hipStreamCreate failed: %s", hipGetErrorString(se));
     }
-    // load the three code objects now (first-launch cost otherwise: ≈ 5 ms inside the first table insert)
+    // load these code objects now (first-launch cost otherwise: ≈ 5 ms inside the first table insert)
     hipError_t pe = preload_table_kernels();
     if (pe == hipSuccess) pe = preload_anchor_kernels();
+    if (pe == hipSuccess) pe = preload_rows_kernels();
     if (pe == hipSuccess) pe = preload_deflate_kernels();
     if (pe != hipSuccess) {
         hipStreamDestroy(c->aux_stream);

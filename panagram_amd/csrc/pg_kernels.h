@@ -17,6 +17,10 @@ namespace pg {
 #endif
 constexpr int PROBE_TILE = PG_PROBE_TILE;      // k-mer positions per wave-tile (k_probe) / per block (k_epilogue)
 constexpr int PROBE_MAXRUN = PG_PROBE_MAXRUN;  // table lines staged in LDS per step of a 64-lane batch
+// bit columns of the genome-sharded mode (k_probe's ROWMODE 3 in pg_anchor.hip, k_cols_* in pg_rows.hip)
+constexpr int COLS_G = 8;  // genomes per block in columns mode
+constexpr uint32_t TILE_SLOTS = PROBE_TILE / 64;  // u64 column words per genome and tile (a slot = 64 positions)
+static_assert(PROBE_TILE % 512 == 0, "the column kernels take a tile in units of 512 positions");
 #ifndef PG_PROBE_STAGED_LEVELS
 #define PG_PROBE_STAGED_LEVELS 2
 #endif
@@ -101,6 +105,7 @@ hipError_t launch_insert_tiles(hipStream_t st, const SubTable &t, int w, uint32_
 // kernels' file ≈ 5 ms, which used to land on the first genome's insert.  pg_ctx_create calls these instead.
 hipError_t preload_table_kernels();
 hipError_t preload_anchor_kernels();
+hipError_t preload_rows_kernels();
 hipError_t preload_deflate_kernels();
 // first tile of every contig (+ the total) of a launch over all contigs of a seqset, computed on the device
 hipError_t launch_tile0(hipStream_t st, const SeqDesc *sd, uint32_t n, uint32_t k, uint32_t tile, uint32_t *tile0);

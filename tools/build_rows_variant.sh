@@ -1,0 +1,7 @@
+#!/bin/bash
+# A library variant that differs in pg_rows.hip only (the statistics kernels and their launchers: defines on the command line), linked
+# with the objects of the last `python panagram_amd/build.py`:  bash tools/build_rows_variant.sh <tag> [-DNAME=VALUE ...]
+TAG=$1; shift
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
+mkdir -p $ROOT/build_variants
+python $ROOT/panagram_amd/build.py --out=$ROOT/build_variants/lib_$TAG.so --only=pg_rows.hip "$@" && echo built $TAG

@@ -382,6 +382,16 @@ int pg_result_window_stats(pg_result *r, uint32_t idx, int step, uint32_t nwin, 
 int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, uint32_t nbins, const uint32_t *contig,
                           const uint64_t *starts, const uint64_t *ends, const uint32_t *keep_words, int omit_fixed,
                           uint64_t *cs_out, uint64_t *kept_out);
+/* pair counts of the genomes over windows of rows, the one matrix behind the viewer's tree of the genomes over a region
+ * (panagram/view.py:751-764: create_tree runs linkage(bitmap.T, "ward", "euclidean") on a sample of the region's rows):
+ * window i = SAMPLED rows [starts[i], ends[i]) of contig contig[i]'s bitmap.<step> rows in HBM, sampled row j being row
+ * j * stride.  pairs_out[(i*ngenomes + a)*ngenomes + b] = rows of window i holding both genome a's and genome b's bit — the
+ * full symmetric matrix; its diagonal are the column sums, and pairs[a][a] + pairs[b][b] - 2 pairs[a][b] is the Hamming
+ * distance of the two genomes' columns, whose square root is the Euclidean distance linkage computes.  Bits past ngenomes
+ * in a row's last byte are ignored.  Every sampled row must lie inside its contig; at most 512 genomes (PG_E_INVALID
+ * beyond).  One launch for all windows (k_pair_counts); synchronises. */
+int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
+                          const uint64_t *starts, const uint64_t *ends, uint64_t *pairs_out);
 /* stream the whole bitmap.1 (step 1) or bitmap.100 (step 100) payload of the result — every
  * contig, in order — from HBM into a BGZF file + .gzi index (gzi_path may be NULL): D2H through
  * pinned double buffers on a private stream overlapped with multi-threaded deflate.  Replaces

@@ -1,6 +1,7 @@
 """CLI surface kept from the reference (`panagram index <samples.tsv> -k K [-o prefix] [-c cores]
 [--prepare]`, panagram/__main__.py:154-194, index.py:90-123) plus the process-level seam of
-cpp/run_anchor (`run_anchor <ngenomes> <root> [<name> <fasta>]...`)."""
+cpp/run_anchor (`run_anchor <ngenomes> <root> [<name> <fasta>]...`), and what the reference only does inside its viewer:
+`tree <index_dir> <genome> <chrom> [start] [end] [step]` prints the Newick tree of the genomes over a region."""
 import argparse
 import os
 import sys
@@ -35,6 +36,17 @@ def main(argv=None):
     an.add_argument("gff_file")
     an.add_argument("--nogene", action="store_true")
     an.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    tr = sub.add_parser("tree", help="Newick tree of the genomes over a region of an anchored genome, from pair counts of its "
+                                     "bitmap rows reduced on the GPU")
+    tr.add_argument("index_dir")
+    tr.add_argument("genome")
+    tr.add_argument("chrom", nargs="?", default=None)
+    tr.add_argument("start", nargs="?", type=int, default=None)
+    tr.add_argument("end", nargs="?", type=int, default=None)
+    tr.add_argument("step", nargs="?", type=int, default=None, help="default: the index's low-resolution step")
+    tr.add_argument("--whole", action="store_true", help="the whole genome in place of a chromosome")
+    tr.add_argument("--matrix", metavar="FILE", default=None, help="also write the pair counts as a tab-separated table")
+    tr.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     it = sub.add_parser("intros", help="call introgressions from k-mer similarity binned on the GPU: `intros call [flags]` "
                                        "(call_introgressions.py's flags) or `intros <config.yaml> [--sweep]`", add_help=False)
     it.add_argument("args", nargs=argparse.REMAINDER)
@@ -64,6 +76,19 @@ def main(argv=None):
             idx[a.genome].run_annotate(a.gff_file, nogene=a.nogene)
         finally:
             idx.close()
+        return 0
+    if a.cmd == "tree":
+        if a.whole == (a.chrom is not None):
+            ap.error("tree: give a chromosome or --whole (and no region with --whole)")
+        from .index import Index
+        idx = Index(a.index_dir, mode="r", device=a.device)
+        try:
+            tree = idx.region_tree(a.genome, a.chrom, a.start, a.end, a.step)
+        finally:
+            idx.close()
+        if a.matrix:
+            tree.counts.to_csv(a.matrix, sep="\t", index_label="name")
+        print(tree.newick)
         return 0
     from .index import run_anchor_cli
     return run_anchor_cli(a.args, a.device)

@@ -3394,6 +3394,76 @@ extern "C" int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, ui
     PG_API_END
 }
 
+// pair counts over sampled rows (the matrix behind view.py:751-764's tree of the genomes over a region): one launch for
+// windows of any of the result's contigs
+extern "C" int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
+                                     const uint64_t *starts, const uint64_t *ends, uint64_t *pairs_out) {
+    PG_API_BEGIN
+    if (!r || (nwin && (!contig || !starts || !ends || !pairs_out)))
+        return fail(PG_E_INVALID, "pg_result_pair_counts: NULL argument");
+    if (step != 1 && step != 100 && (uint32_t)step != r->lowres_step)
+        return fail(PG_E_INVALID, "step must be 1 or the result's low-resolution step (%u; 100 is accepted as its alias)", r->lowres_step);
+    if (stride < 1) return fail(PG_E_INVALID, "pg_result_pair_counts: stride must be >= 1");
+    if (nwin > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_pair_counts: %u windows (at most 2^31 - 1 per call)", nwin);
+    const uint32_t N = r->N;
+    if (N < 1 || N > PAIRS_MAX_GENOMES)
+        return fail(PG_E_INVALID, "pg_result_pair_counts: %u genomes (the pair counts take 1 to %u)", N, PAIRS_MAX_GENOMES);
+    if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
+    if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
+    if (step != 1 && (r->flags & PG_ANCHOR_ROWS_ONLY) && !r->ev_epi && !r->rows_valid)
+        return fail(PG_E_INVALID, "rows-only result: the low-resolution rows need pg_rows_epilogue first");
+    // window i: device byte offset of its contig's rows, then [start, end) in sampled rows
+    std::vector<uint64_t> se((size_t)nwin * 3);
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < nwin; ++i) {
+        if (contig[i] >= r->ad.size()) return fail(PG_E_INVALID, "window %u: contig %u out of range", i, contig[i]);
+        const AnchorDesc &a = r->ad[contig[i]];
+        const uint64_t nrows = step == 1 ? (uint64_t)a.nkmers : r->nrows100[contig[i]];
+        if (starts[i] > ends[i]) return fail(PG_E_INVALID, "window %u: start %llu past end %llu", i, (unsigned long long)starts[i],
+                                             (unsigned long long)ends[i]);
+        if (ends[i] > starts[i] && (nrows == 0 || ends[i] - 1 > (nrows - 1) / stride))
+            return fail(PG_E_INVALID, "window %u: sampled row %llu (x %u) past the %llu rows of contig %u", i,
+                        (unsigned long long)(ends[i] - 1), stride, (unsigned long long)nrows, contig[i]);
+        se[i] = step == 1 ? a.out_off : a.out100_off;
+        se[nwin + i] = starts[i];
+        se[2 * (size_t)nwin + i] = ends[i];
+        longest = std::max(longest, ends[i] - starts[i]);
+    }
+    if (nwin == 0) return PG_OK;
+    if (int e = use_device(r->ctx)) return e;
+    if (int e = join_result(r)) return e;
+    hipStream_t st = r->ctx->stream;
+    // pieces: about 32 K sampled rows each for the longest window, then doubled while the grid has fewer than 4096 blocks
+    // (a lone window of 32 M rows in 256 pieces leaves three quarters of the SIMDs' wave slots empty: 3.3 ms, in 2048
+    // pieces as below) and a piece keeps more than 4096 rows (it ends with up to N^2 / 2 atomics)
+    uint32_t pieces = (uint32_t)std::min<uint64_t>(2048, std::max<uint64_t>(1, longest / 32768));
+    while (pieces < 2048 && (uint64_t)nwin * pieces < 4096 && (uint64_t)pieces * 4096 < longest) pieces *= 2;
+    uint64_t *d_se = nullptr;
+    unsigned long long *d_out = nullptr;
+    const size_t nc = (size_t)nwin * N * N;
+    int rc = PG_OK;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_se), se.size() * 8);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), nc * 8);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se, se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, nc * 8, st);
+    if (e == hipSuccess)
+        e = launch_pair_counts(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nwin, pieces, d_se, d_se + nwin,
+                               d_se + 2 * (size_t)nwin, d_out);
+    if (e == hipSuccess) e = hipMemcpyAsync(pairs_out, d_out, nc * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_result_pair_counts: %s", hipGetErrorString(e));
+    // the kernel counts the pairs on and above the diagonal: the matrix is symmetric
+    for (size_t i = 0; rc == PG_OK && i < nwin; ++i) {
+        uint64_t *m = pairs_out + i * N * N;
+        for (uint32_t a = 0; a < N; ++a)
+            for (uint32_t b = a + 1; b < N; ++b) m[(size_t)b * N + a] = m[(size_t)a * N + b];
+    }
+    if (d_se) hipFree(d_se);
+    if (d_out) hipFree(d_out);
+    return rc;
+    PG_API_END
+}
+
 extern "C" int pg_result_contig_info(const pg_result *r, uint32_t idx, uint64_t *nkmers, uint64_t *nrows100,
                                      uint32_t *nbins, uint32_t *binlen) {
     PG_API_BEGIN

@@ -205,6 +205,13 @@ hipError_t launch_window_stats(hipStream_t st, uint32_t ngenomes, const uint8_t 
 hipError_t launch_bin_colsums(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, uint32_t nbins,
                               uint32_t pieces, const uint64_t *base, const uint64_t *starts, const uint64_t *ends,
                               const uint32_t *keep, uint32_t omit_fixed, unsigned long long *cs, unsigned long long *kept);
+// pair counts (pg_pairs.hip): window i = sampled rows [starts[i], ends[i]) of the rows at rows + base[i], as the bins above;
+// pairs ([nwin][N][N]) is zeroed by the caller and accumulated into: the entries on and above the diagonal — the caller
+// mirrors them into the lower triangle.  1 <= N <= PAIRS_MAX_GENOMES.
+constexpr uint32_t PAIRS_MAX_GENOMES = 512;
+hipError_t launch_pair_counts(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, uint32_t nwin,
+                              uint32_t pieces, const uint64_t *base, const uint64_t *starts, const uint64_t *ends,
+                              unsigned long long *pairs);
 hipError_t launch_rows_epilogue(hipStream_t st, uint32_t ngenomes, const AnchorDesc *ad, const uint32_t *tile_contig,
                                 uint32_t ntiles, const uint8_t *out1, uint8_t *out100, uint32_t *bins,
                                 unsigned long long *colsums, uint32_t flags, const uint2 *d_ranges = nullptr,

@@ -1,0 +1,171 @@
+// pg_pairs.hip — pair counts of a finished bitmap's rows ON THE GPU (gfx950): C[a][b] = rows of a window holding both genome
+// a's and genome b's bit, the one integer matrix the viewer's tree of the genomes over a region needs (panagram/view.py:
+// 751-764: create_tree runs linkage(bitmap.T, "ward", "euclidean"); diag(C) are the column sums, C[a][a] + C[b][b] - 2 C[a][b]
+// the squared Euclidean distance of two 0/1 columns).
+//
+// A window is a range [s, e) of SAMPLED rows of one contig, as in pg_bins.hip: sampled row j is row j * stride of the contig's
+// rows (bitmap.1 or the low-resolution bitmap, as inflated into a result).  Only the first N bits of a row count: the bits
+// past N in its last byte are masked off.
+//
+// grid = (windows, pieces, slices), 256 threads: piece p of a window takes its 256-row tiles p, p + pieces, ...
+//   transpose  a wave takes 64 sampled rows of the tile, one per lane; the ballot of bit c over the wave IS the 64-row word
+//              of column c.  Lane c % 64 keeps it, and after every 64 columns the wave stores one word per lane:
+//              tile[wave][c] in LDS, 4 words per column and tile, columns past N zero.
+//   pairs      the N x N matrix is cut into 4 x 4 blocks, and only the blocks on and above the diagonal are computed.  A thread
+//              owns blocks t, t + 256, t + 512 of its slice (PAIRS_ROUNDS = 3: the 528 blocks of N = 128 are one slice) with
+//              their 16 counters each in registers across all tiles of the piece: per tile and word it reads its 4 + 4
+//              column words (two 16-byte LDS reads each side) and adds popcount(col_a & col_b) for the 16 pairs.
+//              Wider rows have more blocks than 3 x 256: slice z of the grid takes blocks [768 z, 768 (z + 1)) and repeats
+//              the transpose for itself.  Two tile buffers, so one barrier per tile.
+//   flush      one 64-bit global atomic add per non-zero pair of the thread's blocks: the entries on and above the diagonal
+//              (and the few below it inside the diagonal blocks).  The caller mirrors them into the lower triangle.
+// A thread's counter is 32 bits wide: it never exceeds the sampled rows its block visits, which are rows of ONE contig,
+// and a contig's rows are counted in 32 bits (AnchorDesc::nkmers) — so it stays below 2^32; the sums across blocks are
+// 64-bit atomics.
+// N <= 128 (k_pair_counts<4>): a lane loads its row's words once, into registers, before the ballots; beyond, up to
+// PAIRS_MAX_GENOMES (k_pair_counts<0>), word by word.
+#include "pg_kernels.h"
+
+namespace pg {
+
+constexpr uint32_t PAIRS_TILE = 256;  // sampled rows per tile: one 64-row word per wave
+constexpr uint32_t PAIRS_ROUNDS = 3;  // 4 x 4 blocks per thread and slice
+
+// bytes [4d, min(4d + 4, nbytes)) of a row as a little-endian word (rows of whole words: one aligned load — a contig's rows
+// start on 16 bytes)
+__device__ __forceinline__ uint32_t pairs_row_word(const uint8_t *__restrict__ p, uint32_t d, uint32_t nbytes) {
+    if ((nbytes & 3u) == 0) return *reinterpret_cast<const uint32_t *>(p + 4 * d);
+    const uint32_t nb = min(4u, nbytes - 4 * d);
+    uint32_t v = 0;
+    for (uint32_t b = 0; b < nb; ++b) v |= (uint32_t)p[4 * d + b] << (8 * b);
+    return v;
+}
+
+__device__ __forceinline__ uint32_t pairs_valid_bits(uint32_t N, uint32_t d) {
+    const uint32_t ng = N - 32 * d;
+    return ng >= 32 ? 0xFFFFFFFFu : (1u << ng) - 1u;
+}
+
+// word d of the wave's 64 rows: the column word of bit b goes to lane b (d even) / 32 + b (d odd)
+__device__ __forceinline__ uint64_t pairs_ballot_word(uint32_t w, uint32_t d, uint32_t N, uint32_t lane, uint64_t mine) {
+    if (__ballot(w != 0) == 0) return mine;  // (wave-uniform: no bit in these 32 columns)
+    const uint32_t ng = min(32u, N - 32 * d), l0 = 32 * (d & 1);
+    // (unrolled by 8, not 32: the full unroll keeps 32 ballot masks live and spills SGPRs into VGPR lanes)
+#pragma unroll 8
+    for (uint32_t b = 0; b < 32; ++b) {
+        if (b < ng) {
+            const uint64_t m = __ballot((w >> b) & 1u);
+            mine = lane == l0 + b ? m : mine;
+        }
+    }
+    return mine;
+}
+
+template <uint32_t MAXW>
+__global__ __launch_bounds__(256) void k_pair_counts(uint32_t N, const uint8_t *__restrict__ rows, uint32_t stride,
+                                                     const uint64_t *__restrict__ base, const uint64_t *__restrict__ starts,
+                                                     const uint64_t *__restrict__ ends, unsigned long long *__restrict__ pairs_out) {
+    extern __shared__ __align__(16) uint64_t psm[];  // [2 buffers][4 waves][NC] column words
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t nbytes = (N + 7) / 8, ndw = (N + 31) / 32;
+    const uint32_t NC = (N + 63) & ~63u, NB = (N + 3) / 4, nblk = NB * (NB + 1) / 2;
+    // this thread's blocks: number t of the blocks on and above the diagonal, row by row -> (block row, block column)
+    uint32_t ca[PAIRS_ROUNDS], cb[PAIRS_ROUNDS];
+    bool have[PAIRS_ROUNDS];
+    uint32_t acc[PAIRS_ROUNDS][16];
+#pragma unroll
+    for (uint32_t r = 0; r < PAIRS_ROUNDS; ++r) {
+        const uint32_t t = (blockIdx.z * PAIRS_ROUNDS + r) * 256 + tid;
+        have[r] = t < nblk;
+        uint32_t a = 0, rem = have[r] ? t : 0;
+        while (rem >= NB - a) {
+            rem -= NB - a;
+            ++a;
+        }
+        ca[r] = 4 * a;
+        cb[r] = 4 * (a + rem);
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) acc[r][i] = 0;
+    }
+    const uint8_t *crow = rows + base[blockIdx.x];
+    const uint64_t s = starts[blockIdx.x], e = ends[blockIdx.x];
+    uint32_t buf = 0;
+    for (uint64_t g0 = s + (uint64_t)PAIRS_TILE * blockIdx.y; g0 < e; g0 += (uint64_t)PAIRS_TILE * gridDim.y, buf ^= 1) {
+        const uint64_t j = g0 + tid;
+        const bool act = j < e;
+        const uint8_t *p = crow + j * stride * nbytes;
+        uint64_t *tile = psm + (size_t)buf * 4 * NC;
+        uint64_t *mycols = tile + wave * NC;
+        if (MAXW) {
+            uint32_t w[MAXW ? MAXW : 1];
+#pragma unroll
+            for (uint32_t d = 0; d < (MAXW ? MAXW : 1); ++d)
+                w[d] = act && d < ndw ? pairs_row_word(p, d, nbytes) & pairs_valid_bits(N, d) : 0u;
+            uint64_t mine = 0;
+#pragma unroll
+            for (uint32_t d = 0; d < (MAXW ? MAXW : 1); ++d) {
+                if (d < ndw) mine = pairs_ballot_word(w[d], d, N, lane, mine);
+                if ((d & 1) && 32 * (d - 1) < NC) {
+                    mycols[32 * (d - 1) + lane] = mine;
+                    mine = 0;
+                }
+            }
+        } else {
+            for (uint32_t q = 0; 64 * q < NC; ++q) {
+                uint64_t mine = 0;
+                for (uint32_t d = 2 * q; d < min(2 * q + 2, ndw); ++d)
+                    mine = pairs_ballot_word(act ? pairs_row_word(p, d, nbytes) & pairs_valid_bits(N, d) : 0u, d, N, lane, mine);
+                mycols[64 * q + lane] = mine;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t r = 0; r < PAIRS_ROUNDS; ++r) {
+            if (!have[r]) continue;
+#pragma unroll
+            for (uint32_t wv = 0; wv < 4; ++wv) {
+                const ulonglong2 *pa = reinterpret_cast<const ulonglong2 *>(tile + wv * NC + ca[r]);
+                const ulonglong2 *pb = reinterpret_cast<const ulonglong2 *>(tile + wv * NC + cb[r]);
+                const ulonglong2 a01 = pa[0], a23 = pa[1], b01 = pb[0], b23 = pb[1];
+                const uint64_t A[4] = {a01.x, a01.y, a23.x, a23.y}, B[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+                for (uint32_t i = 0; i < 4; ++i)
+#pragma unroll
+                    for (uint32_t k = 0; k < 4; ++k) acc[r][4 * i + k] += (uint32_t)__popcll(A[i] & B[k]);
+            }
+        }
+        // (no second barrier: the next tile goes to the other buffer, and this one is written again only behind the next
+        // tile's barrier, which every wave passes after these reads)
+    }
+    unsigned long long *out = pairs_out + (uint64_t)blockIdx.x * N * N;
+#pragma unroll
+    for (uint32_t r = 0; r < PAIRS_ROUNDS; ++r) {
+        if (!have[r]) continue;
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i)
+#pragma unroll
+            for (uint32_t k = 0; k < 4; ++k) {
+                const uint32_t a = ca[r] + i, b = cb[r] + k, c = acc[r][4 * i + k];
+                if (a < N && b < N && c) atomicAdd(&out[(uint64_t)a * N + b], (unsigned long long)c);
+            }
+    }
+}
+
+hipError_t launch_pair_counts(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, uint32_t nwin,
+                              uint32_t pieces, const uint64_t *base, const uint64_t *starts, const uint64_t *ends,
+                              unsigned long long *pairs) {
+    if (nwin == 0) return hipSuccess;
+    if (ngenomes < 1 || ngenomes > PAIRS_MAX_GENOMES) return hipErrorInvalidValue;
+    const uint32_t NC = (ngenomes + 63) & ~63u, NB = (ngenomes + 3) / 4, nblk = NB * (NB + 1) / 2;
+    const uint32_t slices = (nblk + PAIRS_ROUNDS * 256 - 1) / (PAIRS_ROUNDS * 256);
+    const size_t lds = (size_t)2 * 4 * NC * 8;
+    if (ngenomes <= 128)
+        hipLaunchKernelGGL(k_pair_counts<4>, dim3(nwin, pieces, slices), dim3(256), lds, st, ngenomes, rows, stride, base, starts,
+                           ends, pairs);
+    else
+        hipLaunchKernelGGL(k_pair_counts<0>, dim3(nwin, pieces, slices), dim3(256), lds, st, ngenomes, rows, stride, base, starts,
+                           ends, pairs);
+    return hipGetLastError();
+}
+
+}  // namespace pg

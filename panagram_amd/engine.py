@@ -840,6 +840,21 @@ class AnchorResult:
                                               _ptr(kw), 1 if omit_fixed else 0, _ptr(cs), _ptr(kept)))
         return cs, kept
 
+    def pair_counts(self, contigs, starts, ends, step: int = 1, stride: int = 1) -> np.ndarray:
+        """[nwin, N, N] uint64: entry (i, a, b) = sampled rows [starts[i], ends[i]) of contig contigs[i]'s bitmap.<step> rows
+        holding both genome a's and genome b's bit, sampled row j = row j * stride (k_pair_counts, one launch).  The full
+        symmetric matrix; its diagonal are the column sums."""
+        contigs = np.ascontiguousarray(contigs, np.uint32)
+        starts = np.ascontiguousarray(starts, np.uint64)
+        ends = np.ascontiguousarray(ends, np.uint64)
+        n, N = len(starts), self.ngenomes
+        if len(contigs) != n or len(ends) != n:
+            raise ValueError("contigs, starts and ends need one entry per window")
+        out = np.zeros((n, N, N), np.uint64)
+        check(self._lib.pg_result_pair_counts(self._h, int(step), int(stride), n, _ptr(contigs), _ptr(starts), _ptr(ends),
+                                              _ptr(out)))
+        return out
+
     def write_bgzf(self, step: int, gz_path: str, gzi_path: Optional[str] = None, level: int = 6,
                    threads: int = 1, first_contig: int = 0, ncontigs: Optional[int] = None) -> None:
         """Stream the bitmap.<step> payload of contigs [first_contig, first_contig + ncontigs) (default:

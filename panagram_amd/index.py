@@ -268,6 +268,73 @@ class UMAP:
     bin_size: int = 100000
 
 
+# ---------------------------------------------------------------------------
+# the tree of the genomes over a region, from their pair counts (view.py:576-596, 751-764)
+# ---------------------------------------------------------------------------
+def linkage_newick(Z: np.ndarray, names: Sequence[str]) -> str:
+    """A scipy linkage matrix as Newick text in the convention of the viewer's trees (view.py:576-596): leaves ``name:%.2f``,
+    a branch's length its parent's height minus its own, a node's second child written before its first, the root closed
+    with ``);``.  Built bottom-up over the rows of ``Z`` (no recursion: a tree of one long chain is as deep as N)."""
+    n = len(names)
+    if n == 1:
+        return "(%s:%.2f);" % (names[0], 0.0)
+    text, height = {i: str(names[i]) for i in range(n)}, {i: 0.0 for i in range(n)}
+    for k, (a, b, h, _) in enumerate(np.asarray(Z, np.float64)):
+        a, b = int(a), int(b)
+        text[n + k] = "(%s:%.2f,%s:%.2f)" % (text.pop(b), h - height[b], text.pop(a), h - height[a])
+        height[n + k] = float(h)
+    return text[2 * n - 2] + ";"
+
+
+def linkage_order(Z: np.ndarray, n: int) -> List[int]:
+    """leaf numbers in dendrogram order (a node's first child before its second: scipy's ``leaves_list``)"""
+    out, todo = [], [2 * n - 2] if n > 1 else [0]
+    while todo:
+        i = todo.pop()
+        if i < n:
+            out.append(i)
+        else:
+            todo += [int(Z[i - n, 1]), int(Z[i - n, 0])]
+    return out
+
+
+@dataclasses.dataclass
+class RegionTree:
+    """What ``Index.region_tree`` returns.  ``counts``: the pair counts C (N x N frame); ``distance``: the Hamming distances
+    H = C[a][a] + C[b][b] - 2 C[a][b] (integers; sqrt(H) is the Euclidean distance of the two 0/1 columns); ``linkage``:
+    scipy's Ward linkage of sqrt(H), equal to ``linkage(bitmap.T, "ward", "euclidean")``; ``order``: the leaf names in
+    dendrogram order; ``shared_pct``: diag(C) / max(diag(C)) * 100, the viewer's kmer_num (zeros when no row holds a bit);
+    ``newick``: the tree as text."""
+    counts: pd.DataFrame
+    distance: pd.DataFrame
+    linkage: np.ndarray
+    order: List[str]
+    shared_pct: pd.Series
+    newick: str
+
+    @classmethod
+    def from_counts(cls, counts, names: Sequence[str]) -> "RegionTree":
+        names = list(names)
+        n = len(names)
+        C = np.asarray(counts, np.int64).reshape(n, n)
+        d = np.diag(C)
+        H = d[:, None] + d[None, :] - 2 * C
+        if n > 1:
+            try:
+                from scipy.cluster.hierarchy import linkage
+            except ImportError as e:
+                raise ImportError("region_tree needs scipy for the Ward linkage (pair_counts does not)") from e
+            Z = linkage(np.sqrt(H[np.triu_indices(n, 1)].astype(np.float64)), method="ward")
+        else:
+            Z = np.zeros((0, 4))
+        idx = pd.Index(names)
+        top = int(d.max()) if n else 0
+        pct = d / top * 100.0 if top > 0 else np.zeros(n)
+        return cls(counts=pd.DataFrame(C, index=idx, columns=idx), distance=pd.DataFrame(H, index=idx, columns=idx), linkage=Z,
+                   order=[names[i] for i in linkage_order(Z, n)], shared_pct=pd.Series(pct, index=idx),
+                   newick=linkage_newick(Z, names))
+
+
 @dataclasses.dataclass
 class Index:
     """Anchor k-mer bitvectors to reference FASTA files to create the pan-kmer bitmap."""
@@ -1157,6 +1224,21 @@ class Index:
     def query_bitmap(self, genome, chrom, start=None, end=None, step=1):
         return self.genomes[genome].query(chrom, start, end, step)
 
+    def pair_counts(self, genome, chrom=None, start=None, end=None, step=1) -> pd.DataFrame:
+        """N x N pair counts of the genomes over the rows ``query_bitmap(genome, chrom, start, end, step)`` returns"""
+        return self.genomes[genome].pair_counts(chrom, start, end, step)
+
+    def region_tree(self, genome, chrom, start=None, end=None, step=None) -> "RegionTree":
+        """The tree of the genomes over a region, as the viewer draws it (view.py:751-764: create_tree) — but from the pair
+        counts of EVERY row of the region at ``step`` (default: the low-resolution step), not from a random sample of
+        50 000 rows, so the same region gives the same tree.  ``chrom=None``: the whole genome."""
+        step = int(self.lowres_step) if step is None else int(step)
+        counts, nrows = self.genomes[genome]._pair_counts(chrom, start, end, step)
+        if nrows == 0:
+            where = "the whole genome" if chrom is None else f"{chrom}:{0 if start is None else start}-{'' if end is None else end}"
+            raise ValueError(f"{genome}: no rows in {where} at step {step}")
+        return RegionTree.from_counts(counts, list(self.genome_names))
+
     def close(self):
         for nm in list(self._seqsets):
             self.drop_seqset(nm)
@@ -1641,6 +1723,68 @@ class Genome:
         with np.errstate(invalid="ignore", divide="ignore"):
             v = v / v.max(axis=1, keepdims=True)
         return pd.DataFrame(v.T, index=names, columns=pd.Index(np.asarray(starts, np.int64)))
+
+    # ---- TREE: pair counts of the genomes over a region (view.py:751-764: create_tree) ----
+    def _rows_region(self, bstep: int, row0: int, nrows: int) -> "engine.AnchorResult":
+        """a rows result of ONE pseudo-contig: rows [row0, row0 + nrows) of bitmap.<bstep>.gz's payload, inflated on the GPU"""
+        # (a container derives its low-resolution rows from its contig's length: the shortest contig with nrows of them)
+        nk = nrows if bstep == 1 else (nrows - 1) * bstep + 1
+        return engine.AnchorResult.from_bgzf(self.index.context, int(self.index.k), self.ngenomes, [nk], self.bitmap_gz_fname(bstep),
+                                             self.bitmap_gzi_fname(bstep), file_row0=row0, step=bstep,
+                                             lowres_step=int(self.index.lowres_step))
+
+    def _region_rows(self, chrom: str, start, end, step: int):
+        """(bstep, stride, first payload row, rows) of what ``query(chrom, start, end, step)`` reads: ``rows`` rows of
+        bitmap.<bstep>.gz from ``first``, of which it keeps every ``stride``-th"""
+        bstep = max(s for s in self.steps if step % s == 0)
+        start = 0 if start is None else int(start)
+        end = self.seq_len(chrom) if end is None else int(end)
+        row0 = int(self.offsets.loc[chrom, bstep]) + start // bstep
+        file_rows = int(np.ceil(self.sizes / bstep).sum())  # (query reads to the payload's end at most)
+        nrows = min((end - 1 - start) // bstep + 1, file_rows - row0) if end > start and start >= 0 else 0
+        return bstep, step // bstep, row0, max(0, nrows)
+
+    def _pair_counts(self, chrom=None, start=None, end=None, step: int = 1):
+        """(N x N int64 pair counts, sampled rows they were taken over)"""
+        step = int(step)
+        if step < 1:
+            raise ValueError(f"step must be positive, got {step}")
+        if self.chrs is None:
+            self.load_chrs()
+        if chrom is None and (start is not None or end is not None):
+            raise ValueError("start and end need a chromosome")
+        for c in ([] if chrom is None else [chrom]):
+            if c not in self.chrs.index:
+                raise KeyError(f"{self.name}: no chromosome {c!r}")
+        N = self.ngenomes
+        total, seen = np.zeros((N, N), np.int64), 0
+        for c in (list(self.chrs.index) if chrom is None else [chrom]):
+            bstep, stride, row0, nrows = self._region_rows(c, start, end, step)
+            # pieces of at most similarity_budget bytes of HBM (a container of low-resolution rows holds, zeroed, the
+            # full-resolution rows they span); a piece starts at the first row of the region's sampling phase inside it
+            per = max(1, int(self.similarity_budget) // (self.nbytes * bstep))
+            for p0 in range(0, nrows, per):
+                p1 = min(p0 + per, nrows)
+                first = -(-p0 // stride) * stride
+                if first >= p1:
+                    continue
+                ns = (p1 - first - 1) // stride + 1
+                res = self._rows_region(bstep, row0 + first, p1 - first)
+                try:
+                    total += res.pair_counts([0], [0], [ns], step=bstep, stride=stride)[0].astype(np.int64)
+                finally:
+                    res.close()
+                seen += ns
+        return total, seen
+
+    def pair_counts(self, chrom=None, start=None, end=None, step: int = 1) -> pd.DataFrame:
+        """N x N integers, indexed and labelled by the genome names: entry (a, b) = rows of ``query(chrom, start, end, step)``
+        holding both genomes' bits (``B.T @ B`` of that frame) — every such row, none of them read back to the host: the
+        region's rows are inflated into HBM and reduced by k_pair_counts, in consecutive pieces of at most
+        ``similarity_budget`` bytes.  ``chrom=None``: the sum over all chromosomes.  The diagonal are the column sums."""
+        total, _ = self._pair_counts(chrom, start, end, step)
+        names = pd.Index(self.index.genome_names)
+        return pd.DataFrame(total, index=names, columns=names)
 
     def _tabix(self, typ: str):
         from . import annotation as an

@@ -392,6 +392,20 @@ int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, uint32_t nbin
  * beyond).  One launch for all windows (k_pair_counts); synchronises. */
 int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
                           const uint64_t *starts, const uint64_t *ends, uint64_t *pairs_out);
+/* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
+ * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
+ * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a
+ * device pointer works too: the copies are hipMemcpyDefault); seg holds nseg + 1 ascending row offsets from 0 to n, and a row
+ * of segment s searches the rows [seg[s], seg[s+1]) only, itself included — every chromosome of an anchor in one launch
+ * (seg NULL: one segment of all n rows).  idx_out / d2_out are n x k: the global row numbers and distances of each row's k
+ * nearest rows, sorted by (d2, row number) ascending — equal distances: the lower row number first; the row itself
+ * appears at distance 0 under the same rule — padded with (-1, +inf) where a segment has fewer than k rows.
+ * d2(i, j) is EXACTLY the float32 sum over g = 0 .. ncols-1, in that order, of (X[i][g] - X[j][g])^2 with every subtract,
+ * multiply and add rounded to float32 (no fused multiply-add).  X must hold no NaN.  1 <= k <= 32, 1 <= ncols <= 4096,
+ * n < 2^31: PG_E_INVALID otherwise, before anything is launched.  Staged through the context's stream (k_knn_rows);
+ * synchronises. */
+int pg_knn_rows(pg_ctx *ctx, const float *X, uint64_t n, uint32_t ncols, uint32_t k, const uint64_t *seg, uint32_t nseg,
+                int32_t *idx_out, float *d2_out);
 /* stream the whole bitmap.1 (step 1) or bitmap.100 (step 100) payload of the result — every
  * contig, in order — from HBM into a BGZF file + .gzi index (gzi_path may be NULL): D2H through
  * pinned double buffers on a private stream overlapped with multi-threaded deflate.  Replaces

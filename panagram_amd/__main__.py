@@ -1,7 +1,8 @@
 """CLI surface kept from the reference (`panagram index <samples.tsv> -k K [-o prefix] [-c cores]
 [--prepare]`, panagram/__main__.py:154-194, index.py:90-123) plus the process-level seam of
 cpp/run_anchor (`run_anchor <ngenomes> <root> [<name> <fasta>]...`), and what the reference only does inside its viewer:
-`tree <index_dir> <genome> <chrom> [start] [end] [step]` prints the Newick tree of the genomes over a region."""
+`tree <index_dir> <genome> <chrom> [start] [end] [step]` prints the Newick tree of the genomes over a region; and
+`umaps <index_dir> [genome ...]` writes chrom_umaps.csv and genome_umap.csv (index.py:1107-1156) for an existing index."""
 import argparse
 import os
 import sys
@@ -27,6 +28,7 @@ def main(argv=None):
     ix.add_argument("--kmc.use_existing", dest="use_existing", action="store_true")
     ix.add_argument("--genome_dist", action="store_true", help="also write genome_dist.tsv (MinHash distances, for panagram view)")
     ix.add_argument("--annotate", action="store_true", help="also write the gene / annotation tracks of annotated anchor genomes")
+    ix.add_argument("--umaps", action="store_true", help="also write chrom_umaps.csv and genome_umap.csv of the anchor genomes")
     ds = sub.add_parser("dist", help="write genome_dist.tsv of an existing index (MinHash sketches on the GPU)")
     ds.add_argument("index_dir")
     ds.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
@@ -47,6 +49,11 @@ def main(argv=None):
     tr.add_argument("--whole", action="store_true", help="the whole genome in place of a chromosome")
     tr.add_argument("--matrix", metavar="FILE", default=None, help="also write the pair counts as a tab-separated table")
     tr.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
+                                      "the bins on the GPU, layout and clusters on the host")
+    um.add_argument("index_dir")
+    um.add_argument("genomes", nargs="*", help="default: every anchor genome")
+    um.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     it = sub.add_parser("intros", help="call introgressions from k-mer similarity binned on the GPU: `intros call [flags]` "
                                        "(call_introgressions.py's flags) or `intros <config.yaml> [--sweep]`", add_help=False)
     it.add_argument("args", nargs=argparse.REMAINDER)
@@ -58,7 +65,7 @@ def main(argv=None):
         from .index import KMC, Index
         idx = Index(a.input, prefix=a.prefix, k=a.k, cores=a.cores, prepare=a.prepare,
                     anchor_genomes=a.anchor_genomes, device=a.device, export_kmc=a.export_kmc,
-                    kmc=KMC(use_existing=a.use_existing), genome_dist=a.genome_dist, annotate=a.annotate)
+                    kmc=KMC(use_existing=a.use_existing), genome_dist=a.genome_dist, annotate=a.annotate, umaps=a.umaps)
         idx.run()
         return 0
     if a.cmd == "dist":
@@ -74,6 +81,19 @@ def main(argv=None):
         idx = Index(a.index_dir, mode="r", device=a.device)
         try:
             idx[a.genome].run_annotate(a.gff_file, nogene=a.nogene)
+        finally:
+            idx.close()
+        return 0
+    if a.cmd == "umaps":
+        from .index import Index
+        idx = Index(a.index_dir, mode="r", device=a.device)
+        try:
+            names = a.genomes or [n for n in idx.genome_names if idx[n].anchored]
+            for n in names:
+                if n not in idx.genomes or not idx[n].anchored:
+                    ap.error(f"umaps: {n!r} is not an anchor genome of {a.index_dir}")
+            for n in names:
+                print("Wrote", *idx[n].write_umaps())
         finally:
             idx.close()
         return 0

@@ -3464,6 +3464,67 @@ extern "C" int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, ui
     PG_API_END
 }
 
+// exact k nearest neighbours among the rows of a host matrix (the neighbour graph of index.py:1131-1137's umap.UMAP): the
+// rows of every segment are cut into tiles of query rows, one block each, and all segments share one launch
+extern "C" int pg_knn_rows(pg_ctx *ctx, const float *X, uint64_t n, uint32_t ncols, uint32_t k, const uint64_t *seg,
+                           uint32_t nseg, int32_t *idx_out, float *d2_out) {
+    PG_API_BEGIN
+    if (k < 1 || k > KNN_MAX_K) return fail(PG_E_INVALID, "pg_knn_rows: k = %u (1 to %u neighbours)", k, KNN_MAX_K);
+    if (ncols < 1 || ncols > KNN_MAX_COLS) return fail(PG_E_INVALID, "pg_knn_rows: %u columns (1 to %u)", ncols, KNN_MAX_COLS);
+    if (!ctx || (n && (!X || !idx_out || !d2_out))) return fail(PG_E_INVALID, "pg_knn_rows: NULL argument");
+    if (n > 0x7FFFFFFFull) return fail(PG_E_INVALID, "pg_knn_rows: %llu rows (row numbers are 31 bits)", (unsigned long long)n);
+    const uint64_t whole[2] = {0, n};
+    if (!seg) {
+        seg = whole;
+        nseg = 1;
+    }
+    if (nseg > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_knn_rows: %u segments", nseg);
+    if (seg[0] != 0 || seg[nseg] != n)
+        return fail(PG_E_INVALID, "pg_knn_rows: the segments must run from row 0 to row %llu, not %llu to %llu",
+                    (unsigned long long)n, (unsigned long long)seg[0], (unsigned long long)seg[nseg]);
+    for (uint32_t s = 0; s < nseg; ++s)
+        if (seg[s] > seg[s + 1])
+            return fail(PG_E_INVALID, "pg_knn_rows: segment offsets not ascending (%llu before %llu at segment %u)",
+                        (unsigned long long)seg[s], (unsigned long long)seg[s + 1], s);
+    if (n == 0) return PG_OK;
+    // tiles of 256 query rows; of 64 — one wave per block — while 256 would leave the grid short of two blocks per CU
+    uint64_t t256 = 0;
+    for (uint32_t s = 0; s < nseg; ++s) t256 += (seg[s + 1] - seg[s] + 255) / 256;
+    const uint32_t threads = t256 < 512 ? 64 : 256;
+    std::vector<uint32_t> tiles;
+    for (uint32_t s = 0; s < nseg; ++s)
+        for (uint64_t r = seg[s]; r < seg[s + 1]; r += threads) {
+            const uint32_t t[4] = {(uint32_t)r, (uint32_t)std::min<uint64_t>(threads, seg[s + 1] - r), (uint32_t)seg[s],
+                                   (uint32_t)seg[s + 1]};
+            tiles.insert(tiles.end(), t, t + 4);
+        }
+    const uint32_t ntiles = (uint32_t)(tiles.size() / 4);
+    if (int e = use_device(ctx)) return e;
+    hipStream_t st = ctx->stream;
+    float *d_x = nullptr, *d_d2 = nullptr;
+    int32_t *d_idx = nullptr;
+    uint32_t *d_tiles = nullptr;
+    const size_t xb = (size_t)n * ncols * 4, ob = (size_t)n * k * 4;
+    int rc = PG_OK;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_x), xb);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_idx), ob);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_d2), ob);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tiles), tiles.size() * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_x, X, xb, hipMemcpyDefault, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch_knn_rows(st, d_x, ncols, k, d_tiles, ntiles, threads, d_idx, d_d2);
+    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, d_idx, ob, hipMemcpyDefault, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d2_out, d_d2, ob, hipMemcpyDefault, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_knn_rows: %s", hipGetErrorString(e));
+    if (d_x) hipFree(d_x);
+    if (d_idx) hipFree(d_idx);
+    if (d_d2) hipFree(d_d2);
+    if (d_tiles) hipFree(d_tiles);
+    return rc;
+    PG_API_END
+}
+
 extern "C" int pg_result_contig_info(const pg_result *r, uint32_t idx, uint64_t *nkmers, uint64_t *nrows100,
                                      uint32_t *nbins, uint32_t *binlen) {
     PG_API_BEGIN

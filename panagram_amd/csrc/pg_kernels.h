@@ -212,6 +212,14 @@ constexpr uint32_t PAIRS_MAX_GENOMES = 512;
 hipError_t launch_pair_counts(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, uint32_t nwin,
                               uint32_t pieces, const uint64_t *base, const uint64_t *starts, const uint64_t *ends,
                               unsigned long long *pairs);
+// exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
+// lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
+// threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the
+// segment has fewer than K rows.  1 <= K <= KNN_MAX_K, 1 <= D <= KNN_MAX_COLS; rows of up to KNN_REG_COLS columns are held
+// in registers.
+constexpr uint32_t KNN_MAX_K = 32, KNN_MAX_COLS = 4096, KNN_REG_COLS = 128;
+hipError_t launch_knn_rows(hipStream_t st, const float *X, uint32_t D, uint32_t K, const uint32_t *tiles, uint32_t ntiles,
+                           uint32_t threads, int32_t *idx, float *d2);
 hipError_t launch_rows_epilogue(hipStream_t st, uint32_t ngenomes, const AnchorDesc *ad, const uint32_t *tile_contig,
                                 uint32_t ntiles, const uint8_t *out1, uint8_t *out100, uint32_t *bins,
                                 unsigned long long *colsums, uint32_t flags, const uint2 *d_ranges = nullptr,

@@ -443,6 +443,24 @@ def minhash_distances(sketches: Sequence[np.ndarray], bases: Optional[Sequence[i
     return dist, pval, common, denom
 
 
+def knn_rows(ctx: Context, X, k: int, seg=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(idx [n, k] int32, d2 [n, k] float32): the k nearest rows of every row of the n x D float32 matrix ``X`` under squared
+    Euclidean distance, exact (k_knn_rows, one launch).  ``seg``: ascending row offsets from 0 to n — a row searches only the
+    rows of its own segment, itself included (None: one segment).  Entries are sorted by (d2, row number); d2 is the float32
+    sum over the columns in order, each subtract, multiply and add rounded; (-1, inf) pads a segment of fewer than k rows."""
+    X = np.ascontiguousarray(X, np.float32)
+    if X.ndim != 2:
+        raise ValueError("X must be a matrix")
+    n, D = X.shape
+    s = None if seg is None else np.ascontiguousarray(seg, np.uint64)
+    if s is not None and (s.ndim != 1 or len(s) < 1):
+        raise ValueError("seg needs at least one offset")
+    idx = np.empty((n, int(k) if 0 < int(k) <= 32 else 0), np.int32)
+    d2 = np.empty(idx.shape, np.float32)
+    check(ctx._lib.pg_knn_rows(ctx._h, _ptr(X), n, D, int(k), _ptr(s), 0 if s is None else len(s) - 1, _ptr(idx), _ptr(d2)))
+    return idx, d2
+
+
 class PanTable(_Owner):
     """GPU-resident k-mer -> genome-mask table (replaces kmc/bitvec{i})."""
 

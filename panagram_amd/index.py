@@ -25,7 +25,12 @@ Output tree (identical to the reference's):
                                    (opt-in: ``annotate=True`` / ``index --annotate`` / the ``annotate`` command:
                                     ``Genome.run_annotate``, index.py:971-1010; bitmap.1.gz inflated on the GPU)
 
-Out of scope here: UMAPs, mash's own .msh files, the viewer.
+    <prefix>/anchor/<name>/chrom_umaps.csv genome_umap.csv
+                                   (opt-in: ``umaps=True`` / ``index --umaps`` / the ``umaps`` command: ``Genome.write_umaps``,
+                                    index.py:1107-1156; exact neighbours on the GPU, the layout restated in ``umap.py`` —
+                                    the files' layout is the reference's, umap-learn's numbers are not claimed)
+
+Out of scope here: mash's own .msh files, the viewer.
 """
 from __future__ import annotations
 
@@ -376,8 +381,11 @@ class Index:
     # run Genome.run_annotate() for every annotated anchor genome this process completes (off by default: the default tree
     # stays as it was)
     annotate: bool = False
+    # run Genome.write_umaps() for every anchor genome this process completes (off by default: the default tree stays as it was)
+    umaps: bool = False
 
-    _EXTRA = ("device", "export_kmc", "rank", "world", "shard", "genome_blocks", "filtered_table", "genome_dist", "annotate")
+    _EXTRA = ("device", "export_kmc", "rank", "world", "shard", "genome_blocks", "filtered_table", "genome_dist", "annotate",
+              "umaps")
     # keys of config.yaml that describe one invocation, not the index: not taken over when a directory is re-opened
     # (`prepare` is written for schema compatibility, but a later `index <dir>` run must not stop at "Prepared")
     _NOT_IN_CONFIG = ("input", "mode", "prefix", "prepare")
@@ -980,6 +988,10 @@ class Index:
                 for name in list(self._completed):
                     if self.genomes[name].annotated:
                         self.genomes[name].run_annotate()
+                self.close()
+            if self.umaps:  # (as above: by the process that completed the genome's files)
+                for name in list(self._completed):
+                    self.genomes[name].write_umaps()
                 self.close()
             if self.genome_dist and self.rank == 0:  # (one writer in a multi-rank run)
                 self.write_genome_dist()
@@ -1785,6 +1797,52 @@ class Genome:
         total, _ = self._pair_counts(chrom, start, end, step)
         names = pd.Index(self.index.genome_names)
         return pd.DataFrame(total, index=names, columns=names)
+
+    # ---- UMAPS: chrom_umaps.csv and genome_umap.csv (index.py:1100-1167) ----
+    @property
+    def chrom_umaps_filename(self):
+        return os.path.join(self.prefix, "chrom_umaps.csv")
+
+    @property
+    def genome_umap_filename(self):
+        return os.path.join(self.prefix, "genome_umap.csv")
+
+    def write_umaps(self) -> Tuple[str, str]:
+        """Write ``chrom_umaps.csv`` — every chromosome's bins of ``chrom_umap.bin_size`` embedded on their own, ``chrom``
+        as the index — and ``genome_umap.csv`` — all bins of ``genome_umap.bin_size`` in one embedding, no index — both with
+        the columns chrom, start, end, umap1, umap2, cluster (index.py:1107-1129).  The bins' pair-count rows come from
+        ``kmer_similarity_bins``; their exact nearest neighbours from k_knn_rows, all chromosomes in ONE segmented launch;
+        graph, layout and clusters from ``umap.py`` on the host (its docstring says what is claimed of them)."""
+        from . import umap
+        ix = self.index
+        if self.chrs is None:
+            self.load_chrs()
+        cu, gu = ix.chrom_umap, ix.genome_umap
+        frame, X = umap.paircount_matrix(self, cu.bin_size)
+        c = frame["chrom"].to_numpy()
+        seg = np.concatenate([[0], np.flatnonzero(c[1:] != c[:-1]) + 1, [len(c)]]).astype(np.int64)  # (a chromosome's bins are consecutive rows)
+        k = min(int(cu.neighbors), int(np.diff(seg).max()) - 1)
+        idx = d2 = None
+        if k >= 2:
+            idx, d2 = engine.knn_rows(ix.context, X, k, seg)
+        parts = []
+        for lo, hi in zip(seg[:-1], seg[1:]):
+            knn = None if idx is None else (idx[lo:hi] - np.int32(lo), d2[lo:hi])
+            parts.append(umap.run_umap(X[lo:hi], frame.iloc[lo:hi], cu, knn=knn, name=self.name))
+        self.chrom_umaps = (pd.concat(parts) if parts else pd.DataFrame(columns=umap.COLUMNS)).set_index("chrom")
+        ix._write_atomically(self.chrom_umaps_filename, lambda tmp: self.chrom_umaps.to_csv(tmp))
+        if int(gu.bin_size) != int(cu.bin_size):
+            frame, X = umap.paircount_matrix(self, gu.bin_size)
+        self.genome_umap = umap.run_umap(X, frame, gu, ctx=ix.context, name=self.name)
+        ix._write_atomically(self.genome_umap_filename, lambda tmp: self.genome_umap.to_csv(tmp, index=False))
+        return self.chrom_umaps_filename, self.genome_umap_filename
+
+    def load_umaps(self) -> None:
+        """``chrom_umaps`` (indexed by chrom) and ``genome_umap`` as the viewer reads them (index.py:1158-1167); None where the
+        file is missing"""
+        self.chrom_umaps = (pd.read_csv(self.chrom_umaps_filename, index_col="chrom")
+                            if os.path.exists(self.chrom_umaps_filename) else None)
+        self.genome_umap = pd.read_csv(self.genome_umap_filename) if os.path.exists(self.genome_umap_filename) else None
 
     def _tabix(self, typ: str):
         from . import annotation as an

@@ -195,6 +195,55 @@ struct pg_result {
 };
 static constexpr size_t EV_RING = 128;
 
+// Scratch: what lives for one call of one entry point belongs to a scope and goes on every way out of it, an
+// exception's included (the firewall of pg_guard.h turns that into an error code; nothing may leak behind it).  What
+// outlives the call belongs to a handle above and is freed by its *_free / *_destroy.  A stream is declared AFTER the
+// buffers and events it uses: it goes first, and drains before they do.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    ~DevBuf() {
+        if (p) hipFree(p);
+    }
+    hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T)); }
+    T *get() const { return p; }
+};
+template <class T>
+struct PinBuf {
+    T *p = nullptr;
+    PinBuf() = default;
+    PinBuf(PinBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    ~PinBuf() {
+        if (p) hipHostFree(p);
+    }
+    hipError_t alloc(size_t count, unsigned flags) { return hipHostMalloc(reinterpret_cast<void **>(&p), count * sizeof(T), flags); }
+    T *get() const { return p; }
+};
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+    ~Stream() {
+        if (!s) return;
+        hipStreamSynchronize(s);
+        hipStreamDestroy(s);
+    }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    hipStream_t get() const { return s; }
+};
+struct Event {
+    hipEvent_t ev = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    ~Event() {
+        if (ev) hipEventDestroy(ev);
+    }
+    hipError_t create(unsigned flags) { return hipEventCreateWithFlags(&ev, flags); }
+    hipEvent_t get() const { return ev; }
+};
+
 static constexpr uint32_t MAX_PROBE = 512;  // lines an insert may walk before the table is grown
 static constexpr double GROW_AT = 0.55;     // grow when keys > GROW_AT * slots
 #ifndef PG_INLINE_LAYOUT
@@ -205,6 +254,42 @@ static constexpr double HARD_LOAD = 0.85;   // worst-case guard before a batch
 
 static int use_device(const pg_ctx *c) {
     HIP_TRY(hipSetDevice(c->device));
+    return PG_OK;
+}
+
+// Checks shared by the entry points that read a result's rows: one wording each, whoever asks.
+static int check_step(const pg_result *r, int step) {
+    if (step != 1 && step != 100 && (uint32_t)step != r->lowres_step)
+        return fail(PG_E_INVALID, "step must be 1 or the result's low-resolution step (%u; 100 is accepted as its alias)", r->lowres_step);
+    return PG_OK;
+}
+static int check_rows_readable(const pg_result *r, int step) {
+    if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
+    if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
+    if (step != 1 && (r->flags & PG_ANCHOR_ROWS_ONLY) && !r->ev_epi && !r->rows_valid)
+        return fail(PG_E_INVALID, "rows-only result: the low-resolution rows need pg_rows_epilogue first");
+    return PG_OK;
+}
+// n windows ("bin", "window": the noun of the messages) of sampled rows, refused unless each lies within its contig ->
+// se[3 * n]: device byte offset of the contig's rows, then [start, end) in sampled rows; *longest: the longest of them
+static int gather_windows(const pg_result *r, int step, uint32_t stride, uint32_t n, const uint32_t *contig, const uint64_t *starts,
+                          const uint64_t *ends, const char *noun, std::vector<uint64_t> &se, uint64_t *longest) {
+    se.assign((size_t)n * 3, 0);
+    *longest = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (contig[i] >= r->ad.size()) return fail(PG_E_INVALID, "%s %u: contig %u out of range", noun, i, contig[i]);
+        const AnchorDesc &a = r->ad[contig[i]];
+        const uint64_t nrows = step == 1 ? (uint64_t)a.nkmers : r->nrows100[contig[i]];
+        if (starts[i] > ends[i]) return fail(PG_E_INVALID, "%s %u: start %llu past end %llu", noun, i, (unsigned long long)starts[i],
+                                             (unsigned long long)ends[i]);
+        if (ends[i] > starts[i] && (nrows == 0 || ends[i] - 1 > (nrows - 1) / stride))
+            return fail(PG_E_INVALID, "%s %u: sampled row %llu (x %u) past the %llu rows of contig %u", noun, i,
+                        (unsigned long long)(ends[i] - 1), stride, (unsigned long long)nrows, contig[i]);
+        se[i] = step == 1 ? a.out_off : a.out100_off;
+        se[n + i] = starts[i];
+        se[2 * (size_t)n + i] = ends[i];
+        *longest = std::max(*longest, ends[i] - starts[i]);
+    }
     return PG_OK;
 }
 
@@ -994,22 +1079,17 @@ extern "C" int pg_table_insert_keys(pg_table *t, int db_idx, const uint64_t *key
     if (n == 0) return PG_OK;
     if (int r = use_device(t->ctx)) return r;
     TABLE_WRITER(t);
-    uint64_t *dk = nullptr;
-    uint32_t *dv = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dk), n * 8));
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&dv), n * 4);
-    if (e != hipSuccess) {
-        hipFree(dk);
-        return fail(PG_E_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
-    }
+    DevBuf<uint64_t> dk;
+    DevBuf<uint32_t> dv;
+    hipError_t e = dk.alloc(n);
+    if (e == hipSuccess) e = dv.alloc(n);
+    if (e != hipSuccess) return fail(PG_E_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
     int r = PG_OK;
-    if (hipMemcpyAsync(dk, keys, n * 8, hipMemcpyHostToDevice, t->ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(dv, counters, n * 4, hipMemcpyHostToDevice, t->ctx->stream) != hipSuccess)
+    if (hipMemcpyAsync(dk.get(), keys, n * 8, hipMemcpyHostToDevice, t->ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(dv.get(), counters, n * 4, hipMemcpyHostToDevice, t->ctx->stream) != hipSuccess)
         r = fail(PG_E_HIP, "H2D copy of keys failed");
-    if (!r) r = insert_keys_dev(t, db_idx, dk, dv, n);
+    if (!r) r = insert_keys_dev(t, db_idx, dk.get(), dv.get(), n);
     hipStreamSynchronize(t->ctx->stream);
-    hipFree(dk);
-    hipFree(dv);
     return r;
     PG_API_END
 }
@@ -1127,20 +1207,20 @@ extern "C" int pg_table_load_kmc(pg_table *t, int db_idx, const void *pre_, size
     // chunks of whole records, about 256 MiB each, through two device buffers: the upload of chunk c+1 (pageable or
     // mapped host memory: HIP stages it) runs behind the import kernel of chunk c
     const uint64_t chunk_recs = std::max<uint64_t>(1, (256ull << 20) / rec);
-    uint64_t *d_lut = nullptr;
-    uint8_t *d_rec[2] = {nullptr, nullptr};
-    hipStream_t up = nullptr;
-    hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+    DevBuf<uint64_t> d_lut;
+    DevBuf<uint8_t> d_rec[2];
+    Event ev_up[2], ev_done[2];
+    Stream up;
     int rc = PG_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_lut), H.nlut * 8);
+    hipError_t e = d_lut.alloc(H.nlut);
     const uint64_t buf_bytes = std::min<uint64_t>(chunk_recs, H.total) * rec;
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipMalloc(reinterpret_cast<void **>(&d_rec[i]), buf_bytes);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_up[i], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev_done[i], hipEventDisableTiming);
+        e = d_rec[i].alloc(buf_bytes);
+        if (e == hipSuccess) e = ev_up[i].create(hipEventDisableTiming);
+        if (e == hipSuccess) e = ev_done[i].create(hipEventDisableTiming);
     }
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lut, lut.data(), H.nlut * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = up.create();
+    if (e == hipSuccess) e = hipMemcpyAsync(d_lut.get(), lut.data(), H.nlut * 8, hipMemcpyHostToDevice, st);
     const uint8_t *recs = suf + 4;
     const uint64_t nchunks = (H.total + chunk_recs - 1) / chunk_recs;
     for (int attempt = 0; attempt < 8 && e == hipSuccess && rc == PG_OK; ++attempt) {
@@ -1155,9 +1235,9 @@ extern "C" int pg_table_load_kmc(pg_table *t, int db_idx, const void *pre_, size
         auto upload_seq = [&](uint64_t c, uint64_t sq) {
             const int b = (int)(sq & 1);
             const uint64_t r0 = c * chunk_recs, n = std::min(chunk_recs, H.total - r0);
-            hipError_t x = sq >= 2 ? hipStreamWaitEvent(up, ev_done[b], 0) : hipSuccess;  // the buffer's previous kernel
-            if (x == hipSuccess) x = hipMemcpyAsync(d_rec[b], recs + r0 * rec, n * rec, hipMemcpyHostToDevice, up);
-            if (x == hipSuccess) x = hipEventRecord(ev_up[b], up);
+            hipError_t x = sq >= 2 ? hipStreamWaitEvent(up.get(), ev_done[b].get(), 0) : hipSuccess;  // the buffer's previous kernel
+            if (x == hipSuccess) x = hipMemcpyAsync(d_rec[b].get(), recs + r0 * rec, n * rec, hipMemcpyHostToDevice, up.get());
+            if (x == hipSuccess) x = hipEventRecord(ev_up[b].get(), up.get());
             return x;
         };
         const uint64_t total_chunks = nchunks * nphases;
@@ -1169,11 +1249,11 @@ extern "C" int pg_table_load_kmc(pg_table *t, int db_idx, const void *pre_, size
             const int b = (int)(seq & 1);
             const uint64_t r0 = c * chunk_recs, n = std::min(chunk_recs, H.total - r0);
             if (seq + 1 < total_chunks) e = upload_seq((seq + 1) % nchunks, seq + 1);
-            if (e == hipSuccess) e = hipStreamWaitEvent(st, ev_up[b], 0);
+            if (e == hipSuccess) e = hipStreamWaitEvent(st, ev_up[b].get(), 0);
             if (e == hipSuccess)
-                e = launch_import_kmc(st, t->subs[si].d, w, d_rec[b], r0, n, d_lut, H.nlut, 1u << (2 * H.lut_p), sb, H.csz,
+                e = launch_import_kmc(st, t->subs[si].d, w, d_rec[b].get(), r0, n, d_lut.get(), H.nlut, 1u << (2 * H.lut_p), sb, H.csz,
                                       H.minc, H.maxc, t->d_counters, MAX_PROBE, phase, db_genomes / 2);
-            if (e == hipSuccess) e = hipEventRecord(ev_done[b], st);
+            if (e == hipSuccess) e = hipEventRecord(ev_done[b].get(), st);
         }
         if (e != hipSuccess) break;
         unsigned long long cnt[2];
@@ -1185,20 +1265,10 @@ extern "C" int pg_table_load_kmc(pg_table *t, int db_idx, const void *pre_, size
         }
         if ((rc = grow_after_overflow(t, si, H.total))) break;
         if (attempt == 7) rc = fail(PG_E_CAPACITY, "k-mer table keeps overflowing");
-        if (up) hipStreamSynchronize(up);
+        hipStreamSynchronize(up.get());
     }
     if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_table_load_kmc: %s", hipGetErrorString(e));
     hipStreamSynchronize(st);
-    if (up) {
-        hipStreamSynchronize(up);
-        hipStreamDestroy(up);
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (d_rec[i]) hipFree(d_rec[i]);
-        if (ev_up[i]) hipEventDestroy(ev_up[i]);
-        if (ev_done[i]) hipEventDestroy(ev_done[i]);
-    }
-    if (d_lut) hipFree(d_lut);
     return rc;
     PG_API_END
 }
@@ -1322,34 +1392,25 @@ extern "C" int pg_table_export(pg_table *t, int db_idx, uint64_t *keys, uint32_t
     if (int r = use_device(t->ctx)) return r;
     const int si = 0, w = db_idx;
     hipStream_t st = t->ctx->stream;
-    uint64_t *dk = nullptr;
-    uint32_t *dv = nullptr;
+    DevBuf<uint64_t> dk;
+    DevBuf<uint32_t> dv;
     if (keys && cap) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dk), cap * 8));
-        hipError_t e = hipMalloc(reinterpret_cast<void **>(&dv), cap * 4);
-        if (e != hipSuccess) {
-            hipFree(dk);
-            return fail(PG_E_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
-        }
+        hipError_t e = dk.alloc(cap);
+        if (e == hipSuccess) e = dv.alloc(cap);
+        if (e != hipSuccess) return fail(PG_E_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
     }
     int rc = PG_OK;
     unsigned long long cnt[2] = {0, 0};
-    do {
-        if (hipMemsetAsync(t->d_counters, 0, 16, st) != hipSuccess ||
-            launch_export(st, t->subs[si].d, w, dk, dv, dk ? cap : 0, t->d_counters) != hipSuccess) {
-            rc = fail(PG_E_HIP, "export kernel failed");
-            break;
-        }
-        if ((rc = read_counters(t, cnt))) break;
-        if (dk) {
-            uint64_t m = std::min<uint64_t>(cnt[0], cap);
-            if (hipMemcpy(keys, dk, m * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(counters, dv, m * 4, hipMemcpyDeviceToHost) != hipSuccess)
-                rc = fail(PG_E_HIP, "D2H copy failed");
-        }
-    } while (0);
-    if (dk) hipFree(dk);
-    if (dv) hipFree(dv);
+    if (hipMemsetAsync(t->d_counters, 0, 16, st) != hipSuccess ||
+        launch_export(st, t->subs[si].d, w, dk.get(), dv.get(), dk.get() ? cap : 0, t->d_counters) != hipSuccess)
+        rc = fail(PG_E_HIP, "export kernel failed");
+    if (!rc) rc = read_counters(t, cnt);
+    if (!rc && dk.get()) {
+        uint64_t m = std::min<uint64_t>(cnt[0], cap);
+        if (hipMemcpy(keys, dk.get(), m * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(counters, dv.get(), m * 4, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = fail(PG_E_HIP, "D2H copy failed");
+    }
     *n = cnt[0];
     return rc;
     PG_API_END
@@ -1411,12 +1472,11 @@ extern "C" int pg_sketch_add_seqset(pg_sketch *sk, const pg_seqset *sq) {
     }
     if (jobs.empty()) return PG_OK;
     hipStream_t st = sk->ctx->stream;
-    uint2 *d_jobs = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_jobs), jobs.size() * sizeof(uint2)));
-    hipError_t e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(uint2), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_sketch_set(st, sk->k, sq->d_desc, d_jobs, (uint32_t)jobs.size(), sq->d_seqw, sq->d_nmw, sq->d_has_n, sk->d_regs);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the job list is freed below)
-    hipFree(d_jobs);
+    DevBuf<uint2> d_jobs;
+    hipError_t e = d_jobs.alloc(jobs.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_jobs.get(), jobs.data(), jobs.size() * sizeof(uint2), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch_sketch_set(st, sk->k, sq->d_desc, d_jobs.get(), (uint32_t)jobs.size(), sq->d_seqw, sq->d_nmw, sq->d_has_n, sk->d_regs);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the job list goes with the scope)
     if (e != hipSuccess) return fail(PG_E_HIP, "pg_sketch_add_seqset: %s", hipGetErrorString(e));
     return PG_OK;
     PG_API_END
@@ -1579,16 +1639,14 @@ extern "C" int pg_minhash_add_seqset(pg_minhash *mh, const pg_seqset *sq, uint64
     }
     cap = std::max<uint64_t>(cap, 1);
     hipStream_t st = mh->ctx->stream;
-    uint2 *d_jobs = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_jobs), jobs.size() * sizeof(uint2)));
-    int rc = PG_OK;
+    DevBuf<uint2> d_jobs;
     std::vector<uint64_t> cand;
     unsigned long long counts[2] = {0, 0};
-    hipError_t e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(uint2), hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_minhash_add_seqset: %s", hipGetErrorString(e));
-    while (rc == PG_OK) {
-        rc = minhash_pass(mh, sq, d_jobs, (uint32_t)jobs.size(), limit, cap, counts);
-        if (rc != PG_OK) break;
+    hipError_t e = d_jobs.alloc(jobs.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_jobs.get(), jobs.data(), jobs.size() * sizeof(uint2), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_minhash_add_seqset: %s", hipGetErrorString(e));
+    for (;;) {
+        if (int rc = minhash_pass(mh, sq, d_jobs.get(), (uint32_t)jobs.size(), limit, cap, counts)) return rc;
         if (counts[0] > cap) {  // the buffer overflowed: the same threshold, a 4x buffer (at most one slot per position)
             cap = std::min<uint64_t>(std::max<uint64_t>(positions, 1), std::max<uint64_t>(cap * 4, counts[0]));
             continue;
@@ -1596,10 +1654,7 @@ extern "C" int pg_minhash_add_seqset(pg_minhash *mh, const pg_seqset *sq, uint64
         cand.resize(counts[0]);
         if (!cand.empty()) {
             e = hipMemcpy(cand.data(), mh->d_cand, cand.size() * sizeof(uint64_t), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) {
-                rc = fail(PG_E_HIP, "pg_minhash_add_seqset: %s", hipGetErrorString(e));
-                break;
-            }
+            if (e != hipSuccess) return fail(PG_E_HIP, "pg_minhash_add_seqset: %s", hipGetErrorString(e));
         }
         std::sort(cand.begin(), cand.end());
         cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
@@ -1607,8 +1662,6 @@ extern "C" int pg_minhash_add_seqset(pg_minhash *mh, const pg_seqset *sq, uint64
         if (cand.size() >= mh->s || limit == all) break;
         limit = limit >= (all >> 2) ? all : limit * 4 + 3;  // tau -> 4 tau
     }
-    hipFree(d_jobs);
-    if (rc != PG_OK) return rc;
     if (cand.size() > mh->s) cand.resize(mh->s);
     std::vector<uint64_t> merged;
     merged.reserve(mh->hashes.size() + cand.size());
@@ -1880,13 +1933,11 @@ extern "C" int pg_seqset_from_fasta(pg_ctx *ctx, const void *text_, uint64_t nby
         }
         // (a stream of its own: several genomes may be loading at once — Index.load_inputs parses in its reader threads —
         // and the staging of a pageable copy is host work that runs in the calling thread)
-        hipStream_t us = nullptr;
-        e_up = hipStreamCreateWithFlags(&us, hipStreamNonBlocking);
-        if (e_up != hipSuccess) return;
-        e_up = hipMemsetAsync(d_text + nbytes, 0, tcap - nbytes, us);
-        if (e_up == hipSuccess && nbytes) e_up = hipMemcpyAsync(d_text, text, nbytes, hipMemcpyHostToDevice, us);
-        if (e_up == hipSuccess) e_up = hipStreamSynchronize(us);
-        (void)hipStreamDestroy(us);
+        Stream us;
+        e_up = us.create();
+        if (e_up == hipSuccess) e_up = hipMemsetAsync(d_text + nbytes, 0, tcap - nbytes, us.get());
+        if (e_up == hipSuccess && nbytes) e_up = hipMemcpyAsync(d_text, text, nbytes, hipMemcpyHostToDevice, us.get());
+        if (e_up == hipSuccess) e_up = hipStreamSynchronize(us.get());
     };
     if (nbytes < (1u << 20)) {
         upload();  // (a small text: a thread and a stream per call cost more than the overlap brings)
@@ -1911,23 +1962,21 @@ extern "C" int pg_seqset_from_fasta(pg_ctx *ctx, const void *text_, uint64_t nby
     bool have_hdrs = false;
     if (nbytes >= (4u << 20) && !getenv("PG_FASTA_HOST_SCAN")) {
         if (up.th.joinable()) up.th.join();
-        uint64_t *d_hdr = nullptr;
-        uint32_t *d_nhdr = nullptr, nh = 0;
-        if (e_up == hipSuccess && hipMalloc(reinterpret_cast<void **>(&d_hdr), (size_t)HDR_CAP * 8) == hipSuccess &&
-            hipMalloc(reinterpret_cast<void **>(&d_nhdr), 4) == hipSuccess) {
+        DevBuf<uint64_t> d_hdr;
+        DevBuf<uint32_t> d_nhdr;
+        uint32_t nh = 0;
+        if (e_up == hipSuccess && d_hdr.alloc(HDR_CAP) == hipSuccess && d_nhdr.alloc(1) == hipSuccess) {
             hipStream_t st = ctx->stream;
-            if (launch_text_headers(st, d_text, nbytes, d_hdr, HDR_CAP, d_nhdr) == hipSuccess &&
-                hipMemcpyAsync(&nh, d_nhdr, 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess && nh <= HDR_CAP) {
+            if (launch_text_headers(st, d_text, nbytes, d_hdr.get(), HDR_CAP, d_nhdr.get()) == hipSuccess &&
+                hipMemcpyAsync(&nh, d_nhdr.get(), 4, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess && nh <= HDR_CAP) {
                 hdrs.resize(nh);
-                if (nh == 0 || hipMemcpy(hdrs.data(), d_hdr, (size_t)nh * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+                if (nh == 0 || hipMemcpy(hdrs.data(), d_hdr.get(), (size_t)nh * 8, hipMemcpyDeviceToHost) == hipSuccess) {
                     std::sort(hdrs.begin(), hdrs.end());
                     have_hdrs = true;
                 }
             }
         }
         (void)hipGetLastError();
-        if (d_hdr) hipFree(d_hdr);
-        if (d_nhdr) hipFree(d_nhdr);
     }
     size_t hdr_at = 0;
     // first header: at offset 0 or right after a newline; anything before it is ignored
@@ -1990,44 +2039,35 @@ extern "C" int pg_seqset_from_fasta(pg_ctx *ctx, const void *text_, uint64_t nby
     }
     hipStream_t st = ctx->stream;
     const uint64_t nch = chunks.size();
-    TextChunk *d_chunks = nullptr;
-    uint64_t *d_chunk0 = nullptr, *d_base = nullptr, *d_len = nullptr;
-    uint32_t *d_counts = nullptr;
+    DevBuf<TextChunk> d_chunks;
+    DevBuf<uint64_t> d_chunk0, d_base, d_len;
+    DevBuf<uint32_t> d_counts;
     std::vector<uint64_t> lens(nrec, 0);
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t x) {
-        if (e == hipSuccess) e = x;
-        return e == hipSuccess;
-    };
-    if (ok(hipMalloc(reinterpret_cast<void **>(&d_chunks), std::max<uint64_t>(nch, 1) * sizeof(TextChunk))) &&
-        ok(hipMalloc(reinterpret_cast<void **>(&d_chunk0), (nrec + 1) * 8)) &&
-        ok(hipMalloc(reinterpret_cast<void **>(&d_base), std::max<uint64_t>(nch, 1) * 8)) &&
-        ok(hipMalloc(reinterpret_cast<void **>(&d_len), nrec * 8)) &&
-        ok(hipMalloc(reinterpret_cast<void **>(&d_counts), std::max<uint64_t>(nch, 1) * 4))) {
+    hipError_t e = d_chunks.alloc(std::max<uint64_t>(nch, 1));
+    if (e == hipSuccess) e = d_chunk0.alloc(nrec + 1);
+    if (e == hipSuccess) e = d_base.alloc(std::max<uint64_t>(nch, 1));
+    if (e == hipSuccess) e = d_len.alloc(nrec);
+    if (e == hipSuccess) e = d_counts.alloc(std::max<uint64_t>(nch, 1));
+    if (e == hipSuccess) {
         if (up.th.joinable()) up.th.join();  // (the text is up — the helper waited for its stream)
-        ok(e_up);
-        if (nch) ok(hipMemcpyAsync(d_chunks, chunks.data(), nch * sizeof(TextChunk), hipMemcpyHostToDevice, st));
-        ok(hipMemcpyAsync(d_chunk0, chunk0.data(), (nrec + 1) * 8, hipMemcpyHostToDevice, st));
-        if (e == hipSuccess)
-            ok(launch_text_pack(st, d_text, d_chunks, nch, d_chunk0, nrec, d_counts, d_base, d_len, s->d_desc, s->d_seqw,
-                                s->d_nmw, s->d_has_n));
-        ok(hipMemcpyAsync(lens.data(), d_len, nrec * 8, hipMemcpyDeviceToHost, st));
-        ok(hipStreamSynchronize(st));
-        if (e == hipSuccess) {
-            for (uint32_t i = 0; i < nrec; ++i) s->desc[i].len = lens[i];
-            ok(hipMemcpyAsync(s->d_desc, s->desc.data(), nrec * sizeof(SeqDesc), hipMemcpyHostToDevice, st));
-            ok(hipStreamSynchronize(st));
-        }
+        e = e_up;
     }
+    if (e == hipSuccess && nch) e = hipMemcpyAsync(d_chunks.get(), chunks.data(), nch * sizeof(TextChunk), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_chunk0.get(), chunk0.data(), (nrec + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = launch_text_pack(st, d_text, d_chunks.get(), nch, d_chunk0.get(), nrec, d_counts.get(), d_base.get(), d_len.get(),
+                             s->d_desc, s->d_seqw, s->d_nmw, s->d_has_n);
+    if (e == hipSuccess) e = hipMemcpyAsync(lens.data(), d_len.get(), nrec * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) {
+        for (uint32_t i = 0; i < nrec; ++i) s->desc[i].len = lens[i];
+        e = hipMemcpyAsync(s->d_desc, s->desc.data(), nrec * sizeof(SeqDesc), hipMemcpyHostToDevice, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
     // (an error may have come back with kernels still queued on st that read the text buffer — the upload ran on a stream of
     // its own, nothing else orders them against the buffer's next user once it is back in the context's cache)
-    if (e != hipSuccess) (void)hipStreamSynchronize(st);
-    hipFree(d_chunks);
-    hipFree(d_chunk0);
-    hipFree(d_base);
-    hipFree(d_len);
-    hipFree(d_counts);
     if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
         pg_seqset_destroy(s);
         return fail(PG_E_HIP, "FASTA packing failed: %s", hipGetErrorString(e));
     }
@@ -2074,14 +2114,13 @@ static int seqset_concat(pg_ctx *ctx, const pg_seqset *const *sets, const uint32
             s->names.push_back(j < src->names.size() ? src->names[j] : std::string());
         }
     }
-    SeqCopy *d_jobs = nullptr;
+    DevBuf<SeqCopy> d_jobs;
     if (!jobs.empty()) {
-        e = hipMalloc(reinterpret_cast<void **>(&d_jobs), jobs.size() * sizeof(SeqCopy));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(SeqCopy), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = launch_seq_gather(st, d_jobs, (uint32_t)jobs.size(), max_words, s->d_seqw, s->d_nmw, s->d_has_n);
+        e = d_jobs.alloc(jobs.size());
+        if (e == hipSuccess) e = hipMemcpyAsync(d_jobs.get(), jobs.data(), jobs.size() * sizeof(SeqCopy), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = launch_seq_gather(st, d_jobs.get(), (uint32_t)jobs.size(), max_words, s->d_seqw, s->d_nmw, s->d_has_n);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (d_jobs) hipFree(d_jobs);
     if (e != hipSuccess) {
         pg_seqset_destroy(s);
         return fail(PG_E_HIP, "pg_seqset_concat: %s", hipGetErrorString(e));
@@ -3071,10 +3110,10 @@ static int write_bgzf_gpu(pg_result *r, const uint8_t *src, const std::vector<st
     FILE *f = fopen(gz_path, "wb");
     if (!f) return fail(PG_E_IO, "cannot open %s for writing", gz_path);
     pg_ctx::DfSet *D = df_acquire(ctx);
-    hipStream_t cs = nullptr;
-    PaySeg *d_segs = nullptr;
-    hipEvent_t done[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
-    hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
+    DevBuf<PaySeg> d_segs;
+    Event done[2], copied[2];
+    Stream cs;
+    hipError_t e = cs.create();
     auto ok = [&](hipError_t x) {
         if (e == hipSuccess) e = x;
         return e == hipSuccess;
@@ -3092,23 +3131,23 @@ static int write_bgzf_gpu(pg_result *r, const uint8_t *src, const std::vector<st
             ok(hipHostMalloc(reinterpret_cast<void **>(&D->h_sizes[i]), (size_t)(DF_BATCH + 1) * 4, 0));  // their offsets
         }
         if (e == hipSuccess) {
-            ok(hipMemcpyAsync(D->d_crc, crc_tables_host(), CRC_TAB_WORDS * 4, hipMemcpyHostToDevice, cs));
-            ok(hipStreamSynchronize(cs));
+            ok(hipMemcpyAsync(D->d_crc, crc_tables_host(), CRC_TAB_WORDS * 4, hipMemcpyHostToDevice, cs.get()));
+            ok(hipStreamSynchronize(cs.get()));
         }
         D->ready = e == hipSuccess;
         if (!D->ready) df_free_buffers(*D);  // never keep half a set: the next call would overwrite (leak) its pointers
     }
-    ok(hipMalloc(reinterpret_cast<void **>(&d_segs), segs.size() * sizeof(PaySeg)));
+    ok(d_segs.alloc(segs.size()));
     for (int i = 0; i < 2; ++i) {
-        ok(hipEventCreateWithFlags(&done[i], hipEventDisableTiming));
-        ok(hipEventCreateWithFlags(&copied[i], hipEventDisableTiming));
+        ok(done[i].create(hipEventDisableTiming));
+        ok(copied[i].create(hipEventDisableTiming));
     }
     if (e == hipSuccess) {
-        ok(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(PaySeg), hipMemcpyHostToDevice, cs));
-        ok(hipStreamWaitEvent(cs, r->ev[r->ev_epi ? 3 : 1], 0));
+        ok(hipMemcpyAsync(d_segs.get(), segs.data(), segs.size() * sizeof(PaySeg), hipMemcpyHostToDevice, cs.get()));
+        ok(hipStreamWaitEvent(cs.get(), r->ev[r->ev_epi ? 3 : 1], 0));
     }
     // ONE Huffman code for the file, from a sample of its blocks (pg_deflate.hip)
-    if (e == hipSuccess && nblocks) ok(launch_deflate_code(cs, src, d_segs, (uint32_t)segs.size() - 1, total, row, D->d_hist, D->d_code));
+    if (e == hipSuccess && nblocks) ok(launch_deflate_code(cs.get(), src, d_segs.get(), (uint32_t)segs.size() - 1, total, row, D->d_hist, D->d_code));
     std::vector<uint64_t> coffs, uoffs;
     uint64_t cpos = 0;
     int rc = PG_OK;
@@ -3116,30 +3155,30 @@ static int write_bgzf_gpu(pg_result *r, const uint8_t *src, const std::vector<st
     // (they say how many packed bytes to fetch), then the bytes
     auto issue = [&](uint64_t b0, int slot) {
         const uint32_t nb = (uint32_t)std::min<uint64_t>(DF_BATCH, nblocks - b0);
-        hipError_t x = hipMemsetAsync(D->d_slots[slot], 0, (size_t)nb * 65536, cs);
+        hipError_t x = hipMemsetAsync(D->d_slots[slot], 0, (size_t)nb * 65536, cs.get());
         if (x == hipSuccess)
-            x = launch_row_deflate(cs, src, d_segs, (uint32_t)segs.size() - 1, total, b0, nb, row, D->d_crc, D->d_code, D->d_slots[slot],
+            x = launch_row_deflate(cs.get(), src, d_segs.get(), (uint32_t)segs.size() - 1, total, b0, nb, row, D->d_crc, D->d_code, D->d_slots[slot],
                                    D->d_sizes[slot], getenv("PG_DEFLATE_FORCE_STORED") ? (uint32_t)atoi(getenv("PG_DEFLATE_FORCE_STORED")) : 0u, D->d_offs[slot], D->d_packed[slot]);
         if (x == hipSuccess)
-            x = hipMemcpyAsync(D->h_sizes[slot], D->d_offs[slot], (size_t)(nb + 1) * 4, hipMemcpyDeviceToHost, cs);
-        if (x == hipSuccess) x = hipEventRecord(done[slot], cs);
+            x = hipMemcpyAsync(D->h_sizes[slot], D->d_offs[slot], (size_t)(nb + 1) * 4, hipMemcpyDeviceToHost, cs.get());
+        if (x == hipSuccess) x = hipEventRecord(done[slot].get(), cs.get());
         return x;
     };
     if (e == hipSuccess && nblocks) ok(issue(0, 0));
     int slot = 0;
     for (uint64_t b0 = 0; e == hipSuccess && rc == PG_OK && b0 < nblocks; b0 += DF_BATCH, slot ^= 1) {
         const uint32_t nb = (uint32_t)std::min<uint64_t>(DF_BATCH, nblocks - b0);
-        if (!ok(hipEventSynchronize(done[slot]))) break;
+        if (!ok(hipEventSynchronize(done[slot].get()))) break;
         const uint32_t *offs = D->h_sizes[slot];
         const uint32_t bytes = offs[nb];
         if (bytes < 26u * nb || bytes > nb * 65536ull) {
             rc = fail(PG_E_IO, "GPU deflate produced %u bytes for %u blocks", bytes, nb);
             break;
         }
-        if (!ok(hipMemcpyAsync(D->h_slots[slot], D->d_packed[slot], bytes, hipMemcpyDeviceToHost, cs))) break;
-        if (!ok(hipEventRecord(copied[slot], cs))) break;
+        if (!ok(hipMemcpyAsync(D->h_slots[slot], D->d_packed[slot], bytes, hipMemcpyDeviceToHost, cs.get()))) break;
+        if (!ok(hipEventRecord(copied[slot].get(), cs.get()))) break;
         if (b0 + DF_BATCH < nblocks && !ok(issue(b0 + DF_BATCH, slot ^ 1))) break;  // the next batch runs behind the copy
-        if (!ok(hipEventSynchronize(copied[slot]))) break;
+        if (!ok(hipEventSynchronize(copied[slot].get()))) break;
         for (uint32_t i = 0; i < nb; ++i) {
             coffs.push_back(cpos + offs[i]);
             uoffs.push_back((b0 + i) * 65280ull);
@@ -3151,7 +3190,7 @@ static int write_bgzf_gpu(pg_result *r, const uint8_t *src, const std::vector<st
         cpos += bytes;
     }
     if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_result_write_bgzf (GPU deflate): %s", hipGetErrorString(e));
-    if (cs) hipStreamSynchronize(cs);
+    if (cs.get()) hipStreamSynchronize(cs.get());
     df_release(ctx, D);
     const std::string keep = rc ? g_err : std::string();
     if (!rc && fwrite(EOF_BLOCK, 1, sizeof EOF_BLOCK, f) != sizeof EOF_BLOCK) rc = fail(PG_E_IO, "short write of BGZF EOF block");
@@ -3168,12 +3207,6 @@ static int write_bgzf_gpu(pg_result *r, const uint8_t *src, const std::vector<st
         }
     }
     if (!keep.empty()) g_err = keep;
-    hipFree(d_segs);
-    for (int i = 0; i < 2; ++i) {
-        if (done[i]) hipEventDestroy(done[i]);
-        if (copied[i]) hipEventDestroy(copied[i]);
-    }
-    if (cs) hipStreamDestroy(cs);
     return rc;
 }
 
@@ -3196,8 +3229,7 @@ extern "C" int pg_result_write_bgzf_range(pg_result *r, int step, uint32_t first
     if (!r || !gz_path) return fail(PG_E_INVALID, "pg_result_write_bgzf: NULL argument");
     if ((uint64_t)first_contig + ncontigs > r->ad.size())
         return fail(PG_E_INVALID, "contigs %u..%u out of range", first_contig, first_contig + ncontigs);
-    if (step != 1 && step != 100 && (uint32_t)step != r->lowres_step)
-        return fail(PG_E_INVALID, "step must be 1 or the result's low-resolution step (%u; 100 is accepted as its alias)", r->lowres_step);
+    if (int e = check_step(r, step)) return e;
     if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
     if (step == 100 && (r->flags & PG_ANCHOR_ROWS_ONLY) && !r->ev_epi)
         return fail(PG_E_INVALID, "rows-only result: bitmap.100 needs pg_rows_epilogue first");
@@ -3219,16 +3251,16 @@ extern "C" int pg_result_write_bgzf_range(pg_result *r, int step, uint32_t first
     if (level >= 0) level |= nbytes_row == 1 ? PG_BGZF_RLE : (nbytes_row < 256 ? PG_BGZF_ROWS(nbytes_row) : 0);
     if (int e = pg_bgzf_open(gz_path, level, nthreads, &w)) return e;
     const size_t chunk = (size_t)512 * 65280;  // 32 MiB: 512 BGZF blocks, shared out one by one among the threads
-    hipStream_t cs = nullptr;
-    uint8_t *pin[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
+    PinBuf<uint8_t> pin[2];
+    Event done[2];
+    Stream cs;
     int rc = PG_OK;
-    hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
+    hipError_t e = cs.create();
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = hipHostMalloc(reinterpret_cast<void **>(&pin[i]), std::min<uint64_t>(chunk, std::max<uint64_t>(total, 1)), 0);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
+        e = pin[i].alloc(std::min<uint64_t>(chunk, std::max<uint64_t>(total, 1)), 0);
+        if (e == hipSuccess) e = done[i].create(hipEventDisableTiming);
     }
-    if (e == hipSuccess) e = hipStreamWaitEvent(cs, r->ev[r->ev_epi ? 3 : 1], 0);
+    if (e == hipSuccess) e = hipStreamWaitEvent(cs.get(), r->ev[r->ev_epi ? 3 : 1], 0);
     if (e == hipSuccess) {
         size_t seg = 0;
         uint64_t seg_pos = 0;  // cursor of the next byte to fetch
@@ -3238,7 +3270,7 @@ extern "C" int pg_result_write_bgzf_range(pg_result *r, int step, uint32_t first
             uint64_t got = 0;
             while (got < n && x == hipSuccess) {
                 const uint64_t take = std::min<uint64_t>(n - got, segs[seg].second - seg_pos);
-                x = hipMemcpyAsync(pin[b] + got, src + segs[seg].first + seg_pos, take, hipMemcpyDeviceToHost, cs);
+                x = hipMemcpyAsync(pin[b].get() + got, src + segs[seg].first + seg_pos, take, hipMemcpyDeviceToHost, cs.get());
                 got += take;
                 seg_pos += take;
                 if (seg_pos == segs[seg].second) {
@@ -3246,7 +3278,7 @@ extern "C" int pg_result_write_bgzf_range(pg_result *r, int step, uint32_t first
                     seg_pos = 0;
                 }
             }
-            if (x == hipSuccess) x = hipEventRecord(done[b], cs);
+            if (x == hipSuccess) x = hipEventRecord(done[b].get(), cs.get());
             return x;
         };
         uint64_t off = 0;
@@ -3254,27 +3286,22 @@ extern "C" int pg_result_write_bgzf_range(pg_result *r, int step, uint32_t first
         if (total) e = issue(0, 0);
         while (e == hipSuccess && off < total) {
             const uint64_t n = std::min<uint64_t>(chunk, total - off);
-            e = hipEventSynchronize(done[b]);
+            e = hipEventSynchronize(done[b].get());
             if (e != hipSuccess) break;
             if (off + n < total) {
                 e = issue(off + n, b ^ 1);
                 if (e != hipSuccess) break;
             }
-            if ((rc = pg_bgzf_write(w, pin[b], n))) break;
+            if ((rc = pg_bgzf_write(w, pin[b].get(), n))) break;
             off += n;
             b ^= 1;
         }
     }
     if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_result_write_bgzf: %s", hipGetErrorString(e));
-    if (cs) hipStreamSynchronize(cs);
+    if (cs.get()) hipStreamSynchronize(cs.get());
     const std::string keep = rc ? g_err : std::string();
     const int rc2 = pg_bgzf_close(w, rc ? nullptr : gzi_path);
     if (rc) g_err = keep;
-    for (int i = 0; i < 2; ++i) {
-        if (pin[i]) hipHostFree(pin[i]);
-        if (done[i]) hipEventDestroy(done[i]);
-    }
-    if (cs) hipStreamDestroy(cs);
     return rc ? rc : rc2;
     PG_API_END
 }
@@ -3287,8 +3314,7 @@ extern "C" int pg_result_window_stats(pg_result *r, uint32_t idx, int step, uint
     PG_API_BEGIN
     if (!r || (nwin && (!starts || !ends || !hist))) return fail(PG_E_INVALID, "pg_result_window_stats: NULL argument");
     if (idx >= r->ad.size()) return fail(PG_E_INVALID, "contig %u out of range", idx);
-    if (step != 1 && step != 100 && (uint32_t)step != r->lowres_step)
-        return fail(PG_E_INVALID, "step must be 1 or the result's low-resolution step (%u; 100 is accepted as its alias)", r->lowres_step);
+    if (int e = check_step(r, step)) return e;
     if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
     if (nwin == 0) return PG_OK;
     if (int e = use_device(r->ctx)) return e;
@@ -3302,24 +3328,22 @@ extern "C" int pg_result_window_stats(pg_result *r, uint32_t idx, int step, uint
     for (uint32_t i = 0; i < nwin; ++i)
         if (ends[i] > starts[i]) longest = std::max(longest, std::min(ends[i], nrows) - std::min(starts[i], nrows));
     const uint32_t pieces = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, longest / 32768));
-    uint64_t *d_se = nullptr;
-    unsigned long long *d_out = nullptr;
+    DevBuf<uint64_t> d_se;
+    DevBuf<unsigned long long> d_out;
     const size_t nh = (size_t)nwin * (N + 1), nc = colsums ? (size_t)nwin * N : 0;
-    int rc = PG_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_se), (size_t)nwin * 16);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), (nh + nc) * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_se, starts, (size_t)nwin * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_se + nwin, ends, (size_t)nwin * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (nh + nc) * 8, st);
+    hipError_t e = d_se.alloc((size_t)nwin * 2);
+    if (e == hipSuccess) e = d_out.alloc(nh + nc);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), starts, (size_t)nwin * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get() + nwin, ends, (size_t)nwin * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, (nh + nc) * 8, st);
     if (e == hipSuccess)
-        e = launch_window_stats(st, N, rows, nrows, nwin, pieces, d_se, d_se + nwin, d_out, colsums ? d_out + nh : nullptr);
-    if (e == hipSuccess) e = hipMemcpyAsync(hist, d_out, nh * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && colsums) e = hipMemcpyAsync(colsums, d_out + nh, nc * 8, hipMemcpyDeviceToHost, st);
+        e = launch_window_stats(st, N, rows, nrows, nwin, pieces, d_se.get(), d_se.get() + nwin, d_out.get(),
+                                colsums ? d_out.get() + nh : nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(hist, d_out.get(), nh * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && colsums) e = hipMemcpyAsync(colsums, d_out.get() + nh, nc * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_result_window_stats: %s", hipGetErrorString(e));
-    if (d_se) hipFree(d_se);
-    if (d_out) hipFree(d_out);
-    return rc;
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_window_stats: %s", hipGetErrorString(e));
+    return PG_OK;
     PG_API_END
 }
 
@@ -3331,34 +3355,16 @@ extern "C" int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, ui
     PG_API_BEGIN
     if (!r || (nbins && (!contig || !starts || !ends || !cs_out || !kept_out)))
         return fail(PG_E_INVALID, "pg_result_bin_colsums: NULL argument");
-    if (step != 1 && step != 100 && (uint32_t)step != r->lowres_step)
-        return fail(PG_E_INVALID, "step must be 1 or the result's low-resolution step (%u; 100 is accepted as its alias)", r->lowres_step);
+    if (int e = check_step(r, step)) return e;
     if (stride < 1) return fail(PG_E_INVALID, "pg_result_bin_colsums: stride must be >= 1");
     if (nbins > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_bin_colsums: %u bins (at most 2^31 - 1 per call)", nbins);
     const uint32_t N = r->N;
     if (N < 1 || N > 4096) return fail(PG_E_INVALID, "pg_result_bin_colsums: %u genomes (1 to 4096)", N);
-    if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
-    if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
-    if (step != 1 && (r->flags & PG_ANCHOR_ROWS_ONLY) && !r->ev_epi && !r->rows_valid)
-        return fail(PG_E_INVALID, "rows-only result: the low-resolution rows need pg_rows_epilogue first");
+    if (int e = check_rows_readable(r, step)) return e;
     const uint32_t ndw = (N + 31) / 32;
-    // bin i: device byte offset of its contig's rows, then [start, end) in sampled rows
-    std::vector<uint64_t> se((size_t)nbins * 3);
+    std::vector<uint64_t> se;
     uint64_t longest = 0;
-    for (uint32_t i = 0; i < nbins; ++i) {
-        if (contig[i] >= r->ad.size()) return fail(PG_E_INVALID, "bin %u: contig %u out of range", i, contig[i]);
-        const AnchorDesc &a = r->ad[contig[i]];
-        const uint64_t nrows = step == 1 ? (uint64_t)a.nkmers : r->nrows100[contig[i]];
-        if (starts[i] > ends[i]) return fail(PG_E_INVALID, "bin %u: start %llu past end %llu", i, (unsigned long long)starts[i],
-                                             (unsigned long long)ends[i]);
-        if (ends[i] > starts[i] && (nrows == 0 || ends[i] - 1 > (nrows - 1) / stride))
-            return fail(PG_E_INVALID, "bin %u: sampled row %llu (x %u) past the %llu rows of contig %u", i,
-                        (unsigned long long)(ends[i] - 1), stride, (unsigned long long)nrows, contig[i]);
-        se[i] = step == 1 ? a.out_off : a.out100_off;
-        se[nbins + i] = starts[i];
-        se[2 * (size_t)nbins + i] = ends[i];
-        longest = std::max(longest, ends[i] - starts[i]);
-    }
+    if (int e = gather_windows(r, step, stride, nbins, contig, starts, ends, "bin", se, &longest)) return e;
     std::vector<uint32_t> kw(ndw, 0);
     if (keep_words)
         for (uint32_t d = 0; d < ndw; ++d) kw[d] = keep_words[d] & (N - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (N - 32 * d)) - 1u);
@@ -3369,28 +3375,24 @@ extern "C" int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, ui
     // pieces: about 32 K sampled rows each for the longest bin, and enough blocks to fill the device
     uint32_t pieces = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, longest / 32768));
     while (pieces < 256 && (uint64_t)nbins * pieces < 4096 && (uint64_t)pieces * 4096 < longest) pieces *= 2;
-    uint64_t *d_se = nullptr;
-    uint32_t *d_kw = nullptr;
-    unsigned long long *d_out = nullptr;
+    DevBuf<uint64_t> d_se;
+    DevBuf<uint32_t> d_kw;
+    DevBuf<unsigned long long> d_out;
     const size_t nc = (size_t)nbins * N;
-    int rc = PG_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_se), se.size() * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_kw), (size_t)ndw * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), (nc + nbins) * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_se, se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_kw, kw.data(), (size_t)ndw * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, (nc + nbins) * 8, st);
+    hipError_t e = d_se.alloc(se.size());
+    if (e == hipSuccess) e = d_kw.alloc(ndw);
+    if (e == hipSuccess) e = d_out.alloc(nc + nbins);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_kw.get(), kw.data(), (size_t)ndw * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, (nc + nbins) * 8, st);
     if (e == hipSuccess)
-        e = launch_bin_colsums(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nbins, pieces, d_se, d_se + nbins,
-                               d_se + 2 * (size_t)nbins, d_kw, omit_fixed ? 1u : 0u, d_out, d_out + nc);
-    if (e == hipSuccess) e = hipMemcpyAsync(cs_out, d_out, nc * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(kept_out, d_out + nc, (size_t)nbins * 8, hipMemcpyDeviceToHost, st);
+        e = launch_bin_colsums(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nbins, pieces, d_se.get(), d_se.get() + nbins,
+                               d_se.get() + 2 * (size_t)nbins, d_kw.get(), omit_fixed ? 1u : 0u, d_out.get(), d_out.get() + nc);
+    if (e == hipSuccess) e = hipMemcpyAsync(cs_out, d_out.get(), nc * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(kept_out, d_out.get() + nc, (size_t)nbins * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_result_bin_colsums: %s", hipGetErrorString(e));
-    if (d_se) hipFree(d_se);
-    if (d_kw) hipFree(d_kw);
-    if (d_out) hipFree(d_out);
-    return rc;
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_bin_colsums: %s", hipGetErrorString(e));
+    return PG_OK;
     PG_API_END
 }
 
@@ -3401,34 +3403,16 @@ extern "C" int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, ui
     PG_API_BEGIN
     if (!r || (nwin && (!contig || !starts || !ends || !pairs_out)))
         return fail(PG_E_INVALID, "pg_result_pair_counts: NULL argument");
-    if (step != 1 && step != 100 && (uint32_t)step != r->lowres_step)
-        return fail(PG_E_INVALID, "step must be 1 or the result's low-resolution step (%u; 100 is accepted as its alias)", r->lowres_step);
+    if (int e = check_step(r, step)) return e;
     if (stride < 1) return fail(PG_E_INVALID, "pg_result_pair_counts: stride must be >= 1");
     if (nwin > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_pair_counts: %u windows (at most 2^31 - 1 per call)", nwin);
     const uint32_t N = r->N;
     if (N < 1 || N > PAIRS_MAX_GENOMES)
         return fail(PG_E_INVALID, "pg_result_pair_counts: %u genomes (the pair counts take 1 to %u)", N, PAIRS_MAX_GENOMES);
-    if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
-    if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
-    if (step != 1 && (r->flags & PG_ANCHOR_ROWS_ONLY) && !r->ev_epi && !r->rows_valid)
-        return fail(PG_E_INVALID, "rows-only result: the low-resolution rows need pg_rows_epilogue first");
-    // window i: device byte offset of its contig's rows, then [start, end) in sampled rows
-    std::vector<uint64_t> se((size_t)nwin * 3);
+    if (int e = check_rows_readable(r, step)) return e;
+    std::vector<uint64_t> se;
     uint64_t longest = 0;
-    for (uint32_t i = 0; i < nwin; ++i) {
-        if (contig[i] >= r->ad.size()) return fail(PG_E_INVALID, "window %u: contig %u out of range", i, contig[i]);
-        const AnchorDesc &a = r->ad[contig[i]];
-        const uint64_t nrows = step == 1 ? (uint64_t)a.nkmers : r->nrows100[contig[i]];
-        if (starts[i] > ends[i]) return fail(PG_E_INVALID, "window %u: start %llu past end %llu", i, (unsigned long long)starts[i],
-                                             (unsigned long long)ends[i]);
-        if (ends[i] > starts[i] && (nrows == 0 || ends[i] - 1 > (nrows - 1) / stride))
-            return fail(PG_E_INVALID, "window %u: sampled row %llu (x %u) past the %llu rows of contig %u", i,
-                        (unsigned long long)(ends[i] - 1), stride, (unsigned long long)nrows, contig[i]);
-        se[i] = step == 1 ? a.out_off : a.out100_off;
-        se[nwin + i] = starts[i];
-        se[2 * (size_t)nwin + i] = ends[i];
-        longest = std::max(longest, ends[i] - starts[i]);
-    }
+    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", se, &longest)) return e;
     if (nwin == 0) return PG_OK;
     if (int e = use_device(r->ctx)) return e;
     if (int e = join_result(r)) return e;
@@ -3438,29 +3422,26 @@ extern "C" int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, ui
     // pieces as below) and a piece keeps more than 4096 rows (it ends with up to N^2 / 2 atomics)
     uint32_t pieces = (uint32_t)std::min<uint64_t>(2048, std::max<uint64_t>(1, longest / 32768));
     while (pieces < 2048 && (uint64_t)nwin * pieces < 4096 && (uint64_t)pieces * 4096 < longest) pieces *= 2;
-    uint64_t *d_se = nullptr;
-    unsigned long long *d_out = nullptr;
+    DevBuf<uint64_t> d_se;
+    DevBuf<unsigned long long> d_out;
     const size_t nc = (size_t)nwin * N * N;
-    int rc = PG_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_se), se.size() * 8);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_out), nc * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_se, se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, nc * 8, st);
+    hipError_t e = d_se.alloc(se.size());
+    if (e == hipSuccess) e = d_out.alloc(nc);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, nc * 8, st);
     if (e == hipSuccess)
-        e = launch_pair_counts(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nwin, pieces, d_se, d_se + nwin,
-                               d_se + 2 * (size_t)nwin, d_out);
-    if (e == hipSuccess) e = hipMemcpyAsync(pairs_out, d_out, nc * 8, hipMemcpyDeviceToHost, st);
+        e = launch_pair_counts(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nwin, pieces, d_se.get(), d_se.get() + nwin,
+                               d_se.get() + 2 * (size_t)nwin, d_out.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(pairs_out, d_out.get(), nc * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_result_pair_counts: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_pair_counts: %s", hipGetErrorString(e));
     // the kernel counts the pairs on and above the diagonal: the matrix is symmetric
-    for (size_t i = 0; rc == PG_OK && i < nwin; ++i) {
+    for (size_t i = 0; i < nwin; ++i) {
         uint64_t *m = pairs_out + i * N * N;
         for (uint32_t a = 0; a < N; ++a)
             for (uint32_t b = a + 1; b < N; ++b) m[(size_t)b * N + a] = m[(size_t)a * N + b];
     }
-    if (d_se) hipFree(d_se);
-    if (d_out) hipFree(d_out);
-    return rc;
+    return PG_OK;
     PG_API_END
 }
 
@@ -3501,27 +3482,22 @@ extern "C" int pg_knn_rows(pg_ctx *ctx, const float *X, uint64_t n, uint32_t nco
     const uint32_t ntiles = (uint32_t)(tiles.size() / 4);
     if (int e = use_device(ctx)) return e;
     hipStream_t st = ctx->stream;
-    float *d_x = nullptr, *d_d2 = nullptr;
-    int32_t *d_idx = nullptr;
-    uint32_t *d_tiles = nullptr;
+    DevBuf<float> d_x, d_d2;
+    DevBuf<int32_t> d_idx;
+    DevBuf<uint32_t> d_tiles;
     const size_t xb = (size_t)n * ncols * 4, ob = (size_t)n * k * 4;
-    int rc = PG_OK;
-    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_x), xb);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_idx), ob);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_d2), ob);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d_tiles), tiles.size() * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_x, X, xb, hipMemcpyDefault, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = launch_knn_rows(st, d_x, ncols, k, d_tiles, ntiles, threads, d_idx, d_d2);
-    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, d_idx, ob, hipMemcpyDefault, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d2_out, d_d2, ob, hipMemcpyDefault, st);
+    hipError_t e = d_x.alloc((size_t)n * ncols);
+    if (e == hipSuccess) e = d_idx.alloc((size_t)n * k);
+    if (e == hipSuccess) e = d_d2.alloc((size_t)n * k);
+    if (e == hipSuccess) e = d_tiles.alloc(tiles.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_x.get(), X, xb, hipMemcpyDefault, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tiles.get(), tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch_knn_rows(st, d_x.get(), ncols, k, d_tiles.get(), ntiles, threads, d_idx.get(), d_d2.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, d_idx.get(), ob, hipMemcpyDefault, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d2_out, d_d2.get(), ob, hipMemcpyDefault, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) rc = fail(PG_E_HIP, "pg_knn_rows: %s", hipGetErrorString(e));
-    if (d_x) hipFree(d_x);
-    if (d_idx) hipFree(d_idx);
-    if (d_d2) hipFree(d_d2);
-    if (d_tiles) hipFree(d_tiles);
-    return rc;
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_knn_rows: %s", hipGetErrorString(e));
+    return PG_OK;
     PG_API_END
 }
 
@@ -3664,17 +3640,16 @@ extern "C" int pg_counters_for_read(pg_table *t, int db_idx, const char *ascii, 
     pg_seqset *sq = nullptr;
     int rc = pg_seqset_create(t->ctx, 1, &len, &sq);
     if (!rc) rc = pg_seqset_load_host(sq, 0, ascii, len);
-    uint32_t *d_out = nullptr;
-    if (!rc && hipMalloc(reinterpret_cast<void **>(&d_out), nk * 4) != hipSuccess) rc = fail(PG_E_HIP, "hipMalloc failed");
+    DevBuf<uint32_t> d_out;
+    if (!rc && d_out.alloc(nk) != hipSuccess) rc = fail(PG_E_HIP, "hipMalloc failed");
     if (!rc) {
         hipStream_t st = t->ctx->stream;
         const int si = 0, w = db_idx;
-        if (launch_counters(st, t->subs[si].d, w, t->k, sq->d_seqw, sq->d_nmw, sq->d_has_n, nk, d_out) != hipSuccess ||
-            hipMemcpyAsync(out, d_out, nk * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (launch_counters(st, t->subs[si].d, w, t->k, sq->d_seqw, sq->d_nmw, sq->d_has_n, nk, d_out.get()) != hipSuccess ||
+            hipMemcpyAsync(out, d_out.get(), nk * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
             rc = fail(PG_E_HIP, "counters kernel failed: %s", hipGetErrorString(hipGetLastError()));
     }
-    if (d_out) hipFree(d_out);
     pg_seqset_destroy(sq);
     return rc;
     PG_API_END
@@ -3732,14 +3707,9 @@ static int inflate_blocks(pg_ctx *ctx, const uint8_t *comp, uint64_t file_base, 
                           const std::vector<PaySeg> &segs, uint8_t *d_dst) {
     if (blocks.empty()) return PG_OK;
     hipStream_t st = ctx->stream;
-    uint32_t *d_comp = nullptr, *d_status = nullptr, *d_crc = nullptr;
-    InflBlock *d_blocks = nullptr;
-    PaySeg *d_segs = nullptr;
-    hipError_t e = hipSuccess;
-    auto ok = [&](hipError_t x) {
-        if (e == hipSuccess) e = x;
-        return e == hipSuccess;
-    };
+    DevBuf<uint32_t> d_comp, d_status, d_crc;
+    DevBuf<InflBlock> d_blocks;
+    DevBuf<PaySeg> d_segs;
     uint64_t span_max = 0;
     size_t nb_max = 0;
     for (size_t b0 = 0, b1; b0 < blocks.size(); b0 = b1) {  // piece geometry first: one allocation for every piece
@@ -3749,13 +3719,13 @@ static int inflate_blocks(pg_ctx *ctx, const uint8_t *comp, uint64_t file_base, 
         span_max = std::max<uint64_t>(span_max, blocks[b1 - 1].coff + blocks[b1 - 1].csize - blocks[b0].coff);
         nb_max = std::max(nb_max, b1 - b0);
     }
-    ok(hipMalloc(reinterpret_cast<void **>(&d_comp), (span_max + 3) / 4 * 4 + 16));
-    ok(hipMalloc(reinterpret_cast<void **>(&d_blocks), nb_max * sizeof(InflBlock)));
-    ok(hipMalloc(reinterpret_cast<void **>(&d_status), nb_max * 4));
-    ok(hipMalloc(reinterpret_cast<void **>(&d_crc), CRC_TAB_WORDS * 4));
-    ok(hipMalloc(reinterpret_cast<void **>(&d_segs), segs.size() * sizeof(PaySeg)));
-    ok(hipMemcpyAsync(d_crc, crc_tables_host(), CRC_TAB_WORDS * 4, hipMemcpyHostToDevice, st));
-    ok(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(PaySeg), hipMemcpyHostToDevice, st));
+    hipError_t e = d_comp.alloc((span_max + 3) / 4 + 4);
+    if (e == hipSuccess) e = d_blocks.alloc(nb_max);
+    if (e == hipSuccess) e = d_status.alloc(nb_max);
+    if (e == hipSuccess) e = d_crc.alloc(CRC_TAB_WORDS);
+    if (e == hipSuccess) e = d_segs.alloc(segs.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_crc.get(), crc_tables_host(), CRC_TAB_WORDS * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_segs.get(), segs.data(), segs.size() * sizeof(PaySeg), hipMemcpyHostToDevice, st);
     std::vector<uint32_t> status;
     int rc = PG_OK;
     for (size_t b0 = 0, b1; e == hipSuccess && rc == PG_OK && b0 < blocks.size(); b0 = b1) {
@@ -3766,14 +3736,15 @@ static int inflate_blocks(pg_ctx *ctx, const uint8_t *comp, uint64_t file_base, 
         const uint32_t nb = (uint32_t)(b1 - b0);
         std::vector<InflBlock> piece(blocks.begin() + b0, blocks.begin() + b1);
         for (auto &b : piece) b.coff -= c0;
-        ok(hipMemcpyAsync(d_comp, comp + c0, span, hipMemcpyHostToDevice, st));
-        ok(hipMemcpyAsync(d_blocks, piece.data(), nb * sizeof(InflBlock), hipMemcpyHostToDevice, st));
-        ok(hipMemsetAsync(d_status, 0, (size_t)nb * 4, st));
-        if (e == hipSuccess)
-            ok(launch_bgzf_inflate(st, d_comp, (span + 3) / 4, d_blocks, nb, d_segs, (uint32_t)segs.size() - 1, d_dst, d_crc, d_status));
         status.resize(nb);
-        ok(hipMemcpyAsync(status.data(), d_status, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        ok(hipStreamSynchronize(st));
+        e = hipMemcpyAsync(d_comp.get(), comp + c0, span, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_blocks.get(), piece.data(), nb * sizeof(InflBlock), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemsetAsync(d_status.get(), 0, (size_t)nb * 4, st);
+        if (e == hipSuccess)
+            e = launch_bgzf_inflate(st, d_comp.get(), (span + 3) / 4, d_blocks.get(), nb, d_segs.get(), (uint32_t)segs.size() - 1, d_dst,
+                                    d_crc.get(), d_status.get());
+        if (e == hipSuccess) e = hipMemcpyAsync(status.data(), d_status.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) break;
         for (uint32_t i = 0; i < nb; ++i)
             if (status[i]) {
@@ -3783,11 +3754,6 @@ static int inflate_blocks(pg_ctx *ctx, const uint8_t *comp, uint64_t file_base, 
             }
     }
     if (e != hipSuccess) rc = fail(PG_E_HIP, "BGZF inflate: %s", hipGetErrorString(e));
-    hipFree(d_comp);
-    hipFree(d_blocks);
-    hipFree(d_status);
-    hipFree(d_crc);
-    hipFree(d_segs);
     return rc;
 }
 
@@ -3845,8 +3811,7 @@ extern "C" int pg_result_inflate_bgzf(pg_result *r, int step, const char *gz_pat
     if (!r || !gz_path) return fail(PG_E_INVALID, "pg_result_inflate_bgzf: NULL argument");
     if ((uint64_t)first_contig + ncontigs > r->ad.size())
         return fail(PG_E_INVALID, "contigs %u..%u out of range", first_contig, first_contig + ncontigs);
-    if (step != 1 && step != 100 && (uint32_t)step != r->lowres_step)
-        return fail(PG_E_INVALID, "step must be 1 or the result's low-resolution step (%u; 100 is accepted as its alias)", r->lowres_step);
+    if (int e = check_step(r, step)) return e;
     if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
     const uint64_t nbytes = (r->N + 7) / 8;
     // the payload range of the contigs and where each one's rows live in the result
@@ -3891,10 +3856,9 @@ extern "C" int pg_result_inflate_bgzf(pg_result *r, int step, const char *gz_pat
     if (int x = use_device(r->ctx)) return x;
     if (int x = join_result(r)) return x;
     uint8_t *dst = step == 1 ? r->d_out1 : r->d_out100;
-    uint8_t *h = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void **>(&h), INF_PIECE_BYTES, hipHostMallocDefault) != hipSuccess)
+    PinBuf<uint8_t> h;
+    if (h.alloc(INF_PIECE_BYTES, hipHostMallocDefault) != hipSuccess)
         return fail(PG_E_HIP, "pg_result_inflate_bgzf: no pinned staging buffer");
-    std::unique_ptr<uint8_t, hipError_t (*)(void *)> hguard(h, hipHostFree);
     size_t gi = 0;  // next .gzi entry to compare the walk with
     int rc = PG_OK;
     uint64_t prev_coff = UINT64_MAX;
@@ -3902,12 +3866,12 @@ extern "C" int pg_result_inflate_bgzf(pg_result *r, int step, const char *gz_pat
         if (cpos >= fsize) return fail(PG_E_FORMAT, "%s ends at payload byte %llu, before byte %llu", gz_path, (unsigned long long)rpos,
                                        (unsigned long long)R1);
         const uint64_t want = std::min<uint64_t>(INF_PIECE_BYTES, fsize - cpos);
-        if (fseeko(f, (off_t)cpos, SEEK_SET) != 0 || fread(h, 1, want, f) != want) return fail(PG_E_IO, "short read of %s", gz_path);
+        if (fseeko(f, (off_t)cpos, SEEK_SET) != 0 || fread(h.get(), 1, want, f) != want) return fail(PG_E_IO, "short read of %s", gz_path);
         std::vector<InflBlock> blocks;
         uint64_t off = 0;
         while (off < want && rpos < R1) {
             InflBlock b{};
-            if (!bgzf_header(h + off, want - off, &b.hlen, &b.csize, &b.isize)) {
+            if (!bgzf_header(h.get() + off, want - off, &b.hlen, &b.csize, &b.isize)) {
                 if (want - off < 65536 + 8 && cpos + want < fsize) break;  // the block continues in the next piece
                 return fail(PG_E_FORMAT, "BGZF block at file offset %llu: bad header", (unsigned long long)(cpos + off));
             }
@@ -3924,7 +3888,7 @@ extern "C" int pg_result_inflate_bgzf(pg_result *r, int step, const char *gz_pat
             if (rpos > R0) blocks.push_back(b);  // (blocks wholly before the range: walked, not inflated)
         }
         if (off == 0) return fail(PG_E_FORMAT, "BGZF block at file offset %llu: bad header", (unsigned long long)cpos);
-        rc = inflate_blocks(r->ctx, h, cpos, blocks, segs, dst);
+        rc = inflate_blocks(r->ctx, h.get(), cpos, blocks, segs, dst);
         cpos += off;
     }
     if (rc) return rc;

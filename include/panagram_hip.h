@@ -392,6 +392,29 @@ int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, uint32_t nbin
  * beyond).  One launch for all windows (k_pair_counts); synchronises. */
 int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
                           const uint64_t *starts, const uint64_t *ends, uint64_t *pairs_out);
+/* presence/absence pattern runs: where are the rows that THESE genomes hold and THOSE genomes lack (scripts/query_index.py's
+ * "custom" branch: np.flatnonzero((kmers[:,0]==1) & (kmers[:,1]==0) & ...) on a chromosome unpacked on the host)?
+ * The rule: have_words / lack_words are two sets of genomes as ceil(ngenomes / 32) words each (bit g of a set = bit g % 32 of
+ * word g / 32; NULL: the empty set; bits at and past ngenomes are ignored, in the masks and in a row's last byte).  A row
+ * matches iff popcount(row & have) >= min_have and popcount(row & lack) <= max_lack: min_have = |have|, max_lack = 0 is the
+ * reference's expression, other thresholds are quorum rules; min_have > |have| matches nothing, min_have = 0 with an empty lack
+ * set every row.
+ * Runs: window i = SAMPLED rows [starts[i], ends[i]) of contig contig[i]'s bitmap.<step> rows in HBM, sampled row j being row
+ * j * stride.  A run is a maximal range [a, b) of consecutive sampled rows of a window that all match; the window's edges cut
+ * runs, and no row outside the window is read.  nruns_out[i] / matched_out[i] = the runs and the matching sampled rows of
+ * window i, *total_out = the sum of nruns_out.
+ * Capacity: the counts are always computed.  If *total_out > cap, or cap == 0, the call returns PG_OK with the counts filled
+ * and writes nothing to run_start / run_end (which may then be NULL when cap == 0): call again with arrays of *total_out
+ * entries.  Otherwise their first *total_out entries are the runs' first sampled rows and exclusive ends, as sampled row
+ * numbers of their contig, sorted by (window, start) — window i's runs behind those of the windows before it — and the same on
+ * every call.  Every sampled row must lie inside its contig; 1 to 4096 genomes (PG_E_INVALID otherwise, before anything is
+ * launched).  Two launches of k_find_runs (count, then emit; one when nothing is emitted) over chunks of 4096 sampled rows, no
+ * atomics; synchronises. */
+int pg_result_find_runs(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
+                        const uint64_t *starts, const uint64_t *ends,
+                        const uint32_t *have_words, const uint32_t *lack_words, uint32_t min_have, uint32_t max_lack,
+                        uint64_t cap, uint32_t *run_start, uint32_t *run_end,
+                        uint64_t *nruns_out, uint64_t *matched_out, uint64_t *total_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

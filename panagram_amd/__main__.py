@@ -1,8 +1,10 @@
 """CLI surface kept from the reference (`panagram index <samples.tsv> -k K [-o prefix] [-c cores]
 [--prepare]`, panagram/__main__.py:154-194, index.py:90-123) plus the process-level seam of
 cpp/run_anchor (`run_anchor <ngenomes> <root> [<name> <fasta>]...`), and what the reference only does inside its viewer:
-`tree <index_dir> <genome> <chrom> [start] [end] [step]` prints the Newick tree of the genomes over a region; and
-`umaps <index_dir> [genome ...]` writes chrom_umaps.csv and genome_umap.csv (index.py:1107-1156) for an existing index."""
+`tree <index_dir> <genome> <chrom> [start] [end] [step]` prints the Newick tree of the genomes over a region;
+`umaps <index_dir> [genome ...]` writes chrom_umaps.csv and genome_umap.csv (index.py:1107-1156) for an existing index; and
+`find <index_dir> <genome> [chrom] [start] [end] [step] --have A,B --lack C,D` lists the runs of positions whose k-mers the
+`--have` genomes hold and the `--lack` genomes do not (the query scripts/query_index.py's "custom" branch sketches)."""
 import argparse
 import os
 import sys
@@ -49,6 +51,25 @@ def main(argv=None):
     tr.add_argument("--whole", action="store_true", help="the whole genome in place of a chromosome")
     tr.add_argument("--matrix", metavar="FILE", default=None, help="also write the pair counts as a tab-separated table")
     tr.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    fd = sub.add_parser("find", help="runs of positions whose k-mers the --have genomes hold and the --lack genomes lack, found "
+                                     "in the bitmap rows on the GPU: tab-separated chrom start end rows")
+    fd.add_argument("index_dir")
+    fd.add_argument("genome")
+    fd.add_argument("chrom", nargs="?", default=None)
+    fd.add_argument("start", nargs="?", type=int, default=None)
+    fd.add_argument("end", nargs="?", type=int, default=None)
+    fd.add_argument("step", nargs="?", type=int, default=1)
+    fd.add_argument("--have", default="", metavar="A,B", help="genomes that hold the k-mer")
+    fd.add_argument("--lack", default="", metavar="C,D", help="genomes that do not")
+    fd.add_argument("--min-have", type=int, default=None, metavar="N", help="at least N of --have (default: all of them)")
+    fd.add_argument("--max-lack", type=int, default=0, metavar="N", help="at most N of --lack (default: 0)")
+    fd.add_argument("--min-len", type=int, default=1, metavar="N", help="drop runs of fewer than N rows")
+    fd.add_argument("--max-gap", type=int, default=0, metavar="N", help="first merge runs at most N non-matching rows apart")
+    fd.add_argument("--density", type=int, default=None, metavar="BIN_SIZE",
+                    help="write chrom start matched rows per bin of BIN_SIZE positions instead")
+    fd.add_argument("--whole", action="store_true", help="the whole genome in place of a chromosome")
+    fd.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    fd.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -96,6 +117,33 @@ def main(argv=None):
                 print("Wrote", *idx[n].write_umaps())
         finally:
             idx.close()
+        return 0
+    if a.cmd == "find":
+        if a.whole == (a.chrom is not None):
+            ap.error("find: give a chromosome or --whole (and no region with --whole)")
+        if a.density is not None and (a.start is not None or a.min_len != 1 or a.max_gap != 0):
+            ap.error("find: --density takes whole chromosomes and no --min-len / --max-gap")
+        from .index import Index
+        have, lack = ([g for g in v.split(",") if g] for v in (a.have, a.lack))
+        idx = Index(a.index_dir, mode="r", device=a.device)
+        try:
+            if a.genome not in idx.genomes or not idx[a.genome].anchored:
+                ap.error(f"find: {a.genome!r} is not an anchor genome of {a.index_dir}")
+            for g in have + lack:
+                if g not in idx.genome_names:
+                    ap.error(f"find: unknown genome {g!r} (the index has {', '.join(idx.genome_names)})")
+            try:
+                if a.density is not None:
+                    out = idx.pattern_density(a.genome, have, lack, a.min_have, a.max_lack, None if a.chrom is None else [a.chrom],
+                                              a.step, a.density)
+                else:
+                    out = idx.find_pattern(a.genome, have, lack, a.min_have, a.max_lack, a.chrom, a.start, a.end, a.step,
+                                           a.min_len, a.max_gap)
+            except (ValueError, KeyError) as e:
+                ap.error(f"find: {e}")
+        finally:
+            idx.close()
+        out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
         return 0
     if a.cmd == "tree":
         if a.whole == (a.chrom is not None):

@@ -3445,6 +3445,106 @@ extern "C" int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, ui
     PG_API_END
 }
 
+// pattern runs over sampled rows (scripts/query_index.py's "custom" branch: the rows where these genomes' bits are set and
+// those genomes' are not): a count launch over the chunks of all windows, the scans of their counts on the host, and — when
+// the runs fit the caller's arrays — an emit launch
+extern "C" int pg_result_find_runs(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
+                                   const uint64_t *starts, const uint64_t *ends, const uint32_t *have_words,
+                                   const uint32_t *lack_words, uint32_t min_have, uint32_t max_lack, uint64_t cap,
+                                   uint32_t *run_start, uint32_t *run_end, uint64_t *nruns_out, uint64_t *matched_out,
+                                   uint64_t *total_out) {
+    PG_API_BEGIN
+    if (!r || !total_out || (nwin && (!contig || !starts || !ends || !nruns_out || !matched_out)) || (cap && (!run_start || !run_end)))
+        return fail(PG_E_INVALID, "pg_result_find_runs: NULL argument");
+    if (int e = check_step(r, step)) return e;
+    if (stride < 1) return fail(PG_E_INVALID, "pg_result_find_runs: stride must be >= 1");
+    if (nwin > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_find_runs: %u windows (at most 2^31 - 1 per call)", nwin);
+    const uint32_t N = r->N;
+    if (N < 1 || N > FIND_MAX_GENOMES) return fail(PG_E_INVALID, "pg_result_find_runs: %u genomes (1 to %u)", N, FIND_MAX_GENOMES);
+    if (int e = check_rows_readable(r, step)) return e;
+    std::vector<uint64_t> se;
+    uint64_t longest = 0;
+    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", se, &longest)) return e;
+    *total_out = 0;
+    if (nwin == 0) return PG_OK;
+    // the masks: a NULL pointer is the empty set, and the bits at and past N never count
+    const uint32_t ndw = (N + 31) / 32;
+    std::vector<uint32_t> mw((size_t)2 * ndw, 0);
+    for (uint32_t d = 0; d < ndw; ++d) {
+        const uint32_t valid = N - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (N - 32 * d)) - 1u;
+        if (have_words) mw[d] = have_words[d] & valid;
+        if (lack_words) mw[ndw + d] = lack_words[d] & valid;
+    }
+    // the chunks: FIND_CHUNK sampled rows each, a window's in order (an empty window has none)
+    std::vector<uint2> chunks;
+    std::vector<uint64_t> first((size_t)nwin + 1, 0);  // window i's chunks: [first[i], first[i + 1])
+    for (uint32_t i = 0; i < nwin; ++i) {
+        for (uint64_t c0 = starts[i]; c0 < ends[i]; c0 += FIND_CHUNK) chunks.push_back(make_uint2(i, (uint32_t)c0));
+        first[i + 1] = chunks.size();
+    }
+    for (uint32_t i = 0; i < nwin; ++i) nruns_out[i] = matched_out[i] = 0;
+    if (chunks.empty()) return PG_OK;
+    if (chunks.size() > 0x7FFFFFFFu)
+        return fail(PG_E_INVALID, "pg_result_find_runs: %zu chunks of %u sampled rows (at most 2^31 - 1 per call)", chunks.size(), FIND_CHUNK);
+    const uint32_t nchunks = (uint32_t)chunks.size();
+    if (int e = use_device(r->ctx)) return e;
+    if (int e = join_result(r)) return e;
+    hipStream_t st = r->ctx->stream;
+    const uint8_t *rows = step == 1 ? r->d_out1 : r->d_out100;
+    DevBuf<uint64_t> d_se;
+    DevBuf<uint32_t> d_mw;
+    DevBuf<uint2> d_chunks;
+    DevBuf<uint4> d_counts;
+    std::vector<uint4> counts(nchunks);
+    hipError_t e = d_se.alloc(se.size());
+    if (e == hipSuccess) e = d_mw.alloc(mw.size());
+    if (e == hipSuccess) e = d_chunks.alloc(nchunks);
+    if (e == hipSuccess) e = d_counts.alloc(nchunks);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_mw.get(), mw.data(), mw.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_chunks.get(), chunks.data(), (size_t)nchunks * sizeof(uint2), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = launch_find_runs(st, N, rows, stride, d_se.get(), d_se.get() + nwin, d_se.get() + 2 * (size_t)nwin, d_chunks.get(), nchunks,
+                             d_mw.get(), d_mw.get() + ndw, min_have, max_lack, d_counts.get(), nullptr, 0, nullptr, nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_find_runs: %s", hipGetErrorString(e));
+    // per window: the sums; per chunk: the starts and the ends of all chunks before it
+    std::vector<ulonglong2> offs(nchunks);
+    uint64_t nstarts = 0, nends = 0;
+    for (uint32_t i = 0; i < nwin; ++i) {
+        const uint64_t s0 = nstarts;
+        for (uint64_t c = first[i]; c < first[i + 1]; ++c) {
+            offs[c] = make_ulonglong2(nstarts, nends);
+            matched_out[i] += counts[c].x;
+            nstarts += counts[c].y;
+            nends += counts[c].z;
+        }
+        nruns_out[i] = nstarts - s0;
+        if (nstarts != nends)  // (every run of a window starts and ends inside it)
+            return fail(PG_E_HIP, "pg_result_find_runs: window %u: %llu run starts, %llu run ends", i, (unsigned long long)nstarts,
+                        (unsigned long long)nends);
+    }
+    const uint64_t total = nstarts;
+    *total_out = total;
+    if (total == 0 || cap == 0 || total > cap) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
+    DevBuf<ulonglong2> d_offs;
+    DevBuf<uint32_t> d_runs;
+    e = d_offs.alloc(nchunks);
+    if (e == hipSuccess) e = d_runs.alloc((size_t)2 * total);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_offs.get(), offs.data(), (size_t)nchunks * sizeof(ulonglong2), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = launch_find_runs(st, N, rows, stride, d_se.get(), d_se.get() + nwin, d_se.get() + 2 * (size_t)nwin, d_chunks.get(), nchunks,
+                             d_mw.get(), d_mw.get() + ndw, min_have, max_lack, nullptr, d_offs.get(), total, d_runs.get(),
+                             d_runs.get() + total);
+    if (e == hipSuccess) e = hipMemcpyAsync(run_start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(run_end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_find_runs: %s", hipGetErrorString(e));
+    return PG_OK;
+    PG_API_END
+}
+
 // exact k nearest neighbours among the rows of a host matrix (the neighbour graph of index.py:1131-1137's umap.UMAP): the
 // rows of every segment are cut into tiles of query rows, one block each, and all segments share one launch
 extern "C" int pg_knn_rows(pg_ctx *ctx, const float *X, uint64_t n, uint32_t ncols, uint32_t k, const uint64_t *seg,

@@ -212,6 +212,20 @@ constexpr uint32_t PAIRS_MAX_GENOMES = 512;
 hipError_t launch_pair_counts(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, uint32_t nwin,
                               uint32_t pieces, const uint64_t *base, const uint64_t *starts, const uint64_t *ends,
                               unsigned long long *pairs);
+// pattern runs (pg_find.hip): a sampled row matches iff popcount(row & have) >= min_have and popcount(row & lack) <= max_lack
+// (have / lack: ceil(N / 32) words each, bits at and past N zero).  Window i = sampled rows [starts[i], ends[i]) of the rows at
+// rows + base[i], as the bins above; chunk c = {window, first sampled row}: the FIND_CHUNK sampled rows from there, cut at its
+// window's end, a window's chunks consecutive and in order.  One block per chunk; no block waits for another.
+//   offs == NULL  count: counts[c] = {matching rows, run starts, run ends, 0} of chunk c
+//   offs != NULL  emit: offs[c] = {starts, ends} of all chunks before c; the sampled row numbers of the run starts / the
+//                 exclusive run ends go to run_start / run_end from there on (entries at or past `total` are never written)
+// 1 <= N <= FIND_MAX_GENOMES.
+constexpr uint32_t FIND_CHUNK = 4096;  // sampled rows per chunk, a multiple of 256
+constexpr uint32_t FIND_MAX_GENOMES = 4096;
+hipError_t launch_find_runs(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, const uint64_t *base,
+                            const uint64_t *starts, const uint64_t *ends, const uint2 *chunks, uint32_t nchunks,
+                            const uint32_t *have, const uint32_t *lack, uint32_t min_have, uint32_t max_lack, uint4 *counts,
+                            const ulonglong2 *offs, uint64_t total, uint32_t *run_start, uint32_t *run_end);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

@@ -47,6 +47,12 @@ COLUMNS_DIRECT = os.environ.get("PG_COLUMNS_DIRECT", "0") not in ("", "0")
 
 _ADOPT_LOCK = threading.Lock()
 
+# pattern runs (pg_find.hip).  FIND_CHUNK: sampled rows per workgroup — pg_kernels.h's constant, restated for the tests that aim
+# at chunk edges (tests/test_find_cpu.py holds the two together); FIND_FIRST_CAP: runs AnchorResult.find_runs makes room for in
+# its first call — 512 KiB of sampled row numbers; a second call with the exact total follows only beyond it
+FIND_CHUNK = 4096
+FIND_FIRST_CAP = 1 << 16
+
 
 def tile_positions() -> int:
     """k-mer positions per tile (launch unit; a bit-column block holds tile_positions() // 8 bytes per tile and genome:
@@ -872,6 +878,58 @@ class AnchorResult:
         check(self._lib.pg_result_pair_counts(self._h, int(step), int(stride), n, _ptr(contigs), _ptr(starts), _ptr(ends),
                                               _ptr(out)))
         return out
+
+    def _find(self, contigs, starts, ends, have_words, lack_words, min_have, max_lack, step, stride, cap):
+        """one pg_result_find_runs call -> (total, nruns [nwin], matched [nwin], run starts, run ends; the last two None
+        unless 0 < total <= cap)"""
+        contigs = np.ascontiguousarray(contigs, np.uint32)
+        starts = np.ascontiguousarray(starts, np.uint64)
+        ends = np.ascontiguousarray(ends, np.uint64)
+        n, ndw = len(starts), (self.ngenomes + 31) // 32
+        if len(contigs) != n or len(ends) != n:
+            raise ValueError("contigs, starts and ends need one entry per window")
+        if int(min_have) < 0 or int(max_lack) < 0:
+            raise ValueError(f"min_have and max_lack must not be negative, got {min_have}, {max_lack}")
+        masks = []
+        for given in (have_words, lack_words):
+            w = np.zeros(ndw, np.uint32)
+            if given is not None:
+                given = np.asarray(given, np.uint32).ravel()
+                w[:min(ndw, len(given))] = given[:ndw]
+            masks.append(w)
+        nruns, matched = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        rs, re = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        total = C.c_uint64(0)
+        check(self._lib.pg_result_find_runs(self._h, int(step), int(stride), n, _ptr(contigs), _ptr(starts), _ptr(ends),
+                                            _ptr(masks[0]), _ptr(masks[1]), min(int(min_have), 0xFFFFFFFF),
+                                            min(int(max_lack), 0xFFFFFFFF), int(cap), _ptr(rs) if cap else None,
+                                            _ptr(re) if cap else None, _ptr(nruns), _ptr(matched), C.byref(total)))
+        fits = 0 < total.value <= cap
+        return total.value, nruns, matched, rs[:total.value] if fits else None, re[:total.value] if fits else None
+
+    def find_runs(self, contigs, starts, ends, have_words, lack_words, min_have, max_lack, step: int = 1, stride: int = 1):
+        """(runs [total, 3] int64, matched [nwin] uint64): the maximal runs of consecutive MATCHING sampled rows of every
+        window — window i = sampled rows [starts[i], ends[i]) of contig contigs[i]'s bitmap.<step> rows, sampled row
+        j = row j * stride; a row matches iff popcount(row & have) >= min_have and popcount(row & lack) <= max_lack
+        (``have_words`` / ``lack_words``: ceil(N / 32) words, None: the empty set).  A row of ``runs`` is (window, first
+        sampled row, exclusive end), sorted by (window, start); ``matched[i]`` the matching sampled rows of window i.  The
+        window's edges cut runs.  k_find_runs: a first call with room for FIND_FIRST_CAP runs, a second one only when
+        there are more."""
+        args = (contigs, starts, ends, have_words, lack_words, min_have, max_lack, step, stride)
+        total, nruns, matched, rs, re = self._find(*args, FIND_FIRST_CAP)
+        if total > FIND_FIRST_CAP:
+            total, nruns, matched, rs, re = self._find(*args, total)
+        runs = np.zeros((total, 3), np.int64)
+        if total:
+            runs[:, 0] = np.repeat(np.arange(len(nruns), dtype=np.int64), nruns.astype(np.int64))
+            runs[:, 1] = rs
+            runs[:, 2] = re
+        return runs, matched
+
+    def find_counts(self, contigs, starts, ends, have_words, lack_words, min_have, max_lack, step: int = 1, stride: int = 1):
+        """(nruns [nwin] uint64, matched [nwin] uint64) of ``find_runs``' windows: the count launch alone (capacity 0)"""
+        _, nruns, matched, _, _ = self._find(contigs, starts, ends, have_words, lack_words, min_have, max_lack, step, stride, 0)
+        return nruns, matched
 
     def write_bgzf(self, step: int, gz_path: str, gzi_path: Optional[str] = None, level: int = 6,
                    threads: int = 1, first_contig: int = 0, ncontigs: Optional[int] = None) -> None:

@@ -1240,6 +1240,17 @@ class Index:
         """N x N pair counts of the genomes over the rows ``query_bitmap(genome, chrom, start, end, step)`` returns"""
         return self.genomes[genome].pair_counts(chrom, start, end, step)
 
+    def find_pattern(self, genome, have, lack=(), min_have=None, max_lack=0, chrom=None, start=None, end=None, step=1,
+                     min_len=1, max_gap=0) -> pd.DataFrame:
+        """the runs of rows of ``query_bitmap(genome, chrom, start, end, step)`` that at least ``min_have`` of the ``have``
+        genomes hold and at most ``max_lack`` of the ``lack`` genomes do (``Genome.find_pattern``)"""
+        return self.genomes[genome].find_pattern(have, lack, min_have, max_lack, chrom, start, end, step, min_len, max_gap)
+
+    def pattern_density(self, genome, have, lack=(), min_have=None, max_lack=0, chroms=None, step=1,
+                        bin_size=1_000_000) -> pd.DataFrame:
+        """the matching rows of every bin of ``bin_size`` positions (``Genome.pattern_density``)"""
+        return self.genomes[genome].pattern_density(have, lack, min_have, max_lack, chroms, step, bin_size)
+
     def region_tree(self, genome, chrom, start=None, end=None, step=None) -> "RegionTree":
         """The tree of the genomes over a region, as the viewer draws it (view.py:751-764: create_tree) — but from the pair
         counts of EVERY row of the region at ``step`` (default: the low-resolution step), not from a random sample of
@@ -1797,6 +1808,92 @@ class Genome:
         total, _ = self._pair_counts(chrom, start, end, step)
         names = pd.Index(self.index.genome_names)
         return pd.DataFrame(total, index=names, columns=names)
+
+    # ---- FIND: runs of rows that these genomes hold and those lack (scripts/query_index.py: the "custom" query) ----
+    def find_pattern(self, have, lack=(), min_have=None, max_lack=0, chrom=None, start=None, end=None, step: int = 1,
+                     min_len: int = 1, max_gap: int = 0) -> pd.DataFrame:
+        """chr, start, end, rows: the runs of consecutive rows of ``query(chrom, start, end, step)`` that MATCH — at least
+        ``min_have`` of the ``have`` genomes (names or columns; default: all of them) hold the row's k-mer and at most
+        ``max_lack`` of the ``lack`` genomes do.  ``start`` is the label ``query`` gives the run's first row, ``end`` the label
+        of its last row + 1.  Runs separated by at most ``max_gap`` non-matching rows are merged, then spans shorter than
+        ``min_len`` rows dropped; ``rows`` = the matching rows inside the span.  ``chrom=None``: every chromosome, and no run
+        joins two of them.  The rows are inflated into HBM in consecutive pieces of at most ``similarity_budget`` bytes and
+        searched there by k_find_runs; only the runs come back."""
+        from . import find
+        step = int(step)
+        if step < 1:
+            raise ValueError(f"step must be positive, got {step}")
+        if self.chrs is None:
+            self.load_chrs()
+        if chrom is None and (start is not None or end is not None):
+            raise ValueError("start and end need a chromosome")
+        for c in ([] if chrom is None else [chrom]):
+            if c not in self.chrs.index:
+                raise KeyError(f"{self.name}: no chromosome {c!r}")
+        hw, lw, min_have, max_lack = find.rule_words(self.index.genome_names, have, lack, min_have, max_lack)
+        find.merge_runs([], [], min_len, max_gap)  # (its argument checks, before anything is read)
+        frames = []
+        for c in (list(self.chrs.index) if chrom is None else [chrom]):
+            bstep, stride, row0, nrows = self._region_rows(c, start, end, step)
+            # pieces as _pair_counts cuts them: at most similarity_budget bytes of HBM each, a piece starting at the first row
+            # of the region's sampling phase inside it
+            per = max(1, int(self.similarity_budget) // (self.nbytes * bstep))
+            pieces = []
+            for p0 in range(0, nrows, per):
+                p1 = min(p0 + per, nrows)
+                first = -(-p0 // stride) * stride
+                if first >= p1:
+                    continue
+                ns = (p1 - first - 1) // stride + 1
+                res = self._rows_region(bstep, row0 + first, p1 - first)
+                try:
+                    runs, _ = res.find_runs([0], [0], [ns], hw, lw, min_have, max_lack, step=bstep, stride=stride)
+                finally:
+                    res.close()
+                pieces.append((first // stride, ns, runs[:, 1], runs[:, 2]))
+            s, e, rows = find.merge_runs(*find.join_pieces(pieces), min_len, max_gap)
+            label0 = 0 if start is None else int(start)  # (query labels its j-th row start + j * step)
+            frames.append(pd.DataFrame({"chr": np.full(len(s), c, object), "start": label0 + s * step,
+                                        "end": label0 + (e - 1) * step + 1, "rows": rows}))
+        return pd.concat(frames, ignore_index=True)
+
+    def pattern_density(self, have, lack=(), min_have=None, max_lack=0, chroms=None, step: int = 1,
+                        bin_size: int = 1_000_000) -> pd.DataFrame:
+        """chr, start, matched, rows: per bin of ``bin_size`` positions of every chromosome (bins and batches of chromosomes as
+        ``kmer_similarity_bins`` takes them), the rows sampled every ``step`` that match the rule of ``find_pattern`` and the
+        sampled rows of the bin.  One k_find_runs count launch per batch; no run is written."""
+        from . import find
+        step, bin_size = int(step), int(bin_size)
+        if step < 1 or bin_size < 1:
+            raise ValueError(f"step and bin_size must be positive, got {step}, {bin_size}")
+        if self.chrs is None:
+            self.load_chrs()
+        chroms = list(self.chrs.index) if chroms is None else [str(c) for c in chroms]
+        for c in chroms:
+            if c not in self.chrs.index:
+                raise KeyError(f"{self.name}: no chromosome {c!r}")
+        hw, lw, min_have, max_lack = find.rule_words(self.index.genome_names, have, lack, min_have, max_lack)
+        bstep = max(s for s in self.steps if step % s == 0)
+        stride = step // bstep
+        geo = {c: self.similarity_bin_geometry(int(self.chrs.loc[c, "size"]), step, bin_size) for c in chroms}
+        matched = {}
+        for batch in self._annotate_batches([c for c in dict.fromkeys(chroms) if len(geo[c][0])], self.similarity_budget):
+            res = self._rows_from_disk(batch, bstep)
+            try:
+                ci = np.concatenate([np.full(len(geo[c][0]), i, np.uint32) for i, c in enumerate(batch)])
+                st = np.concatenate([geo[c][1] for c in batch])
+                en = np.concatenate([geo[c][2] for c in batch])
+                _, m = res.find_counts(ci, st, en, hw, lw, min_have, max_lack, step=bstep, stride=stride)
+            finally:
+                res.close()
+            at = 0
+            for c in batch:
+                matched[c] = m[at:at + len(geo[c][0])].astype(np.int64)
+                at += len(geo[c][0])
+        frames = [pd.DataFrame({"chr": np.full(len(geo[c][0]), c, object), "start": geo[c][0] * bin_size,
+                                "matched": matched.get(c, np.zeros(0, np.int64)), "rows": geo[c][2] - geo[c][1]}) for c in chroms]
+        return pd.concat(frames, ignore_index=True) if frames else pd.DataFrame(
+            {"chr": np.zeros(0, object), "start": np.zeros(0, np.int64), "matched": np.zeros(0, np.int64), "rows": np.zeros(0, np.int64)})
 
     # ---- UMAPS: chrom_umaps.csv and genome_umap.csv (index.py:1100-1167) ----
     @property

@@ -379,6 +379,28 @@ class Inflater:
                 return s, L
         raise InflateError(what)
 
+    def dynamic_header(self) -> dict:
+        """the header of a dynamic block behind its three BFINAL / BTYPE bits: HLIT / HDIST / HCLEN and the code lengths"""
+        hlit, hdist, hclen = self.bits(5) + 257, self.bits(5) + 1, self.bits(4) + 4
+        cl = [0] * 19
+        for i in range(hclen):
+            cl[CL_ORDER[i]] = self.bits(3)
+        clt = self.table(cl)
+        lens: List[int] = []
+        while len(lens) < hlit + hdist:
+            s, _ = self.sym(clt, "invalid code lengths set")
+            if s < 16:
+                lens.append(s)
+            elif s == 16:
+                lens += [lens[-1]] * (3 + self.bits(2))
+            elif s == 17:
+                lens += [0] * (3 + self.bits(3))
+            else:
+                lens += [0] * (11 + self.bits(7))
+        if len(lens) > hlit + hdist:
+            raise InflateError("invalid bit length repeat")
+        return dict(hlit=hlit, hdist=hdist, hclen=hclen, cl_lens=cl, ll_lens=lens[:hlit], d_lens=lens[hlit:])
+
     def run(self) -> bytes:
         last = 0
         while not last:
@@ -402,26 +424,9 @@ class Inflater:
             if t == 1:
                 ll_lens, d_lens = FIXED_LL, FIXED_D
             else:
-                hlit, hdist, hclen = self.bits(5) + 257, self.bits(5) + 1, self.bits(4) + 4
-                cl = [0] * 19
-                for i in range(hclen):
-                    cl[CL_ORDER[i]] = self.bits(3)
-                clt = self.table(cl)
-                lens: List[int] = []
-                while len(lens) < hlit + hdist:
-                    s, _ = self.sym(clt, "invalid code lengths set")
-                    if s < 16:
-                        lens.append(s)
-                    elif s == 16:
-                        lens += [lens[-1]] * (3 + self.bits(2))
-                    elif s == 17:
-                        lens += [0] * (3 + self.bits(3))
-                    else:
-                        lens += [0] * (11 + self.bits(7))
-                if len(lens) > hlit + hdist:
-                    raise InflateError("invalid bit length repeat")
-                ll_lens, d_lens = lens[:hlit], lens[hlit:]
-                blk.update(hlit=hlit, hdist=hdist, hclen=hclen, cl_lens=cl, ll_lens=ll_lens, d_lens=d_lens)
+                hdr = self.dynamic_header()
+                ll_lens, d_lens = hdr["ll_lens"], hdr["d_lens"]
+                blk.update(hdr)
             llt, dt = self.table(ll_lens), self.table(d_lens)
             while True:
                 s, L = self.sym(llt, "invalid literal/length code")

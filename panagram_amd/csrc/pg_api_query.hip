@@ -1,0 +1,328 @@
+// pg_api_query.hip — host side of the C-ABI: window queries over a result's finished rows, k-NN of rows.
+#include "pg_host.h"
+
+// Checks shared by the entry points that read a result's rows, beside check_step (pg_api.hip): one wording each, whoever asks.
+static int check_rows_readable(const pg_result *r, int step) {
+    if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
+    if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
+    if (step != 1 && (r->flags & PG_ANCHOR_ROWS_ONLY) && !r->ev_epi && !r->rows_valid)
+        return fail(PG_E_INVALID, "rows-only result: the low-resolution rows need pg_rows_epilogue first");
+    return PG_OK;
+}
+// n windows ("bin", "window": the noun of the messages) of sampled rows, refused unless each lies within its contig ->
+// se[3 * n]: device byte offset of the contig's rows, then [start, end) in sampled rows; *longest: the longest of them
+static int gather_windows(const pg_result *r, int step, uint32_t stride, uint32_t n, const uint32_t *contig, const uint64_t *starts,
+                          const uint64_t *ends, const char *noun, std::vector<uint64_t> &se, uint64_t *longest) {
+    se.assign((size_t)n * 3, 0);
+    *longest = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (contig[i] >= r->ad.size()) return fail(PG_E_INVALID, "%s %u: contig %u out of range", noun, i, contig[i]);
+        const AnchorDesc &a = r->ad[contig[i]];
+        const uint64_t nrows = step == 1 ? (uint64_t)a.nkmers : r->nrows100[contig[i]];
+        if (starts[i] > ends[i]) return fail(PG_E_INVALID, "%s %u: start %llu past end %llu", noun, i, (unsigned long long)starts[i],
+                                             (unsigned long long)ends[i]);
+        if (ends[i] > starts[i] && (nrows == 0 || ends[i] - 1 > (nrows - 1) / stride))
+            return fail(PG_E_INVALID, "%s %u: sampled row %llu (x %u) past the %llu rows of contig %u", noun, i,
+                        (unsigned long long)(ends[i] - 1), stride, (unsigned long long)nrows, contig[i]);
+        se[i] = step == 1 ? a.out_off : a.out100_off;
+        se[n + i] = starts[i];
+        se[2 * (size_t)n + i] = ends[i];
+        *longest = std::max(*longest, ends[i] - starts[i]);
+    }
+    return PG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// window statistics over finished rows resident in HBM
+// ---------------------------------------------------------------------------
+extern "C" int pg_result_window_stats(pg_result *r, uint32_t idx, int step, uint32_t nwin, const uint64_t *starts,
+                                      const uint64_t *ends, uint64_t *hist, uint64_t *colsums) {
+    PG_API_BEGIN
+    if (!r || (nwin && (!starts || !ends || !hist))) return fail(PG_E_INVALID, "pg_result_window_stats: NULL argument");
+    if (idx >= r->ad.size()) return fail(PG_E_INVALID, "contig %u out of range", idx);
+    if (int e = check_step(r, step)) return e;
+    if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
+    if (nwin == 0) return PG_OK;
+    if (int e = use_device(r->ctx)) return e;
+    if (int e = join_result(r)) return e;
+    hipStream_t st = r->ctx->stream;
+    const uint32_t N = r->N;
+    const AnchorDesc &a = r->ad[idx];
+    const uint8_t *rows = step == 1 ? r->d_out1 + a.out_off : r->d_out100 + a.out100_off;
+    const uint64_t nrows = step == 1 ? (uint64_t)a.nkmers : r->nrows100[idx];
+    uint64_t longest = 0;
+    for (uint32_t i = 0; i < nwin; ++i)
+        if (ends[i] > starts[i]) longest = std::max(longest, std::min(ends[i], nrows) - std::min(starts[i], nrows));
+    const uint32_t pieces = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, longest / 32768));
+    DevBuf<uint64_t> d_se;
+    DevBuf<unsigned long long> d_out;
+    const size_t nh = (size_t)nwin * (N + 1), nc = colsums ? (size_t)nwin * N : 0;
+    hipError_t e = d_se.alloc((size_t)nwin * 2);
+    if (e == hipSuccess) e = d_out.alloc(nh + nc);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), starts, (size_t)nwin * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get() + nwin, ends, (size_t)nwin * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, (nh + nc) * 8, st);
+    if (e == hipSuccess)
+        e = launch_window_stats(st, N, rows, nrows, nwin, pieces, d_se.get(), d_se.get() + nwin, d_out.get(),
+                                colsums ? d_out.get() + nh : nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(hist, d_out.get(), nh * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && colsums) e = hipMemcpyAsync(colsums, d_out.get() + nh, nc * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_window_stats: %s", hipGetErrorString(e));
+    return PG_OK;
+    PG_API_END
+}
+
+// masked per-bin column sums over sampled rows (call_introgressions.py: bitmap_to_bins): one launch for bins of any of
+// the result's contigs
+extern "C" int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, uint32_t nbins, const uint32_t *contig,
+                                     const uint64_t *starts, const uint64_t *ends, const uint32_t *keep_words, int omit_fixed,
+                                     uint64_t *cs_out, uint64_t *kept_out) {
+    PG_API_BEGIN
+    if (!r || (nbins && (!contig || !starts || !ends || !cs_out || !kept_out)))
+        return fail(PG_E_INVALID, "pg_result_bin_colsums: NULL argument");
+    if (int e = check_step(r, step)) return e;
+    if (stride < 1) return fail(PG_E_INVALID, "pg_result_bin_colsums: stride must be >= 1");
+    if (nbins > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_bin_colsums: %u bins (at most 2^31 - 1 per call)", nbins);
+    const uint32_t N = r->N;
+    if (N < 1 || N > 4096) return fail(PG_E_INVALID, "pg_result_bin_colsums: %u genomes (1 to 4096)", N);
+    if (int e = check_rows_readable(r, step)) return e;
+    const uint32_t ndw = (N + 31) / 32;
+    std::vector<uint64_t> se;
+    uint64_t longest = 0;
+    if (int e = gather_windows(r, step, stride, nbins, contig, starts, ends, "bin", se, &longest)) return e;
+    std::vector<uint32_t> kw(ndw, 0);
+    if (keep_words)
+        for (uint32_t d = 0; d < ndw; ++d) kw[d] = keep_words[d] & (N - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (N - 32 * d)) - 1u);
+    if (nbins == 0) return PG_OK;
+    if (int e = use_device(r->ctx)) return e;
+    if (int e = join_result(r)) return e;
+    hipStream_t st = r->ctx->stream;
+    // pieces: about 32 K sampled rows each for the longest bin, and enough blocks to fill the device
+    uint32_t pieces = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, longest / 32768));
+    while (pieces < 256 && (uint64_t)nbins * pieces < 4096 && (uint64_t)pieces * 4096 < longest) pieces *= 2;
+    DevBuf<uint64_t> d_se;
+    DevBuf<uint32_t> d_kw;
+    DevBuf<unsigned long long> d_out;
+    const size_t nc = (size_t)nbins * N;
+    hipError_t e = d_se.alloc(se.size());
+    if (e == hipSuccess) e = d_kw.alloc(ndw);
+    if (e == hipSuccess) e = d_out.alloc(nc + nbins);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_kw.get(), kw.data(), (size_t)ndw * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, (nc + nbins) * 8, st);
+    if (e == hipSuccess)
+        e = launch_bin_colsums(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nbins, pieces, d_se.get(), d_se.get() + nbins,
+                               d_se.get() + 2 * (size_t)nbins, d_kw.get(), omit_fixed ? 1u : 0u, d_out.get(), d_out.get() + nc);
+    if (e == hipSuccess) e = hipMemcpyAsync(cs_out, d_out.get(), nc * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(kept_out, d_out.get() + nc, (size_t)nbins * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_bin_colsums: %s", hipGetErrorString(e));
+    return PG_OK;
+    PG_API_END
+}
+
+// pair counts over sampled rows (the matrix behind view.py:751-764's tree of the genomes over a region): one launch for
+// windows of any of the result's contigs
+extern "C" int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
+                                     const uint64_t *starts, const uint64_t *ends, uint64_t *pairs_out) {
+    PG_API_BEGIN
+    if (!r || (nwin && (!contig || !starts || !ends || !pairs_out)))
+        return fail(PG_E_INVALID, "pg_result_pair_counts: NULL argument");
+    if (int e = check_step(r, step)) return e;
+    if (stride < 1) return fail(PG_E_INVALID, "pg_result_pair_counts: stride must be >= 1");
+    if (nwin > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_pair_counts: %u windows (at most 2^31 - 1 per call)", nwin);
+    const uint32_t N = r->N;
+    if (N < 1 || N > PAIRS_MAX_GENOMES)
+        return fail(PG_E_INVALID, "pg_result_pair_counts: %u genomes (the pair counts take 1 to %u)", N, PAIRS_MAX_GENOMES);
+    if (int e = check_rows_readable(r, step)) return e;
+    std::vector<uint64_t> se;
+    uint64_t longest = 0;
+    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", se, &longest)) return e;
+    if (nwin == 0) return PG_OK;
+    if (int e = use_device(r->ctx)) return e;
+    if (int e = join_result(r)) return e;
+    hipStream_t st = r->ctx->stream;
+    // pieces: about 32 K sampled rows each for the longest window, then doubled while the grid has fewer than 4096 blocks
+    // (a lone window of 32 M rows in 256 pieces leaves three quarters of the SIMDs' wave slots empty: 3.3 ms, in 2048
+    // pieces as below) and a piece keeps more than 4096 rows (it ends with up to N^2 / 2 atomics)
+    uint32_t pieces = (uint32_t)std::min<uint64_t>(2048, std::max<uint64_t>(1, longest / 32768));
+    while (pieces < 2048 && (uint64_t)nwin * pieces < 4096 && (uint64_t)pieces * 4096 < longest) pieces *= 2;
+    DevBuf<uint64_t> d_se;
+    DevBuf<unsigned long long> d_out;
+    const size_t nc = (size_t)nwin * N * N;
+    hipError_t e = d_se.alloc(se.size());
+    if (e == hipSuccess) e = d_out.alloc(nc);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, nc * 8, st);
+    if (e == hipSuccess)
+        e = launch_pair_counts(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nwin, pieces, d_se.get(), d_se.get() + nwin,
+                               d_se.get() + 2 * (size_t)nwin, d_out.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(pairs_out, d_out.get(), nc * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_pair_counts: %s", hipGetErrorString(e));
+    // the kernel counts the pairs on and above the diagonal: the matrix is symmetric
+    for (size_t i = 0; i < nwin; ++i) {
+        uint64_t *m = pairs_out + i * N * N;
+        for (uint32_t a = 0; a < N; ++a)
+            for (uint32_t b = a + 1; b < N; ++b) m[(size_t)b * N + a] = m[(size_t)a * N + b];
+    }
+    return PG_OK;
+    PG_API_END
+}
+
+// pattern runs over sampled rows (scripts/query_index.py's "custom" branch: the rows where these genomes' bits are set and
+// those genomes' are not): a count launch over the chunks of all windows, the scans of their counts on the host, and — when
+// the runs fit the caller's arrays — an emit launch
+extern "C" int pg_result_find_runs(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
+                                   const uint64_t *starts, const uint64_t *ends, const uint32_t *have_words,
+                                   const uint32_t *lack_words, uint32_t min_have, uint32_t max_lack, uint64_t cap,
+                                   uint32_t *run_start, uint32_t *run_end, uint64_t *nruns_out, uint64_t *matched_out,
+                                   uint64_t *total_out) {
+    PG_API_BEGIN
+    if (!r || !total_out || (nwin && (!contig || !starts || !ends || !nruns_out || !matched_out)) || (cap && (!run_start || !run_end)))
+        return fail(PG_E_INVALID, "pg_result_find_runs: NULL argument");
+    if (int e = check_step(r, step)) return e;
+    if (stride < 1) return fail(PG_E_INVALID, "pg_result_find_runs: stride must be >= 1");
+    if (nwin > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_find_runs: %u windows (at most 2^31 - 1 per call)", nwin);
+    const uint32_t N = r->N;
+    if (N < 1 || N > FIND_MAX_GENOMES) return fail(PG_E_INVALID, "pg_result_find_runs: %u genomes (1 to %u)", N, FIND_MAX_GENOMES);
+    if (int e = check_rows_readable(r, step)) return e;
+    std::vector<uint64_t> se;
+    uint64_t longest = 0;
+    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", se, &longest)) return e;
+    *total_out = 0;
+    if (nwin == 0) return PG_OK;
+    // the masks: a NULL pointer is the empty set, and the bits at and past N never count
+    const uint32_t ndw = (N + 31) / 32;
+    std::vector<uint32_t> mw((size_t)2 * ndw, 0);
+    for (uint32_t d = 0; d < ndw; ++d) {
+        const uint32_t valid = N - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (N - 32 * d)) - 1u;
+        if (have_words) mw[d] = have_words[d] & valid;
+        if (lack_words) mw[ndw + d] = lack_words[d] & valid;
+    }
+    // the chunks: FIND_CHUNK sampled rows each, a window's in order (an empty window has none)
+    std::vector<uint2> chunks;
+    std::vector<uint64_t> first((size_t)nwin + 1, 0);  // window i's chunks: [first[i], first[i + 1])
+    for (uint32_t i = 0; i < nwin; ++i) {
+        for (uint64_t c0 = starts[i]; c0 < ends[i]; c0 += FIND_CHUNK) chunks.push_back(make_uint2(i, (uint32_t)c0));
+        first[i + 1] = chunks.size();
+    }
+    for (uint32_t i = 0; i < nwin; ++i) nruns_out[i] = matched_out[i] = 0;
+    if (chunks.empty()) return PG_OK;
+    if (chunks.size() > 0x7FFFFFFFu)
+        return fail(PG_E_INVALID, "pg_result_find_runs: %zu chunks of %u sampled rows (at most 2^31 - 1 per call)", chunks.size(), FIND_CHUNK);
+    const uint32_t nchunks = (uint32_t)chunks.size();
+    if (int e = use_device(r->ctx)) return e;
+    if (int e = join_result(r)) return e;
+    hipStream_t st = r->ctx->stream;
+    const uint8_t *rows = step == 1 ? r->d_out1 : r->d_out100;
+    DevBuf<uint64_t> d_se;
+    DevBuf<uint32_t> d_mw;
+    DevBuf<uint2> d_chunks;
+    DevBuf<uint4> d_counts;
+    std::vector<uint4> counts(nchunks);
+    hipError_t e = d_se.alloc(se.size());
+    if (e == hipSuccess) e = d_mw.alloc(mw.size());
+    if (e == hipSuccess) e = d_chunks.alloc(nchunks);
+    if (e == hipSuccess) e = d_counts.alloc(nchunks);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_mw.get(), mw.data(), mw.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_chunks.get(), chunks.data(), (size_t)nchunks * sizeof(uint2), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = launch_find_runs(st, N, rows, stride, d_se.get(), d_se.get() + nwin, d_se.get() + 2 * (size_t)nwin, d_chunks.get(), nchunks,
+                             d_mw.get(), d_mw.get() + ndw, min_have, max_lack, d_counts.get(), nullptr, 0, nullptr, nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_find_runs: %s", hipGetErrorString(e));
+    // per window: the sums; per chunk: the starts and the ends of all chunks before it
+    std::vector<ulonglong2> offs(nchunks);
+    uint64_t nstarts = 0, nends = 0;
+    for (uint32_t i = 0; i < nwin; ++i) {
+        const uint64_t s0 = nstarts;
+        for (uint64_t c = first[i]; c < first[i + 1]; ++c) {
+            offs[c] = make_ulonglong2(nstarts, nends);
+            matched_out[i] += counts[c].x;
+            nstarts += counts[c].y;
+            nends += counts[c].z;
+        }
+        nruns_out[i] = nstarts - s0;
+        if (nstarts != nends)  // (every run of a window starts and ends inside it)
+            return fail(PG_E_HIP, "pg_result_find_runs: window %u: %llu run starts, %llu run ends", i, (unsigned long long)nstarts,
+                        (unsigned long long)nends);
+    }
+    const uint64_t total = nstarts;
+    *total_out = total;
+    if (total == 0 || cap == 0 || total > cap) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
+    DevBuf<ulonglong2> d_offs;
+    DevBuf<uint32_t> d_runs;
+    e = d_offs.alloc(nchunks);
+    if (e == hipSuccess) e = d_runs.alloc((size_t)2 * total);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_offs.get(), offs.data(), (size_t)nchunks * sizeof(ulonglong2), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess)
+        e = launch_find_runs(st, N, rows, stride, d_se.get(), d_se.get() + nwin, d_se.get() + 2 * (size_t)nwin, d_chunks.get(), nchunks,
+                             d_mw.get(), d_mw.get() + ndw, min_have, max_lack, nullptr, d_offs.get(), total, d_runs.get(),
+                             d_runs.get() + total);
+    if (e == hipSuccess) e = hipMemcpyAsync(run_start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(run_end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_find_runs: %s", hipGetErrorString(e));
+    return PG_OK;
+    PG_API_END
+}
+
+// exact k nearest neighbours among the rows of a host matrix (the neighbour graph of index.py:1131-1137's umap.UMAP): the
+// rows of every segment are cut into tiles of query rows, one block each, and all segments share one launch
+extern "C" int pg_knn_rows(pg_ctx *ctx, const float *X, uint64_t n, uint32_t ncols, uint32_t k, const uint64_t *seg,
+                           uint32_t nseg, int32_t *idx_out, float *d2_out) {
+    PG_API_BEGIN
+    if (k < 1 || k > KNN_MAX_K) return fail(PG_E_INVALID, "pg_knn_rows: k = %u (1 to %u neighbours)", k, KNN_MAX_K);
+    if (ncols < 1 || ncols > KNN_MAX_COLS) return fail(PG_E_INVALID, "pg_knn_rows: %u columns (1 to %u)", ncols, KNN_MAX_COLS);
+    if (!ctx || (n && (!X || !idx_out || !d2_out))) return fail(PG_E_INVALID, "pg_knn_rows: NULL argument");
+    if (n > 0x7FFFFFFFull) return fail(PG_E_INVALID, "pg_knn_rows: %llu rows (row numbers are 31 bits)", (unsigned long long)n);
+    const uint64_t whole[2] = {0, n};
+    if (!seg) {
+        seg = whole;
+        nseg = 1;
+    }
+    if (nseg > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_knn_rows: %u segments", nseg);
+    if (seg[0] != 0 || seg[nseg] != n)
+        return fail(PG_E_INVALID, "pg_knn_rows: the segments must run from row 0 to row %llu, not %llu to %llu",
+                    (unsigned long long)n, (unsigned long long)seg[0], (unsigned long long)seg[nseg]);
+    for (uint32_t s = 0; s < nseg; ++s)
+        if (seg[s] > seg[s + 1])
+            return fail(PG_E_INVALID, "pg_knn_rows: segment offsets not ascending (%llu before %llu at segment %u)",
+                        (unsigned long long)seg[s], (unsigned long long)seg[s + 1], s);
+    if (n == 0) return PG_OK;
+    // tiles of 256 query rows; of 64 — one wave per block — while 256 would leave the grid short of two blocks per CU
+    uint64_t t256 = 0;
+    for (uint32_t s = 0; s < nseg; ++s) t256 += (seg[s + 1] - seg[s] + 255) / 256;
+    const uint32_t threads = t256 < 512 ? 64 : 256;
+    std::vector<uint32_t> tiles;
+    for (uint32_t s = 0; s < nseg; ++s)
+        for (uint64_t r = seg[s]; r < seg[s + 1]; r += threads) {
+            const uint32_t t[4] = {(uint32_t)r, (uint32_t)std::min<uint64_t>(threads, seg[s + 1] - r), (uint32_t)seg[s],
+                                   (uint32_t)seg[s + 1]};
+            tiles.insert(tiles.end(), t, t + 4);
+        }
+    const uint32_t ntiles = (uint32_t)(tiles.size() / 4);
+    if (int e = use_device(ctx)) return e;
+    hipStream_t st = ctx->stream;
+    DevBuf<float> d_x, d_d2;
+    DevBuf<int32_t> d_idx;
+    DevBuf<uint32_t> d_tiles;
+    const size_t xb = (size_t)n * ncols * 4, ob = (size_t)n * k * 4;
+    hipError_t e = d_x.alloc((size_t)n * ncols);
+    if (e == hipSuccess) e = d_idx.alloc((size_t)n * k);
+    if (e == hipSuccess) e = d_d2.alloc((size_t)n * k);
+    if (e == hipSuccess) e = d_tiles.alloc(tiles.size());
+    if (e == hipSuccess) e = hipMemcpyAsync(d_x.get(), X, xb, hipMemcpyDefault, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tiles.get(), tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = launch_knn_rows(st, d_x.get(), ncols, k, d_tiles.get(), ntiles, threads, d_idx.get(), d_d2.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(idx_out, d_idx.get(), ob, hipMemcpyDefault, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d2_out, d_d2.get(), ob, hipMemcpyDefault, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_knn_rows: %s", hipGetErrorString(e));
+    return PG_OK;
+    PG_API_END
+}

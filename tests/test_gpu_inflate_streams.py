@@ -15,8 +15,8 @@ from tests import deflate_craft as dc
 pytestmark = pytest.mark.gpu
 
 PG_E_FORMAT = -3
-PIECE_BLOCKS = 1 << 18  # pg_api.hip INF_PIECE_BLOCKS
-STAGING = 64 << 20  # pg_api.hip INF_PIECE_BYTES
+PIECE_BLOCKS = 1 << 18  # pg_api_bgzf.hip INF_PIECE_BLOCKS
+STAGING = 64 << 20  # pg_api_bgzf.hip INF_PIECE_BYTES
 
 
 @pytest.fixture(scope="module")

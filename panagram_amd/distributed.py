@@ -719,7 +719,7 @@ def build_partial_table(ctx, k: int, ngenomes: int, rank: int, world: int, genom
 def anchor_genome_sharded(table, seqs: Sequence[bytes], group=None, rank: Optional[int] = None,
                           world: Optional[int] = None, exchange: str = "columns"):
     """Anchor contigs against this rank's partial table, complete the rows across ranks, derive
-    bitmap.100 / bins / column sums from the completed rows.  Returns like Genome.anchor_contigs.
+    bitmap.100 / bins / column sums from the completed rows.  Returns ([``AnchorResult.download(ci)`` of every contig], int64 column sums).
     ``exchange``: "columns" = all-gather of compact bit columns (default; ranks must own the
     contiguous genome blocks of ``genome_owner``), "allreduce" = SUM all-reduce of the rows."""
     from . import engine

@@ -680,6 +680,25 @@ def homology_classes(name_lists: Sequence[Sequence[str]]) -> np.ndarray:
     return np.asarray(out, np.uint32)
 
 
+def _windows(contigs, starts, ends, what: str):
+    """contigs, starts, ends as the C ABI takes them: contiguous uint32 / uint64 / uint64, one entry per ``what``"""
+    contigs = np.ascontiguousarray(contigs, np.uint32)
+    starts = np.ascontiguousarray(starts, np.uint64)
+    ends = np.ascontiguousarray(ends, np.uint64)
+    if len(contigs) != len(starts) or len(ends) != len(starts):
+        raise ValueError(f"contigs, starts and ends need one entry per {what}")
+    return contigs, starts, ends
+
+
+def _mask_words(ngenomes: int, given) -> np.ndarray:
+    """a genome mask padded or cut to ceil(N / 32) uint32 words; None: the empty set"""
+    w = np.zeros((ngenomes + 31) // 32, np.uint32)
+    if given is not None:
+        given = np.asarray(given, np.uint32).ravel()
+        w[:min(len(w), len(given))] = given[:len(w)]
+    return w
+
+
 class AnchorResult:
     """Device-resident outputs of anchoring one SeqSet against one PanTable."""
 
@@ -847,17 +866,9 @@ class AnchorResult:
         """(cs [nbins, N] uint64, kept [nbins] uint64): bin i = sampled rows [starts[i], ends[i]) of contig contigs[i]'s
         bitmap.<step> rows, sampled row j = row j * stride; rows without any ``keep_words`` bit get them ORed in, and with
         ``omit_fixed`` rows whose N bits are then all set are dropped (k_bin_colsums, one launch)"""
-        contigs = np.ascontiguousarray(contigs, np.uint32)
-        starts = np.ascontiguousarray(starts, np.uint64)
-        ends = np.ascontiguousarray(ends, np.uint64)
+        contigs, starts, ends = _windows(contigs, starts, ends, "bin")
         n, N = len(starts), self.ngenomes
-        if len(contigs) != n or len(ends) != n:
-            raise ValueError("contigs, starts and ends need one entry per bin")
-        kw = None
-        if keep_words is not None:
-            kw = np.zeros((N + 31) // 32, np.uint32)
-            given = np.asarray(keep_words, np.uint32).ravel()
-            kw[:min(len(kw), len(given))] = given[:len(kw)]
+        kw = None if keep_words is None else _mask_words(N, keep_words)  # (no mask is a null pointer, not a mask of zeros)
         cs = np.zeros((n, N), np.uint64)
         kept = np.zeros(n, np.uint64)
         check(self._lib.pg_result_bin_colsums(self._h, int(step), int(stride), n, _ptr(contigs), _ptr(starts), _ptr(ends),
@@ -868,12 +879,8 @@ class AnchorResult:
         """[nwin, N, N] uint64: entry (i, a, b) = sampled rows [starts[i], ends[i]) of contig contigs[i]'s bitmap.<step> rows
         holding both genome a's and genome b's bit, sampled row j = row j * stride (k_pair_counts, one launch).  The full
         symmetric matrix; its diagonal are the column sums."""
-        contigs = np.ascontiguousarray(contigs, np.uint32)
-        starts = np.ascontiguousarray(starts, np.uint64)
-        ends = np.ascontiguousarray(ends, np.uint64)
+        contigs, starts, ends = _windows(contigs, starts, ends, "window")
         n, N = len(starts), self.ngenomes
-        if len(contigs) != n or len(ends) != n:
-            raise ValueError("contigs, starts and ends need one entry per window")
         out = np.zeros((n, N, N), np.uint64)
         check(self._lib.pg_result_pair_counts(self._h, int(step), int(stride), n, _ptr(contigs), _ptr(starts), _ptr(ends),
                                               _ptr(out)))
@@ -882,21 +889,11 @@ class AnchorResult:
     def _find(self, contigs, starts, ends, have_words, lack_words, min_have, max_lack, step, stride, cap):
         """one pg_result_find_runs call -> (total, nruns [nwin], matched [nwin], run starts, run ends; the last two None
         unless 0 < total <= cap)"""
-        contigs = np.ascontiguousarray(contigs, np.uint32)
-        starts = np.ascontiguousarray(starts, np.uint64)
-        ends = np.ascontiguousarray(ends, np.uint64)
-        n, ndw = len(starts), (self.ngenomes + 31) // 32
-        if len(contigs) != n or len(ends) != n:
-            raise ValueError("contigs, starts and ends need one entry per window")
+        contigs, starts, ends = _windows(contigs, starts, ends, "window")
+        n = len(starts)
         if int(min_have) < 0 or int(max_lack) < 0:
             raise ValueError(f"min_have and max_lack must not be negative, got {min_have}, {max_lack}")
-        masks = []
-        for given in (have_words, lack_words):
-            w = np.zeros(ndw, np.uint32)
-            if given is not None:
-                given = np.asarray(given, np.uint32).ravel()
-                w[:min(ndw, len(given))] = given[:ndw]
-            masks.append(w)
+        masks = [_mask_words(self.ngenomes, given) for given in (have_words, lack_words)]
         nruns, matched = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         rs, re = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
         total = C.c_uint64(0)

@@ -1355,39 +1355,6 @@ class Genome:
         self.set_chrs(pd.read_table(self.chrs_fname, index_col="name"))
 
     # ---- WRITE: the hot path ----
-    def anchor_contigs(self, table: engine.PanTable, seqs: Sequence[bytes]):
-        """GPU compute for a list of contigs: returns ([(rows, rows100, bins, info)], colsums)."""
-        ctx = table.ctx
-        ss = engine.SeqSet.from_host(ctx, seqs)
-        res = engine.AnchorResult(table, ss, colsums=True)
-        res.run()
-        out = [res.download(ci) for ci in range(len(seqs))]
-        cs = res.colsums().astype(np.int64)
-        res.close()
-        ss.close()
-        return out, cs
-
-    def write_outputs(self, names: Sequence[str], results, paircount_sums: np.ndarray,
-                      bgzf_threads: Optional[int] = None):
-        """Write anchor/<name>/ exactly as the reference lays it out (cpp/anchor.cpp:37-109,
-        index.py:1035-1094).  ``results[i] = (rows, rows100, bins, info)`` for contig i in
-        FASTA order; files are written to temporaries and renamed, chrs.tsv last."""
-        N = self.ngenomes
-        os.makedirs(self.prefix, exist_ok=True)
-        nthreads = bgzf_threads or self._bgzf_threads()
-        tmp = {s: self.bitmap_gz_fname(s) + ".tmp" for s in self.steps}
-        # one-byte rows: equal rows are byte runs (zlib RLE); wider rows: the row-aware encoder
-        level = 6 | (engine.BgzfWriter.RLE if self.nbytes == 1 else engine.BgzfWriter.ROWS(self.nbytes) if self.nbytes < 256 else 0)
-        writers = {s: engine.BgzfWriter(tmp[s], level=level, threads=nthreads) for s in self.steps}
-        for rows, rows100, _, _ in results:
-            writers[1].write(rows)
-            writers[self.steps[1]].write(rows100)
-        for s in self.steps:
-            writers[s].close(self.bitmap_gzi_fname(s) + ".tmp")
-            os.replace(tmp[s], self.bitmap_gz_fname(s))
-            os.replace(self.bitmap_gzi_fname(s) + ".tmp", self.bitmap_gzi_fname(s))
-        self._write_tables(names, [(b, info) for _, _, b, info in results], paircount_sums)
-
     def setup_log(self, logfile: Optional[str]):
         """route this genome's messages to ``logfile`` (same line format as the reference's anchor logs)"""
         self.close_log()
@@ -1509,38 +1476,27 @@ class Genome:
                            ncontigs=hi - lo)
             os.replace(gz + ".tmp", gz)
             os.replace(gzi + ".tmp", gzi)
-        self._write_tables(names, small if isinstance(small, engine.SmallOutputs) else [(b, info) for _, _, b, info in small], cs, gene_hists)
+        self._write_tables(names, small, cs, gene_hists)
         self.close_log()
 
     def _bgzf_threads(self) -> int:
         return max(1, min(64, self.index.cores if self.index.cores > 1 else engine.usable_cpus()))
 
-    def _write_tables(self, names, bins_infos, paircount_sums, gene_hists=None):
+    def _write_tables(self, names, small: "engine.SmallOutputs", paircount_sums, gene_hists=None):
+        """bitsum.bins.tsv, bitsum.genes.tsv, total_paircounts.csv and chrs.tsv of the contigs ``names``; ``small``: their
+        small outputs as ``AnchorResult.contigs_small`` gives them (an engine.SmallOutputs, nothing else)"""
         N = self.ngenomes
-        chr_rows: List[Tuple[str, int, int, int]] = []
-        if isinstance(bins_infos, engine.SmallOutputs):
-            # the contigs' bins in one array: the text is formatted by the library (two million rows per anchor genome for
-            # an assembly of 20 000 contigs; row by row in the interpreter that was most of such a run)
-            bins_infos.write_bins_tsv(self.bins_fname, N)
-            for ci, chrom in enumerate(names):
-                gene_count = gene_hists[chrom][0] if gene_hists and chrom in gene_hists else 0
-                chr_rows.append((chrom, ci, int(bins_infos.nkmers[ci]), gene_count))
-            if len(names) <= 1000:
-                for chrom in names:
-                    self.log.info(f"Anchored {chrom}")
-            else:  # (a log line per contig of a fragmented assembly is a second of logging per genome)
-                self.log.info(f"Anchored {len(names)} contigs ({names[0]} ... {names[-1]})")
-        else:
-            bins_rows: List[str] = ["chr\tstart" + "".join(f"\t{i}" for i in range(N + 1)) + "\n"]
-            for ci, (chrom, (bins, info)) in enumerate(zip(names, bins_infos)):
-                starts = np.arange(info["nbins"], dtype=np.int64) * info["binlen"]
-                body = np.column_stack([np.full(info["nbins"], ci, np.int64), starts, bins.astype(np.int64)])
-                bins_rows.extend("\t".join(map(str, row)) + "\n" for row in body.tolist())
-                gene_count = gene_hists[chrom][0] if gene_hists and chrom in gene_hists else 0
-                chr_rows.append((chrom, ci, info["nkmers"], gene_count))
+        # the contigs' bins in one array: the text is formatted by the library (two million rows per anchor genome for
+        # an assembly of 20 000 contigs; row by row in the interpreter that was most of such a run)
+        small.write_bins_tsv(self.bins_fname, N)
+        chr_rows: List[Tuple[str, int, int, int]] = [
+            (chrom, ci, int(small.nkmers[ci]), gene_hists[chrom][0] if gene_hists and chrom in gene_hists else 0)
+            for ci, chrom in enumerate(names)]
+        if len(names) <= 1000:
+            for chrom in names:
                 self.log.info(f"Anchored {chrom}")
-            with open(self.bins_fname, "w") as f:
-                f.writelines(bins_rows)
+        else:  # (a log line per contig of a fragmented assembly is a second of logging per genome)
+            self.log.info(f"Anchored {len(names)} contigs ({names[0]} ... {names[-1]})")
         if gene_hists is not None:  # bitsum.genes.tsv: one row per annotated chromosome (index.py:1079-1082)
             self._write_gene_sums(self.chr_genes_fname, gene_hists)
         # total_paircounts.csv (index.py:1068-1074): count[g] = positions holding genome g's bit
@@ -1658,7 +1614,11 @@ class Genome:
             row0 = int(self.chrs["size"].cumsum().shift(fill_value=0).loc[chroms[0]])
         else:
             row0 = int(self.offsets.loc[chroms[0], step])
-        return engine.AnchorResult.from_bgzf(self.index.context, int(self.index.k), self.ngenomes, sizes, self.bitmap_gz_fname(step),
+        return self._rows_container(sizes, step, row0)
+
+    def _rows_container(self, nkmers: List[int], step: int, row0: int) -> "engine.AnchorResult":
+        """a rows result over contigs of ``nkmers`` rows, filled on the GPU from bitmap.<step>.gz's payload from row ``row0``"""
+        return engine.AnchorResult.from_bgzf(self.index.context, int(self.index.k), self.ngenomes, nkmers, self.bitmap_gz_fname(step),
                                              self.bitmap_gzi_fname(step), file_row0=row0, step=step,
                                              lowres_step=int(self.index.lowres_step))
 
@@ -1694,6 +1654,58 @@ class Genome:
             words[i // 32] |= np.uint32(1 << (i % 32))
         return words
 
+    def _base_step(self, step: int) -> Tuple[int, int]:
+        """(bstep, stride) of a sampling step: it reads every ``stride``-th row of bitmap.<bstep>.gz, the coarsest bitmap
+        whose step divides it"""
+        bstep = max(s for s in self.steps if step % s == 0)
+        return bstep, step // bstep
+
+    def _checked_chroms(self, step: int, bin_size: Optional[int] = None, region=None, chroms=None) -> List[str]:
+        """The row readers' argument checks, in the order they refuse, and the chromosomes to visit: that of ``region`` =
+        (chrom, start, end), or ``chroms`` as strings; every chromosome where that is None."""
+        if bin_size is None and step < 1:
+            raise ValueError(f"step must be positive, got {step}")
+        if bin_size is not None and (step < 1 or bin_size < 1):
+            raise ValueError(f"step and bin_size must be positive, got {step}, {bin_size}")
+        if self.chrs is None:
+            self.load_chrs()
+        if region is not None:
+            chrom, start, end = region
+            if chrom is None and (start is not None or end is not None):
+                raise ValueError("start and end need a chromosome")
+            chroms = None if chrom is None else [chrom]
+        elif chroms is not None:
+            chroms = [str(c) for c in chroms]
+        chroms = list(self.chrs.index) if chroms is None else chroms
+        for c in chroms:
+            if c not in self.chrs.index:
+                raise KeyError(f"{self.name}: no chromosome {c!r}")
+        return chroms
+
+    def _binned_batches(self, chroms: List[str], step: int, bin_size: int, fn):
+        """(geo, per): ``geo[c]`` = similarity_bin_geometry of chromosome c, ``per[c]`` = its bins' rows of what
+        ``fn(res, ci, st, en, bstep, stride)`` gave — an array, or a tuple of arrays, with one leading row per bin — for the
+        chromosomes that have bins.  One container and one ``fn`` call per batch of neighbouring chromosomes whose bitmap.1
+        rows fit ``similarity_budget`` bytes of HBM; the container is closed before the next one is opened."""
+        bstep, stride = self._base_step(step)
+        geo = {c: self.similarity_bin_geometry(int(self.chrs.loc[c, "size"]), step, bin_size) for c in chroms}
+        per = {}
+        for batch in self._annotate_batches([c for c in dict.fromkeys(chroms) if len(geo[c][0])], self.similarity_budget):
+            res = self._rows_from_disk(batch, bstep)
+            try:
+                ci = np.concatenate([np.full(len(geo[c][0]), i, np.uint32) for i, c in enumerate(batch)])
+                st = np.concatenate([geo[c][1] for c in batch])
+                en = np.concatenate([geo[c][2] for c in batch])
+                got = fn(res, ci, st, en, bstep, stride)
+            finally:
+                res.close()
+            at = 0
+            for c in batch:
+                nb = len(geo[c][0])
+                per[c] = tuple(a[at:at + nb] for a in got) if isinstance(got, tuple) else got[at:at + nb]
+                at += nb
+        return geo, per
+
     def kmer_similarity_bins(self, chroms=None, step: int = 100, bin_size: int = 1_000_000, omit_fixed: bool = False,
                              keep=None) -> Dict[str, pd.DataFrame]:
         """{chrom: DataFrame} as ``bitmap_to_bins(genome.query(chrom, 0, size, step), bin_size, ...)`` of the reference's
@@ -1703,39 +1715,13 @@ class Genome:
         bin whose sums are all zero NaN.  The rows are read back from the bitmap on the GPU (batches of neighbouring
         chromosomes whose bitmap.1 rows fit ``similarity_budget`` bytes of HBM) and binned by k_bin_colsums, one launch per batch."""
         step, bin_size = int(step), int(bin_size)
-        if step < 1 or bin_size < 1:
-            raise ValueError(f"step and bin_size must be positive, got {step}, {bin_size}")
-        if self.chrs is None:
-            self.load_chrs()
-        chroms = list(self.chrs.index) if chroms is None else [str(c) for c in chroms]
-        for c in chroms:
-            if c not in self.chrs.index:
-                raise KeyError(f"{self.name}: no chromosome {c!r}")
-        bstep = max(s for s in self.steps if step % s == 0)
-        stride = step // bstep
+        chroms = self._checked_chroms(step, bin_size, chroms=chroms)
         kw = self.similarity_keep_words(keep)
         names = pd.Index(self.index.genome_names)
-        out: Dict[str, pd.DataFrame] = {}
-        geo = {c: self.similarity_bin_geometry(int(self.chrs.loc[c, "size"]), step, bin_size) for c in chroms}
-        todo = [c for c in dict.fromkeys(chroms) if len(geo[c][0])]
-        for c in chroms:
-            if not len(geo[c][0]):
-                out[c] = pd.DataFrame(np.zeros((self.ngenomes, 0)), index=names, columns=pd.Index([], dtype=np.int64))
-        for batch in self._annotate_batches(todo, self.similarity_budget):
-            res = self._rows_from_disk(batch, bstep)
-            try:
-                ci = np.concatenate([np.full(len(geo[c][0]), i, np.uint32) for i, c in enumerate(batch)])
-                st = np.concatenate([geo[c][1] for c in batch])
-                en = np.concatenate([geo[c][2] for c in batch])
-                cs, kept = res.bin_colsums(ci, st, en, step=bstep, stride=stride, keep_words=kw, omit_fixed=omit_fixed)
-            finally:
-                res.close()
-            at = 0
-            for c in batch:
-                nb = len(geo[c][0])
-                out[c] = self._similarity_frame(cs[at:at + nb], kept[at:at + nb], geo[c][0] * bin_size, names)
-                at += nb
-        return {c: out[c] for c in chroms}
+        geo, sums = self._binned_batches(chroms, step, bin_size, lambda res, ci, st, en, bstep, stride: res.bin_colsums(
+            ci, st, en, step=bstep, stride=stride, keep_words=kw, omit_fixed=omit_fixed))
+        return {c: self._similarity_frame(*sums[c], geo[c][0] * bin_size, names) if c in sums else
+                pd.DataFrame(np.zeros((self.ngenomes, 0)), index=names, columns=pd.Index([], dtype=np.int64)) for c in chroms}
 
     @staticmethod
     def _similarity_frame(cs: np.ndarray, kept: np.ndarray, starts: np.ndarray, names: pd.Index) -> pd.DataFrame:
@@ -1752,51 +1738,50 @@ class Genome:
         """a rows result of ONE pseudo-contig: rows [row0, row0 + nrows) of bitmap.<bstep>.gz's payload, inflated on the GPU"""
         # (a container derives its low-resolution rows from its contig's length: the shortest contig with nrows of them)
         nk = nrows if bstep == 1 else (nrows - 1) * bstep + 1
-        return engine.AnchorResult.from_bgzf(self.index.context, int(self.index.k), self.ngenomes, [nk], self.bitmap_gz_fname(bstep),
-                                             self.bitmap_gzi_fname(bstep), file_row0=row0, step=bstep,
-                                             lowres_step=int(self.index.lowres_step))
+        return self._rows_container([nk], bstep, row0)
 
     def _region_rows(self, chrom: str, start, end, step: int):
         """(bstep, stride, first payload row, rows) of what ``query(chrom, start, end, step)`` reads: ``rows`` rows of
         bitmap.<bstep>.gz from ``first``, of which it keeps every ``stride``-th"""
-        bstep = max(s for s in self.steps if step % s == 0)
+        bstep, stride = self._base_step(step)
         start = 0 if start is None else int(start)
         end = self.seq_len(chrom) if end is None else int(end)
         row0 = int(self.offsets.loc[chrom, bstep]) + start // bstep
         file_rows = int(np.ceil(self.sizes / bstep).sum())  # (query reads to the payload's end at most)
         nrows = min((end - 1 - start) // bstep + 1, file_rows - row0) if end > start and start >= 0 else 0
-        return bstep, step // bstep, row0, max(0, nrows)
+        return bstep, stride, row0, max(0, nrows)
+
+    def _region_pieces(self, chrom: str, start, end, step: int, fn) -> list:
+        """[(first sampled row, sampled rows, fn(res, sampled rows, bstep, stride))] of the consecutive pieces of what
+        ``query(chrom, start, end, step)`` reads, ``res`` the piece's rows container: one container per piece, closed before
+        the next one is opened.  A piece takes at most similarity_budget bytes of HBM (a container of low-resolution rows
+        holds, zeroed, the full-resolution rows they span) and starts at the first row of the region's sampling phase inside it."""
+        bstep, stride, row0, nrows = self._region_rows(chrom, start, end, step)
+        per = max(1, int(self.similarity_budget) // (self.nbytes * bstep))
+        out = []
+        for p0 in range(0, nrows, per):
+            p1 = min(p0 + per, nrows)
+            first = -(-p0 // stride) * stride
+            if first >= p1:
+                continue
+            ns = (p1 - first - 1) // stride + 1
+            res = self._rows_region(bstep, row0 + first, p1 - first)
+            try:
+                out.append((first // stride, ns, fn(res, ns, bstep, stride)))
+            finally:
+                res.close()
+        return out
 
     def _pair_counts(self, chrom=None, start=None, end=None, step: int = 1):
         """(N x N int64 pair counts, sampled rows they were taken over)"""
         step = int(step)
-        if step < 1:
-            raise ValueError(f"step must be positive, got {step}")
-        if self.chrs is None:
-            self.load_chrs()
-        if chrom is None and (start is not None or end is not None):
-            raise ValueError("start and end need a chromosome")
-        for c in ([] if chrom is None else [chrom]):
-            if c not in self.chrs.index:
-                raise KeyError(f"{self.name}: no chromosome {c!r}")
+        chroms = self._checked_chroms(step, region=(chrom, start, end))
         N = self.ngenomes
         total, seen = np.zeros((N, N), np.int64), 0
-        for c in (list(self.chrs.index) if chrom is None else [chrom]):
-            bstep, stride, row0, nrows = self._region_rows(c, start, end, step)
-            # pieces of at most similarity_budget bytes of HBM (a container of low-resolution rows holds, zeroed, the
-            # full-resolution rows they span); a piece starts at the first row of the region's sampling phase inside it
-            per = max(1, int(self.similarity_budget) // (self.nbytes * bstep))
-            for p0 in range(0, nrows, per):
-                p1 = min(p0 + per, nrows)
-                first = -(-p0 // stride) * stride
-                if first >= p1:
-                    continue
-                ns = (p1 - first - 1) // stride + 1
-                res = self._rows_region(bstep, row0 + first, p1 - first)
-                try:
-                    total += res.pair_counts([0], [0], [ns], step=bstep, stride=stride)[0].astype(np.int64)
-                finally:
-                    res.close()
+        for c in chroms:
+            for _, ns, counts in self._region_pieces(c, start, end, step, lambda res, ns, bstep, stride: res.pair_counts(
+                    [0], [0], [ns], step=bstep, stride=stride)[0].astype(np.int64)):
+                total += counts
                 seen += ns
         return total, seen
 
@@ -1821,36 +1806,16 @@ class Genome:
         searched there by k_find_runs; only the runs come back."""
         from . import find
         step = int(step)
-        if step < 1:
-            raise ValueError(f"step must be positive, got {step}")
-        if self.chrs is None:
-            self.load_chrs()
-        if chrom is None and (start is not None or end is not None):
-            raise ValueError("start and end need a chromosome")
-        for c in ([] if chrom is None else [chrom]):
-            if c not in self.chrs.index:
-                raise KeyError(f"{self.name}: no chromosome {c!r}")
+        chroms = self._checked_chroms(step, region=(chrom, start, end))
         hw, lw, min_have, max_lack = find.rule_words(self.index.genome_names, have, lack, min_have, max_lack)
         find.merge_runs([], [], min_len, max_gap)  # (its argument checks, before anything is read)
+
+        def runs_of(res, ns, bstep, stride):
+            runs, _ = res.find_runs([0], [0], [ns], hw, lw, min_have, max_lack, step=bstep, stride=stride)
+            return runs[:, 1], runs[:, 2]
         frames = []
-        for c in (list(self.chrs.index) if chrom is None else [chrom]):
-            bstep, stride, row0, nrows = self._region_rows(c, start, end, step)
-            # pieces as _pair_counts cuts them: at most similarity_budget bytes of HBM each, a piece starting at the first row
-            # of the region's sampling phase inside it
-            per = max(1, int(self.similarity_budget) // (self.nbytes * bstep))
-            pieces = []
-            for p0 in range(0, nrows, per):
-                p1 = min(p0 + per, nrows)
-                first = -(-p0 // stride) * stride
-                if first >= p1:
-                    continue
-                ns = (p1 - first - 1) // stride + 1
-                res = self._rows_region(bstep, row0 + first, p1 - first)
-                try:
-                    runs, _ = res.find_runs([0], [0], [ns], hw, lw, min_have, max_lack, step=bstep, stride=stride)
-                finally:
-                    res.close()
-                pieces.append((first // stride, ns, runs[:, 1], runs[:, 2]))
+        for c in chroms:
+            pieces = [(j0, ns, a, b) for j0, ns, (a, b) in self._region_pieces(c, start, end, step, runs_of)]
             s, e, rows = find.merge_runs(*find.join_pieces(pieces), min_len, max_gap)
             label0 = 0 if start is None else int(start)  # (query labels its j-th row start + j * step)
             frames.append(pd.DataFrame({"chr": np.full(len(s), c, object), "start": label0 + s * step,
@@ -1864,32 +1829,10 @@ class Genome:
         sampled rows of the bin.  One k_find_runs count launch per batch; no run is written."""
         from . import find
         step, bin_size = int(step), int(bin_size)
-        if step < 1 or bin_size < 1:
-            raise ValueError(f"step and bin_size must be positive, got {step}, {bin_size}")
-        if self.chrs is None:
-            self.load_chrs()
-        chroms = list(self.chrs.index) if chroms is None else [str(c) for c in chroms]
-        for c in chroms:
-            if c not in self.chrs.index:
-                raise KeyError(f"{self.name}: no chromosome {c!r}")
+        chroms = self._checked_chroms(step, bin_size, chroms=chroms)
         hw, lw, min_have, max_lack = find.rule_words(self.index.genome_names, have, lack, min_have, max_lack)
-        bstep = max(s for s in self.steps if step % s == 0)
-        stride = step // bstep
-        geo = {c: self.similarity_bin_geometry(int(self.chrs.loc[c, "size"]), step, bin_size) for c in chroms}
-        matched = {}
-        for batch in self._annotate_batches([c for c in dict.fromkeys(chroms) if len(geo[c][0])], self.similarity_budget):
-            res = self._rows_from_disk(batch, bstep)
-            try:
-                ci = np.concatenate([np.full(len(geo[c][0]), i, np.uint32) for i, c in enumerate(batch)])
-                st = np.concatenate([geo[c][1] for c in batch])
-                en = np.concatenate([geo[c][2] for c in batch])
-                _, m = res.find_counts(ci, st, en, hw, lw, min_have, max_lack, step=bstep, stride=stride)
-            finally:
-                res.close()
-            at = 0
-            for c in batch:
-                matched[c] = m[at:at + len(geo[c][0])].astype(np.int64)
-                at += len(geo[c][0])
+        geo, matched = self._binned_batches(chroms, step, bin_size, lambda res, ci, st, en, bstep, stride: res.find_counts(
+            ci, st, en, hw, lw, min_have, max_lack, step=bstep, stride=stride)[1].astype(np.int64))
         frames = [pd.DataFrame({"chr": np.full(len(geo[c][0]), c, object), "start": geo[c][0] * bin_size,
                                 "matched": matched.get(c, np.zeros(0, np.int64)), "rows": geo[c][2] - geo[c][1]}) for c in chroms]
         return pd.concat(frames, ignore_index=True) if frames else pd.DataFrame(
@@ -2020,10 +1963,7 @@ class Genome:
     def query(self, name, start=None, end=None, step=1) -> pd.DataFrame:
         if self.blocks is None:
             self.init_read()
-        bstep = 1
-        for s in self.steps:
-            if step % s == 0:
-                bstep = max(bstep, s)
+        bstep, _ = self._base_step(step)
         start = 0 if start is None else start
         end = self.seq_len(name) if end is None else end
         pac = self._query_bytes(name, start, end - 1, step, bstep)
@@ -2067,14 +2007,10 @@ def run_anchor_cli(argv: Sequence[str], device: int = 0) -> int:
         for step in (1, 100):
             res.write_bgzf(step, os.path.join(adir, f"bitmap.{step}.gz"), os.path.join(adir, f"bitmap.{step}.gzi"),
                            level=bgzf_level, threads=max(1, engine.usable_cpus() // 2), first_contig=lo, ncontigs=len(names))
-        with open(os.path.join(adir, "bitsum.bins.tsv"), "w") as fb, open(os.path.join(adir, "chrs.tsv"), "w") as fc:
-            fb.write("chr\tstart" + "".join(f"\t{i}" for i in range(ngenomes + 1)) + "\n")
-            fc.write("name\tid\tsize\tgene_count\n")
-            for ci, chrom in enumerate(names):
-                _, _, bins, info = res.download(lo + ci, want_bitmap1=False, want_bitmap100=False)
-                for b in range(info["nbins"]):
-                    fb.write(f"{ci}\t{b * info['binlen']}" + "".join(f"\t{int(c)}" for c in bins[b]) + "\n")
-                fc.write(f"{chrom}\t{ci}\t{info['nkmers']}\t0\n")
+        small = res.contigs_small(lo, len(names))  # (one call for all contigs; the bins' text is formatted by the library)
+        small.write_bins_tsv(os.path.join(adir, "bitsum.bins.tsv"), ngenomes)
+        with open(os.path.join(adir, "chrs.tsv"), "w") as fc:
+            fc.write("name\tid\tsize\tgene_count\n" + "".join(f"{chrom}\t{ci}\t{int(small.nkmers[ci])}\t0\n" for ci, chrom in enumerate(names)))
 
     free = ctx.mem_info()[0]
     batch_bytes = int(min(Index.batch_bytes, max(1 << 30, (free - (6 << 30)) / 2.3)))

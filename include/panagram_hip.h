@@ -415,6 +415,29 @@ int pg_result_find_runs(pg_result *r, int step, uint32_t stride, uint32_t nwin, 
                         const uint32_t *have_words, const uint32_t *lack_words, uint32_t min_have, uint32_t max_lack,
                         uint64_t cap, uint32_t *run_start, uint32_t *run_end,
                         uint64_t *nruns_out, uint64_t *matched_out, uint64_t *total_out);
+/* presence/absence pattern spectrum: WHICH patterns occur in these rows, and how many rows does each hold (query_bitmap followed
+ * by DataFrame.value_counts(), the table behind an UpSet plot or a core / shell / private breakdown — the question to settle
+ * before pg_result_find_runs is asked where one pattern's rows are)?
+ * The selection: select_words is a set of 1 to 64 genomes as ceil(ngenomes / 32) words (bit g of the set = bit g % 32 of word
+ * g / 32; bits at and past ngenomes are ignored, in the words and in a row's last byte); NULL: all ngenomes genomes.  A row's key
+ * is a 64-bit word: bit i of the key is the row's bit for the i-th selected genome, in ascending column order.
+ * Windows as in pg_result_find_runs: window i = SAMPLED rows [starts[i], ends[i]) of contig contig[i]'s bitmap.<step> rows in HBM,
+ * sampled row j being row j * stride; no row outside a window is read.  The result is ONE spectrum over all windows of the call:
+ * for every distinct key the number of sampled rows, over all windows, that have it (a row that two windows cover counts twice).
+ * *rows_out = the sampled rows of all windows, always written.
+ * Capacity: the rows are reduced into a hash table of max(1024, the next power of two >= 2 * cap) slots in HBM.  If no more than
+ * cap distinct keys occur, *exceeded_out = 0, *ndistinct_out = their number, and the first *ndistinct_out entries of keys_out /
+ * counts_out are the spectrum sorted by key ascending — the same on every call; counts_out sums to *rows_out.  Otherwise
+ * *exceeded_out = 1, nothing is written to the arrays (which may be NULL when cap == 0), *ndistinct_out is unspecified and the
+ * call still returns PG_OK: call again with a larger cap.  Which of the two happens depends on the rows alone, never on the run.
+ * No window, or only empty ones: zero patterns, not exceeded.
+ * PG_E_INVALID before anything is launched: no genome or more than 64 selected (NULL on a result of more than 64 genomes
+ * included), a sampled row outside its contig, more than 4096 genomes, cap > 2^30.  One launch of k_pattern_counts over chunks
+ * of 8192 sampled rows (equal neighbouring rows are counted as one run; LDS and global atomics on integers); synchronises. */
+int pg_result_pattern_counts(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
+                             const uint64_t *starts, const uint64_t *ends, const uint32_t *select_words,
+                             uint64_t cap, uint64_t *keys_out, uint64_t *counts_out,
+                             uint64_t *ndistinct_out, uint64_t *rows_out, int *exceeded_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

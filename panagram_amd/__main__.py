@@ -4,7 +4,9 @@ cpp/run_anchor (`run_anchor <ngenomes> <root> [<name> <fasta>]...`), and what th
 `tree <index_dir> <genome> <chrom> [start] [end] [step]` prints the Newick tree of the genomes over a region;
 `umaps <index_dir> [genome ...]` writes chrom_umaps.csv and genome_umap.csv (index.py:1107-1156) for an existing index; and
 `find <index_dir> <genome> [chrom] [start] [end] [step] --have A,B --lack C,D` lists the runs of positions whose k-mers the
-`--have` genomes hold and the `--lack` genomes do not (the query scripts/query_index.py's "custom" branch sketches)."""
+`--have` genomes hold and the `--lack` genomes do not (the query scripts/query_index.py's "custom" branch sketches);
+`patterns <index_dir> <genome> [chrom] [start] [end] [step] [--genomes A,B,...]` lists the presence/absence patterns that occur in
+a region's rows with the rows each holds (query_bitmap + value_counts(), reduced on the GPU)."""
 import argparse
 import os
 import sys
@@ -70,6 +72,21 @@ def main(argv=None):
     fd.add_argument("--whole", action="store_true", help="the whole genome in place of a chromosome")
     fd.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     fd.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    pt = sub.add_parser("patterns", help="the presence/absence patterns that occur in a region's bitmap rows and the rows each "
+                                         "holds, counted on the GPU: tab-separated pattern n rows frac genomes")
+    pt.add_argument("index_dir")
+    pt.add_argument("genome")
+    pt.add_argument("chrom", nargs="?", default=None)
+    pt.add_argument("start", nargs="?", type=int, default=None)
+    pt.add_argument("end", nargs="?", type=int, default=None)
+    pt.add_argument("step", nargs="?", type=int, default=1)
+    pt.add_argument("--genomes", default="", metavar="A,B", help="the genomes of a pattern, at most 64 (default: all of them)")
+    pt.add_argument("--top", type=int, default=None, metavar="K", help="only the K patterns with the most rows")
+    pt.add_argument("--min-rows", type=int, default=1, metavar="N", help="drop patterns of fewer than N rows")
+    pt.add_argument("--occupancy", action="store_true", help="write n rows instead: the rows held by n of the genomes, n = 0..m")
+    pt.add_argument("--whole", action="store_true", help="the whole genome in place of a chromosome")
+    pt.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    pt.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -144,6 +161,41 @@ def main(argv=None):
         finally:
             idx.close()
         out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
+        return 0
+    if a.cmd == "patterns":
+        if a.whole == (a.chrom is not None):
+            ap.error("patterns: give a chromosome or --whole (and no region with --whole)")
+        if a.occupancy and (a.top is not None or a.min_rows != 1):
+            ap.error("patterns: --occupancy takes no --top / --min-rows")
+        if (a.top is not None and a.top < 0) or a.min_rows < 0:
+            ap.error("patterns: --top and --min-rows must not be negative")
+        from . import patterns
+        from .index import Index
+        chosen = [g for g in a.genomes.split(",") if g]
+        idx = Index(a.index_dir, mode="r", device=a.device)
+        try:
+            if a.genome not in idx.genomes or not idx[a.genome].anchored:
+                ap.error(f"patterns: {a.genome!r} is not an anchor genome of {a.index_dir}")
+            for g in chosen:
+                if g not in idx.genome_names:
+                    ap.error(f"patterns: unknown genome {g!r} (the index has {', '.join(idx.genome_names)})")
+            if not chosen and len(idx.genome_names) > patterns.MAX_SELECTED:
+                ap.error(f"patterns: the index has {len(idx.genome_names)} genomes and a pattern takes at most "
+                         f"{patterns.MAX_SELECTED}: name them with --genomes")
+            try:
+                keys, counts, selected = idx.pattern_counts(a.genome, chosen or None, a.chrom, a.start, a.end, a.step)
+            except (ValueError, KeyError) as e:
+                ap.error(f"patterns: {e}")
+        finally:
+            idx.close()
+        if a.occupancy:
+            import pandas as pd
+            rows = patterns.occupancy(keys, counts, len(selected))
+            out = pd.DataFrame({"n": range(len(rows)), "rows": rows})
+        else:
+            out = patterns.spectrum_frame(keys, counts, selected, a.top, a.min_rows)
+            out["genomes"] = [",".join(g for g, b in zip(selected, p) if b == "1") or "-" for p in out["pattern"]]
+        out.to_csv(a.output if a.output else sys.stdout, sep="\t", index=False)
         return 0
     if a.cmd == "tree":
         if a.whole == (a.chrom is not None):

@@ -1,8 +1,9 @@
 // pg_api_query.hip — host side of the C-ABI: window queries over a result's finished rows, k-NN of rows.
 #include "pg_host.h"
 
-// Checks shared by the entry points that read a result's rows, beside check_step (pg_api.hip): one wording each, whoever asks.
-static int check_rows_readable(const pg_result *r, int step) {
+// Checks shared by the entry points that read a result's rows (here and in pg_api_patterns.hip), beside check_step (pg_api.hip):
+// one wording each, whoever asks.
+int pg::check_rows_readable(const pg_result *r, int step) {
     if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
     if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
     if (step != 1 && (r->flags & PG_ANCHOR_ROWS_ONLY) && !r->ev_epi && !r->rows_valid)
@@ -11,8 +12,8 @@ static int check_rows_readable(const pg_result *r, int step) {
 }
 // n windows ("bin", "window": the noun of the messages) of sampled rows, refused unless each lies within its contig ->
 // se[3 * n]: device byte offset of the contig's rows, then [start, end) in sampled rows; *longest: the longest of them
-static int gather_windows(const pg_result *r, int step, uint32_t stride, uint32_t n, const uint32_t *contig, const uint64_t *starts,
-                          const uint64_t *ends, const char *noun, std::vector<uint64_t> &se, uint64_t *longest) {
+int pg::gather_windows(const pg_result *r, int step, uint32_t stride, uint32_t n, const uint32_t *contig, const uint64_t *starts,
+                       const uint64_t *ends, const char *noun, std::vector<uint64_t> &se, uint64_t *longest) {
     se.assign((size_t)n * 3, 0);
     *longest = 0;
     for (uint32_t i = 0; i < n; ++i) {

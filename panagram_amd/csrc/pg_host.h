@@ -250,6 +250,10 @@ PG_INTERNAL int join_result(pg_result *r);
 PG_INTERNAL int next_events(pg_result *r, bool probe);
 // pg_api_seqset.hip
 PG_INTERNAL void seqset_release(pg_seqset *s);
+// pg_api_query.hip
+PG_INTERNAL int check_rows_readable(const pg_result *r, int step);
+PG_INTERNAL int gather_windows(const pg_result *r, int step, uint32_t stride, uint32_t n, const uint32_t *contig, const uint64_t *starts,
+                               const uint64_t *ends, const char *noun, std::vector<uint64_t> &se, uint64_t *longest);
 // pg_api_bgzf.hip
 PG_INTERNAL void df_free_buffers(pg_ctx::DfSet &d);
 }  // namespace pg

@@ -226,6 +226,18 @@ hipError_t launch_find_runs(hipStream_t st, uint32_t ngenomes, const uint8_t *ro
                             const uint64_t *starts, const uint64_t *ends, const uint2 *chunks, uint32_t nchunks,
                             const uint32_t *have, const uint32_t *lack, uint32_t min_have, uint32_t max_lack, uint4 *counts,
                             const ulonglong2 *offs, uint64_t total, uint32_t *run_start, uint32_t *run_end);
+// pattern spectrum (pg_patterns.hip): the key of a sampled row = its bits for the `nselected` (1 to 64) genomes of `select`
+// (ceil(N / 32) words, bits at and past N zero), in ascending column order; low_columns: they are columns 0..nselected-1.
+// Windows (base, ends) and chunks as above, PATTERN_CHUNK sampled rows each.  keys / counts: the global table of `slots`
+// (a power of two, >= 2 * cap) entries, keys all-ones (= empty), counts zero; ctr[4] zero: {slots claimed, rows whose key found
+// the table full, rows whose key is the all-ones word (nselected = 64: never in the table), 0}.  ctr[0] <= cap and ctr[1] == 0
+// afterwards: the table holds every other key with its rows.  Otherwise it holds nothing of use.  1 <= N <= PATTERN_MAX_GENOMES.
+constexpr uint32_t PATTERN_CHUNK = 8192;  // sampled rows per chunk, a multiple of 256
+constexpr uint32_t PATTERN_MAX_GENOMES = 4096;
+hipError_t launch_pattern_counts(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, const uint64_t *base,
+                                 const uint64_t *ends, const uint2 *chunks, uint32_t nchunks, const uint32_t *select,
+                                 uint32_t nselected, bool low_columns, uint64_t cap, unsigned long long *keys,
+                                 unsigned long long *counts, uint64_t slots, unsigned long long *ctr);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

@@ -53,6 +53,14 @@ _ADOPT_LOCK = threading.Lock()
 FIND_CHUNK = 4096
 FIND_FIRST_CAP = 1 << 16
 
+# pattern spectrum (pg_patterns.hip).  PATTERN_CHUNK: sampled rows per workgroup — pg_kernels.h's constant, restated for the tests
+# that aim at chunk edges (tests/test_patterns_cpu.py holds the two together); PATTERN_FIRST_CAP: distinct patterns
+# AnchorResult.pattern_counts makes room for in its first call — a table of 2 MiB in HBM; on "exceeded" the room grows 16-fold
+# per call up to PATTERN_MAX_CAP (a table of 2 GiB)
+PATTERN_CHUNK = 8192
+PATTERN_FIRST_CAP = 1 << 16
+PATTERN_MAX_CAP = 1 << 26
+
 
 def tile_positions() -> int:
     """k-mer positions per tile (launch unit; a bit-column block holds tile_positions() // 8 bytes per tile and genome:
@@ -927,6 +935,36 @@ class AnchorResult:
         """(nruns [nwin] uint64, matched [nwin] uint64) of ``find_runs``' windows: the count launch alone (capacity 0)"""
         _, nruns, matched, _, _ = self._find(contigs, starts, ends, have_words, lack_words, min_have, max_lack, step, stride, 0)
         return nruns, matched
+
+    def _patterns(self, contigs, starts, ends, select_words, step, stride, cap):
+        """one pg_result_pattern_counts call -> (exceeded, sampled rows, keys, counts; the last two None when exceeded)"""
+        contigs, starts, ends = _windows(contigs, starts, ends, "window")
+        sel = None if select_words is None else _mask_words(self.ngenomes, select_words)  # (no selection is a null pointer: all)
+        keys, counts = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+        nd, rows, exceeded = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        check(self._lib.pg_result_pattern_counts(self._h, int(step), int(stride), len(starts), _ptr(contigs), _ptr(starts),
+                                                 _ptr(ends), _ptr(sel), int(cap), _ptr(keys) if cap else None,
+                                                 _ptr(counts) if cap else None, C.byref(nd), C.byref(rows), C.byref(exceeded)))
+        if exceeded.value:
+            return True, rows.value, None, None
+        return False, rows.value, keys[:nd.value], counts[:nd.value]
+
+    def pattern_counts(self, contigs, starts, ends, select_words=None, step: int = 1, stride: int = 1):
+        """(keys uint64, counts uint64): the presence/absence pattern spectrum of the sampled rows of ALL windows together —
+        window i = sampled rows [starts[i], ends[i]) of contig contigs[i]'s bitmap.<step> rows, sampled row j = row j * stride.
+        ``select_words``: 1 to 64 genomes as ceil(N / 32) words (None: all N, which must then be at most 64); bit i of a key is
+        the row's bit for the i-th selected genome in column order.  ``keys`` ascending, ``counts[i]`` the sampled rows with key
+        ``keys[i]``; ``counts.sum()`` is the windows' total of sampled rows.  k_pattern_counts: a first call with room for
+        PATTERN_FIRST_CAP patterns, 16 times the room per further call while the kernel reports more, ValueError beyond
+        PATTERN_MAX_CAP."""
+        cap = PATTERN_FIRST_CAP
+        while True:
+            exceeded, _, keys, counts = self._patterns(contigs, starts, ends, select_words, step, stride, cap)
+            if not exceeded:
+                return keys, counts
+            if cap >= PATTERN_MAX_CAP:
+                raise ValueError(f"more than {PATTERN_MAX_CAP} distinct patterns (the cap of pattern_counts): select fewer genomes")
+            cap = min(cap * 16, PATTERN_MAX_CAP)
 
     def write_bgzf(self, step: int, gz_path: str, gzi_path: Optional[str] = None, level: int = 6,
                    threads: int = 1, first_contig: int = 0, ncontigs: Optional[int] = None) -> None:

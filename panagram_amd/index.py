@@ -1251,6 +1251,16 @@ class Index:
         """the matching rows of every bin of ``bin_size`` positions (``Genome.pattern_density``)"""
         return self.genomes[genome].pattern_density(have, lack, min_have, max_lack, chroms, step, bin_size)
 
+    def pattern_counts(self, genome, genomes=None, chrom=None, start=None, end=None, step=1):
+        """(keys, counts, selected names): the pattern spectrum of ``query_bitmap(genome, chrom, start, end, step)``'s rows over
+        the ``genomes`` selected (``Genome.pattern_counts``)"""
+        return self.genomes[genome].pattern_counts(genomes, chrom, start, end, step)
+
+    def pattern_spectrum(self, genome, genomes=None, chrom=None, start=None, end=None, step=1, top=None, min_rows=1) -> pd.DataFrame:
+        """the presence/absence patterns of the rows of ``query_bitmap(genome, chrom, start, end, step)`` and the rows each
+        holds (``Genome.pattern_spectrum``)"""
+        return self.genomes[genome].pattern_spectrum(genomes, chrom, start, end, step, top, min_rows)
+
     def region_tree(self, genome, chrom, start=None, end=None, step=None) -> "RegionTree":
         """The tree of the genomes over a region, as the viewer draws it (view.py:751-764: create_tree) — but from the pair
         counts of EVERY row of the region at ``step`` (default: the low-resolution step), not from a random sample of
@@ -1837,6 +1847,36 @@ class Genome:
                                 "matched": matched.get(c, np.zeros(0, np.int64)), "rows": geo[c][2] - geo[c][1]}) for c in chroms]
         return pd.concat(frames, ignore_index=True) if frames else pd.DataFrame(
             {"chr": np.zeros(0, object), "start": np.zeros(0, np.int64), "matched": np.zeros(0, np.int64), "rows": np.zeros(0, np.int64)})
+
+    # ---- PATTERNS: which presence/absence patterns occur, and how many rows each holds (query + value_counts) ----
+    def pattern_counts(self, genomes=None, chrom=None, start=None, end=None, step: int = 1):
+        """(keys uint64, counts uint64, selected names): the pattern spectrum of the rows of ``query(chrom, start, end, step)``
+        over the ``genomes`` selected (names or columns, at most 64; default: all of them) — bit i of a key is the row's bit
+        for the i-th selected genome in column order, ``keys`` ascending.  ``chrom=None``: every chromosome.  The rows are
+        inflated into HBM in consecutive pieces of at most ``similarity_budget`` bytes and reduced there by k_pattern_counts,
+        one call per piece; pieces and chromosomes are added up on the host.  No row comes back."""
+        from . import patterns
+        step = int(step)
+        chroms = self._checked_chroms(step, region=(chrom, start, end))
+        words, selected = patterns.select_words(self.index.genome_names, genomes)
+        parts = []
+        for c in chroms:
+            parts += [kc for _, _, kc in self._region_pieces(c, start, end, step, lambda res, ns, bstep, stride: res.pattern_counts(
+                [0], [0], [ns], words, step=bstep, stride=stride))]
+        keys, counts = patterns.merge(parts)
+        return keys, counts, selected
+
+    def pattern_spectrum(self, genomes=None, chrom=None, start=None, end=None, step: int = 1, top: Optional[int] = None,
+                         min_rows: int = 1) -> pd.DataFrame:
+        """pattern, n, rows, frac: the presence/absence patterns that occur in the rows of ``query(chrom, start, end, step)``
+        and the rows each holds — ``value_counts()`` of that frame's ``genomes`` columns, none of it read back to the host
+        (``pattern_counts``).  ``pattern`` has one 0 / 1 per selected genome in column order, ``n`` counts its ones, ``frac`` is
+        rows over all rows of the region; sorted by rows descending, then pattern.  ``min_rows`` drops rarer patterns, ``top``
+        keeps the first so many (``patterns.spectrum_frame``)."""
+        from . import patterns
+        patterns.spectrum_frame([], [], ["-"], top, min_rows)  # (its argument checks, before anything is read)
+        keys, counts, selected = self.pattern_counts(genomes, chrom, start, end, step)
+        return patterns.spectrum_frame(keys, counts, selected, top, min_rows)
 
     # ---- UMAPS: chrom_umaps.csv and genome_umap.csv (index.py:1100-1167) ----
     @property

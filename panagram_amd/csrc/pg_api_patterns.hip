@@ -13,73 +13,51 @@ extern "C" int pg_result_pattern_counts(pg_result *r, int step, uint32_t stride,
     PG_API_BEGIN
     if (!r || !ndistinct_out || !rows_out || !exceeded_out || (nwin && (!contig || !starts || !ends)) || (cap && (!keys_out || !counts_out)))
         return fail(PG_E_INVALID, "pg_result_pattern_counts: NULL argument");
-    if (int e = check_step(r, step)) return e;
-    if (stride < 1) return fail(PG_E_INVALID, "pg_result_pattern_counts: stride must be >= 1");
-    if (nwin > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_pattern_counts: %u windows (at most 2^31 - 1 per call)", nwin);
+    if (int e = check_window_call(r, step, stride, nwin, "pg_result_pattern_counts", "windows")) return e;
     if (cap > PATTERN_CAP_LIMIT)
         return fail(PG_E_INVALID, "pg_result_pattern_counts: room for %llu patterns asked (at most 2^30 per call)", (unsigned long long)cap);
     const uint32_t N = r->N;
     if (N < 1 || N > PATTERN_MAX_GENOMES)
         return fail(PG_E_INVALID, "pg_result_pattern_counts: %u genomes (1 to %u)", N, PATTERN_MAX_GENOMES);
-    // the selection: NULL is every genome, and the bits at and past N never count
     const uint32_t ndw = (N + 31) / 32;
-    std::vector<uint32_t> sw(ndw, 0);
+    const std::vector<uint32_t> sw = mask_words(N, select_words, 0xFFFFFFFFu);  // (NULL: every genome)
     uint32_t m = 0;
-    for (uint32_t d = 0; d < ndw; ++d) {
-        const uint32_t valid = N - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (N - 32 * d)) - 1u;
-        sw[d] = select_words ? select_words[d] & valid : valid;
-        m += (uint32_t)__builtin_popcount(sw[d]);
-    }
+    for (uint32_t d = 0; d < ndw; ++d) m += (uint32_t)__builtin_popcount(sw[d]);
     if (m == 0) return fail(PG_E_INVALID, "pg_result_pattern_counts: no genome selected");
     if (m > 64)
         return fail(PG_E_INVALID, "pg_result_pattern_counts: %u genomes selected (a pattern takes 1 to 64: select fewer)", m);
     bool low_columns = true;  // the selection is columns 0..m-1: a key is the row's first bytes
-    for (uint32_t d = 0; d < ndw; ++d) {
-        const uint32_t below = m <= 32 * d ? 0u : m - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (m - 32 * d)) - 1u;
-        low_columns = low_columns && sw[d] == below;
-    }
-    if (int e = check_rows_readable(r, step)) return e;
-    std::vector<uint64_t> se;
-    uint64_t longest = 0;
-    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", se, &longest)) return e;
+    for (uint32_t d = 0; d < ndw; ++d) low_columns = low_columns && sw[d] == (m <= 32 * d ? 0u : valid_word(m, d));
+    Windows w;
+    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", w)) return e;
     uint64_t total = 0;
     for (uint32_t i = 0; i < nwin; ++i) total += ends[i] - starts[i];
     *rows_out = total;
     *ndistinct_out = 0;
     *exceeded_out = 0;
     if (total == 0) return PG_OK;
-    // the chunks: PATTERN_CHUNK sampled rows each (an empty window has none)
     std::vector<uint2> chunks;
-    for (uint32_t i = 0; i < nwin; ++i)
-        for (uint64_t c0 = starts[i]; c0 < ends[i]; c0 += PATTERN_CHUNK) chunks.push_back(make_uint2(i, (uint32_t)c0));
-    if (chunks.size() > 0x7FFFFFFFu)
-        return fail(PG_E_INVALID, "pg_result_pattern_counts: %zu chunks of %u sampled rows (at most 2^31 - 1 per call)", chunks.size(),
-                    PATTERN_CHUNK);
+    if (int e = cut_chunks("pg_result_pattern_counts", nwin, starts, ends, PATTERN_CHUNK, chunks)) return e;
     const uint32_t nchunks = (uint32_t)chunks.size();
     uint64_t slots = 1024;
     while (slots < 2 * cap) slots *= 2;
     if (int e = use_device(r->ctx)) return e;
     if (int e = join_result(r)) return e;
     hipStream_t st = r->ctx->stream;
-    DevBuf<uint64_t> d_se;
     DevBuf<uint32_t> d_sw;
     DevBuf<uint2> d_chunks;
     DevBuf<unsigned long long> d_keys, d_cnt;  // d_cnt: the counts, then the four counters
     unsigned long long ctr[4] = {0, 0, 0, 0};
-    hipError_t e = d_se.alloc(se.size());
-    if (e == hipSuccess) e = d_sw.alloc(ndw);
-    if (e == hipSuccess) e = d_chunks.alloc(nchunks);
+    hipError_t e = w.upload(st);
+    if (e == hipSuccess) e = d_sw.upload(sw, st);
+    if (e == hipSuccess) e = d_chunks.upload(chunks, st);
     if (e == hipSuccess) e = d_keys.alloc(slots);
     if (e == hipSuccess) e = d_cnt.alloc(slots + 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_sw.get(), sw.data(), (size_t)ndw * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_chunks.get(), chunks.data(), (size_t)nchunks * sizeof(uint2), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_keys.get(), 0xFF, slots * 8, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_cnt.get(), 0, (slots + 4) * 8, st);
     if (e == hipSuccess)
-        e = launch_pattern_counts(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, d_se.get(), d_se.get() + 2 * (size_t)nwin,
-                                  d_chunks.get(), nchunks, d_sw.get(), m, low_columns, cap, d_keys.get(), d_cnt.get(), slots,
-                                  d_cnt.get() + slots);
+        e = launch_pattern_counts(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, w.base(), w.ends(), d_chunks.get(), nchunks,
+                                  d_sw.get(), m, low_columns, cap, d_keys.get(), d_cnt.get(), slots, d_cnt.get() + slots);
     if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_cnt.get() + slots, sizeof ctr, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_pattern_counts: %s", hipGetErrorString(e));

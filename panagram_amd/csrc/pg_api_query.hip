@@ -1,21 +1,31 @@
 // pg_api_query.hip — host side of the C-ABI: window queries over a result's finished rows, k-NN of rows.
 #include "pg_host.h"
 
-// Checks shared by the entry points that read a result's rows (here and in pg_api_patterns.hip), beside check_step (pg_api.hip):
-// one wording each, whoever asks.
-int pg::check_rows_readable(const pg_result *r, int step) {
+// What the window queries (here and in pg_api_patterns.hip) share, beside check_step (pg_api.hip): one wording of every refusal,
+// whoever asks.  A call opens with check_window_call, makes its own checks, and goes on with gather_windows.
+// the step, the stride and the number n of windows ("bins", "windows") of entry point fn
+int pg::check_window_call(const pg_result *r, int step, uint32_t stride, uint32_t n, const char *fn, const char *nouns) {
+    if (int e = check_step(r, step)) return e;
+    if (stride < 1) return fail(PG_E_INVALID, "%s: stride must be >= 1", fn);
+    if (n > 0x7FFFFFFFu) return fail(PG_E_INVALID, "%s: %u %s (at most 2^31 - 1 per call)", fn, n, nouns);
+    return PG_OK;
+}
+static int check_rows_readable(const pg_result *r, int step) {
     if (r->flags & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "the result has no row buffer");
     if (!r->ev_ok) return fail(PG_E_INVALID, "pg_anchor_run has not been called on this result");
     if (step != 1 && (r->flags & PG_ANCHOR_ROWS_ONLY) && !r->ev_epi && !r->rows_valid)
         return fail(PG_E_INVALID, "rows-only result: the low-resolution rows need pg_rows_epilogue first");
     return PG_OK;
 }
-// n windows ("bin", "window": the noun of the messages) of sampled rows, refused unless each lies within its contig ->
-// se[3 * n]: device byte offset of the contig's rows, then [start, end) in sampled rows; *longest: the longest of them
+// the rows must be readable; then n windows ("bin", "window": the noun of the messages) of sampled rows, refused unless each
+// lies within its contig -> w
 int pg::gather_windows(const pg_result *r, int step, uint32_t stride, uint32_t n, const uint32_t *contig, const uint64_t *starts,
-                       const uint64_t *ends, const char *noun, std::vector<uint64_t> &se, uint64_t *longest) {
+                       const uint64_t *ends, const char *noun, Windows &w) {
+    if (int e = check_rows_readable(r, step)) return e;
+    std::vector<uint64_t> &se = w.se;
     se.assign((size_t)n * 3, 0);
-    *longest = 0;
+    w.n = n;
+    w.longest = 0;
     for (uint32_t i = 0; i < n; ++i) {
         if (contig[i] >= r->ad.size()) return fail(PG_E_INVALID, "%s %u: contig %u out of range", noun, i, contig[i]);
         const AnchorDesc &a = r->ad[contig[i]];
@@ -28,8 +38,36 @@ int pg::gather_windows(const pg_result *r, int step, uint32_t stride, uint32_t n
         se[i] = step == 1 ? a.out_off : a.out100_off;
         se[n + i] = starts[i];
         se[2 * (size_t)n + i] = ends[i];
-        *longest = std::max(*longest, ends[i] - starts[i]);
+        w.longest = std::max(w.longest, ends[i] - starts[i]);
     }
+    return PG_OK;
+}
+// the bits of word d of a genome mask that are genomes: the bits at and past N never count
+uint32_t pg::valid_word(uint32_t N, uint32_t d) { return N - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (N - 32 * d)) - 1u; }
+// a caller's genome mask as ceil(N / 32) clamped words; a NULL pointer stands for if_null in every word
+std::vector<uint32_t> pg::mask_words(uint32_t N, const uint32_t *words, uint32_t if_null) {
+    std::vector<uint32_t> out((N + 31) / 32);
+    for (uint32_t d = 0; d < out.size(); ++d) out[d] = (words ? words[d] : if_null) & valid_word(N, d);
+    return out;
+}
+// pieces of a window for a (windows, pieces) grid: about 32 K sampled rows each for the longest window, then doubled (up to
+// cap) while the grid has fewer than 4096 blocks and a piece keeps more than 4096 rows
+uint32_t pg::pieces_for(uint64_t longest, uint32_t nwin, uint32_t cap) {
+    uint32_t pieces = (uint32_t)std::min<uint64_t>(cap, std::max<uint64_t>(1, longest / 32768));
+    while (pieces < cap && (uint64_t)nwin * pieces < 4096 && (uint64_t)pieces * 4096 < longest) pieces *= 2;
+    return pieces;
+}
+// the windows cut into chunks {window, first sampled row} of chunk_rows sampled rows each, a window's in order (an empty window
+// has none); window i's chunks are [first[i], first[i + 1])
+int pg::cut_chunks(const char *fn, uint32_t nwin, const uint64_t *starts, const uint64_t *ends, uint32_t chunk_rows,
+                   std::vector<uint2> &chunks, std::vector<uint64_t> *first) {
+    if (first) first->assign((size_t)nwin + 1, 0);
+    for (uint32_t i = 0; i < nwin; ++i) {
+        for (uint64_t c0 = starts[i]; c0 < ends[i]; c0 += chunk_rows) chunks.push_back(make_uint2(i, (uint32_t)c0));
+        if (first) (*first)[i + 1] = chunks.size();
+    }
+    if (chunks.size() > 0x7FFFFFFFu)
+        return fail(PG_E_INVALID, "%s: %zu chunks of %u sampled rows (at most 2^31 - 1 per call)", fn, chunks.size(), chunk_rows);
     return PG_OK;
 }
 
@@ -82,39 +120,27 @@ extern "C" int pg_result_bin_colsums(pg_result *r, int step, uint32_t stride, ui
     PG_API_BEGIN
     if (!r || (nbins && (!contig || !starts || !ends || !cs_out || !kept_out)))
         return fail(PG_E_INVALID, "pg_result_bin_colsums: NULL argument");
-    if (int e = check_step(r, step)) return e;
-    if (stride < 1) return fail(PG_E_INVALID, "pg_result_bin_colsums: stride must be >= 1");
-    if (nbins > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_bin_colsums: %u bins (at most 2^31 - 1 per call)", nbins);
+    if (int e = check_window_call(r, step, stride, nbins, "pg_result_bin_colsums", "bins")) return e;
     const uint32_t N = r->N;
     if (N < 1 || N > 4096) return fail(PG_E_INVALID, "pg_result_bin_colsums: %u genomes (1 to 4096)", N);
-    if (int e = check_rows_readable(r, step)) return e;
-    const uint32_t ndw = (N + 31) / 32;
-    std::vector<uint64_t> se;
-    uint64_t longest = 0;
-    if (int e = gather_windows(r, step, stride, nbins, contig, starts, ends, "bin", se, &longest)) return e;
-    std::vector<uint32_t> kw(ndw, 0);
-    if (keep_words)
-        for (uint32_t d = 0; d < ndw; ++d) kw[d] = keep_words[d] & (N - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (N - 32 * d)) - 1u);
+    Windows w;
+    if (int e = gather_windows(r, step, stride, nbins, contig, starts, ends, "bin", w)) return e;
+    const std::vector<uint32_t> kw = mask_words(N, keep_words, 0u);  // (NULL: no keep mask)
     if (nbins == 0) return PG_OK;
     if (int e = use_device(r->ctx)) return e;
     if (int e = join_result(r)) return e;
     hipStream_t st = r->ctx->stream;
-    // pieces: about 32 K sampled rows each for the longest bin, and enough blocks to fill the device
-    uint32_t pieces = (uint32_t)std::min<uint64_t>(256, std::max<uint64_t>(1, longest / 32768));
-    while (pieces < 256 && (uint64_t)nbins * pieces < 4096 && (uint64_t)pieces * 4096 < longest) pieces *= 2;
-    DevBuf<uint64_t> d_se;
+    const uint32_t pieces = pieces_for(w.longest, nbins, 256);
     DevBuf<uint32_t> d_kw;
     DevBuf<unsigned long long> d_out;
     const size_t nc = (size_t)nbins * N;
-    hipError_t e = d_se.alloc(se.size());
-    if (e == hipSuccess) e = d_kw.alloc(ndw);
+    hipError_t e = w.upload(st);
+    if (e == hipSuccess) e = d_kw.upload(kw, st);
     if (e == hipSuccess) e = d_out.alloc(nc + nbins);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_kw.get(), kw.data(), (size_t)ndw * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, (nc + nbins) * 8, st);
     if (e == hipSuccess)
-        e = launch_bin_colsums(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nbins, pieces, d_se.get(), d_se.get() + nbins,
-                               d_se.get() + 2 * (size_t)nbins, d_kw.get(), omit_fixed ? 1u : 0u, d_out.get(), d_out.get() + nc);
+        e = launch_bin_colsums(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nbins, pieces, w.base(), w.starts(), w.ends(),
+                               d_kw.get(), omit_fixed ? 1u : 0u, d_out.get(), d_out.get() + nc);
     if (e == hipSuccess) e = hipMemcpyAsync(cs_out, d_out.get(), nc * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(kept_out, d_out.get() + nc, (size_t)nbins * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -130,35 +156,27 @@ extern "C" int pg_result_pair_counts(pg_result *r, int step, uint32_t stride, ui
     PG_API_BEGIN
     if (!r || (nwin && (!contig || !starts || !ends || !pairs_out)))
         return fail(PG_E_INVALID, "pg_result_pair_counts: NULL argument");
-    if (int e = check_step(r, step)) return e;
-    if (stride < 1) return fail(PG_E_INVALID, "pg_result_pair_counts: stride must be >= 1");
-    if (nwin > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_pair_counts: %u windows (at most 2^31 - 1 per call)", nwin);
+    if (int e = check_window_call(r, step, stride, nwin, "pg_result_pair_counts", "windows")) return e;
     const uint32_t N = r->N;
     if (N < 1 || N > PAIRS_MAX_GENOMES)
         return fail(PG_E_INVALID, "pg_result_pair_counts: %u genomes (the pair counts take 1 to %u)", N, PAIRS_MAX_GENOMES);
-    if (int e = check_rows_readable(r, step)) return e;
-    std::vector<uint64_t> se;
-    uint64_t longest = 0;
-    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", se, &longest)) return e;
+    Windows w;
+    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", w)) return e;
     if (nwin == 0) return PG_OK;
     if (int e = use_device(r->ctx)) return e;
     if (int e = join_result(r)) return e;
     hipStream_t st = r->ctx->stream;
-    // pieces: about 32 K sampled rows each for the longest window, then doubled while the grid has fewer than 4096 blocks
-    // (a lone window of 32 M rows in 256 pieces leaves three quarters of the SIMDs' wave slots empty: 3.3 ms, in 2048
-    // pieces as below) and a piece keeps more than 4096 rows (it ends with up to N^2 / 2 atomics)
-    uint32_t pieces = (uint32_t)std::min<uint64_t>(2048, std::max<uint64_t>(1, longest / 32768));
-    while (pieces < 2048 && (uint64_t)nwin * pieces < 4096 && (uint64_t)pieces * 4096 < longest) pieces *= 2;
-    DevBuf<uint64_t> d_se;
+    // up to 2048 pieces, not bin_colsums' 256: a lone window of 32 M rows in 256 pieces leaves three quarters of the SIMDs' wave
+    // slots empty (3.3 ms, in 2048 pieces as here); a piece keeps more than 4096 rows as it ends with up to N^2 / 2 atomics
+    const uint32_t pieces = pieces_for(w.longest, nwin, 2048);
     DevBuf<unsigned long long> d_out;
     const size_t nc = (size_t)nwin * N * N;
-    hipError_t e = d_se.alloc(se.size());
+    hipError_t e = w.upload(st);
     if (e == hipSuccess) e = d_out.alloc(nc);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, nc * 8, st);
     if (e == hipSuccess)
-        e = launch_pair_counts(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nwin, pieces, d_se.get(), d_se.get() + nwin,
-                               d_se.get() + 2 * (size_t)nwin, d_out.get());
+        e = launch_pair_counts(st, N, step == 1 ? r->d_out1 : r->d_out100, stride, nwin, pieces, w.base(), w.starts(), w.ends(),
+                               d_out.get());
     if (e == hipSuccess) e = hipMemcpyAsync(pairs_out, d_out.get(), nc * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_pair_counts: %s", hipGetErrorString(e));
@@ -183,56 +201,39 @@ extern "C" int pg_result_find_runs(pg_result *r, int step, uint32_t stride, uint
     PG_API_BEGIN
     if (!r || !total_out || (nwin && (!contig || !starts || !ends || !nruns_out || !matched_out)) || (cap && (!run_start || !run_end)))
         return fail(PG_E_INVALID, "pg_result_find_runs: NULL argument");
-    if (int e = check_step(r, step)) return e;
-    if (stride < 1) return fail(PG_E_INVALID, "pg_result_find_runs: stride must be >= 1");
-    if (nwin > 0x7FFFFFFFu) return fail(PG_E_INVALID, "pg_result_find_runs: %u windows (at most 2^31 - 1 per call)", nwin);
+    if (int e = check_window_call(r, step, stride, nwin, "pg_result_find_runs", "windows")) return e;
     const uint32_t N = r->N;
     if (N < 1 || N > FIND_MAX_GENOMES) return fail(PG_E_INVALID, "pg_result_find_runs: %u genomes (1 to %u)", N, FIND_MAX_GENOMES);
-    if (int e = check_rows_readable(r, step)) return e;
-    std::vector<uint64_t> se;
-    uint64_t longest = 0;
-    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", se, &longest)) return e;
+    Windows w;
+    if (int e = gather_windows(r, step, stride, nwin, contig, starts, ends, "window", w)) return e;
     *total_out = 0;
     if (nwin == 0) return PG_OK;
-    // the masks: a NULL pointer is the empty set, and the bits at and past N never count
+    // the masks, have then lack: a NULL pointer is the empty set
     const uint32_t ndw = (N + 31) / 32;
-    std::vector<uint32_t> mw((size_t)2 * ndw, 0);
-    for (uint32_t d = 0; d < ndw; ++d) {
-        const uint32_t valid = N - 32 * d >= 32 ? 0xFFFFFFFFu : (1u << (N - 32 * d)) - 1u;
-        if (have_words) mw[d] = have_words[d] & valid;
-        if (lack_words) mw[ndw + d] = lack_words[d] & valid;
-    }
-    // the chunks: FIND_CHUNK sampled rows each, a window's in order (an empty window has none)
-    std::vector<uint2> chunks;
-    std::vector<uint64_t> first((size_t)nwin + 1, 0);  // window i's chunks: [first[i], first[i + 1])
-    for (uint32_t i = 0; i < nwin; ++i) {
-        for (uint64_t c0 = starts[i]; c0 < ends[i]; c0 += FIND_CHUNK) chunks.push_back(make_uint2(i, (uint32_t)c0));
-        first[i + 1] = chunks.size();
-    }
+    std::vector<uint32_t> mw = mask_words(N, have_words, 0u);
+    const std::vector<uint32_t> lw = mask_words(N, lack_words, 0u);
+    mw.insert(mw.end(), lw.begin(), lw.end());
     for (uint32_t i = 0; i < nwin; ++i) nruns_out[i] = matched_out[i] = 0;
+    std::vector<uint2> chunks;
+    std::vector<uint64_t> first;
+    if (int e = cut_chunks("pg_result_find_runs", nwin, starts, ends, FIND_CHUNK, chunks, &first)) return e;
     if (chunks.empty()) return PG_OK;
-    if (chunks.size() > 0x7FFFFFFFu)
-        return fail(PG_E_INVALID, "pg_result_find_runs: %zu chunks of %u sampled rows (at most 2^31 - 1 per call)", chunks.size(), FIND_CHUNK);
     const uint32_t nchunks = (uint32_t)chunks.size();
     if (int e = use_device(r->ctx)) return e;
     if (int e = join_result(r)) return e;
     hipStream_t st = r->ctx->stream;
     const uint8_t *rows = step == 1 ? r->d_out1 : r->d_out100;
-    DevBuf<uint64_t> d_se;
     DevBuf<uint32_t> d_mw;
     DevBuf<uint2> d_chunks;
     DevBuf<uint4> d_counts;
     std::vector<uint4> counts(nchunks);
-    hipError_t e = d_se.alloc(se.size());
-    if (e == hipSuccess) e = d_mw.alloc(mw.size());
-    if (e == hipSuccess) e = d_chunks.alloc(nchunks);
+    hipError_t e = w.upload(st);
+    if (e == hipSuccess) e = d_mw.upload(mw, st);
+    if (e == hipSuccess) e = d_chunks.upload(chunks, st);
     if (e == hipSuccess) e = d_counts.alloc(nchunks);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_se.get(), se.data(), se.size() * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_mw.get(), mw.data(), mw.size() * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_chunks.get(), chunks.data(), (size_t)nchunks * sizeof(uint2), hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = launch_find_runs(st, N, rows, stride, d_se.get(), d_se.get() + nwin, d_se.get() + 2 * (size_t)nwin, d_chunks.get(), nchunks,
-                             d_mw.get(), d_mw.get() + ndw, min_have, max_lack, d_counts.get(), nullptr, 0, nullptr, nullptr);
+        e = launch_find_runs(st, N, rows, stride, w.base(), w.starts(), w.ends(), d_chunks.get(), nchunks, d_mw.get(),
+                             d_mw.get() + ndw, min_have, max_lack, d_counts.get(), nullptr, 0, nullptr, nullptr);
     if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_find_runs: %s", hipGetErrorString(e));
@@ -257,13 +258,11 @@ extern "C" int pg_result_find_runs(pg_result *r, int step, uint32_t stride, uint
     if (total == 0 || cap == 0 || total > cap) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
     DevBuf<ulonglong2> d_offs;
     DevBuf<uint32_t> d_runs;
-    e = d_offs.alloc(nchunks);
+    e = d_offs.upload(offs, st);
     if (e == hipSuccess) e = d_runs.alloc((size_t)2 * total);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_offs.get(), offs.data(), (size_t)nchunks * sizeof(ulonglong2), hipMemcpyHostToDevice, st);
     if (e == hipSuccess)
-        e = launch_find_runs(st, N, rows, stride, d_se.get(), d_se.get() + nwin, d_se.get() + 2 * (size_t)nwin, d_chunks.get(), nchunks,
-                             d_mw.get(), d_mw.get() + ndw, min_have, max_lack, nullptr, d_offs.get(), total, d_runs.get(),
-                             d_runs.get() + total);
+        e = launch_find_runs(st, N, rows, stride, w.base(), w.starts(), w.ends(), d_chunks.get(), nchunks, d_mw.get(),
+                             d_mw.get() + ndw, min_have, max_lack, nullptr, d_offs.get(), total, d_runs.get(), d_runs.get() + total);
     if (e == hipSuccess) e = hipMemcpyAsync(run_start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(run_end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);

@@ -15,21 +15,9 @@
 // A wave's counter never exceeds the rows it visits, at most a quarter of the bin plus 64 — below 2^32 for any contig (a
 // contig's rows are counted in 32 bits) — and the block sums its waves in 64 bits.
 #include "pg_kernels.h"
+#include "pg_rowread.h"
 
 namespace pg {
-
-// bytes [4d, min(4d + 4, nbytes)) of a row as a little-endian word
-__device__ __forceinline__ uint32_t bins_row_word(const uint8_t *__restrict__ p, uint32_t d, uint32_t nbytes) {
-    const uint32_t nb = min(4u, nbytes - 4 * d);
-    uint32_t v = 0;
-    for (uint32_t b = 0; b < nb; ++b) v |= (uint32_t)p[4 * d + b] << (8 * b);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t bins_valid_bits(uint32_t N, uint32_t d) {
-    const uint32_t ng = N - 32 * d;
-    return ng >= 32 ? 0xFFFFFFFFu : (1u << ng) - 1u;
-}
 
 // word d (ng of its bits) of the wave's 64 rows -> the wave's counters wc[32 d ..]
 __device__ __forceinline__ void bins_count_word(uint32_t w, uint32_t d, uint32_t N, uint32_t *wc, uint32_t lane) {
@@ -48,8 +36,9 @@ __device__ __forceinline__ void bins_count_word(uint32_t w, uint32_t d, uint32_t
 }
 
 // MAXW = 4: rows of up to 16 bytes (N <= 128), the row's words held in registers between the two passes; MAXW = 0: any
-// width, the words read again for the second pass (from the cache)
-template <uint32_t MAXW>
+// width, the words read again for the second pass (from the cache).  WHOLE: rows of whole words, read by aligned loads; the
+// kernel of all other rows has no test for them (N = 8 and 16 run as they did before there was one: profiles/intros_rate.txt)
+template <uint32_t MAXW, bool WHOLE>
 __global__ __launch_bounds__(256) void k_bin_colsums(uint32_t N, const uint8_t *__restrict__ rows, uint32_t stride,
                                                      const uint64_t *__restrict__ base, const uint64_t *__restrict__ starts,
                                                      const uint64_t *__restrict__ ends, const uint32_t *__restrict__ keep,
@@ -80,8 +69,8 @@ __global__ __launch_bounds__(256) void k_bin_colsums(uint32_t N, const uint8_t *
             for (uint32_t d = 0; d < (MAXW ? MAXW : 1); ++d) {
                 w[d] = 0;
                 if (d < ndw) {
-                    const uint32_t vm = bins_valid_bits(N, d);
-                    w[d] = act ? bins_row_word(p, d, nbytes) & vm : 0u;
+                    const uint32_t vm = valid_bits(N, d);
+                    w[d] = act ? row_word<WHOLE>(p, d, nbytes) & vm : 0u;
                     anyk |= w[d] & kw[d];
                     full_raw &= w[d] == vm;
                     full_kept &= (w[d] | kw[d]) == vm;
@@ -89,8 +78,8 @@ __global__ __launch_bounds__(256) void k_bin_colsums(uint32_t N, const uint8_t *
             }
         } else {
             for (uint32_t d = 0; d < ndw; ++d) {
-                const uint32_t vm = bins_valid_bits(N, d), k = keep[d];
-                const uint32_t x = act ? bins_row_word(p, d, nbytes) & vm : 0u;
+                const uint32_t vm = valid_bits(N, d), k = keep[d];
+                const uint32_t x = act ? row_word<WHOLE>(p, d, nbytes) & vm : 0u;
                 anyk |= x & k;
                 full_raw &= x == vm;
                 full_kept &= (x | k) == vm;
@@ -106,7 +95,7 @@ __global__ __launch_bounds__(256) void k_bin_colsums(uint32_t N, const uint8_t *
         } else {
             for (uint32_t d = 0; d < ndw; ++d) {
                 const uint32_t k = keep[d];
-                const uint32_t x = take ? bins_row_word(p, d, nbytes) & bins_valid_bits(N, d) : 0u;
+                const uint32_t x = take ? row_word<WHOLE>(p, d, nbytes) & valid_bits(N, d) : 0u;
                 bins_count_word(take ? (anyk ? x : x | k) : 0u, d, N, wc, lane);
             }
         }
@@ -128,12 +117,22 @@ hipError_t launch_bin_colsums(hipStream_t st, uint32_t ngenomes, const uint8_t *
                               const uint32_t *keep, uint32_t omit_fixed, unsigned long long *cs, unsigned long long *kept) {
     if (nbins == 0) return hipSuccess;
     const size_t lds = (4 * (size_t)ngenomes + 4) * 4;
-    if (ngenomes <= 128)
-        hipLaunchKernelGGL(k_bin_colsums<4>, dim3(nbins, pieces), dim3(256), lds, st, ngenomes, rows, stride, base, starts, ends,
-                           keep, omit_fixed, cs, kept);
-    else
-        hipLaunchKernelGGL(k_bin_colsums<0>, dim3(nbins, pieces), dim3(256), lds, st, ngenomes, rows, stride, base, starts, ends,
-                           keep, omit_fixed, cs, kept);
+    const bool whole = (ngenomes + 7) / 8 % 4 == 0;
+#define PG_BINS_LAUNCH(MAXW, WHOLE)                                                                                              \
+    hipLaunchKernelGGL((k_bin_colsums<MAXW, WHOLE>), dim3(nbins, pieces), dim3(256), lds, st, ngenomes, rows, stride, base, starts, \
+                       ends, keep, omit_fixed, cs, kept)
+    if (ngenomes <= 128) {
+        if (whole)
+            PG_BINS_LAUNCH(4, true);
+        else
+            PG_BINS_LAUNCH(4, false);
+    } else {
+        if (whole)
+            PG_BINS_LAUNCH(0, true);
+        else
+            PG_BINS_LAUNCH(0, false);
+    }
+#undef PG_BINS_LAUNCH
     return hipGetLastError();
 }
 

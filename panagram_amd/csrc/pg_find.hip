@@ -34,21 +34,12 @@
 // N <= 128 (k_find_runs<4, .>): the masks in registers, a row's words loaded once; beyond, up to FIND_MAX_GENOMES
 // (k_find_runs<0, .>), word by word against masks staged in LDS.
 #include "pg_kernels.h"
+#include "pg_rowread.h"
 
 namespace pg {
 
 constexpr uint32_t FIND_TILE = 256;  // sampled rows per tile: one 64-row word per wave
 static_assert(FIND_CHUNK % FIND_TILE == 0, "a chunk is a whole number of tiles");
-
-// bytes [4d, min(4d + 4, nbytes)) of a row as a little-endian word (rows of whole words: one aligned load — a contig's rows
-// start on 16 bytes); never a byte outside the row
-__device__ __forceinline__ uint32_t find_row_word(const uint8_t *__restrict__ p, uint32_t d, uint32_t nbytes) {
-    if ((nbytes & 3u) == 0) return *reinterpret_cast<const uint32_t *>(p + 4 * d);
-    const uint32_t nb = min(4u, nbytes - 4 * d);
-    uint32_t v = 0;
-    for (uint32_t b = 0; b < nb; ++b) v |= (uint32_t)p[4 * d + b] << (8 * b);
-    return v;
-}
 
 // does the row at p match?  MAXW: hw / lw are the masks' words in registers; 0: msk = [have words][lack words] in LDS
 template <uint32_t MAXW>
@@ -59,14 +50,14 @@ __device__ __forceinline__ bool find_match(const uint8_t *__restrict__ p, uint32
 #pragma unroll
         for (uint32_t d = 0; d < (MAXW ? MAXW : 1); ++d) {
             if (d < ndw) {
-                const uint32_t w = find_row_word(p, d, nbytes);
+                const uint32_t w = row_word(p, d, nbytes);
                 ch += (uint32_t)__popc(w & hw[d]);
                 cl += (uint32_t)__popc(w & lw[d]);
             }
         }
     } else {
         for (uint32_t d = 0; d < ndw; ++d) {
-            const uint32_t w = find_row_word(p, d, nbytes);
+            const uint32_t w = row_word(p, d, nbytes);
             ch += (uint32_t)__popc(w & msk[d]);
             cl += (uint32_t)__popc(w & msk[ndw + d]);
         }

@@ -187,6 +187,10 @@ struct DevBuf {
         if (p) hipFree(p);
     }
     hipError_t alloc(size_t count) { return hipMalloc(reinterpret_cast<void **>(&p), count * sizeof(T)); }
+    hipError_t upload(const std::vector<T> &h, hipStream_t st) {  // alloc, then the host vector's copy enqueued
+        const hipError_t e = alloc(h.size());
+        return e != hipSuccess ? e : hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st);
+    }
     T *get() const { return p; }
 };
 template <class T>
@@ -231,6 +235,19 @@ static constexpr double GROW_AT = 0.55;     // grow when keys > GROW_AT * slots
 static constexpr double TARGET_LOAD = 0.375; // load right after growing (3 keys per 8-slot line)
 static constexpr double HARD_LOAD = 0.85;   // worst-case guard before a batch
 
+// The windows of one window query (pg_result_bin_colsums, _pair_counts, _find_runs, _pattern_counts), as gather_windows
+// leaves them: per window the device byte offset of its contig's rows and [start, end) in sampled rows.
+struct Windows {
+    uint32_t n = 0;
+    uint64_t longest = 0;      // sampled rows of the longest window
+    std::vector<uint64_t> se;  // [3 n]: the offsets, the starts, the ends
+    DevBuf<uint64_t> d_se;
+    hipError_t upload(hipStream_t st) { return d_se.upload(se, st); }
+    const uint64_t *base() const { return d_se.get(); }
+    const uint64_t *starts() const { return d_se.get() + n; }
+    const uint64_t *ends() const { return d_se.get() + 2 * (size_t)n; }
+};
+
 // Helpers that cross a unit: defined once, in the unit named, and hidden from the dynamic symbol table.
 namespace pg {
 // pg_api.hip
@@ -250,10 +267,15 @@ PG_INTERNAL int join_result(pg_result *r);
 PG_INTERNAL int next_events(pg_result *r, bool probe);
 // pg_api_seqset.hip
 PG_INTERNAL void seqset_release(pg_seqset *s);
-// pg_api_query.hip
-PG_INTERNAL int check_rows_readable(const pg_result *r, int step);
+// pg_api_query.hip: what the window queries share (a call's own checks come between check_window_call and gather_windows)
+PG_INTERNAL int check_window_call(const pg_result *r, int step, uint32_t stride, uint32_t n, const char *fn, const char *nouns);
 PG_INTERNAL int gather_windows(const pg_result *r, int step, uint32_t stride, uint32_t n, const uint32_t *contig, const uint64_t *starts,
-                               const uint64_t *ends, const char *noun, std::vector<uint64_t> &se, uint64_t *longest);
+                               const uint64_t *ends, const char *noun, Windows &w);
+PG_INTERNAL uint32_t valid_word(uint32_t N, uint32_t d);
+PG_INTERNAL std::vector<uint32_t> mask_words(uint32_t N, const uint32_t *words, uint32_t if_null);
+PG_INTERNAL uint32_t pieces_for(uint64_t longest, uint32_t nwin, uint32_t cap);
+PG_INTERNAL int cut_chunks(const char *fn, uint32_t nwin, const uint64_t *starts, const uint64_t *ends, uint32_t chunk_rows,
+                           std::vector<uint2> &chunks, std::vector<uint64_t> *first = nullptr);
 // pg_api_bgzf.hip
 PG_INTERNAL void df_free_buffers(pg_ctx::DfSet &d);
 }  // namespace pg

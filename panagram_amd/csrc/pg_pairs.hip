@@ -25,26 +25,12 @@
 // N <= 128 (k_pair_counts<4>): a lane loads its row's words once, into registers, before the ballots; beyond, up to
 // PAIRS_MAX_GENOMES (k_pair_counts<0>), word by word.
 #include "pg_kernels.h"
+#include "pg_rowread.h"
 
 namespace pg {
 
 constexpr uint32_t PAIRS_TILE = 256;  // sampled rows per tile: one 64-row word per wave
 constexpr uint32_t PAIRS_ROUNDS = 3;  // 4 x 4 blocks per thread and slice
-
-// bytes [4d, min(4d + 4, nbytes)) of a row as a little-endian word (rows of whole words: one aligned load — a contig's rows
-// start on 16 bytes)
-__device__ __forceinline__ uint32_t pairs_row_word(const uint8_t *__restrict__ p, uint32_t d, uint32_t nbytes) {
-    if ((nbytes & 3u) == 0) return *reinterpret_cast<const uint32_t *>(p + 4 * d);
-    const uint32_t nb = min(4u, nbytes - 4 * d);
-    uint32_t v = 0;
-    for (uint32_t b = 0; b < nb; ++b) v |= (uint32_t)p[4 * d + b] << (8 * b);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t pairs_valid_bits(uint32_t N, uint32_t d) {
-    const uint32_t ng = N - 32 * d;
-    return ng >= 32 ? 0xFFFFFFFFu : (1u << ng) - 1u;
-}
 
 // word d of the wave's 64 rows: the column word of bit b goes to lane b (d even) / 32 + b (d odd)
 __device__ __forceinline__ uint64_t pairs_ballot_word(uint32_t w, uint32_t d, uint32_t N, uint32_t lane, uint64_t mine) {
@@ -100,7 +86,7 @@ __global__ __launch_bounds__(256) void k_pair_counts(uint32_t N, const uint8_t *
             uint32_t w[MAXW ? MAXW : 1];
 #pragma unroll
             for (uint32_t d = 0; d < (MAXW ? MAXW : 1); ++d)
-                w[d] = act && d < ndw ? pairs_row_word(p, d, nbytes) & pairs_valid_bits(N, d) : 0u;
+                w[d] = act && d < ndw ? row_word(p, d, nbytes) & valid_bits(N, d) : 0u;
             uint64_t mine = 0;
 #pragma unroll
             for (uint32_t d = 0; d < (MAXW ? MAXW : 1); ++d) {
@@ -114,7 +100,7 @@ __global__ __launch_bounds__(256) void k_pair_counts(uint32_t N, const uint8_t *
             for (uint32_t q = 0; 64 * q < NC; ++q) {
                 uint64_t mine = 0;
                 for (uint32_t d = 2 * q; d < min(2 * q + 2, ndw); ++d)
-                    mine = pairs_ballot_word(act ? pairs_row_word(p, d, nbytes) & pairs_valid_bits(N, d) : 0u, d, N, lane, mine);
+                    mine = pairs_ballot_word(act ? row_word(p, d, nbytes) & valid_bits(N, d) : 0u, d, N, lane, mine);
                 mycols[64 * q + lane] = mine;
             }
         }

@@ -37,6 +37,7 @@
 //              the host appends it as the spectrum's last (largest) key.
 // Counts are integers: the result does not depend on the order of the atomics.
 #include "pg_kernels.h"
+#include "pg_rowread.h"
 
 namespace pg {
 
@@ -47,28 +48,6 @@ constexpr unsigned long long PAT_EMPTY = ~0ull;
 static_assert(PATTERN_CHUNK % PAT_TILE == 0, "a chunk is a whole number of tiles");
 static_assert((PAT_LSLOTS & (PAT_LSLOTS - 1)) == 0, "the LDS table is indexed by the hash's low bits");
 
-// bytes [4d, min(4d + 4, nbytes)) of a row as a little-endian word, never a byte outside the row (pg_find.hip: find_row_word)
-__device__ __forceinline__ uint32_t pat_row_word(const uint8_t *__restrict__ p, uint32_t d, uint32_t nbytes) {
-    if ((nbytes & 3u) == 0) return *reinterpret_cast<const uint32_t *>(p + 4 * d);
-    const uint32_t nb = min(4u, nbytes - 4 * d);
-    uint32_t v = 0;
-    for (uint32_t b = 0; b < nb; ++b) v |= (uint32_t)p[4 * d + b] << (8 * b);
-    return v;
-}
-
-// bytes [0, min(8, nbytes)) of a row, zero-extended (rows of whole 8 / 4 bytes: aligned loads — a contig's rows start on 16 bytes)
-__device__ __forceinline__ uint64_t pat_row_low(const uint8_t *__restrict__ p, uint32_t nbytes) {
-    if ((nbytes & 7u) == 0) return *reinterpret_cast<const uint64_t *>(p);
-    if ((nbytes & 3u) == 0) {
-        const uint64_t lo = *reinterpret_cast<const uint32_t *>(p);
-        return nbytes > 4 ? lo | (uint64_t)*reinterpret_cast<const uint32_t *>(p + 4) << 32 : lo;
-    }
-    const uint32_t nb = min(8u, nbytes);
-    uint64_t v = 0;
-    for (uint32_t b = 0; b < nb; ++b) v |= (uint64_t)p[b] << (8 * b);
-    return v;
-}
-
 // the key of the row at p under the selection words sel[ndw] (uniform: every lane walks the same fields)
 __device__ __forceinline__ uint64_t pat_key_select(const uint8_t *__restrict__ p, uint32_t nbytes, uint32_t ndw, const uint32_t *sel) {
     uint64_t key = 0;
@@ -76,7 +55,7 @@ __device__ __forceinline__ uint64_t pat_key_select(const uint8_t *__restrict__ p
     for (uint32_t d = 0; d < ndw; ++d) {
         uint32_t mk = sel[d];
         if (!mk) continue;
-        const uint32_t w = pat_row_word(p, d, nbytes);
+        const uint32_t w = row_word(p, d, nbytes);
         while (mk) {  // one maximal run of selected bits [b, b + len) per turn
             const uint32_t b = (uint32_t)__builtin_ctz(mk);
             const uint32_t t = ~(mk >> b);  // (0 only for b = 0 and a word of 32 selected bits)
@@ -157,7 +136,7 @@ __global__ __launch_bounds__(256) void k_pattern_counts(uint32_t N, const uint8_
         uint64_t key = 0;
         if (valid) {
             const uint8_t *p = crow + j * stride * nbytes;
-            key = FAST ? pat_row_low(p, nbytes) & low : pat_key_select(p, nbytes, ndw, lsel);
+            key = FAST ? row_low(p, nbytes) & low : pat_key_select(p, nbytes, ndw, lsel);
         }
         const uint64_t before = __shfl_up((unsigned long long)key, 1);
         const bool head = valid && (lane == 0 || key != before);

@@ -272,7 +272,7 @@ def windows(nk):
     return np.array([s for s, _ in w], np.uint64), np.array([e for _, e in w], np.uint64)
 
 
-BINS_N = [3, 8, 9, 32, 33, 64, 65, 128, 129, 130, 300]
+BINS_N = [3, 8, 9, 32, 33, 64, 65, 128, 129, 130, 256, 300]
 BINS_NK = [201000, 1000, 1]
 BINS_STRIDES = [1, 7, 100]
 BINS_MIN_ROWS = 64  # bins of at least this many sampled rows hold every class of row (test_rows_craft_cpu.py)

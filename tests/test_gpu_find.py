@@ -17,7 +17,7 @@ from tests.test_gpu_pair_counts import windows as pair_windows
 pytestmark = pytest.mark.gpu
 
 K = 21
-FIND_N = [1, 2, 7, 8, 9, 31, 32, 33, 64, 65, 127, 128, 129, 130, 1000]
+FIND_N = [1, 2, 7, 8, 9, 31, 32, 33, 64, 65, 127, 128, 129, 130, 256, 1000]
 STRIDES = [1, 3, 100]
 PG_E_INVALID = -1
 

@@ -146,10 +146,21 @@ def _straddling(n):
     return cols
 
 
-SELECTIONS = [(9, [0, 8]), (33, [31, 32]), (130, None), (1000, [0, 511, 999]), (64, list(range(63)))]
+# (the last two: rows of whole words, 8 and 32 bytes, off the low columns, with a field that crosses a word boundary)
+SELECTIONS = [(9, [0, 8]), (33, [31, 32]), (130, None), (1000, [0, 511, 999]), (64, list(range(63))), (64, [0, 63]),
+              (256, [31, 32, 255])]
 
 
-@pytest.mark.parametrize("planted,select", [pytest.param(n, s, id=f"N{n}") for n, s in SELECTIONS], indirect=["planted"])
+def _selection_ids():
+    """N<n>, and N<n>-<columns> for a second selection at the same N"""
+    seen = set()
+    for n, s in SELECTIONS:
+        yield f"N{n}" if n not in seen else f"N{n}-" + "_".join(map(str, s))
+        seen.add(n)
+
+
+@pytest.mark.parametrize("planted,select", [pytest.param(n, s, id=i) for (n, s), i in zip(SELECTIONS, _selection_ids())],
+                         indirect=["planted"])
 def test_selections(planted, select):
     """(N = 64, the 63 columns below the top one: the fast path's condition is false by one bit)"""
     res, n = planted

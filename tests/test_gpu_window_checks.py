@@ -1,6 +1,6 @@
 """GPU: what the host checks of pg_result_bin_colsums, pg_result_pair_counts and pg_result_window_stats refuse, in which
-words, and what they let through (panagram_amd/csrc: check_step in pg_api.hip, check_rows_readable and gather_windows in
-pg_api_query.hip).  The two
+words, and what they let through (panagram_amd/csrc: check_step in pg_api.hip, check_window_call, check_rows_readable and
+gather_windows in pg_api_query.hip).  The two
 first share their checks and differ in one noun; pg_result_window_stats clamps a window at its contig's end where they
 refuse it.  The messages below were written down from the entry points as they stood before they shared those helpers.
 

@@ -155,6 +155,17 @@ int pg_kmc_kmer_length(const void *pre, size_t pre_len, uint32_t *k);
 /* statistics: distinct keys, slot capacity, bucket count, bytes, summed over sub-tables */
 int pg_table_stats(pg_table *tbl, uint64_t *nkeys, uint64_t *nslots, uint64_t *nbuckets,
                    uint64_t *bytes);
+/* Shared distinct k-mer counts of the pan-genome, read off the table in one pass over its slots (k_table_pair_counts):
+ * pairs[a*ngenomes + b] = distinct canonical k-mers held by both genome a and genome b — the full symmetric matrix, its
+ * diagonal the distinct k-mers of each genome; occ[n], n = 0..ngenomes, = distinct k-mers held by exactly n genomes
+ * (occ[ngenomes] is the core; occ[0] counts slots that hold a key and no bit, and is reported as found); priv[g] = k-mers
+ * of genome g alone; *nkeys = the keys counted.  occ, priv and nkeys may be NULL.  The reference's `mash triangle` step
+ * (workflow/Snakefile:124-149) ESTIMATES each pair's Jaccard index from a sketch at mash's k = 21; beside it this is the
+ * exact index pairs[a][b] / (pairs[a][a] + pairs[b][b] - pairs[a][b]) at the table's own k, with the core / shell / private
+ * breakdown the sketch cannot give.  One restriction: the result describes the k-mers THE TABLE WAS BUILT FROM — a table
+ * that was fed the anchor genomes' k-mers only answers for those k-mers, not for the genomes.  1 to 512 genomes
+ * (PG_E_INVALID beyond); runs on the context's stream behind the table's last writer; synchronises. */
+int pg_table_pair_counts(pg_table *tbl, uint64_t *pairs, uint64_t *occ, uint64_t *priv, uint64_t *nkeys);
 /* Distinct canonical k-mers of a set of inputs before a table exists (HyperLogLog, 2^16 registers,
  * standard error 0.4 %): sizes pg_table_create's expected_keys, so the table is neither re-hashed
  * while it grows nor held twice in HBM.  Replaces nothing in the reference (KMC is only given a memory cap:

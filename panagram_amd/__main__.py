@@ -6,7 +6,10 @@ cpp/run_anchor (`run_anchor <ngenomes> <root> [<name> <fasta>]...`), and what th
 `find <index_dir> <genome> [chrom] [start] [end] [step] --have A,B --lack C,D` lists the runs of positions whose k-mers the
 `--have` genomes hold and the `--lack` genomes do not (the query scripts/query_index.py's "custom" branch sketches);
 `patterns <index_dir> <genome> [chrom] [start] [end] [step] [--genomes A,B,...]` lists the presence/absence patterns that occur in
-a region's rows with the rows each holds (query_bitmap + value_counts(), reduced on the GPU)."""
+a region's rows with the rows each holds (query_bitmap + value_counts(), reduced on the GPU);
+`pangenome <index_dir> [--matrix FILE] [--occupancy FILE]` prints every sample's distinct, private, core and shell k-mers, counted
+on the GPU in one pass over the table of all samples' k-mers (`index --kmer_stats` writes the matrix and the occupancy table with
+the index; `dist <index_dir> --exact` writes genome_dist.tsv from the exact Jaccard index at the index's k)."""
 import argparse
 import os
 import sys
@@ -33,9 +36,19 @@ def main(argv=None):
     ix.add_argument("--genome_dist", action="store_true", help="also write genome_dist.tsv (MinHash distances, for panagram view)")
     ix.add_argument("--annotate", action="store_true", help="also write the gene / annotation tracks of annotated anchor genomes")
     ix.add_argument("--umaps", action="store_true", help="also write chrom_umaps.csv and genome_umap.csv of the anchor genomes")
+    ix.add_argument("--kmer_stats", action="store_true", help="also write kmer_shared.tsv and kmer_occupancy.tsv: the distinct k-mers "
+                    "every pair of samples shares and the k-mers held by n samples, counted on the GPU off the table of all samples")
     ds = sub.add_parser("dist", help="write genome_dist.tsv of an existing index (MinHash sketches on the GPU)")
     ds.add_argument("index_dir")
+    ds.add_argument("--exact", action="store_true", help="the exact Jaccard index of the samples' distinct k-mers at the index's k "
+                    "(counted on the GPU off the k-mer table) in place of the MinHash estimate at k = 21; the p-value column reads 0")
     ds.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    pg = sub.add_parser("pangenome", help="distinct, private, core and shell k-mers of every sample of an index, counted on the GPU "
+                                          "in one pass over the k-mer table: tab-separated name kmers private core shell")
+    pg.add_argument("index_dir")
+    pg.add_argument("--matrix", metavar="FILE", default=None, help="also write the shared distinct k-mers of every pair as a tab-separated table")
+    pg.add_argument("--occupancy", metavar="FILE", default=None, help="also write n kmers: the distinct k-mers held by n of the samples")
+    pg.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     an = sub.add_parser("annotate", help="(Re-)annotate an existing anchored genome using a GFF file")
     an.add_argument("index_dir")
     an.add_argument("genome")
@@ -103,16 +116,42 @@ def main(argv=None):
         from .index import KMC, Index
         idx = Index(a.input, prefix=a.prefix, k=a.k, cores=a.cores, prepare=a.prepare,
                     anchor_genomes=a.anchor_genomes, device=a.device, export_kmc=a.export_kmc,
-                    kmc=KMC(use_existing=a.use_existing), genome_dist=a.genome_dist, annotate=a.annotate, umaps=a.umaps)
+                    kmc=KMC(use_existing=a.use_existing), genome_dist=a.genome_dist, annotate=a.annotate, umaps=a.umaps,
+                    kmer_stats=a.kmer_stats)
         idx.run()
         return 0
     if a.cmd == "dist":
         from .index import Index
         idx = Index(a.index_dir, mode="r", device=a.device)
         try:
-            print("Wrote", idx.write_genome_dist())
+            print("Wrote", idx.write_genome_dist(exact=True) if a.exact else idx.write_genome_dist())
         finally:
             idx.close()
+        return 0
+    if a.cmd == "pangenome":
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"pangenome: {a.index_dir!r} is not an index directory")
+        from . import pangenome
+        from .index import Index
+        try:
+            idx = Index(a.index_dir, mode="r", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"pangenome: {e}")
+        try:
+            import pandas as pd
+            for n in idx.genome_names:  # (the table is built from the samples' sequences)
+                fa = idx[n].fasta
+                if pd.isna(fa) or not os.path.isfile(str(fa)):
+                    ap.error(f"pangenome: sample {n!r} of {a.index_dir} has no sequence file to count k-mers of ({fa})")
+            stats = idx._kmer_stats_raw()
+            shared, genomes = pangenome.frames(stats, idx.genome_names)
+        finally:
+            idx.close()
+        if a.matrix:
+            shared.to_csv(a.matrix, sep="\t", index_label="name")
+        if a.occupancy:
+            pangenome.occupancy_frame(stats).to_csv(a.occupancy, sep="\t", index=False)
+        genomes.to_csv(sys.stdout, sep="\t", index_label="name")
         return 0
     if a.cmd == "annotate":
         from .index import Index

@@ -212,6 +212,12 @@ constexpr uint32_t PAIRS_MAX_GENOMES = 512;
 hipError_t launch_pair_counts(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, uint32_t nwin,
                               uint32_t pieces, const uint64_t *base, const uint64_t *starts, const uint64_t *ends,
                               unsigned long long *pairs);
+// shared distinct k-mer counts of a table (pg_tablestats.hip): one pass over every slot of t, whatever its layout.  pairs
+// ([N][N]: k-mers held by both genomes, the entries on and above the diagonal — the caller mirrors them), occ ([N + 1]: k-mers
+// held by exactly n genomes), priv ([N]: k-mers of genome g alone) and nkeys (the slots counted) are zeroed by the caller and
+// accumulated into.  1 <= N <= PAIRS_MAX_GENOMES, N <= 32 t.W.
+hipError_t launch_table_pair_counts(hipStream_t st, const SubTable &t, uint32_t ngenomes, unsigned long long *pairs,
+                                    unsigned long long *occ, unsigned long long *priv, unsigned long long *nkeys);
 // pattern runs (pg_find.hip): a sampled row matches iff popcount(row & have) >= min_have and popcount(row & lack) <= max_lack
 // (have / lack: ceil(N / 32) words each, bits at and past N zero).  Window i = sampled rows [starts[i], ends[i]) of the rows at
 // rows + base[i], as the bins above; chunk c = {window, first sampled row}: the FIND_CHUNK sampled rows from there, cut at its

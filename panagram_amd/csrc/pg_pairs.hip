@@ -26,26 +26,9 @@
 // PAIRS_MAX_GENOMES (k_pair_counts<0>), word by word.
 #include "pg_kernels.h"
 #include "pg_rowread.h"
+#include "pg_pairblocks.h"
 
 namespace pg {
-
-constexpr uint32_t PAIRS_TILE = 256;  // sampled rows per tile: one 64-row word per wave
-constexpr uint32_t PAIRS_ROUNDS = 3;  // 4 x 4 blocks per thread and slice
-
-// word d of the wave's 64 rows: the column word of bit b goes to lane b (d even) / 32 + b (d odd)
-__device__ __forceinline__ uint64_t pairs_ballot_word(uint32_t w, uint32_t d, uint32_t N, uint32_t lane, uint64_t mine) {
-    if (__ballot(w != 0) == 0) return mine;  // (wave-uniform: no bit in these 32 columns)
-    const uint32_t ng = min(32u, N - 32 * d), l0 = 32 * (d & 1);
-    // (unrolled by 8, not 32: the full unroll keeps 32 ballot masks live and spills SGPRs into VGPR lanes)
-#pragma unroll 8
-    for (uint32_t b = 0; b < 32; ++b) {
-        if (b < ng) {
-            const uint64_t m = __ballot((w >> b) & 1u);
-            mine = lane == l0 + b ? m : mine;
-        }
-    }
-    return mine;
-}
 
 template <uint32_t MAXW>
 __global__ __launch_bounds__(256) void k_pair_counts(uint32_t N, const uint8_t *__restrict__ rows, uint32_t stride,
@@ -54,25 +37,10 @@ __global__ __launch_bounds__(256) void k_pair_counts(uint32_t N, const uint8_t *
     extern __shared__ __align__(16) uint64_t psm[];  // [2 buffers][4 waves][NC] column words
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t nbytes = (N + 7) / 8, ndw = (N + 31) / 32;
-    const uint32_t NC = (N + 63) & ~63u, NB = (N + 3) / 4, nblk = NB * (NB + 1) / 2;
+    const uint32_t NC = (N + 63) & ~63u;
     // this thread's blocks: number t of the blocks on and above the diagonal, row by row -> (block row, block column)
-    uint32_t ca[PAIRS_ROUNDS], cb[PAIRS_ROUNDS];
-    bool have[PAIRS_ROUNDS];
-    uint32_t acc[PAIRS_ROUNDS][16];
-#pragma unroll
-    for (uint32_t r = 0; r < PAIRS_ROUNDS; ++r) {
-        const uint32_t t = (blockIdx.z * PAIRS_ROUNDS + r) * 256 + tid;
-        have[r] = t < nblk;
-        uint32_t a = 0, rem = have[r] ? t : 0;
-        while (rem >= NB - a) {
-            rem -= NB - a;
-            ++a;
-        }
-        ca[r] = 4 * a;
-        cb[r] = 4 * (a + rem);
-#pragma unroll
-        for (uint32_t i = 0; i < 16; ++i) acc[r][i] = 0;
-    }
+    PairBlocks<> pb;  // (pg_pairblocks.h, shared with k_table_pair_counts)
+    pb.init(tid, blockIdx.z, N);
     const uint8_t *crow = rows + base[blockIdx.x];
     const uint64_t s = starts[blockIdx.x], e = ends[blockIdx.x];
     uint32_t buf = 0;
@@ -107,34 +75,14 @@ __global__ __launch_bounds__(256) void k_pair_counts(uint32_t N, const uint8_t *
         __syncthreads();
 #pragma unroll
         for (uint32_t r = 0; r < PAIRS_ROUNDS; ++r) {
-            if (!have[r]) continue;
+            if (!pb.have[r]) continue;
 #pragma unroll
-            for (uint32_t wv = 0; wv < 4; ++wv) {
-                const ulonglong2 *pa = reinterpret_cast<const ulonglong2 *>(tile + wv * NC + ca[r]);
-                const ulonglong2 *pb = reinterpret_cast<const ulonglong2 *>(tile + wv * NC + cb[r]);
-                const ulonglong2 a01 = pa[0], a23 = pa[1], b01 = pb[0], b23 = pb[1];
-                const uint64_t A[4] = {a01.x, a01.y, a23.x, a23.y}, B[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-                for (uint32_t i = 0; i < 4; ++i)
-#pragma unroll
-                    for (uint32_t k = 0; k < 4; ++k) acc[r][4 * i + k] += (uint32_t)__popcll(A[i] & B[k]);
-            }
+            for (uint32_t wv = 0; wv < 4; ++wv) pb.add(r, tile + wv * NC);
         }
         // (no second barrier: the next tile goes to the other buffer, and this one is written again only behind the next
         // tile's barrier, which every wave passes after these reads)
     }
-    unsigned long long *out = pairs_out + (uint64_t)blockIdx.x * N * N;
-#pragma unroll
-    for (uint32_t r = 0; r < PAIRS_ROUNDS; ++r) {
-        if (!have[r]) continue;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i)
-#pragma unroll
-            for (uint32_t k = 0; k < 4; ++k) {
-                const uint32_t a = ca[r] + i, b = cb[r] + k, c = acc[r][4 * i + k];
-                if (a < N && b < N && c) atomicAdd(&out[(uint64_t)a * N + b], (unsigned long long)c);
-            }
-    }
+    pb.flush(pairs_out + (uint64_t)blockIdx.x * N * N, N);
 }
 
 hipError_t launch_pair_counts(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, uint32_t nwin,

@@ -585,6 +585,18 @@ class PanTable(_Owner):
         check(self._lib.pg_table_stats(self._h, *[C.byref(x) for x in v]))
         return dict(nkeys=v[0].value, nslots=v[1].value, nbuckets=v[2].value, bytes=v[3].value)
 
+    def kmer_stats(self) -> dict:
+        """shared distinct k-mer counts of the k-mers the table was built from, one pass over its slots on the GPU
+        (pg_table_pair_counts): ``pairs`` (N x N int64, symmetric: k-mers held by both genomes, the diagonal a genome's
+        distinct k-mers), ``occupancy`` (N + 1: k-mers held by exactly n genomes), ``private`` (N: k-mers of one genome
+        alone) and ``nkeys``"""
+        n = self.ngenomes
+        pairs = np.zeros((n, n), np.uint64)
+        occ, priv, nkeys = np.zeros(n + 1, np.uint64), np.zeros(n, np.uint64), C.c_uint64()
+        check(self._lib.pg_table_pair_counts(self._h, _ptr(pairs), _ptr(occ), _ptr(priv), C.byref(nkeys)))
+        return dict(pairs=pairs.astype(np.int64), occupancy=occ.astype(np.int64), private=priv.astype(np.int64),
+                    nkeys=int(nkeys.value))
+
     def rehash(self, keys_per_bucket: float) -> None:
         check(self._lib.pg_table_rehash(self._h, keys_per_bucket))
 

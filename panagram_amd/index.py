@@ -340,6 +340,38 @@ class RegionTree:
                    newick=linkage_newick(Z, names))
 
 
+class _KmerStatsSwitch:
+    """What ``Index.kmer_stats`` reads as: the switch ``Index(kmer_stats=True)`` set (its truth value) and, called, the
+    pan-genome's k-mer statistics (``Index._kmer_stats_frames``) — one name for both, as the command line has one."""
+
+    def __init__(self, index, on: bool):
+        self._index, self._on = index, bool(on)
+
+    def __bool__(self):
+        return self._on
+
+    def __call__(self):
+        return self._index._kmer_stats_frames()
+
+    def __deepcopy__(self, memo):  # (dataclasses.asdict: the switch alone)
+        return self._on
+
+    def __repr__(self):
+        return repr(self._on)
+
+
+class _KmerStatsField:
+    """the dataclass field behind ``Index.kmer_stats``: stores the switch, reads as a _KmerStatsSwitch"""
+
+    def __get__(self, obj, owner=None):
+        if obj is None:
+            return False  # (the field's default)
+        return _KmerStatsSwitch(obj, obj.__dict__.get("_kmer_stats_on", False))
+
+    def __set__(self, obj, value):
+        obj.__dict__["_kmer_stats_on"] = bool(value)
+
+
 @dataclasses.dataclass
 class Index:
     """Anchor k-mer bitvectors to reference FASTA files to create the pan-kmer bitmap."""
@@ -383,9 +415,12 @@ class Index:
     annotate: bool = False
     # run Genome.write_umaps() for every anchor genome this process completes (off by default: the default tree stays as it was)
     umaps: bool = False
+    # build the table from every sample's k-mers and write kmer_shared.tsv and kmer_occupancy.tsv after the table build
+    # (write_kmer_stats; off by default: the default tree stays as it was).  Called, ``kmer_stats()`` returns the frames.
+    kmer_stats: bool = _KmerStatsField()
 
     _EXTRA = ("device", "export_kmc", "rank", "world", "shard", "genome_blocks", "filtered_table", "genome_dist", "annotate",
-              "umaps")
+              "umaps", "kmer_stats")
     # keys of config.yaml that describe one invocation, not the index: not taken over when a directory is re-opened
     # (`prepare` is written for schema compatibility, but a later `index <dir>` run must not stop at "Prepared")
     _NOT_IN_CONFIG = ("input", "mode", "prefix", "prepare")
@@ -474,6 +509,14 @@ class Index:
     @property
     def genome_dist_fname(self):
         return os.path.join(self.prefix, "genome_dist.tsv")
+
+    @property
+    def kmer_shared_fname(self):
+        return os.path.join(self.prefix, "kmer_shared.tsv")
+
+    @property
+    def kmer_occupancy_fname(self):
+        return os.path.join(self.prefix, "kmer_occupancy.tsv")
 
     def get_subdir(self, name):
         return os.path.join(self.prefix, name)
@@ -679,7 +722,7 @@ class Index:
         """distinct k-mers of the largest table a rank holds in the replicated mode: the union of the genomes it anchors
         (``build_table``'s filtered build) — or of all samples where that build does not apply.  The same answer in
         every process."""
-        if not (self.filtered_table and not self.export_kmc and all(i[3] <= 1 for i in inputs)):
+        if not (self.filtered_table and not self.export_kmc and not self.kmer_stats and all(i[3] <= 1 for i in inputs)):
             return self._expected_keys(inputs)
         if self.world > 1 and os.environ.get("PG_PARTITION", "pieces") != "genomes":
             # pieces of homology classes: a rank's table is built from its 1 / world of the anchored sequence
@@ -746,10 +789,11 @@ class Index:
             # (pg_table_update_seqset) — the rows are the ones the table of all genomes gives, the table is as small as
             # the anchored sequence's own k-mer set (a rank of a multi-GPU run, or a pangenome in which only some genomes
             # are anchors).  Not when the merged databases are to be exported, nor with read-set samples (their -ci2
-            # count tables merge through the inserting path).
+            # count tables merge through the inserting path), nor when the pan-genome's k-mer statistics are wanted (kmer_stats:
+            # they describe the k-mers the table was built from).
             first = [i for i in inputs if i[0] in keep]
             rest = [i for i in inputs if i[0] not in keep]
-            can_filter = self.filtered_table and not self.export_kmc and all(i[3] <= 1 for i in inputs)
+            can_filter = self.filtered_table and not self.export_kmc and not self.kmer_stats and all(i[3] <= 1 for i in inputs)
             if insert_sets is not None and can_filter:
                 sketch = engine.KmerSketch(self.context, self.k)
                 for ss in insert_sets.values():
@@ -805,7 +849,7 @@ class Index:
         minhash.add(ss, distinct)
         return minhash.result()
 
-    def write_genome_dist(self) -> str:
+    def write_genome_dist(self, exact: bool = False) -> str:
         """Write ``genome_dist.tsv`` — what the reference's workflow makes with ``mash sketch -r -s 10000`` and ``mash
         triangle -E`` (workflow/Snakefile:124-149) and ``panagram view`` reads at start-up (figs.py:50-59): one line per
         pair of samples in sample order, ``name_a, name_b, distance, p-value, common/denom``, numbers as %.6g.
@@ -815,8 +859,22 @@ class Index:
         are read, sketched and freed one at a time.  Distances: mash's merge and formula (engine.minhash_distances).  The
         p-value uses each sample's ACGT bases where mash under ``-r`` estimates a genome size, so that column can differ
         from mash's; the viewer reads only the names and the distance.  Byte-for-byte agreement with mash 2.3 is the intent,
-        not a tested claim.  Returns the file's path."""
+        not a tested claim.  Returns the file's path.
+
+        ``exact``: the same file from the pan table's shared distinct k-mer counts (``kmer_stats``) in place of sketches —
+        same five columns, same pair order, numbers as %.6g: the distance is mash's formula on the EXACT Jaccard index at
+        this index's k (not an estimate at k = 21), the p-value column the literal ``0`` (nothing was sampled), the last
+        column ``shared/union`` in distinct k-mers.  The default writes what it always wrote."""
         names = [str(n) for n in self.genome_names]
+        if exact:
+            from . import pangenome
+            lines = pangenome.genome_dist_lines(names, self._kmer_stats_raw()["pairs"], self.k)
+
+            def write_exact(tmp):
+                with open(tmp, "w") as f:
+                    f.write("".join(lines))
+            self._write_atomically(self.genome_dist_fname, write_exact)
+            return self.genome_dist_fname
         todo = [n for n in names if n not in self._minhash]
         if todo:
             minhash = engine.MinHashSketch(self.context)
@@ -856,6 +914,42 @@ class Index:
                 f.write("".join(lines))
         self._write_atomically(self.genome_dist_fname, write)
         return self.genome_dist_fname
+
+    # ---- the pan-genome's own k-mer statistics (pangenome.py), off the pan table ----
+    def _full_table(self) -> engine.PanTable:
+        """the table of EVERY sample's k-mers: the cached one when it is that, else built now with filtering off and cached"""
+        if self._table is not None:
+            scope = self._table_scope
+            if scope != "all":
+                raise RuntimeError("the cached table was built for " + ("this process's pieces" if scope == "pieces" else f"the anchors {sorted(scope)}") +
+                                   " only; close() the index before building a table for other anchors")
+            return self._table
+        filtered, self.filtered_table = self.filtered_table, False
+        try:
+            return self.build_table()
+        finally:
+            self.filtered_table = filtered
+
+    def _kmer_stats_raw(self) -> dict:
+        return self._full_table().kmer_stats()
+
+    def _kmer_stats_frames(self):
+        """``kmer_stats()``: (shared, genomes) — the shared distinct k-mers of every pair of samples as a named matrix, and per
+        sample its distinct, private, core and shell k-mers (pangenome.frames) — counted on the GPU in one pass over the
+        table of all samples' k-mers.  A cached table that was built from some anchors' k-mers only cannot answer: RuntimeError."""
+        from . import pangenome
+        return pangenome.frames(self._kmer_stats_raw(), self.genome_names)
+
+    def write_kmer_stats(self) -> Tuple[str, str]:
+        """Write ``kmer_shared.tsv`` (the shared-k-mer matrix: a header row, a ``name`` column) and ``kmer_occupancy.tsv``
+        (columns ``n``, ``kmers``: distinct k-mers held by exactly n samples) into the index directory; returns their paths."""
+        from . import pangenome
+        stats = self._kmer_stats_raw()
+        shared, _ = pangenome.frames(stats, self.genome_names)
+        occ = pangenome.occupancy_frame(stats)
+        self._write_atomically(self.kmer_shared_fname, lambda tmp: shared.to_csv(tmp, sep="\t", index_label="name"))
+        self._write_atomically(self.kmer_occupancy_fname, lambda tmp: occ.to_csv(tmp, sep="\t", index=False))
+        return self.kmer_shared_fname, self.kmer_occupancy_fname
 
     def seqset_for(self, name: str) -> engine.SeqSet:
         """The genome's FASTA, parsed and 2-bit packed in HBM (0.375 byte per base), cached."""
@@ -973,6 +1067,10 @@ class Index:
         stream each genome's rows out of HBM into its BGZF files while the next batch is anchored.
         A pangenome whose table does not fit one GPU goes through the genome-sharded mode instead
         (``plan_sharding``)."""
+        if self.kmer_stats and self.world > 1:
+            # (a rank's table holds its pieces' or its genome block's k-mers, never the pan-genome's)
+            raise ValueError("kmer_stats needs the one table of all samples' k-mers: it is single-GPU, and this run has "
+                             f"{self.world} processes")
         print("Wrote config.yaml and samples.tsv")
         if self.prepare:
             print("Prepared. Run 'python -m panagram_amd index <dir>' to build the index")
@@ -1025,6 +1123,8 @@ class Index:
         mode, nblocks = self.plan_sharding()
         self._check_plan_agreed((mode, nblocks, self._block_keys_per_line if mode == "genome" else 0.0))
         if mode == "genome":
+            if self.kmer_stats:  # (a genome block's table holds its block's bits only)
+                raise ValueError("kmer_stats needs the one table of all samples' k-mers, and this pan-genome is indexed in genome blocks")
             from .distributed import run_genome_sharded
             logger.info("genome-sharded mode: %d genome blocks over %d GPU(s)%s", nblocks, self.world,
                         f", block tables at {self._block_keys_per_line:g} keys per line" if self._block_keys_per_line else "")
@@ -1047,6 +1147,8 @@ class Index:
             self.close()
             return
         tbl = self.build_table(keep=mine)
+        if self.kmer_stats:
+            self.write_kmer_stats()
         nb = (self.ngenomes + 7) // 8
         # two batches of rows are resident at a time (one being written, one being anchored), next to the
         # table: with a table that fills most of the HBM the batches shrink to what is left

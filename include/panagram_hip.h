@@ -449,6 +449,36 @@ int pg_result_pattern_counts(pg_result *r, int step, uint32_t stride, uint32_t n
                              const uint64_t *starts, const uint64_t *ends, const uint32_t *select_words,
                              uint64_t cap, uint64_t *keys_out, uint64_t *counts_out,
                              uint64_t *ndistinct_out, uint64_t *rows_out, int *exceeded_out);
+/* absence runs: where, and how, does each genome differ from the anchor (Index.query_bitmap's frame with a per-column
+ * np.diff of the padded absence vector, every column of it, none of it read back)?  Row r of bitmap.1 is the k-mer at anchor
+ * bases [r, r + k): one substituted base in genome g clears k consecutive rows of g's column, an insertion k - 1, a deletion of
+ * d bases k - 1 + d, so the LENGTHS of the runs of absent rows of a column are a variant signal.
+ * Windows as in pg_result_find_runs: window i = SAMPLED rows [starts[i], ends[i]) of contig contig[i]'s bitmap.<step> rows in HBM,
+ * sampled row j being row j * stride; no row outside a window is read.  select_words: the genomes to follow, as ceil(ngenomes /
+ * 32) words (bit g = bit g % 32 of word g / 32; bits at and past ngenomes are ignored, in the words and in a row's last byte);
+ * NULL: all of them.  Everything below is zero for a genome outside the selection.
+ * A run of genome g is a maximal range of consecutive sampled rows of a window without g's bit.  It is CLOSED when a present
+ * row of the window bounds it on both sides; the (at most two) runs that touch the window's edges are open.
+ *   hist_out[(i*ngenomes + g)*(maxlen+1) + L]  closed runs of L rows; bin maxlen holds L >= maxlen, bin 0 stays 0
+ *   absent_out[i*ngenomes + g]                 absent sampled rows
+ *   edge_out[(i*ngenomes + g)*2 + {0, 1}]      absent rows from the window's first row on / up to its last row: the open
+ *                                              runs; both the window's rows when no row of it is present
+ *   nruns_out[i]                               closed runs selected for emission: min_len <= L, and L <= max_len unless
+ *                                              max_len is 0; *total_out = their sum
+ * Capacity, as pg_result_find_runs: the counts above are always computed.  If *total_out > cap, or cap == 0, the call returns
+ * PG_OK and writes nothing to run_genome / run_start / run_rows (which may then be NULL when cap == 0): call again with arrays
+ * of *total_out entries.  Otherwise their first *total_out entries are the selected runs — genome, first sampled row of the
+ * contig, rows — sorted by (window, genome, first row), window i's nruns_out[i] runs behind those of the windows before it,
+ * and the same on every call.
+ * PG_E_INVALID before anything is launched: fewer than 1 or more than 512 genomes, maxlen outside 1..4096, min_len < 1, a sampled
+ * row outside its contig.  One launch of k_absence_runs over chunks of 4096 sampled rows (every row read once, all columns
+ * followed together; integer atomics), the chunks' edges stitched on the host; synchronises. */
+int pg_result_absence_runs(pg_result *r, int step, uint32_t stride, uint32_t nwin, const uint32_t *contig,
+                           const uint64_t *starts, const uint64_t *ends, const uint32_t *select_words,
+                           uint32_t maxlen, uint32_t min_len, uint32_t max_len,
+                           uint64_t cap, uint32_t *run_genome, uint32_t *run_start, uint32_t *run_rows,
+                           uint64_t *hist_out, uint64_t *absent_out, uint64_t *edge_out,
+                           uint64_t *nruns_out, uint64_t *total_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

@@ -7,6 +7,8 @@ cpp/run_anchor (`run_anchor <ngenomes> <root> [<name> <fasta>]...`), and what th
 `--have` genomes hold and the `--lack` genomes do not (the query scripts/query_index.py's "custom" branch sketches);
 `patterns <index_dir> <genome> [chrom] [start] [end] [step] [--genomes A,B,...]` lists the presence/absence patterns that occur in
 a region's rows with the rows each holds (query_bitmap + value_counts(), reduced on the GPU);
+`gaps <index_dir> <genome> [chrom] [start] [end] [--genomes A,B,...]` lists, per genome, the runs of positions whose k-mers it lacks
+with the kind of difference their length suggests (query_bitmap + a per-column np.diff, reduced on the GPU);
 `pangenome <index_dir> [--matrix FILE] [--occupancy FILE]` prints every sample's distinct, private, core and shell k-mers, counted
 on the GPU in one pass over the table of all samples' k-mers (`index --kmer_stats` writes the matrix and the occupancy table with
 the index; `dist <index_dir> --exact` writes genome_dist.tsv from the exact Jaccard index at the index's k)."""
@@ -100,6 +102,23 @@ def main(argv=None):
     pt.add_argument("--whole", action="store_true", help="the whole genome in place of a chromosome")
     pt.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     pt.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    gp = sub.add_parser("gaps", help="per genome, the runs of positions whose k-mers it lacks — a substitution clears k rows, an "
+                                     "insertion k - 1, a deletion of d bases k - 1 + d — counted in the bitmap rows on the GPU: "
+                                     "tab-separated chrom start end genome rows class site")
+    gp.add_argument("index_dir")
+    gp.add_argument("genome")
+    gp.add_argument("chrom", nargs="?", default=None)
+    gp.add_argument("start", nargs="?", type=int, default=None)
+    gp.add_argument("end", nargs="?", type=int, default=None)
+    gp.add_argument("--genomes", default="", metavar="A,B", help="the genomes to follow (default: all of them)")
+    gp.add_argument("--min-len", type=int, default=None, metavar="N", help="drop runs of fewer than N rows (default: k - 1)")
+    gp.add_argument("--max-len", type=int, default=0, metavar="N", help="drop runs of more than N rows (default 0: none)")
+    gp.add_argument("--maxlen", type=int, default=None, metavar="N", help="the spectrum's last bin: runs of N rows and more (default: 4 k)")
+    gp.add_argument("--spectrum", metavar="FILE", default=None, help="also write genome rows runs: the closed runs of every length")
+    gp.add_argument("--summary", metavar="FILE", default=None, help="also write one line per genome: rows, absent rows, runs by class")
+    gp.add_argument("--whole", action="store_true", help="the whole genome in place of a chromosome")
+    gp.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    gp.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -199,6 +218,35 @@ def main(argv=None):
                 ap.error(f"find: {e}")
         finally:
             idx.close()
+        out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
+        return 0
+    if a.cmd == "gaps":
+        if a.whole == (a.chrom is not None):
+            ap.error("gaps: give a chromosome or --whole (and no region with --whole)")
+        from .index import Index
+        chosen = [g for g in a.genomes.split(",") if g]
+        idx = Index(a.index_dir, mode="r", device=a.device)
+        try:
+            if a.genome not in idx.genomes or not idx[a.genome].anchored:
+                ap.error(f"gaps: {a.genome!r} is not an anchor genome of {a.index_dir}")
+            for g in chosen:
+                if g not in idx.genome_names:
+                    ap.error(f"gaps: unknown genome {g!r} (the index has {', '.join(idx.genome_names)})")
+            k = int(idx.k)
+            try:
+                out, spectrum, summary = idx[a.genome].absence_tables(chosen or None, a.chrom, a.start, a.end, 1,
+                                                                      k - 1 if a.min_len is None else a.min_len, a.max_len,
+                                                                      4 * k if a.maxlen is None else a.maxlen)
+            except (ValueError, KeyError) as e:
+                ap.error(f"gaps: {e}")
+            if a.summary and summary is None:
+                ap.error(f"gaps: --summary needs a spectrum that reaches past k: --maxlen above {k}")
+        finally:
+            idx.close()
+        if a.spectrum:
+            spectrum.to_csv(a.spectrum, sep="\t", index=False)
+        if a.summary:
+            summary.to_csv(a.summary, sep="\t", index=False)
         out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
         return 0
     if a.cmd == "patterns":

@@ -126,6 +126,8 @@ PROTOTYPES = {
                                       C.c_uint64, _vp, _vp, _vp, _vp, _u64p]),
     "pg_result_pattern_counts": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _u64p,
                                            _u64p, C.POINTER(C.c_int)]),
+    "pg_result_absence_runs": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64p]),
     "pg_knn_rows": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "pg_result_write_bgzf": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "pg_bgzf_inflate": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),

@@ -244,6 +244,22 @@ hipError_t launch_pattern_counts(hipStream_t st, uint32_t ngenomes, const uint8_
                                  const uint64_t *ends, const uint2 *chunks, uint32_t nchunks, const uint32_t *select,
                                  uint32_t nselected, bool low_columns, uint64_t cap, unsigned long long *keys,
                                  unsigned long long *counts, uint64_t slots, unsigned long long *ctr);
+// absence runs (pg_gaps.hip): per column g of `select` (ceil(N / 32) words, bits at and past N zero) the maximal runs of sampled
+// rows WITHOUT bit g.  Windows (base, ends) and chunks as above, GAPS_CHUNK sampled rows each; one block per chunk, no block
+// waits for another.  A run with a present row on both sides inside its chunk is closed there: hist ([nwin][N][maxlen + 1],
+// zeroed by the caller) gets 1 at min(rows, maxlen); when min_len <= rows and (max_len == 0 or rows <= max_len) nsel[window]
+// gets 1 and, with cap != 0, one record {window, g, first sampled row, rows} goes to recs at the cursor while that is below cap
+// (the cursor counts on; a chunk takes it once for the records it collected in LDS).
+// absent ([nwin][N], zeroed) gets the chunk's absent rows; edges[chunk * N + g] = {head, tail}: the absent rows from the chunk's
+// first row on / up to its last row, both the chunk's rows when no row is present (the caller stitches them: pg_gaps_host.h).
+// Nothing is written for a column outside `select`.  1 <= N <= GAPS_MAX_GENOMES, 1 <= maxlen <= GAPS_MAX_MAXLEN.
+constexpr uint32_t GAPS_CHUNK = 4096;  // sampled rows per chunk, a multiple of 256
+constexpr uint32_t GAPS_MAX_GENOMES = 512, GAPS_MAX_MAXLEN = 4096;
+constexpr uint32_t GAPS_LDS_BINS = 6144;  // N * (maxlen + 1) up to here: the chunk's spectrum is kept in LDS (24 KiB)
+hipError_t launch_absence_runs(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, uint32_t stride, const uint64_t *base,
+                               const uint64_t *ends, const uint2 *chunks, uint32_t nchunks, const uint32_t *select,
+                               uint32_t maxlen, uint32_t min_len, uint32_t max_len, uint32_t *hist, unsigned long long *absent,
+                               uint2 *edges, unsigned long long *nsel, unsigned long long *cursor, uint64_t cap, uint4 *recs);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

@@ -61,6 +61,12 @@ PATTERN_CHUNK = 8192
 PATTERN_FIRST_CAP = 1 << 16
 PATTERN_MAX_CAP = 1 << 26
 
+# absence runs (pg_gaps.hip).  GAPS_CHUNK: sampled rows per workgroup — pg_kernels.h's constant, restated for the tests that aim at
+# chunk edges (tests/test_gaps_cpu.py holds the two together); GAPS_FIRST_CAP: runs AnchorResult.absence_runs makes room for in
+# its first call
+GAPS_CHUNK = 4096
+GAPS_FIRST_CAP = 1 << 16
+
 
 def tile_positions() -> int:
     """k-mer positions per tile (launch unit; a bit-column block holds tile_positions() // 8 bytes per tile and genome:
@@ -977,6 +983,49 @@ class AnchorResult:
             if cap >= PATTERN_MAX_CAP:
                 raise ValueError(f"more than {PATTERN_MAX_CAP} distinct patterns (the cap of pattern_counts): select fewer genomes")
             cap = min(cap * 16, PATTERN_MAX_CAP)
+
+    def _gaps(self, contigs, starts, ends, select_words, maxlen, min_len, max_len, step, stride, cap):
+        """one pg_result_absence_runs call -> (total, hist, absent, edges, nruns, genome / start / rows of the selected runs;
+        the last three None unless 0 < total <= cap)"""
+        contigs, starts, ends = _windows(contigs, starts, ends, "window")
+        n, N = len(starts), self.ngenomes
+        for name, v in (("maxlen", maxlen), ("min_len", min_len), ("max_len", max_len)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} must be a 32-bit count, got {v}")
+        sel = None if select_words is None else _mask_words(N, select_words)  # (no selection is a null pointer: all)
+        hist = np.zeros((n, N, int(maxlen) + 1), np.uint64)
+        absent, edges, nruns = np.zeros((n, N), np.uint64), np.zeros((n, N, 2), np.uint64), np.zeros(n, np.uint64)
+        rg, rs, rr = (np.zeros(cap, np.uint32) for _ in range(3))
+        total = C.c_uint64(0)
+        check(self._lib.pg_result_absence_runs(self._h, int(step), int(stride), n, _ptr(contigs), _ptr(starts), _ptr(ends), _ptr(sel),
+                                               int(maxlen), int(min_len), int(max_len), int(cap), _ptr(rg) if cap else None,
+                                               _ptr(rs) if cap else None, _ptr(rr) if cap else None, _ptr(hist), _ptr(absent),
+                                               _ptr(edges), _ptr(nruns), C.byref(total)))
+        t = total.value
+        fits = 0 < t <= cap
+        return (t, hist, absent, edges, nruns) + ((rg[:t], rs[:t], rr[:t]) if fits else (None, None, None))
+
+    def absence_runs(self, contigs, starts, ends, select_words=None, maxlen: int = 84, min_len: int = 1, max_len: int = 0,
+                     step: int = 1, stride: int = 1, emit: bool = True):
+        """(runs [total, 4] int64, hist [nwin, N, maxlen + 1], absent [nwin, N], edges [nwin, N, 2]; the last three uint64):
+        per genome the maximal runs of consecutive sampled rows WITHOUT its bit — window i = sampled rows [starts[i], ends[i])
+        of contig contigs[i]'s bitmap.<step> rows, sampled row j = row j * stride.  A run is closed when a present row of the
+        window bounds it on both sides.  ``hist[i, g, L]`` counts the closed runs of L rows (bin ``maxlen``: L >= maxlen),
+        ``absent[i, g]`` the absent sampled rows, ``edges[i, g]`` the two open runs at the window's edges (both the window's
+        rows when genome g holds none of them).  A row of ``runs`` is (window, genome, first sampled row, rows) of a closed
+        run with min_len <= rows (and rows <= max_len unless that is 0), sorted by (window, genome, first row); with
+        ``emit=False`` no run is written and ``runs`` is empty.  ``select_words``: the genomes to follow as ceil(N / 32) words
+        (None: all); the others' entries are zero.  k_absence_runs: a first call with room for GAPS_FIRST_CAP runs, a second
+        one only when there are more."""
+        args = (contigs, starts, ends, select_words, maxlen, min_len, max_len, step, stride)
+        total, hist, absent, edges, nruns, rg, rs, rr = self._gaps(*args, GAPS_FIRST_CAP if emit else 0)
+        if emit and total > GAPS_FIRST_CAP:
+            total, hist, absent, edges, nruns, rg, rs, rr = self._gaps(*args, total)
+        runs = np.zeros((total if emit else 0, 4), np.int64)
+        if emit and total:
+            runs[:, 0] = np.repeat(np.arange(len(nruns), dtype=np.int64), nruns.astype(np.int64))
+            runs[:, 1], runs[:, 2], runs[:, 3] = rg, rs, rr
+        return runs, hist, absent, edges
 
     def write_bgzf(self, step: int, gz_path: str, gzi_path: Optional[str] = None, level: int = 6,
                    threads: int = 1, first_contig: int = 0, ncontigs: Optional[int] = None) -> None:

@@ -1363,6 +1363,16 @@ class Index:
         holds (``Genome.pattern_spectrum``)"""
         return self.genomes[genome].pattern_spectrum(genomes, chrom, start, end, step, top, min_rows)
 
+    def absence_runs(self, genome, genomes=None, chrom=None, start=None, end=None, step=1, min_len=1, max_len=0) -> pd.DataFrame:
+        """per genome of ``genomes``, the closed runs of rows of ``query_bitmap(genome, chrom, start, end, step)`` that lack its
+        bit, with their candidate class at step 1 (``Genome.absence_runs``)"""
+        return self.genomes[genome].absence_runs(genomes, chrom, start, end, step, min_len, max_len)
+
+    def absence_spectrum(self, genome, genomes=None, chrom=None, start=None, end=None, step=1, maxlen=None) -> pd.DataFrame:
+        """the closed absence runs of every length that each genome of ``genomes`` has in the rows of
+        ``query_bitmap(genome, chrom, start, end, step)`` (``Genome.absence_spectrum``)"""
+        return self.genomes[genome].absence_spectrum(genomes, chrom, start, end, step, maxlen)
+
     def region_tree(self, genome, chrom, start=None, end=None, step=None) -> "RegionTree":
         """The tree of the genomes over a region, as the viewer draws it (view.py:751-764: create_tree) — but from the pair
         counts of EVERY row of the region at ``step`` (default: the low-resolution step), not from a random sample of
@@ -1979,6 +1989,86 @@ class Genome:
         patterns.spectrum_frame([], [], ["-"], top, min_rows)  # (its argument checks, before anything is read)
         keys, counts, selected = self.pattern_counts(genomes, chrom, start, end, step)
         return patterns.spectrum_frame(keys, counts, selected, top, min_rows)
+
+    # ---- GAPS: per genome, the runs of rows it lacks — where and how it differs from this anchor ----
+    def _absence(self, genomes, chrom, start, end, step: int, maxlen: int, min_len: int, max_len: int, emit: bool = True):
+        """([(chrom, sampled rows, runs, hist, absent, edges)], selected names): ``gaps.join_pieces`` of every chromosome of
+        the region.  The rows are inflated into HBM in consecutive pieces of at most ``similarity_budget`` bytes, each reduced
+        by one k_absence_runs call; runs are joined across the pieces' borders on the host."""
+        from . import gaps
+        chroms = self._checked_chroms(step, region=(chrom, start, end))
+        gaps.check_lengths(maxlen, min_len, max_len)
+        words, selected = gaps.select_words(self.index.genome_names, genomes)
+
+        def reduce(res, ns, bstep, stride):
+            runs, hist, absent, edges = res.absence_runs([0], [0], [ns], words, maxlen, min_len, max_len, step=bstep, stride=stride,
+                                                         emit=emit)
+            return runs[:, 1:], hist[0], absent[0], edges[0]
+        out = []
+        for c in chroms:
+            pieces = [(j0, ns) + got for j0, ns, got in self._region_pieces(c, start, end, step, reduce)]
+            out.append((c, sum(ns for _, ns, *_ in pieces)) + gaps.join_pieces(pieces, self.ngenomes, maxlen, min_len, max_len))
+        return out, selected
+
+    def _absence_frames(self, parts, selected, start, step: int, runs: bool = True):
+        """(runs frame, summed hist, summed absent, summed rows of open runs, sampled rows) of ``_absence``'s parts"""
+        from . import gaps
+        names, k = np.array(self.index.genome_names, object), int(self.index.k)
+        label0 = 0 if start is None else int(start)  # (query labels its j-th row start + j * step)
+        frames = []
+        hist = absent = open_rows = 0
+        nrows = 0
+        for c, ns, r, h, a, edges in parts:
+            hist, absent, open_rows, nrows = hist + h, absent + a, open_rows + gaps.open_rows(edges, ns), nrows + ns
+            if not runs:
+                continue
+            r = r[np.lexsort((r[:, 0], r[:, 1]))]  # by position, then genome
+            first = label0 + r[:, 1] * step
+            if step == 1:
+                cls, site, _ = gaps.classify(r[:, 2], k, first)
+            else:
+                cls, site = np.full(len(r), "", object), np.full(len(r), -1, np.int64)
+            frames.append(pd.DataFrame({"chr": np.full(len(r), c, object), "start": first, "end": label0 + (r[:, 1] + r[:, 2] - 1) * step + 1,
+                                        "genome": names[r[:, 0]], "rows": r[:, 2], "class": cls, "site": site}))
+        frame = pd.concat(frames, ignore_index=True) if frames else pd.DataFrame(
+            {"chr": np.zeros(0, object), "start": np.zeros(0, np.int64), "end": np.zeros(0, np.int64), "genome": np.zeros(0, object),
+             "rows": np.zeros(0, np.int64), "class": np.zeros(0, object), "site": np.zeros(0, np.int64)})
+        return frame, hist, absent, open_rows, nrows
+
+    def absence_runs(self, genomes=None, chrom=None, start=None, end=None, step: int = 1, min_len: int = 1,
+                     max_len: int = 0) -> pd.DataFrame:
+        """chr, start, end, genome, rows, class, site: per genome of ``genomes`` (names or columns; default: all), the CLOSED
+        runs of consecutive rows of ``query(chrom, start, end, step)`` that lack the genome's bit — a present row of the region
+        on both sides — with min_len <= rows (and rows <= max_len unless that is 0); the two runs a genome may have at the
+        region's edges are not listed.  ``start`` is the label ``query`` gives the run's first row, ``end`` the label of its
+        last row + 1, as ``find_pattern``'s.  At step 1 ``class`` and ``site`` are ``gaps.classify``'s candidate class and
+        anchor base of the run; at other steps "" and -1.  Sorted by chromosome, start, genome column.  ``chrom=None``: every
+        chromosome, and no run joins two of them.  Every row is read once on the GPU for all genomes (k_absence_runs), in
+        pieces of at most ``similarity_budget`` bytes; a run is never cut at a piece border."""
+        step = int(step)
+        parts, selected = self._absence(genomes, chrom, start, end, step, 1, min_len, max_len)
+        return self._absence_frames(parts, selected, start, step)[0]
+
+    def absence_spectrum(self, genomes=None, chrom=None, start=None, end=None, step: int = 1, maxlen: Optional[int] = None) -> pd.DataFrame:
+        """genome, rows, runs: how many closed runs of each length every genome of ``genomes`` has in the rows of
+        ``query(chrom, start, end, step)``; the bin ``rows`` = ``maxlen`` (default 4 k) holds the runs of maxlen rows and
+        more (``gaps.spectrum_frame``).  No run is written."""
+        return self.absence_tables(genomes, chrom, start, end, step, maxlen=maxlen, runs=False)[1]
+
+    def absence_tables(self, genomes=None, chrom=None, start=None, end=None, step: int = 1, min_len: int = 1, max_len: int = 0,
+                       maxlen: Optional[int] = None, runs: bool = True):
+        """(``absence_runs``' frame, ``absence_spectrum``'s frame, ``gaps.summary_frame`` per genome — None unless step is 1
+        and maxlen > k) from ONE pass over the region's rows; ``runs=False``: no run is written, the first frame is empty"""
+        from . import gaps
+        step, k = int(step), int(self.index.k)
+        maxlen = 4 * k if maxlen is None else int(maxlen)
+        parts, selected = self._absence(genomes, chrom, start, end, step, maxlen, min_len, max_len, emit=runs)
+        frame, hist, absent, open_rows, nrows = self._absence_frames(parts, selected, start, step, runs)
+        names = list(self.index.genome_names)
+        cols = [names.index(g) for g in selected]
+        spectrum = gaps.spectrum_frame(hist[cols], selected)
+        summary = gaps.summary_frame(hist[cols], absent[cols], open_rows[cols], nrows, selected, k) if step == 1 and maxlen > k else None
+        return frame, spectrum, summary
 
     # ---- UMAPS: chrom_umaps.csv and genome_umap.csv (index.py:1100-1167) ----
     @property

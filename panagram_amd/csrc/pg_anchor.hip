@@ -623,18 +623,19 @@ __device__ __forceinline__ void cols_or_position(unsigned long long *cols, uint3
 // for the wide-window tables of up to 16 genomes, where the second staged level costs more than the few lanes it saves
 // (+1.5 % at configs 1-2, tools/ab_one.sh; -1 % at 64 genomes).
 template <bool TWO, int ROWMODE, int SLOTS, int MAXRUN, bool WIDE, int LEVELS, bool INL = false>
-__device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, const uint64_t *sw, const uint64_t *rw, uint32_t *q_line,
-                                            uint32_t *q_step, uint16_t *q_pl, uint32_t *lines_w, uint4 *buf,
+__device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, const uint64_t *sw, const uint64_t *rw, uint32_t *q_grp,
+                                            uint16_t *q_pl, uint32_t *lines_w, uint4 *buf,
                                             uint8_t *tile_rows, uint32_t nbytes, const RowCols rc, int lane) {
-    // a queue entry is (position in the tile, next line to try, step of its sequence): the key is
-    // taken from the tile's sequence words again — 10 bytes of LDS per entry instead of 18 let the
-    // kernel run 32 waves per CU instead of 26
+    // a queue entry is (group, position in the tile): SIX bytes of LDS.  The key is taken from the tile's sequence words
+    // again, and the line and step of the entry's level are functions of the group, the key and the level (line_of_level,
+    // pg_device.h) — worked out here, in the drain's dense batches.  (18 bytes per entry let the kernel run 26 waves per CU,
+    // 10 bytes 32 with a queue of 192 entries; six bytes make that 320 entries in the same LDS.)
     const int k = (int)st.k;
     constexpr int LDS_LINE_U4 = SLOTS + 1;
     constexpr int STAGE_ITERS = (MAXRUN * SLOTS + 63) / 64;
     const uint8_t *chunk_base = st.buckets + (uint32_t)(lane % SLOTS) * 16u;
     const uint32_t lbytes = INL ? st.layout * 64u : st.slots * (WIDE ? 8u : 16u);  // (= 16 * SLOTS = 128, as a run-time scalar: see k_probe)
-    static_assert(LEVELS >= 1, "k_probe's entries (home line, group) are turned into (next line, step) by level 1's staged batches");
+    static_assert(LEVELS >= 1, "k_probe's entries (group, position) get their line and step from level 1's staged batches");
     for (int level = 1; qn > 0; ++level) {
         __syncthreads();
         if (level > LEVELS) {
@@ -643,15 +644,17 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
             for (uint32_t e = lane; e < qn; e += 64) {
                 uint32_t m0, m1;
                 const uint64_t key = canonical_from_le(extract_bases(sw, q_pl[e]), k);
+                uint32_t cl, cs;  // the line this level tries and the step of its sequence
+                line_of_level(q_grp[e], key, (uint32_t)level, st.nbuckets, cl, cs);
                 if constexpr (WIDE && INL) {
                     uint32_t rw4[4];
-                    lane_chase_inl(st, key, (uint32_t)level, q_line[e], q_step[e], rw4);
+                    lane_chase_inl(st, key, (uint32_t)level, cl, cs, rw4);
                     if (rw4[0] | rw4[1] | rw4[2] | rw4[3]) store_row_regs(tile_rows + (uint64_t)q_pl[e] * nbytes, nbytes, rw4);
                 } else if constexpr (WIDE) {
-                    lane_chase_wide(st, key, (uint32_t)level, q_line[e], q_step[e], m0, m1);
+                    lane_chase_wide(st, key, (uint32_t)level, cl, cs, m0, m1);
                     if (m1) store_row_wide(st.masks, st.W, nbytes, tile_rows + (uint64_t)q_pl[e] * nbytes, m0, m1);
                 } else {
-                    lane_chase<TWO, SLOTS>(st, key, (uint32_t)level, q_line[e], q_step[e], m0, m1);
+                    lane_chase<TWO, SLOTS>(st, key, (uint32_t)level, cl, cs, m0, m1);
                     if constexpr (ROWMODE == 3) cols_or_position(reinterpret_cast<unsigned long long *>(tile_rows), q_pl[e], m0);
                     else if (m0 | m1) store_row<ROWMODE>(tile_rows + (uint64_t)q_pl[e] * nbytes, m0, m1, rc);
                 }
@@ -663,15 +666,19 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
             const uint32_t e = i0 + lane;
             const bool act = e < qn;
             const uint32_t ec = act ? e : qn - 1;
-            uint32_t line = q_line[ec], step = q_step[ec];
-            if (GROUP_CHAIN > 1 && level == 1) {  // (k_probe's entries: home line and group — see there)
-                step = step_of_group(step, st.nbuckets);
-                line = next_line(line, step, st.nbuckets);
-            }
+            const uint32_t grp = q_grp[ec];
             const uint32_t pl = q_pl[ec];
             const uint64_t kmask = kmer_mask(k);
             const uint64_t X = extract_bases32(reinterpret_cast<const uint32_t *>(sw), pl) & kmask;
             const uint64_t key = canonical_from_xb(X, revcomp_window(rw, pl, kmask, PROBE_SEQ_BASES - (uint32_t)k), k);
+            uint32_t line, step;
+            if constexpr (LEVELS < (int)GROUP_CHAIN) {  // (the staged levels end before the group's chain does: none of the key's own hashing here)
+                line = home_of_group(grp, st.nbuckets);
+                step = step_of_group(grp, st.nbuckets);
+                for (int i = 0; i < level; ++i) line = next_line(line, step, st.nbuckets);  // (wave-uniform: once or twice)
+            } else {
+                line_of_level(grp, key, (uint32_t)level, st.nbuckets, line, step);
+            }
             const uint32_t prev_line = lane_up1(line);
             const bool leader = act && (lane == 0 || line != prev_line);
             const unsigned long long lmask = __builtin_amdgcn_ballot_w64(leader);
@@ -729,13 +736,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
             const unsigned long long kmask2 = __builtin_amdgcn_ballot_w64(again);
             if (again) {  // in-place compaction: slot <= e, and this batch's reads are already done
                 const uint32_t slot = set_lane_index(kmask2, kept);
-                uint32_t nl2 = line, ns2 = step;
-                // (staged levels end before the group's chain does: no switch to the key's own sequence
-                // here, and none of its hashing on this path)
-                if constexpr (LEVELS + 1 < (int)GROUP_CHAIN) nl2 = next_line(line, step, st.nbuckets);
-                else advance_line(key, (uint32_t)level + 1, st.nbuckets, nl2, ns2);
-                q_line[slot] = nl2;
-                q_step[slot] = ns2;
+                q_grp[slot] = grp;  // (the same two fields: the next level derives its own line)
                 q_pl[slot] = (uint16_t)pl;
             }
             kept += (uint32_t)__popcll(kmask2);
@@ -1010,8 +1011,8 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
     constexpr int BUF_U4 = ((STAGE_ITERS * 64 + SLOTS - 1) / SLOTS) * LDS_LINE_U4;  // room for every staged chunk slot
     constexpr int OFF_RW = PROBE_SEQW * 8, OFF_NW = OFF_RW + (PROBE_SEQW + 1) * 8, OFF_LW = OFF_NW + PROBE_SEQW * 4;
     constexpr int QCAP = PROBE_QCAP;
-    constexpr int OFF_BUF = (OFF_LW + MAXRUN * 4 + 15) & ~15, OFF_QL = OFF_BUF + BUF_U4 * 16, OFF_QS = OFF_QL + QCAP * 4;
-    constexpr int OFF_QP = OFF_QS + QCAP * 4, LDS_BYTES = OFF_QP + QCAP * 2;
+    constexpr int OFF_BUF = (OFF_LW + MAXRUN * 4 + 15) & ~15, OFF_QG = OFF_BUF + BUF_U4 * 16;
+    constexpr int OFF_QP = OFF_QG + QCAP * 4, LDS_BYTES = OFF_QP + QCAP * 2;
     static_assert(OFF_LW <= 1020 || PROBE_TILE > 1024, "the sequence words must stay within reach of ds_read2_b32's offsets");
     __shared__ __attribute__((aligned(16))) uint8_t lds[LDS_BYTES];
     uint64_t *const sw = reinterpret_cast<uint64_t *>(lds);
@@ -1019,9 +1020,8 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
     uint32_t *const nw = reinterpret_cast<uint32_t *>(lds + OFF_NW);
     uint32_t(*const lines_w)[MAXRUN] = reinterpret_cast<uint32_t(*)[MAXRUN]>(lds + OFF_LW);
     uint4(*const buf)[BUF_U4] = reinterpret_cast<uint4(*)[BUF_U4]>(lds + OFF_BUF);
-    uint32_t *const q_line = reinterpret_cast<uint32_t *>(lds + OFF_QL);  // overflow queue of the tile (position order): next line to try,
-    uint32_t *const q_step = reinterpret_cast<uint32_t *>(lds + OFF_QS);  // step of the entry's sequence
-    uint16_t *const q_pl = reinterpret_cast<uint16_t *>(lds + OFF_QP);    // and position within the tile (the key is re-derived from sw)
+    uint32_t *const q_grp = reinterpret_cast<uint32_t *>(lds + OFF_QG);  // overflow queue of the tile (position order): the entry's group
+    uint16_t *const q_pl = reinterpret_cast<uint16_t *>(lds + OFF_QP);   // and position within the tile (the key is re-derived from sw)
     PG_PH_DECL
     const int lane = threadIdx.x;
     const int k = (int)st.k;
@@ -1304,21 +1304,14 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
         const unsigned long long omask = f.amask & __builtin_amdgcn_sicmp(rcode, 0, 40);
         const bool ovf = __builtin_amdgcn_inverse_ballot_w64(omask);
         if (omask) {
-            // (the entry carries the home line and the GROUP: its step and next line — two multiplies and the wrap — are
-            // worked out by the drain's dense batches (drain_queue, level 1), not here for the few overflowing lanes of
-            // every batch: nine VALU instructions per batch)
-            uint32_t step, nx;
-            if constexpr (GROUP_CHAIN == 1) {  // (tuning build: the group owns its home line only — level 1 is the key's own sequence)
-                key_sequence(f.key, st.nbuckets, nx, step);
-            } else {
-                step = f.grp;
-                nx = f.line;
-            }
+            // (the entry carries the GROUP and the position, nothing else: the line and step of every later level — the
+            // multiplies and the wrap — are worked out by the drain's dense batches (drain_queue), not here for the few
+            // overflowing lanes of every batch; a GROUP_CHAIN == 1 tuning build, whose level 1 is the key's own sequence,
+            // is served by the same entry: line_of_level takes the key, which the drain cuts out of the sequence words)
             // (the queue always has room for a whole batch: the batch loop leaves for an early drain before it could not)
             const uint32_t slot = set_lane_index(omask, qn);
             if (ovf) {
-                q_line[slot] = nx;
-                q_step[slot] = step;
+                q_grp[slot] = f.grp;
                 q_pl[slot] = (uint16_t)pl;
             }
             qn += (uint32_t)__popcll(omask);
@@ -1474,7 +1467,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
     }
     PG_PH(7)
     for (;;) {
-        drain_queue<TWO, ROWMODE, SLOTS, MAXRUN, WIDE, LEVELS, INL>(st, qn, sw, rw, q_line, q_step, q_pl, lines_w[0], buf[0], tile_rows, nbytes, rc, lane);
+        drain_queue<TWO, ROWMODE, SLOTS, MAXRUN, WIDE, LEVELS, INL>(st, qn, sw, rw, q_grp, q_pl, lines_w[0], buf[0], tile_rows, nbytes, rc, lane);
         qn = 0;
         if (b0 >= npos) break;
         __syncthreads();

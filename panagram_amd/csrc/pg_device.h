@@ -250,6 +250,19 @@ __device__ __forceinline__ void advance_line(uint64_t key, uint32_t level, uint6
         line = next_line(line, step, nlines);
     }
 }
+// Line number `level` (0 = home) of the probe sequence of a key of group `grp`, from nothing else, and the step of the
+// sequence that line belongs to: what advance_line reaches step by step from the home line
+__device__ __forceinline__ void line_of_level(uint32_t grp, uint64_t key, uint32_t level, uint64_t nlines, uint32_t &line,
+                                              uint32_t &step) {
+    uint32_t g = grp, n = level;
+    if (level >= GROUP_CHAIN) {  // the key's own sequence
+        g = fmix32(group_of_key(key) ^ 0x7feb352du);
+        n = level - GROUP_CHAIN;
+    }
+    line = home_of_group(g, nlines);
+    step = step_of_group(g, nlines);
+    for (uint32_t i = 0; i < n; ++i) line = next_line(line, step, nlines);
+}
 
 // ---- packed sequence ------------------------------------------------------
 // base i of a contig lives in bits [2*(i%32), 2*(i%32)+1] of u64 word i/32 (little-endian in

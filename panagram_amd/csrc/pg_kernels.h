@@ -26,9 +26,10 @@ static_assert(PROBE_TILE % 512 == 0, "the column kernels take a tile in units of
 #endif
 constexpr int PROBE_STAGED_LEVELS = PG_PROBE_STAGED_LEVELS;  // LDS-staged overflow levels; beyond: lanes chase inline
 #ifndef PG_PROBE_QCAP
-#define PG_PROBE_QCAP 192  // (with the 1024-position tile's sequence words: 5104 bytes of LDS per wave, 32 waves per CU)
+#define PG_PROBE_QCAP 320  // (entries of six bytes — group, position: with the 1024-position tile's sequence words 5104 bytes of LDS per wave, 32 waves per CU;
+                           // the 192 ten-byte entries before them took the same 1920 bytes)
 #endif
-constexpr int PROBE_QCAP = PG_PROBE_QCAP;      // per-tile LDS overflow queue (beyond: resolved inline)
+constexpr int PROBE_QCAP = PG_PROBE_QCAP;      // per-tile LDS overflow queue (a batch starts with at most QCAP - 64 entries queued: beyond, the tile drains early)
 
 // which row bytes a sub-table writes: low nb0 bytes of mask word 0 at column col0, low nb1 bytes
 // of mask word 1 at col0+4; words: 1 = rows are a whole number of 32-bit words, so a full mask word

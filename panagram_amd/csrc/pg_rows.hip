@@ -5,18 +5,21 @@
 // gene windows (index.py:1055-1063) and the lowres_step rows (index.py:101-106).  The genome-sharded exchange has no
 // counterpart there.
 //
-//   k_epilogue   streaming statistics from the finished bitmap.1 rows: bitmap.100 (1-in-100
+//   k_epilogue_* streaming statistics from the finished bitmap.1 rows: bitmap.100 (1-in-100
 //                rows), per-bin popcount histogram, per-contig column sums — persistent
-//                workgroups, register accumulators, one instantiation per row width (1..8 bytes;
-//                16 consecutive rows per thread over 4 full tiles of one bin).
-//   k_epilogue_w the same for rows of 9..16 bytes (65..128 genomes): three or four words per row.
-//   k_epilogue_chunks  the same for rows wider than 16 bytes (more than 128 genomes): a lane owns one
+//                workgroups, register accumulators.  They share the histogram window (HistWindow), the prologue
+//                (epi_prologue) and, but for one-byte rows, the column sums' counter planes (pg_planes.h).
+//   k_epilogue_b1  one-byte rows (up to 8 genomes): 32 rows per thread over 8 full tiles, bit-sliced.
+//   k_epilogue_n   rows of 2..8 bytes, one instantiation per width: 16 consecutive rows per thread over 4 full tiles.
+//   k_epilogue_w   rows of 9..16 bytes (65..128 genomes): three or four words per row.
+//   k_epilogue_chunks  rows wider than 16 bytes (more than 128 genomes): a lane owns one
 //                16-byte chunk of the rows it visits, one launch reads every row once.
 //   k_window_stats, k_cols_extract / k_cols_merge: side paths (gene / bin windows; the
 //                genome-sharded exchange).
 //   k_lowres, k_tile_reduce: the low-resolution bitmap for steps other than 100; the per-tile counters of a fused k_probe launch
 //                (FuseArgs, pg_kernels.h) into the bins and column sums.
 #include "pg_kernels.h"
+#include "pg_planes.h"
 #include <map>
 #include <mutex>
 #include <utility>
@@ -76,7 +79,7 @@ __device__ __forceinline__ void hist_position(bool active, uint32_t pos, uint32_
 
 // Every lane adds its own value to the LDS counter p (one ds_add per lane).  With an address the compiler sees as uniform,
 // its atomic optimizer sums the lanes first in a SCALAR loop over the active lanes (s_ff1 / v_readlane / s_add ..., seven
-// scalar instructions per lane and a dependent chain through all 64): k_epilogue<0,1>'s end-of-bin and end-of-range
+// scalar instructions per lane and a dependent chain through all 64): k_epilogue_b1's end-of-bin and end-of-range
 // reductions (9 + 8 counters) came to most of the pass's SQ_INSTS_SALU, and their chains were most of its fixed cost
 // (profiles/r7_stats_fixed_cost.md).  The zero comes out of inline assembly, so that the address stays per lane; the LDS
 // works the same-address lanes off one after the other, about 64 cycles per instruction.
@@ -118,6 +121,9 @@ constexpr int EPI_THREADS = PROBE_TILE / 4;
 
 static_assert(EPI_THREADS >= 64 && EPI_THREADS % 64 == 0, "PROBE_TILE must be a multiple of 256");
 
+struct __attribute__((packed)) U32 { uint32_t v; };             // (unaligned 4- and 16-byte accesses)
+struct __attribute__((packed)) U128 { uint32_t x, y, z, w; };
+
 __device__ __forceinline__ void flush_hist(uint32_t N, uint32_t *hist, uint32_t *bins, uint64_t bin_row0, int tid, uint32_t maxb) {
     for (uint32_t i = tid; i < maxb * (N + 1); i += EPI_THREADS) {
         const uint32_t hv = hist[i];
@@ -129,9 +135,105 @@ __device__ __forceinline__ void flush_hist(uint32_t N, uint32_t *hist, uint32_t 
     }
 }
 
-// MODE 0: one-byte rows (N <= 8), 1: rows of 2..8 bytes (N <= 64); wider rows go through
-// k_epilogue_chunks below.  One instantiation per mode so that each carries only its own accumulators
-// in registers.
+// The histogram window of a workgroup: the LDS counters `hist` stand for the MAXB bins rows from cur_row0 on (~0: none yet).
+// All of its state is block-uniform; every member is called by the whole workgroup.
+//
+// The group paths of rows of 2..16 bytes add ONE to an LDS counter per row, and the lanes of a wave mostly ask for the
+// same few counters (the popcount classes near N): the LDS works a wave's atomic off one lane per cycle and address —
+// 0.9-1.0 ps per row whatever the row width, twice what 2-byte rows need otherwise.  While the groups lie inside one
+// or two long bins (any contig of more than 200 kb) the window is therefore used as EPI_REPL copies of those two bin
+// rows, lane l adding to copy l % EPI_REPL (copy c at c * repl_stride, an odd stride: the copies of one class sit in
+// different banks); `unreplicate` folds the copies into the window's ordinary form — rows 0 and 1 — before anything
+// else reads or flushes it.  (The chunk kernel keeps the plain window: the copies lose 3-6 % where only every second or third
+// lane adds, profiles/r4e_ab_stats_hist_copies_wide.txt.)
+constexpr uint32_t EPI_REPL = 8;  // (16 copies: no further gain, profiles/r3_ab_stats_hist_copies.txt)
+struct HistWindow {
+    uint32_t *hist, *bins;
+    uint32_t N, MAXB, MINBIN;  // MINBIN: bins at least this long let a tile span <= MAXB of them
+    int tid;
+    uint64_t cur_row0;  // bins row the counters currently stand for
+    bool repl;          // the window holds copies
+    __device__ __forceinline__ uint32_t repl_stride() const { return (2u * (N + 1u)) | 1u; }
+    // the copies must fit the window: the last one would run into the column counters behind it otherwise (8 copies need
+    // 16 (N + 1) + 8 words: MAXB >= 17 — epi_maxb_for gives >= 23 for N <= 128)
+    __device__ __forceinline__ bool copies_fit() const { return EPI_REPL * repl_stride() <= MAXB * (N + 1u); }
+    __device__ __forceinline__ void flush() {
+        __syncthreads();
+        flush_hist(N, hist, bins, cur_row0, tid, MAXB);
+        __syncthreads();
+    }
+    __device__ __forceinline__ void unreplicate() {
+        if (!repl) return;
+        __syncthreads();
+        for (uint32_t i = tid; i < 2u * (N + 1u); i += EPI_THREADS) {
+            uint32_t v = hist[i];
+#pragma unroll
+            for (uint32_t cpy = 1; cpy < EPI_REPL; ++cpy) {
+                v += hist[cpy * repl_stride() + i];
+                hist[cpy * repl_stride() + i] = 0;
+            }
+            hist[i] = v;
+        }
+        __syncthreads();
+        repl = false;
+    }
+    // Seat the bins rows row0 .. row0 + last_rel (a tile's, or a one-byte group's) in the window in its ordinary form: may
+    // they add to it as it stands?  If not it is flushed and moved to row0.  exact: the caller's per-thread accumulators stand
+    // for the window's FIRST row, so row0 must be it; an unwindowed tile (bins shorter than MINBIN) likewise uses row 0 only.
+    // before_flush: what the caller has to put into the window first (the one-byte kernel's register accumulators).
+    // Returns row0's place in the window.
+    template <class F>
+    __device__ __forceinline__ uint32_t seat_tile(uint64_t row0, uint32_t last_rel, bool windowed, bool exact, F &&before_flush) {
+        const bool fits = cur_row0 != ~0ull && (exact || !windowed ? row0 == cur_row0
+                                                : (row0 >= cur_row0 && row0 + last_rel < cur_row0 + MAXB));
+        if (!fits) {
+            if (cur_row0 != ~0ull) {
+                before_flush();
+                flush();
+            }
+            cur_row0 = row0;
+        }
+        return (uint32_t)(row0 - cur_row0);
+    }
+    __device__ __forceinline__ uint32_t seat_tile(uint64_t row0, uint32_t last_rel, bool windowed) {
+        return seat_tile(row0, last_rel, windowed, false, [] {});
+    }
+    // Seat the nbg bins rows of a group of rows of 2..16 bytes: as copies while the group lies inside one or two bins.
+    // Returns whether the window holds copies now.
+    __device__ __forceinline__ bool seat_group(uint64_t row0g, uint32_t nbg) {
+        const bool want_repl = nbg <= 2u && copies_fit();
+        if (want_repl) {
+            if (!(repl && row0g >= cur_row0 && row0g + nbg <= cur_row0 + 2u)) {
+                if (cur_row0 != ~0ull) {
+                    unreplicate();
+                    flush();
+                }
+                cur_row0 = row0g;
+                repl = true;
+            }
+        } else {
+            unreplicate();
+            if (cur_row0 == ~0ull || row0g < cur_row0 || row0g + nbg > cur_row0 + MAXB) {
+                if (cur_row0 != ~0ull) flush();
+                cur_row0 = row0g;
+            }
+        }
+        return want_repl;
+    }
+    // the counters of bins row row0g + rel0 after seat_group: the lane's copy of them, or the only one
+    __device__ __forceinline__ uint32_t *group_row(uint64_t row0g, uint32_t rel0, bool copies, int lane) const {
+        return hist + ((uint32_t)(row0g - cur_row0) + rel0) * (N + 1) + (copies ? ((uint32_t)lane % EPI_REPL) * repl_stride() : 0u);
+    }
+    template <class F>
+    __device__ __forceinline__ void finish(F &&before_flush) {  // the end of the workgroup's range
+        unreplicate();
+        before_flush();
+        __syncthreads();
+        if (cur_row0 != ~0ull) flush_hist(N, hist, bins, cur_row0, tid, MAXB);
+    }
+    __device__ __forceinline__ void finish() { finish([] {}); }
+};
+
 // The tiles a statistics workgroup takes: a contiguous range, cut in units of `gt` tiles (the group paths' granule).
 // ranges == NULL: the launch covers tiles [0, ntiles), split evenly over the grid.  Otherwise (a CHUNK of a run whose
 // probe launches are interleaved with their statistics passes, pg_api.hip: anchor_run): the launch covers the tile ranges
@@ -155,54 +257,175 @@ __device__ __forceinline__ EpiRange epi_range(uint32_t gt, uint32_t ntiles, cons
     return e;
 }
 
-// (one-byte rows: held to the registers of 7 waves per SIMD — 72 VGPRs and 20 bytes of scratch on a cold path instead of 79,
+// What every statistics kernel starts from: the LDS carved into the histogram window and `ncs` column counters behind it, both
+// zeroed; the launch's flags; an empty contig descriptor; the workgroup's tile range in units of `gt` tiles.
+struct EpiStart {
+    HistWindow win;
+    uint32_t *cs;
+    bool want_cs, want100;  // column sums asked for; bitmap.100 written here (flags bit 1: k_lowres takes the low-resolution rows, step != 100)
+    uint32_t t_begin, t_end;
+    AnchorDesc a;
+};
+__device__ __forceinline__ EpiStart epi_prologue(uint4 *smem, uint32_t N, uint32_t ncs, uint32_t flags, uint32_t *bins, uint32_t gt,
+                                                 uint32_t ntiles, const uint2 *ranges, uint32_t wpr) {
+    EpiStart s;
+    const int tid = threadIdx.x;
+    uint32_t *hist = reinterpret_cast<uint32_t *>(smem);
+    const uint32_t MAXB = max(EPI_MAXB, (flags >> 8) & 0xFFu);  // bins in the LDS window (launcher's choice)
+    s.cs = hist + ((MAXB * (N + 1) + 3) & ~3u);
+    for (uint32_t i = tid; i < MAXB * (N + 1); i += EPI_THREADS) hist[i] = 0;
+    for (uint32_t i = tid; i < ncs; i += EPI_THREADS) s.cs[i] = 0;
+    __syncthreads();
+    s.win.hist = hist;
+    s.win.bins = bins;
+    s.win.N = N;
+    s.win.MAXB = MAXB;
+    s.win.MINBIN = epi_minbin(MAXB);
+    s.win.tid = tid;
+    s.win.cur_row0 = ~0ull;
+    s.win.repl = false;
+    s.want_cs = (flags & 1u) != 0;
+    s.want100 = (flags & 2u) == 0;
+    const EpiRange er = epi_range(gt, ntiles, ranges, wpr);
+    s.t_begin = er.begin;
+    s.t_end = er.end;
+    s.a.out_off = s.a.out100_off = s.a.bin_off = 0;
+    s.a.nkmers = s.a.binlen = s.a.tile0 = s.a.nbins = 0;
+    return s;
+}
+
+// column sums are kept per contig (colsums[contig][N]): the workgroup's N plain LDS counters are emptied whenever its tile
+// range moves on to another contig (block-uniform, rare)
+__device__ __forceinline__ void flush_colsums(uint32_t N, uint32_t *cs, unsigned long long *colsums, uint32_t contig, int tid) {
+    __syncthreads();
+    for (uint32_t i = tid; i < N; i += EPI_THREADS) {
+        const uint32_t v = cs[i];
+        if (v) {
+            atomicAdd(&colsums[(uint64_t)contig * N + i], (unsigned long long)v);
+            cs[i] = 0;
+        }
+    }
+    __syncthreads();
+}
+
+// The low-resolution copy takes every 100th row: among a thread's n <= 100 consecutive rows from pos0 there is at most one,
+// row `r100` of the copy, `first` rows behind pos0 — it is one of the thread's if first < n.
+struct Hit100 {
+    uint32_t r100, first;
+};
+__device__ __forceinline__ Hit100 hit100(uint32_t pos0) {
+    Hit100 h;
+    h.r100 = (pos0 + 99u) / 100u;
+    h.first = h.r100 * 100u - pos0;
+    return h;
+}
+
+// one row of NBT bytes copied to the low-resolution bitmap: one unaligned 16-byte read (it may reach into the rows that follow, or
+// into the 16 bytes of slack every row buffer carries), whole words and the tail's bytes written
+template <int NBT>
+__device__ __forceinline__ void copy_row_w(const uint8_t *pr, uint8_t *o) {
+    const U128 t = *reinterpret_cast<const U128 *>(pr);
+    const uint32_t xw[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int w = 0; w < NBT / 4; ++w) reinterpret_cast<U32 *>(o + 4 * w)->v = xw[w];
+#pragma unroll
+    for (int bb = 0; bb < NBT % 4; ++bb) o[4 * (NBT / 4) + bb] = (uint8_t)(xw[(NBT / 4) & 3] >> (8 * bb));
+}
+
+// A tile whose bins are shorter than MINBIN — it may span more bins than the window holds (rows of 1..8 bytes): byte loads, the
+// histogram wave-aggregated into the window or, beyond it, global memory; one ballot per genome for the column sums.
+template <int NBT, int PT>
+__device__ __forceinline__ void epi_tile_unwindowed(const HistWindow &win, uint32_t N, const AnchorDesc &a, const uint8_t *g, uint32_t p0,
+                                                    uint32_t npos, uint32_t tile_start, uint32_t bin0, uint32_t bin0_start,
+                                                    uint32_t rel_base, bool want100, bool want_cs, uint8_t *out100, uint32_t *cs, int lane) {
+    constexpr uint32_t nbytes = NBT;
+    const uint32_t ndbs_all = (N + 31) / 32;
+#pragma unroll
+    for (int jj = 0; jj < PT; ++jj) {
+        const uint32_t pl = p0 + jj;
+        const bool active = pl < npos;
+        const uint32_t pos = tile_start + pl;
+        uint32_t popc = 0;
+        const bool is100 = want100 && active && (pos % 100u == 0);
+        for (uint32_t d = 0; d < ndbs_all; ++d) {
+            const uint32_t nb = min(4u, nbytes - 4 * d);
+            uint32_t wv = 0;
+            if (active)
+                for (uint32_t bb = 0; bb < nb; ++bb) wv |= (uint32_t)g[(uint64_t)pl * nbytes + 4 * d + bb] << (8 * bb);
+            popc += __popc(wv);
+            if (is100) {
+                uint8_t *o100 = out100 + a.out100_off + (uint64_t)(pos / 100u) * nbytes + 4 * d;
+                for (uint32_t bb = 0; bb < nb; ++bb) o100[bb] = (uint8_t)(wv >> (8 * bb));
+            }
+            if (want_cs) colsum_word(wv, d, N, cs, lane);
+        }
+        hist_position(active, pos, popc, N, a.binlen, bin0, bin0_start, rel_base, win.hist, win.bins, a.bin_off, lane, win.MAXB);
+    }
+}
+
+// (k_epilogue_b1's bit-sliced planes) row j = 4 * word + byte of a thread sits at bit 8 * byte + word of every plane: the rows below j
+__device__ __forceinline__ uint32_t b1_rows_below(uint32_t j) {
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t rb = 0; rb < 4; ++rb) {
+        const uint32_t nw = j > rb ? min(8u, (j - rb + 3u) >> 2) : 0u;  // words whose byte rb is below row j
+        m |= ((1u << nw) - 1u) << (8u * rb);
+    }
+    return m;
+}
+
+// ---------------------------------------------------------------------------
+// One-byte rows (N <= 8): persistent workgroups, register accumulators.
+// GROUP PATH: 8 full tiles of one contig inside one bin = 32 one-byte rows per thread in two
+// 16-byte loads, worked on BIT-SLICED: a three-stage butterfly between the 8 words regroups their 256 bits so
+// that word g holds bit g of all 32 rows (same row, same bit position in every word: 4 instructions per word
+// pair and stage); an 8-input sorting network on those planes (19 compare-exchanges = AND / OR pairs) turns
+// them into thresholds "row has more than i bits"; popcounts of the planes are the column sums, popcounts of
+// the thresholds the cumulative histogram.  3.2 instructions per row, where one-hot adds per row took 13.
+// Two kinds of group: (1) all 4096 rows inside ONE bin — thresholds and rows counted in registers, reduced when the
+// bin changes; (2) several bins (contigs of a few kb .. Mb have bins of nkmers / 100 rows): bins of at least 32
+// rows, so that a thread's 32 rows meet at most one bin boundary, and all of the group's bins inside the LDS window —
+// the thread splits its threshold popcounts at the boundary (a mask over the planes' bit positions) and adds the
+// classes of its one or two bins to the window with up to 9 LDS atomics each, where the per-tile path does one per row.
+// A group need not be whole: a contig's last tiles (and a workgroup's last ones) form a group of fewer rows — a thread
+// then holds nv < 32 valid rows (possibly none) and masks the planes with the same kind of position mask.
+// STREAK: whole one-bin groups known to follow the current one inside its bin, contig and tile range.  This
+// pass is bound by its SCALAR instructions — a SIMD issues at most one per four cycles, and the block-uniform bookkeeping of
+// a group (two tile_contig look-ups, six divisions by the bin length at 11 instructions each, the window checks) came to
+// 330 of them against 195 vector instructions (100 dummy s_add per group: +0.07 ms on 8 x 10^8 rows, 100 dummy VALU: +0.04;
+// profiles/r4e_stats_scalar_bound.txt).  Worked out ONCE when a group turns out whole and inside one bin; the groups of
+// the streak then take nothing of that: same contig, same bin row, no window check, the next group's prefetch certain.
+// (held to the registers of 7 waves per SIMD — 72 VGPRs and 20 bytes of scratch on a cold path instead of 79,
 // 96 SGPRs instead of 106: 6 -> 7 workgroups per CU, the pass 0.362 -> 0.353 ms on 8 x 10^8 rows, 0.616 -> 0.588 on
 // 1.6 x 10^9; 8 waves (64 VGPRs, 40 bytes of scratch) are slower, 0.392; profiles/r4b_ab_epilogue_waves.txt)
+// ---------------------------------------------------------------------------
 #ifndef PG_EPI_WAVES0
 #define PG_EPI_WAVES0 7
-#endif
-// (rows of 2 to 5 bytes: 6 waves per SIMD instead of the 4-5 their 96-106 VGPRs allowed — 12 x 60 Mb 0.578 -> 0.509 ms,
-// 20 x 40 Mb 0.647 -> 0.57, 27 x 40 Mb and 40 x 30 Mb 2-6 %; 8-byte rows lose with it, 1.95 -> 2.1-2.3 ms, and stay as they were)
-#ifndef PG_EPI_WAVES1
-#define PG_EPI_WAVES1 6
 #endif
 #ifndef PG_EPI_SGPRS0
 #define PG_EPI_SGPRS0 96
 #endif
-template <int MODE, int NBT>  // NBT = bytes per row (1..8): one instantiation, and one register allocation, per width
-__global__ __launch_bounds__(EPI_THREADS, (MODE == 0 ? PG_EPI_WAVES0 : NBT <= 5 ? PG_EPI_WAVES1 : 1))
-__attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, const AnchorDesc *__restrict__ ad,
-                                                          const uint32_t *__restrict__ tile_contig, uint32_t ntiles,
-                                                          const uint8_t *__restrict__ out1, uint8_t *__restrict__ out100,
-                                                          uint32_t *__restrict__ bins,
-                                                          unsigned long long *__restrict__ colsums, uint32_t flags,
-                                                          const uint2 *__restrict__ ranges, uint32_t wpr) {
+__global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVES0)
+__attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue_b1(uint32_t N, const AnchorDesc *__restrict__ ad,
+                                                             const uint32_t *__restrict__ tile_contig, uint32_t ntiles,
+                                                             const uint8_t *__restrict__ out1, uint8_t *__restrict__ out100,
+                                                             uint32_t *__restrict__ bins,
+                                                             unsigned long long *__restrict__ colsums, uint32_t flags,
+                                                             const uint2 *__restrict__ ranges, uint32_t wpr) {
     extern __shared__ uint4 smem[];
     constexpr int PT = 4;  // rows per thread and tile: EPI_THREADS = PROBE_TILE / 4 threads per workgroup
-    constexpr bool WIDE = MODE == 1;
     const int tid = threadIdx.x, lane = tid & 63;
-    constexpr uint32_t nbytes = NBT;
-    const uint32_t Nw = N;
-    const uint32_t ndbs = (N + 31) / 32;
-    uint32_t *hist = reinterpret_cast<uint32_t *>(smem);
-    const uint32_t MAXB = max(EPI_MAXB, (flags >> 8) & 0xFFu), MINBIN = epi_minbin(MAXB);  // bins in the LDS window (launcher's choice)
-    uint32_t *cs = hist + ((MAXB * (N + 1) + 3) & ~3u);
-    for (uint32_t i = tid; i < MAXB * (N + 1); i += EPI_THREADS) hist[i] = 0;
-    for (uint32_t i = tid; i < N; i += EPI_THREADS) cs[i] = 0;
-    __syncthreads();
-    const bool want_cs = (flags & 1u) != 0;
-    const bool want100 = (flags & 2u) == 0;  // bit 1: the low-resolution rows are taken by k_lowres (step != 100)
-    // contiguous tile ranges, cut in units of the group paths' 4 tiles (16 rows per thread; one-byte rows: 8 tiles, 32 rows)
-    constexpr uint32_t GT = MODE == 0 ? 8u : 4u;
-    const EpiRange er = epi_range(GT, ntiles, ranges, wpr);
-    const uint32_t t_begin = er.begin, t_end = er.end;
-    uint64_t cur_row0 = ~0ull;  // bins row the accumulators currently stand for
+    // contiguous tile ranges, cut in units of the group path's 8 tiles (32 rows per thread)
+    EpiStart st = epi_prologue(smem, N, N, flags, bins, 8u, ntiles, ranges, wpr);
+    HistWindow &win = st.win;
+    uint32_t *const hist = win.hist, *const cs = st.cs;
+    const uint32_t MAXB = win.MAXB, MINBIN = win.MINBIN;
+    const bool want_cs = st.want_cs, want100 = st.want100;
+    const uint32_t t_begin = st.t_begin, t_end = st.t_end;
     uint32_t cur_c = ~0u;
-    AnchorDesc a;
-    a.out_off = a.out100_off = a.bin_off = 0;
-    a.nkmers = a.binlen = a.tile0 = a.nbins = 0;
+    AnchorDesc a = st.a;
     const uint32_t p0 = tid * PT;
-    // fast path (N <= 8) per-thread accumulators, reduced over the workgroup only when the bin
+    // per-thread accumulators, reduced over the workgroup only when the bin
     // changes / at the end: 9 popcount classes as 7-bit fields of one u64 (spilled to the u32 counters
     // below every 31 tiles), 8 column counters
     unsigned long long hacc = 0;
@@ -213,19 +436,313 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
     uint32_t since_spill = 0;
     uint32_t next_packed = 0;  // software prefetch of the next tile's rows
     bool next_valid = false;
-    uint4 wp_a = make_uint4(0, 0, 0, 0), wp_b = make_uint4(0, 0, 0, 0);  // ... and of 4- / 8-byte rows on the wide path
+    auto spill = [&]() {  // the per-tile path's classes (7-bit fields of hacc) join the thresholds: thr[i] += rows of class > i
+        uint32_t run = 0;
+#pragma unroll
+        for (int v = 8; v >= 1; --v) {
+            run += (uint32_t)(hacc >> (7 * v)) & 127u;
+            thr[v - 1] += run;
+        }
+        grows += run + ((uint32_t)hacc & 127u);
+        hacc = 0;
+        since_spill = 0;
+    };
+    auto reduce_hist = [&]() {  // per-thread thresholds -> classes -> LDS histogram (bin-relative row 0)
+        spill();
+        uint32_t hc[9];
+        hc[0] = grows - thr[0];
+#pragma unroll
+        for (int v = 1; v < 8; ++v) hc[v] = thr[v - 1] - thr[v];
+        hc[8] = thr[7];
+#pragma unroll
+        for (int v = 8; v >= 1; --v)  // (junk bits beyond ngenomes count as class N, as on the per-tile path)
+            if ((uint32_t)v > N) {
+                hc[v - 1] += hc[v];
+                hc[v] = 0;
+            }
+        grows = 0;
+#pragma unroll
+        for (int v = 0; v < 8; ++v) thr[v] = 0;
+#pragma unroll
+        for (int v = 0; v < 9; ++v)
+            if ((uint32_t)v <= N && hc[v]) lds_add_lanes(&hist[v], hc[v]);
+    };
+    auto contig_done = [&](uint32_t contig) {  // the register column counters join the LDS ones, those leave for the contig's sums
+#pragma unroll
+        for (int gb = 0; gb < 8; ++gb) {
+            if ((uint32_t)gb < N && cacc[gb]) lds_add_lanes(&cs[gb], cacc[gb]);
+            cacc[gb] = 0;
+        }
+        flush_colsums(N, cs, colsums, contig, tid);
+    };
+    uint4 gq_next = make_uint4(0, 0, 0, 0), gq_next2 = make_uint4(0, 0, 0, 0);  // group path: prefetched rows of the next group
+    bool gq_valid = false;
+    // the streak (see above the kernel): whole one-bin groups known to follow, and what the group before worked out of the next one
+    uint32_t streak = 0, nk_ba = 0, nk_bz = 0;
+    int nk_kind = 0;
+    for (uint32_t tile = t_begin; tile < t_end; ++tile) {
+        uint32_t c = cur_c;
+        if (!(streak || gq_valid)) {  // (a group the one before has announced lies in its contig)
+            c = tile_contig[tile];
+            if (c != cur_c) {  // block-uniform; consecutive tiles nearly always share their contig
+                if (want_cs && cur_c != ~0u) contig_done(cur_c);
+                a = ad[c];
+                cur_c = c;
+            }
+        }
+        // ---- group path (see above the kernel) ----
+        {
+            const uint32_t ts = (tile - a.tile0) * PROBE_TILE;
+            const uint32_t span = 8u * PROBE_TILE;
+            // rows of this contig from ts on that belong to this workgroup's tile range, at most a whole group's
+            auto rows_at = [&](uint32_t tl, uint32_t t0) -> uint32_t {  // (block-uniform)
+                if (tl >= t_end || tile_contig[tl] != c || t0 >= a.nkmers) return 0u;
+                return min(min(span, a.nkmers - t0), (t_end - tl) * (uint32_t)PROBE_TILE);
+            };
+            // (block-uniform) first and last bin of the rows [t0, t0 + rows) and the kind of group they make — 1: one bin, 2: several
+            // bins, 0: not a group
+            auto group_kind = [&](uint32_t t0, uint32_t rows, uint32_t &ba, uint32_t &bz) -> int {
+                if (rows == 0) return 0;
+                const uint32_t bl = a.binlen;
+                ba = t0 / bl;
+                bz = (t0 + rows - 1) / bl;
+                if (ba == bz) return 1;
+                return (bl >= 32u && bz - ba + 1u <= MAXB) ? 2 : 0;
+            };
+            const bool fast = streak != 0;  // (block-uniform) a group of a streak: whole, one bin, the bin of the group before
+            const bool known = !fast && gq_valid;  // the group before worked this one out (whole; nk_kind, nk_ba .. nk_bz) when it asked for its rows
+            uint32_t grows_n = span, ba = nk_ba, bz = nk_bz;
+            int kind = fast ? 1 : nk_kind;
+            if (fast) {
+                --streak;
+            } else if (!known) {
+                grows_n = rows_at(tile, ts);  // (>= 1: this tile has rows)
+                kind = group_kind(ts, grows_n, ba, bz);
+            }
+            if (kind != 0) {
+                uint64_t row0g = win.cur_row0;
+                if (!fast) {
+                    row0g = a.bin_off + ba;
+                    // (a one-bin group's thresholds are counted in registers: they stand for the window's first row)
+                    win.seat_tile(row0g, bz - ba, true, kind == 1, reduce_hist);
+                    if (kind == 1 && grows_n == span) {
+                        // whole groups from ts on that end inside this bin, this contig and this workgroup's range (this one included)
+                        const uint64_t bin_end = min((uint64_t)(ba + 1u) * a.binlen, (uint64_t)a.nkmers);
+                        streak = min((uint32_t)(bin_end - ts) / span, (t_end - tile) / 8u) - 1u;
+                    }
+                }
+                const uint32_t nv = 32u * tid < grows_n ? min(32u, grows_n - 32u * tid) : 0u;  // this thread's valid rows
+                // (a 16-byte load that begins on a valid row ends inside the contig's 16-byte padded region)
+                const uint4 *gg = reinterpret_cast<const uint4 *>(out1 + a.out_off + (uint64_t)ts + 32u * tid);
+                const uint4 z4 = make_uint4(0, 0, 0, 0);
+                const uint4 qa = gq_valid ? gq_next : (nv > 0u ? gg[0] : z4);
+                const uint4 qb = gq_valid ? gq_next2 : (nv > 16u ? gg[1] : z4);
+                // This group's rows are waited for HERE, before the next group's loads go out.  Left to the compiler the wait sat
+                // at the rows' first use — BEHIND the prefetch — and, the paths above having merged, as vmcnt(0): it waited for
+                // the prefetch as well, so that a group's load latency and its arithmetic ran one after the other (0.35 ms for
+                // 8 x 10^8 rows where a kernel of the same geometry that only loads and counts takes 0.19).
+                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), nothing else
+                // prefetch the next group when this one is whole and a whole group follows right behind
+                const uint32_t tiles_here = (grows_n + PROBE_TILE - 1) / PROBE_TILE;
+                gq_valid = streak != 0;
+                if (!gq_valid && grows_n == span && rows_at(tile + 8, ts + span) == span) {
+                    nk_kind = group_kind(ts + span, span, nk_ba, nk_bz);
+                    gq_valid = nk_kind != 0;
+                }
+                if (gq_valid) {
+                    gq_next = gg[span / 16u];
+                    gq_next2 = gg[span / 16u + 1];
+                }
+                uint32_t w[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+                const uint32_t pos0 = ts + 32u * tid;
+                const Hit100 h = hit100(pos0);
+                if (want100 && h.first < nv) {
+                    uint32_t sel = w[0];
+#pragma unroll
+                    for (uint32_t i = 1; i < 8; ++i) sel = (h.first >> 2) == i ? w[i] : sel;
+                    out100[a.out100_off + h.r100] = (uint8_t)(sel >> (8 * (h.first & 3)));
+                }
+#pragma unroll
+                for (int kb = 0; kb < 3; ++kb) {
+                    const uint32_t m0 = kb == 0 ? 0x55555555u : kb == 1 ? 0x33333333u : 0x0F0F0F0Fu;
+                    const int sh = 1 << kb;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        if (i & sh) continue;
+                        const uint32_t x = w[i], y = w[i | sh];
+                        w[i] = (x & m0) | ((y << sh) & ~m0);       // the pair's bits with bit kb of g clear
+                        w[i | sh] = ((x >> sh) & m0) | (y & ~m0);  // ... and set
+                    }
+                }
+                const bool whole = grows_n == span;  // (block-uniform)
+                const uint32_t mval = whole ? 0xFFFFFFFFu : b1_rows_below(nv);
+                if (!whole) {
+#pragma unroll
+                    for (int gb = 0; gb < 8; ++gb) w[gb] &= mval;  // rows past the group hold whatever follows in memory
+                }
+                if (want_cs) {
+#pragma unroll
+                    for (int gb = 0; gb < 8; ++gb) cacc[gb] += __popc(w[gb]);
+                }
+                auto cx = [&](int i, int j) __attribute__((always_inline)) {
+                    const uint32_t lo = w[i] & w[j], hi = w[i] | w[j];
+                    w[i] = lo;
+                    w[j] = hi;
+                };
+                cx(0, 1), cx(2, 3), cx(4, 5), cx(6, 7);
+                cx(0, 2), cx(1, 3), cx(4, 6), cx(5, 7);
+                cx(1, 2), cx(5, 6), cx(0, 4), cx(3, 7);
+                cx(1, 5), cx(2, 6);
+                cx(1, 4), cx(3, 6);
+                cx(2, 4), cx(3, 5);
+                cx(3, 4);
+                if (kind == 1) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) thr[i] += __popc(w[7 - i]);  // ascending order: w[7] = any bit set
+                    grows += nv;
+                } else {
+                    // this thread's rows pos0 .. pos0 + nv - 1: bin of the first one (relative to the group's first bin) and
+                    // rows until the next bin boundary
+                    const uint32_t bl = a.binlen, bin0s = ba * bl, d0 = pos0 - bin0s;  // (ba = ts / bl)
+                    const uint32_t rel0 = bl >= span ? (d0 >= bl ? 1u : 0u) : __umulhi(d0, 0xFFFFFFFFu / bl + 1u);  // (d0 < 2^16)
+                    const uint32_t jb = min(nv, (rel0 + 1u) * bl - d0);  // valid rows of the first bin
+                    const uint32_t mlo = b1_rows_below(jb);
+                    uint32_t *h0 = hist + ((uint32_t)(row0g - win.cur_row0) + rel0) * (N + 1);
+                    auto add_classes = [&](uint32_t *hb, uint32_t mask, uint32_t rows) __attribute__((always_inline)) {
+                        uint32_t cl[9], above = rows;
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) {
+                            const uint32_t t = (uint32_t)__popc(w[7 - i] & mask);  // rows of this bin with more than i bits
+                            cl[i] = above - t;
+                            above = t;
+                        }
+                        cl[8] = above;
+#pragma unroll
+                        for (int v = 8; v >= 1; --v)  // (junk bits beyond ngenomes count as class N)
+                            if ((uint32_t)v > N) {
+                                cl[v - 1] += cl[v];
+                                cl[v] = 0;
+                            }
+#pragma unroll
+                        for (int v = 0; v < 9; ++v)
+                            if ((uint32_t)v <= N && cl[v]) atomicAdd(&hb[v], cl[v]);
+                    };
+                    if (jb) add_classes(h0, mlo, jb);
+                    if (jb < nv) add_classes(h0 + (N + 1), mval & ~mlo, nv - jb);
+                }
+                next_valid = false;
+                tile += tiles_here - 1;
+                continue;
+            }
+            gq_valid = false;
+        }
+        // ---- one tile: 4 one-byte rows per thread in one 32-bit word ----
+        const uint32_t tile_start = (tile - a.tile0) * PROBE_TILE;
+        const uint32_t npos = min((uint32_t)PROBE_TILE, a.nkmers - tile_start);
+        const uint32_t binlen = a.binlen, bin0 = tile_start / binlen, bin0_start = bin0 * binlen;
+        const uint64_t row0 = a.bin_off + bin0;
+        const bool onebin = (tile_start + npos) <= (bin0_start + binlen);  // block-uniform
+        const bool big = binlen >= (uint32_t)PROBE_TILE;                    // a tile spans at most 2 bins
+        const bool windowed = binlen >= MINBIN;                             // ... at most MAXB bins
+        const uint32_t last_rel = (tile_start + npos - 1 - bin0_start) / binlen;
+        // (bin - bin0) of a position for short bins: exact for pos - bin0_start < 2^16 > tile + bin
+        const uint32_t binv = big ? 0u : 0xFFFFFFFFu / binlen + 1u;
+        // The per-thread accumulators stand for the window's first bin, so a one-bin tile needs row0 == cur_row0.
+        const bool reg_tile = big && onebin;
+        const uint32_t rel_base = win.seat_tile(row0, last_rel, windowed, reg_tile, reduce_hist);
+        auto rel_of = [&](uint32_t pos) -> uint32_t {  // bin of a position of this tile, relative to bin0
+            const uint32_t dpos = pos - bin0_start;
+            return big ? (dpos >= binlen ? 1u : 0u) : __umulhi(dpos, binv);
+        };
+        const uint8_t *g = out1 + a.out_off + (uint64_t)tile_start;
+        if (windowed) {
+            uint32_t packed = 0;
+            if (next_valid) packed = next_packed;
+            else if (p0 + 3 < npos) packed = *reinterpret_cast<const uint32_t *>(g + p0);
+            else
+                for (uint32_t j = 0; j < 4; ++j)
+                    if (p0 + j < npos) packed |= (uint32_t)g[p0 + j] << (8 * j);
+            // prefetch: the next tile of the same contig is a full tile right behind this one
+            next_valid = (tile + 1 < t_end) && (npos == (uint32_t)PROBE_TILE) &&
+                         (tile_start + 2u * PROBE_TILE <= a.nkmers) && (tile_contig[tile + 1] == c);
+            if (next_valid) next_packed = *reinterpret_cast<const uint32_t *>(g + PROBE_TILE + p0);
+            const uint32_t nact = p0 < npos ? min(4u, npos - p0) : 0u;
+            if (want_cs) {  // bit g of the 4 rows = bits g, g+8, g+16, g+24 of the word
+#pragma unroll
+                for (int gb = 0; gb < 8; ++gb) cacc[gb] += __popc(packed & (0x01010101u << gb));
+            }
+            if (reg_tile) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t pcj = min((uint32_t)__popc((packed >> (8 * j)) & 0xFFu), N);
+                    if ((uint32_t)j < nact) hacc += 1ull << (7 * pcj);
+                }
+                if (++since_spill == 31) spill();
+            } else {  // the tile spans several bins: one LDS counter per (bin, popcount)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if ((uint32_t)j < nact)
+                        atomicAdd(&hist[(rel_base + rel_of(tile_start + p0 + j)) * (N + 1) +
+                                        min((uint32_t)__popc((packed >> (8 * j)) & 0xFFu), N)], 1u);
+            }
+            if (nact) {
+                const Hit100 h = hit100(tile_start + p0);
+                if (want100 && h.first < nact) out100[a.out100_off + h.r100] = (uint8_t)(packed >> (8 * h.first));
+            }
+        } else {
+            next_valid = false;
+            epi_tile_unwindowed<1, PT>(win, N, a, g, p0, npos, tile_start, bin0, bin0_start, rel_base, want100, want_cs, out100, cs, lane);
+        }
+    }
+    if (want_cs && cur_c != ~0u) contig_done(cur_c);
+    win.finish(reduce_hist);
+}
+
+// ---------------------------------------------------------------------------
+// Rows of 2..8 bytes (9..64 genomes), one or two words per row: one instantiation, and one register allocation, per width.
+// Column sums in two levels, all in registers until the very end —
+//  L1  the counter planes of pg_planes.h, per thread and word;
+//  L2  every PLANES_FLUSH rows the planes are transposed into byte counters, and a halving exchange over the wave
+//      leaves each total in one lane, which adds it to the workgroup's LDS counters.
+// (rows of 2 to 5 bytes: 6 waves per SIMD instead of the 4-5 their 96-106 VGPRs allowed — 12 x 60 Mb 0.578 -> 0.509 ms,
+// 20 x 40 Mb 0.647 -> 0.57, 27 x 40 Mb and 40 x 30 Mb 2-6 %; 8-byte rows lose with it, 1.95 -> 2.1-2.3 ms, and stay as they were)
+// ---------------------------------------------------------------------------
+#ifndef PG_EPI_WAVES1
+#define PG_EPI_WAVES1 6
+#endif
+template <int NBT>  // NBT = bytes per row (2..8)
+__global__ __launch_bounds__(EPI_THREADS, (NBT <= 5 ? PG_EPI_WAVES1 : 1))
+__attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue_n(uint32_t N, const AnchorDesc *__restrict__ ad,
+                                                            const uint32_t *__restrict__ tile_contig, uint32_t ntiles,
+                                                            const uint8_t *__restrict__ out1, uint8_t *__restrict__ out100,
+                                                            uint32_t *__restrict__ bins,
+                                                            unsigned long long *__restrict__ colsums, uint32_t flags,
+                                                            const uint2 *__restrict__ ranges, uint32_t wpr) {
+    static_assert(NBT >= 2 && NBT <= 8, "rows of 2..8 bytes");
+    extern __shared__ uint4 smem[];
+    constexpr int PT = 4;  // rows per thread and tile: EPI_THREADS = PROBE_TILE / 4 threads per workgroup
+    constexpr uint32_t nbytes = NBT;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const uint32_t ndbs = (N + 31) / 32;
+    // contiguous tile ranges, cut in units of the group path's 4 tiles (16 rows per thread)
+    EpiStart st = epi_prologue(smem, N, N, flags, bins, 4u, ntiles, ranges, wpr);
+    HistWindow &win = st.win;
+    uint32_t *const hist = win.hist, *const cs = st.cs;
+    const uint32_t MAXB = win.MAXB, MINBIN = win.MINBIN;
+    const bool want_cs = st.want_cs, want100 = st.want100;
+    const uint32_t t_begin = st.t_begin, t_end = st.t_end;
+    uint32_t cur_c = ~0u;
+    AnchorDesc a = st.a;
+    const uint32_t p0 = tid * PT;
+    uint4 wp_a = make_uint4(0, 0, 0, 0), wp_b = make_uint4(0, 0, 0, 0);  // software prefetch of the next tile's 4- / 8-byte rows
     bool wp_valid = false;
-    // wide path (8 < N <= 64): column sums in two levels, all in registers until the very end —
-    //  L1  per-thread VERTICAL counters: bit g of plane p is bit p of the number of rows seen with genome g set.  EIGHT bit
-    //      planes per word behind a Harley-Seal carry-save tree, as in k_epilogue_chunks: four rows enter the ones / twos
-    //      planes per call (9 instructions), their carry of weight 4 is held back every other call and enters the fours plane
-    //      with the next one (3), likewise the eights, and every 16 rows one carry ripples through the upper four planes (8):
-    //      3.3 instructions per row and word (profiles/r4e_ab_stats_harley_seal_mid.txt);
-    //  L2  every 240 rows the planes are transposed into byte counters, and a halving exchange over the wave (17 shuffles
-    //      per word) leaves each total in one lane, which adds it to the workgroup's LDS counters.
+    // This kernel keeps ITS OWN WORDING of two shared pieces, because its registers and scratch follow the parent's only so
+    // (profiles/stats_share_isa.txt): the flush of the planes below (through planes_flush_wave the loop nest of the exchange is
+    // compiled inside an always_inline function and comes out with R[] dynamically indexed: 3.7 -> 17.7 thousand VALU), and
+    // the unwindowed tile path at the bottom of the tile loop.  The planes are the three arrays Planes is a view of.
+    const uint32_t Nw = N;
     uint32_t vp[2][8] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}}, pf[2] = {0, 0}, pe[2] = {0, 0};
     uint32_t vrows = 0;  // rows in the planes (block-uniform, a multiple of 4): the carries held back follow from it
-    constexpr uint32_t VROWS_FLUSH = 240;
     auto ripple = [&](uint32_t (&p)[8], uint32_t cw, int q0) __attribute__((always_inline)) {
 #pragma unroll
         for (int q = 0; q < 8; ++q)
@@ -236,31 +753,10 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
             }
     };
     auto vadd4 = [&](int ws, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3) __attribute__((always_inline)) {
-        const bool odd4 = (vrows & 4u) != 0, odd8 = (vrows & 8u) != 0;  // (the caller advances vrows once all words of the four rows are in)
-        uint32_t (&p)[8] = vp[ws];
-        const uint32_t x = p[0];
-        const uint32_t t1 = x ^ r0, s1 = t1 ^ r1, ca = (t1 & r1) | (~t1 & x);      // x + r0 + r1
-        const uint32_t t2 = s1 ^ r2, s2 = t2 ^ r3, cb = (t2 & r3) | (~t2 & s1);    // .. + r2 + r3
-        p[0] = s2;
-        const uint32_t y = p[1];
-        const uint32_t t3 = y ^ ca, cc = (t3 & cb) | (~t3 & y);                     // twos + ca + cb -> a carry of weight 4
-        p[1] = t3 ^ cb;
-        if (!odd4) {
-            pf[ws] = cc;
-            return;
-        }
-        const uint32_t z = p[2], t4 = z ^ pf[ws], c8 = (t4 & cc) | (~t4 & z);      // fours + both carries -> weight 8
-        p[2] = t4 ^ cc;
-        if (!odd8) {
-            pe[ws] = c8;
-            return;
-        }
-        const uint32_t u = p[3], t5 = u ^ pe[ws], c16 = (t5 & c8) | (~t5 & u);     // eights + both carries -> weight 16
-        p[3] = t5 ^ c8;
-        ripple(p, c16, 4);
+        Planes(vp[ws], pf[ws], pe[ws]).add4(r0, r1, r2, r3, Planes::odd4(vrows), Planes::odd8(vrows));  // (the caller advances vrows once all words of the four rows are in)
     };
     auto vflush = [&]() {  // L1 -> L2, wave-uniform call sites only
-        const bool odd4 = (vrows & 4u) != 0, odd8 = (vrows & 8u) != 0;  // carries still held back (a flush between whole 16-row blocks)
+        const bool odd4 = Planes::odd4(vrows), odd8 = Planes::odd8(vrows);  // carries still held back (a flush between whole 16-row blocks)
         for (uint32_t ws = 0; ws < ndbs && ws < 2; ++ws) {
             if (odd4) ripple(vp[ws], pf[ws], 2);
             if (odd8) ripple(vp[ws], pe[ws], 3);
@@ -296,292 +792,22 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
         }
         vrows = 0;
     };
-    auto spill = [&]() {  // the per-tile path's classes (7-bit fields of hacc) join the thresholds: thr[i] += rows of class > i
-        uint32_t run = 0;
-#pragma unroll
-        for (int v = 8; v >= 1; --v) {
-            run += (uint32_t)(hacc >> (7 * v)) & 127u;
-            thr[v - 1] += run;
-        }
-        grows += run + ((uint32_t)hacc & 127u);
-        hacc = 0;
-        since_spill = 0;
+    auto contig_done = [&](uint32_t contig) {  // what the planes hold joins the LDS counters, those leave for the contig's sums
+        if (vrows) vflush();
+        flush_colsums(N, cs, colsums, contig, tid);
     };
-    auto reduce_hist = [&]() {  // per-thread thresholds -> classes -> LDS histogram (bin-relative row 0)
-        if constexpr (MODE != 0) return;
-        spill();
-        uint32_t hc[9];
-        hc[0] = grows - thr[0];
-#pragma unroll
-        for (int v = 1; v < 8; ++v) hc[v] = thr[v - 1] - thr[v];
-        hc[8] = thr[7];
-#pragma unroll
-        for (int v = 8; v >= 1; --v)  // (junk bits beyond ngenomes count as class N, as on the per-tile path)
-            if ((uint32_t)v > N) {
-                hc[v - 1] += hc[v];
-                hc[v] = 0;
-            }
-        grows = 0;
-#pragma unroll
-        for (int v = 0; v < 8; ++v) thr[v] = 0;
-#pragma unroll
-        for (int v = 0; v < 9; ++v)
-            if ((uint32_t)v <= N && hc[v]) lds_add_lanes(&hist[v], hc[v]);
-    };
-
-    // column sums are kept per contig (colsums[contig][N]): register / LDS accumulators are emptied
-    // whenever the workgroup's tile range moves on to another contig (block-uniform, rare)
-    auto flush_colsums = [&](uint32_t contig) {
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int gb = 0; gb < 8; ++gb) {
-                if ((uint32_t)gb < N && cacc[gb]) lds_add_lanes(&cs[gb], cacc[gb]);
-                cacc[gb] = 0;
-            }
-        }
-        if constexpr (WIDE) {
-            if (vrows) vflush();
-        }
-        __syncthreads();
-        for (uint32_t i = tid; i < N; i += EPI_THREADS) {
-            const uint32_t v = cs[i];
-            if (v) {
-                atomicAdd(&colsums[(uint64_t)contig * N + i], (unsigned long long)v);
-                cs[i] = 0;
-            }
-        }
-        __syncthreads();
-    };
-
-    // The group path of the 2..8-byte rows adds ONE to an LDS counter per row, and the lanes of a wave mostly ask for the
-    // same few counters (the popcount classes near N): the LDS works a wave's atomic off one lane per cycle and address —
-    // 0.9-1.0 ps per row whatever the row width, twice what 2-byte rows need otherwise.  While the groups lie inside one
-    // or two long bins (any contig of more than 200 kb) the window is therefore used as EPI_REPL copies of those two bin
-    // rows, lane l adding to copy l % EPI_REPL (copy c at c * repl_stride, an odd stride: the copies of one class sit in
-    // different banks); `unreplicate` folds the copies into the window's ordinary form — rows 0 and 1 — before anything
-    // else reads or flushes it.  `repl` is block-uniform.
-    constexpr uint32_t EPI_REPL = 8;  // (16 copies: no further gain, profiles/r3_ab_stats_hist_copies.txt)
-    const uint32_t repl_stride = (2u * (N + 1u)) | 1u;  // (EPI_REPL * repl_stride <= MAXB * (N + 1): MAXB >= 47 for N <= 64)
-    bool repl = false;
-    auto unreplicate = [&]() {
-        if constexpr (MODE != 1) return;
-        if (!repl) return;
-        __syncthreads();
-        for (uint32_t i = tid; i < 2u * (N + 1u); i += EPI_THREADS) {
-            uint32_t v = hist[i];
-#pragma unroll
-            for (uint32_t cpy = 1; cpy < EPI_REPL; ++cpy) {
-                v += hist[cpy * repl_stride + i];
-                hist[cpy * repl_stride + i] = 0;
-            }
-            hist[i] = v;
-        }
-        __syncthreads();
-        repl = false;
-    };
-    uint4 gq_next = make_uint4(0, 0, 0, 0), gq_next2 = make_uint4(0, 0, 0, 0);  // group path: prefetched rows of the next group
-    bool gq_valid = false;
-    // (one-byte rows) STREAK: whole one-bin groups known to follow the current one inside its bin, contig and tile range.  This
-    // pass is bound by its SCALAR instructions — a SIMD issues at most one per four cycles, and the block-uniform bookkeeping of
-    // a group (two tile_contig look-ups, six divisions by the bin length at 11 instructions each, the window checks) came to
-    // 330 of them against 195 vector instructions (100 dummy s_add per group: +0.07 ms on 8 x 10^8 rows, 100 dummy VALU: +0.04;
-    // profiles/r4e_stats_scalar_bound.txt).  Worked out ONCE when a group turns out whole and inside one bin; the groups of
-    // the streak then take nothing of that: same contig, same bin row, no window check, the next group's prefetch certain.
-    uint32_t streak = 0, nk_ba = 0, nk_bz = 0;
-    int nk_kind = 0;
     for (uint32_t tile = t_begin; tile < t_end; ++tile) {
-        uint32_t c = cur_c;
-        if (!(MODE == 0 && (streak || gq_valid))) {  // (a group the one before has announced lies in its contig)
-            c = tile_contig[tile];
-            if (c != cur_c) {  // block-uniform; consecutive tiles nearly always share their contig
-                if (want_cs && cur_c != ~0u) flush_colsums(cur_c);
-                a = ad[c];
-                cur_c = c;
-            }
+        const uint32_t c = tile_contig[tile];
+        if (c != cur_c) {  // block-uniform; consecutive tiles nearly always share their contig
+            if (want_cs && cur_c != ~0u) contig_done(cur_c);
+            a = ad[c];
+            cur_c = c;
         }
-        // ---- group path (N <= 8): 8 full tiles of one contig inside one bin = 32 one-byte rows per thread in two
-        // 16-byte loads, worked on BIT-SLICED: a three-stage butterfly between the 8 words regroups their 256 bits so
-        // that word g holds bit g of all 32 rows (same row, same bit position in every word: 4 instructions per word
-        // pair and stage); an 8-input sorting network on those planes (19 compare-exchanges = AND / OR pairs) turns
-        // them into thresholds "row has more than i bits"; popcounts of the planes are the column sums, popcounts of
-        // the thresholds the cumulative histogram.  3.2 instructions per row, where one-hot adds per row took 13 ----
-        // Two kinds of group: (1) all 4096 rows inside ONE bin — thresholds and rows counted in registers, reduced when the
-        // bin changes; (2) several bins (contigs of a few kb .. Mb have bins of nkmers / 100 rows): bins of at least 32
-        // rows, so that a thread's 32 rows meet at most one bin boundary, and all of the group's bins inside the LDS window —
-        // the thread splits its threshold popcounts at the boundary (a mask over the planes' bit positions) and adds the
-        // classes of its one or two bins to the window with up to 9 LDS atomics each, where the per-tile path does one per row.
-        // A group need not be whole: a contig's last tiles (and a workgroup's last ones) form a group of fewer rows — a thread
-        // then holds nv < 32 valid rows (possibly none) and masks the planes with the same kind of position mask.
-        if constexpr (MODE == 0) {
-            const uint32_t ts = (tile - a.tile0) * PROBE_TILE;
-            const uint32_t span = 8u * PROBE_TILE;
-            // rows of this contig from ts on that belong to this workgroup's tile range, at most a whole group's
-            auto rows_at = [&](uint32_t tl, uint32_t t0) -> uint32_t {  // (block-uniform)
-                if (tl >= t_end || tile_contig[tl] != c || t0 >= a.nkmers) return 0u;
-                return min(min(span, a.nkmers - t0), (t_end - tl) * (uint32_t)PROBE_TILE);
-            };
-            // (block-uniform) first and last bin of the rows [t0, t0 + rows) and the kind of group they make — 1: one bin, 2: several
-            // bins, 0: not a group
-            auto group_kind = [&](uint32_t t0, uint32_t rows, uint32_t &ba, uint32_t &bz) -> int {
-                if (rows == 0) return 0;
-                const uint32_t bl = a.binlen;
-                ba = t0 / bl;
-                bz = (t0 + rows - 1) / bl;
-                if (ba == bz) return 1;
-                return (bl >= 32u && bz - ba + 1u <= MAXB) ? 2 : 0;
-            };
-            const bool fast = streak != 0;  // (block-uniform) a group of a streak: whole, one bin, the bin of the group before
-            const bool known = !fast && gq_valid;  // the group before worked this one out (whole; nk_kind, nk_ba .. nk_bz) when it asked for its rows
-            uint32_t grows_n = span, ba = nk_ba, bz = nk_bz;
-            int kind = fast ? 1 : nk_kind;
-            if (fast) {
-                --streak;
-            } else if (!known) {
-                grows_n = rows_at(tile, ts);  // (>= 1: this tile has rows)
-                kind = group_kind(ts, grows_n, ba, bz);
-            }
-            if (kind != 0) {
-                uint64_t row0g = cur_row0;
-                if (!fast) {
-                    row0g = a.bin_off + ba;
-                    const uint32_t nbg = bz - ba + 1u;  // bins of the group
-                    const bool keep = cur_row0 != ~0ull && (kind == 1 ? row0g == cur_row0 : (row0g >= cur_row0 && row0g + nbg <= cur_row0 + MAXB));
-                    if (!keep) {
-                        if (cur_row0 != ~0ull) {
-                            reduce_hist();
-                            __syncthreads();
-                            flush_hist(N, hist, bins, cur_row0, tid, MAXB);
-                            __syncthreads();
-                        }
-                        cur_row0 = row0g;
-                    }
-                    if (kind == 1 && grows_n == span) {
-                        // whole groups from ts on that end inside this bin, this contig and this workgroup's range (this one included)
-                        const uint64_t bin_end = min((uint64_t)(ba + 1u) * a.binlen, (uint64_t)a.nkmers);
-                        streak = min((uint32_t)(bin_end - ts) / span, (t_end - tile) / 8u) - 1u;
-                    }
-                }
-                const uint32_t nv = 32u * tid < grows_n ? min(32u, grows_n - 32u * tid) : 0u;  // this thread's valid rows
-                // (a 16-byte load that begins on a valid row ends inside the contig's 16-byte padded region)
-                const uint4 *gg = reinterpret_cast<const uint4 *>(out1 + a.out_off + (uint64_t)ts + 32u * tid);
-                const uint4 z4 = make_uint4(0, 0, 0, 0);
-                const uint4 qa = gq_valid ? gq_next : (nv > 0u ? gg[0] : z4);
-                const uint4 qb = gq_valid ? gq_next2 : (nv > 16u ? gg[1] : z4);
-                // This group's rows are waited for HERE, before the next group's loads go out.  Left to the compiler the wait sat
-                // at the rows' first use — BEHIND the prefetch — and, the paths above having merged, as vmcnt(0): it waited for
-                // the prefetch as well, so that a group's load latency and its arithmetic ran one after the other (0.35 ms for
-                // 8 x 10^8 rows where a kernel of the same geometry that only loads and counts takes 0.19).
-                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), nothing else
-                // prefetch the next group when this one is whole and a whole group follows right behind
-                const uint32_t tiles_here = (grows_n + PROBE_TILE - 1) / PROBE_TILE;
-                gq_valid = streak != 0;
-                if (!gq_valid && grows_n == span && rows_at(tile + 8, ts + span) == span) {
-                    nk_kind = group_kind(ts + span, span, nk_ba, nk_bz);
-                    gq_valid = nk_kind != 0;
-                }
-                if (gq_valid) {
-                    gq_next = gg[span / 16u];
-                    gq_next2 = gg[span / 16u + 1];
-                }
-                uint32_t w[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-                const uint32_t pos0 = ts + 32u * tid;  // at most one multiple of 100 among 32 positions
-                const uint32_t r100 = (pos0 + 99u) / 100u;
-                const uint32_t first = r100 * 100u - pos0;
-                if (want100 && first < nv) {
-                    uint32_t sel = w[0];
-#pragma unroll
-                    for (uint32_t i = 1; i < 8; ++i) sel = (first >> 2) == i ? w[i] : sel;
-                    out100[a.out100_off + r100] = (uint8_t)(sel >> (8 * (first & 3)));
-                }
-#pragma unroll
-                for (int kb = 0; kb < 3; ++kb) {
-                    const uint32_t m0 = kb == 0 ? 0x55555555u : kb == 1 ? 0x33333333u : 0x0F0F0F0Fu;
-                    const int sh = 1 << kb;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        if (i & sh) continue;
-                        const uint32_t x = w[i], y = w[i | sh];
-                        w[i] = (x & m0) | ((y << sh) & ~m0);       // the pair's bits with bit kb of g clear
-                        w[i | sh] = ((x >> sh) & m0) | (y & ~m0);  // ... and set
-                    }
-                }
-                // row j = 4 * word + byte of the thread sits at bit 8 * byte + word of every plane: the rows below j
-                auto rows_below = [](uint32_t j) __attribute__((always_inline)) -> uint32_t {
-                    uint32_t m = 0;
-#pragma unroll
-                    for (uint32_t rb = 0; rb < 4; ++rb) {
-                        const uint32_t nw = j > rb ? min(8u, (j - rb + 3u) >> 2) : 0u;  // words whose byte rb is below row j
-                        m |= ((1u << nw) - 1u) << (8u * rb);
-                    }
-                    return m;
-                };
-                const bool whole = grows_n == span;  // (block-uniform)
-                const uint32_t mval = whole ? 0xFFFFFFFFu : rows_below(nv);
-                if (!whole) {
-#pragma unroll
-                    for (int gb = 0; gb < 8; ++gb) w[gb] &= mval;  // rows past the group hold whatever follows in memory
-                }
-                if (want_cs) {
-#pragma unroll
-                    for (int gb = 0; gb < 8; ++gb) cacc[gb] += __popc(w[gb]);
-                }
-                auto cx = [&](int i, int j) __attribute__((always_inline)) {
-                    const uint32_t lo = w[i] & w[j], hi = w[i] | w[j];
-                    w[i] = lo;
-                    w[j] = hi;
-                };
-                cx(0, 1), cx(2, 3), cx(4, 5), cx(6, 7);
-                cx(0, 2), cx(1, 3), cx(4, 6), cx(5, 7);
-                cx(1, 2), cx(5, 6), cx(0, 4), cx(3, 7);
-                cx(1, 5), cx(2, 6);
-                cx(1, 4), cx(3, 6);
-                cx(2, 4), cx(3, 5);
-                cx(3, 4);
-                if (kind == 1) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) thr[i] += __popc(w[7 - i]);  // ascending order: w[7] = any bit set
-                    grows += nv;
-                } else {
-                    // this thread's rows pos0 .. pos0 + nv - 1: bin of the first one (relative to the group's first bin) and
-                    // rows until the next bin boundary
-                    const uint32_t bl = a.binlen, bin0s = ba * bl, d0 = pos0 - bin0s;  // (ba = ts / bl)
-                    const uint32_t rel0 = bl >= span ? (d0 >= bl ? 1u : 0u) : __umulhi(d0, 0xFFFFFFFFu / bl + 1u);  // (d0 < 2^16)
-                    const uint32_t jb = min(nv, (rel0 + 1u) * bl - d0);  // valid rows of the first bin
-                    const uint32_t mlo = rows_below(jb);
-                    uint32_t *h0 = hist + ((uint32_t)(row0g - cur_row0) + rel0) * (N + 1);
-                    auto add_classes = [&](uint32_t *h, uint32_t mask, uint32_t rows) __attribute__((always_inline)) {
-                        uint32_t cl[9], above = rows;
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            const uint32_t t = (uint32_t)__popc(w[7 - i] & mask);  // rows of this bin with more than i bits
-                            cl[i] = above - t;
-                            above = t;
-                        }
-                        cl[8] = above;
-#pragma unroll
-                        for (int v = 8; v >= 1; --v)  // (junk bits beyond ngenomes count as class N)
-                            if ((uint32_t)v > N) {
-                                cl[v - 1] += cl[v];
-                                cl[v] = 0;
-                            }
-#pragma unroll
-                        for (int v = 0; v < 9; ++v)
-                            if ((uint32_t)v <= N && cl[v]) atomicAdd(&h[v], cl[v]);
-                    };
-                    if (jb) add_classes(h0, mlo, jb);
-                    if (jb < nv) add_classes(h0 + (N + 1), mval & ~mlo, nv - jb);
-                }
-                next_valid = false;
-                tile += tiles_here - 1;
-                continue;
-            }
-            gq_valid = false;
-        }
-        // ---- group path (2..8-byte rows): 4 full tiles of one contig inside one bin = 16 consecutive
+        // ---- group path: 4 full tiles of one contig inside one bin = 16 consecutive
         // rows per thread (4 x nbytes aligned words).  The per-tile bookkeeping (bin arithmetic, window
         // check, 1-in-100 search) is paid once per 16 rows instead of once per 4 — it was two thirds of
         // the instructions of this pass — and the histogram index needs no bin lookup ----
-        if constexpr (MODE == 1) {
+        {
             const uint32_t ts = (tile - a.tile0) * PROBE_TILE;
             const uint32_t span = 4u * PROBE_TILE;
             // (the group may span several bins — contigs under 20 Mb have bins of nkmers / 100 rows — as long as a bin holds
@@ -591,29 +817,7 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
                                 (nbg == 1u || (a.binlen >= 16u && nbg <= MAXB));
             if (grp_ok) {
                 const uint64_t row0g = a.bin_off + ts / a.binlen;
-                const bool want_repl = nbg <= 2u && EPI_REPL * repl_stride <= MAXB * (N + 1u);  // (block-uniform; the copies must fit the window: the last one would run into `cs` otherwise)
-                if (want_repl) {
-                    if (!(repl && row0g >= cur_row0 && row0g + nbg <= cur_row0 + 2u)) {
-                        if (cur_row0 != ~0ull) {
-                            unreplicate();
-                            __syncthreads();
-                            flush_hist(N, hist, bins, cur_row0, tid, MAXB);
-                            __syncthreads();
-                        }
-                        cur_row0 = row0g;
-                        repl = true;
-                    }
-                } else {
-                    unreplicate();
-                    if (cur_row0 == ~0ull || row0g < cur_row0 || row0g + nbg > cur_row0 + MAXB) {
-                        if (cur_row0 != ~0ull) {
-                            __syncthreads();
-                            flush_hist(N, hist, bins, cur_row0, tid, MAXB);
-                            __syncthreads();
-                        }
-                        cur_row0 = row0g;
-                    }
-                }
+                const bool copies = win.seat_group(row0g, nbg);
                 // this thread's 16 rows: bin of the first one (relative to the group's first bin) and rows until the boundary
                 uint32_t rel0 = 0, jb = 16;
                 if (nbg > 1u) {
@@ -621,48 +825,36 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
                     rel0 = bl >= span ? (d0 >= bl ? 1u : 0u) : __umulhi(d0, 0xFFFFFFFFu / bl + 1u);  // (d0 < 2^16)
                     jb = min(16u, (rel0 + 1u) * bl - d0);
                 }
-                uint32_t *hrow = hist + ((uint32_t)(row0g - cur_row0) + rel0) * (N + 1) + (want_repl ? ((uint32_t)lane % EPI_REPL) * repl_stride : 0u);
+                uint32_t *hrow = win.group_row(row0g, rel0, copies, lane);
                 const uint8_t *gt = out1 + a.out_off + ((uint64_t)ts + 16u * tid) * nbytes;
-                auto rows16 = [&](auto nbc) {
-                    constexpr int NB = decltype(nbc)::value;
+                auto rows16 = [&]() {
                     uint32_t raw[4][8];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) load_row_words<NB>(gt + q * 4 * NB, raw[q]);  // all 16 rows in flight
+                    for (int q = 0; q < 4; ++q) load_row_words<NBT>(gt + q * 4 * NBT, raw[q]);  // all 16 rows in flight
                     // (fewer in flight saves registers but measured slower: 2.6 / 2.74 / 2.78 ms at N=64 for 4 / 2 / 1
                     // groups ahead; requesting the NEXT group's rows as well costs a wave of occupancy: 2.2 vs 1.4 ms at N=27)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         uint32_t w0[4], w1[4];
-                        cut4_rows<NB>(raw[q], w0, w1);
+                        cut4_rows<NBT>(raw[q], w0, w1);
 #pragma unroll
                         for (int j = 0; j < 4; ++j)
                             atomicAdd(&hrow[((uint32_t)(4 * q + j) >= jb ? N + 1 : 0u) +
-                                            min((uint32_t)(__popc(w0[j]) + (NB > 4 ? __popc(w1[j]) : 0)), N)], 1u);
+                                            min((uint32_t)(__popc(w0[j]) + (NBT > 4 ? __popc(w1[j]) : 0)), N)], 1u);
                         if (want_cs) {
                             vadd4(0, w0[0], w0[1], w0[2], w0[3]);
-                            if (NB > 4) vadd4(1, w1[0], w1[1], w1[2], w1[3]);
+                            if (NBT > 4) vadd4(1, w1[0], w1[1], w1[2], w1[3]);
                             vrows += PT;
-                            if (vrows == VROWS_FLUSH) vflush();
+                            if (vrows == PLANES_FLUSH) vflush();
                         }
                     }
                 };
-                switch (nbytes) {  // block-uniform
-                    case 2: rows16(std::integral_constant<int, 2>{}); break;
-                    case 3: rows16(std::integral_constant<int, 3>{}); break;
-                    case 4: rows16(std::integral_constant<int, 4>{}); break;
-                    case 5: rows16(std::integral_constant<int, 5>{}); break;
-                    case 6: rows16(std::integral_constant<int, 6>{}); break;
-                    case 7: rows16(std::integral_constant<int, 7>{}); break;
-                    default: rows16(std::integral_constant<int, 8>{}); break;
-                }
-                // 1-in-100 rows: at most one multiple of 100 among 16 consecutive positions; its row is read
-                // again (a cache hit) rather than selected out of 16 register pairs
-                const uint32_t pos0 = ts + 16u * tid;
-                const uint32_t r100 = (pos0 + 99u) / 100u;
-                const uint32_t first = r100 * 100u - pos0;
-                if (want100 && first < 16u) {
-                    const uint8_t *pr = gt + first * nbytes;
-                    uint8_t *o100 = out100 + a.out100_off + (uint64_t)r100 * nbytes;
+                rows16();
+                // 1-in-100 rows: the row is read again (a cache hit) rather than selected out of 16 register pairs
+                const Hit100 h = hit100(ts + 16u * tid);
+                if (want100 && h.first < 16u) {
+                    const uint8_t *pr = gt + h.first * nbytes;
+                    uint8_t *o100 = out100 + a.out100_off + (uint64_t)h.r100 * nbytes;
                     for (uint32_t bb = 0; bb < nbytes; ++bb) o100[bb] = pr[bb];
                 }
                 wp_valid = false;
@@ -670,119 +862,62 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
                 continue;
             }
         }
-        unreplicate();  // (the per-tile paths read the window in its ordinary form)
+        // ---- one tile: the thread's four rows ----
+        win.unreplicate();  // (the per-tile paths read the window in its ordinary form)
         const uint32_t tile_start = (tile - a.tile0) * PROBE_TILE;
         const uint32_t npos = min((uint32_t)PROBE_TILE, a.nkmers - tile_start);
         const uint32_t binlen = a.binlen, bin0 = tile_start / binlen, bin0_start = bin0 * binlen;
         const uint64_t row0 = a.bin_off + bin0;
-        const bool onebin = (tile_start + npos) <= (bin0_start + binlen);  // block-uniform
-        const bool big = binlen >= (uint32_t)PROBE_TILE;                    // a tile spans at most 2 bins
-        const bool windowed = binlen >= MINBIN;                             // ... at most MAXB bins
+        const bool big = binlen >= (uint32_t)PROBE_TILE;  // a tile spans at most 2 bins
+        const bool windowed = binlen >= MINBIN;           // ... at most MAXB bins
         const uint32_t last_rel = (tile_start + npos - 1 - bin0_start) / binlen;
         // (bin - bin0) of a position for short bins: exact for pos - bin0_start < 2^16 > tile + bin
         const uint32_t binv = big ? 0u : 0xFFFFFFFFu / binlen + 1u;
-        // block-uniform: may this tile add to the LDS window as it stands?  The per-thread one-byte
-        // accumulators stand for the window's first bin, so a one-bin tile needs row0 == cur_row0.
-        const bool reg_tile = MODE == 0 && big && onebin;
-        const bool fits = cur_row0 != ~0ull && (reg_tile || !windowed ? row0 == cur_row0
-                                                : (row0 >= cur_row0 && row0 + last_rel < cur_row0 + MAXB));
-        if (!fits) {
-            if (cur_row0 != ~0ull) {
-                reduce_hist();
-                __syncthreads();
-                flush_hist(N, hist, bins, cur_row0, tid, MAXB);
-                __syncthreads();
-            }
-            cur_row0 = row0;
-        }
-        const uint32_t rel_base = (uint32_t)(row0 - cur_row0);
+        const uint32_t rel_base = win.seat_tile(row0, last_rel, windowed);
         auto rel_of = [&](uint32_t pos) -> uint32_t {  // bin of a position of this tile, relative to bin0
             const uint32_t dpos = pos - bin0_start;
             return big ? (dpos >= binlen ? 1u : 0u) : __umulhi(dpos, binv);
         };
         const uint8_t *g = out1 + a.out_off + (uint64_t)tile_start * nbytes;
-        if (MODE == 0 && windowed) {
-            // ---- fast path (N <= 8): 4 one-byte rows per thread in one 32-bit word ----
-            uint32_t packed = 0;
-            if (next_valid) packed = next_packed;
-            else if (p0 + 3 < npos) packed = *reinterpret_cast<const uint32_t *>(g + p0);
-            else
-                for (uint32_t j = 0; j < 4; ++j)
-                    if (p0 + j < npos) packed |= (uint32_t)g[p0 + j] << (8 * j);
-            // prefetch: the next tile of the same contig is a full tile right behind this one
-            next_valid = (tile + 1 < t_end) && (npos == (uint32_t)PROBE_TILE) &&
-                         (tile_start + 2u * PROBE_TILE <= a.nkmers) && (tile_contig[tile + 1] == c);
-            if (next_valid) next_packed = *reinterpret_cast<const uint32_t *>(g + PROBE_TILE + p0);
-            const uint32_t nact = p0 < npos ? min(4u, npos - p0) : 0u;
-            if (want_cs) {  // bit g of the 4 rows = bits g, g+8, g+16, g+24 of the word
-#pragma unroll
-                for (int gb = 0; gb < 8; ++gb) cacc[gb] += __popc(packed & (0x01010101u << gb));
-            }
-            if (reg_tile) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint32_t pcj = min((uint32_t)__popc((packed >> (8 * j)) & 0xFFu), N);
-                    if ((uint32_t)j < nact) hacc += 1ull << (7 * pcj);
-                }
-                if (++since_spill == 31) spill();
-            } else {  // the tile spans several bins: one LDS counter per (bin, popcount)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if ((uint32_t)j < nact)
-                        atomicAdd(&hist[(rel_base + rel_of(tile_start + p0 + j)) * (N + 1) +
-                                        min((uint32_t)__popc((packed >> (8 * j)) & 0xFFu), N)], 1u);
-            }
-            // 1-in-100 rows: at most one of 4 consecutive positions is a multiple of 100
-            if (nact) {
-                const uint32_t pos0 = tile_start + p0;
-                const uint32_t r100 = (pos0 + 99u) / 100u;
-                const uint32_t first = r100 * 100u;
-                if (want100 && first < pos0 + nact) out100[a.out100_off + r100] = (uint8_t)(packed >> (8 * (first - pos0)));
-            }
-        } else if (WIDE && windowed) {
-            // ---- wide path: the row bytes this launch sums, as one or two 32-bit words ----
-            next_valid = false;
+        if (windowed) {
+            // ---- the row bytes as one or two 32-bit words ----
             uint32_t w0[PT], w1[PT];
-            if (npos == (uint32_t)PROBE_TILE && (nbytes == 4 || nbytes == 8)) {  // (block-uniform) a full tile of 4- or 8-byte rows
-                // the thread's 4 rows are 16 / 32 aligned bytes.  The next tile's are requested before this
-                // tile is worked on when it is an equally regular one right behind: loads issued only when
-                // their tile starts leave the memory latency exposed (2.2-3.4 TB/s of the 6.3 a plain
-                // streaming read reaches with this geometry)
-                const bool two = nbytes == 8;
-                uint4 qa, qb = make_uint4(0, 0, 0, 0);
-                const uint8_t *g4 = g + (uint64_t)p0 * nbytes;
-                if (wp_valid) {
-                    qa = wp_a;
-                    qb = wp_b;
-                } else {
-                    qa = *reinterpret_cast<const uint4 *>(g4);
-                    if (two) qb = *reinterpret_cast<const uint4 *>(g4 + 16);
+            if (npos == (uint32_t)PROBE_TILE) {  // (block-uniform) a full tile
+                if constexpr (NBT == 4 || NBT == 8) {
+                    // the thread's 4 rows are 16 / 32 aligned bytes.  The next tile's are requested before this
+                    // tile is worked on when it is an equally regular one right behind: loads issued only when
+                    // their tile starts leave the memory latency exposed (2.2-3.4 TB/s of the 6.3 a plain
+                    // streaming read reaches with this geometry)
+                    constexpr bool two = NBT == 8;
+                    uint4 qa, qb = make_uint4(0, 0, 0, 0);
+                    const uint8_t *g4 = g + (uint64_t)p0 * nbytes;
+                    if (wp_valid) {
+                        qa = wp_a;
+                        qb = wp_b;
+                    } else {
+                        qa = *reinterpret_cast<const uint4 *>(g4);
+                        if (two) qb = *reinterpret_cast<const uint4 *>(g4 + 16);
+                    }
+                    wp_valid = (tile + 1 < t_end) && (tile_start + 2u * PROBE_TILE <= a.nkmers) && (tile_contig[tile + 1] == c);
+                    if (wp_valid) {
+                        const uint8_t *gn = g4 + (uint64_t)PROBE_TILE * nbytes;
+                        wp_a = *reinterpret_cast<const uint4 *>(gn);
+                        if (two) wp_b = *reinterpret_cast<const uint4 *>(gn + 16);
+                    }
+                    if (two) {
+                        w0[0] = qa.x; w1[0] = qa.y; w0[1] = qa.z; w1[1] = qa.w;
+                        w0[2] = qb.x; w1[2] = qb.y; w0[3] = qb.z; w1[3] = qb.w;
+                    } else {
+                        w0[0] = qa.x; w0[1] = qa.y; w0[2] = qa.z; w0[3] = qa.w;
+                        w1[0] = w1[1] = w1[2] = w1[3] = 0;
+                    }
+                } else {  // other widths: nbytes aligned words, rows cut out with static shifts
+                    wp_valid = false;
+                    uint32_t raw[8];
+                    load_row_words<NBT>(g + (uint64_t)p0 * nbytes, raw);
+                    cut4_rows<NBT>(raw, w0, w1);
                 }
-                wp_valid = (tile + 1 < t_end) && (tile_start + 2u * PROBE_TILE <= a.nkmers) && (tile_contig[tile + 1] == c);
-                if (wp_valid) {
-                    const uint8_t *gn = g4 + (uint64_t)PROBE_TILE * nbytes;
-                    wp_a = *reinterpret_cast<const uint4 *>(gn);
-                    if (two) wp_b = *reinterpret_cast<const uint4 *>(gn + 16);
-                }
-                if (two) {
-                    w0[0] = qa.x; w1[0] = qa.y; w0[1] = qa.z; w1[1] = qa.w;
-                    w0[2] = qb.x; w1[2] = qb.y; w0[3] = qb.z; w1[3] = qb.w;
-                } else {
-                    w0[0] = qa.x; w0[1] = qa.y; w0[2] = qa.z; w0[3] = qa.w;
-                    w1[0] = w1[1] = w1[2] = w1[3] = 0;
-                }
-            } else if (npos == (uint32_t)PROBE_TILE) {  // other widths: nbytes aligned words, rows cut out with static shifts
-                wp_valid = false;
-                const uint8_t *g4 = g + (uint64_t)p0 * nbytes;
-                uint32_t raw[8];
-                switch (nbytes) {  // block-uniform
-                    case 2: load_row_words<2>(g4, raw); cut4_rows<2>(raw, w0, w1); break;
-                    case 3: load_row_words<3>(g4, raw); cut4_rows<3>(raw, w0, w1); break;
-                    case 5: load_row_words<5>(g4, raw); cut4_rows<5>(raw, w0, w1); break;
-                    case 6: load_row_words<6>(g4, raw); cut4_rows<6>(raw, w0, w1); break;
-                    default: load_row_words<7>(g4, raw); cut4_rows<7>(raw, w0, w1); break;
-                }
-            } else {
+            } else {  // a contig's last tile: byte loads
                 wp_valid = false;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -794,25 +929,22 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
                 }
             }
             const uint32_t nact = p0 < npos ? min(4u, npos - p0) : 0u;
-            {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if ((uint32_t)j < nact) {
-                        const uint32_t pc = __popc(w0[j]) + __popc(w1[j]);
-                        atomicAdd(&hist[(rel_base + rel_of(tile_start + p0 + j)) * (N + 1) + min(pc, N)], 1u);
-                    }
+            for (int j = 0; j < 4; ++j) {
+                if ((uint32_t)j < nact) {
+                    const uint32_t pc = __popc(w0[j]) + __popc(w1[j]);
+                    atomicAdd(&hist[(rel_base + rel_of(tile_start + p0 + j)) * (N + 1) + min(pc, N)], 1u);
                 }
             }
-            if (nact) {  // 1-in-100 rows: at most one of 4 consecutive positions is a multiple of 100
-                const uint32_t pos0 = tile_start + p0;
-                const uint32_t r100 = (pos0 + 99u) / 100u;
-                const uint32_t jsel = r100 * 100u - pos0;
+            if (nact) {
+                const Hit100 h = hit100(tile_start + p0);
+                const uint32_t jsel = h.first;
                 if (want100 && jsel < nact) {
                     const uint32_t a0 = jsel == 0 ? w0[0] : jsel == 1 ? w0[1] : jsel == 2 ? w0[2] : w0[3];
                     const uint32_t a1 = jsel == 0 ? w1[0] : jsel == 1 ? w1[1] : jsel == 2 ? w1[2] : w1[3];
-                    uint8_t *o100 = out100 + a.out100_off + (uint64_t)r100 * nbytes;
-                    if (nbytes == 4) *reinterpret_cast<uint32_t *>(o100) = a0;
-                    else if (nbytes == 8) *reinterpret_cast<uint2 *>(o100) = make_uint2(a0, a1);
+                    uint8_t *o100 = out100 + a.out100_off + (uint64_t)h.r100 * nbytes;
+                    if constexpr (NBT == 4) *reinterpret_cast<uint32_t *>(o100) = a0;
+                    else if constexpr (NBT == 8) *reinterpret_cast<uint2 *>(o100) = make_uint2(a0, a1);
                     else {
                         const uint64_t r = (uint64_t)a0 | ((uint64_t)a1 << 32);
                         for (uint32_t bb = 0; bb < nbytes; ++bb) o100[bb] = (uint8_t)(r >> (8 * bb));
@@ -823,10 +955,10 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
                 vadd4(0, w0[0], w0[1], w0[2], w0[3]);
                 if (ndbs > 1) vadd4(1, w1[0], w1[1], w1[2], w1[3]);
                 vrows += PT;
-                if (vrows == VROWS_FLUSH) vflush();
+                if (vrows == PLANES_FLUSH) vflush();
             }
         } else {
-            next_valid = false;
+            // (epi_tile_unwindowed's text: called as a function it costs rows of 6..8 bytes a VGPR and moves the scratch of 3 and 5)
             const uint32_t ndbs_all = (N + 31) / 32;
 #pragma unroll
             for (int jj = 0; jj < PT; ++jj) {
@@ -851,15 +983,12 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
             }
         }
     }
-    if (want_cs && cur_c != ~0u) flush_colsums(cur_c);
-    unreplicate();
-    reduce_hist();
-    __syncthreads();
-    if (cur_row0 != ~0ull) flush_hist(N, hist, bins, cur_row0, tid, MAXB);
+    if (want_cs && cur_c != ~0u) contig_done(cur_c);
+    win.finish();
 }
 
 // ---------------------------------------------------------------------------
-// Rows wider than 8 bytes (more than 64 genomes): the same statistics CHUNK-PARALLEL.  A lane owns one
+// Rows wider than 16 bytes (more than 128 genomes): the same statistics CHUNK-PARALLEL.  A lane owns one
 // 16-byte chunk c of the rows it visits (C = ceil(nbytes / 16) consecutive lanes share a row, 64 / C
 // rows per wave and step; one 16-byte load per lane and row, contiguous over the wave, at whatever byte
 // alignment the row stride gives), so the per-row work (addressing, tail masking, histogram, the
@@ -868,8 +997,8 @@ __attribute__((amdgpu_num_sgpr(PG_EPI_SGPRS0))) void k_epilogue(uint32_t N, cons
 // instructions per word, 2.8 wave-instructions per 16-byte row, issue-bound at 2.7 TB/s.)
 //   popcount of a row   4 v_bcnt per lane, C - 1 shuffles to the row's first lane, one LDS atomic
 //   bitmap.100          each lane copies its chunk of the 1-in-100 rows
-//   column sums         carry-save vertical counters per word: eight bit planes behind a Harley-Seal
-//                       tree (4 rows at a time), LDS atomics every 240 rows, per contig to global
+//   column sums         the counter planes of pg_planes.h per word, per-lane LDS adds every PLANES_FLUSH rows, per contig
+//                       to global
 // EXACT: nbytes == 16 C (N a multiple of 128): aligned loads, no tail mask.
 // ---------------------------------------------------------------------------
 // (it runs 3-4 waves per SIMD on 104-149 VGPRs; round 4's first attempt to hold it to 5 or 6: 65-128 genomes 2.7-5.5 -> 5.0-13.9 ms,
@@ -903,93 +1032,26 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
         const uint32_t nb = vb > 4u * w ? min(4u, vb - 4u * w) : 0u;
         wm[w] = nb == 4 ? 0xFFFFFFFFu : (1u << (8 * nb)) - 1u;
     }
-    uint32_t *hist = reinterpret_cast<uint32_t *>(smem);
-    const uint32_t MAXB = max(EPI_MAXB, (flags >> 8) & 0xFFu), MINBIN = epi_minbin(MAXB);  // bins in the LDS window (launcher's choice)
-    uint32_t *cs = hist + ((MAXB * (N + 1) + 3) & ~3u);
-    for (uint32_t i = tid; i < MAXB * (N + 1); i += EPI_THREADS) hist[i] = 0;
-    for (uint32_t i = tid; i < K * cs_words; i += EPI_THREADS) cs[i] = 0;
+    EpiStart st = epi_prologue(smem, N, K * cs_words, flags, bins, 4u, ntiles, ranges, wpr);
+    HistWindow &win = st.win;
+    uint32_t *const hist = win.hist, *const cs = st.cs;
+    const uint32_t MAXB = win.MAXB, MINBIN = win.MINBIN;
     uint32_t *cs_mine = cs + ((uint32_t)lane / C / 16u) * cs_words + 128u * c;
-    __syncthreads();
-    const bool want_cs = (flags & 1u) != 0;
-    const bool want100 = (flags & 2u) == 0;
-    const EpiRange er = epi_range(4u, ntiles, ranges, wpr);
-    const uint32_t t_begin = er.begin, t_end = er.end;
-    uint64_t cur_row0 = ~0ull;
+    const bool want_cs = st.want_cs, want100 = st.want100;
+    const uint32_t t_begin = st.t_begin, t_end = st.t_end;
     uint32_t cur_c = ~0u;
-    AnchorDesc a;
-    a.out_off = a.out100_off = a.bin_off = 0;
-    a.nkmers = a.binlen = a.tile0 = a.nbins = 0;
-    // Column sums: per lane and word EIGHT bit planes of vertical counters (bit g of plane p = bit p of the number of rows seen
-    // with genome g set: up to 255 rows between flushes) fed through a Harley-Seal carry-save tree — four rows enter the
-    // ones / twos planes per iteration (9 instructions), their carry of weight 4 is held back every other iteration and
-    // enters the fours plane together with the next one (3), likewise the eights (3 per 8 rows), and only every 16 rows a
-    // carry ripples through the four upper planes (8): 3.3 instructions per row and word.  (Rounds 2-4 kept four planes,
-    // emptied every 12 rows into byte-sliced accumulators — 64 instructions per word — and those every 252 rows into LDS:
-    // 8.3 per row and word, a third of this pass's instructions, and 48 registers where this takes 40.)
-    uint32_t vp[4][8], pf[4], pe[4];
+    AnchorDesc a = st.a;
+    uint32_t vp[4][8], pf[4], pe[4];  // column sums of this lane's four words
 #pragma unroll
-    for (int w = 0; w < 4; ++w) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) vp[w][q] = 0;
-        pf[w] = pe[w] = 0;
-    }
+    for (int w = 0; w < 4; ++w) Planes(vp[w], pf[w], pe[w]).clear();
     uint32_t vrows = 0;  // rows in the planes (block-uniform, a multiple of 4): the carries held back follow from it
-    // add a word of carries of weight 2^q0 to the planes q0 .. 7 (no carry leaves plane 7: fewer than 256 rows)
-    auto ripple = [&](uint32_t (&p)[8], uint32_t cw, int q0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            if (q >= q0) {
-                const uint32_t n = p[q] & cw;
-                p[q] ^= cw;
-                cw = n;
-            }
-    };
-    auto vadd4 = [&](int w, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, bool odd4, bool odd8) __attribute__((always_inline)) {
-        uint32_t (&p)[8] = vp[w];
-        const uint32_t x = p[0];
-        const uint32_t t1 = x ^ r0, s1 = t1 ^ r1, ca = (t1 & r1) | (~t1 & x);      // x + r0 + r1
-        const uint32_t t2 = s1 ^ r2, s2 = t2 ^ r3, cb = (t2 & r3) | (~t2 & s1);    // .. + r2 + r3
-        p[0] = s2;
-        const uint32_t y = p[1];
-        const uint32_t t3 = y ^ ca, cc = (t3 & cb) | (~t3 & y);                     // twos + ca + cb -> a carry of weight 4
-        p[1] = t3 ^ cb;
-        if (!odd4) {  // (block-uniform) held back: the next four rows' carry joins it
-            pf[w] = cc;
-            return;
-        }
-        const uint32_t z = p[2], t4 = z ^ pf[w], c8 = (t4 & cc) | (~t4 & z);       // fours + both carries -> weight 8
-        p[2] = t4 ^ cc;
-        if (!odd8) {
-            pe[w] = c8;
-            return;
-        }
-        const uint32_t u = p[3], t5 = u ^ pe[w], c16 = (t5 & c8) | (~t5 & u);      // eights + both carries -> weight 16
-        p[3] = t5 ^ c8;
-        ripple(p, c16, 4);
-    };
     auto vflush = [&]() __attribute__((always_inline)) {  // planes -> the workgroup's LDS counters of this lane's words
-        const bool odd4 = (vrows & 4u) != 0, odd8 = (vrows & 8u) != 0;  // carries still held back (a flush between whole 16-row blocks)
+        const bool odd4 = Planes::odd4(vrows), odd8 = Planes::odd8(vrows);
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            if (odd4) ripple(vp[w], pf[w], 2);
-            if (odd8) ripple(vp[w], pe[w], 3);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {  // bits j, 8 + j, 16 + j, 24 + j of the word: their four counts as the bytes of v
-                uint32_t v = 0;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) v |= ((vp[w][q] >> j) & 0x01010101u) << q;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const uint32_t cnt = (v >> (8 * b)) & 255u;
-                    if (cnt) atomicAdd(&cs_mine[32 * w + 8 * b + j], cnt);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) vp[w][q] = 0;
-        }
+        for (int w = 0; w < 4; ++w) planes_flush_lanes(Planes(vp[w], pf[w], pe[w]), cs_mine + 32 * w, odd4, odd8);
         vrows = 0;
     };
-    auto flush_colsums = [&](uint32_t contig) __attribute__((always_inline)) {
+    auto flush_colsums_k = [&](uint32_t contig) __attribute__((always_inline)) {  // ... and the K copies of those -> the contig's sums
         if (vrows) vflush();
         __syncthreads();
         for (uint32_t i = tid; i < N; i += EPI_THREADS) {
@@ -1002,8 +1064,6 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
         }
         __syncthreads();
     };
-    struct __attribute__((packed)) U32 { uint32_t v; };
-    struct __attribute__((packed)) U128 { uint32_t x, y, z, w; };
     // popcount of a whole row from its lanes' chunks, valid (at least) in the row's first lane
     auto row_popc = [&](uint32_t pc) __attribute__((always_inline)) -> uint32_t {
         if (C_T == 2) return pc + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pc, 0xB1, 0xF, 0xF, false);  // quad_perm [1,0,3,2]
@@ -1045,8 +1105,6 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
     // per-tile state (block-uniform), set when an iteration starts a tile
     uint32_t tile_start = 0, npos = 0, binlen = 1, bin0 = 0, bin0_start = 0, binv = 0, rel_base = 0;
     bool big = false, windowed = false;
-    // (one LDS counter per row and (bin, class), the plain window: the histogram in several copies, k_epilogue's scheme, loses 3-6 %
-    // where only every second or third lane adds: profiles/r4e_ab_stats_hist_copies_wide.txt)
     for (uint32_t it = 0; it <= nit; ++it) {  // (one more round: the last contig's column sums, flushed at ONE site)
         const bool fin = it == nit;
         if (it + 1 < nit) issue(it + 1, vn);
@@ -1054,7 +1112,7 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
         if (r0 == 0) {
             const uint32_t cg = fin ? ~0u : tile_contig[tile];
             if (cg != cur_c) {
-                if (want_cs && cur_c != ~0u) flush_colsums(cur_c);
+                if (want_cs && cur_c != ~0u) flush_colsums_k(cur_c);
                 if (!fin) a = ad[cg];
                 cur_c = cg;
             }
@@ -1069,16 +1127,7 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
             windowed = binlen >= MINBIN;
             const uint32_t last_rel = (tile_start + npos - 1 - bin0_start) / binlen;
             binv = big ? 0u : 0xFFFFFFFFu / binlen + 1u;
-            const bool fits = cur_row0 != ~0ull && (!windowed ? row0 == cur_row0 : (row0 >= cur_row0 && row0 + last_rel < cur_row0 + MAXB));
-            if (!fits) {
-                if (cur_row0 != ~0ull) {
-                    __syncthreads();
-                    flush_hist(N, hist, bins, cur_row0, tid, MAXB);
-                    __syncthreads();
-                }
-                cur_row0 = row0;
-            }
-            rel_base = (uint32_t)(row0 - cur_row0);
+            rel_base = win.seat_tile(row0, last_rel, windowed);
         }
         if (r0 < npos) {  // (block-uniform)
             uint32_t *hrow = hist + rel_base * (N + 1);
@@ -1120,31 +1169,30 @@ __global__ __launch_bounds__(EPI_THREADS, PG_EPI_WAVESC) void k_epilogue_chunks(
                 }
             }
             if (want_cs) {  // rows beyond npos are zero: adding them is harmless
-                const bool odd4 = (vrows & 4u) != 0, odd8 = (vrows & 8u) != 0;
-                vadd4(0, v[0].x, v[1].x, v[2].x, v[3].x, odd4, odd8);
-                vadd4(1, v[0].y, v[1].y, v[2].y, v[3].y, odd4, odd8);
-                vadd4(2, v[0].z, v[1].z, v[2].z, v[3].z, odd4, odd8);
-                vadd4(3, v[0].w, v[1].w, v[2].w, v[3].w, odd4, odd8);
+                const bool odd4 = Planes::odd4(vrows), odd8 = Planes::odd8(vrows);
+                Planes(vp[0], pf[0], pe[0]).add4(v[0].x, v[1].x, v[2].x, v[3].x, odd4, odd8);
+                Planes(vp[1], pf[1], pe[1]).add4(v[0].y, v[1].y, v[2].y, v[3].y, odd4, odd8);
+                Planes(vp[2], pf[2], pe[2]).add4(v[0].z, v[1].z, v[2].z, v[3].z, odd4, odd8);
+                Planes(vp[3], pf[3], pe[3]).add4(v[0].w, v[1].w, v[2].w, v[3].w, odd4, odd8);
                 vrows += 4;
-                if (vrows == 240) vflush();  // (the 8 planes count to 255)
+                if (vrows == PLANES_FLUSH) vflush();
             }
         }
 #pragma unroll
         for (uint32_t j = 0; j < NJ; ++j) v[j] = vn[j];
     }
-    __syncthreads();
-    if (cur_row0 != ~0ull) flush_hist(N, hist, bins, cur_row0, tid, MAXB);
+    win.finish();
 }
 
 // ---------------------------------------------------------------------------
-// Rows of 9..16 bytes (65..128 genomes): k_epilogue's scheme for 2..8-byte rows at THREE or FOUR words per row.
+// Rows of 9..16 bytes (65..128 genomes): k_epilogue_n's scheme at THREE or FOUR words per row.
 // k_epilogue_chunks gives every row one lane and one (unaligned) 16-byte load whatever its width — ≈ 38 instructions per
 // row and lane, 4.1 ps per row at 9 bytes as at 16: the 65th genome paid for 128 (0.98 -> 2.68 ms for one more row byte).
 // Here a thread owns RPT consecutive rows of a group of full tiles (NBT aligned words per four rows, cut into rows with
 // static funnel shifts; RPT = 8, a group = two tiles: 16 rows per thread as for the narrower widths cost a wave of occupancy
 // and 2-7 %, profiles/r5g_ab_stats_w_rows.txt), the group's bookkeeping (bins, window, the 1-in-100 row) is paid once per group,
 // the histogram takes one LDS atomic per row (in 8 copies while the group lies inside one or two long bins), and the
-// column sums go through eight counter planes per word behind the Harley-Seal tree (3.3 instructions per row and word).
+// column sums go through the counter planes of pg_planes.h, one set per word.
 // Tiles that form no group — a contig's last ones, contigs of a few tiles, bins shorter than 16 rows — take the same
 // four rows per thread one tile at a time.  Reference: the per-bin histogram and rows of cpp/anchor.cpp:150-189,
 // index.py:1169-1183; column sums: index.py:1051,1068-1074.
@@ -1178,19 +1226,6 @@ __device__ __forceinline__ void cut4_rows_w(const uint32_t (&raw)[NB], uint32_t 
         }
     }
 }
-// one row of NBT bytes copied to the low-resolution bitmap: one unaligned 16-byte read (it may reach into the rows that follow, or
-// into the 16 bytes of slack every row buffer carries), whole words and the tail's bytes written
-template <int NBT>
-__device__ __forceinline__ void copy_row_w(const uint8_t *pr, uint8_t *o) {
-    struct __attribute__((packed)) U32 { uint32_t v; };
-    struct __attribute__((packed)) U128 { uint32_t x, y, z, w; };
-    const U128 t = *reinterpret_cast<const U128 *>(pr);
-    const uint32_t xw[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int w = 0; w < NBT / 4; ++w) reinterpret_cast<U32 *>(o + 4 * w)->v = xw[w];
-#pragma unroll
-    for (int bb = 0; bb < NBT % 4; ++bb) o[4 * (NBT / 4) + bb] = (uint8_t)(xw[(NBT / 4) & 3] >> (8 * bb));
-}
 template <int NBT>
 __global__ __launch_bounds__(EPI_THREADS, (NBT <= 12 ? PG_EPI_WAVESW12 : PG_EPI_WAVESW16)) void k_epilogue_w(uint32_t N, const AnchorDesc *__restrict__ ad,
                                                                           const uint32_t *__restrict__ tile_contig, uint32_t ntiles,
@@ -1206,136 +1241,30 @@ __global__ __launch_bounds__(EPI_THREADS, (NBT <= 12 ? PG_EPI_WAVESW12 : PG_EPI_
     constexpr uint32_t RPT = 4u * GQ;   // consecutive rows of a group per thread
     constexpr uint32_t nbytes = NBT;
     const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t Nw = N;
-    uint32_t *hist = reinterpret_cast<uint32_t *>(smem);
-    const uint32_t MAXB = max(EPI_MAXB, (flags >> 8) & 0xFFu), MINBIN = epi_minbin(MAXB);
-    uint32_t *cs = hist + ((MAXB * (N + 1) + 3) & ~3u);
-    for (uint32_t i = tid; i < MAXB * (N + 1); i += EPI_THREADS) hist[i] = 0;
-    for (uint32_t i = tid; i < N; i += EPI_THREADS) cs[i] = 0;
-    __syncthreads();
-    const bool want_cs = (flags & 1u) != 0;
-    const bool want100 = (flags & 2u) == 0;
-    const EpiRange er = epi_range(4u, ntiles, ranges, wpr);
-    const uint32_t t_begin = er.begin, t_end = er.end;
-    uint64_t cur_row0 = ~0ull;
+    EpiStart st = epi_prologue(smem, N, N, flags, bins, 4u, ntiles, ranges, wpr);
+    HistWindow &win = st.win;
+    uint32_t *const hist = win.hist, *const cs = st.cs;
+    const uint32_t MAXB = win.MAXB, MINBIN = win.MINBIN;
+    const bool want_cs = st.want_cs, want100 = st.want100;
+    const uint32_t t_begin = st.t_begin, t_end = st.t_end;
     uint32_t cur_c = ~0u;
-    AnchorDesc a;
-    a.out_off = a.out100_off = a.bin_off = 0;
-    a.nkmers = a.binlen = a.tile0 = a.nbins = 0;
+    AnchorDesc a = st.a;
     const uint32_t p0 = tid * PT;
-    // ---- column sums: eight counter planes per word behind a Harley-Seal tree (as k_epilogue, rows of 2..8 bytes) ----
-    uint32_t vp[NW][8], pf[NW], pe[NW];
+    uint32_t vp[NW][8], pf[NW], pe[NW];  // column sums, one set of planes per word
 #pragma unroll
-    for (int w = 0; w < NW; ++w) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) vp[w][q] = 0;
-        pf[w] = pe[w] = 0;
-    }
+    for (int w = 0; w < NW; ++w) Planes(vp[w], pf[w], pe[w]).clear();
     uint32_t vrows = 0;  // rows in the planes (block-uniform, a multiple of 4)
-    auto ripple = [&](uint32_t (&p)[8], uint32_t cw, int q0) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            if (q >= q0) {
-                const uint32_t n = p[q] & cw;
-                p[q] ^= cw;
-                cw = n;
-            }
-    };
-    auto vadd4 = [&](uint32_t (&p)[8], uint32_t &pfw, uint32_t &pew, const uint32_t (&r)[4], bool odd4, bool odd8) __attribute__((always_inline)) {
-        const uint32_t x = p[0];
-        const uint32_t t1 = x ^ r[0], s1 = t1 ^ r[1], ca = (t1 & r[1]) | (~t1 & x);      // x + r0 + r1
-        const uint32_t t2 = s1 ^ r[2], s2 = t2 ^ r[3], cb = (t2 & r[3]) | (~t2 & s1);    // .. + r2 + r3
-        p[0] = s2;
-        const uint32_t y = p[1];
-        const uint32_t t3 = y ^ ca, cc = (t3 & cb) | (~t3 & y);                           // twos + ca + cb -> a carry of weight 4
-        p[1] = t3 ^ cb;
-        if (!odd4) {
-            pfw = cc;
-            return;
-        }
-        const uint32_t z = p[2], t4 = z ^ pfw, c8 = (t4 & cc) | (~t4 & z);               // fours + both carries -> weight 8
-        p[2] = t4 ^ cc;
-        if (!odd8) {
-            pew = c8;
-            return;
-        }
-        const uint32_t u = p[3], t5 = u ^ pew, c16 = (t5 & c8) | (~t5 & u);              // eights + both carries -> weight 16
-        p[3] = t5 ^ c8;
-        ripple(p, c16, 4);
-    };
     auto vadd_rows = [&](const uint32_t (&w)[NW][4]) __attribute__((always_inline)) {  // four rows into the planes of every word
-        const bool odd4 = (vrows & 4u) != 0, odd8 = (vrows & 8u) != 0;
+        const bool odd4 = Planes::odd4(vrows), odd8 = Planes::odd8(vrows);
 #pragma unroll
-        for (int t = 0; t < NW; ++t) vadd4(vp[t], pf[t], pe[t], w[t], odd4, odd8);
+        for (int t = 0; t < NW; ++t) Planes(vp[t], pf[t], pe[t]).add4(w[t][0], w[t][1], w[t][2], w[t][3], odd4, odd8);
         vrows += PT;
     };
     auto vflush = [&]() __attribute__((always_inline)) {  // planes -> the workgroup's LDS counters: ONE (wave-uniform) call site, at the top of the tile loop
-        const bool odd4 = (vrows & 4u) != 0, odd8 = (vrows & 8u) != 0;
+        const bool odd4 = Planes::odd4(vrows), odd8 = Planes::odd8(vrows);
 #pragma unroll
-        for (int ws = 0; ws < NW; ++ws) {
-            if (odd4) ripple(vp[ws], pf[ws], 2);
-            if (odd8) ripple(vp[ws], pe[ws], 3);
-            uint32_t R[16];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {  // byte b of v counts genome 32 ws + 8 b + q (up to 255 rows)
-                uint32_t v = 0;
-#pragma unroll
-                for (int pl = 0; pl < 8; ++pl) v |= ((vp[ws][pl] >> q) & 0x01010101u) << pl;
-                R[2 * q] = v & 0x00FF00FFu;
-                R[2 * q + 1] = (v >> 8) & 0x00FF00FFu;
-            }
-#pragma unroll
-            for (int pl = 0; pl < 8; ++pl) vp[ws][pl] = 0;
-#pragma unroll
-            for (int half = 8, bit = 32; half >= 1; half >>= 1, bit >>= 1) {
-                const bool up = (lane & bit) != 0;
-#pragma unroll
-                for (int i = 0; i < half; ++i) {
-                    const uint32_t send = up ? R[i] : R[i + half];
-                    const uint32_t keep = up ? R[i + half] : R[i];
-                    R[i] = keep + (uint32_t)__shfl_xor((int)send, bit);
-                }
-            }
-            R[0] += (uint32_t)__shfl_xor((int)R[0], 2);
-            R[0] += (uint32_t)__shfl_xor((int)R[0], 1);
-            if ((lane & 3) == 0) {  // this lane holds register (lane >> 2): q = idx / 2, odd idx = bytes 1 and 3
-                const uint32_t idx = (uint32_t)lane >> 2;
-                const uint32_t g0 = 32 * ws + (idx >> 1) + ((idx & 1) ? 8u : 0u);
-                if (g0 < Nw && (R[0] & 0xFFFFu)) atomicAdd(&cs[g0], R[0] & 0xFFFFu);
-                if (g0 + 16 < Nw && (R[0] >> 16)) atomicAdd(&cs[g0 + 16], R[0] >> 16);
-            }
-        }
+        for (int ws = 0; ws < NW; ++ws) planes_flush_wave(Planes(vp[ws], pf[ws], pe[ws]), ws, N, cs, lane, odd4, odd8);
         vrows = 0;
-    };
-    auto flush_colsums = [&](uint32_t contig) __attribute__((always_inline)) {  // (one call site)
-        __syncthreads();
-        for (uint32_t i = tid; i < N; i += EPI_THREADS) {
-            const uint32_t v = cs[i];
-            if (v) {
-                atomicAdd(&colsums[(uint64_t)contig * N + i], (unsigned long long)v);
-                cs[i] = 0;
-            }
-        }
-        __syncthreads();
-    };
-    // ---- the histogram window as EPI_REPL copies of two bin rows while the groups lie inside one or two long bins ----
-    constexpr uint32_t EPI_REPL = 8;
-    const uint32_t repl_stride = (2u * (N + 1u)) | 1u;  // (8 copies need 16 (N + 1) + 8 words: they fit from MAXB = 17 on — epi_maxb_for gives >= 23 for N <= 128; want_repl checks)
-    bool repl = false;
-    auto unreplicate = [&]() __attribute__((always_inline)) {
-        if (!repl) return;
-        __syncthreads();
-        for (uint32_t i = tid; i < 2u * (N + 1u); i += EPI_THREADS) {
-            uint32_t v = hist[i];
-#pragma unroll
-            for (uint32_t cpy = 1; cpy < EPI_REPL; ++cpy) {
-                v += hist[cpy * repl_stride + i];
-                hist[cpy * repl_stride + i] = 0;
-            }
-            hist[i] = v;
-        }
-        __syncthreads();
-        repl = false;
     };
     auto popc_row = [&](const uint32_t (&w)[NW][4], int j) __attribute__((always_inline)) -> uint32_t {
         uint32_t pc = (uint32_t)__popc(w[0][j]);
@@ -1346,11 +1275,11 @@ __global__ __launch_bounds__(EPI_THREADS, (NBT <= 12 ? PG_EPI_WAVESW12 : PG_EPI_
     for (uint32_t tile = t_begin; tile <= t_end; ++tile) {  // (one more round: the last contig's column sums leave at the one site)
         const bool fin = tile >= t_end;
         const uint32_t c = fin ? ~0u : tile_contig[tile];
-        // the planes count to 255 rows and a group brings 16: emptied here when they could not take another group, and when
-        // the range moves on to another contig (column sums are kept per contig)
-        if (want_cs && vrows && (vrows + RPT > 255u || c != cur_c)) vflush();
+        // the planes count to PLANES_CEIL rows and a group brings RPT: emptied here when they could not take another group, and
+        // when the range moves on to another contig (column sums are kept per contig)
+        if (want_cs && vrows && (vrows + RPT > PLANES_CEIL || c != cur_c)) vflush();
         if (c != cur_c) {  // block-uniform
-            if (want_cs && cur_c != ~0u) flush_colsums(cur_c);
+            if (want_cs && cur_c != ~0u) flush_colsums(N, cs, colsums, cur_c, tid);
             if (!fin) a = ad[c];
             cur_c = c;
         }
@@ -1364,36 +1293,14 @@ __global__ __launch_bounds__(EPI_THREADS, (NBT <= 12 ? PG_EPI_WAVESW12 : PG_EPI_
                                 (nbg == 1u || (a.binlen >= RPT && nbg <= MAXB));
             if (grp_ok) {
                 const uint64_t row0g = a.bin_off + ts / a.binlen;
-                const bool want_repl = nbg <= 2u && EPI_REPL * repl_stride <= MAXB * (N + 1u);  // (block-uniform; the copies must fit the window: the last one would run into `cs` otherwise)
-                if (want_repl) {
-                    if (!(repl && row0g >= cur_row0 && row0g + nbg <= cur_row0 + 2u)) {
-                        if (cur_row0 != ~0ull) {
-                            unreplicate();
-                            __syncthreads();
-                            flush_hist(N, hist, bins, cur_row0, tid, MAXB);
-                            __syncthreads();
-                        }
-                        cur_row0 = row0g;
-                        repl = true;
-                    }
-                } else {
-                    unreplicate();
-                    if (cur_row0 == ~0ull || row0g < cur_row0 || row0g + nbg > cur_row0 + MAXB) {
-                        if (cur_row0 != ~0ull) {
-                            __syncthreads();
-                            flush_hist(N, hist, bins, cur_row0, tid, MAXB);
-                            __syncthreads();
-                        }
-                        cur_row0 = row0g;
-                    }
-                }
+                const bool copies = win.seat_group(row0g, nbg);
                 uint32_t rel0 = 0, jb = RPT;  // bin of the thread's first row (relative to the group's first bin), rows until the boundary
                 if (nbg > 1u) {
                     const uint32_t bl = a.binlen, d0 = ts + RPT * tid - (ts / bl) * bl;
                     rel0 = bl >= span ? (d0 >= bl ? 1u : 0u) : __umulhi(d0, 0xFFFFFFFFu / bl + 1u);  // (d0 < 2^16)
                     jb = min(RPT, (rel0 + 1u) * bl - d0);
                 }
-                uint32_t *hrow = hist + ((uint32_t)(row0g - cur_row0) + rel0) * (N + 1) + (want_repl ? ((uint32_t)lane % EPI_REPL) * repl_stride : 0u);
+                uint32_t *hrow = win.group_row(row0g, rel0, copies, lane);
                 const uint8_t *gt = out1 + a.out_off + ((uint64_t)ts + RPT * tid) * nbytes;
                 uint32_t raw[GQ][NBT];
 #pragma unroll
@@ -1409,17 +1316,15 @@ __global__ __launch_bounds__(EPI_THREADS, (NBT <= 12 ? PG_EPI_WAVESW12 : PG_EPI_
                     for (int j = 0; j < 4; ++j) atomicAdd(&hrow[((uint32_t)(4 * q + j) >= jb ? N + 1 : 0u) + popc_row(w, j)], 1u);
                     if (want_cs) vadd_rows(w);
                 }
-                // 1-in-100 rows: at most one multiple of 100 among 16 consecutive positions; its row is read again (a cache hit)
-                const uint32_t pos0 = ts + RPT * tid;
-                const uint32_t r100 = (pos0 + 99u) / 100u;
-                const uint32_t first = r100 * 100u - pos0;
-                if (want100 && first < RPT) copy_row_w<NBT>(gt + first * nbytes, out100 + a.out100_off + (uint64_t)r100 * nbytes);
+                // 1-in-100 rows: the row is read again (a cache hit)
+                const Hit100 h = hit100(ts + RPT * tid);
+                if (want100 && h.first < RPT) copy_row_w<NBT>(gt + h.first * nbytes, out100 + a.out100_off + (uint64_t)h.r100 * nbytes);
                 tile += GQ - 1;
                 continue;
             }
         }
         // ---- one tile: the thread's four rows ----
-        unreplicate();
+        win.unreplicate();
         const uint32_t tile_start = (tile - a.tile0) * PROBE_TILE;
         const uint32_t npos = min((uint32_t)PROBE_TILE, a.nkmers - tile_start);
         const uint32_t binlen = a.binlen, bin0 = tile_start / binlen, bin0_start = bin0 * binlen;
@@ -1428,16 +1333,7 @@ __global__ __launch_bounds__(EPI_THREADS, (NBT <= 12 ? PG_EPI_WAVESW12 : PG_EPI_
         const bool windowed = binlen >= MINBIN;           // ... at most MAXB bins
         const uint32_t last_rel = (tile_start + npos - 1 - bin0_start) / binlen;
         const uint32_t binv = big ? 0u : 0xFFFFFFFFu / binlen + 1u;
-        const bool fits = cur_row0 != ~0ull && (!windowed ? row0 == cur_row0 : (row0 >= cur_row0 && row0 + last_rel < cur_row0 + MAXB));
-        if (!fits) {
-            if (cur_row0 != ~0ull) {
-                __syncthreads();
-                flush_hist(N, hist, bins, cur_row0, tid, MAXB);
-                __syncthreads();
-            }
-            cur_row0 = row0;
-        }
-        const uint32_t rel_base = (uint32_t)(row0 - cur_row0);
+        const uint32_t rel_base = win.seat_tile(row0, last_rel, windowed);
         const uint8_t *g = out1 + a.out_off + (uint64_t)tile_start * nbytes;
         const uint32_t nact = p0 < npos ? min(4u, npos - p0) : 0u;
         uint32_t w[NW][4];
@@ -1474,17 +1370,13 @@ __global__ __launch_bounds__(EPI_THREADS, (NBT <= 12 ? PG_EPI_WAVESW12 : PG_EPI_
                 hist_position((uint32_t)j < nact, pos, pc, N, binlen, bin0, bin0_start, rel_base, hist, bins, a.bin_off, lane, MAXB);
             }
         }
-        if (nact) {  // 1-in-100 rows: at most one of 4 consecutive positions is a multiple of 100
-            const uint32_t pos0 = tile_start + p0;
-            const uint32_t r100 = (pos0 + 99u) / 100u;
-            const uint32_t jsel = r100 * 100u - pos0;
-            if (want100 && jsel < nact) copy_row_w<NBT>(g + (uint64_t)(p0 + jsel) * nbytes, out100 + a.out100_off + (uint64_t)r100 * nbytes);
+        if (nact) {
+            const Hit100 h = hit100(tile_start + p0);
+            if (want100 && h.first < nact) copy_row_w<NBT>(g + (uint64_t)(p0 + h.first) * nbytes, out100 + a.out100_off + (uint64_t)h.r100 * nbytes);
         }
         if (want_cs) vadd_rows(w);  // (rows beyond npos are zero — a partial tile's words are built that way: adding them is harmless)
     }
-    unreplicate();
-    __syncthreads();
-    if (cur_row0 != ~0ull) flush_hist(N, hist, bins, cur_row0, tid, MAXB);
+    win.finish();
 }
 
 // ---------------------------------------------------------------------------
@@ -1786,23 +1678,26 @@ hipError_t launch_rows_epilogue(hipStream_t st, uint32_t ngenomes, const AnchorD
         }
         if (grid > it->second) grid = it->second;
     };
+    auto launch = [&](decltype(&k_epilogue_b1) kern, size_t lds_bytes) {
+        fit(reinterpret_cast<const void *>(kern), lds_bytes);
+        per_range();
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(EPI_THREADS), lds_bytes, st, ngenomes, ad, tile_contig, ntiles, out1, out100, bins,
+                           colsums, flags, d_ranges, wpr);
+    };
     const uint32_t nbytes = (ngenomes + 7) / 8;
     if (nbytes <= 8) {
-        auto kern = k_epilogue<0, 1>;
+        auto kern = k_epilogue_b1;
         switch (nbytes) {
-            case 2: kern = k_epilogue<1, 2>; break;
-            case 3: kern = k_epilogue<1, 3>; break;
-            case 4: kern = k_epilogue<1, 4>; break;
-            case 5: kern = k_epilogue<1, 5>; break;
-            case 6: kern = k_epilogue<1, 6>; break;
-            case 7: kern = k_epilogue<1, 7>; break;
-            case 8: kern = k_epilogue<1, 8>; break;
+            case 2: kern = k_epilogue_n<2>; break;
+            case 3: kern = k_epilogue_n<3>; break;
+            case 4: kern = k_epilogue_n<4>; break;
+            case 5: kern = k_epilogue_n<5>; break;
+            case 6: kern = k_epilogue_n<6>; break;
+            case 7: kern = k_epilogue_n<7>; break;
+            case 8: kern = k_epilogue_n<8>; break;
             default: break;
         }
-        fit(reinterpret_cast<const void *>(kern), lds);
-        per_range();
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(EPI_THREADS), lds, st, ngenomes, ad, tile_contig, ntiles, out1, out100, bins,
-                           colsums, flags, d_ranges, wpr);
+        launch(kern, lds);
     }
     else if (nbytes <= 16) {  // 65..128 genomes: 16 rows per thread, three or four words per row
         auto kern = k_epilogue_w<16>;
@@ -1816,10 +1711,7 @@ hipError_t launch_rows_epilogue(hipStream_t st, uint32_t ngenomes, const AnchorD
             case 15: kern = k_epilogue_w<15>; break;
             default: break;
         }
-        fit(reinterpret_cast<const void *>(kern), lds);
-        per_range();
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(EPI_THREADS), lds, st, ngenomes, ad, tile_contig, ntiles, out1, out100, bins,
-                           colsums, flags, d_ranges, wpr);
+        launch(kern, lds);
     }
     else {  // more than 128 genomes, chunk-parallel: one launch, every row read once
         const uint32_t C = (nbytes + 15) / 16;  // (>= 2)
@@ -1833,10 +1725,7 @@ hipError_t launch_rows_epilogue(hipStream_t st, uint32_t ngenomes, const AnchorD
             case 4: kern = exact ? k_epilogue_chunks<4, true> : k_epilogue_chunks<4, false>; break;
             default: break;
         }
-        fit(reinterpret_cast<const void *>(kern), lds_c);
-        per_range();
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(EPI_THREADS), lds_c, st, ngenomes, ad, tile_contig, ntiles, out1, out100, bins,
-                           colsums, flags, d_ranges, wpr);
+        launch(kern, lds_c);
     }
     return hipGetLastError();
 }

@@ -1,4 +1,4 @@
-"""The statistics pass over one-byte rows (k_epilogue<0,1>, N <= 8 genomes) against the oracle: bitmap.100 rows, bins
+"""The statistics pass over one-byte rows (k_epilogue_b1, N <= 8 genomes) against the oracle: bitmap.100 rows, bins
 and per-contig column sums, for every path the pass takes — whole one-bin groups (streaks), groups across several short
 bins, bins shorter than a tile (the per-tile path), contigs that end inside a group, thousands of contigs of less than a
 tile (a workgroup's range crosses many of them), a run in chunks (PG_RUN_CHUNKS: launches over tile ranges), column sums

@@ -5,7 +5,7 @@ not zero — at every row width.  The references are the plain numpy restatement
 oracle.pyoracle.window_stats and tests/intros_ref.bitmap_to_bins (tests/test_rows_craft_cpu.py); every comparison is exact.
 
 Which kernel runs for which N (bytes per row = ceil(N / 8)):
-  rows_epilogue   1 byte k_epilogue<0,1>; 2..8 bytes k_epilogue<1,2..8>; 9..16 bytes k_epilogue_w<9..16>; 17 bytes (N = 130)
+  rows_epilogue   1 byte k_epilogue_b1; 2..8 bytes k_epilogue_n<2..8>; 9..16 bytes k_epilogue_w<9..16>; 17 bytes (N = 130)
                   k_epilogue_chunks<2,false>; 38 bytes (N = 300) k_epilogue_chunks<3,false>; 65 bytes (N = 520)
                   k_epilogue_chunks<0,false>; k_lowres with lowres_step=7
   window_stats    k_window_stats

@@ -2,7 +2,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -o tools/stream_bench tools/stream_bench.hip && tools/stream_bench
 // A: grid-stride, 16 B per lane, fully coalesced (what the memory system can do)
 // B: 128-thread workgroups walk contiguous ranges (RANGE bytes each), lane t reads 4 x 8 B at
-//    32 t + 8 j per 4 KB step (k_epilogue<1> on 8-byte rows)
+//    32 t + 8 j per 4 KB step (k_epilogue_n<8>, 8-byte rows)
 // C: same ranges, lane t reads 8 B at 8 t + 1024 j (rows t, t + 128, ...: coalesced per instruction)
 // D: same ranges, 16 B per lane coalesced, 2 KB per step
 #include <hip/hip_runtime.h>
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(128) void kP(const uint8_t *p, uint64_t range, uint
 
 // the one-byte statistics pass's geometry: a PERSISTENT grid of 128-thread workgroups over contiguous ranges of a 0.8 GB
 // buffer, lane t reads 2 x 16 B at 32 t per 4 KB step, DEPTH - 1 steps ahead in registers; the grid sets the resident
-// waves (3072 workgroups = 6 waves per SIMD, k_epilogue<0>'s occupancy)
+// waves (3072 workgroups = 6 waves per SIMD, k_epilogue_b1's occupancy)
 template <int DEPTH>
 __global__ __launch_bounds__(128) void kE(const uint8_t *p, uint64_t bytes, uint32_t *out) {
     const uint64_t steps = bytes / 4096;

@@ -479,6 +479,61 @@ int pg_result_absence_runs(pg_result *r, int step, uint32_t stride, uint32_t nwi
                            uint64_t cap, uint32_t *run_genome, uint32_t *run_start, uint32_t *run_rows,
                            uint64_t *hist_out, uint64_t *absent_out, uint64_t *edge_out,
                            uint64_t *nruns_out, uint64_t *total_out);
+/* synteny: WHERE in genome B does the k-mer at a position of genome A lie?  The bitmap rows say whether B holds it; nothing in
+ * the reference says where (scripts/pairwise_comp.py stops at per-genome column sums).  These calls work on two sequence sets,
+ * the sides A (0) and B (1), and on these definitions:
+ *   position  of a k-mer of a side: the global base offset of its first base in the concatenation of the side's contigs (the
+ *             offset of contig c = the lengths of the contigs before it).  Windows holding a non-ACGT byte do not exist, contigs
+ *             shorter than k have none.
+ *   key, rc   the canonical k-mer, and rc = 1 when the forward value is greater than the reverse complement's (a reverse-
+ *             complement palindrome: rc = 0).
+ *   unique    a key is unique in a side when exactly one valid window of the side has it, on either strand.
+ *   mate      position i of A has a mate iff its key is unique in A and unique in B: the word posB << 1 | (rcA xor rcB) — strand
+ *             0 is +, 1 is - — and 0xFFFFFFFF for no mate.
+ *   run       a maximal range [a, b) of consecutive k-mer positions of ONE contig of A whose mates have one strand and whose posB
+ *             advances by +1 per position on +, by -1 on -.  Contig edges of A cut runs.
+ * A position table holds, per distinct canonical k-mer, one position field per side in 16-byte slots in HBM; the number of slots
+ * is the power of two at or above 2 * capacity_keys.  capacity_keys = the k-mer positions of both sides always suffices.
+ * PG_E_INVALID: k outside 1..32, capacity_keys outside 1..2^32.  A table is used by one host thread at a time and is destroyed
+ * before its context. */
+typedef struct pg_postable pg_postable;
+int pg_postable_create(pg_ctx *ctx, int k, uint64_t capacity_keys, pg_postable **out);
+int pg_postable_destroy(pg_postable *pt);
+/* every valid k-mer of seqs into the field of `side` (0 or 1): its position when the side holds the key once, a MULTI mark
+ * beyond — the same whatever order the GPU took them in.  Each side is inserted once (PG_E_INVALID: a second time, a side's bases
+ * above 2^31 - 1, before anything is launched).  Probing is bounded: a key that finds no slot makes the call return
+ * PG_E_CAPACITY, and the table answers PG_E_CAPACITY from then on — destroy it and create a larger one.  One launch of
+ * k_pos_insert; synchronises. */
+int pg_postable_insert_seqset(pg_postable *pt, int side, const pg_seqset *seqs);
+/* the mate word of every k-mer position of seqsA, which must be the sequence set inserted as side 0: a position whose key's
+ * field of side 0 is not that very position has no mate.  mates_out: pg_seqset_total_kmers(seqsA, k) entries, the contigs'
+ * positions back to back — a host pointer, or NULL: the array then only stays in HBM with the table (pg_synteny_segments reads
+ * it there).  *nmated = the positions with a mate.  One launch of k_pos_mates; synchronises. */
+int pg_postable_mates(pg_postable *pt, const pg_seqset *seqsA, uint32_t *mates_out, uint64_t *nmated);
+/* the runs of an array of mate words on the host: ncontigs contigs of nkmers[c] entries each, back to back (at most 2^31 - 1 in
+ * all: PG_E_INVALID beyond).  Entry j continues the run of entry j - 1 of its contig iff neither is 0xFFFFFFFF and mates[j] ==
+ * mates[j - 1] + 2 (even words) or mates[j - 1] - 2 (odd words), in exact arithmetic.  nruns_per_contig[c] = the runs of contig c,
+ * *total = their sum.
+ * Capacity, as pg_result_find_runs: the counts are always computed.  If *total > cap, or cap == 0, the call returns PG_OK with the
+ * counts filled and writes nothing to the four run arrays (which may then be NULL when cap == 0): call again with arrays of
+ * *total entries.  Otherwise their first *total entries are the runs — contig, first position and exclusive end as k-mer
+ * positions of that contig, the mate word of the first position — sorted by (contig, start), the same on every call.
+ * Two launches of k_mate_runs (count, then emit; one when nothing is emitted) over chunks of 4096 positions, no atomics;
+ * synchronises. */
+int pg_mate_runs(pg_ctx *ctx, const uint32_t *mates, uint32_t ncontigs, const uint64_t *nkmers, uint64_t cap,
+                 uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end, uint32_t *run_mate,
+                 uint64_t *nruns_per_contig, uint64_t *total);
+/* all of it in one call: a table for both sides' k-mer positions, both inserts, the mates of A and their runs — the mates array
+ * never leaves HBM.  Outputs and capacity as pg_mate_runs, over the contigs of seqsA (nruns_per_contig: one entry per contig of
+ * seqsA); *nmated = the positions of A with a mate = the sum of the runs' lengths.  PG_E_INVALID before anything is launched: k
+ * outside 1..32, a side of more than 2^31 - 1 bases, a sequence set of another context. */
+int pg_synteny_segments(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, uint64_t cap,
+                        uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end, uint32_t *run_mate,
+                        uint64_t *nruns_per_contig, uint64_t *total, uint64_t *nmated);
+/* the HIP-event times, in milliseconds, of the kernels of this host thread's last pg_synteny_segments: ms_out[5] = k_pos_insert of
+ * A, of B, k_pos_mates, k_mate_runs counting, k_mate_runs emitting (0 where a kernel did not run) — what tools/synteny_rate.py
+ * reports. */
+int pg_synteny_last_timing(float *ms_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

@@ -11,7 +11,10 @@ a region's rows with the rows each holds (query_bitmap + value_counts(), reduced
 with the kind of difference their length suggests (query_bitmap + a per-column np.diff, reduced on the GPU);
 `pangenome <index_dir> [--matrix FILE] [--occupancy FILE]` prints every sample's distinct, private, core and shell k-mers, counted
 on the GPU in one pass over the table of all samples' k-mers (`index --kmer_stats` writes the matrix and the occupancy table with
-the index; `dist <index_dir> --exact` writes genome_dist.tsv from the exact Jaccard index at the index's k)."""
+the index; `dist <index_dir> --exact` writes genome_dist.tsv from the exact Jaccard index at the index's k); and
+`synteny <index_dir> <A> <B> [--chroms-a X,Y] [--chroms-b ...] [-k K] [--min-len N]` lists the maximal collinear runs of k-mers that
+occur exactly once in genome A and exactly once in genome B, with their place and strand in B, found on the GPU from the two
+genomes' sequences (the lines of a dot plot; the reference has nothing that says WHERE in B a k-mer lies)."""
 import argparse
 import os
 import sys
@@ -119,6 +122,20 @@ def main(argv=None):
     gp.add_argument("--whole", action="store_true", help="the whole genome in place of a chromosome")
     gp.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     gp.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    sy = sub.add_parser("synteny", help="the maximal collinear runs of k-mers unique in genome A and unique in genome B, found on the "
+                                        "GPU from the two genomes' sequences: tab-separated chrA startA endA chrB startB endB strand kmers")
+    sy.add_argument("index_dir")
+    sy.add_argument("genome_a", metavar="A")
+    sy.add_argument("genome_b", metavar="B")
+    sy.add_argument("--chroms-a", default="", metavar="X,Y", help="only these chromosomes of A (default: all of them)")
+    sy.add_argument("--chroms-b", default="", metavar="X,Y", help="only these chromosomes of B (default: all of them)")
+    sy.add_argument("-k", type=int, default=None, help="1 to 32 (default: the index's k)")
+    sy.add_argument("--min-len", type=int, default=1, metavar="N", help="drop runs of fewer than N k-mers")
+    sy.add_argument("--summary", metavar="FILE", default=None, help="also write chrA chrB strand segments kmers: the segments and shared "
+                    "unique k-mers of every pair of chromosomes and strand, then per chromosome of either side, then in all; in front, "
+                    "as # lines, per side the positions whose k-mer is unique in that genome and those with a mate")
+    sy.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    sy.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -247,6 +264,27 @@ def main(argv=None):
             spectrum.to_csv(a.spectrum, sep="\t", index=False)
         if a.summary:
             summary.to_csv(a.summary, sep="\t", index=False)
+        out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
+        return 0
+    if a.cmd == "synteny":
+        if a.min_len < 1:
+            ap.error("synteny: --min-len must be at least 1")
+        from .index import Index
+        idx = Index(a.index_dir, mode="r", device=a.device)
+        try:
+            for g in (a.genome_a, a.genome_b):
+                if g not in idx.genomes:
+                    ap.error(f"synteny: unknown genome {g!r} (the index has {', '.join(idx.genome_names)})")
+            try:
+                out, summary, totals = idx.synteny_tables(a.genome_a, a.genome_b, [c for c in a.chroms_a.split(",") if c] or None,
+                                                     [c for c in a.chroms_b.split(",") if c] or None, a.k, a.min_len)
+            except (ValueError, KeyError) as e:
+                ap.error(f"synteny: {e}")
+        finally:
+            idx.close()
+        if a.summary:
+            from . import synteny
+            synteny.write_summary(a.summary, summary, totals)
         out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
         return 0
     if a.cmd == "patterns":

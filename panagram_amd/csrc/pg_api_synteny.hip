@@ -1,0 +1,376 @@
+// pg_api_synteny.hip — host side of the C-ABI: the position table of two genomes, the mates of A's positions and their collinear
+// runs (pg_synteny.hip).
+#include "pg_host.h"
+
+static constexpr uint64_t POS_MAX_BASES = 0x7FFFFFFFull;  // a side's bases: the word pos << 1 | rc stays below POS_MULTI
+static constexpr uint64_t POS_MAX_KEYS = 1ull << 32;      // two sides of 2^31 k-mers
+static constexpr uint32_t POS_MAX_PROBE = 4096;           // slots a lane walks before it gives up (load <= 0.5: tens at the most)
+
+struct pg_postable {
+    pg_ctx *ctx;
+    int k;
+    uint64_t capacity, nslots;
+    uint32_t max_probe;
+    void *d_slots = nullptr;
+    uint32_t *d_mates = nullptr;  // of the last pg_postable_mates: kept in HBM for the runs
+    uint64_t nmates = 0;
+    bool inserted[2] = {false, false};
+    bool overflowed = false;  // an insert gave up: the table holds a part of a side and answers nothing any more
+};
+
+namespace {
+
+// the HIP-event time of one launch, for pg_synteny_last_timing: armed only where the caller hands in a place for it
+struct LaunchTimer {
+    float *ms;
+    Event a, b;
+    explicit LaunchTimer(float *out) : ms(out) {}
+    hipError_t start(hipStream_t st) {
+        if (!ms) return hipSuccess;
+        hipError_t e = a.create(hipEventDefault);
+        if (e == hipSuccess) e = b.create(hipEventDefault);
+        return e == hipSuccess ? hipEventRecord(a.get(), st) : e;
+    }
+    hipError_t stop(hipStream_t st) { return ms ? hipEventRecord(b.get(), st) : hipSuccess; }
+    void read() {  // (behind the stream's synchronise)
+        if (ms && hipEventElapsedTime(ms, a.get(), b.get()) != hipSuccess) *ms = -1.0f;
+    }
+};
+thread_local float g_last_ms[5] = {0, 0, 0, 0, 0};  // insert A, insert B, mates, runs (count), runs (emit) of the last pg_synteny_segments
+
+// the (contig, chunk) jobs of a seqset's k-mer positions, the base offset of every contig in the concatenation and its first
+// entry in a back-to-back array of k-mer positions
+struct SideWalk {
+    std::vector<uint2> jobs;
+    std::vector<uint32_t> off, koff;  // [n] each
+    uint64_t bases = 0, nkmers = 0;
+};
+
+int walk_side(const pg_seqset *sq, int k, const char *fn, SideWalk &w) {
+    w.off.resize(sq->n);
+    w.koff.resize(sq->n);
+    for (uint32_t c = 0; c < sq->n; ++c) {
+        const uint64_t len = sq->desc[c].len, nk = len >= (uint64_t)k ? len - k + 1 : 0;
+        if (w.bases + len > POS_MAX_BASES)
+            return fail(PG_E_INVALID, "%s: more than %llu bases in one side (take fewer chromosomes)", fn, (unsigned long long)POS_MAX_BASES);
+        w.off[c] = (uint32_t)w.bases;
+        w.koff[c] = (uint32_t)w.nkmers;
+        for (uint64_t q = 0; q * SYNTENY_JOB < nk; ++q) w.jobs.push_back(make_uint2(c, (uint32_t)q));
+        w.bases += len;
+        w.nkmers += nk;
+    }
+    return PG_OK;
+}
+
+uint64_t slots_for(uint64_t capacity) {
+    uint64_t n = 2;
+    while (n < 2 * capacity) n <<= 1;
+    return n;
+}
+
+int postable_create(pg_ctx *ctx, int k, uint64_t capacity, std::unique_ptr<pg_postable> &out) {
+    if (k < 1 || k > 32) return fail(PG_E_INVALID, "pg_postable_create: k=%d unsupported (1..32)", k);
+    if (capacity < 1 || capacity > POS_MAX_KEYS)
+        return fail(PG_E_INVALID, "pg_postable_create: capacity of %llu keys (1 to 2^32)", (unsigned long long)capacity);
+    if (int r = use_device(ctx)) return r;
+    std::unique_ptr<pg_postable> pt(new pg_postable);
+    pt->ctx = ctx;
+    pt->k = k;
+    pt->capacity = capacity;
+    pt->nslots = slots_for(capacity);
+    pt->max_probe = (uint32_t)std::min<uint64_t>(pt->nslots, POS_MAX_PROBE);
+    hipError_t e = hipMalloc(&pt->d_slots, pt->nslots * POS_SLOT_BYTES);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? PG_E_CAPACITY : PG_E_HIP, "pg_postable_create: %llu slots: %s", (unsigned long long)pt->nslots,
+                    hipGetErrorString(e));
+    e = hipMemsetAsync(pt->d_slots, 0xFF, pt->nslots * POS_SLOT_BYTES, ctx->stream);
+    if (e != hipSuccess) {
+        hipFree(pt->d_slots);
+        return fail(PG_E_HIP, "pg_postable_create: %s", hipGetErrorString(e));
+    }
+    ++ctx->refs;
+    out = std::move(pt);
+    return PG_OK;
+}
+
+void postable_free(pg_postable *pt) {
+    hipSetDevice(pt->ctx->device);
+    hipStreamSynchronize(pt->ctx->stream);
+    if (pt->d_mates) hipFree(pt->d_mates);
+    hipFree(pt->d_slots);
+    pg_ctx *c = pt->ctx;
+    delete pt;
+    ctx_release(c);
+}
+
+int postable_insert(pg_postable *pt, int side, const pg_seqset *sq, float *ms = nullptr) {
+    if (side < 0 || side > 1) return fail(PG_E_INVALID, "pg_postable_insert_seqset: side %d (0 or 1)", side);
+    if (pt->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_postable_insert_seqset: table and seqset belong to different contexts");
+    if (pt->overflowed) return fail(PG_E_CAPACITY, "pg_postable_insert_seqset: the table overflowed before");
+    if (pt->inserted[side]) return fail(PG_E_INVALID, "pg_postable_insert_seqset: side %d is inserted already", side);
+    SideWalk w;
+    if (int r = walk_side(sq, pt->k, "pg_postable_insert_seqset", w)) return r;
+    if (int r = use_device(pt->ctx)) return r;
+    pt->inserted[side] = true;
+    if (w.jobs.empty()) return PG_OK;
+    hipStream_t st = pt->ctx->stream;
+    DevBuf<uint2> d_jobs;
+    DevBuf<uint32_t> d_off;
+    DevBuf<unsigned long long> d_flags;
+    unsigned long long flags = 0;
+    LaunchTimer tm(ms);
+    hipError_t e = d_jobs.upload(w.jobs, st);
+    if (e == hipSuccess) e = d_off.upload(w.off, st);
+    if (e == hipSuccess) e = d_flags.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flags.get(), 0, 8, st);
+    if (e == hipSuccess) e = tm.start(st);
+    if (e == hipSuccess)
+        e = launch_pos_insert(st, pt->k, (uint32_t)side, sq->d_desc, d_jobs.get(), (uint32_t)w.jobs.size(), d_off.get(), sq->d_seqw,
+                              sq->d_nmw, sq->d_has_n, pt->d_slots, pt->nslots, pt->max_probe, d_flags.get());
+    if (e == hipSuccess) e = tm.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&flags, d_flags.get(), 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_postable_insert_seqset: %s", hipGetErrorString(e));
+    tm.read();
+    if (flags) {
+        pt->overflowed = true;
+        return fail(PG_E_CAPACITY, "pg_postable_insert_seqset: %llu slots (created for %llu keys) do not hold side %d's k-mers",
+                    (unsigned long long)pt->nslots, (unsigned long long)pt->capacity, side);
+    }
+    return PG_OK;
+}
+
+// the mates of seqsA's positions into pt->d_mates; the host copy only when mates_out is given
+int postable_mates(pg_postable *pt, const pg_seqset *sq, uint32_t *mates_out, uint64_t *nmated, float *ms = nullptr) {
+    if (pt->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_postable_mates: table and seqset belong to different contexts");
+    if (pt->overflowed) return fail(PG_E_CAPACITY, "pg_postable_mates: the table overflowed");
+    if (!pt->inserted[0]) return fail(PG_E_INVALID, "pg_postable_mates: side 0 has not been inserted");
+    SideWalk w;
+    if (int r = walk_side(sq, pt->k, "pg_postable_mates", w)) return r;
+    if (int r = use_device(pt->ctx)) return r;
+    hipStream_t st = pt->ctx->stream;
+    *nmated = 0;
+    if (pt->d_mates) {
+        HIP_TRY(hipStreamSynchronize(st));
+        hipFree(pt->d_mates);
+        pt->d_mates = nullptr;
+        pt->nmates = 0;
+    }
+    if (w.jobs.empty()) return PG_OK;
+    DevBuf<uint2> d_jobs;
+    DevBuf<uint32_t> d_off, d_koff, d_m;
+    DevBuf<unsigned long long> d_n;
+    unsigned long long n = 0;
+    LaunchTimer tm(ms);
+    hipError_t e = d_jobs.upload(w.jobs, st);
+    if (e == hipSuccess) e = d_off.upload(w.off, st);
+    if (e == hipSuccess) e = d_koff.upload(w.koff, st);
+    if (e == hipSuccess) e = d_m.alloc(w.nkmers);
+    if (e == hipSuccess) e = d_n.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_n.get(), 0, 8, st);
+    if (e == hipSuccess) e = tm.start(st);
+    if (e == hipSuccess)
+        e = launch_pos_mates(st, pt->k, sq->d_desc, d_jobs.get(), (uint32_t)w.jobs.size(), d_off.get(), d_koff.get(), sq->d_seqw,
+                             sq->d_nmw, sq->d_has_n, pt->d_slots, pt->nslots, pt->max_probe, d_m.get(), d_n.get());
+    if (e == hipSuccess) e = tm.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&n, d_n.get(), 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && mates_out) e = hipMemcpyAsync(mates_out, d_m.get(), w.nkmers * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_postable_mates: %s", hipGetErrorString(e));
+    tm.read();
+    pt->d_mates = d_m.p;
+    d_m.p = nullptr;
+    pt->nmates = w.nkmers;
+    *nmated = n;
+    return PG_OK;
+}
+
+// the runs of a mates array in HBM (ncontigs contigs of nkmers[c] entries, back to back); *mated: the mated positions counted
+int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t ncontigs, const uint64_t *nkmers, uint64_t cap,
+                  uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end, uint32_t *run_mate, uint64_t *nruns, uint64_t *total_out,
+                  uint64_t *mated, float *ms = nullptr) {
+    std::vector<uint2> contigs(ncontigs), chunks;
+    std::vector<uint64_t> first(ncontigs + 1, 0);
+    uint64_t tot = 0;
+    for (uint32_t c = 0; c < ncontigs; ++c) {
+        if (nkmers[c] > POS_MAX_BASES || tot + nkmers[c] > POS_MAX_BASES)
+            return fail(PG_E_INVALID, "%s: more than %llu positions", fn, (unsigned long long)POS_MAX_BASES);
+        contigs[c] = make_uint2((uint32_t)tot, (uint32_t)nkmers[c]);
+        first[c] = chunks.size();
+        for (uint64_t p = 0; p < nkmers[c]; p += MATE_CHUNK) chunks.push_back(make_uint2(c, (uint32_t)p));
+        tot += nkmers[c];
+        nruns[c] = 0;
+    }
+    first[ncontigs] = chunks.size();
+    *total_out = 0;
+    if (mated) *mated = 0;
+    if (chunks.empty()) return PG_OK;
+    const uint32_t nchunks = (uint32_t)chunks.size();
+    if (int r = use_device(ctx)) return r;
+    hipStream_t st = ctx->stream;
+    DevBuf<uint2> d_contigs, d_chunks;
+    DevBuf<uint4> d_counts;
+    std::vector<uint4> counts(nchunks);
+    LaunchTimer tc(ms), te(ms ? ms + 1 : nullptr);
+    hipError_t e = d_contigs.upload(contigs, st);
+    if (e == hipSuccess) e = d_chunks.upload(chunks, st);
+    if (e == hipSuccess) e = d_counts.alloc(nchunks);
+    if (e == hipSuccess) e = tc.start(st);
+    if (e == hipSuccess)
+        e = launch_mate_runs(st, d_mates, d_contigs.get(), d_chunks.get(), nchunks, d_counts.get(), nullptr, 0, nullptr, nullptr, nullptr);
+    if (e == hipSuccess) e = tc.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    tc.read();
+    // per contig: the sums; per chunk: the starts and the ends of all chunks before it
+    std::vector<ulonglong2> offs(nchunks);
+    uint64_t nstarts = 0, nends = 0, nm = 0;
+    for (uint32_t c = 0; c < ncontigs; ++c) {
+        const uint64_t s0 = nstarts;
+        for (uint64_t i = first[c]; i < first[c + 1]; ++i) {
+            offs[i] = make_ulonglong2(nstarts, nends);
+            nm += counts[i].x;
+            nstarts += counts[i].y;
+            nends += counts[i].z;
+        }
+        nruns[c] = nstarts - s0;
+        if (nstarts != nends)  // (every run of a contig starts and ends inside it)
+            return fail(PG_E_HIP, "%s: contig %u: %llu run starts, %llu run ends", fn, c, (unsigned long long)nstarts, (unsigned long long)nends);
+    }
+    const uint64_t total = nstarts;
+    *total_out = total;
+    if (mated) *mated = nm;
+    if (total == 0 || cap == 0 || total > cap) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
+    DevBuf<ulonglong2> d_offs;
+    DevBuf<uint32_t> d_runs;
+    e = d_offs.upload(offs, st);
+    if (e == hipSuccess) e = d_runs.alloc((size_t)3 * total);
+    if (e == hipSuccess) e = te.start(st);
+    if (e == hipSuccess)
+        e = launch_mate_runs(st, d_mates, d_contigs.get(), d_chunks.get(), nchunks, nullptr, d_offs.get(), total, d_runs.get(),
+                             d_runs.get() + total, d_runs.get() + 2 * total);
+    if (e == hipSuccess) e = te.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(run_start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(run_end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(run_mate, d_runs.get() + 2 * total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    te.read();
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < ncontigs; ++c)
+        for (uint64_t i = 0; i < nruns[c]; ++i) run_contig[at++] = c;
+    return PG_OK;
+}
+
+bool runs_args_ok(uint32_t ncontigs, uint64_t cap, const uint32_t *run_contig, const uint32_t *run_start, const uint32_t *run_end,
+                  const uint32_t *run_mate, const uint64_t *nruns, const uint64_t *total) {
+    return total && (!ncontigs || nruns) && (!cap || (run_contig && run_start && run_end && run_mate));
+}
+
+}  // namespace
+
+extern "C" int pg_postable_create(pg_ctx *ctx, int k, uint64_t capacity_keys, pg_postable **out) {
+    PG_API_BEGIN
+    if (!ctx || !out) return fail(PG_E_INVALID, "pg_postable_create: NULL argument");
+    std::unique_ptr<pg_postable> pt;
+    if (int r = postable_create(ctx, k, capacity_keys, pt)) return r;
+    *out = pt.release();
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_postable_destroy(pg_postable *pt) {
+    PG_API_BEGIN
+    if (pt) postable_free(pt);
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_postable_insert_seqset(pg_postable *pt, int side, const pg_seqset *seqs) {
+    PG_API_BEGIN
+    if (!pt || !seqs) return fail(PG_E_INVALID, "pg_postable_insert_seqset: NULL argument");
+    return postable_insert(pt, side, seqs);
+    PG_API_END
+}
+
+extern "C" int pg_postable_mates(pg_postable *pt, const pg_seqset *seqsA, uint32_t *mates_out, uint64_t *nmated) {
+    PG_API_BEGIN
+    if (!pt || !seqsA || !nmated) return fail(PG_E_INVALID, "pg_postable_mates: NULL argument");
+    return postable_mates(pt, seqsA, mates_out, nmated);
+    PG_API_END
+}
+
+extern "C" int pg_mate_runs(pg_ctx *ctx, const uint32_t *mates, uint32_t ncontigs, const uint64_t *nkmers, uint64_t cap,
+                            uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end, uint32_t *run_mate,
+                            uint64_t *nruns_per_contig, uint64_t *total) {
+    PG_API_BEGIN
+    if (!ctx || (ncontigs && !nkmers) || !runs_args_ok(ncontigs, cap, run_contig, run_start, run_end, run_mate, nruns_per_contig, total))
+        return fail(PG_E_INVALID, "pg_mate_runs: NULL argument");
+    uint64_t n = 0;
+    for (uint32_t c = 0; c < ncontigs; ++c) {
+        if (nkmers[c] > POS_MAX_BASES || n + nkmers[c] > POS_MAX_BASES)
+            return fail(PG_E_INVALID, "pg_mate_runs: more than %llu positions", (unsigned long long)POS_MAX_BASES);
+        n += nkmers[c];
+    }
+    if (n && !mates) return fail(PG_E_INVALID, "pg_mate_runs: NULL argument");
+    if (int r = use_device(ctx)) return r;
+    DevBuf<uint32_t> d_mates;
+    if (n) {
+        hipError_t e = d_mates.alloc(n);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_mates.get(), mates, n * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) return fail(PG_E_HIP, "pg_mate_runs: %s", hipGetErrorString(e));
+    }
+    const int r = mate_runs_dev(ctx, "pg_mate_runs", d_mates.get(), ncontigs, nkmers, cap, run_contig, run_start, run_end, run_mate,
+                                nruns_per_contig, total, nullptr);
+    if (n) hipStreamSynchronize(ctx->stream);  // (the upload's source is the caller's; the buffer goes with the scope)
+    return r;
+    PG_API_END
+}
+
+extern "C" int pg_synteny_segments(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, uint64_t cap,
+                                   uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end, uint32_t *run_mate,
+                                   uint64_t *nruns_per_contig, uint64_t *total, uint64_t *nmated) {
+    PG_API_BEGIN
+    if (!ctx || !seqsA || !seqsB || !nmated ||
+        !runs_args_ok(seqsA->n, cap, run_contig, run_start, run_end, run_mate, nruns_per_contig, total))
+        return fail(PG_E_INVALID, "pg_synteny_segments: NULL argument");
+    if (k < 1 || k > 32) return fail(PG_E_INVALID, "pg_synteny_segments: k=%d unsupported (1..32)", k);
+    if (seqsA->ctx != ctx || seqsB->ctx != ctx) return fail(PG_E_INVALID, "pg_synteny_segments: a seqset of another context");
+    // both sides' limits before anything is launched
+    std::vector<uint64_t> nk(seqsA->n);
+    SideWalk a, b;
+    if (int r = walk_side(seqsA, k, "pg_synteny_segments", a)) return r;
+    if (int r = walk_side(seqsB, k, "pg_synteny_segments", b)) return r;
+    for (uint32_t c = 0; c < seqsA->n; ++c) nk[c] = seqsA->desc[c].len >= (uint64_t)k ? seqsA->desc[c].len - k + 1 : 0;
+    *total = *nmated = 0;
+    for (uint32_t c = 0; c < seqsA->n; ++c) nruns_per_contig[c] = 0;
+    std::fill(g_last_ms, g_last_ms + 5, 0.0f);
+    if (a.nkmers == 0 || b.nkmers == 0) return PG_OK;  // (no k-mer on one side: no mate)
+    std::unique_ptr<pg_postable> made;
+    if (int r = postable_create(ctx, k, a.nkmers + b.nkmers, made)) return r;
+    struct Guard {
+        pg_postable *p;
+        ~Guard() { postable_free(p); }
+    } pt{made.release()};
+    float *ms = g_last_ms;
+    if (int r = postable_insert(pt.p, 0, seqsA, ms)) return r;
+    if (int r = postable_insert(pt.p, 1, seqsB, ms + 1)) return r;
+    if (int r = postable_mates(pt.p, seqsA, nullptr, nmated, ms + 2)) return r;
+    uint64_t mated = 0;
+    if (int r = mate_runs_dev(ctx, "pg_synteny_segments", pt.p->d_mates, seqsA->n, nk.data(), cap, run_contig, run_start, run_end,
+                              run_mate, nruns_per_contig, total, &mated, ms + 3))
+        return r;
+    if (mated != *nmated)  // (two kernels counted the same array)
+        return fail(PG_E_HIP, "pg_synteny_segments: %llu mates written, %llu read", (unsigned long long)*nmated, (unsigned long long)mated);
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_synteny_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_synteny_last_timing: NULL argument");
+    std::copy(g_last_ms, g_last_ms + 5, ms_out);
+    return PG_OK;
+    PG_API_END
+}

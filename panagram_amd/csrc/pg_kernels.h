@@ -261,6 +261,33 @@ hipError_t launch_absence_runs(hipStream_t st, uint32_t ngenomes, const uint8_t 
                                const uint64_t *ends, const uint2 *chunks, uint32_t nchunks, const uint32_t *select,
                                uint32_t maxlen, uint32_t min_len, uint32_t max_len, uint32_t *hist, unsigned long long *absent,
                                uint2 *edges, unsigned long long *nsel, unsigned long long *cursor, uint64_t cap, uint4 *recs);
+// synteny (pg_synteny.hip): a position table of `nslots` (a power of two) 16-byte slots {u64 key, u32 word of side 0, u32 word of
+// side 1}, every byte 0xFF when empty.  A word = pos << 1 | rc: pos the global base offset of the k-mer in its side's contigs laid
+// end to end (off[c] = the bases before contig c), rc = 1 iff the reverse complement is the canonical strand.  jobs[j] =
+// (contig, chunk): k-mer positions [chunk, chunk + 1) x SYNTENY_JOB of a contig of at least k bases.  A lane walks at most
+// max_probe slots; flags[0] (zeroed by the caller) becomes nonzero when an insert gave up.
+//   insert  the field of `side` of every valid k-mer's key: its word when the side holds the key once, POS_MULTI beyond
+//   mates   mates[koff[c] + p] for position p of contig c of side 0's sequences: word of side 1 ^ own rc when the key's field of
+//           side 0 is this position and that of side 1 a position, NO_MATE otherwise; *nmated (zeroed) += the mated positions
+constexpr uint32_t POS_SLOT_BYTES = 16, POS_EMPTY = 0xFFFFFFFFu, POS_MULTI = 0xFFFFFFFEu, NO_MATE = 0xFFFFFFFFu;
+constexpr uint32_t SYNTENY_JOB = 1u << 14;
+hipError_t launch_pos_insert(hipStream_t st, int k, uint32_t side, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs,
+                             const uint32_t *off, const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n, void *slots,
+                             uint64_t nslots, uint32_t max_probe, unsigned long long *flags);
+hipError_t launch_pos_mates(hipStream_t st, int k, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint32_t *off,
+                            const uint32_t *koff, const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n,
+                            const void *slots, uint64_t nslots, uint32_t max_probe, uint32_t *mates, unsigned long long *nmated);
+// runs of mates: contigs[c] = {first entry of contig c in mates, its entries}; chunk = {contig, first position}: the MATE_CHUNK
+// positions from there, cut at the contig's end, a contig's chunks consecutive and in order.  Position j continues its
+// predecessor's run iff both are mated and mates[j] == mates[j - 1] + 2 (even words: strand +) or - 2 (odd words: strand -).
+//   offs == NULL  count: counts[c] = {mated positions, run starts, run ends, 0} of chunk c
+//   offs != NULL  emit: offs[c] = {starts, ends} of all chunks before c; the positions of the run starts (with their mate
+//                 words) / the exclusive run ends go to run_start (run_mate) / run_end from there on (entries at or past
+//                 `total` are never written)
+constexpr uint32_t MATE_CHUNK = 4096;  // positions per chunk, a multiple of 256
+hipError_t launch_mate_runs(hipStream_t st, const uint32_t *mates, const uint2 *contigs, const uint2 *chunks, uint32_t nchunks,
+                            uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *run_start, uint32_t *run_end,
+                            uint32_t *run_mate);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

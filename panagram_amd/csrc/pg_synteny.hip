@@ -1,0 +1,259 @@
+// pg_synteny.hip — WHERE in genome B does the k-mer at a position of genome A lie (gfx950)?  The bitmap rows answer whether B
+// holds it; this unit carries the positions: a hash table of canonical k-mers with one position field per side, the mate of
+// every position of A, and the maximal collinear runs of mates — the unique-match segments a dot plot draws.
+//
+// Definitions (tests/synteny_ref.py is the same in numpy):
+//   position   of a k-mer of a side = the global base offset of its first base in the concatenation of the side's contigs
+//              (off[c] = the lengths of the contigs before c).  Windows holding a non-ACGT base do not exist.
+//   key, rc    key = canonical_from_le(X); rc = 1 iff value(forward) > value(reverse complement), i.e. X > B in the notation
+//              of pg_device.h (value(fwd) = ~B, value(revcomp) = ~X); a reverse-complement palindrome has X == B: rc = 0.
+//   word       pos << 1 | rc: below POS_MULTI for pos <= 2^31 - 2, which the host checks (a side holds at most 2^31 - 1 bases).
+//   unique     exactly one valid window of the side has the key (both strands count).
+//   mate       of position i of A, iff its key is unique in A and in B: wordB ^ rcA = posB << 1 | (rcA ^ rcB); NO_MATE otherwise.
+//   run        a maximal range [a, b) of consecutive k-mer positions of ONE contig of A whose mates have one strand and whose
+//              posB advances by +1 per position on strand 0, by -1 on strand 1: mate[j] == mate[j - 1] + 2 / - 2.
+//
+// The table: `slots` (a power of two) 16-byte slots {u64 key, u32 word of side 0, u32 word of side 1}, all bytes 0xFF when empty
+// (EMPTY_KEY is no canonical k-mer, pg_device.h).  Home slot = sketch_hash(key) & (slots - 1), linear probing, at most
+// `max_probe` slots: reaching the bound sets flags[0] and the lane gives up — no loop here is unbounded.
+//   k_pos_insert   one launch per side over (contig, chunk) jobs as k_sketch_set.  A lane claims its key by a 64-bit CAS
+//                  (EMPTY -> key) and then  old = atomicCAS(&word[side], POS_EMPTY, mine): old a position -> the field becomes
+//                  POS_MULTI.  A field only ever goes EMPTY -> word -> MULTI, whoever comes first: after the launch it holds
+//                  the single occurrence's word or MULTI, whatever the order the lanes ran in.
+//   k_pos_mates    the same walk over A; mates[koff[c] + p] for k-mer position p of contig c (contigs back to back), and the
+//                  number of mated positions: a ballot per wave, one atomic per block.
+//   k_mate_runs    the structure of k_find_runs (pg_find.hip): chunks of MATE_CHUNK positions of one contig, tiles of 256, the
+//                  predecessor's mate from the lane below, the wave below (LDS), the tile before, and ONE halo element at a
+//                  chunk's first position — none at a contig's first.  With M = mated, P = predecessor mated, C = continues:
+//                    run starts  M & ~C        run ends (exclusive)  P & ~C, and one at the contig's end when its last is mated
+//                  count (EMIT = false): counts[chunk] = {mated, starts, ends, 0}; the host takes exclusive scans.
+//                  emit: starts and ends are numbered separately (the i-th start and the i-th end of a contig are one run), so
+//                  the output is sorted by (contig, start) by construction and the same on every call.
+// Every write to HBM is a vector store or a vector atomic.
+#include "pg_kernels.h"
+
+namespace pg {
+
+constexpr uint32_t MATE_TILE = 256;
+static_assert(MATE_CHUNK % MATE_TILE == 0, "a chunk is a whole number of tiles");
+
+struct PosSlot {
+    unsigned long long key;
+    uint32_t word[2];
+};
+static_assert(sizeof(PosSlot) == POS_SLOT_BYTES, "16-byte slots");
+
+// X > B: the reverse complement's value is the smaller one
+__device__ __forceinline__ bool kmer_key_rc(const uint64_t *seqw, uint64_t p, int k, uint64_t &key) {
+    const uint64_t X = extract_bases(seqw, p) & kmer_mask(k);
+    const uint64_t B = revcomp_le(X, k);
+    key = canonical_from_xb(X, B, k);
+    return X > B;
+}
+
+// job = positions [y * SYNTENY_JOB, (y + 1) * SYNTENY_JOB) of contig x, which holds at least k bases
+__global__ __launch_bounds__(256) void k_pos_insert(int k, uint32_t side, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ jobs,
+                                                    const uint32_t *__restrict__ off, const uint64_t *seqw_all, const uint32_t *nmw_all,
+                                                    const uint32_t *has_n, PosSlot *slots, uint64_t nslots, uint32_t max_probe,
+                                                    unsigned long long *flags) {
+    const uint2 job = jobs[blockIdx.x];
+    const SeqDesc d = sd[job.x];
+    const uint64_t nkmers = d.len - (uint64_t)k + 1, p0 = (uint64_t)job.y * SYNTENY_JOB, p1 = min(nkmers, p0 + SYNTENY_JOB);
+    const uint64_t *seqw = seqw_all + d.seq_off;
+    const uint32_t *nmw = nmw_all + d.seq_off;
+    const bool hasn = has_n[job.x] != 0;
+    const uint32_t base = off[job.x];
+    const uint64_t smask = nslots - 1;
+    for (uint64_t p = p0 + threadIdx.x; p < p1; p += 256) {
+        if (hasn && extract_nmask(nmw, p, k)) continue;
+        uint64_t key;
+        const uint32_t rc = kmer_key_rc(seqw, p, k, key) ? 1u : 0u;
+        const uint32_t mine = ((base + (uint32_t)p) << 1) | rc;
+        uint64_t s = sketch_hash(key) & smask;
+        bool done = false;
+        for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
+            unsigned long long cur = __hip_atomic_load(&slots[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == EMPTY_KEY) {
+                cur = atomicCAS(&slots[s].key, (unsigned long long)EMPTY_KEY, (unsigned long long)key);
+                if (cur == EMPTY_KEY) cur = key;
+            }
+            if (cur != key) continue;
+            const uint32_t old = atomicCAS(&slots[s].word[side], POS_EMPTY, mine);
+            if (old != POS_EMPTY && old != POS_MULTI) atomicExch(&slots[s].word[side], POS_MULTI);
+            done = true;
+            break;
+        }
+        if (!done) atomicOr(reinterpret_cast<unsigned int *>(flags), 1u);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pos_mates(int k, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ jobs,
+                                                   const uint32_t *__restrict__ off, const uint32_t *__restrict__ koff,
+                                                   const uint64_t *seqw_all, const uint32_t *nmw_all, const uint32_t *has_n,
+                                                   const PosSlot *slots, uint64_t nslots, uint32_t max_probe,
+                                                   uint32_t *__restrict__ mates, unsigned long long *nmated) {
+    __shared__ uint32_t wsum[4];
+    const uint2 job = jobs[blockIdx.x];
+    const SeqDesc d = sd[job.x];
+    const uint64_t nkmers = d.len - (uint64_t)k + 1, p0 = (uint64_t)job.y * SYNTENY_JOB, p1 = min(nkmers, p0 + SYNTENY_JOB);
+    const uint64_t *seqw = seqw_all + d.seq_off;
+    const uint32_t *nmw = nmw_all + d.seq_off;
+    const bool hasn = has_n[job.x] != 0;
+    const uint32_t base = off[job.x];
+    uint32_t *out = mates + koff[job.x];
+    const uint64_t smask = nslots - 1;
+    uint32_t found = 0;  // (per wave: every lane of a wave holds the same sum)
+    for (uint64_t q = p0; q < p1; q += 256) {  // (bounds uniform over the block: every lane reaches the ballot)
+        const uint64_t p = q + threadIdx.x;
+        uint32_t mate = NO_MATE;
+        if (p < p1 && !(hasn && extract_nmask(nmw, p, k))) {
+            uint64_t key;
+            const uint32_t rc = kmer_key_rc(seqw, p, k, key) ? 1u : 0u;
+            const uint32_t mine = ((base + (uint32_t)p) << 1) | rc;
+            uint64_t s = sketch_hash(key) & smask;
+            for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
+                const unsigned long long cur = slots[s].key;
+                if (cur == EMPTY_KEY) break;
+                if (cur != key) continue;
+                // unique in A: the field of side 0 is this very position; unique in B: the field of side 1 is a position
+                const uint32_t a = slots[s].word[0], b = slots[s].word[1];
+                if (a == mine && b != POS_EMPTY && b != POS_MULTI) mate = b ^ rc;
+                break;
+            }
+        }
+        if (p < p1) out[p] = mate;
+        found += (uint32_t)__popcll(__ballot(mate != NO_MATE));
+    }
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = found;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (n) atomicAdd(nmated, (unsigned long long)n);
+    }
+}
+
+// does the mate `m` of a position continue the run of its predecessor's mate `prev`?  (64-bit sums: nothing wraps)
+__device__ __forceinline__ bool mate_continues(uint32_t prev, uint32_t m) {
+    if (m == NO_MATE || prev == NO_MATE) return false;
+    return (m & 1u) ? (uint64_t)m + 2 == (uint64_t)prev : (uint64_t)m == (uint64_t)prev + 2;
+}
+
+// contigs[c] = {first entry of contig c in mates, its k-mer positions}; chunk = {contig, first position}
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_mate_runs(const uint32_t *__restrict__ mates, const uint2 *__restrict__ contigs,
+                                                   const uint2 *__restrict__ chunks, uint4 *__restrict__ counts,
+                                                   const ulonglong2 *__restrict__ offs, uint64_t total,
+                                                   uint32_t *__restrict__ run_start, uint32_t *__restrict__ run_end,
+                                                   uint32_t *__restrict__ run_mate) {
+    __shared__ uint32_t lastm[4];  // the mate of every wave's last lane
+    __shared__ uint4 wcnt[4];      // {starts, ends, mated, 0} of every wave
+    __shared__ uint32_t tailm;     // the mate of the chunk's last position
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint2 ck = chunks[blockIdx.x];
+    const uint2 cd = contigs[ck.x];
+    const uint32_t *cm = mates + cd.x;
+    const uint32_t nk = cd.y, c0 = ck.y, ce = min(c0 + MATE_CHUNK, nk);  // this chunk: positions [c0, ce), 0 <= c0 < ce <= nk
+    // the chunk's halo: the mate of position c0 - 1 (every lane the same entry: one broadcast load)
+    uint32_t carry = c0 > 0 ? cm[c0 - 1] : NO_MATE;
+    uint32_t matched = 0, nstarts = 0, nends = 0;
+    uint64_t soff = 0, eoff = 0;
+    if (EMIT) {
+        const ulonglong2 o = offs[blockIdx.x];
+        soff = o.x;
+        eoff = o.y;
+    }
+    for (uint32_t t0 = c0; t0 < ce; t0 += MATE_TILE) {
+        const uint32_t j = t0 + tid;
+        const uint32_t m = j < ce ? cm[j] : NO_MATE;
+        if (lane == 63) lastm[wave] = m;
+        if (j == ce - 1) tailm = m;
+        __syncthreads();
+        uint32_t prev = (uint32_t)__shfl_up((int)m, 1);
+        if (lane == 0) prev = wave ? lastm[wave - 1] : carry;
+        carry = lastm[3];
+        const bool act = j < ce;
+        const bool cont = act && mate_continues(prev, m);
+        const uint64_t sm = __ballot(act && m != NO_MATE && !cont);
+        const uint64_t em = __ballot(act && prev != NO_MATE && !cont);
+        const uint64_t mm = __ballot(act && m != NO_MATE);
+        if (lane == 0) wcnt[wave] = make_uint4((uint32_t)__popcll(sm), (uint32_t)__popcll(em), (uint32_t)__popcll(mm), 0u);
+        __syncthreads();
+        // (one buffer each: lastm is read between the two barriers and written again behind the second, wcnt is read behind
+        // the second and written again behind the next tile's first)
+        uint32_t sbelow = 0, ebelow = 0, stile = 0, etile = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4; ++w) {
+            const uint4 c = wcnt[w];
+            if (w == wave) {
+                sbelow = stile;
+                ebelow = etile;
+            }
+            stile += c.x;
+            etile += c.y;
+            matched += c.z;
+        }
+        if (EMIT) {
+            const uint64_t below = (1ull << lane) - 1ull;
+            if ((sm >> lane) & 1ull) {
+                const uint64_t at = soff + nstarts + sbelow + (uint32_t)__popcll(sm & below);
+                if (at < total) {
+                    run_start[at] = j;
+                    run_mate[at] = m;
+                }
+            }
+            if ((em >> lane) & 1ull) {
+                const uint64_t at = eoff + nends + ebelow + (uint32_t)__popcll(em & below);
+                if (at < total) run_end[at] = j;
+            }
+        }
+        nstarts += stile;
+        nends += etile;
+    }
+    // the contig's last chunk: a run that reaches the contig's last position ends at nk (tailm: written in front of the last
+    // tile's first barrier, which every lane has passed)
+    if (ce == nk && tailm != NO_MATE) {
+        if (EMIT && tid == 0) {
+            const uint64_t at = eoff + nends;
+            if (at < total) run_end[at] = nk;
+        }
+        nends += 1;
+    }
+    if (!EMIT && tid == 0) counts[blockIdx.x] = make_uint4(matched, nstarts, nends, 0u);
+}
+
+hipError_t launch_pos_insert(hipStream_t st, int k, uint32_t side, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs,
+                             const uint32_t *off, const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n, void *slots,
+                             uint64_t nslots, uint32_t max_probe, unsigned long long *flags) {
+    if (njobs == 0) return hipSuccess;
+    if (k < 1 || k > 32 || side > 1 || nslots == 0 || (nslots & (nslots - 1)) || !slots || !flags) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pos_insert, dim3(njobs), dim3(256), 0, st, k, side, sd, jobs, off, seqw, nmw, has_n,
+                       static_cast<PosSlot *>(slots), nslots, max_probe, flags);
+    return hipGetLastError();
+}
+
+hipError_t launch_pos_mates(hipStream_t st, int k, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint32_t *off,
+                            const uint32_t *koff, const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n,
+                            const void *slots, uint64_t nslots, uint32_t max_probe, uint32_t *mates, unsigned long long *nmated) {
+    if (njobs == 0) return hipSuccess;
+    if (k < 1 || k > 32 || nslots == 0 || (nslots & (nslots - 1)) || !slots || !mates || !nmated) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pos_mates, dim3(njobs), dim3(256), 0, st, k, sd, jobs, off, koff, seqw, nmw, has_n,
+                       static_cast<const PosSlot *>(slots), nslots, max_probe, mates, nmated);
+    return hipGetLastError();
+}
+
+hipError_t launch_mate_runs(hipStream_t st, const uint32_t *mates, const uint2 *contigs, const uint2 *chunks, uint32_t nchunks,
+                            uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *run_start, uint32_t *run_end,
+                            uint32_t *run_mate) {
+    if (nchunks == 0) return hipSuccess;
+    const bool emit = offs != nullptr;
+    if (!mates || (emit ? (!run_start || !run_end || !run_mate) : !counts)) return hipErrorInvalidValue;
+    if (emit)
+        hipLaunchKernelGGL(k_mate_runs<true>, dim3(nchunks), dim3(256), 0, st, mates, contigs, chunks, counts, offs, total, run_start,
+                           run_end, run_mate);
+    else
+        hipLaunchKernelGGL(k_mate_runs<false>, dim3(nchunks), dim3(256), 0, st, mates, contigs, chunks, counts, offs, total, run_start,
+                           run_end, run_mate);
+    return hipGetLastError();
+}
+
+}  // namespace pg

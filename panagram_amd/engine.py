@@ -481,6 +481,103 @@ def knn_rows(ctx: Context, X, k: int, seg=None) -> Tuple[np.ndarray, np.ndarray]
     return idx, d2
 
 
+NO_MATE = 0xFFFFFFFF
+
+
+class PosTable:
+    """Position table of two sequence sets in HBM (pg_synteny.hip): per distinct canonical k-mer the position of its one
+    occurrence in side 0 (A) and in side 1 (B), or a mark that the side holds it more than once.  ``capacity_keys``: the distinct
+    keys it must hold — the k-mer positions of both sides always suffice.  A side whose keys do not fit raises with code -4
+    (PG_E_CAPACITY); the table is then of no further use."""
+
+    def __init__(self, ctx: Context, k: int, capacity_keys: int):
+        self.ctx, self._lib, self.k = ctx, ctx._lib, int(k)
+        h = C.c_void_p()
+        check(self._lib.pg_postable_create(ctx._h, int(k), int(capacity_keys), C.byref(h)))
+        self._h = h
+        ctx._adopt(self)
+
+    def insert(self, side: int, seqs: SeqSet) -> None:
+        check(self._lib.pg_postable_insert_seqset(self._h, int(side), seqs._h))
+
+    def mates(self, seqs_a: SeqSet, download: bool = True):
+        """(mate word of every k-mer position of ``seqs_a`` — the set inserted as side 0 — contigs back to back: ``posB << 1 |
+        strand``, NO_MATE where the k-mer is not unique in both sides; the mated positions).  ``download=False``: None in
+        place of the array, which then only stays in HBM."""
+        out = np.empty(seqs_a.total_kmers(self.k), np.uint32) if download else None
+        n = C.c_uint64()
+        check(self._lib.pg_postable_mates(self._h, seqs_a._h, _ptr(out), C.byref(n)))
+        return out, int(n.value)
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.pg_postable_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def mate_runs(ctx: Context, mates, nkmers, cap: Optional[int] = None):
+    """(run_contig, run_start, run_end, run_mate, runs per contig): the maximal collinear runs of an array of mate words
+    (``nkmers[c]`` entries per contig, back to back) — per run its contig, first position and exclusive end inside the contig,
+    and the mate word of its first position; sorted by (contig, start).  ``cap`` (tests of the capacity protocol): ONE call with
+    arrays of ``cap`` entries, returned whole behind the total."""
+    m = np.ascontiguousarray(mates, np.uint32)
+    nk = np.ascontiguousarray(nkmers, np.uint64)
+    if m.ndim != 1 or nk.ndim != 1 or int(nk.sum()) != m.size:
+        raise ValueError("one mate word per k-mer position of every contig")
+    per, total = np.zeros(len(nk), np.uint64), C.c_uint64()
+
+    def call(n):
+        arrs = [np.full(n, NO_MATE, np.uint32) for _ in range(4)]
+        check(ctx._lib.pg_mate_runs(ctx._h, _ptr(m), len(nk), _ptr(nk), n, *[_ptr(a) if n else None for a in arrs], _ptr(per),
+                                    C.byref(total)))
+        return arrs
+    if cap is not None:
+        arrs = call(int(cap))
+        return (*arrs, per, int(total.value))
+    call(0)
+    arrs = call(int(total.value))
+    return (*arrs, per)
+
+
+def synteny_segments(ctx: Context, k: int, seqs_a: SeqSet, seqs_b: SeqSet, cap: Optional[int] = None):
+    """(run_contig, run_start, run_end, run_mate, runs per contig of A, mated positions of A): the maximal collinear runs of
+    k-mers that occur exactly once in ``seqs_a`` and exactly once in ``seqs_b``, as ``mate_runs`` returns them — table, mates
+    and runs in one library call, the mates never leaving HBM.  ``cap``: the runs expected (a second call follows when there
+    are more)."""
+    per, total, nmated = np.zeros(len(seqs_a.lens), np.uint64), C.c_uint64(), C.c_uint64()
+    n = int(cap) if cap is not None else max(1024, min(1 << 20, seqs_a.total_kmers(k) // 16))
+    while True:
+        arrs = [np.empty(n, np.uint32) for _ in range(4)]
+        check(ctx._lib.pg_synteny_segments(ctx._h, int(k), seqs_a._h, seqs_b._h, n, *[_ptr(a) if n else None for a in arrs], _ptr(per),
+                                           C.byref(total), C.byref(nmated)))
+        if int(total.value) <= n:
+            break
+        n = int(total.value)
+    return (*[a[:total.value].copy() for a in arrs], per, int(nmated.value))
+
+
+def synteny_counts(ctx: Context, k: int, seqs_a: SeqSet, seqs_b: SeqSet) -> Tuple[int, int]:
+    """(runs, mated positions of A) of ``synteny_segments`` without the runs: one call that emits nothing.  A set against itself
+    counts the positions whose k-mer is unique in it."""
+    per, total, nmated = np.zeros(len(seqs_a.lens), np.uint64), C.c_uint64(), C.c_uint64()
+    check(ctx._lib.pg_synteny_segments(ctx._h, int(k), seqs_a._h, seqs_b._h, 0, None, None, None, None, _ptr(per), C.byref(total),
+                                       C.byref(nmated)))
+    return int(total.value), int(nmated.value)
+
+
+def synteny_last_timing() -> dict:
+    """HIP-event milliseconds of the kernels of this thread's last ``synteny_segments`` call"""
+    ms = (C.c_float * 5)()
+    check(_lib.load().pg_synteny_last_timing(ms))
+    return dict(zip(("insert_a_ms", "insert_b_ms", "mates_ms", "runs_count_ms", "runs_emit_ms"), (float(x) for x in ms)))
+
+
 class PanTable(_Owner):
     """GPU-resident k-mer -> genome-mask table (replaces kmc/bitvec{i})."""
 

@@ -1373,6 +1373,45 @@ class Index:
         ``query_bitmap(genome, chrom, start, end, step)`` (``Genome.absence_spectrum``)"""
         return self.genomes[genome].absence_spectrum(genomes, chrom, start, end, step, maxlen)
 
+    def synteny_tables(self, a, b, chroms_a=None, chroms_b=None, k=None, min_len=1):
+        """(segments, summary, totals) of ``synteny``: the summary is ``synteny.summary_frame`` of the segments; the totals
+        (``synteny.totals_frame``) give per side the positions whose k-mer is unique in that genome — each side against itself,
+        two more passes that emit nothing — and those with a mate in the other"""
+        from . import synteny
+        k = int(self.k) if k is None else int(k)
+        if not 1 <= k <= 32:
+            raise ValueError(f"synteny: k={k} (1 to 32)")
+        for g in (a, b):
+            if g not in self.genomes:
+                raise KeyError(f"synteny: unknown genome {g!r} (the index has {', '.join(self.genome_names)})")
+        sides, made = [], []
+        try:
+            for g, chosen in ((a, chroms_a), (b, chroms_b)):
+                ss = self.seqset_for(g)
+                names = list(ss.names)
+                pick = synteny.pick_contigs(names, chosen)
+                if chosen is not None:  # (whole contigs: a piece of its contig's full length from base 0)
+                    ss = ss.slice([(c, 0, int(ss.lens[c])) for c in pick])
+                    made.append(ss)
+                sides.append((ss, [names[c] for c in pick], [int(self.seqset_for(g).lens[c]) for c in pick]))
+            (ss_a, names_a, _), (ss_b, names_b, lens_b) = sides
+            rc, rs, re_, rm, _, nmated = engine.synteny_segments(self.context, k, ss_a, ss_b)
+            unique = [engine.synteny_counts(self.context, k, ss, ss)[1] for ss in (ss_a, ss_b)]
+        finally:
+            for ss in made:
+                ss.close()
+        seg = synteny.segment_frame(rc, rs, re_, rm, k, names_a, lens_b, names_b, min_len)
+        return seg, synteny.summary_frame(seg), synteny.totals_frame(a, b, unique[0], unique[1], nmated)
+
+    def synteny(self, a, b, chroms_a=None, chroms_b=None, k=None, min_len=1) -> pd.DataFrame:
+        """The maximal collinear runs of k-mers that occur exactly once in genome ``a`` and exactly once in genome ``b`` — the
+        unique-match segments of a dot plot — found on the GPU from the two genomes' packed sequences: columns ``chrA startA
+        endA chrB startB endB strand kmers``, half-open base ranges, sorted by (chromosome of ``a`` in file order, startA).
+        ``chroms_a`` / ``chroms_b`` narrow a side to some chromosomes (uniqueness is then judged among those); ``k`` defaults to
+        the index's (any 1..32: the table of all samples' k-mers is not read); ``min_len`` drops runs of fewer k-mers.  Not an
+        alignment: a single mismatch ends a segment, and segments are not chained."""
+        return self.synteny_tables(a, b, chroms_a, chroms_b, k, min_len)[0]
+
     def region_tree(self, genome, chrom, start=None, end=None, step=None) -> "RegionTree":
         """The tree of the genomes over a region, as the viewer draws it (view.py:751-764: create_tree) — but from the pair
         counts of EVERY row of the region at ``step`` (default: the low-resolution step), not from a random sample of

@@ -1,0 +1,103 @@
+"""The synteny kernels on genomes of real size: k_pos_insert (both sides), k_pos_mates and k_mate_runs, timed with HIP events.
+
+    python tools/synteny_rate.py [--mb 100] [--contigs 5] [-d 0.01] [-k 21] [--reps 5]
+
+Two synthetic genomes of --mb megabases in --contigs chromosomes: A i.i.d. uniform, B = A with substitutions at rate d, one
+chromosome inverted as a whole and two exchanged, so both strands and a translocation are in the run.  The sequences are drawn
+with torch on the GPU and packed there (SeqSet.load_dev).  engine.synteny_segments runs once warm (the code object's load, the
+first allocations) and --reps times; each kernel's time is the HIP-event interval around its launch that the library records
+(engine.synteny_last_timing), the median over the repetitions with the spread beside it.  The call time is a host clock around the
+synchronous call (table allocation and memset, job lists, both launches of k_mate_runs, the read-back of the runs).
+Rates: k-mer positions per second of the side a kernel walks; for k_mate_runs the bytes of the mates array it reads (once per
+launch) per second.  Checked at this size: the mated positions equal the sum of the runs' lengths, the runs are sorted, and
+with d = 0 every chromosome is one run.  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from panagram_amd import engine  # noqa: E402
+
+
+def genomes(ctx, mb, ncontigs, d, seed):
+    """(SeqSet A, SeqSet B): B's chromosome 0 is A's reverse-complemented, B's last two are A's exchanged"""
+    import torch
+    dev = torch.device("cuda", ctx.device)
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    acgt = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device=dev)
+    n = int(mb * 1e6) // ncontigs
+    lens = [n + 1000 * i for i in range(ncontigs)]
+    a = [torch.randint(0, 4, (m,), dtype=torch.uint8, device=dev, generator=gen) for m in lens]
+    b = []
+    for c in a:
+        mut = torch.rand(c.shape, device=dev, generator=gen) < d
+        shift = torch.randint(1, 4, c.shape, dtype=torch.uint8, device=dev, generator=gen)
+        b.append(torch.where(mut, (c + shift) & 3, c))
+    b[0] = 3 - torch.flip(b[0], [0])
+    if ncontigs >= 3:
+        b[-1], b[-2] = b[-2], b[-1]
+    sets = []
+    for contigs in (a, b):
+        ss = engine.SeqSet(ctx, [int(c.numel()) for c in contigs])
+        for i, c in enumerate(contigs):
+            t = acgt[c.long()]
+            torch.cuda.synchronize()
+            ss.load_dev(i, t.data_ptr(), int(t.numel()))
+            ctx.synchronize()
+        sets.append(ss)
+    return sets
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mb", type=float, default=100.0)
+    ap.add_argument("--contigs", type=int, default=5)
+    ap.add_argument("-d", type=float, default=0.01)
+    ap.add_argument("-k", type=int, default=21)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=7)
+    a = ap.parse_args()
+    ctx = engine.Context(0)
+    ssa, ssb = genomes(ctx, a.mb, a.contigs, a.d, a.seed)
+    nka, nkb = ssa.total_kmers(a.k), ssb.total_kmers(a.k)
+    slots = 2
+    while slots < 2 * (nka + nkb):
+        slots *= 2
+    out = dict(mb=a.mb, contigs=a.contigs, d=a.d, k=a.k, reps=a.reps, kmers_a=nka, kmers_b=nkb, table_slots=slots,
+               table_gb=round(slots * 16 / 1e9, 3), load=round((nka + nkb) / slots, 3))
+    runs = engine.synteny_segments(ctx, a.k, ssa, ssb)  # warm
+    cap = len(runs[0])
+    times, calls = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        got = engine.synteny_segments(ctx, a.k, ssa, ssb, cap=cap)
+        calls.append(time.perf_counter() - t0)
+        times.append(engine.synteny_last_timing())
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(got[:4], runs[:4]))  # the same on every call
+    rc, rs, re_, rm, per, nmated = runs
+    out.update(runs=len(rc), mated=nmated, mated_frac=round(nmated / max(1, nka), 4), minus_runs=int((rm & 1).sum()),
+               checks=dict(mated_is_sum_of_runs=bool(int((re_.astype(np.int64) - rs).sum()) == nmated),
+                           sorted=bool((np.diff(rc.astype(np.int64) * (1 << 32) + rs) > 0).all()),
+                           one_run_per_contig_at_d0=(bool(len(rc) == a.contigs) if a.d == 0 else None)))
+    side = dict(insert_a_ms=nka, insert_b_ms=nkb, mates_ms=nka, runs_count_ms=nka, runs_emit_ms=nka)
+    for name, n in side.items():
+        v = np.array([t[name] for t in times])
+        med = float(np.median(v))
+        out[name] = dict(median=round(med, 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4),
+                         g_positions_per_s=round(n / med / 1e6, 2) if med > 0 else None)
+    for name in ("runs_count_ms", "runs_emit_ms"):
+        med = out[name]["median"]
+        out[name]["mates_gb_per_s"] = round(nka * 4 / med / 1e6, 1) if med > 0 else None
+    out["call_s"] = dict(median=round(float(np.median(calls)), 4), min=round(min(calls), 4), max=round(max(calls), 4))
+    ssa.close()
+    ssb.close()
+    ctx.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -534,6 +534,45 @@ int pg_synteny_segments(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seq
  * A, of B, k_pos_mates, k_mate_runs counting, k_mate_runs emitting (0 where a kernel did not run) — what tools/synteny_rate.py
  * reports. */
 int pg_synteny_last_timing(float *ms_out);
+/* blocks: the runs chained across substitutions and small insertions and deletions, on the GPU, so that only the blocks leave HBM.
+ * With a run's n = end - start, strand = mate & 1, b = mate >> 1, the B position of its last k-mer bl = b + (n - 1) on strand 0,
+ * b - (n - 1) on strand 1, and ml = bl << 1 | strand:
+ *   kept         a run with n >= min_run; dropped runs do not exist for anything below.
+ *   predecessor  of a kept run j: the nearest kept run i before it in the same contig of A.
+ *   link i -> j  dA = start_j - (end_i - 1); dB = b_j - bl_i on strand 0, bl_i - b_j on strand 1 (signed, 64-bit).  It exists iff the
+ *                strands agree, 1 <= dA <= max_gap, 1 <= dB <= max_gap, |dA - dB| <= max_shift, and the global B positions bl_i and
+ *                b_j lie in the same contig of B.  A link is shifted when dA != dB.  (A substitution: dA = dB = k + 1; L bases
+ *                inserted in B: dA = k, dB = k + L; d bases deleted from B: dA = k + d, dB = k.)
+ *   block        a maximal chain of kept runs, each linked to its predecessor: contig of A, start of its first run, end of its
+ *                last, mate_first = the first run's mate word, mate_last = the last run's ml, kmers = the sum of n, runs = their
+ *                number, shifted = its shifted links.  B's positions are monotone inside a block: its B range in bases is
+ *                [mate_first >> 1, (mate_last >> 1) + k) on strand 0, [mate_last >> 1, (mate_first >> 1) + k) on strand 1.
+ * With min_run = 1 and max_gap = 1 the blocks are exactly the runs.
+ * pg_run_blocks takes the runs from host arrays (nruns of them over ncontigsA contigs, as pg_mate_runs returns them) and the
+ * lengths of B's ncontigsB contigs.  nblocks_per_contig[c] = the blocks of contig c of A, *total = their sum.  Capacity as
+ * pg_mate_runs: the counts are always filled; nothing is written to the eight block arrays when cap == 0 (they may then be NULL) or
+ * *total > cap; otherwise their first *total entries are the blocks, sorted by (contig, start), the same on every call.
+ * PG_E_INVALID, before anything is launched: runs not sorted by (contig, start) or overlapping, a contig >= ncontigsA, end <= start,
+ * a mate of 0xFFFFFFFF, a run whose B positions leave [0, sum(lensB)), min_run < 1, max_gap outside 1..2^31 - 1, max_shift above
+ * 2^31 - 1, more than 2^31 - 1 runs.  Two launches of k_run_blocks (count, then emit; one when nothing is emitted) over chunks of
+ * 4096 runs with a stitch of the chunks' edges on the host between them, no atomics; synchronises. */
+int pg_run_blocks(pg_ctx *ctx, const uint32_t *run_contig, const uint32_t *run_start, const uint32_t *run_end,
+                  const uint32_t *run_mate, uint64_t nruns, uint32_t ncontigsA, uint32_t ncontigsB, const uint64_t *lensB,
+                  uint32_t min_run, uint32_t max_gap, uint32_t max_shift, uint64_t cap,
+                  uint32_t *blk_contig, uint32_t *blk_start, uint32_t *blk_end, uint32_t *blk_mate_first, uint32_t *blk_mate_last,
+                  uint32_t *blk_kmers, uint32_t *blk_runs, uint32_t *blk_shifted, uint64_t *nblocks_per_contig, uint64_t *total);
+/* all of it in one call: table, both inserts, mates, the runs counted and emitted into HBM only, the blocks counted, stitched and
+ * emitted — neither the mates nor the runs are downloaded.  Blocks and capacity as pg_run_blocks over the contigs of seqsA and
+ * seqsB; *nmated as pg_synteny_segments, *nruns = all runs (kept or not).  PG_E_INVALID as pg_synteny_segments and for the three
+ * parameters as pg_run_blocks. */
+int pg_synteny_blocks(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, uint32_t min_run, uint32_t max_gap,
+                      uint32_t max_shift, uint64_t cap,
+                      uint32_t *blk_contig, uint32_t *blk_start, uint32_t *blk_end, uint32_t *blk_mate_first, uint32_t *blk_mate_last,
+                      uint32_t *blk_kmers, uint32_t *blk_runs, uint32_t *blk_shifted, uint64_t *nblocks_per_contig, uint64_t *total,
+                      uint64_t *nmated, uint64_t *nruns);
+/* the HIP-event times of this host thread's last pg_synteny_blocks: ms_out[7] = the five of pg_synteny_last_timing, then
+ * k_run_blocks counting and k_run_blocks emitting (0 where a kernel did not run). */
+int pg_synteny_blocks_last_timing(float *ms_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

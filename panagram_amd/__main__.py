@@ -14,7 +14,10 @@ on the GPU in one pass over the table of all samples' k-mers (`index --kmer_stat
 the index; `dist <index_dir> --exact` writes genome_dist.tsv from the exact Jaccard index at the index's k); and
 `synteny <index_dir> <A> <B> [--chroms-a X,Y] [--chroms-b ...] [-k K] [--min-len N]` lists the maximal collinear runs of k-mers that
 occur exactly once in genome A and exactly once in genome B, with their place and strand in B, found on the GPU from the two
-genomes' sequences (the lines of a dot plot; the reference has nothing that says WHERE in B a k-mer lies)."""
+genomes' sequences (the lines of a dot plot; the reference has nothing that says WHERE in B a k-mer lies);
+`synteny <index_dir> <A> <B> --blocks [--min-run N] [--max-gap G] [--max-shift S] [--paf]` chains those runs on the GPU into blocks
+that bridge substitutions and small insertions and deletions — a few thousand lines where the runs are a million — with the runs
+and the shifted links of each, or as PAF lines for the tools that draw dot plots; the runs never leave the GPU."""
 import argparse
 import os
 import sys
@@ -130,7 +133,17 @@ def main(argv=None):
     sy.add_argument("--chroms-a", default="", metavar="X,Y", help="only these chromosomes of A (default: all of them)")
     sy.add_argument("--chroms-b", default="", metavar="X,Y", help="only these chromosomes of B (default: all of them)")
     sy.add_argument("-k", type=int, default=None, help="1 to 32 (default: the index's k)")
-    sy.add_argument("--min-len", type=int, default=1, metavar="N", help="drop runs of fewer than N k-mers")
+    sy.add_argument("--min-len", type=int, default=1, metavar="N", help="drop runs (with --blocks: blocks) of fewer than N k-mers")
+    sy.add_argument("--blocks", action="store_true", help="chain the runs on the GPU into blocks that bridge substitutions and small "
+                    "insertions and deletions: the same columns, then runs and shifted (the links whose gaps differ on A and B)")
+    sy.add_argument("--min-run", type=int, default=None, metavar="N", help="with --blocks: runs of fewer than N k-mers neither "
+                    "join nor break a block (default 1)")
+    sy.add_argument("--max-gap", type=int, default=None, metavar="G", help="with --blocks: a run joins the block of the run before "
+                    "it when it starts at most G positions behind that run's last k-mer, on A and on B (default 1000)")
+    sy.add_argument("--max-shift", type=int, default=None, metavar="S", help="with --blocks: ... and the two distances differ by at "
+                    "most S: the longest insertion or deletion bridged (default 100)")
+    sy.add_argument("--paf", action="store_true", help="with --blocks: PAF lines (query A, target B, matches = k-mers, tags rn:i: "
+                    "runs and sh:i: shifted links) in place of the table")
     sy.add_argument("--summary", metavar="FILE", default=None, help="also write chrA chrB strand segments kmers: the segments and shared "
                     "unique k-mers of every pair of chromosomes and strand, then per chromosome of either side, then in all; in front, "
                     "as # lines, per side the positions whose k-mer is unique in that genome and those with a mate")
@@ -269,22 +282,37 @@ def main(argv=None):
     if a.cmd == "synteny":
         if a.min_len < 1:
             ap.error("synteny: --min-len must be at least 1")
+        if not a.blocks and (a.paf or a.min_run is not None or a.max_gap is not None or a.max_shift is not None):
+            ap.error("synteny: --paf, --min-run, --max-gap and --max-shift need --blocks")
         from .index import Index
         idx = Index(a.index_dir, mode="r", device=a.device)
         try:
             for g in (a.genome_a, a.genome_b):
                 if g not in idx.genomes:
                     ap.error(f"synteny: unknown genome {g!r} (the index has {', '.join(idx.genome_names)})")
+            chroms = [[c for c in s.split(",") if c] or None for s in (a.chroms_a, a.chroms_b)]
             try:
-                out, summary, totals = idx.synteny_tables(a.genome_a, a.genome_b, [c for c in a.chroms_a.split(",") if c] or None,
-                                                     [c for c in a.chroms_b.split(",") if c] or None, a.k, a.min_len)
+                if a.blocks:
+                    out, summary, totals, lens = idx.synteny_blocks_tables(
+                        a.genome_a, a.genome_b, chroms[0], chroms[1], a.k, 1 if a.min_run is None else a.min_run,
+                        1000 if a.max_gap is None else a.max_gap, 100 if a.max_shift is None else a.max_shift, a.min_len)
+                else:
+                    out, summary, totals = idx.synteny_tables(a.genome_a, a.genome_b, chroms[0], chroms[1], a.k, a.min_len)
             except (ValueError, KeyError) as e:
                 ap.error(f"synteny: {e}")
         finally:
             idx.close()
+        from . import synteny
         if a.summary:
-            from . import synteny
             synteny.write_summary(a.summary, summary, totals)
+        if a.paf:
+            f = open(a.output, "w") if a.output else sys.stdout
+            try:
+                f.writelines(line + "\n" for line in synteny.paf_lines(out, *lens))
+            finally:
+                if a.output:
+                    f.close()
+            return 0
         out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
         return 0
     if a.cmd == "patterns":

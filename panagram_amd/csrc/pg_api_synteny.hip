@@ -1,6 +1,8 @@
 // pg_api_synteny.hip — host side of the C-ABI: the position table of two genomes, the mates of A's positions and their collinear
-// runs (pg_synteny.hip).
+// runs (pg_synteny.hip), and the runs chained into blocks (pg_blocks.hip, pg_blocks_host.h).
 #include "pg_host.h"
+
+#include "pg_blocks_host.h"
 
 static constexpr uint64_t POS_MAX_BASES = 0x7FFFFFFFull;  // a side's bases: the word pos << 1 | rc stays below POS_MULTI
 static constexpr uint64_t POS_MAX_KEYS = 1ull << 32;      // two sides of 2^31 k-mers
@@ -37,6 +39,7 @@ struct LaunchTimer {
     }
 };
 thread_local float g_last_ms[5] = {0, 0, 0, 0, 0};  // insert A, insert B, mates, runs (count), runs (emit) of the last pg_synteny_segments
+thread_local float g_blocks_ms[7] = {0, 0, 0, 0, 0, 0, 0};  // those five, blocks (count), blocks (emit) of the last pg_synteny_blocks
 
 // the (contig, chunk) jobs of a seqset's k-mer positions, the base offset of every contig in the concatenation and its first
 // entry in a back-to-back array of k-mer positions
@@ -185,10 +188,21 @@ int postable_mates(pg_postable *pt, const pg_seqset *sq, uint32_t *mates_out, ui
     return PG_OK;
 }
 
-// the runs of a mates array in HBM (ncontigs contigs of nkmers[c] entries, back to back); *mated: the mated positions counted
-int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t ncontigs, const uint64_t *nkmers, uint64_t cap,
-                  uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end, uint32_t *run_mate, uint64_t *nruns, uint64_t *total_out,
-                  uint64_t *mated, float *ms = nullptr) {
+// where the runs of mate_runs_dev go: the caller's four host arrays of `cap` entries under the capacity protocol, or — keep set —
+// all of them into *keep, three planes of the total's words (start, end, mate), which stay in HBM with nothing downloaded
+struct RunsOut {
+    uint64_t cap = 0;
+    uint32_t *contig = nullptr, *start = nullptr, *end = nullptr, *mate = nullptr;
+    DevBuf<uint32_t> *keep = nullptr;
+};
+
+// the runs of a mates array in HBM (ncontigs contigs of nkmers[c] entries, back to back); nruns[c] and *total_out always,
+// *mated: the mated positions counted
+int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t ncontigs, const uint64_t *nkmers, const RunsOut &out,
+                  uint64_t *nruns, uint64_t *total_out, uint64_t *mated, float *ms = nullptr) {
+    DevBuf<uint32_t> *const keep = out.keep;
+    const uint64_t cap = out.cap;
+    uint32_t *const run_contig = out.contig, *const run_start = out.start, *const run_end = out.end, *const run_mate = out.mate;
     std::vector<uint2> contigs(ncontigs), chunks;
     std::vector<uint64_t> first(ncontigs + 1, 0);
     uint64_t tot = 0;
@@ -241,7 +255,7 @@ int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t
     const uint64_t total = nstarts;
     *total_out = total;
     if (mated) *mated = nm;
-    if (total == 0 || cap == 0 || total > cap) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
+    if (total == 0 || (!keep && (cap == 0 || total > cap))) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
     DevBuf<ulonglong2> d_offs;
     DevBuf<uint32_t> d_runs;
     e = d_offs.upload(offs, st);
@@ -251,12 +265,16 @@ int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t
         e = launch_mate_runs(st, d_mates, d_contigs.get(), d_chunks.get(), nchunks, nullptr, d_offs.get(), total, d_runs.get(),
                              d_runs.get() + total, d_runs.get() + 2 * total);
     if (e == hipSuccess) e = te.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(run_start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(run_end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(run_mate, d_runs.get() + 2 * total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !keep) e = hipMemcpyAsync(run_start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !keep) e = hipMemcpyAsync(run_end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !keep) e = hipMemcpyAsync(run_mate, d_runs.get() + 2 * total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     te.read();
+    if (keep) {
+        std::swap(keep->p, d_runs.p);
+        return PG_OK;
+    }
     uint64_t at = 0;
     for (uint32_t c = 0; c < ncontigs; ++c)
         for (uint64_t i = 0; i < nruns[c]; ++i) run_contig[at++] = c;
@@ -266,6 +284,126 @@ int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t
 bool runs_args_ok(uint32_t ncontigs, uint64_t cap, const uint32_t *run_contig, const uint32_t *run_start, const uint32_t *run_end,
                   const uint32_t *run_mate, const uint64_t *nruns, const uint64_t *total) {
     return total && (!ncontigs || nruns) && (!cap || (run_contig && run_start && run_end && run_mate));
+}
+
+struct BlockParams {
+    uint32_t min_run, max_gap, max_shift;
+};
+struct BlockArrays {  // the caller's eight arrays of `cap` entries
+    uint32_t *contig, *start, *end, *mate_first, *mate_last, *kmers, *runs, *shifted;
+    bool all() const { return contig && start && end && mate_first && mate_last && kmers && runs && shifted; }
+};
+
+int block_params_ok(const char *fn, const BlockParams &p) {
+    if (p.min_run < 1) return fail(PG_E_INVALID, "%s: min_run must be at least 1", fn);
+    if (p.max_gap < 1 || p.max_gap > BLOCKS_MAX_GAP) return fail(PG_E_INVALID, "%s: max_gap=%u (1 to 2^31 - 1)", fn, p.max_gap);
+    if (p.max_shift > BLOCKS_MAX_GAP) return fail(PG_E_INVALID, "%s: max_shift=%u (at most 2^31 - 1)", fn, p.max_shift);
+    return PG_OK;
+}
+
+// the blocks of run arrays in HBM (three planes of nruns words: start, end, mate; per_contig[c] runs of contig c of A, back to
+// back); boff: the nb + 1 offsets of B's contigs.  Counts always, the blocks under the capacity protocol.
+int run_blocks_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_runs, uint64_t nruns, uint32_t ncontigs, const uint64_t *per_contig,
+                   const std::vector<uint64_t> &boff, const BlockParams &p, uint64_t cap, const BlockArrays &out, uint64_t *nblocks,
+                   uint64_t *total_out, float *ms = nullptr) {
+    std::vector<uint2> contigs(ncontigs), chunks;
+    std::vector<uint64_t> first(ncontigs + 1, 0);
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < ncontigs; ++c) {
+        contigs[c] = make_uint2((uint32_t)at, (uint32_t)per_contig[c]);
+        first[c] = chunks.size();
+        for (uint64_t r = 0; r < per_contig[c]; r += RUN_CHUNK) chunks.push_back(make_uint2(c, (uint32_t)r));
+        at += per_contig[c];
+        nblocks[c] = 0;
+    }
+    first[ncontigs] = chunks.size();
+    *total_out = 0;
+    if (at != nruns) return fail(PG_E_INVALID, "%s: the contigs hold %llu runs of %llu", fn, (unsigned long long)at, (unsigned long long)nruns);
+    if (chunks.empty()) return PG_OK;
+    const uint32_t nchunks = (uint32_t)chunks.size(), nb = (uint32_t)boff.size();
+    if (int r = use_device(ctx)) return r;
+    hipStream_t st = ctx->stream;
+    DevBuf<uint2> d_contigs, d_chunks;
+    DevBuf<uint64_t> d_boff;
+    DevBuf<BlockChunkCount> d_counts;
+    std::vector<BlockChunkCount> counts(nchunks);
+    LaunchTimer tc(ms), te(ms ? ms + 1 : nullptr);
+    const uint32_t *rs = d_runs, *re = d_runs + nruns, *rm = d_runs + 2 * nruns;
+    hipError_t e = d_contigs.upload(contigs, st);
+    if (e == hipSuccess) e = d_chunks.upload(chunks, st);
+    if (e == hipSuccess) e = d_boff.upload(boff, st);
+    if (e == hipSuccess) e = d_counts.alloc(nchunks);
+    if (e == hipSuccess) e = tc.start(st);
+    if (e == hipSuccess)
+        e = launch_run_blocks(st, rs, re, rm, d_contigs.get(), d_chunks.get(), nchunks, d_boff.get(), nb, p.min_run, p.max_gap,
+                              p.max_shift, d_counts.get(), nullptr, 0, nullptr);
+    if (e == hipSuccess) e = tc.stop(st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(BlockChunkCount), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    tc.read();
+    std::vector<BlockChunkOffs> offs(nchunks);
+    const uint64_t total = blocks_stitch(ncontigs, first.data(), counts.data(), p.max_gap, p.max_shift, boff.data(), nb, offs.data(), nblocks);
+    if (total == ~0ull) return fail(PG_E_HIP, "%s: a contig's block starts and ends differ in number", fn);
+    *total_out = total;
+    if (total == 0 || cap == 0 || total > cap) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
+    DevBuf<BlockChunkOffs> d_offs;
+    DevBuf<uint32_t> d_out;
+    std::vector<uint32_t> rec((size_t)10 * total);
+    e = d_offs.upload(offs, st);
+    if (e == hipSuccess) e = d_out.alloc((size_t)10 * total);
+    if (e == hipSuccess) e = te.start(st);
+    if (e == hipSuccess)
+        e = launch_run_blocks(st, rs, re, rm, d_contigs.get(), d_chunks.get(), nchunks, d_boff.get(), nb, p.min_run, p.max_gap,
+                              p.max_shift, nullptr, d_offs.get(), total, d_out.get());
+    if (e == hipSuccess) e = te.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(rec.data(), d_out.get(), rec.size() * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    te.read();
+    // a block's sums: its end record less its start record
+    const uint32_t *sr = rec.data(), *er = rec.data() + 5 * total;
+    for (uint64_t i = 0; i < total; ++i) {
+        out.start[i] = sr[i];
+        out.mate_first[i] = sr[total + i];
+        out.end[i] = er[i];
+        out.mate_last[i] = er[total + i];
+        out.kmers[i] = er[2 * total + i] - sr[2 * total + i];
+        out.runs[i] = er[3 * total + i] - sr[3 * total + i];
+        out.shifted[i] = er[4 * total + i] - sr[4 * total + i];
+    }
+    at = 0;
+    for (uint32_t c = 0; c < ncontigs; ++c)
+        for (uint64_t i = 0; i < nblocks[c]; ++i) out.contig[at++] = c;
+    return PG_OK;
+}
+
+// the offsets of B's contigs and B's positions; false when they pass 2^32 (no mate word reaches there)
+bool contig_offsets(uint32_t n, const uint64_t *lens, std::vector<uint64_t> &boff) {
+    boff.assign((size_t)n + 1, 0);
+    for (uint32_t c = 0; c < n; ++c) {
+        if (lens[c] > (1ull << 32) || boff[c] + lens[c] > (1ull << 32)) return false;
+        boff[c + 1] = boff[c] + lens[c];
+    }
+    return true;
+}
+
+// a table of `capacity` keys with both sides inserted and the mates of A in its d_mates; freed with the scope
+struct MatedTable {
+    pg_postable *p = nullptr;
+    ~MatedTable() {
+        if (p) postable_free(p);
+    }
+};
+int mated_table(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, uint64_t capacity, MatedTable &pt, uint64_t *nmated,
+                float *ms) {
+    std::unique_ptr<pg_postable> made;
+    if (int r = postable_create(ctx, k, capacity, made)) return r;
+    pt.p = made.release();
+    if (int r = postable_insert(pt.p, 0, seqsA, ms)) return r;
+    if (int r = postable_insert(pt.p, 1, seqsB, ms + 1)) return r;
+    return postable_mates(pt.p, seqsA, nullptr, nmated, ms + 2);
 }
 
 }  // namespace
@@ -321,8 +459,8 @@ extern "C" int pg_mate_runs(pg_ctx *ctx, const uint32_t *mates, uint32_t ncontig
         if (e == hipSuccess) e = hipMemcpyAsync(d_mates.get(), mates, n * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return fail(PG_E_HIP, "pg_mate_runs: %s", hipGetErrorString(e));
     }
-    const int r = mate_runs_dev(ctx, "pg_mate_runs", d_mates.get(), ncontigs, nkmers, cap, run_contig, run_start, run_end, run_mate,
-                                nruns_per_contig, total, nullptr);
+    const RunsOut out{cap, run_contig, run_start, run_end, run_mate, nullptr};
+    const int r = mate_runs_dev(ctx, "pg_mate_runs", d_mates.get(), ncontigs, nkmers, out, nruns_per_contig, total, nullptr);
     if (n) hipStreamSynchronize(ctx->stream);  // (the upload's source is the caller's; the buffer goes with the scope)
     return r;
     PG_API_END
@@ -347,19 +485,12 @@ extern "C" int pg_synteny_segments(pg_ctx *ctx, int k, const pg_seqset *seqsA, c
     for (uint32_t c = 0; c < seqsA->n; ++c) nruns_per_contig[c] = 0;
     std::fill(g_last_ms, g_last_ms + 5, 0.0f);
     if (a.nkmers == 0 || b.nkmers == 0) return PG_OK;  // (no k-mer on one side: no mate)
-    std::unique_ptr<pg_postable> made;
-    if (int r = postable_create(ctx, k, a.nkmers + b.nkmers, made)) return r;
-    struct Guard {
-        pg_postable *p;
-        ~Guard() { postable_free(p); }
-    } pt{made.release()};
+    MatedTable pt;
     float *ms = g_last_ms;
-    if (int r = postable_insert(pt.p, 0, seqsA, ms)) return r;
-    if (int r = postable_insert(pt.p, 1, seqsB, ms + 1)) return r;
-    if (int r = postable_mates(pt.p, seqsA, nullptr, nmated, ms + 2)) return r;
+    if (int r = mated_table(ctx, k, seqsA, seqsB, a.nkmers + b.nkmers, pt, nmated, ms)) return r;
     uint64_t mated = 0;
-    if (int r = mate_runs_dev(ctx, "pg_synteny_segments", pt.p->d_mates, seqsA->n, nk.data(), cap, run_contig, run_start, run_end,
-                              run_mate, nruns_per_contig, total, &mated, ms + 3))
+    const RunsOut out{cap, run_contig, run_start, run_end, run_mate, nullptr};
+    if (int r = mate_runs_dev(ctx, "pg_synteny_segments", pt.p->d_mates, seqsA->n, nk.data(), out, nruns_per_contig, total, &mated, ms + 3))
         return r;
     if (mated != *nmated)  // (two kernels counted the same array)
         return fail(PG_E_HIP, "pg_synteny_segments: %llu mates written, %llu read", (unsigned long long)*nmated, (unsigned long long)mated);
@@ -371,6 +502,104 @@ extern "C" int pg_synteny_last_timing(float *ms_out) {
     PG_API_BEGIN
     if (!ms_out) return fail(PG_E_INVALID, "pg_synteny_last_timing: NULL argument");
     std::copy(g_last_ms, g_last_ms + 5, ms_out);
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_run_blocks(pg_ctx *ctx, const uint32_t *run_contig, const uint32_t *run_start, const uint32_t *run_end,
+                             const uint32_t *run_mate, uint64_t nruns, uint32_t ncontigsA, uint32_t ncontigsB, const uint64_t *lensB,
+                             uint32_t min_run, uint32_t max_gap, uint32_t max_shift, uint64_t cap, uint32_t *blk_contig,
+                             uint32_t *blk_start, uint32_t *blk_end, uint32_t *blk_mate_first, uint32_t *blk_mate_last,
+                             uint32_t *blk_kmers, uint32_t *blk_runs, uint32_t *blk_shifted, uint64_t *nblocks_per_contig,
+                             uint64_t *total) {
+    PG_API_BEGIN
+    const BlockArrays out{blk_contig, blk_start, blk_end, blk_mate_first, blk_mate_last, blk_kmers, blk_runs, blk_shifted};
+    if (!ctx || !total || (ncontigsA && !nblocks_per_contig) || (ncontigsB && !lensB) || (cap && !out.all()) ||
+        (nruns && !(run_contig && run_start && run_end && run_mate)))
+        return fail(PG_E_INVALID, "pg_run_blocks: NULL argument");
+    const BlockParams p{min_run, max_gap, max_shift};
+    if (int r = block_params_ok("pg_run_blocks", p)) return r;
+    if (nruns > POS_MAX_BASES) return fail(PG_E_INVALID, "pg_run_blocks: more than %llu runs", (unsigned long long)POS_MAX_BASES);
+    std::vector<uint64_t> boff;
+    if (!contig_offsets(ncontigsB, lensB, boff)) return fail(PG_E_INVALID, "pg_run_blocks: genome B of more than 2^32 positions");
+    const uint64_t sizeB = boff.back();
+    std::vector<uint64_t> per(ncontigsA, 0);
+    for (uint64_t i = 0; i < nruns; ++i) {
+        const uint64_t c = run_contig[i], s = run_start[i], e = run_end[i], m = run_mate[i];
+        if (c >= ncontigsA) return fail(PG_E_INVALID, "pg_run_blocks: run %llu: contig %llu of %u", (unsigned long long)i, (unsigned long long)c, ncontigsA);
+        if (e <= s) return fail(PG_E_INVALID, "pg_run_blocks: run %llu ends at or before its start", (unsigned long long)i);
+        if (m == NO_MATE) return fail(PG_E_INVALID, "pg_run_blocks: run %llu has no mate", (unsigned long long)i);
+        if (i && (run_contig[i - 1] > c || (run_contig[i - 1] == c && run_end[i - 1] > s)))
+            return fail(PG_E_INVALID, "pg_run_blocks: run %llu: the runs are not sorted by (contig, start), or overlap", (unsigned long long)i);
+        const uint64_t b = m >> 1, n = e - s;
+        if ((m & 1) ? (b < n - 1 || b >= sizeB) : b + (n - 1) >= sizeB)
+            return fail(PG_E_INVALID, "pg_run_blocks: run %llu leaves genome B", (unsigned long long)i);
+        per[c] += 1;
+    }
+    *total = 0;
+    for (uint32_t c = 0; c < ncontigsA; ++c) nblocks_per_contig[c] = 0;
+    if (nruns == 0) return PG_OK;
+    if (int r = use_device(ctx)) return r;
+    DevBuf<uint32_t> d_runs;
+    hipError_t e = d_runs.alloc((size_t)3 * nruns);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_runs.get(), run_start, nruns * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_runs.get() + nruns, run_end, nruns * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_runs.get() + 2 * nruns, run_mate, nruns * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(ctx->stream);
+        return fail(PG_E_HIP, "pg_run_blocks: %s", hipGetErrorString(e));
+    }
+    const int r = run_blocks_dev(ctx, "pg_run_blocks", d_runs.get(), nruns, ncontigsA, per.data(), boff, p, cap, out, nblocks_per_contig, total);
+    hipStreamSynchronize(ctx->stream);  // (the uploads' sources are the caller's; the buffer goes with the scope)
+    return r;
+    PG_API_END
+}
+
+extern "C" int pg_synteny_blocks(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, uint32_t min_run, uint32_t max_gap,
+                                 uint32_t max_shift, uint64_t cap, uint32_t *blk_contig, uint32_t *blk_start, uint32_t *blk_end,
+                                 uint32_t *blk_mate_first, uint32_t *blk_mate_last, uint32_t *blk_kmers, uint32_t *blk_runs,
+                                 uint32_t *blk_shifted, uint64_t *nblocks_per_contig, uint64_t *total, uint64_t *nmated, uint64_t *nruns) {
+    PG_API_BEGIN
+    const BlockArrays out{blk_contig, blk_start, blk_end, blk_mate_first, blk_mate_last, blk_kmers, blk_runs, blk_shifted};
+    if (!ctx || !seqsA || !seqsB || !total || !nmated || !nruns || (seqsA->n && !nblocks_per_contig) || (cap && !out.all()))
+        return fail(PG_E_INVALID, "pg_synteny_blocks: NULL argument");
+    if (k < 1 || k > 32) return fail(PG_E_INVALID, "pg_synteny_blocks: k=%d unsupported (1..32)", k);
+    if (seqsA->ctx != ctx || seqsB->ctx != ctx) return fail(PG_E_INVALID, "pg_synteny_blocks: a seqset of another context");
+    const BlockParams p{min_run, max_gap, max_shift};
+    if (int r = block_params_ok("pg_synteny_blocks", p)) return r;
+    // both sides' limits before anything is launched
+    std::vector<uint64_t> nk(seqsA->n), per(seqsA->n, 0), lensB(seqsB->n), boff;
+    SideWalk a, b;
+    if (int r = walk_side(seqsA, k, "pg_synteny_blocks", a)) return r;
+    if (int r = walk_side(seqsB, k, "pg_synteny_blocks", b)) return r;
+    for (uint32_t c = 0; c < seqsA->n; ++c) nk[c] = seqsA->desc[c].len >= (uint64_t)k ? seqsA->desc[c].len - k + 1 : 0;
+    for (uint32_t c = 0; c < seqsB->n; ++c) lensB[c] = seqsB->desc[c].len;
+    contig_offsets(seqsB->n, lensB.data(), boff);  // (a side of at most 2^31 - 1 bases: checked by walk_side)
+    *total = *nmated = *nruns = 0;
+    for (uint32_t c = 0; c < seqsA->n; ++c) nblocks_per_contig[c] = 0;
+    std::fill(g_blocks_ms, g_blocks_ms + 7, 0.0f);
+    if (a.nkmers == 0 || b.nkmers == 0) return PG_OK;  // (no k-mer on one side: no mate)
+    MatedTable pt;
+    float *ms = g_blocks_ms;
+    if (int r = mated_table(ctx, k, seqsA, seqsB, a.nkmers + b.nkmers, pt, nmated, ms)) return r;
+    uint64_t mated = 0;
+    DevBuf<uint32_t> d_runs;  // the runs: emitted into HBM and read there
+    RunsOut runs_out;
+    runs_out.keep = &d_runs;
+    if (int r = mate_runs_dev(ctx, "pg_synteny_blocks", pt.p->d_mates, seqsA->n, nk.data(), runs_out, per.data(), nruns, &mated, ms + 3))
+        return r;
+    if (mated != *nmated)  // (two kernels counted the same array)
+        return fail(PG_E_HIP, "pg_synteny_blocks: %llu mates written, %llu read", (unsigned long long)*nmated, (unsigned long long)mated);
+    if (*nruns == 0) return PG_OK;
+    return run_blocks_dev(ctx, "pg_synteny_blocks", d_runs.get(), *nruns, seqsA->n, per.data(), boff, p, cap, out, nblocks_per_contig,
+                          total, ms + 5);
+    PG_API_END
+}
+
+extern "C" int pg_synteny_blocks_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_synteny_blocks_last_timing: NULL argument");
+    std::copy(g_blocks_ms, g_blocks_ms + 7, ms_out);
     return PG_OK;
     PG_API_END
 }

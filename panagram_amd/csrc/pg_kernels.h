@@ -2,6 +2,8 @@
 #pragma once
 #include "pg_device.h"
 
+#include "pg_blocks_link.h"
+
 namespace pg {
 
 // Positions per wave-tile.  1024 since round 4: a wave spends a twelfth of a 512-position tile's time before its first
@@ -288,6 +290,17 @@ constexpr uint32_t MATE_CHUNK = 4096;  // positions per chunk, a multiple of 256
 hipError_t launch_mate_runs(hipStream_t st, const uint32_t *mates, const uint2 *contigs, const uint2 *chunks, uint32_t nchunks,
                             uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *run_start, uint32_t *run_end,
                             uint32_t *run_mate);
+// blocks of runs (pg_blocks.hip; the definitions are there): run_start / run_end / run_mate as launch_mate_runs emits them,
+// contigs[c] = {first run of contig c of A, its runs}, chunk = {contig, first run inside it}: the RUN_CHUNK runs from there, a
+// contig's chunks consecutive and in order.  boff: the nb ascending offsets of B's contigs (for the same-contig condition).
+//   offs == NULL  count: counts[c] = the BlockChunkCount of chunk c (its first kept run undecided)
+//   offs != NULL  emit: offs[c] from blocks_stitch (pg_blocks_host.h); out = 10 planes of `total` words: start, mate_first and
+//                 the three sums in front of every block's first run, then end, mate_last and the sums behind its last run
+//                 (entries at or past `total` are never written)
+hipError_t launch_run_blocks(hipStream_t st, const uint32_t *run_start, const uint32_t *run_end, const uint32_t *run_mate,
+                             const uint2 *contigs, const uint2 *chunks, uint32_t nchunks, const uint64_t *boff, uint32_t nb,
+                             uint32_t min_run, uint32_t max_gap, uint32_t max_shift, BlockChunkCount *counts,
+                             const BlockChunkOffs *offs, uint64_t total, uint32_t *out);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

@@ -578,6 +578,70 @@ def synteny_last_timing() -> dict:
     return dict(zip(("insert_a_ms", "insert_b_ms", "mates_ms", "runs_count_ms", "runs_emit_ms"), (float(x) for x in ms)))
 
 
+BLOCK_FIELDS = ("contig", "start", "end", "mate_first", "mate_last", "kmers", "runs", "shifted")
+
+
+def _block_params(min_run, max_gap, max_shift):
+    vals = [int(min_run), int(max_gap), int(max_shift)]
+    if any(not 0 <= v < 1 << 32 for v in vals):  # (the library's own limits are narrower: it answers PG_E_INVALID for those)
+        raise ValueError("min_run, max_gap and max_shift are 32-bit counts")
+    return vals
+
+
+def run_blocks(ctx: Context, run_contig, run_start, run_end, run_mate, ncontigs_a: int, lens_b, min_run: int = 1, max_gap: int = 1000,
+               max_shift: int = 100, cap: Optional[int] = None):
+    """(contig, start, end, mate_first, mate_last, kmers, runs, shifted, blocks per contig of A): the runs of ``mate_runs`` /
+    ``synteny_segments`` chained on the GPU into blocks — maximal chains of runs of at least ``min_run`` k-mers on one strand,
+    each at most ``max_gap`` positions behind its predecessor on both genomes with the two distances at most ``max_shift`` apart,
+    inside one contig of B (``lens_b``: the lengths of B's contigs); the definitions are include/panagram_hip.h's.  Sorted by
+    (contig, start).  ``cap`` (tests of the capacity protocol): ONE call with arrays of ``cap`` entries, returned whole behind
+    the total."""
+    rc, rs, re_, rm = (np.ascontiguousarray(x, np.uint32) for x in (run_contig, run_start, run_end, run_mate))
+    if not (rc.ndim == 1 and rc.shape == rs.shape == re_.shape == rm.shape):
+        raise ValueError("the run arrays differ in length")
+    lb = np.ascontiguousarray(lens_b, np.uint64)
+    params = _block_params(min_run, max_gap, max_shift)
+    per, total = np.zeros(int(ncontigs_a), np.uint64), C.c_uint64()
+
+    def call(n):
+        arrs = [np.full(n, NO_MATE, np.uint32) for _ in range(8)]
+        check(ctx._lib.pg_run_blocks(ctx._h, _ptr(rc), _ptr(rs), _ptr(re_), _ptr(rm), len(rc), len(per), len(lb), _ptr(lb), *params, n,
+                                     *[_ptr(a) if n else None for a in arrs], _ptr(per), C.byref(total)))
+        return arrs
+    if cap is not None:
+        arrs = call(int(cap))
+        return (*arrs, per, int(total.value))
+    call(0)
+    arrs = call(int(total.value))
+    return (*arrs, per)
+
+
+def synteny_blocks(ctx: Context, k: int, seqs_a: SeqSet, seqs_b: SeqSet, min_run: int = 1, max_gap: int = 1000, max_shift: int = 100,
+                   cap: Optional[int] = None):
+    """(the eight block arrays of ``run_blocks``, blocks per contig of A, mated positions of A, runs): the blocks of the unique
+    matches of ``seqs_a`` in ``seqs_b`` — table, mates, runs and blocks in one library call; the mates and the runs never leave
+    HBM.  ``cap``: the blocks expected (a second call follows when there are more)."""
+    params = _block_params(min_run, max_gap, max_shift)
+    per, total, nmated, nruns = np.zeros(len(seqs_a.lens), np.uint64), C.c_uint64(), C.c_uint64(), C.c_uint64()
+    n = int(cap) if cap is not None else 4096
+    while True:
+        arrs = [np.empty(n, np.uint32) for _ in range(8)]
+        check(ctx._lib.pg_synteny_blocks(ctx._h, int(k), seqs_a._h, seqs_b._h, *params, n, *[_ptr(a) if n else None for a in arrs],
+                                         _ptr(per), C.byref(total), C.byref(nmated), C.byref(nruns)))
+        if int(total.value) <= n:
+            break
+        n = int(total.value)
+    return (*[a[:total.value].copy() for a in arrs], per, int(nmated.value), int(nruns.value))
+
+
+def synteny_blocks_last_timing() -> dict:
+    """HIP-event milliseconds of the kernels of this thread's last ``synteny_blocks`` call"""
+    ms = (C.c_float * 7)()
+    check(_lib.load().pg_synteny_blocks_last_timing(ms))
+    return dict(zip(("insert_a_ms", "insert_b_ms", "mates_ms", "runs_count_ms", "runs_emit_ms", "blocks_count_ms", "blocks_emit_ms"),
+                    (float(x) for x in ms)))
+
+
 class PanTable(_Owner):
     """GPU-resident k-mer -> genome-mask table (replaces kmc/bitvec{i})."""
 

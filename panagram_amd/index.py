@@ -1373,10 +1373,9 @@ class Index:
         ``query_bitmap(genome, chrom, start, end, step)`` (``Genome.absence_spectrum``)"""
         return self.genomes[genome].absence_spectrum(genomes, chrom, start, end, step, maxlen)
 
-    def synteny_tables(self, a, b, chroms_a=None, chroms_b=None, k=None, min_len=1):
-        """(segments, summary, totals) of ``synteny``: the summary is ``synteny.summary_frame`` of the segments; the totals
-        (``synteny.totals_frame``) give per side the positions whose k-mer is unique in that genome — each side against itself,
-        two more passes that emit nothing — and those with a mate in the other"""
+    def _synteny_sides(self, a, b, chroms_a, chroms_b, k, run):
+        """``run(k, seqs_a, seqs_b)`` on the two genomes' sequence sets, narrowed to the chosen chromosomes: (its result, k, per
+        side (names, lengths) of the chromosomes taken)"""
         from . import synteny
         k = int(self.k) if k is None else int(k)
         if not 1 <= k <= 32:
@@ -1394,14 +1393,43 @@ class Index:
                     ss = ss.slice([(c, 0, int(ss.lens[c])) for c in pick])
                     made.append(ss)
                 sides.append((ss, [names[c] for c in pick], [int(self.seqset_for(g).lens[c]) for c in pick]))
-            (ss_a, names_a, _), (ss_b, names_b, lens_b) = sides
-            rc, rs, re_, rm, _, nmated = engine.synteny_segments(self.context, k, ss_a, ss_b)
-            unique = [engine.synteny_counts(self.context, k, ss, ss)[1] for ss in (ss_a, ss_b)]
+            (ss_a, names_a, lens_a), (ss_b, names_b, lens_b) = sides
+            got = run(k, ss_a, ss_b)
         finally:
             for ss in made:
                 ss.close()
+        return got, k, (names_a, lens_a), (names_b, lens_b)
+
+    def synteny_tables(self, a, b, chroms_a=None, chroms_b=None, k=None, min_len=1):
+        """(segments, summary, totals) of ``synteny``: the summary is ``synteny.summary_frame`` of the segments; the totals
+        (``synteny.totals_frame``) give per side the positions whose k-mer is unique in that genome — each side against itself,
+        two more passes that emit nothing — and those with a mate in the other"""
+        from . import synteny
+
+        def run(k, ss_a, ss_b):
+            rc, rs, re_, rm, _, nmated = engine.synteny_segments(self.context, k, ss_a, ss_b)
+            return rc, rs, re_, rm, nmated, [engine.synteny_counts(self.context, k, ss, ss)[1] for ss in (ss_a, ss_b)]
+        (rc, rs, re_, rm, nmated, unique), k, (names_a, _), (names_b, lens_b) = self._synteny_sides(a, b, chroms_a, chroms_b, k, run)
         seg = synteny.segment_frame(rc, rs, re_, rm, k, names_a, lens_b, names_b, min_len)
         return seg, synteny.summary_frame(seg), synteny.totals_frame(a, b, unique[0], unique[1], nmated)
+
+    def synteny_blocks_tables(self, a, b, chroms_a=None, chroms_b=None, k=None, min_run=1, max_gap=1000, max_shift=100, min_len=1):
+        """(blocks, summary, totals, lengths) of ``synteny --blocks``: the runs of ``synteny_tables`` chained on the GPU into
+        blocks that bridge substitutions and small insertions and deletions (``engine.synteny_blocks``; the runs never leave
+        HBM) as ``synteny.block_frame`` lays them out — ``min_len`` drops blocks of fewer k-mers; summary and totals as
+        ``synteny_tables``; lengths = per side a dict chromosome -> bases, what ``synteny.paf_lines`` takes"""
+        from . import synteny
+        for name, v, lo in (("min_run", min_run, 1), ("max_gap", max_gap, 1), ("max_shift", max_shift, 0)):
+            if not lo <= int(v) <= 0x7FFFFFFF:
+                raise ValueError(f"synteny: {name}={v} ({lo} to 2^31 - 1)")
+
+        def run(k, ss_a, ss_b):
+            got = engine.synteny_blocks(self.context, k, ss_a, ss_b, min_run, max_gap, max_shift)
+            return got, [engine.synteny_counts(self.context, k, ss, ss)[1] for ss in (ss_a, ss_b)]
+        (got, unique), k, (names_a, lens_a), (names_b, lens_b) = self._synteny_sides(a, b, chroms_a, chroms_b, k, run)
+        blk = synteny.block_frame(*got[:8], k, names_a, lens_b, names_b, min_len)
+        return (blk, synteny.summary_frame(blk), synteny.totals_frame(a, b, unique[0], unique[1], got[9]),
+                (dict(zip(names_a, lens_a)), dict(zip(names_b, lens_b))))
 
     def synteny(self, a, b, chroms_a=None, chroms_b=None, k=None, min_len=1) -> pd.DataFrame:
         """The maximal collinear runs of k-mers that occur exactly once in genome ``a`` and exactly once in genome ``b`` — the
@@ -1409,7 +1437,7 @@ class Index:
         endA chrB startB endB strand kmers``, half-open base ranges, sorted by (chromosome of ``a`` in file order, startA).
         ``chroms_a`` / ``chroms_b`` narrow a side to some chromosomes (uniqueness is then judged among those); ``k`` defaults to
         the index's (any 1..32: the table of all samples' k-mers is not read); ``min_len`` drops runs of fewer k-mers.  Not an
-        alignment: a single mismatch ends a segment, and segments are not chained."""
+        alignment: a single mismatch ends a segment; ``synteny_blocks_tables`` chains the segments into blocks."""
         return self.synteny_tables(a, b, chroms_a, chroms_b, k, min_len)[0]
 
     def region_tree(self, genome, chrom, start=None, end=None, step=None) -> "RegionTree":

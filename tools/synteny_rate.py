@@ -10,7 +10,12 @@ first allocations) and --reps times; each kernel's time is the HIP-event interva
 synchronous call (table allocation and memset, job lists, both launches of k_mate_runs, the read-back of the runs).
 Rates: k-mer positions per second of the side a kernel walks; for k_mate_runs the bytes of the mates array it reads (once per
 launch) per second.  Checked at this size: the mated positions equal the sum of the runs' lengths, the runs are sorted, and
-with d = 0 every chromosome is one run.  Prints one JSON line."""
+with d = 0 every chromosome is one run.  Prints one JSON line.
+
+--blocks adds the blocks (pg_blocks.hip) on the same genomes: engine.synteny_blocks with --min-run / --max-gap / --max-shift, the
+seven kernel times (engine.synteny_blocks_last_timing), the call's wall time, and beside it the wall time of the route without
+k_run_blocks to the same answer: engine.synteny_segments emitting and downloading every run, then the chain built on the host
+with numpy (chain_host below: the link rule on whole arrays, the blocks by np.add.reduceat).  The two answers must be equal."""
 import argparse
 import json
 import os
@@ -52,6 +57,66 @@ def genomes(ctx, mb, ncontigs, d, seed):
     return sets
 
 
+def chain_host(rc, rs, re_, rm, lens_b, min_run, max_gap, max_shift):
+    """the blocks of include/panagram_hip.h from run arrays on the host, vectorised: [n, 8] int64"""
+    rc, rs, re_, rm = (np.asarray(x, np.int64) for x in (rc, rs, re_, rm))
+    n = re_ - rs
+    keep = n >= min_run
+    rc, rs, re_, rm, n = rc[keep], rs[keep], re_[keep], rm[keep], n[keep]
+    if not len(rc):
+        return np.zeros((0, 8), np.int64)
+    strand = rm & 1
+    ml = np.where(strand == 1, rm - 2 * (n - 1), rm + 2 * (n - 1))
+    d_a = rs[1:] - (re_[:-1] - 1)
+    d_b = np.where(strand[1:] == 1, (ml[:-1] >> 1) - (rm[1:] >> 1), (rm[1:] >> 1) - (ml[:-1] >> 1))
+    edges = np.cumsum(np.asarray(lens_b, np.int64))
+    same_b = np.searchsorted(edges, ml[:-1] >> 1, side="right") == np.searchsorted(edges, rm[1:] >> 1, side="right")
+    link = ((rc[1:] == rc[:-1]) & (strand[1:] == strand[:-1]) & (d_a >= 1) & (d_a <= max_gap) & (d_b >= 1) & (d_b <= max_gap) &
+            (np.abs(d_a - d_b) <= max_shift) & same_b)
+    first = np.flatnonzero(np.concatenate([[True], ~link]))
+    last = np.concatenate([first[1:], [len(rc)]]) - 1
+    shifted = np.concatenate([[0], link & (d_a != d_b)]).astype(np.int64)
+    return np.stack([rc[first], rs[first], re_[last], rm[first], ml[last], np.add.reduceat(n, first), last - first + 1,
+                     np.add.reduceat(shifted, first)], axis=1)
+
+
+def blocks_leg(ctx, a, ssa, ssb, out):
+    params = dict(min_run=a.min_run, max_gap=a.max_gap, max_shift=a.max_shift)
+    blk = engine.synteny_blocks(ctx, a.k, ssa, ssb, **params)  # warm
+    cap = len(blk[0])
+    nruns = blk[10]
+    times, calls, host = [], [], []
+    lens_b = [int(n) for n in ssb.lens]
+    for _ in range(a.reps):  # (the two routes in turn)
+        t0 = time.perf_counter()
+        got = engine.synteny_blocks(ctx, a.k, ssa, ssb, cap=cap, **params)
+        calls.append(time.perf_counter() - t0)
+        times.append(engine.synteny_blocks_last_timing())
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(got[:8], blk[:8]))  # the same on every call
+        t0 = time.perf_counter()
+        rc, rs, re_, rm, _, _ = engine.synteny_segments(ctx, a.k, ssa, ssb, cap=nruns)
+        t1 = time.perf_counter()
+        want = chain_host(rc, rs, re_, rm, lens_b, **params)
+        host.append((time.perf_counter() - t0, t1 - t0))
+    have = np.stack(blk[:8], axis=1).astype(np.int64)
+    res = dict(params, blocks=len(have), runs=nruns, runs_per_block=round(nruns / max(1, len(have)), 1),
+               shifted_links=int(have[:, 7].sum()), equal_to_host_chain=bool(have.shape == want.shape and (have == want).all()),
+               bytes_down=dict(blocks=int(have.shape[0]) * 32, runs=int(nruns) * 12))
+    for name in times[0]:
+        v = np.array([t[name] for t in times])
+        res[name] = dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4))
+    for name in ("blocks_count_ms", "blocks_emit_ms"):
+        med = res[name]["median"]
+        res[name]["runs_gb_per_s"] = round(nruns * 12 / med / 1e6, 1) if med > 0 else None
+    res["call_s"] = dict(median=round(float(np.median(calls)), 4), min=round(min(calls), 4), max=round(max(calls), 4))
+    tot, seg = np.array([h[0] for h in host]), np.array([h[1] for h in host])
+    res["host_route_s"] = dict(median=round(float(np.median(tot)), 4), min=round(float(tot.min()), 4), max=round(float(tot.max()), 4),
+                               segments_call_median=round(float(np.median(seg)), 4),
+                               numpy_chain_median=round(float(np.median(tot - seg)), 4))
+    res["gpu_route_faster"] = bool(np.median(calls) < np.median(tot))
+    out["blocks"] = res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mb", type=float, default=100.0)
@@ -60,6 +125,10 @@ def main():
     ap.add_argument("-k", type=int, default=21)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--blocks", action="store_true", help="also time engine.synteny_blocks against the host's chain of the runs")
+    ap.add_argument("--min-run", type=int, default=1)
+    ap.add_argument("--max-gap", type=int, default=1000)
+    ap.add_argument("--max-shift", type=int, default=100)
     a = ap.parse_args()
     ctx = engine.Context(0)
     ssa, ssb = genomes(ctx, a.mb, a.contigs, a.d, a.seed)
@@ -93,6 +162,8 @@ def main():
         med = out[name]["median"]
         out[name]["mates_gb_per_s"] = round(nka * 4 / med / 1e6, 1) if med > 0 else None
     out["call_s"] = dict(median=round(float(np.median(calls)), 4), min=round(min(calls), 4), max=round(max(calls), 4))
+    if a.blocks:
+        blocks_leg(ctx, a, ssa, ssb, out)
     ssa.close()
     ssb.close()
     ctx.close()

@@ -104,7 +104,11 @@ int pg_table_create(pg_ctx *ctx, int k, int ngenomes, uint64_t expected_keys, pg
  * tables (BASELINE configs[4]) — a denser table holds the union of TWO genomes' k-mers in one GPU's HBM, the
  * job takes half the passes over the anchors' positions, and a pass against 3.4-4.5 keys per line is 5-25 % slower, not 100 %
  * (profiles/r6g_config5_blocks.txt).  The table is not grown back to 3 keys per line while it fills.  The reference has one
- * density: KMC's sorted suffix arrays (call site cpp/anchor.cpp:28-31). */
+ * density: KMC's sorted suffix arrays (call site cpp/anchor.cpp:28-31).
+ * With up to 8 genomes the table takes the byte-mask lines (two halves of seven bare keys and seven mask bytes per 128-byte line,
+ * pg_table_stats reports 14 slots per line; keys_per_line and the table's bytes mean what they did; mask
+ * values handed in through pg_table_insert_keys / pg_table_load_kmc keep their low 8 bits, the genomes the table has).
+ * PG_BYTEMASK_LAYOUT=0 in the environment, read at every creation, keeps the 8-slot lines. */
 int pg_table_create_dense(pg_ctx *ctx, int k, int ngenomes, uint64_t expected_keys, double keys_per_line, pg_table **out);
 /* device bytes pg_table_create_dense would allocate (host only; the planner's arithmetic) */
 int pg_table_bytes_for_dense(int k, int ngenomes, uint64_t expected_keys, double keys_per_line, uint64_t *bytes);

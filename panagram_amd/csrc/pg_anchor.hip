@@ -28,7 +28,7 @@
 #include "pg_kernels.h"
 
 // ---- translation units (round 6) ----
-// k_probe and k_insert_tile are instantiated per minimizer window (0, 3..8) x row mode x layout x (fused): 300 kernels, three
+// k_probe and k_insert_tile are instantiated per minimizer window (0, 3..8) x row mode x layout x (fused): 320 kernels, three
 // minutes of hipcc in one unit.  panagram_amd/build.py compiles this file THREE times in parallel, each unit instantiating the
 // windows of its part (probe_part<N> / insert_part<N> below); part 0 also holds the two launchers and the preload.
 // -1 (the default: tools/isa.sh, a -DPG_PHASE_TIMING build, a plain `hipcc pg_anchor.hip`): everything in one unit.
@@ -167,6 +167,65 @@ __device__ __forceinline__ int scan_line_lds(const uint4 *line, uint64_t key, ui
 
 // (a scan without control flow was within 0.5 %: profiles/r4e_ab_probe_scalar_cuts.txt)
 
+// ---- byte-mask layout (up to 8 genomes: two halves of seven bare keys + seven mask bytes, pg_device.h) ----
+// The line is staged as it is; a lane scans the half of its key: four ds_read_b128 bring the seven keys AND, in the eighth word,
+// their mask bytes.  Seven compares into scalar lane masks, folded on the scalar unit into the three bits of the hit's slot number
+// as in scan_line_lds; the hit's byte is cut out of the two mask dwords in registers — no second LDS read.
+// the mask byte of slot b0 + 2 b1 + 4 b2 out of the half's eighth word {lo: the bytes of slots 0..3, hi: of slots 4..6}
+__device__ __forceinline__ uint32_t bm_pick(uint32_t lo, uint32_t hi, bool b0, bool b1, bool b2) {
+    const uint32_t sel = b2 ? hi : lo;
+    const uint32_t sh = (b0 ? 8u : 0u) | (b1 ? 16u : 0u);
+    return __builtin_amdgcn_ubfe(sel, sh, 8u);
+}
+// returns 1 = found, 0 = absent (half not full), -1 = absent from a full half
+// FIRST: several slots may hold the key (k_insert_tile's snapshots, see scan_keys16_lds) — the LOWEST one counts; slot: its number within the half
+template <bool FIRST = false>
+__device__ __forceinline__ int scan_line_bm(const uint4 *line, uint64_t key, uint32_t &m0, uint32_t *slot = nullptr) {
+    const uint4 *half = reinterpret_cast<const uint4 *>(reinterpret_cast<const uint8_t *>(line) + half_offset_of_key(key));
+    const uint4 v0 = half[0], v1 = half[1], v2 = half[2], v3 = half[3];
+    const uint64_t kk[7] = {(uint64_t)v0.x | ((uint64_t)v0.y << 32), (uint64_t)v0.z | ((uint64_t)v0.w << 32), (uint64_t)v1.x | ((uint64_t)v1.y << 32),
+                            (uint64_t)v1.z | ((uint64_t)v1.w << 32), (uint64_t)v2.x | ((uint64_t)v2.y << 32), (uint64_t)v2.z | ((uint64_t)v2.w << 32),
+                            (uint64_t)v3.x | ((uint64_t)v3.y << 32)};
+    unsigned long long e[7];
+#pragma unroll
+    for (int sl = 0; sl < 7; ++sl) e[sl] = __builtin_amdgcn_ballot_w64(kk[sl] == key);
+    if constexpr (FIRST) {
+        unsigned long long seen = e[0];
+#pragma unroll
+        for (int sl = 1; sl < 7; ++sl) {
+            const unsigned long long m = e[sl];
+            e[sl] = m & ~seen;
+            seen |= m;
+        }
+    }
+    const unsigned long long b0 = e[1] | e[3] | e[5], b1 = e[2] | e[3] | e[6], b2 = e[4] | e[5] | e[6];
+    const bool hit = __builtin_amdgcn_inverse_ballot_w64(b0 | b1 | b2 | e[0]);
+    m0 = 0;
+    if (hit) {
+        const bool h0 = __builtin_amdgcn_inverse_ballot_w64(b0), h1 = __builtin_amdgcn_inverse_ballot_w64(b1), h2 = __builtin_amdgcn_inverse_ballot_w64(b2);
+        m0 = bm_pick(v3.z, v3.w, h0, h1, h2);
+        if (slot) *slot = (h0 ? 1u : 0u) | (h1 ? 2u : 0u) | (h2 ? 4u : 0u);
+    }
+    return hit ? 1 : (kk[6] == EMPTY_KEY ? 0 : -1);
+}
+// the half of one line straight from global memory (four 16-byte loads in flight)
+__device__ __forceinline__ int scan_line_global_bm(const SubTable &st, uint32_t b, uint64_t key, uint32_t &m0) {
+    const uint4 *half = reinterpret_cast<const uint4 *>(st.buckets + (uint64_t)b * 128u + half_offset_of_key(key));
+    const uint4 v[4] = {half[0], half[1], half[2], half[3]};
+    const uint64_t mb = (uint64_t)v[3].z | ((uint64_t)v[3].w << 32);  // the seven mask bytes
+    m0 = 0;
+    bool hit = false;
+#pragma unroll
+    for (int sl = 0; sl < 7; ++sl) {
+        const uint64_t kk = (sl & 1) ? ((uint64_t)v[sl / 2].z | ((uint64_t)v[sl / 2].w << 32)) : ((uint64_t)v[sl / 2].x | ((uint64_t)v[sl / 2].y << 32));
+        const bool h = kk == key;
+        m0 = h ? (uint32_t)(mb >> (8 * sl)) & 0xFFu : m0;
+        hit |= h;
+    }
+    const uint64_t last = (uint64_t)v[3].x | ((uint64_t)v[3].y << 32);
+    return hit ? 1 : (last == EMPTY_KEY ? 0 : -1);
+}
+
 // one line straight from global memory: the 8 slot loads are issued together (one latency)
 template <bool TWO, int SLOTS>
 __device__ __forceinline__ int scan_line_global(const SubTable &st, uint32_t b, uint64_t key, uint32_t &m0, uint32_t &m1) {
@@ -187,11 +246,14 @@ __device__ __forceinline__ int scan_line_global(const SubTable &st, uint32_t b, 
 }
 
 // follow a key's probe sequence from its line number `level` (b, step) to the end
-template <bool TWO, int SLOTS>
+template <bool TWO, int SLOTS, bool BM = false>
 __device__ __forceinline__ void lane_chase(const SubTable &st, uint64_t key, uint32_t level, uint32_t b, uint32_t step,
                                            uint32_t &m0, uint32_t &m1) {
     for (uint64_t n = 0; n < st.nbuckets + GROUP_CHAIN; ++n) {
-        if (scan_line_global<TWO, SLOTS>(st, b, key, m0, m1) >= 0) return;
+        if constexpr (BM) {
+            m1 = 0;
+            if (scan_line_global_bm(st, b, key, m0) >= 0) return;
+        } else if (scan_line_global<TWO, SLOTS>(st, b, key, m0, m1) >= 0) return;
         level = min(level + 1, GROUP_CHAIN + 1);
         advance_line(key, level, st.nbuckets, b, step);
     }
@@ -622,7 +684,7 @@ __device__ __forceinline__ void cols_or_position(unsigned long long *cols, uint3
 // by lane.  Two for many-genome tables (narrow windows, big groups: a third of the overflowing keys overflow again); ONE
 // for the wide-window tables of up to 16 genomes, where the second staged level costs more than the few lanes it saves
 // (+1.5 % at configs 1-2, tools/ab_one.sh; -1 % at 64 genomes).
-template <bool TWO, int ROWMODE, int SLOTS, int MAXRUN, bool WIDE, int LEVELS, bool INL = false>
+template <bool TWO, int ROWMODE, int SLOTS, int MAXRUN, bool WIDE, int LEVELS, bool INL = false, bool BM = false>
 __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, const uint64_t *sw, const uint64_t *rw, uint32_t *q_grp,
                                             uint16_t *q_pl, uint32_t *lines_w, uint4 *buf,
                                             uint8_t *tile_rows, uint32_t nbytes, const RowCols rc, int lane) {
@@ -634,7 +696,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
     constexpr int LDS_LINE_U4 = SLOTS + 1;
     constexpr int STAGE_ITERS = (MAXRUN * SLOTS + 63) / 64;
     const uint8_t *chunk_base = st.buckets + (uint32_t)(lane % SLOTS) * 16u;
-    const uint32_t lbytes = INL ? st.layout * 64u : st.slots * (WIDE ? 8u : 16u);  // (= 16 * SLOTS = 128, as a run-time scalar: see k_probe)
+    const uint32_t lbytes = BM ? st.W * 128u : INL ? st.layout * 64u : st.slots * (WIDE ? 8u : 16u);  // (= 16 * SLOTS = 128, as a run-time scalar: see k_probe)
     static_assert(LEVELS >= 1, "k_probe's entries (group, position) get their line and step from level 1's staged batches");
     for (int level = 1; qn > 0; ++level) {
         __syncthreads();
@@ -654,7 +716,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
                     lane_chase_wide(st, key, (uint32_t)level, cl, cs, m0, m1);
                     if (m1) store_row_wide(st.masks, st.W, nbytes, tile_rows + (uint64_t)q_pl[e] * nbytes, m0, m1);
                 } else {
-                    lane_chase<TWO, SLOTS>(st, key, (uint32_t)level, cl, cs, m0, m1);
+                    lane_chase<TWO, SLOTS, BM>(st, key, (uint32_t)level, cl, cs, m0, m1);
                     if constexpr (ROWMODE == 3) cols_or_position(reinterpret_cast<unsigned long long *>(tile_rows), q_pl[e], m0);
                     else if (m0 | m1) store_row<ROWMODE>(tile_rows + (uint64_t)q_pl[e] * nbytes, m0, m1, rc);
                 }
@@ -704,7 +766,7 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
 #pragma unroll
                 for (int u = 0; u < STAGE_ITERS; ++u) {
                     const uint32_t idx = u * 64 + lane;
-                    if constexpr (WIDE) buf[(idx / SLOTS) * LDS_LINE_U4 + (idx % SLOTS)] = v[u];  // (bare keys: as they are)
+                    if constexpr (WIDE || BM) buf[(idx / SLOTS) * LDS_LINE_U4 + (idx % SLOTS)] = v[u];  // (bare keys: as they are)
                     else stage_chunk(buf + (idx / SLOTS) * LDS_LINE_U4, idx % SLOTS, SLOTS, v[u]);
                 }
                 __syncthreads();
@@ -715,6 +777,8 @@ __device__ __forceinline__ void drain_queue(const SubTable &st, uint32_t qn, con
                     } else if constexpr (WIDE) {
                         rcode = scan_keys16_lds(buf + (rid - r0) * LDS_LINE_U4, key, m1);
                         m0 = line;
+                    } else if constexpr (BM) {
+                        rcode = scan_line_bm(buf + (rid - r0) * LDS_LINE_U4, key, m0);
                     } else {
                         rcode = scan_line_lds<TWO, SLOTS>(buf + (rid - r0) * LDS_LINE_U4, key, m0, m1);
                     }
@@ -990,7 +1054,9 @@ constexpr bool probe_pipelined = SLOTS == 8 && !WIDE && ROWMODE != 3 && (ROWMODE
 // split-layout instantiations took 92 and 105 (their lane masks live on the scalar unit): 7 and 6 waves.  Held to 80, a dozen
 // masks move to vector lanes and the ninth to 63rd genome gain 3-6 % (27 x 40 Mb 140 -> 148 G k-mers/s).
 // FUSE: the tile ends with its statistics (tile_statistics above; `fo` says where they go)
-template <int W_C, bool TWO, int ROWMODE, int SLOTS, bool M64, bool WIDE = false, bool INL = false, bool FUSE = false>
+// BM: the byte-mask layout (SLOTS = 8 counts the 16-byte chunks of a line, as for WIDE; TWO false; ROWMODE 1 — pipelined, held to
+// 8 waves like the 8-slot one-byte probe — or 3, whose column words in LDS admit 6 waves per SIMD whatever the registers)
+template <int W_C, bool TWO, int ROWMODE, int SLOTS, bool M64, bool WIDE = false, bool INL = false, bool FUSE = false, bool BM = false>
 __global__ __launch_bounds__(64, ((probe_pipelined<TWO, ROWMODE, SLOTS, WIDE> || INL || FUSE) ? 8 : 1))
 __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint64_t *__restrict__ seqw,
                                               const uint32_t *__restrict__ nmw, const uint32_t *__restrict__ has_n,
@@ -1078,7 +1144,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
     uint32_t qn = 0;  // wave-uniform: overflow entries of this tile so far
 
     const uint8_t *chunk_base = st.buckets + (uint32_t)(lane % SLOTS) * 16u;  // this lane's 16-byte chunk of line 0
-    const uint32_t lbytes = INL ? st.layout * 64u : st.slots * (WIDE ? 8u : 16u);  // bytes per line (= 16 * SLOTS = 128), as a run-time scalar (inline layout: LAYOUT_INLINE * 64)
+    const uint32_t lbytes = BM ? st.W * 128u : INL ? st.layout * 64u : st.slots * (WIDE ? 8u : 16u);  // bytes per line (= 16 * SLOTS = 128), as a run-time scalar (inline layout: LAYOUT_INLINE * 64; byte-mask: W = 1)
 
     // A batch in three parts, so that the front end of batch i + 1 can run while the table lines of batch i are on
     // their way: the fetch is the longest wait of a batch — a couple of thousand cycles behind a busy
@@ -1248,7 +1314,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
             uint4 *const mine = buf[0] + ((uint32_t)lane / SLOTS) * LDS_LINE_U4;
 #pragma unroll
             for (int it = 0; it < STAGE_ITERS; ++it) {
-                if constexpr (WIDE) mine[it * (64 / SLOTS) * LDS_LINE_U4 + ((uint32_t)lane % SLOTS)] = S.v[it];  // (bare keys: as they are)
+                if constexpr (WIDE || BM) mine[it * (64 / SLOTS) * LDS_LINE_U4 + ((uint32_t)lane % SLOTS)] = S.v[it];  // (bare keys: as they are)
                 else stage_chunk(mine + it * (64 / SLOTS) * LDS_LINE_U4, (uint32_t)lane % SLOTS, SLOTS, S.v[it]);
             }
             __syncthreads();
@@ -1268,6 +1334,8 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
                 } else if constexpr (WIDE) {
                     rcode = scan_keys16_lds(buf[0] + (f.rid - r0) * LDS_LINE_U4, f.key, m1);
                     m0 = f.line;
+                } else if constexpr (BM) {
+                    rcode = scan_line_bm(buf[0] + (f.rid - r0) * LDS_LINE_U4, f.key, m0);
                 } else {
                     rcode = scan_line_lds<TWO, SLOTS>(buf[0] + (f.rid - r0) * LDS_LINE_U4, f.key, m0, m1);
                 }
@@ -1467,7 +1535,7 @@ __attribute__((amdgpu_num_sgpr(80))) void k_probe(const SubTable st, const uint6
     }
     PG_PH(7)
     for (;;) {
-        drain_queue<TWO, ROWMODE, SLOTS, MAXRUN, WIDE, LEVELS, INL>(st, qn, sw, rw, q_grp, q_pl, lines_w[0], buf[0], tile_rows, nbytes, rc, lane);
+        drain_queue<TWO, ROWMODE, SLOTS, MAXRUN, WIDE, LEVELS, INL, BM>(st, qn, sw, rw, q_grp, q_pl, lines_w[0], buf[0], tile_rows, nbytes, rc, lane);
         qn = 0;
         if (b0 >= npos) break;
         __syncthreads();
@@ -1541,7 +1609,13 @@ constexpr int INSERT_QCAP = 256;
 template <bool COUNT, bool CLAIM = true>
 __device__ __forceinline__ int wave_insert_batch(const SubTable &st, bool valid, uint64_t key, uint32_t grp, int w, uint32_t bits,
                                                  uint32_t max_probe, int lane) {
-    const uint32_t kstride = key_stride(st), slots = st.slots;
+    // (byte-mask layout: the walk sees the key's HALF of every line — seven keys at `hoff`, slots numbered 0..6 within it; lanes of a
+    // run whose keys live in different halves aim at different addresses and form groups of their own below)
+    const bool bm = st.layout == LAYOUT_BYTEMASK;
+    const uint32_t kstride = key_stride(st), slots = bm ? BM_HALF_KEYS : st.slots, hoff = bm ? half_offset_of_key(key) : 0u;
+    auto slot_key = [&](uint32_t line, uint32_t sl) __attribute__((always_inline)) {
+        return reinterpret_cast<unsigned long long *>(st.buckets + (uint64_t)line * line_bytes(st) + hoff + kstride * sl);
+    };
     uint32_t b = home_of_group(grp, st.nbuckets), step = step_of_group(grp, st.nbuckets), probes = 0;
     int s = -1;  // slot to try next in line b; -1: the line has not been read yet; slots: the line is full
     bool done = !valid, fresh = false;  // fresh: the line has just been read, s is its first empty slot
@@ -1550,6 +1624,12 @@ __device__ __forceinline__ int wave_insert_batch(const SubTable &st, bool valid,
         return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, src) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src) << 32);
     };
     auto resolve = [&](uint32_t sl, bool claimed) __attribute__((always_inline)) {
+        if (bm) {  // (never a counting table: pg_api.hip)
+            mask_byte_or<false>(st.buckets + (uint64_t)b * 128u + hoff + BM_MASK0 + sl, bits, claimed);
+            r = claimed ? 1 : 0;
+            done = true;
+            return;
+        }
         uint32_t *mp = mask_ptr(st, b, sl, (uint32_t)w);
         if (COUNT) {
             if (*mp < 0xFFFFFF00u) atomicAdd(mp, bits);  // saturates far above any -ci threshold
@@ -1573,7 +1653,7 @@ __device__ __forceinline__ int wave_insert_batch(const SubTable &st, bool valid,
             }
         }
         if (!done && s < 0) {  // read the line: the key itself, or the first empty slot (lines fill front to back)
-            uint8_t *base = st.buckets + (uint64_t)b * line_bytes(st);
+            uint8_t *base = st.buckets + (uint64_t)b * line_bytes(st) + hoff;
             int hit = -1, fr = -1;
             for (uint32_t s0 = 0; s0 < slots; s0 += 8) {
                 uint64_t kk[8];
@@ -1613,7 +1693,7 @@ __device__ __forceinline__ int wave_insert_batch(const SubTable &st, bool valid,
             const bool sp = !done && fresh && s < (int)slots;
             const unsigned long long spmask = __ballot(sp);
             if (spmask) {
-                const uint64_t gaddr = sp ? reinterpret_cast<uint64_t>(key_ptr(st, b, (uint32_t)s)) : 0;  // (line, first empty slot)
+                const uint64_t gaddr = sp ? reinterpret_cast<uint64_t>(slot_key(b, (uint32_t)s)) : 0;  // (line, first empty slot)
                 const uint64_t gprev = (uint64_t)(uint32_t)__shfl_up((int)(uint32_t)gaddr, 1) | ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(gaddr >> 32), 1) << 32);
                 const bool gl = sp && (lane == 0 || gprev != gaddr);
                 const unsigned long long glmask = __ballot(gl);
@@ -1627,7 +1707,7 @@ __device__ __forceinline__ int wave_insert_batch(const SubTable &st, bool valid,
                 uint64_t content = 0;
                 bool won = false;
                 if (part) {
-                    const unsigned long long cur = atomicCAS(key_ptr(st, b, (uint32_t)t), (unsigned long long)EMPTY_KEY, (unsigned long long)key);
+                    const unsigned long long cur = atomicCAS(slot_key(b, (uint32_t)t), (unsigned long long)EMPTY_KEY, (unsigned long long)key);
                     won = cur == EMPTY_KEY;
                     content = won ? key : cur;
                 }
@@ -1639,7 +1719,7 @@ __device__ __forceinline__ int wave_insert_batch(const SubTable &st, bool valid,
                 if (sp) {
                     if (pos >= 0) {
                         const bool mine = part && won && pos == t;
-                        if (part && won && pos != t) *reinterpret_cast<volatile unsigned long long *>(key_ptr(st, b, (uint32_t)t)) = TOMB_KEY;
+                        if (part && won && pos != t) *reinterpret_cast<volatile unsigned long long *>(slot_key(b, (uint32_t)t)) = TOMB_KEY;
                         resolve((uint32_t)pos, mine);
                     } else {
                         s += (int)mm;  // other keys all the way: on behind them, one slot per round from here
@@ -1650,7 +1730,7 @@ __device__ __forceinline__ int wave_insert_batch(const SubTable &st, bool valid,
         fresh = false;
         // one compare-and-swap round among the lanes that have a slot to try
         const bool want = !done && s >= 0 && s < (int)slots;
-        unsigned long long *kp = want ? key_ptr(st, b, (uint32_t)s) : nullptr;
+        unsigned long long *kp = want ? slot_key(b, (uint32_t)s) : nullptr;
         const uint64_t addr = reinterpret_cast<uint64_t>(kp);
         const uint64_t prev = (uint64_t)(uint32_t)__shfl_up((int)(uint32_t)addr, 1) | ((uint64_t)(uint32_t)__shfl_up((int)(uint32_t)(addr >> 32), 1) << 32);
         const bool leader = want && (lane == 0 || prev != addr);  // (a lane without a slot to try carries address 0)
@@ -1825,6 +1905,15 @@ __global__ __launch_bounds__(64) void k_insert_tile(const SubTable st, int w, ui
                         mp = reinterpret_cast<uint32_t *>(st.masks) + ((uint64_t)line * SPLIT_KEYS + (slot1 - 1u)) * st.W + (uint32_t)w;
                         cur = *reinterpret_cast<const volatile uint32_t *>(mp);
                     }
+                } else if (st.layout == LAYOUT_BYTEMASK) {  // (uniform) the key's half of the snapshot; the genome's bit goes into the slot's mask BYTE
+                    uint32_t mb, slot = 0;
+                    const int rcode = scan_line_bm<true>(ln, key, mb, &slot);
+                    full = rcode < 0;
+                    found = rcode > 0;
+                    // (found with the bit missing: a byte store — never the dword, whose other bytes are other slots'; every writer of
+                    // this byte during the launch ORs in the same bits.  mp stays null: byte-mask tables never count)
+                    if (found && (mb & bits) != bits)
+                        *reinterpret_cast<volatile uint8_t *>(st.buckets + (uint64_t)line * 128u + half_offset_of_key(key) + BM_MASK0 + slot) = (uint8_t)(mb | bits);
                 } else {
                     uint32_t m0, m1;
                     // (the slot's byte offset is what is needed here: scan the keys like scan_line_lds does)
@@ -1856,7 +1945,7 @@ __global__ __launch_bounds__(64) void k_insert_tile(const SubTable st, int w, ui
                         mp = reinterpret_cast<uint32_t *>(st.buckets + (uint64_t)line * 128u + off + 8 + 4 * w);
                     }
                 }
-                if (found) {
+                if (found && mp) {
                     if (count_mode) {
                         if (cur < 0xFFFFFF00u) atomicAdd(mp, bits);
                     } else if ((cur & bits) != bits) {
@@ -1950,6 +2039,17 @@ static hipError_t probe_w(hipStream_t s, uint32_t ntiles, const SubTable &st, co
                 if (m64) hipLaunchKernelGGL((k_probe<W_C, false, 0, 8, true, true>), dim3(ntiles), dim3(64), 0, PG_K, none);
                 else hipLaunchKernelGGL((k_probe<W_C, false, 0, 8, false, true>), dim3(ntiles), dim3(64), 0, PG_K, none);
             }
+        }
+        return hipGetLastError();
+    }
+    if (st.layout == LAYOUT_BYTEMASK) {  // up to 8 genomes: one-byte rows, or the sharded mode's bit columns — nothing else occurs
+        if (fuse || (rowmode != 1 && rowmode != 3)) return hipErrorInvalidValue;
+        if (rowmode == 1) {
+            if (m64) hipLaunchKernelGGL((k_probe<W_C, false, 1, 8, true, false, false, false, true>), dim3(ntiles), dim3(64), 0, PG_K, none);
+            else hipLaunchKernelGGL((k_probe<W_C, false, 1, 8, false, false, false, false, true>), dim3(ntiles), dim3(64), 0, PG_K, none);
+        } else {
+            if (m64) hipLaunchKernelGGL((k_probe<W_C, false, 3, 8, true, false, false, false, true>), dim3(ntiles), dim3(64), 0, PG_K, none);
+            else hipLaunchKernelGGL((k_probe<W_C, false, 3, 8, false, false, false, false, true>), dim3(ntiles), dim3(64), 0, PG_K, none);
         }
         return hipGetLastError();
     }
@@ -2058,7 +2158,7 @@ static int row_mode(uint32_t nbytes, const RowCols &rc) {
     return 0;
 }
 
-// columns_width != 0: the genome-sharded mode's narrow tables (up to 8 genomes, 8-slot lines) emit the block's bit
+// columns_width != 0: the genome-sharded mode's narrow tables (up to 8 genomes, 8-slot or byte-mask lines) emit the block's bit
 // columns (`columns_width` genomes wide) into `out1` instead of rows
 hipError_t launch_anchor(hipStream_t s, const TableDesc &T, const uint64_t *seqw, const uint32_t *nmw,
                          const uint32_t *has_n, const SeqDesc *sd, const AnchorDesc *ad, const uint32_t *tile_contig,
@@ -2074,7 +2174,7 @@ hipError_t launch_anchor(hipStream_t s, const TableDesc &T, const uint64_t *seqw
         return hipErrorInvalidValue;
     if (columns_width) {
         const SubTable &st = T.sub[0];
-        if (T.nsub != 1 || st.layout != LAYOUT_SLOTS || st.W != 1 || st.slots != 8 || T.ngenomes > (uint32_t)COLS_G ||
+        if (T.nsub != 1 || !((st.layout == LAYOUT_SLOTS && st.slots == 8) || st.layout == LAYOUT_BYTEMASK) || st.W != 1 || T.ngenomes > (uint32_t)COLS_G ||
             columns_width > (uint32_t)COLS_G || columns_width < T.ngenomes)
             return hipErrorInvalidValue;
         RowCols rc;

@@ -327,8 +327,21 @@ struct TableGeom {
 };
 // 65..96 genomes (W = 3): the inline layout — 6 keys per 128-byte line with their mask blocks behind them (5 at W = 4: kept for experiments), no
 // dependent gather (PG_WIDE_LAYOUT=split: the split layout for them too, rounds 2-4; PG_WIDE_LAYOUT=inline: the default)
-static TableGeom geom_for(int ngenomes) {
+// Up to 8 genomes in a table created for a known density (`dense`: pg_table_create_dense — Index.build_table, the sharded planner's
+// block tables): the byte-mask layout, two halves of seven bare keys and their mask bytes per 128-byte line (pg_device.h).  Plain
+// pg_table_create keeps the 8-slot lines.  PG_BYTEMASK_LAYOUT=0, read at every creation: the 8-slot lines for dense tables too
+// (A/B runs, tests).
+static bool bytemask_wanted() {
+    const char *e = getenv("PG_BYTEMASK_LAYOUT");
+    return !(e && *e) || atoi(e) != 0;
+}
+// slots of a line that the per-slot loads (TARGET_LOAD, GROW_AT, HARD_LOAD, keys_per_line / 8) count on: a byte-mask line is
+// sized and grown like the 8-slot line it replaces — keys_per_line keeps meaning keys per 128-byte line, a table's bytes for a
+// given density do not change
+static uint32_t load_slots(uint32_t layout, uint32_t slots) { return layout == LAYOUT_BYTEMASK ? 8u : slots; }
+static TableGeom geom_for(int ngenomes, bool dense = false) {
     const uint32_t ndbs = (uint32_t)(ngenomes + 31) / 32;
+    if (dense && ngenomes <= 8 && bytemask_wanted()) return {1u, BM_SLOTS, LAYOUT_BYTEMASK};
     if (ndbs <= 2) return {ndbs, 8u, LAYOUT_SLOTS};
     static const int want_inline = [] {  // 0: never, 1: W = 3 (the default), 2: W = 4 too (experiments: PG_WIDE_LAYOUT=inline4)
         const char *e = getenv("PG_WIDE_LAYOUT");
@@ -378,9 +391,9 @@ extern "C" int pg_table_bytes_for_dense(int k, int ngenomes, uint64_t expected_k
     PG_API_BEGIN
     if (!bytes) return fail(PG_E_INVALID, "pg_table_bytes_for_dense: NULL argument");
     if (k < 1 || k > 32 || ngenomes < 1 || !(keys_per_line >= 1.0 && keys_per_line <= 6.4)) return fail(PG_E_INVALID, "pg_table_bytes_for_dense: bad argument");
-    const TableGeom g = geom_for(ngenomes);  // (keys_per_line counts per 8 slots: a load of keys_per_line / 8 whatever the line holds)
-    const uint64_t nb = std::max<uint64_t>((uint64_t)((double)std::max<uint64_t>(expected_keys, 1ull << 18) / (keys_per_line / 8.0 * g.slots)) + 1, 64);
-    *bytes = g.layout == LAYOUT_SPLIT ? nb * g.slots * (8ull + 4ull * g.W) : g.layout == LAYOUT_INLINE ? nb * 128ull : nb * 16ull * g.slots;
+    const TableGeom g = geom_for(ngenomes, true);  // (keys_per_line counts per 8 slots: a load of keys_per_line / 8 whatever the line holds)
+    const uint64_t nb = std::max<uint64_t>((uint64_t)((double)std::max<uint64_t>(expected_keys, 1ull << 18) / (keys_per_line / 8.0 * load_slots(g.layout, g.slots))) + 1, 64);
+    *bytes = g.layout == LAYOUT_SPLIT ? nb * g.slots * (8ull + 4ull * g.W) : (g.layout == LAYOUT_INLINE || g.layout == LAYOUT_BYTEMASK) ? nb * 128ull : nb * 16ull * g.slots;
     return PG_OK;
     PG_API_END
 }
@@ -413,14 +426,14 @@ static int table_create(pg_ctx *ctx, int k, int ngenomes, uint64_t expected_keys
         t->h_counters = nullptr;  // (read_counters then lands in the caller's pageable memory)
     }
     {
-        const TableGeom g = geom_for(ngenomes);
+        const TableGeom g = geom_for(ngenomes, keys_per_line >= 1.0);
         const uint64_t want = expected_keys ? expected_keys : (1ull << 18);
         // keys per line the table is created for: 3 of 8 slots (TARGET_LOAD) unless PG_TABLE_KEYS_PER_LINE says otherwise (a
         // tuning knob, 1..6.4 keys per 8 slots; the genome-sharded planner's block tables: distributed.py)
         const double load = create_load(expected_keys, keys_per_line);
         t->load0 = load;
         // (pg_table_rehash may widen the lines of the slots layout when the keys call for it)
-        const uint64_t nb = (uint64_t)((double)want / (load * g.slots)) + 1;
+        const uint64_t nb = (uint64_t)((double)want / (load * load_slots(g.layout, g.slots))) + 1;
         SubHost sh;
         sh.count = 0;
         int r = alloc_sub(ctx, g.W, 0, (uint32_t)k, t->m, g.slots, nb, g.layout, &sh.d);
@@ -610,7 +623,7 @@ static int regrow(pg_table *t, int si, uint64_t nb, uint32_t slots = 0) {
 
 int pg::ensure_room(pg_table *t, int si, uint64_t incoming) {
     SubHost &s = t->subs[si];
-    const int ns = (int)s.d.slots;
+    const int ns = (int)load_slots(s.d.layout, s.d.slots);
     const double slots = (double)s.d.nbuckets * ns;
     // `incoming` counts positions, an upper bound on new keys.  A table created for a known number of
     // distinct keys (pg_table_create's expected_keys, e.g. from a pg_sketch) is trusted while its
@@ -637,7 +650,7 @@ int pg::grow_after_overflow(pg_table *t, int si, uint64_t incoming) {
 
 int pg::after_insert(pg_table *t, int si) {
     SubHost &s = t->subs[si];
-    const int ns = (int)s.d.slots;
+    const int ns = (int)load_slots(s.d.layout, s.d.slots);
     // (a table created denser on purpose — the genome-sharded mode's block tables: fewer passes — is not grown back to 3 keys per line)
     if ((double)s.count > std::max(GROW_AT, t->load0 + 0.1) * (double)s.d.nbuckets * ns) {
         uint64_t nb = (uint64_t)((double)s.count / (TARGET_LOAD * ns)) + 1;
@@ -654,6 +667,7 @@ int pg::after_insert(pg_table *t, int si) {
 static int enqueue_insert(pg_table *t, const SubTable &d, int w, uint32_t bits, int count_mode, const pg_seqset *sq,
                           unsigned long long *counters) {
     hipStream_t st = t->ctx->stream;
+    if ((count_mode & 1) && d.layout == LAYOUT_BYTEMASK) return fail(PG_E_INVALID, "occurrence counts need mask words: not a byte-mask table");
     const bool tiles_ok = d.layout != LAYOUT_SLOTS || d.slots == 8;
     if (!tiles_ok || getenv("PG_INSERT_PER_THREAD")) {
         for (uint32_t c = 0; c < sq->n; ++c) {
@@ -893,7 +907,8 @@ extern "C" int pg_table_rehash(pg_table *t, double keys_per_bucket) {
     uint64_t keys = 0, spilled = 0;
     for (size_t si = 0; si < t->subs.size(); ++si) {
         if (t->subs[si].d.layout != LAYOUT_SLOTS) slots = t->subs[si].d.slots;  // (split and inline lines keep their geometry)
-        const double kpb = std::min(keys_per_bucket * (slots / 8.0), 0.8 * slots);  // keys per line
+        const uint32_t lslots = load_slots(t->subs[si].d.layout, slots);  // (a byte-mask line counts as the 8-slot line it replaces)
+        const double kpb = std::min(keys_per_bucket * (lslots / 8.0), 0.8 * lslots);  // keys per line
         if (int r = regrow(t, (int)si, (uint64_t)((double)t->subs[si].count / kpb) + 1, slots)) return r;
         uint64_t sp = 0;
         if (int r = count_spill(t, (int)si, &sp)) return r;
@@ -1577,8 +1592,8 @@ extern "C" int pg_result_columns_direct(const pg_result *r, uint32_t width) {
     PG_API_BEGIN
     if (!r || !r->tbl) return 0;
     const pg_table *t = r->tbl;
-    return t->subs.size() == 1 && t->subs[0].d.layout == LAYOUT_SLOTS && t->subs[0].d.W == 1 && t->subs[0].d.slots == 8 &&
-           t->ngenomes <= 8 && width <= 8 && (int)width >= t->ngenomes;
+    return t->subs.size() == 1 && ((t->subs[0].d.layout == LAYOUT_SLOTS && t->subs[0].d.slots == 8) || t->subs[0].d.layout == LAYOUT_BYTEMASK) &&
+           t->subs[0].d.W == 1 && t->ngenomes <= 8 && width <= 8 && (int)width >= t->ngenomes;
     PG_API_END
 }
 

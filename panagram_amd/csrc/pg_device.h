@@ -1,6 +1,7 @@
 // pg_device.h — device-side building blocks shared by the gfx950 kernels.
 //
-// Table layout (up to 64 genomes: one sub-table of W = 1 or 2 mask words per slot, described here; 65..96 genomes: ONE table in
+// Table layout (up to 64 genomes: one sub-table of W = 1 or 2 mask words per slot, described here; up to 8 genomes in a table created
+// for a known density: the byte-mask layout, two halves of seven bare keys and seven mask bytes per line — LAYOUT_BYTEMASK below; 65..96 genomes: ONE table in
 // the inline layout — 6 bare keys and their mask blocks in one line; more genomes: ONE table in the split layout — bare keys
 // in the lines, all mask words of a slot in a second array — see SubTable):
 //   line   = 128 bytes, 128-byte aligned: MI355X moves 128 B per random HBM access whatever
@@ -52,18 +53,30 @@ struct SubTable {
     uint32_t k;
     uint32_t m;         // minimizer length (0 = hash the whole k-mer)
     uint32_t slots;     // slots (keys) per line: 8 or 16
-    uint32_t layout;    // LAYOUT_SLOTS / LAYOUT_SPLIT
+    uint32_t layout;    // LAYOUT_SLOTS / LAYOUT_SPLIT / LAYOUT_INLINE / LAYOUT_BYTEMASK
     uint8_t *masks;     // LAYOUT_SPLIT only
 };
-constexpr uint32_t LAYOUT_SLOTS = 0, LAYOUT_SPLIT = 1, LAYOUT_INLINE = 2;
+constexpr uint32_t LAYOUT_SLOTS = 0, LAYOUT_SPLIT = 1, LAYOUT_INLINE = 2, LAYOUT_BYTEMASK = 3;
 constexpr uint32_t SPLIT_KEYS = 16;  // keys per line of the split layout
 //   LAYOUT_INLINE (65..128 genomes, round 5): a 128-byte line = S bare keys followed by the S slots' mask blocks of W words —
 //                S = 6 at W = 3 (48 + 72 bytes), S = 5 at W = 4 (40 + 80 bytes): ONE fetch brings a hit's mask words with its
 //                key, where the split layout's probe follows its key line with a dependent, divergent gather
 __host__ __device__ __forceinline__ uint32_t inline_slots(uint32_t W) { return 120u / (8u + 4u * W); }
+//   LAYOUT_BYTEMASK (up to 8 genomes, tables created for a known density): a 128-byte line = two 64-byte HALVES, each seven bare
+//                keys (bytes 0..55), their seven mask BYTES (bytes 56..62, bit g = genome g) and one unused byte.  A key lives in
+//                half half_offset_of_key(key) of every line of its probe sequence: a half fills front to back, is full when its seventh
+//                key is not EMPTY, and a look-up ends at the first line whose half is not full.  Slots are numbered 0..13
+//                through the two halves (st.slots == 14).  A minimizer group of 8 genomes (4-7 positions x their SNP variants)
+//                outgrows 8 slots far more often than 2 x 7: a slot of the slots layout spends 7 of its 16 bytes on nothing.
+constexpr uint32_t BM_HALF_KEYS = 7, BM_SLOTS = 2 * BM_HALF_KEYS, BM_HALF_BYTES = 64, BM_MASK0 = 8 * BM_HALF_KEYS;
+// the half of a key: the parity of its 64 bits (xor, bit count, and, shift: four full-rate instructions; the top bit of
+// (lo ^ hi) * 0x9E3779B1 spreads the keys as evenly and costs a quarter-rate multiply) — as the half's byte offset in the line
+__host__ __device__ __forceinline__ uint32_t half_offset_of_key(uint64_t key) {
+    return ((uint32_t)__builtin_popcount((uint32_t)key ^ (uint32_t)(key >> 32)) & 1u) * BM_HALF_BYTES;
+}
 
 __host__ __device__ __forceinline__ uint32_t line_bytes(const SubTable &st) {
-    return st.layout == LAYOUT_INLINE ? 128u : (st.layout == LAYOUT_SPLIT ? 8u : 16u) * st.slots;
+    return (st.layout == LAYOUT_INLINE || st.layout == LAYOUT_BYTEMASK) ? 128u : (st.layout == LAYOUT_SPLIT ? 8u : 16u) * st.slots;
 }
 // bytes from one key of a line to the next
 __host__ __device__ __forceinline__ uint32_t key_stride(const SubTable &st) { return st.layout == LAYOUT_SLOTS ? 16u : 8u; }
@@ -71,12 +84,44 @@ __host__ __device__ __forceinline__ uint64_t table_bytes(const SubTable &st) {
     return st.nbuckets * line_bytes(st) + (st.layout == LAYOUT_SPLIT ? st.nbuckets * st.slots * 4ull * st.W : 0ull);
 }
 __device__ __forceinline__ unsigned long long *key_ptr(const SubTable &st, uint64_t line, uint32_t s) {
+    if (st.layout == LAYOUT_BYTEMASK) s += s >= BM_HALF_KEYS ? 1u : 0u;  // (slot 7.. = the second half: the eighth word of a half holds its mask bytes)
     return reinterpret_cast<unsigned long long *>(st.buckets + line * line_bytes(st) + key_stride(st) * s);
 }
+// byte-mask layout: the mask BYTE of slot s (0..13) of a line
+__device__ __forceinline__ uint8_t *mask_byte_ptr(const SubTable &st, uint64_t line, uint32_t s) {
+    const uint32_t h = s >= BM_HALF_KEYS ? 1u : 0u;
+    return st.buckets + line * 128u + h * BM_HALF_BYTES + BM_MASK0 + (s - h * BM_HALF_KEYS);
+}
+// (not for byte-mask tables: their masks are bytes — mask_byte_ptr / mask_load / mask_byte_or; a -DPG_CHECK_LAYOUT build stops a
+// kernel that gets here with one)
 __device__ __forceinline__ uint32_t *mask_ptr(const SubTable &st, uint64_t line, uint32_t s, uint32_t w) {
+#ifdef PG_CHECK_LAYOUT
+    if (st.layout == LAYOUT_BYTEMASK) __builtin_trap();
+#endif
     if (st.layout == LAYOUT_SPLIT) return reinterpret_cast<uint32_t *>(st.masks) + (line * st.slots + s) * st.W + w;
     if (st.layout == LAYOUT_INLINE) return reinterpret_cast<uint32_t *>(st.buckets + line * 128u + 8u * st.slots) + s * st.W + w;
     return reinterpret_cast<uint32_t *>(st.buckets + line * (16u * st.slots) + 16u * s + 8u) + w;
+}
+// mask word w of a slot, whatever the layout (a byte-mask table has one word, eight bits of it)
+__device__ __forceinline__ uint32_t mask_load(const SubTable &st, uint64_t line, uint32_t s, uint32_t w) {
+    if (st.layout == LAYOUT_BYTEMASK) return *mask_byte_ptr(st, line, s);
+    return *mask_ptr(st, line, s, w);
+}
+// `bits` into a mask byte.  The neighbouring bytes of its dword belong to other slots, other threads': a byte store (every
+// writer of one byte during one launch ORs in the same bits — lane_insert_grp's note) or, ATOMIC, an atomic OR on the aligned
+// dword; never a read-modify-write of the dword.  claimed: the slot is this thread's own claim of just now, its byte is zero.
+template <bool ATOMIC>
+__device__ __forceinline__ void mask_byte_or(uint8_t *mp, uint32_t bits, bool claimed) {
+    bits &= 0xFFu;
+    if (ATOMIC) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(mp);
+        atomicOr(reinterpret_cast<uint32_t *>(a & ~(uintptr_t)3), bits << (8u * (uint32_t)(a & 3u)));
+    } else if (claimed) {
+        *reinterpret_cast<volatile uint8_t *>(mp) = (uint8_t)bits;
+    } else {
+        const uint32_t cur = *reinterpret_cast<volatile uint8_t *>(mp);
+        if ((cur & bits) != bits) *reinterpret_cast<volatile uint8_t *>(mp) = (uint8_t)(cur | bits);
+    }
 }
 
 struct TableDesc {
@@ -380,12 +425,15 @@ __device__ __forceinline__ bool lane_lookup(const SubTable &st, uint64_t key, ui
     const uint32_t grp = group_of(st, key);
     uint32_t b = home_of_group(grp, st.nbuckets);
     uint32_t step = step_of_group(grp, st.nbuckets);
+    // (byte-mask layout: the slots of the key's half only)
+    const bool bm = st.layout == LAYOUT_BYTEMASK;
+    const uint32_t s_lo = bm && half_offset_of_key(key) ? BM_HALF_KEYS : 0u, s_hi = bm ? s_lo + BM_HALF_KEYS : st.slots;
     for (uint64_t probes = 0; probes < st.nbuckets + GROUP_CHAIN; ++probes) {
         bool empty_seen = false;
-        for (uint32_t s = 0; s < st.slots; ++s) {
+        for (uint32_t s = s_lo; s < s_hi; ++s) {
             const uint64_t cur = *key_ptr(st, b, s);
             if (cur == key) {
-                out = *mask_ptr(st, b, s, w);
+                out = mask_load(st, b, s, w);
                 return true;
             }
             empty_seen |= (cur == EMPTY_KEY);
@@ -406,15 +454,18 @@ __device__ __forceinline__ int lane_insert_grp(const SubTable &st, uint64_t key,
     uint32_t b = home_of_group(grp, st.nbuckets);
     uint32_t step = step_of_group(grp, st.nbuckets);
     const uint32_t kstride = key_stride(st);  // bytes from one key of a line to the next
+    // (byte-mask layout: the walk sees the key's half of every line — seven keys, the eighth word holds their mask bytes)
+    const bool bm = st.layout == LAYOUT_BYTEMASK;
+    const uint32_t hoff = bm ? half_offset_of_key(key) : 0u, nslots = bm ? BM_HALF_KEYS : st.slots;
     for (uint32_t probes = 0; probes < max_probe; ++probes) {
-        uint8_t *base = st.buckets + (uint64_t)b * line_bytes(st);
-        for (uint32_t s0 = 0; s0 < st.slots; s0 += 8) {  // 8 slots at a time: all key loads in flight together
+        uint8_t *base = st.buckets + (uint64_t)b * line_bytes(st) + hoff;
+        for (uint32_t s0 = 0; s0 < nslots; s0 += 8) {  // 8 slots at a time: all key loads in flight together
             uint8_t *grp8 = base + kstride * s0;
             uint64_t kk[8];
 #pragma unroll
             for (int s = 0; s < 8; ++s) {  // (relaxed atomic loads: all eight in flight together; volatile ones are waited for one by one)
                 kk[s] = __hip_atomic_load(reinterpret_cast<unsigned long long *>(grp8 + kstride * s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (s0 + s >= st.slots) kk[s] = TOMB_KEY;  // (inline layout: 5 or 6 keys, mask words behind them — neither a key nor empty)
+                if (s0 + s >= nslots) kk[s] = TOMB_KEY;  // (inline layout: 5 or 6 keys, mask words behind them — neither a key nor empty)
             }
             int hit = -1, free_s = -1;
 #pragma unroll
@@ -425,7 +476,7 @@ __device__ __forceinline__ int lane_insert_grp(const SubTable &st, uint64_t key,
             int claimed = 0;
             // slots before the first empty one hold other keys for good; from there on a slot may be
             // taken by a concurrent insert between our read and our CAS: walk on, one CAS per slot
-            for (int s = (hit >= 0 ? hit : free_s); hit < 0 && s >= 0 && s < 8 && s0 + (uint32_t)s < st.slots; ++s) {
+            for (int s = (hit >= 0 ? hit : free_s); hit < 0 && s >= 0 && s < 8 && s0 + (uint32_t)s < nslots; ++s) {
                 unsigned long long *kp = reinterpret_cast<unsigned long long *>(grp8 + kstride * s);
                 const unsigned long long cur = atomicCAS(kp, (unsigned long long)EMPTY_KEY, (unsigned long long)key);
                 if (cur == EMPTY_KEY) {
@@ -436,6 +487,10 @@ __device__ __forceinline__ int lane_insert_grp(const SubTable &st, uint64_t key,
                 }
             }
             if (hit >= 0) {
+                if (bm) {  // (never a counting table: pg_api.hip creates those in the slots layout)
+                    mask_byte_or<ATOMIC_OR>(base + BM_MASK0 + (uint32_t)hit, bits, claimed != 0);
+                    return claimed;
+                }
                 uint32_t *mp = mask_ptr(st, b, s0 + (uint32_t)hit, (uint32_t)w);
                 if (COUNT) {
                     if (*mp < 0xFFFFFF00u) atomicAdd(mp, bits);  // saturates far above any -ci threshold

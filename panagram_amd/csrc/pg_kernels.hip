@@ -25,7 +25,9 @@ __global__ __launch_bounds__(256) void k_table_init(uint4 *chunks, uint64_t nchu
     for (; i < nchunks; i += stride) {
         // slots layout: {EMPTY key, mask0 = 0, mask1 = 0}; split layout: two EMPTY keys (the mask array is memset);
         // inline layout: the line's first S 8-byte words are EMPTY keys, the mask blocks behind them zero
-        if (mode >= 2) {
+        if (mode == 1000u) {  // byte-mask layout: a half = seven EMPTY keys, then the word of their mask bytes, zero
+            chunks[i] = (i & 3u) == 3u ? make_uint4(~0u, ~0u, 0u, 0u) : make_uint4(~0u, ~0u, ~0u, ~0u);
+        } else if (mode >= 2) {
             const uint32_t S = mode - 2u, k0 = 2u * (uint32_t)(i & 7u);  // this chunk's two 8-byte words of its line
             const uint32_t a = k0 < S ? ~0u : 0u, b = k0 + 1u < S ? ~0u : 0u;
             chunks[i] = make_uint4(a, a, b, b);
@@ -365,11 +367,11 @@ __global__ __launch_bounds__(256) void k_rehash(SubTable src, SubTable dst, unsi
         if (key >= TOMB_KEY) continue;  // empty, or a retired copy
         if (phase < 2u) {
             uint32_t pc = 0;
-            for (uint32_t w = 0; w < src.W; ++w) pc += (uint32_t)__popc(*mask_ptr(src, b, (uint32_t)s, w));
+            for (uint32_t w = 0; w < src.W; ++w) pc += (uint32_t)__popc(mask_load(src, b, (uint32_t)s, w));
             if ((pc > dense_above) != (phase == 0u)) continue;
         }
         for (uint32_t w = 0; w < src.W; ++w) {
-            uint32_t m = *mask_ptr(src, b, (uint32_t)s, w);
+            uint32_t m = mask_load(src, b, (uint32_t)s, w);
             if (m == 0 && w > 0) continue;
             int r = lane_insert(dst, key, (int)w, m, max_probe);
             if (r < 0) atomicOr(reinterpret_cast<unsigned int *>(&counters[1]), 1u);
@@ -393,7 +395,7 @@ __global__ __launch_bounds__(256) void k_merge_min(SubTable src, SubTable dst, i
         int s = (int)(i - b * ns);
         uint64_t key = *key_ptr(src, b, (uint32_t)s);
         if (key == EMPTY_KEY) continue;
-        if (*mask_ptr(src, b, (uint32_t)s, 0) < min_count) continue;
+        if (mask_load(src, b, (uint32_t)s, 0) < min_count) continue;
         int r = lane_insert(dst, key, w, bits, max_probe);
         if (r < 0) atomicOr(reinterpret_cast<unsigned int *>(&counters[1]), 1u);
         else claimed += r;
@@ -430,7 +432,7 @@ __global__ __launch_bounds__(256) void k_export(SubTable st, int w, uint64_t *ke
         int s = (int)(i - b * ns);
         uint64_t key = *key_ptr(st, b, (uint32_t)s);
         if (key >= TOMB_KEY) continue;  // empty, or a retired copy (whose mask a racing finder may have written before it was retired)
-        uint32_t m = *mask_ptr(st, b, (uint32_t)s, (uint32_t)w);
+        uint32_t m = mask_load(st, b, (uint32_t)s, (uint32_t)w);
         if (m == 0) continue;
         unsigned long long idx = atomicAdd(count, 1ull);
         if (keys && idx < cap) {
@@ -471,7 +473,7 @@ hipError_t launch_table_init(hipStream_t st, const SubTable &t) {
     const uint64_t nchunks = t.nbuckets * line_bytes(t) / 16;
     hipLaunchKernelGGL(k_table_init, dim3(grid_for(nchunks, 256, 256 * 32)), dim3(256), 0, st,
                        reinterpret_cast<uint4 *>(t.buckets), nchunks,
-                       t.layout == LAYOUT_INLINE ? 2u + t.slots : t.layout == LAYOUT_SPLIT ? 1u : 0u);
+                       t.layout == LAYOUT_BYTEMASK ? 1000u : t.layout == LAYOUT_INLINE ? 2u + t.slots : t.layout == LAYOUT_SPLIT ? 1u : 0u);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && t.layout == LAYOUT_SPLIT)
         e = hipMemsetAsync(t.masks, 0, t.nbuckets * t.slots * 4ull * t.W, st);

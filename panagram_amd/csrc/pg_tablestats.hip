@@ -86,9 +86,11 @@ __global__ __launch_bounds__(256) void k_table_pair_counts(SubTable st, uint32_t
     const uint32_t l = lane / st.slots, s = lane - l * st.slots;
     const bool mine = l < chunk_lines;
     const uint8_t *key0 = reinterpret_cast<const uint8_t *>(key_ptr(st, mine ? l : 0, s));
-    const uint8_t *mask0 = reinterpret_cast<const uint8_t *>(mask_ptr(st, mine ? l : 0, s, 0));
+    // (byte-mask layout: a slot's mask is one byte in its line — the same walk by pointer steps, a byte read where the others read words)
+    const bool bm = st.layout == LAYOUT_BYTEMASK;
+    const uint8_t *mask0 = bm ? mask_byte_ptr(st, mine ? l : 0, s) : reinterpret_cast<const uint8_t *>(mask_ptr(st, mine ? l : 0, s, 0));
     const uint64_t key_step = reinterpret_cast<const uint8_t *>(key_ptr(st, chunk_lines, 0)) - reinterpret_cast<const uint8_t *>(key_ptr(st, 0, 0));
-    const uint64_t mask_step = reinterpret_cast<const uint8_t *>(mask_ptr(st, chunk_lines, 0, 0)) - reinterpret_cast<const uint8_t *>(mask_ptr(st, 0, 0, 0));
+    const uint64_t mask_step = bm ? key_step : reinterpret_cast<const uint8_t *>(mask_ptr(st, chunk_lines, 0, 0)) - reinterpret_cast<const uint8_t *>(mask_ptr(st, 0, 0, 0));
     auto key_of = [&](uint64_t c) -> uint64_t {  // (empty where the chunk has no such slot)
         return c < nchunks && mine && c * chunk_lines + l < st.nbuckets ? *reinterpret_cast<const unsigned long long *>(key0 + c * key_step) : EMPTY_KEY;
     };
@@ -112,7 +114,8 @@ __global__ __launch_bounds__(256) void k_table_pair_counts(SubTable st, uint32_t
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(keys >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)keys, 0u));
                 uint32_t *e = queue + ((qh + qn + rank) & (TS_QCAP - 1)) * W;
                 const uint32_t *m = reinterpret_cast<const uint32_t *>(mask0 + cur * mask_step);
-                for (uint32_t d = 0; d < W; ++d) e[d] = m[d] & valid_bits(N, d);
+                if (bm) e[0] = (uint32_t)mask0[cur * mask_step] & valid_bits(N, 0);
+                else for (uint32_t d = 0; d < W; ++d) e[d] = m[d] & valid_bits(N, d);
             }
             qn += (uint32_t)__popcll(keys);
         }

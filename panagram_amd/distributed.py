@@ -1095,7 +1095,7 @@ class ShardedAnchoring:
             # narrow result needs no row buffer
             want_direct = getattr(self.engine, "COLUMNS_DIRECT", False) if self.direct_columns is None else bool(self.direct_columns)
             self._direct = (want_direct and table.ngenomes <= 8 and self.per <= max(self.DIRECT_MAX_WIDTH, 2 if self.direct_columns else 0)
-                            and table.spill()[1] == 8)  # (8-slot lines: what pg_result_columns_direct asks for)
+                            and table.spill()[1] in (8, 14))  # (8-slot or byte-mask lines: what pg_result_columns_direct asks for)
             self._part = self.engine.AnchorResult(table, self.merged, colsums=False, rows_only=True,
                                                   **({"columns_only": True} if self._direct else {}))
             if self._direct and not self._part.columns_direct(self.per):

@@ -577,6 +577,57 @@ int pg_synteny_blocks(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqse
 /* the HIP-event times of this host thread's last pg_synteny_blocks: ms_out[7] = the five of pg_synteny_last_timing, then
  * k_run_blocks counting and k_run_blocks emitting (0 where a kernel did not run). */
 int pg_synteny_blocks_last_timing(float *ms_out);
+/* variants: every link of every block classified, compared base by base on the GPU and emitted with its alleles — the differences
+ * of B against A inside the blocks; only the variants leave HBM.  Run, kept, predecessor, link, dA, dB and strand are those of the
+ * blocks above.  For a link i -> j write p = end_i - 1, the A position of run i's last k-mer; s = start_j; bl = the B position of
+ * run i's last k-mer; b = b_j.  Positions of A are contig-relative, positions of B global, as in the mate words.
+ *   overlap     t = max(0, k - min(dA, dB)); min(dA, dB) >= 1, so t <= k - 1.  The two matched flanks overlap by t bases on the
+ *               shorter side — an indel inside a short tandem repeat — and the difference is placed at the leftmost place in A
+ *               that the flanks allow.
+ *   A allele    bases [posA, posA + lenA) of the contig of A, posA = p + k - t, lenA = dA - k + t.  Base posA - 1 always exists,
+ *               lies in run i's last matched k-mer, is ACGT and identical in B: the anchor base a VCF indel needs.
+ *   B allele    lenB = dB - k + t bases: [bl + k - t, b) on strand 0, [b + k, bl + t) on strand 1; posB is the lowest base of that
+ *               range, which lies inside one contig of B (a link requires bl and b in the same contig).  "In A's orientation": as
+ *               stored on strand 0, reverse-complemented on strand 1 — A base posA + i faces B base posB + i on strand 0 and the
+ *               complement of B base posB + lenB - 1 - i on strand 1.
+ *   mismatches  defined only when lenA == lenB: the number of i in [0, lenA) where the facing bases differ or either is non-ACGT.
+ *               0 otherwise.
+ *   class       0 same: lenA == lenB and mismatches == 0 (lenA == 0 included: the run broke on k-mers that are not unique, not on
+ *               a difference) — counted, never emitted; 1 snp: lenA == lenB == 1 and mismatches == 1; 2 mnp: lenA == lenB >= 2 and
+ *               mismatches >= 1; 3 ins: lenA == 0 < lenB; 4 del: lenB == 0 < lenA; 5 complex: both positive and unequal.
+ *   N flag      either allele range holds a non-ACGT base.
+ *   record      one per link of class != 0: contig of A, posA, lenA, posB, lenB, info = strand | class << 1 | code of A base
+ *               posA - 1 << 4 | N flag << 6, mismatches, and two 64-bit words holding the first min(len, 32) bases of the A allele
+ *               and of the B allele in A's orientation: 2 bits per base, base i at bits 2i and 2i + 1 (the seqset's own packing),
+ *               the unused high bits zero.
+ * Records are sorted by (contig of A, run j), which is (contig, posA), the same on every call.
+ * Invariant: for every block, A's bases from the first run's start to the last run's end + k - 1, with each emitted record's A
+ * allele replaced by its B allele in A's orientation, are exactly B's range of the block, reverse-complemented on strand 1.
+ * pg_run_variants is pg_run_blocks's sibling: the runs from host arrays, ncontigsA and B's contig lengths from the seqsets.
+ * class_counts[6] (the links of every class), *links (all links, class 0 included) and *total (the records) are always filled.
+ * Capacity as pg_run_blocks: nothing is written to the nine record arrays when cap == 0 (they may then be NULL) or *total > cap.
+ * PG_E_INVALID, before anything is launched: as pg_run_blocks, and k outside 1..32, a run whose k-mers' bases leave its contig of A
+ * (end + k - 1 > its length) or do not lie inside one contig of B, max_gap above 65536 (a lane compares the gap's bases, 32 per
+ * step).  The blocks' count pass and stitch, then two launches of k_link_variants (count, then emit; one when nothing is emitted)
+ * with a scan of the chunks' records on the host between them, no atomics; synchronises. */
+int pg_run_variants(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, const uint32_t *run_contig,
+                    const uint32_t *run_start, const uint32_t *run_end, const uint32_t *run_mate, uint64_t nruns,
+                    uint32_t min_run, uint32_t max_gap, uint32_t max_shift, uint64_t cap,
+                    uint32_t *var_contig, uint32_t *var_posA, uint32_t *var_lenA, uint32_t *var_posB, uint32_t *var_lenB,
+                    uint32_t *var_info, uint32_t *var_mismatches, uint64_t *var_alleleA, uint64_t *var_alleleB,
+                    uint64_t *class_counts, uint64_t *links, uint64_t *total);
+/* all of it in one call: table, both inserts, mates, runs (into HBM only), the blocks counted and stitched, the variants counted
+ * and emitted — neither mates nor runs nor blocks are downloaded.  Records, counts and capacity as pg_run_variants; *nmated and
+ * *nruns as pg_synteny_blocks, *nblocks = the blocks.  PG_E_INVALID as pg_synteny_blocks, and max_gap above 65536. */
+int pg_synteny_variants(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, uint32_t min_run, uint32_t max_gap,
+                        uint32_t max_shift, uint64_t cap,
+                        uint32_t *var_contig, uint32_t *var_posA, uint32_t *var_lenA, uint32_t *var_posB, uint32_t *var_lenB,
+                        uint32_t *var_info, uint32_t *var_mismatches, uint64_t *var_alleleA, uint64_t *var_alleleB,
+                        uint64_t *class_counts, uint64_t *links, uint64_t *total, uint64_t *nmated, uint64_t *nruns,
+                        uint64_t *nblocks);
+/* the HIP-event times of this host thread's last pg_synteny_variants: ms_out[9] = the seven of pg_synteny_blocks_last_timing (the
+ * blocks' emit pass does not run: 0), then k_link_variants counting and k_link_variants emitting. */
+int pg_synteny_variants_last_timing(float *ms_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

@@ -17,7 +17,10 @@ occur exactly once in genome A and exactly once in genome B, with their place an
 genomes' sequences (the lines of a dot plot; the reference has nothing that says WHERE in B a k-mer lies);
 `synteny <index_dir> <A> <B> --blocks [--min-run N] [--max-gap G] [--max-shift S] [--paf]` chains those runs on the GPU into blocks
 that bridge substitutions and small insertions and deletions — a few thousand lines where the runs are a million — with the runs
-and the shifted links of each, or as PAF lines for the tools that draw dot plots; the runs never leave the GPU."""
+and the shifted links of each, or as PAF lines for the tools that draw dot plots; the runs never leave the GPU;
+`synteny <index_dir> <A> <B> --variants [--vcf] [--min-run N] [--max-gap G] [--max-shift S] [--summary FILE]` says what differs inside
+those blocks: every link of every block is classified and compared base by base on the GPU, and the SNPs, insertions and deletions of
+B against A come out with their place on both genomes and both alleles — as a table, or as a VCF of B against A."""
 import argparse
 import os
 import sys
@@ -136,17 +139,22 @@ def main(argv=None):
     sy.add_argument("--min-len", type=int, default=1, metavar="N", help="drop runs (with --blocks: blocks) of fewer than N k-mers")
     sy.add_argument("--blocks", action="store_true", help="chain the runs on the GPU into blocks that bridge substitutions and small "
                     "insertions and deletions: the same columns, then runs and shifted (the links whose gaps differ on A and B)")
-    sy.add_argument("--min-run", type=int, default=None, metavar="N", help="with --blocks: runs of fewer than N k-mers neither "
+    sy.add_argument("--variants", action="store_true", help="the differences inside the blocks, found on the GPU from the blocks' links: "
+                    "chrA posA refLen chrB posB altLen strand class mismatches ref alt, one line per snp, mnp, ins, del or complex "
+                    "variant of B against A (alt in A's orientation; - for an empty allele)")
+    sy.add_argument("--vcf", action="store_true", help="with --variants: VCF 4.2 lines of B against A in place of the table")
+    sy.add_argument("--min-run", type=int, default=None, metavar="N", help="with --blocks or --variants: runs of fewer than N k-mers neither "
                     "join nor break a block (default 1)")
-    sy.add_argument("--max-gap", type=int, default=None, metavar="G", help="with --blocks: a run joins the block of the run before "
+    sy.add_argument("--max-gap", type=int, default=None, metavar="G", help="with --blocks or --variants: a run joins the block of the run before "
                     "it when it starts at most G positions behind that run's last k-mer, on A and on B (default 1000)")
-    sy.add_argument("--max-shift", type=int, default=None, metavar="S", help="with --blocks: ... and the two distances differ by at "
+    sy.add_argument("--max-shift", type=int, default=None, metavar="S", help="with --blocks or --variants: ... and the two distances differ by at "
                     "most S: the longest insertion or deletion bridged (default 100)")
     sy.add_argument("--paf", action="store_true", help="with --blocks: PAF lines (query A, target B, matches = k-mers, tags rn:i: "
                     "runs and sh:i: shifted links) in place of the table")
     sy.add_argument("--summary", metavar="FILE", default=None, help="also write chrA chrB strand segments kmers: the segments and shared "
                     "unique k-mers of every pair of chromosomes and strand, then per chromosome of either side, then in all; in front, "
-                    "as # lines, per side the positions whose k-mer is unique in that genome and those with a mate")
+                    "as # lines, per side the positions whose k-mer is unique in that genome and those with a mate; with --variants: class count "
+                    "basesA basesB per class of variant, then the links without a difference and all links")
     sy.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     sy.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
@@ -282,8 +290,14 @@ def main(argv=None):
     if a.cmd == "synteny":
         if a.min_len < 1:
             ap.error("synteny: --min-len must be at least 1")
-        if not a.blocks and (a.paf or a.min_run is not None or a.max_gap is not None or a.max_shift is not None):
-            ap.error("synteny: --paf, --min-run, --max-gap and --max-shift need --blocks")
+        if a.blocks and a.variants:
+            ap.error("synteny: --blocks and --variants exclude each other")
+        if a.vcf and not a.variants:
+            ap.error("synteny: --vcf needs --variants")
+        if not a.blocks and (a.paf or (not a.variants and (a.min_run is not None or a.max_gap is not None or a.max_shift is not None))):
+            ap.error("synteny: --paf, --min-run, --max-gap and --max-shift need --blocks (the last three: or --variants)")
+        if a.variants and a.min_len != 1:
+            ap.error("synteny: --min-len goes with runs or blocks, not with --variants")
         from .index import Index
         idx = Index(a.index_dir, mode="r", device=a.device)
         try:
@@ -292,7 +306,11 @@ def main(argv=None):
                     ap.error(f"synteny: unknown genome {g!r} (the index has {', '.join(idx.genome_names)})")
             chroms = [[c for c in s.split(",") if c] or None for s in (a.chroms_a, a.chroms_b)]
             try:
-                if a.blocks:
+                if a.variants:
+                    out, summary, totals, lens = idx.synteny_variants_tables(
+                        a.genome_a, a.genome_b, chroms[0], chroms[1], a.k, 1 if a.min_run is None else a.min_run,
+                        1000 if a.max_gap is None else a.max_gap, 100 if a.max_shift is None else a.max_shift)
+                elif a.blocks:
                     out, summary, totals, lens = idx.synteny_blocks_tables(
                         a.genome_a, a.genome_b, chroms[0], chroms[1], a.k, 1 if a.min_run is None else a.min_run,
                         1000 if a.max_gap is None else a.max_gap, 100 if a.max_shift is None else a.max_shift, a.min_len)
@@ -305,14 +323,16 @@ def main(argv=None):
         from . import synteny
         if a.summary:
             synteny.write_summary(a.summary, summary, totals)
-        if a.paf:
+        if a.paf or a.vcf:
             f = open(a.output, "w") if a.output else sys.stdout
             try:
-                f.writelines(line + "\n" for line in synteny.paf_lines(out, *lens))
+                f.writelines(line + "\n" for line in (synteny.paf_lines(out, *lens) if a.paf else synteny.vcf_lines(out, lens[0], a.genome_b)))
             finally:
                 if a.output:
                     f.close()
             return 0
+        if a.variants:
+            out = out.replace({"ref": {"": "-"}, "alt": {"": "-"}})  # (an empty allele: no empty field in the table)
         out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
         return 0
     if a.cmd == "patterns":

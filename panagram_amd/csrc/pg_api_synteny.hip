@@ -1,5 +1,6 @@
 // pg_api_synteny.hip — host side of the C-ABI: the position table of two genomes, the mates of A's positions and their collinear
-// runs (pg_synteny.hip), and the runs chained into blocks (pg_blocks.hip, pg_blocks_host.h).
+// runs (pg_synteny.hip), the runs chained into blocks (pg_blocks.hip, pg_blocks_host.h), and the blocks' links as variants of B
+// against A (pg_variants.hip).
 #include "pg_host.h"
 
 #include "pg_blocks_host.h"
@@ -40,6 +41,7 @@ struct LaunchTimer {
 };
 thread_local float g_last_ms[5] = {0, 0, 0, 0, 0};  // insert A, insert B, mates, runs (count), runs (emit) of the last pg_synteny_segments
 thread_local float g_blocks_ms[7] = {0, 0, 0, 0, 0, 0, 0};  // those five, blocks (count), blocks (emit) of the last pg_synteny_blocks
+thread_local float g_variants_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // those seven, variants (count), variants (emit) of the last pg_synteny_variants
 
 // the (contig, chunk) jobs of a seqset's k-mer positions, the base offset of every contig in the concatenation and its first
 // entry in a back-to-back array of k-mer positions
@@ -301,13 +303,28 @@ int block_params_ok(const char *fn, const BlockParams &p) {
     return PG_OK;
 }
 
-// the blocks of run arrays in HBM (three planes of nruns words: start, end, mate; per_contig[c] runs of contig c of A, back to
-// back); boff: the nb + 1 offsets of B's contigs.  Counts always, the blocks under the capacity protocol.
-int run_blocks_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_runs, uint64_t nruns, uint32_t ncontigs, const uint64_t *per_contig,
-                   const std::vector<uint64_t> &boff, const BlockParams &p, uint64_t cap, const BlockArrays &out, uint64_t *nblocks,
-                   uint64_t *total_out, float *ms = nullptr) {
-    std::vector<uint2> contigs(ncontigs), chunks;
-    std::vector<uint64_t> first(ncontigs + 1, 0);
+// what the blocks' count pass and the stitch leave for the passes behind them: the chunk geometry on both sides of the bus and
+// the stitched offsets (the carried predecessor of every chunk among them)
+struct BlocksPlan {
+    std::vector<uint2> contigs, chunks;
+    std::vector<uint64_t> first;
+    std::vector<BlockChunkOffs> offs;
+    DevBuf<uint2> d_contigs, d_chunks;
+    DevBuf<uint64_t> d_boff;
+    uint32_t nchunks = 0, nb = 0;
+    uint64_t total = 0;
+};
+
+// the count half of the blocks of run arrays in HBM (three planes of nruns words: start, end, mate; per_contig[c] runs of contig
+// c of A, back to back); boff: the nb + 1 offsets of B's contigs.  nblocks[c], *total_out and the plan; ms: the count launch.
+int blocks_count_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_runs, uint64_t nruns, uint32_t ncontigs, const uint64_t *per_contig,
+                     const std::vector<uint64_t> &boff, const BlockParams &p, BlocksPlan &plan, uint64_t *nblocks, uint64_t *total_out,
+                     float *ms = nullptr) {
+    std::vector<uint2> &contigs = plan.contigs, &chunks = plan.chunks;
+    std::vector<uint64_t> &first = plan.first;
+    contigs.assign(ncontigs, make_uint2(0, 0));
+    chunks.clear();
+    first.assign(ncontigs + 1, 0);
     uint64_t at = 0;
     for (uint32_t c = 0; c < ncontigs; ++c) {
         contigs[c] = make_uint2((uint32_t)at, (uint32_t)per_contig[c]);
@@ -318,45 +335,58 @@ int run_blocks_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_runs, uint64_t
     }
     first[ncontigs] = chunks.size();
     *total_out = 0;
+    plan.nchunks = 0;
+    plan.total = 0;
     if (at != nruns) return fail(PG_E_INVALID, "%s: the contigs hold %llu runs of %llu", fn, (unsigned long long)at, (unsigned long long)nruns);
     if (chunks.empty()) return PG_OK;
     const uint32_t nchunks = (uint32_t)chunks.size(), nb = (uint32_t)boff.size();
     if (int r = use_device(ctx)) return r;
     hipStream_t st = ctx->stream;
-    DevBuf<uint2> d_contigs, d_chunks;
-    DevBuf<uint64_t> d_boff;
     DevBuf<BlockChunkCount> d_counts;
     std::vector<BlockChunkCount> counts(nchunks);
-    LaunchTimer tc(ms), te(ms ? ms + 1 : nullptr);
+    LaunchTimer tc(ms);
     const uint32_t *rs = d_runs, *re = d_runs + nruns, *rm = d_runs + 2 * nruns;
-    hipError_t e = d_contigs.upload(contigs, st);
-    if (e == hipSuccess) e = d_chunks.upload(chunks, st);
-    if (e == hipSuccess) e = d_boff.upload(boff, st);
+    hipError_t e = plan.d_contigs.upload(contigs, st);
+    if (e == hipSuccess) e = plan.d_chunks.upload(chunks, st);
+    if (e == hipSuccess) e = plan.d_boff.upload(boff, st);
     if (e == hipSuccess) e = d_counts.alloc(nchunks);
     if (e == hipSuccess) e = tc.start(st);
     if (e == hipSuccess)
-        e = launch_run_blocks(st, rs, re, rm, d_contigs.get(), d_chunks.get(), nchunks, d_boff.get(), nb, p.min_run, p.max_gap,
-                              p.max_shift, d_counts.get(), nullptr, 0, nullptr);
+        e = launch_run_blocks(st, rs, re, rm, plan.d_contigs.get(), plan.d_chunks.get(), nchunks, plan.d_boff.get(), nb, p.min_run,
+                              p.max_gap, p.max_shift, d_counts.get(), nullptr, 0, nullptr);
     if (e == hipSuccess) e = tc.stop(st);
     if (e == hipSuccess)
         e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(BlockChunkCount), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     tc.read();
-    std::vector<BlockChunkOffs> offs(nchunks);
-    const uint64_t total = blocks_stitch(ncontigs, first.data(), counts.data(), p.max_gap, p.max_shift, boff.data(), nb, offs.data(), nblocks);
+    plan.offs.resize(nchunks);
+    const uint64_t total = blocks_stitch(ncontigs, first.data(), counts.data(), p.max_gap, p.max_shift, boff.data(), nb, plan.offs.data(), nblocks);
     if (total == ~0ull) return fail(PG_E_HIP, "%s: a contig's block starts and ends differ in number", fn);
     *total_out = total;
+    plan.nchunks = nchunks;
+    plan.nb = nb;
+    plan.total = total;
+    return PG_OK;
+}
+
+// the emit half: the plan's blocks under the capacity protocol; ms: the emit launch
+int blocks_emit_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_runs, uint64_t nruns, uint32_t ncontigs, const BlockParams &p,
+                    const BlocksPlan &plan, uint64_t cap, const BlockArrays &out, const uint64_t *nblocks, float *ms = nullptr) {
+    const uint64_t total = plan.total;
     if (total == 0 || cap == 0 || total > cap) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
+    hipStream_t st = ctx->stream;
+    const uint32_t *rs = d_runs, *re = d_runs + nruns, *rm = d_runs + 2 * nruns;
+    LaunchTimer te(ms);
     DevBuf<BlockChunkOffs> d_offs;
     DevBuf<uint32_t> d_out;
     std::vector<uint32_t> rec((size_t)10 * total);
-    e = d_offs.upload(offs, st);
+    hipError_t e = d_offs.upload(plan.offs, st);
     if (e == hipSuccess) e = d_out.alloc((size_t)10 * total);
     if (e == hipSuccess) e = te.start(st);
     if (e == hipSuccess)
-        e = launch_run_blocks(st, rs, re, rm, d_contigs.get(), d_chunks.get(), nchunks, d_boff.get(), nb, p.min_run, p.max_gap,
-                              p.max_shift, nullptr, d_offs.get(), total, d_out.get());
+        e = launch_run_blocks(st, rs, re, rm, plan.d_contigs.get(), plan.d_chunks.get(), plan.nchunks, plan.d_boff.get(), plan.nb,
+                              p.min_run, p.max_gap, p.max_shift, nullptr, d_offs.get(), total, d_out.get());
     if (e == hipSuccess) e = te.stop(st);
     if (e == hipSuccess) e = hipMemcpyAsync(rec.data(), d_out.get(), rec.size() * 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -373,9 +403,100 @@ int run_blocks_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_runs, uint64_t
         out.runs[i] = er[3 * total + i] - sr[3 * total + i];
         out.shifted[i] = er[4 * total + i] - sr[4 * total + i];
     }
-    at = 0;
+    uint64_t at = 0;
     for (uint32_t c = 0; c < ncontigs; ++c)
         for (uint64_t i = 0; i < nblocks[c]; ++i) out.contig[at++] = c;
+    return PG_OK;
+}
+
+// the blocks of run arrays in HBM: counts always, the blocks under the capacity protocol
+int run_blocks_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_runs, uint64_t nruns, uint32_t ncontigs, const uint64_t *per_contig,
+                   const std::vector<uint64_t> &boff, const BlockParams &p, uint64_t cap, const BlockArrays &out, uint64_t *nblocks,
+                   uint64_t *total_out, float *ms = nullptr) {
+    BlocksPlan plan;
+    if (int r = blocks_count_dev(ctx, fn, d_runs, nruns, ncontigs, per_contig, boff, p, plan, nblocks, total_out, ms)) return r;
+    return blocks_emit_dev(ctx, fn, d_runs, nruns, ncontigs, p, plan, cap, out, nblocks, ms ? ms + 1 : nullptr);
+}
+
+struct VariantArrays {  // the caller's nine arrays of `cap` entries
+    uint32_t *contig, *posA, *lenA, *posB, *lenB, *info, *mismatches;
+    uint64_t *alleleA, *alleleB;
+    bool all() const { return contig && posA && lenA && posB && lenB && info && mismatches && alleleA && alleleB; }
+};
+
+// the links of a plan's blocks as variants (pg_variants.hip): class_counts[6], *links and *total always, the records under the
+// capacity protocol; ms[0] the count launch, ms[1] the emit launch
+int link_variants_dev(pg_ctx *ctx, const char *fn, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, const uint32_t *d_runs,
+                      uint64_t nruns, const BlockParams &p, const BlocksPlan &plan, uint64_t cap, const VariantArrays &out,
+                      uint64_t *class_counts, uint64_t *links, uint64_t *total_out, float *ms = nullptr) {
+    std::fill(class_counts, class_counts + 6, 0ull);
+    *links = *total_out = 0;
+    const uint32_t nchunks = plan.nchunks;
+    if (nchunks == 0) return PG_OK;
+    hipStream_t st = ctx->stream;
+    const uint32_t *rs = d_runs, *re = d_runs + nruns, *rm = d_runs + 2 * nruns;
+    DevBuf<BlockChunkOffs> d_offs;
+    DevBuf<VariantChunkCount> d_counts;
+    std::vector<VariantChunkCount> counts(nchunks);
+    LaunchTimer tc(ms), te(ms ? ms + 1 : nullptr);
+    hipError_t e = d_offs.upload(plan.offs, st);
+    if (e == hipSuccess) e = d_counts.alloc(nchunks);
+    if (e == hipSuccess) e = tc.start(st);
+    if (e == hipSuccess)
+        e = launch_link_variants(st, rs, re, rm, plan.d_contigs.get(), plan.d_chunks.get(), nchunks, plan.d_boff.get(), plan.nb,
+                                 (uint32_t)k, p.min_run, p.max_gap, p.max_shift, d_offs.get(), seqsA->d_desc, seqsA->d_seqw, seqsA->d_nmw,
+                                 seqsB->d_desc, seqsB->n, seqsB->d_seqw, seqsB->d_nmw, d_counts.get(), nullptr, 0, nullptr, nullptr);
+    if (e == hipSuccess) e = tc.stop(st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(VariantChunkCount), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    tc.read();
+    // the exclusive scan of the chunks' records
+    std::vector<uint64_t> voffs(nchunks);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < nchunks; ++i) {
+        voffs[i] = total;
+        total += counts[i].records;
+        for (int c = 0; c < 6; ++c) class_counts[c] += counts[i].cls[c];
+    }
+    for (int c = 0; c < 6; ++c) *links += class_counts[c];
+    *total_out = total;
+    if (total != *links - class_counts[0]) return fail(PG_E_HIP, "%s: %llu records of %llu links that differ", fn, (unsigned long long)total,
+                                                        (unsigned long long)(*links - class_counts[0]));
+    if (total == 0 || cap == 0 || total > cap) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
+    DevBuf<uint64_t> d_voffs, d_out;  // (8 planes: the two of 64-bit words first, then the six of 32-bit words)
+    std::vector<uint64_t> rec((size_t)5 * total);
+    e = d_voffs.upload(voffs, st);
+    if (e == hipSuccess) e = d_out.alloc((size_t)5 * total);
+    if (e == hipSuccess) e = te.start(st);
+    if (e == hipSuccess)
+        e = launch_link_variants(st, rs, re, rm, plan.d_contigs.get(), plan.d_chunks.get(), nchunks, plan.d_boff.get(), plan.nb,
+                                 (uint32_t)k, p.min_run, p.max_gap, p.max_shift, d_offs.get(), seqsA->d_desc, seqsA->d_seqw, seqsA->d_nmw,
+                                 seqsB->d_desc, seqsB->n, seqsB->d_seqw, seqsB->d_nmw, nullptr, d_voffs.get(), total,
+                                 reinterpret_cast<uint32_t *>(d_out.get() + 2 * total), d_out.get());
+    if (e == hipSuccess) e = te.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(rec.data(), d_out.get(), rec.size() * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    te.read();
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(rec.data() + 2 * total);
+    std::copy(rec.data(), rec.data() + total, out.alleleA);
+    std::copy(rec.data() + total, rec.data() + 2 * total, out.alleleB);
+    std::copy(w, w + total, out.posA);
+    std::copy(w + total, w + 2 * total, out.lenA);
+    std::copy(w + 2 * total, w + 3 * total, out.posB);
+    std::copy(w + 3 * total, w + 4 * total, out.lenB);
+    std::copy(w + 4 * total, w + 5 * total, out.info);
+    std::copy(w + 5 * total, w + 6 * total, out.mismatches);
+    for (uint32_t i = 0; i < nchunks; ++i)  // (a chunk is of one contig of A)
+        std::fill(out.contig + voffs[i], out.contig + voffs[i] + counts[i].records, plan.chunks[i].x);
+    return PG_OK;
+}
+
+int variant_params_ok(const char *fn, const BlockParams &p) {
+    if (int r = block_params_ok(fn, p)) return r;
+    if (p.max_gap > VARIANTS_MAX_GAP) return fail(PG_E_INVALID, "%s: max_gap=%u (at most %u: a lane compares the gap's bases)", fn, p.max_gap, VARIANTS_MAX_GAP);
     return PG_OK;
 }
 
@@ -404,6 +525,25 @@ int mated_table(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seq
     if (int r = postable_insert(pt.p, 0, seqsA, ms)) return r;
     if (int r = postable_insert(pt.p, 1, seqsB, ms + 1)) return r;
     return postable_mates(pt.p, seqsA, nullptr, nmated, ms + 2);
+}
+
+// the run list of pg_run_blocks / pg_run_variants checked on the host: sorted, inside B; per[c] = the runs of contig c of A
+int runs_ok(const char *fn, const uint32_t *run_contig, const uint32_t *run_start, const uint32_t *run_end, const uint32_t *run_mate,
+                   uint64_t nruns, uint32_t ncontigsA, uint64_t sizeB, std::vector<uint64_t> &per) {
+    per.assign(ncontigsA, 0);
+    for (uint64_t i = 0; i < nruns; ++i) {
+        const uint64_t c = run_contig[i], s = run_start[i], e = run_end[i], m = run_mate[i];
+        if (c >= ncontigsA) return fail(PG_E_INVALID, "%s: run %llu: contig %llu of %u", fn, (unsigned long long)i, (unsigned long long)c, ncontigsA);
+        if (e <= s) return fail(PG_E_INVALID, "%s: run %llu ends at or before its start", fn, (unsigned long long)i);
+        if (m == NO_MATE) return fail(PG_E_INVALID, "%s: run %llu has no mate", fn, (unsigned long long)i);
+        if (i && (run_contig[i - 1] > c || (run_contig[i - 1] == c && run_end[i - 1] > s)))
+            return fail(PG_E_INVALID, "%s: run %llu: the runs are not sorted by (contig, start), or overlap", fn, (unsigned long long)i);
+        const uint64_t b = m >> 1, n = e - s;
+        if ((m & 1) ? (b < n - 1 || b >= sizeB) : b + (n - 1) >= sizeB)
+            return fail(PG_E_INVALID, "%s: run %llu leaves genome B", fn, (unsigned long long)i);
+        per[c] += 1;
+    }
+    return PG_OK;
 }
 
 }  // namespace
@@ -522,20 +662,8 @@ extern "C" int pg_run_blocks(pg_ctx *ctx, const uint32_t *run_contig, const uint
     if (nruns > POS_MAX_BASES) return fail(PG_E_INVALID, "pg_run_blocks: more than %llu runs", (unsigned long long)POS_MAX_BASES);
     std::vector<uint64_t> boff;
     if (!contig_offsets(ncontigsB, lensB, boff)) return fail(PG_E_INVALID, "pg_run_blocks: genome B of more than 2^32 positions");
-    const uint64_t sizeB = boff.back();
-    std::vector<uint64_t> per(ncontigsA, 0);
-    for (uint64_t i = 0; i < nruns; ++i) {
-        const uint64_t c = run_contig[i], s = run_start[i], e = run_end[i], m = run_mate[i];
-        if (c >= ncontigsA) return fail(PG_E_INVALID, "pg_run_blocks: run %llu: contig %llu of %u", (unsigned long long)i, (unsigned long long)c, ncontigsA);
-        if (e <= s) return fail(PG_E_INVALID, "pg_run_blocks: run %llu ends at or before its start", (unsigned long long)i);
-        if (m == NO_MATE) return fail(PG_E_INVALID, "pg_run_blocks: run %llu has no mate", (unsigned long long)i);
-        if (i && (run_contig[i - 1] > c || (run_contig[i - 1] == c && run_end[i - 1] > s)))
-            return fail(PG_E_INVALID, "pg_run_blocks: run %llu: the runs are not sorted by (contig, start), or overlap", (unsigned long long)i);
-        const uint64_t b = m >> 1, n = e - s;
-        if ((m & 1) ? (b < n - 1 || b >= sizeB) : b + (n - 1) >= sizeB)
-            return fail(PG_E_INVALID, "pg_run_blocks: run %llu leaves genome B", (unsigned long long)i);
-        per[c] += 1;
-    }
+    std::vector<uint64_t> per;
+    if (int r = runs_ok("pg_run_blocks", run_contig, run_start, run_end, run_mate, nruns, ncontigsA, boff.back(), per)) return r;
     *total = 0;
     for (uint32_t c = 0; c < ncontigsA; ++c) nblocks_per_contig[c] = 0;
     if (nruns == 0) return PG_OK;
@@ -600,6 +728,115 @@ extern "C" int pg_synteny_blocks_last_timing(float *ms_out) {
     PG_API_BEGIN
     if (!ms_out) return fail(PG_E_INVALID, "pg_synteny_blocks_last_timing: NULL argument");
     std::copy(g_blocks_ms, g_blocks_ms + 7, ms_out);
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_run_variants(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, const uint32_t *run_contig,
+                               const uint32_t *run_start, const uint32_t *run_end, const uint32_t *run_mate, uint64_t nruns,
+                               uint32_t min_run, uint32_t max_gap, uint32_t max_shift, uint64_t cap, uint32_t *var_contig,
+                               uint32_t *var_posA, uint32_t *var_lenA, uint32_t *var_posB, uint32_t *var_lenB, uint32_t *var_info,
+                               uint32_t *var_mismatches, uint64_t *var_alleleA, uint64_t *var_alleleB, uint64_t *class_counts,
+                               uint64_t *links, uint64_t *total) {
+    PG_API_BEGIN
+    const VariantArrays out{var_contig, var_posA, var_lenA, var_posB, var_lenB, var_info, var_mismatches, var_alleleA, var_alleleB};
+    if (!ctx || !seqsA || !seqsB || !class_counts || !links || !total || (cap && !out.all()) ||
+        (nruns && !(run_contig && run_start && run_end && run_mate)))
+        return fail(PG_E_INVALID, "pg_run_variants: NULL argument");
+    if (k < 1 || k > 32) return fail(PG_E_INVALID, "pg_run_variants: k=%d unsupported (1..32)", k);
+    if (seqsA->ctx != ctx || seqsB->ctx != ctx) return fail(PG_E_INVALID, "pg_run_variants: a seqset of another context");
+    const BlockParams p{min_run, max_gap, max_shift};
+    if (int r = variant_params_ok("pg_run_variants", p)) return r;
+    if (nruns > POS_MAX_BASES) return fail(PG_E_INVALID, "pg_run_variants: more than %llu runs", (unsigned long long)POS_MAX_BASES);
+    SideWalk wa, wb;  // (a side of at most 2^31 - 1 bases)
+    if (int r = walk_side(seqsA, k, "pg_run_variants", wa)) return r;
+    if (int r = walk_side(seqsB, k, "pg_run_variants", wb)) return r;
+    std::vector<uint64_t> lensB(seqsB->n), boff, per, nblocks(seqsA->n, 0);
+    for (uint32_t c = 0; c < seqsB->n; ++c) lensB[c] = seqsB->desc[c].len;
+    contig_offsets(seqsB->n, lensB.data(), boff);
+    if (int r = runs_ok("pg_run_variants", run_contig, run_start, run_end, run_mate, nruns, seqsA->n, boff.back(), per)) return r;
+    for (uint64_t i = 0; i < nruns; ++i) {
+        // the bases of the run's k-mers: inside its contig of A, and inside ONE contig of B
+        const uint64_t n = run_end[i] - run_start[i], b = run_mate[i] >> 1, lo = (run_mate[i] & 1) ? b - (n - 1) : b;
+        if ((uint64_t)run_end[i] + (uint64_t)k - 1 > seqsA->desc[run_contig[i]].len)
+            return fail(PG_E_INVALID, "pg_run_variants: run %llu leaves its contig of A", (unsigned long long)i);
+        const size_t cb = (size_t)(std::upper_bound(boff.begin(), boff.end(), lo) - boff.begin()) - 1;
+        if (lo + n + (uint64_t)k - 1 > boff[cb + 1])
+            return fail(PG_E_INVALID, "pg_run_variants: run %llu leaves its contig of B", (unsigned long long)i);
+    }
+    std::fill(class_counts, class_counts + 6, 0ull);
+    *links = *total = 0;
+    if (nruns == 0) return PG_OK;
+    if (int r = use_device(ctx)) return r;
+    DevBuf<uint32_t> d_runs;
+    hipError_t e = d_runs.alloc((size_t)3 * nruns);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_runs.get(), run_start, nruns * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_runs.get() + nruns, run_end, nruns * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_runs.get() + 2 * nruns, run_mate, nruns * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(ctx->stream);
+        return fail(PG_E_HIP, "pg_run_variants: %s", hipGetErrorString(e));
+    }
+    BlocksPlan plan;
+    uint64_t nblk = 0;
+    int r = blocks_count_dev(ctx, "pg_run_variants", d_runs.get(), nruns, seqsA->n, per.data(), boff, p, plan, nblocks.data(), &nblk);
+    if (r == PG_OK)
+        r = link_variants_dev(ctx, "pg_run_variants", k, seqsA, seqsB, d_runs.get(), nruns, p, plan, cap, out, class_counts, links, total);
+    hipStreamSynchronize(ctx->stream);  // (the uploads' sources are the caller's; the buffer goes with the scope)
+    return r;
+    PG_API_END
+}
+
+extern "C" int pg_synteny_variants(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seqset *seqsB, uint32_t min_run, uint32_t max_gap,
+                                   uint32_t max_shift, uint64_t cap, uint32_t *var_contig, uint32_t *var_posA, uint32_t *var_lenA,
+                                   uint32_t *var_posB, uint32_t *var_lenB, uint32_t *var_info, uint32_t *var_mismatches,
+                                   uint64_t *var_alleleA, uint64_t *var_alleleB, uint64_t *class_counts, uint64_t *links, uint64_t *total,
+                                   uint64_t *nmated, uint64_t *nruns, uint64_t *nblocks) {
+    PG_API_BEGIN
+    const VariantArrays out{var_contig, var_posA, var_lenA, var_posB, var_lenB, var_info, var_mismatches, var_alleleA, var_alleleB};
+    if (!ctx || !seqsA || !seqsB || !class_counts || !links || !total || !nmated || !nruns || !nblocks || (cap && !out.all()))
+        return fail(PG_E_INVALID, "pg_synteny_variants: NULL argument");
+    if (k < 1 || k > 32) return fail(PG_E_INVALID, "pg_synteny_variants: k=%d unsupported (1..32)", k);
+    if (seqsA->ctx != ctx || seqsB->ctx != ctx) return fail(PG_E_INVALID, "pg_synteny_variants: a seqset of another context");
+    const BlockParams p{min_run, max_gap, max_shift};
+    if (int r = variant_params_ok("pg_synteny_variants", p)) return r;
+    // both sides' limits before anything is launched
+    std::vector<uint64_t> nk(seqsA->n), per(seqsA->n, 0), perblk(seqsA->n, 0), lensB(seqsB->n), boff;
+    SideWalk a, b;
+    if (int r = walk_side(seqsA, k, "pg_synteny_variants", a)) return r;
+    if (int r = walk_side(seqsB, k, "pg_synteny_variants", b)) return r;
+    for (uint32_t c = 0; c < seqsA->n; ++c) nk[c] = seqsA->desc[c].len >= (uint64_t)k ? seqsA->desc[c].len - k + 1 : 0;
+    for (uint32_t c = 0; c < seqsB->n; ++c) lensB[c] = seqsB->desc[c].len;
+    contig_offsets(seqsB->n, lensB.data(), boff);  // (a side of at most 2^31 - 1 bases: checked by walk_side)
+    std::fill(class_counts, class_counts + 6, 0ull);
+    *links = *total = *nmated = *nruns = *nblocks = 0;
+    std::fill(g_variants_ms, g_variants_ms + 9, 0.0f);
+    if (a.nkmers == 0 || b.nkmers == 0) return PG_OK;  // (no k-mer on one side: no mate)
+    MatedTable pt;
+    float *ms = g_variants_ms;
+    if (int r = mated_table(ctx, k, seqsA, seqsB, a.nkmers + b.nkmers, pt, nmated, ms)) return r;
+    uint64_t mated = 0;
+    DevBuf<uint32_t> d_runs;  // the runs: emitted into HBM and read there
+    RunsOut runs_out;
+    runs_out.keep = &d_runs;
+    if (int r = mate_runs_dev(ctx, "pg_synteny_variants", pt.p->d_mates, seqsA->n, nk.data(), runs_out, per.data(), nruns, &mated, ms + 3))
+        return r;
+    if (mated != *nmated)  // (two kernels counted the same array)
+        return fail(PG_E_HIP, "pg_synteny_variants: %llu mates written, %llu read", (unsigned long long)*nmated, (unsigned long long)mated);
+    if (*nruns == 0) return PG_OK;
+    BlocksPlan plan;
+    if (int r = blocks_count_dev(ctx, "pg_synteny_variants", d_runs.get(), *nruns, seqsA->n, per.data(), boff, p, plan, perblk.data(), nblocks,
+                                 ms + 5))
+        return r;
+    return link_variants_dev(ctx, "pg_synteny_variants", k, seqsA, seqsB, d_runs.get(), *nruns, p, plan, cap, out, class_counts, links,
+                             total, ms + 7);
+    PG_API_END
+}
+
+extern "C" int pg_synteny_variants_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_synteny_variants_last_timing: NULL argument");
+    std::copy(g_variants_ms, g_variants_ms + 9, ms_out);
     return PG_OK;
     PG_API_END
 }

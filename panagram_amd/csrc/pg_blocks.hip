@@ -36,6 +36,8 @@
 // by every lane, every write to HBM is a vector store.
 #include "pg_kernels.h"
 
+#include "pg_blocks_pred.h"
+
 namespace pg {
 
 constexpr uint32_t RUN_TILE = 256;
@@ -81,32 +83,10 @@ __global__ __launch_bounds__(256) void k_run_blocks(const uint32_t *__restrict__
         const uint32_t n = e - s;
         const bool kept = act && n >= min_run;
         const uint32_t ml = blocks_last_mate(m, n);
-        const uint64_t kb = __ballot(kept);
-        const uint64_t below = (1ull << lane) - 1ull;
-        // the wave's last and first kept run
-        if (kb ? lane == 63u - (uint32_t)__clzll((long long)kb) : lane == 0) wlast[wave] = make_uint2(e, kb ? ml : BLOCKS_NONE);
-        if (kb && lane == (uint32_t)__ffsll((long long)kb) - 1u) wfirst[wave] = make_uint2(s, m);
-        // the predecessor inside the wave: every lane takes part in the shuffles
-        const uint64_t kbelow = kb & below;
-        const int src = kbelow ? 63 - __clzll((long long)kbelow) : 0;
-        uint32_t pe = (uint32_t)__shfl((int)e, src), pml = (uint32_t)__shfl((int)ml, src);
-        __syncthreads();
-        uint32_t under_e = carry_e, under_ml = carry_ml;  // the last kept run below this wave
-        uint32_t next_e = carry_e, next_ml = carry_ml;    // ... and below the next tile
-#pragma unroll
-        for (uint32_t w = 0; w < 4; ++w) {
-            const uint2 l = wlast[w];
-            if (l.y != BLOCKS_NONE) {
-                if (w < wave) under_e = l.x, under_ml = l.y;
-                next_e = l.x, next_ml = l.y;
-                if (!EMIT && !have_first) {
-                    const uint2 f = wfirst[w];
-                    first_s = f.x, first_m = f.y, have_first = true;
-                }
-            }
-        }
-        if (!kbelow) pe = under_e, pml = under_ml;
-        carry_e = next_e, carry_ml = next_ml;
+        // the last kept run before the lane (pg_blocks_pred.h: one barrier inside)
+        const RunPred pr = blocks_pred<!EMIT>(kept, s, e, m, ml, wlast, wfirst, carry_e, carry_ml, first_s, first_m, have_first);
+        const uint64_t kb = pr.kb, kbelow = pr.kbelow, below = (1ull << lane) - 1ull;
+        const uint32_t pe = pr.pe, pml = pr.pml;
         bool shifted = false;
         const bool link = kept && blocks_link(pe, pml, s, m, max_gap, max_shift, boff, nb, &shifted);
         const bool pred = pml != BLOCKS_NONE;
@@ -138,14 +118,14 @@ __global__ __launch_bounds__(256) void k_run_blocks(const uint32_t *__restrict__
         if (EMIT && ((sm >> lane) & 1ull)) {
             // the contig's sums over the kept runs before this one; a start has no link, so `shifted` at it and before it agree
             const uint32_t pk = kmers + kunder + kin - n;
-            const uint32_t pr = kept_n + under.z + (uint32_t)__popcll(kbelow);
+            const uint32_t prn = kept_n + under.z + (uint32_t)__popcll(kbelow);
             const uint32_t ps = shifted_n + under.w + (uint32_t)__popcll(hm & below);
             const uint64_t at = soff + nstarts + under.x + (uint32_t)__popcll(sm & below);
             if (at < total) {
                 out[at] = s;
                 out[total + at] = m;
                 out[2 * total + at] = pk;
-                out[3 * total + at] = pr;
+                out[3 * total + at] = prn;
                 out[4 * total + at] = ps;
             }
             if (pred) {
@@ -154,7 +134,7 @@ __global__ __launch_bounds__(256) void k_run_blocks(const uint32_t *__restrict__
                     out[5 * total + ea] = pe;
                     out[6 * total + ea] = pml;
                     out[7 * total + ea] = pk;
-                    out[8 * total + ea] = pr;
+                    out[8 * total + ea] = prn;
                     out[9 * total + ea] = ps;
                 }
             }

@@ -35,6 +35,14 @@ struct BlockChunkOffs {
 };
 static_assert(sizeof(BlockChunkOffs) == 40, "five 8-byte words");
 
+// the links as variants (pg_variants.hip): what its count pass leaves per chunk — the links of classes 0..5 (same, snp, mnp, ins,
+// del, complex) and the records, which are the links of classes 1..5.  A lane compares at most VARIANTS_MAX_GAP / 32 words.
+constexpr uint32_t VARIANTS_MAX_GAP = 65536;
+struct VariantChunkCount {
+    uint32_t records, cls[6], pad;
+};
+static_assert(sizeof(VariantChunkCount) == 32, "two 16-byte stores");
+
 // the mate word of the last k-mer of a run of n >= 1 k-mers whose first mate word is m (the host has checked that the run lies
 // inside B: nothing wraps, and the result is never BLOCKS_NONE)
 PG_BLOCKS_HD uint32_t blocks_last_mate(uint32_t m, uint32_t n) {

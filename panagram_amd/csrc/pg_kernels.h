@@ -301,6 +301,19 @@ hipError_t launch_run_blocks(hipStream_t st, const uint32_t *run_start, const ui
                              const uint2 *contigs, const uint2 *chunks, uint32_t nchunks, const uint64_t *boff, uint32_t nb,
                              uint32_t min_run, uint32_t max_gap, uint32_t max_shift, BlockChunkCount *counts,
                              const BlockChunkOffs *offs, uint64_t total, uint32_t *out);
+// the links of those blocks as variants of B against A (pg_variants.hip; the definitions are there): runs, contigs, chunks and boff
+// as launch_run_blocks takes them (nb = ncb + 1 offsets, the first 0), offs = blocks_stitch's (the carried predecessor of every
+// chunk), the two sides' descriptors and planes.  1 <= k <= 32, max_gap <= VARIANTS_MAX_GAP.
+//   voffs == NULL  count: counts[c] = the VariantChunkCount of chunk c
+//   voffs != NULL  emit: voffs[c] = the records of all chunks before c; out32 = 6 planes of `total` words (posA, lenA, posB, lenB,
+//                  info, mismatches), out64 = 2 planes (the A allele, the B allele in A's orientation); entries at or past `total`
+//                  are never written
+hipError_t launch_link_variants(hipStream_t st, const uint32_t *run_start, const uint32_t *run_end, const uint32_t *run_mate,
+                                const uint2 *contigs, const uint2 *chunks, uint32_t nchunks, const uint64_t *boff, uint32_t nb,
+                                uint32_t k, uint32_t min_run, uint32_t max_gap, uint32_t max_shift, const BlockChunkOffs *offs,
+                                const SeqDesc *sdA, const uint64_t *seqwA, const uint32_t *nmwA, const SeqDesc *sdB, uint32_t ncb,
+                                const uint64_t *seqwB, const uint32_t *nmwB, VariantChunkCount *counts, const uint64_t *voffs,
+                                uint64_t total, uint32_t *out32, uint64_t *out64);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

@@ -642,6 +642,69 @@ def synteny_blocks_last_timing() -> dict:
                     (float(x) for x in ms)))
 
 
+VARIANT_FIELDS = ("contig", "posA", "lenA", "posB", "lenB", "info", "mismatches", "alleleA", "alleleB")
+VARIANT_CLASSES = ("same", "snp", "mnp", "ins", "del", "complex")
+
+
+def _variant_arrays(n):
+    return [np.full(n, NO_MATE, np.uint32) for _ in range(7)] + [np.full(n, (1 << 64) - 1, np.uint64) for _ in range(2)]
+
+
+def run_variants(ctx: Context, k: int, seqs_a: SeqSet, seqs_b: SeqSet, run_contig, run_start, run_end, run_mate, min_run: int = 1,
+                 max_gap: int = 1000, max_shift: int = 100, cap: Optional[int] = None):
+    """(contig, posA, lenA, posB, lenB, info, mismatches, alleleA, alleleB, class counts [6], links): the links of the blocks that
+    ``run_blocks`` chains from these runs as variants of ``seqs_b`` against ``seqs_a`` — every link classified (``VARIANT_CLASSES``),
+    compared base by base on the GPU and, unless its class is ``same``, emitted with its place on both genomes and the first 32
+    bases of both alleles in A's orientation; the definitions are include/panagram_hip.h's.  ``info`` = strand | class << 1 | code
+    of the anchor base << 4 | N flag << 6.  Sorted by (contig, posA).  ``links`` counts all links, class 0 included.  ``cap``
+    (tests of the capacity protocol): ONE call with arrays of ``cap`` entries, returned whole behind the total."""
+    rc, rs, re_, rm = (np.ascontiguousarray(x, np.uint32) for x in (run_contig, run_start, run_end, run_mate))
+    if not (rc.ndim == 1 and rc.shape == rs.shape == re_.shape == rm.shape):
+        raise ValueError("the run arrays differ in length")
+    params = _block_params(min_run, max_gap, max_shift)
+    cls, links, total = np.zeros(6, np.uint64), C.c_uint64(), C.c_uint64()
+
+    def call(n):
+        arrs = _variant_arrays(n)
+        check(ctx._lib.pg_run_variants(ctx._h, int(k), seqs_a._h, seqs_b._h, _ptr(rc), _ptr(rs), _ptr(re_), _ptr(rm), len(rc), *params, n,
+                                       *[_ptr(a) if n else None for a in arrs], _ptr(cls), C.byref(links), C.byref(total)))
+        return arrs
+    if cap is not None:
+        arrs = call(int(cap))
+        return (*arrs, cls, int(links.value), int(total.value))
+    call(0)
+    arrs = call(int(total.value))
+    return (*arrs, cls, int(links.value))
+
+
+def synteny_variants(ctx: Context, k: int, seqs_a: SeqSet, seqs_b: SeqSet, min_run: int = 1, max_gap: int = 1000, max_shift: int = 100,
+                     cap: Optional[int] = None):
+    """(the nine record arrays of ``run_variants``, class counts [6], links, mated positions of A, runs, blocks): the variants of
+    ``seqs_b`` against ``seqs_a`` inside the blocks of their unique matches — table, mates, runs, blocks and variants in one
+    library call; mates, runs and blocks never leave HBM.  ``cap``: the records expected (a second call follows when there are
+    more)."""
+    params = _block_params(min_run, max_gap, max_shift)
+    cls, links, total = np.zeros(6, np.uint64), C.c_uint64(), C.c_uint64()
+    nmated, nruns, nblocks = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    n = int(cap) if cap is not None else 4096
+    while True:
+        arrs = _variant_arrays(n)
+        check(ctx._lib.pg_synteny_variants(ctx._h, int(k), seqs_a._h, seqs_b._h, *params, n, *[_ptr(a) if n else None for a in arrs],
+                                           _ptr(cls), C.byref(links), C.byref(total), C.byref(nmated), C.byref(nruns), C.byref(nblocks)))
+        if int(total.value) <= n:
+            break
+        n = int(total.value)
+    return (*[a[:total.value].copy() for a in arrs], cls, int(links.value), int(nmated.value), int(nruns.value), int(nblocks.value))
+
+
+def synteny_variants_last_timing() -> dict:
+    """HIP-event milliseconds of the kernels of this thread's last ``synteny_variants`` call"""
+    ms = (C.c_float * 9)()
+    check(_lib.load().pg_synteny_variants_last_timing(ms))
+    return dict(zip(("insert_a_ms", "insert_b_ms", "mates_ms", "runs_count_ms", "runs_emit_ms", "blocks_count_ms", "blocks_emit_ms",
+                     "variants_count_ms", "variants_emit_ms"), (float(x) for x in ms)))
+
+
 class PanTable(_Owner):
     """GPU-resident k-mer -> genome-mask table (replaces kmc/bitvec{i})."""
 

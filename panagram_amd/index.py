@@ -1431,6 +1431,29 @@ class Index:
         return (blk, synteny.summary_frame(blk), synteny.totals_frame(a, b, unique[0], unique[1], got[9]),
                 (dict(zip(names_a, lens_a)), dict(zip(names_b, lens_b))))
 
+    def synteny_variants_tables(self, a, b, chroms_a=None, chroms_b=None, k=None, min_run=1, max_gap=1000, max_shift=100):
+        """(variants, class summary, totals, lengths) of ``synteny --variants``: every link of the blocks of
+        ``synteny_blocks_tables`` classified and compared base by base on the GPU (``engine.synteny_variants``; runs and blocks
+        never leave HBM) as ``synteny.variant_frame`` lays them out — the SNPs, insertions and deletions of ``b`` against ``a``
+        with both alleles; the class summary is ``synteny.variant_summary_frame``; totals and lengths as
+        ``synteny_blocks_tables``"""
+        from . import synteny
+        for name, v, lo, hi in (("min_run", min_run, 1, 0x7FFFFFFF), ("max_gap", max_gap, 1, 65536), ("max_shift", max_shift, 0, 0x7FFFFFFF)):
+            if not lo <= int(v) <= hi:
+                raise ValueError(f"synteny: {name}={v} ({lo} to {hi})")
+
+        def run(k, ss_a, ss_b):
+            got = engine.synteny_variants(self.context, k, ss_a, ss_b, min_run, max_gap, max_shift)
+            # (long and N-flagged alleles are cut from the sets while they live; the chromosomes are numbered here and named below:
+            # a narrowed side's set names its pieces, not its chromosomes)
+            frame = synteny.variant_frame(*got[:9], range(len(ss_a.lens)), [int(n) for n in ss_b.lens], range(len(ss_b.lens)), ss_a, ss_b)
+            return got, frame, [engine.synteny_counts(self.context, k, ss, ss)[1] for ss in (ss_a, ss_b)]
+        (got, frame, unique), k, (names_a, lens_a), (names_b, lens_b) = self._synteny_sides(a, b, chroms_a, chroms_b, k, run)
+        for col, names in (("chrA", names_a), ("chrB", names_b)):
+            frame[col] = np.asarray(list(names), object)[frame[col].to_numpy(np.int64)] if len(frame) else np.zeros(0, object)
+        return (frame, synteny.variant_summary_frame(frame, got[9], got[10]), synteny.totals_frame(a, b, unique[0], unique[1], got[11]),
+                (dict(zip(names_a, lens_a)), dict(zip(names_b, lens_b))))
+
     def synteny(self, a, b, chroms_a=None, chroms_b=None, k=None, min_len=1) -> pd.DataFrame:
         """The maximal collinear runs of k-mers that occur exactly once in genome ``a`` and exactly once in genome ``b`` — the
         unique-match segments of a dot plot — found on the GPU from the two genomes' packed sequences: columns ``chrA startA

@@ -15,7 +15,12 @@ with d = 0 every chromosome is one run.  Prints one JSON line.
 --blocks adds the blocks (pg_blocks.hip) on the same genomes: engine.synteny_blocks with --min-run / --max-gap / --max-shift, the
 seven kernel times (engine.synteny_blocks_last_timing), the call's wall time, and beside it the wall time of the route without
 k_run_blocks to the same answer: engine.synteny_segments emitting and downloading every run, then the chain built on the host
-with numpy (chain_host below: the link rule on whole arrays, the blocks by np.add.reduceat).  The two answers must be equal."""
+with numpy (chain_host below: the link rule on whole arrays, the blocks by np.add.reduceat).  The two answers must be equal.
+
+--variants adds the variants (pg_variants.hip) on the same genomes and with the same three parameters: engine.synteny_variants,
+the nine kernel times (engine.synteny_variants_last_timing: the seven above, then k_link_variants counting and emitting), the call's
+wall time, the links of every class, and two checks against the blocks of the same parameters: the links are the sum of (runs - 1)
+over the blocks, and on this workload, which has substitutions only, every variant is a snp or an mnp."""
 import argparse
 import json
 import os
@@ -117,6 +122,37 @@ def blocks_leg(ctx, a, ssa, ssb, out):
     out["blocks"] = res
 
 
+def variants_leg(ctx, a, ssa, ssb, out):
+    params = dict(min_run=a.min_run, max_gap=a.max_gap, max_shift=a.max_shift)
+    var = engine.synteny_variants(ctx, a.k, ssa, ssb, **params)  # warm
+    cap = len(var[0])
+    blk = engine.synteny_blocks(ctx, a.k, ssa, ssb, **params)
+    times, calls = [], []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        got = engine.synteny_variants(ctx, a.k, ssa, ssb, cap=cap, **params)
+        calls.append(time.perf_counter() - t0)
+        times.append(engine.synteny_variants_last_timing())
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(got[:10], var[:10]))  # the same on every call
+    classes = [int(x) for x in var[9]]
+    nruns = var[12]
+    res = dict(params, variants=cap, links=var[10], classes=dict(zip(engine.VARIANT_CLASSES, classes)), runs=nruns, blocks=var[13],
+               bases_a=int(var[2].astype(np.int64).sum()), bases_b=int(var[4].astype(np.int64).sum()),
+               n_flagged=int(((var[5] >> 6) & 1).sum()), bytes_down=cap * 44,
+               checks=dict(links_are_block_runs_less_one=bool(var[10] == int((blk[6].astype(np.int64) - 1).sum())),
+                           classes_add_up=bool(sum(classes) == var[10] and sum(classes[1:]) == cap),
+                           sorted=bool((np.diff(var[0].astype(np.int64) * (1 << 32) + var[1]) > 0).all()),
+                           substitutions_only=bool(classes[3] == classes[4] == classes[5] == 0)))
+    for name in times[0]:
+        v = np.array([t[name] for t in times])
+        res[name] = dict(median=round(float(np.median(v)), 4), min=round(float(v.min()), 4), max=round(float(v.max()), 4))
+    for name in ("blocks_count_ms", "variants_count_ms", "variants_emit_ms"):
+        med = res[name]["median"]
+        res[name]["runs_gb_per_s"] = round(nruns * 12 / med / 1e6, 1) if med > 0 else None
+    res["call_s"] = dict(median=round(float(np.median(calls)), 4), min=round(min(calls), 4), max=round(max(calls), 4))
+    out["variants"] = res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mb", type=float, default=100.0)
@@ -126,6 +162,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--blocks", action="store_true", help="also time engine.synteny_blocks against the host's chain of the runs")
+    ap.add_argument("--variants", action="store_true", help="also time engine.synteny_variants: the nine kernel times, the links by class")
     ap.add_argument("--min-run", type=int, default=1)
     ap.add_argument("--max-gap", type=int, default=1000)
     ap.add_argument("--max-shift", type=int, default=100)
@@ -164,6 +201,8 @@ def main():
     out["call_s"] = dict(median=round(float(np.median(calls)), 4), min=round(min(calls), 4), max=round(max(calls), 4))
     if a.blocks:
         blocks_leg(ctx, a, ssa, ssb, out)
+    if a.variants:
+        variants_leg(ctx, a, ssa, ssb, out)
     ssa.close()
     ssb.close()
     ctx.close()

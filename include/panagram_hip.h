@@ -483,6 +483,37 @@ int pg_result_absence_runs(pg_result *r, int step, uint32_t stride, uint32_t nwi
                            uint64_t cap, uint32_t *run_genome, uint32_t *run_start, uint32_t *run_rows,
                            uint64_t *hist_out, uint64_t *absent_out, uint64_t *edge_out,
                            uint64_t *nruns_out, uint64_t *total_out);
+/* presence profile: WHICH genomes carry a sequence, and how completely?  The question a query sequence that is not in the index
+ * asks once its k-mers have been anchored against the table of every sample (a PG_ANCHOR_ROWS_ONLY result over the queries as
+ * contigs; panagram_amd/search.py), reduced to six numbers per window and genome instead of pg_result_absence_runs' spectrum.
+ * Window i = rows [starts[i], ends[i]) of contig contig[i]'s bitmap.1 rows in HBM (step 1, stride 1), n = ends[i] - starts[i];
+ * no row outside a window is read or counted.  k is the result's own k: row j of the window is the k-mer at the window's bases
+ * [j, j + k), and the window spans n + k - 1 bases.  select_words: the genomes to follow, as ceil(ngenomes / 32) words (bit g =
+ * bit g % 32 of word g / 32; bits at and past ngenomes are ignored, in the words and in a row's last byte); NULL: all of them.
+ * For a selected genome g, p[0..n) being its bit in each row of the window:
+ *   profile_out[(i*ngenomes + g)*6 + 0]  hits     rows with the bit set
+ *   profile_out[(i*ngenomes + g)*6 + 1]  runs     maximal runs of consecutive set rows
+ *   profile_out[(i*ngenomes + g)*6 + 2]  longest  rows of the longest such run (0 if none)
+ *   profile_out[(i*ngenomes + g)*6 + 3]  first    window-relative index of the first set row
+ *   profile_out[(i*ngenomes + g)*6 + 4]  end      one past the last set row; first = end = 0 when hits == 0
+ *   profile_out[(i*ngenomes + g)*6 + 5]  covered  |union over p[j] = 1 of [j, j + k)|: the bases of the window's n + k - 1 that
+ *                                                 lie in at least one held k-mer.  A substituted base clears k rows but leaves one
+ *                                                 base uncovered, so covered / (n + k - 1) reads as an identity where hits / n
+ *                                                 does not.
+ * With L running over the runs of absent rows that lie between two set rows of the window:
+ *   covered = hits + sum of min(k - 1, L) + (k - 1 if hits > 0),   runs = #L + (1 if hits > 0).
+ * Per window, over the selected genomes, when at least one is selected:
+ *   rows_out[i*2 + 0]  all   rows in which every selected genome's bit is set
+ *   rows_out[i*2 + 1]  none  rows in which no selected genome's bit is set
+ * Every output for a genome outside the selection is 0; an empty selection, or an empty window (starts[i] == ends[i]), gives
+ * zeros.
+ * PG_E_INVALID before anything is launched: a NULL argument, fewer than 1 or more than 512 genomes, a window outside its contig,
+ * n + k - 1 >= 2^32, a result without readable rows.  One launch of k_presence_profile over chunks of 4096 rows (every row read
+ * once, all columns followed together; no atomics), then one download of the chunks' partials, which the host stitches;
+ * synchronises. */
+int pg_result_presence_profile(pg_result *r, uint32_t nwin, const uint32_t *contig,
+                               const uint64_t *starts, const uint64_t *ends, const uint32_t *select_words,
+                               uint32_t *profile_out, uint32_t *rows_out);
 /* synteny: WHERE in genome B does the k-mer at a position of genome A lie?  The bitmap rows say whether B holds it; nothing in
  * the reference says where (scripts/pairwise_comp.py stops at per-genome column sums).  These calls work on two sequence sets,
  * the sides A (0) and B (1), and on these definitions:

@@ -20,7 +20,10 @@ that bridge substitutions and small insertions and deletions — a few thousand 
 and the shifted links of each, or as PAF lines for the tools that draw dot plots; the runs never leave the GPU;
 `synteny <index_dir> <A> <B> --variants [--vcf] [--min-run N] [--max-gap G] [--max-shift S] [--summary FILE]` says what differs inside
 those blocks: every link of every block is classified and compared base by base on the GPU, and the SNPs, insertions and deletions of
-B against A come out with their place on both genomes and both alleles — as a table, or as a VCF of B against A."""
+B against A come out with their place on both genomes and both alleles — as a table, or as a VCF of B against A; and
+`search <index_dir> <queries.fa> [--genomes A,B] [--min-frac F] [--by kmers|bases] [--matrix FILE] [--summary FILE]` says which genomes
+carry each query sequence — a gene, a marker, a contig that is NOT in the index — and how completely: the query's k-mers are probed
+against the table of every sample's k-mers and their rows reduced per query and genome on the GPU."""
 import argparse
 import os
 import sys
@@ -157,6 +160,20 @@ def main(argv=None):
                     "basesA basesB per class of variant, then the links without a difference and all links")
     sy.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     sy.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    se = sub.add_parser("search", help="which genomes carry each query sequence, and how completely: the queries' k-mers probed against "
+                                       "the table of every sample's k-mers and reduced per query and genome on the GPU: tab-separated, with "
+                                       "a header, query length kmers genome hits frac covered cov_frac runs longest first end")
+    se.add_argument("index_dir")
+    se.add_argument("queries", metavar="queries.fa", help="FASTA, plain or .gz")
+    se.add_argument("--genomes", default="", metavar="A,B", help="the genomes to report (default: all of them)")
+    se.add_argument("--min-frac", type=float, default=0.0, metavar="F", help="drop lines whose frac (with --by bases: cov_frac) is below F")
+    se.add_argument("--by", choices=["kmers", "bases"], default="kmers", help="what --min-frac, the matrix and the summary's best go by: "
+                    "frac = hits / kmers, or cov_frac = covered / length (default: kmers)")
+    se.add_argument("--matrix", metavar="FILE", default=None, help="also write the queries x genomes table of frac (--by bases: cov_frac)")
+    se.add_argument("--summary", metavar="FILE", default=None, help="also write one line per query: query length kmers all none genomes_hit best best_frac")
+    se.add_argument("--batch-bases", type=int, default=None, metavar="N", help="query bases anchored at a time (default 2^26)")
+    se.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    se.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -286,6 +303,42 @@ def main(argv=None):
         if a.summary:
             summary.to_csv(a.summary, sep="\t", index=False)
         out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
+        return 0
+    if a.cmd == "search":
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"search: {a.index_dir!r} is not an index directory")
+        if not os.path.isfile(a.queries):
+            ap.error(f"search: no query file {a.queries!r}")
+        if not 0.0 <= a.min_frac <= 1.0:
+            ap.error("search: --min-frac is a fraction, 0 to 1")
+        if a.batch_bases is not None and a.batch_bases < 1:
+            ap.error("search: --batch-bases must be at least 1")
+        from .index import Index
+        chosen = [g for g in a.genomes.split(",") if g]
+        try:
+            idx = Index(a.index_dir, mode="r", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"search: {e}")
+        try:
+            import pandas as pd
+            for g in chosen:
+                if g not in idx.genome_names:
+                    ap.error(f"search: unknown genome {g!r} (the index has {', '.join(idx.genome_names)})")
+            for n in idx.genome_names:  # (the table is built from the samples' sequences)
+                fa = idx[n].fasta
+                if pd.isna(fa) or not os.path.isfile(str(fa)):
+                    ap.error(f"search: sample {n!r} of {a.index_dir} has no sequence file to take k-mers of ({fa})")
+            try:
+                out, matrix, summary = idx.search(a.queries, chosen or None, a.min_frac, a.by, a.batch_bases)
+            except (ValueError, KeyError) as e:
+                ap.error(f"search: {e}")
+        finally:
+            idx.close()
+        if a.matrix:
+            matrix.to_csv(a.matrix, sep="\t", index_label="query")
+        if a.summary:
+            summary.to_csv(a.summary, sep="\t", index=False)
+        out.to_csv(a.output if a.output else sys.stdout, sep="\t", index=False)
         return 0
     if a.cmd == "synteny":
         if a.min_len < 1:

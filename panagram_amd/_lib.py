@@ -128,6 +128,7 @@ PROTOTYPES = {
                                            _u64p, C.POINTER(C.c_int)]),
     "pg_result_absence_runs": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64p]),
+    "pg_result_presence_profile": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pg_postable_create": (C.c_int, [_vp, C.c_int, C.c_uint64, _vpp]),
     "pg_postable_destroy": (C.c_int, [_vp]),
     "pg_postable_insert_seqset": (C.c_int, [_vp, C.c_int, _vp]),

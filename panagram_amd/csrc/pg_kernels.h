@@ -263,6 +263,17 @@ hipError_t launch_absence_runs(hipStream_t st, uint32_t ngenomes, const uint8_t 
                                const uint64_t *ends, const uint2 *chunks, uint32_t nchunks, const uint32_t *select,
                                uint32_t maxlen, uint32_t min_len, uint32_t max_len, uint32_t *hist, unsigned long long *absent,
                                uint2 *edges, unsigned long long *nsel, unsigned long long *cursor, uint64_t cap, uint4 *recs);
+// presence profile (pg_profile.hip): per column g what a window's hits, runs, longest run, first / end and covered bases are folded
+// from.  Windows (base, ends) and chunks as above at stride 1, PROFILE_CHUNK rows each; one block per chunk, no block waits for
+// another, no atomics.  partial[(chunk * N + g) * 2 + {0, 1}] = {hits, runs, longest, first} {end, gapsum, head, tail}, chunk-
+// relative (ProfilePartial, pg_profile_host.h, where the caller stitches them); zeros for a column outside `select` (ceil(N / 32)
+// words, bits at and past N zero).  allnone[chunk] = the chunk's rows with every selected column's bit / with none: the caller
+// launches nothing for an empty selection.  1 <= N <= PROFILE_MAX_GENOMES, k >= 1.
+constexpr uint32_t PROFILE_CHUNK = 4096;  // rows per chunk, a multiple of 256
+constexpr uint32_t PROFILE_MAX_GENOMES = 512;
+hipError_t launch_presence_profile(hipStream_t st, uint32_t ngenomes, const uint8_t *rows, const uint64_t *base,
+                                   const uint64_t *ends, const uint2 *chunks, uint32_t nchunks, const uint32_t *select, uint32_t k,
+                                   uint4 *partial, uint2 *allnone);
 // synteny (pg_synteny.hip): a position table of `nslots` (a power of two) 16-byte slots {u64 key, u32 word of side 0, u32 word of
 // side 1}, every byte 0xFF when empty.  A word = pos << 1 | rc: pos the global base offset of the k-mer in its side's contigs laid
 // end to end (off[c] = the bases before contig c), rc = 1 iff the reverse complement is the canonical strand.  jobs[j] =

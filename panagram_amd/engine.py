@@ -67,6 +67,10 @@ PATTERN_MAX_CAP = 1 << 26
 GAPS_CHUNK = 4096
 GAPS_FIRST_CAP = 1 << 16
 
+# presence profile (pg_profile.hip).  PROFILE_CHUNK: rows per workgroup — pg_kernels.h's constant, restated for the tests that aim
+# at chunk edges (tests/test_search_cpu.py holds the two together)
+PROFILE_CHUNK = 4096
+
 
 def tile_positions() -> int:
     """k-mer positions per tile (launch unit; a bit-column block holds tile_positions() // 8 bytes per tile and genome:
@@ -1250,6 +1254,23 @@ class AnchorResult:
             runs[:, 0] = np.repeat(np.arange(len(nruns), dtype=np.int64), nruns.astype(np.int64))
             runs[:, 1], runs[:, 2], runs[:, 3] = rg, rs, rr
         return runs, hist, absent, edges
+
+    def presence_profile(self, contigs, starts, ends, select_words=None):
+        """(profile [nwin, N, 6], rows [nwin, 2]; both uint32): per window and genome ``hits, runs, longest, first, end,
+        covered`` of the genome's column over the window's rows — window i = rows [starts[i], ends[i]) of contig contigs[i]'s
+        bitmap.1 rows.  hits: the set rows; runs: the maximal runs of set rows; longest: the rows of the longest; first / end:
+        window-relative index of the first set row and one past the last (0, 0 without one); covered: the bases of the window's
+        n + k - 1 that lie in at least one held k-mer (k: the result's own).  ``rows[i]``: the rows in which every selected
+        genome's bit is set, and those in which none is.  ``select_words``: the genomes to follow as ceil(N / 32) words (None:
+        all); the others' entries are zero, and so is everything for an empty selection or an empty window.
+        k_presence_profile: one launch, one download."""
+        contigs, starts, ends = _windows(contigs, starts, ends, "window")
+        n, N = len(starts), self.ngenomes
+        sel = None if select_words is None else _mask_words(N, select_words)  # (no selection is a null pointer: all)
+        profile, rows = np.zeros((n, N, 6), np.uint32), np.zeros((n, 2), np.uint32)
+        check(self._lib.pg_result_presence_profile(self._h, n, _ptr(contigs), _ptr(starts), _ptr(ends), _ptr(sel), _ptr(profile),
+                                                   _ptr(rows)))
+        return profile, rows
 
     def write_bgzf(self, step: int, gz_path: str, gzi_path: Optional[str] = None, level: int = 6,
                    threads: int = 1, first_contig: int = 0, ncontigs: Optional[int] = None) -> None:

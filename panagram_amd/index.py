@@ -1373,6 +1373,50 @@ class Index:
         ``query_bitmap(genome, chrom, start, end, step)`` (``Genome.absence_spectrum``)"""
         return self.genomes[genome].absence_spectrum(genomes, chrom, start, end, step, maxlen)
 
+    def search(self, queries, genomes=None, min_frac: float = 0.0, by: str = "kmers", batch_bases: Optional[int] = None):
+        """(long, matrix, summary) — ``search.frames`` — of query sequences that are NOT in the index: which of the ``genomes``
+        (names; None: all) carry each query, and how completely.  ``queries``: a FASTA path (plain or ``.gz``), FASTA bytes, or
+        a list of (name, sequence).  Per query and genome: the query's k-mers the genome holds (``hits``, ``frac`` of the
+        query's k-mers), the query's bases inside at least one held k-mer (``covered``, ``cov_frac`` of its length), the runs
+        of held k-mers, the longest, the first held k-mer and one past the last.  ``min_frac`` drops lines of the long table
+        below it; ``by="bases"`` makes ``cov_frac`` the value that ``min_frac``, the matrix and ``best`` go by.
+        The query's k-mers are probed against the table of every sample's k-mers (built from the samples' sequence files
+        on first use and cached), ``batch_bases`` bases at a time (``search.BATCH_BASES``; batches are cut between records, a
+        longer record is a batch of its own), and their rows are reduced on the GPU (k_presence_profile).  A query shorter than
+        k is reported with zeros.  A k-mer that holds a non-ACGT base is a row of zeros — held by no genome — as everywhere
+        in the project: it counts in ``kmers`` and in ``none``, and cuts runs.  Queries stay in file order; duplicate names
+        are kept.  KeyError: an unknown genome name."""
+        from . import search as srch
+        names = list(self.genome_names)
+        cols = srch.pick_genomes(names, genomes)
+        if by not in ("kmers", "bases"):
+            raise ValueError(f"search: by must be 'kmers' or 'bases', got {by!r}")
+        text, qnames, qlens, offs = srch.read_queries(queries)
+        k, nq, N = int(self.k), len(qnames), len(names)
+        profile, rows = np.zeros((nq, N, len(srch.FIELDS)), np.uint32), np.zeros((nq, 2), np.uint32)
+        words = np.zeros((N + 31) // 32, np.uint32)
+        for c in cols:
+            words[c // 32] |= np.uint32(1 << (c % 32))
+        todo = [(i, j) for i, j in srch.batches(qlens, srch.BATCH_BASES if batch_bases is None else batch_bases) if (qlens[i:j] >= k).any()]
+        table = self._full_table() if todo and cols else None
+        for i, j in todo if table is not None else []:
+            at = i + np.flatnonzero(qlens[i:j] >= k)  # (a query shorter than k has no row: it stays on the host)
+            whole = len(at) == j - i
+            ss = engine.SeqSet.from_fasta(self.context, text[offs[i]:offs[j]] if whole else np.concatenate([text[offs[q]:offs[q + 1]] for q in at]))
+            try:
+                if list(ss.names) != [qnames[q] for q in at] or not np.array_equal(np.asarray(ss.lens, np.int64), qlens[at]):
+                    raise RuntimeError(f"search: records {i} to {j} of the queries were read differently on the host and on the GPU")
+                res = engine.AnchorResult(table, ss, colsums=False, rows_only=True)
+                try:
+                    res.run()
+                    p, r = res.presence_profile(np.arange(len(at)), np.zeros(len(at), np.uint64), qlens[at] - k + 1, words)
+                    profile[at], rows[at] = p, r
+                finally:
+                    res.close()
+            finally:
+                ss.close()
+        return srch.frames(qnames, qlens, k, [names[c] for c in cols], profile[:, cols], rows, min_frac, by)
+
     def _synteny_sides(self, a, b, chroms_a, chroms_b, k, run):
         """``run(k, seqs_a, seqs_b)`` on the two genomes' sequence sets, narrowed to the chosen chromosomes: (its result, k, per
         side (names, lengths) of the chromosomes taken)"""

@@ -27,12 +27,11 @@ COLUMNS = ("contig", "start", "end", "mate_first", "mate_last", "kmers", "runs",
 
 def contig_of(pos, lens_b):
     """the contig of B that holds global position ``pos`` (an empty contig holds none)"""
-    off = 0
-    for c, n in enumerate(lens_b):
-        if off <= pos < off + int(n):
-            return c
-        off += int(n)
-    raise ValueError(f"position {pos} outside genome B")
+    ends = np.cumsum(np.asarray(lens_b, np.int64))
+    c = int(np.searchsorted(ends, pos, side="right"))  # the first contig that ends behind pos: it starts at or before it
+    if pos < 0 or c >= len(ends):
+        raise ValueError(f"position {pos} outside genome B")
+    return c
 
 
 def last_mate(m, n):

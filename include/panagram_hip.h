@@ -659,6 +659,49 @@ int pg_synteny_variants(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seq
 /* the HIP-event times of this host thread's last pg_synteny_variants: ms_out[9] = the seven of pg_synteny_blocks_last_timing (the
  * blocks' emit pass does not run: 0), then k_link_variants counting and k_link_variants emitting. */
 int pg_synteny_variants_last_timing(float *ms_out);
+/* copies: HOW OFTEN does a genome hold the k-mer at a position of a target sequence?  Every answer above is about presence (one bit
+ * per genome and k-mer) or about k-mers that occur once (the position table); nothing in the reference counts the occurrences of a
+ * k-mer along a sequence (scripts/pairwise_comp.py stops at column sums of presence bits).  These calls work on sequence sets —
+ * targets T and a genome G — and on these definitions:
+ *   depth_G(key)  the valid windows of G, over all its contigs, whose canonical k-mer is key: both strands count, windows holding a
+ *                 non-ACGT byte do not exist, contigs shorter than k have none.
+ *   d(p)          of k-mer position p of a target contig: depth_G(key(p)); p is invalid when its window is.  Targets are not
+ *                 deduplicated: positions with one key read one depth.
+ * A count table holds the distinct canonical k-mers of the targets as 8-byte keys in HBM — the number of slots is the power of two
+ * at or above 2 * capacity_keys — and beside them nplanes planes of one 32-bit counter per slot, zero at creation: one plane per
+ * genome counted.  capacity_keys = the targets' k-mer positions always suffices.  PG_E_INVALID: k outside 1..32, capacity_keys
+ * outside 1..2^30, nplanes < 1; PG_E_CAPACITY: no memory for keys and planes.  A table is used by one host thread at a time and is
+ * destroyed before its context. */
+typedef struct pg_copytable pg_copytable;
+int pg_copytable_create(pg_ctx *ctx, int k, uint64_t capacity_keys, uint32_t nplanes, pg_copytable **out);
+int pg_copytable_destroy(pg_copytable *ct);
+/* the key of every valid k-mer of `targets` into the table; may be called more than once, the keys accumulate (the planes keep what
+ * they counted: a key that comes later has missed the genomes counted before).  *distinct = the keys this call added.  Probing is
+ * bounded: a key that finds no slot makes the call return PG_E_CAPACITY, and the table answers PG_E_CAPACITY from then on — destroy
+ * it and create a larger one.  One launch of k_copy_insert; synchronises. */
+int pg_copytable_insert_seqset(pg_copytable *ct, const pg_seqset *targets, uint64_t *distinct);
+/* `genome` streamed through the table, which is only read: plane[slot of key] += 1 for every valid window of the genome whose key
+ * the table holds — added to what the plane held, exactly, whatever the contention (a homopolymer puts every lane on one
+ * counter).  *hits = the windows counted = what this call added to the plane's sum.  PG_E_INVALID before anything is launched: a
+ * plane >= nplanes, a genome of more than 2^32 - 1 k-mer positions (the counters are 32 bits).  One launch of k_copy_count;
+ * synchronises. */
+int pg_copytable_count_seqset(pg_copytable *ct, uint32_t plane, const pg_seqset *genome, uint64_t *hits);
+/* every counter of one plane back to zero */
+int pg_copytable_clear_plane(pg_copytable *ct, uint32_t plane);
+/* the depths along the contigs of `seqs` — any sequence set of the table's context, not only an inserted one: a key the table does
+ * not hold reads depth 0 — in planes plane0 .. plane0 + nplanes - 1 (g below counts from plane0).  With n = pg_seqset_ncontigs:
+ *   valid_out[t]                   t < n: the valid k-mer positions of contig t
+ *   hist_out[(t*nplanes + g)*64 + c]  c < 64: the valid positions of contig t with min(d, 63) == c in plane g (they sum to valid_out[t])
+ *   depth_out                      NULL, or nplanes * pg_seqset_total_kmers(seqs, k) entries: [g][the contigs' positions back to
+ *                                  back] = min(d, 65534), 65535 at an invalid position
+ * PG_E_INVALID before anything is launched: a NULL argument, nplanes < 1 or a range that leaves the table's planes, a sequence set
+ * of another context.  Launches of k_copy_profile over chunks of 4096 positions (no block waits for another, no global atomics),
+ * the chunks' partial histograms summed on the host in 64 bits; synchronises. */
+int pg_copytable_profile(pg_copytable *ct, const pg_seqset *seqs, uint32_t plane0, uint32_t nplanes, uint64_t *hist_out,
+                         uint64_t *valid_out, uint16_t *depth_out);
+/* the HIP-event times, in milliseconds, of this host thread's last calls: ms_out[3] = k_copy_insert of the last insert, k_copy_count
+ * of the last count, k_copy_profile (all its launches) of the last profile — what tools/copies_rate.py reports. */
+int pg_copies_last_timing(float *ms_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

@@ -23,7 +23,11 @@ those blocks: every link of every block is classified and compared base by base 
 B against A come out with their place on both genomes and both alleles — as a table, or as a VCF of B against A; and
 `search <index_dir> <queries.fa> [--genomes A,B] [--min-frac F] [--by kmers|bases] [--matrix FILE] [--summary FILE]` says which genomes
 carry each query sequence — a gene, a marker, a contig that is NOT in the index — and how completely: the query's k-mers are probed
-against the table of every sample's k-mers and their rows reduced per query and genome on the GPU."""
+against the table of every sample's k-mers and their rows reduced per query and genome on the GPU; and
+`copies <index_dir> [targets.fa] [--genes GENOME] [--genomes A,B] [-k K] [--matrix FILE] [--summary FILE] [--track FILE]` says how MANY
+copies of each target sequence — the records of a FASTA, or the annotated genes of a genome — the genomes' assemblies hold: the
+targets' k-mers go into a count table, every genome is streamed through it, and the depths along each target are reduced to a
+histogram and its median on the GPU."""
 import argparse
 import os
 import sys
@@ -174,6 +178,19 @@ def main(argv=None):
     se.add_argument("--batch-bases", type=int, default=None, metavar="N", help="query bases anchored at a time (default 2^26)")
     se.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     se.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    cp = sub.add_parser("copies", help="how many copies of each target sequence the genomes' assemblies hold: the k-mers of every genome "
+                                       "counted against the targets' on the GPU, the depth along each target reduced to its median: "
+                                       "tab-separated, with a header, target length kmers valid genome present frac copies copies_nz mean max_bin")
+    cp.add_argument("index_dir")
+    cp.add_argument("targets", metavar="targets.fa", nargs="?", default=None, help="FASTA, plain or .gz (or --genes)")
+    cp.add_argument("--genes", metavar="GENOME", default=None, help="the targets are the annotated genes of this genome (in place of targets.fa)")
+    cp.add_argument("--genomes", default="", metavar="A,B", help="the genomes to count in (default: all of them)")
+    cp.add_argument("-k", type=int, default=None, help="k-mer length, 1 to 32 (default: the index's)")
+    cp.add_argument("--matrix", metavar="FILE", default=None, help="also write the targets x genomes table of copies")
+    cp.add_argument("--summary", metavar="FILE", default=None, help="also write one line per genome: genome targets 0 1 2 3 4+")
+    cp.add_argument("--track", metavar="FILE", default=None, help="also write the runs of equal depth along every target: target genome start end depth")
+    cp.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    cp.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -339,6 +356,47 @@ def main(argv=None):
         if a.summary:
             summary.to_csv(a.summary, sep="\t", index=False)
         out.to_csv(a.output if a.output else sys.stdout, sep="\t", index=False)
+        return 0
+    if a.cmd == "copies":
+        if (a.targets is None) == (a.genes is None):
+            ap.error("copies: give exactly one of targets.fa and --genes GENOME")
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"copies: {a.index_dir!r} is not an index directory")
+        if a.targets is not None and not os.path.isfile(a.targets):
+            ap.error(f"copies: no target file {a.targets!r}")
+        if a.k is not None and not 1 <= a.k <= 32:
+            ap.error(f"copies: k={a.k} (1 to 32)")
+        from .index import Index
+        from . import copies
+        chosen = [g for g in a.genomes.split(",") if g]
+        try:
+            idx = Index(a.index_dir, mode="r", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"copies: {e}")
+        try:
+            if a.genes is not None and a.genes not in idx.genomes:
+                ap.error(f"copies: unknown genome {a.genes!r} (the index has {', '.join(idx.genome_names)})")
+            try:
+                if a.genes is not None:
+                    got = idx[a.genes].gene_copies(chosen or None, a.k, bool(a.track))
+                else:
+                    got = idx.copies(a.targets, chosen or None, a.k, bool(a.track))
+            except (ValueError, KeyError) as e:
+                ap.error(f"copies: {e}")
+        finally:
+            idx.close()
+        out, matrix, summary = got[:3]
+        if a.matrix:
+            copies.matrix_text(matrix).to_csv(a.matrix, sep="\t", index_label="target")
+        if a.summary:
+            summary.to_csv(a.summary, sep="\t", index=False)
+        if a.track:
+            ng = max(1, len(matrix.columns))
+            with open(a.track, "w") as f:
+                f.write(copies.TRACK_HEADER + "\n")
+                f.writelines(line + "\n" for line in copies.track_lines(list(matrix.index), out["length"].to_numpy()[::ng], idx.k if a.k is None else a.k,
+                                                                        list(matrix.columns), got[3]))
+        copies.long_text(out).to_csv(a.output if a.output else sys.stdout, sep="\t", index=False)
         return 0
     if a.cmd == "synteny":
         if a.min_len < 1:

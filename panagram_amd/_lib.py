@@ -146,6 +146,13 @@ PROTOTYPES = {
     "pg_synteny_variants": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p]),
     "pg_synteny_variants_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
+    "pg_copytable_create": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint32, _vpp]),
+    "pg_copytable_destroy": (C.c_int, [_vp]),
+    "pg_copytable_insert_seqset": (C.c_int, [_vp, _vp, _u64p]),
+    "pg_copytable_count_seqset": (C.c_int, [_vp, C.c_uint32, _vp, _u64p]),
+    "pg_copytable_clear_plane": (C.c_int, [_vp, C.c_uint32]),
+    "pg_copytable_profile": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    "pg_copies_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
     "pg_knn_rows": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "pg_result_write_bgzf": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "pg_bgzf_inflate": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),

@@ -1,0 +1,270 @@
+// pg_api_copies.hip — host side of the C-ABI: the count table of target k-mers, a genome counted into one of its planes, and the
+// depth histograms of sequences along the planes (pg_copies.hip, pg_copies_host.h).
+#include "pg_host.h"
+
+#include "pg_copies_host.h"
+
+static constexpr uint64_t COPIES_MAX_KEYS = COPIES_MAX_SLOTS / 2;   // slots = the power of two at or above 2 * capacity
+static constexpr uint64_t COPIES_MAX_POSITIONS = 0xFFFFFFFFull;     // of one genome: a counter is 32 bits
+static constexpr uint32_t COPIES_MAX_PROBE = 4096;                  // slots a lane walks before it gives up (load <= 0.5: tens at the most)
+static constexpr size_t COPIES_PARTIAL_BYTES = (size_t)256 << 20;   // partials of one profile launch (a longer chunk list goes in pieces)
+
+struct pg_copytable {
+    pg_ctx *ctx;
+    int k;
+    uint64_t capacity, nslots;
+    uint32_t max_probe, nplanes;
+    unsigned long long *d_keys = nullptr;
+    uint32_t *d_planes = nullptr;  // [nplanes][nslots]
+    bool overflowed = false;       // an insert gave up: the table holds a part of the targets and answers nothing any more
+};
+
+namespace {
+
+thread_local float g_copies_ms[3] = {0, 0, 0};  // k_copy_insert, k_copy_count, k_copy_profile of this thread's last calls
+
+// the (contig, piece) jobs of a seqset's k-mer positions in pieces of `piece`, and the first entry of every contig in a back-to-back
+// array of k-mer positions; first[c] = the first job of contig c
+struct CopyWalk {
+    std::vector<uint2> jobs;
+    std::vector<uint64_t> koff, first;  // [n], [n + 1]
+    uint64_t nkmers = 0;
+};
+
+int walk_seqs(const pg_seqset *sq, int k, uint32_t piece, const char *fn, CopyWalk &w) {
+    w.koff.resize(sq->n);
+    w.first.assign((size_t)sq->n + 1, 0);
+    for (uint32_t c = 0; c < sq->n; ++c) {
+        const uint64_t len = sq->desc[c].len, nk = len >= (uint64_t)k ? len - k + 1 : 0;
+        w.koff[c] = w.nkmers;
+        w.first[c] = w.jobs.size();
+        if ((nk + piece - 1) / piece + w.jobs.size() > 0x7FFFFFFFull)
+            return fail(PG_E_INVALID, "%s: more than 2^31 - 1 pieces of %u positions", fn, piece);
+        for (uint64_t q = 0; q * piece < nk; ++q) w.jobs.push_back(make_uint2(c, (uint32_t)q));
+        w.nkmers += nk;
+    }
+    w.first[sq->n] = w.jobs.size();
+    return PG_OK;
+}
+
+void copytable_free(pg_copytable *ct) {
+    hipSetDevice(ct->ctx->device);
+    hipStreamSynchronize(ct->ctx->stream);
+    if (ct->d_planes) hipFree(ct->d_planes);
+    if (ct->d_keys) hipFree(ct->d_keys);
+    pg_ctx *c = ct->ctx;
+    delete ct;
+    ctx_release(c);
+}
+
+int copytable_create(pg_ctx *ctx, int k, uint64_t capacity, uint32_t nplanes, pg_copytable **out) {
+    if (k < 1 || k > 32) return fail(PG_E_INVALID, "pg_copytable_create: k=%d unsupported (1..32)", k);
+    if (capacity < 1 || capacity > COPIES_MAX_KEYS)
+        return fail(PG_E_INVALID, "pg_copytable_create: capacity of %llu keys (1 to 2^30)", (unsigned long long)capacity);
+    if (nplanes < 1) return fail(PG_E_INVALID, "pg_copytable_create: at least one plane");
+    if (int r = use_device(ctx)) return r;
+    std::unique_ptr<pg_copytable> ct(new pg_copytable);
+    ct->ctx = ctx;
+    ct->k = k;
+    ct->capacity = capacity;
+    ct->nslots = 2;
+    while (ct->nslots < 2 * capacity) ct->nslots <<= 1;
+    ct->max_probe = (uint32_t)std::min<uint64_t>(ct->nslots, COPIES_MAX_PROBE);
+    ct->nplanes = nplanes;
+    DevBuf<unsigned long long> keys;
+    DevBuf<uint32_t> planes;
+    hipError_t e = keys.alloc(ct->nslots);
+    if (e == hipSuccess) e = planes.alloc((size_t)ct->nslots * nplanes);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? PG_E_CAPACITY : PG_E_HIP, "pg_copytable_create: %llu slots, %u planes: %s",
+                    (unsigned long long)ct->nslots, nplanes, hipGetErrorString(e));
+    e = hipMemsetAsync(keys.get(), 0xFF, ct->nslots * 8, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(planes.get(), 0, (size_t)ct->nslots * nplanes * 4, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_copytable_create: %s", hipGetErrorString(e));
+    std::swap(ct->d_keys, keys.p);
+    std::swap(ct->d_planes, planes.p);
+    ++ctx->refs;
+    *out = ct.release();
+    return PG_OK;
+}
+
+int copytable_insert(pg_copytable *ct, const pg_seqset *sq, uint64_t *distinct) {
+    if (ct->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_copytable_insert_seqset: table and seqset belong to different contexts");
+    if (ct->overflowed) return fail(PG_E_CAPACITY, "pg_copytable_insert_seqset: the table overflowed before");
+    CopyWalk w;
+    if (int r = walk_seqs(sq, ct->k, COPIES_JOB, "pg_copytable_insert_seqset", w)) return r;
+    if (int r = use_device(ct->ctx)) return r;
+    *distinct = 0;
+    g_copies_ms[0] = 0;
+    if (w.jobs.empty()) return PG_OK;
+    hipStream_t st = ct->ctx->stream;
+    DevBuf<uint2> d_jobs;
+    DevBuf<unsigned long long> d_ctr;
+    unsigned long long ctr[2] = {0, 0};
+    LaunchTimer tm(&g_copies_ms[0]);
+    hipError_t e = d_jobs.upload(w.jobs, st);
+    if (e == hipSuccess) e = d_ctr.alloc(2);
+    if (e == hipSuccess) e = hipMemsetAsync(d_ctr.get(), 0, 16, st);
+    if (e == hipSuccess) e = tm.start(st);
+    if (e == hipSuccess)
+        e = launch_copy_insert(st, ct->k, sq->d_desc, d_jobs.get(), (uint32_t)w.jobs.size(), sq->d_seqw, sq->d_nmw, sq->d_has_n, ct->d_keys,
+                               ct->nslots, ct->max_probe, d_ctr.get());
+    if (e == hipSuccess) e = tm.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr.get(), 16, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_copytable_insert_seqset: %s", hipGetErrorString(e));
+    tm.read();
+    *distinct = ctr[1];
+    if (ctr[0]) {
+        ct->overflowed = true;
+        return fail(PG_E_CAPACITY, "pg_copytable_insert_seqset: %llu slots (created for %llu keys) do not hold the targets' k-mers",
+                    (unsigned long long)ct->nslots, (unsigned long long)ct->capacity);
+    }
+    return PG_OK;
+}
+
+int copytable_count(pg_copytable *ct, uint32_t plane, const pg_seqset *sq, uint64_t *hits) {
+    if (plane >= ct->nplanes) return fail(PG_E_INVALID, "pg_copytable_count_seqset: plane %u of %u", plane, ct->nplanes);
+    if (ct->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_copytable_count_seqset: table and seqset belong to different contexts");
+    if (ct->overflowed) return fail(PG_E_CAPACITY, "pg_copytable_count_seqset: the table overflowed");
+    CopyWalk w;
+    if (int r = walk_seqs(sq, ct->k, COPIES_JOB, "pg_copytable_count_seqset", w)) return r;
+    if (w.nkmers > COPIES_MAX_POSITIONS)
+        return fail(PG_E_INVALID, "pg_copytable_count_seqset: %llu k-mer positions in one genome (the counters hold 2^32 - 1)",
+                    (unsigned long long)w.nkmers);
+    if (int r = use_device(ct->ctx)) return r;
+    *hits = 0;
+    g_copies_ms[1] = 0;
+    if (w.jobs.empty()) return PG_OK;
+    hipStream_t st = ct->ctx->stream;
+    DevBuf<uint2> d_jobs;
+    DevBuf<unsigned long long> d_n;
+    unsigned long long n = 0;
+    LaunchTimer tm(&g_copies_ms[1]);
+    hipError_t e = d_jobs.upload(w.jobs, st);
+    if (e == hipSuccess) e = d_n.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_n.get(), 0, 8, st);
+    if (e == hipSuccess) e = tm.start(st);
+    if (e == hipSuccess)
+        e = launch_copy_count(st, ct->k, sq->d_desc, d_jobs.get(), (uint32_t)w.jobs.size(), sq->d_seqw, sq->d_nmw, sq->d_has_n, ct->d_keys,
+                              ct->nslots, ct->max_probe, ct->d_planes + (size_t)plane * ct->nslots, d_n.get());
+    if (e == hipSuccess) e = tm.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&n, d_n.get(), 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_copytable_count_seqset: %s", hipGetErrorString(e));
+    tm.read();
+    *hits = n;
+    return PG_OK;
+}
+
+int copytable_profile(pg_copytable *ct, const pg_seqset *sq, uint32_t plane0, uint32_t nplanes, uint64_t *hist_out, uint64_t *valid_out,
+                      uint16_t *depth_out) {
+    if (nplanes < 1 || plane0 >= ct->nplanes || nplanes > ct->nplanes - plane0)
+        return fail(PG_E_INVALID, "pg_copytable_profile: planes [%u, %u + %u) of %u", plane0, plane0, nplanes, ct->nplanes);
+    if (ct->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_copytable_profile: table and seqset belong to different contexts");
+    if (ct->overflowed) return fail(PG_E_CAPACITY, "pg_copytable_profile: the table overflowed");
+    CopyWalk w;
+    if (int r = walk_seqs(sq, ct->k, COPIES_CHUNK, "pg_copytable_profile", w)) return r;
+    if (int r = use_device(ct->ctx)) return r;
+    const size_t row = (size_t)nplanes * COPIES_BINS;
+    std::fill(hist_out, hist_out + (size_t)sq->n * row, 0ull);
+    std::fill(valid_out, valid_out + sq->n, 0ull);
+    g_copies_ms[2] = 0;
+    if (w.jobs.empty()) return PG_OK;
+    const size_t nchunks = w.jobs.size();
+    const size_t per = std::max<size_t>(1, COPIES_PARTIAL_BYTES / (row * 4));  // chunks per launch
+    hipStream_t st = ct->ctx->stream;
+    DevBuf<uint2> d_chunks;
+    DevBuf<uint64_t> d_koff;
+    DevBuf<uint32_t> d_part;  // [per][nplanes][64] partials, then [per] valid counts
+    DevBuf<uint16_t> d_depth;
+    std::vector<uint32_t> partial(nchunks * row), valid_partial(nchunks);
+    hipError_t e = d_chunks.upload(w.jobs, st);
+    if (e == hipSuccess) e = d_koff.upload(w.koff, st);
+    if (e == hipSuccess) e = d_part.alloc(std::min(per, nchunks) * (row + 1));
+    if (e == hipSuccess && depth_out) e = d_depth.alloc((size_t)nplanes * w.nkmers);
+    if (e == hipErrorOutOfMemory) return fail(PG_E_CAPACITY, "pg_copytable_profile: no memory for %zu chunks of %u planes", nchunks, nplanes);
+    float total_ms = 0;
+    for (size_t c0 = 0; c0 < nchunks && e == hipSuccess; c0 += per) {
+        const size_t n = std::min(per, nchunks - c0);
+        float ms = 0;
+        LaunchTimer tm(&ms);
+        e = tm.start(st);
+        if (e == hipSuccess)
+            e = launch_copy_profile(st, ct->k, sq->d_desc, d_chunks.get() + c0, (uint32_t)n, d_koff.get(), sq->d_seqw, sq->d_nmw, sq->d_has_n,
+                                    ct->d_keys, ct->nslots, ct->max_probe, ct->d_planes + (size_t)plane0 * ct->nslots, nplanes, d_part.get(),
+                                    d_part.get() + n * row, d_depth.get(), w.nkmers);
+        if (e == hipSuccess) e = tm.stop(st);
+        if (e == hipSuccess) e = hipMemcpyAsync(partial.data() + c0 * row, d_part.get(), n * row * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(valid_partial.data() + c0, d_part.get() + n * row, n * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess) tm.read();
+        total_ms += ms;
+    }
+    if (e == hipSuccess && depth_out) {
+        e = hipMemcpyAsync(depth_out, d_depth.get(), (size_t)nplanes * w.nkmers * 2, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (e != hipSuccess) return fail(PG_E_HIP, "pg_copytable_profile: %s", hipGetErrorString(e));
+    g_copies_ms[2] = total_ms;
+    copies_stitch(sq->n, w.first.data(), nplanes, COPIES_BINS, partial.data(), valid_partial.data(), hist_out, valid_out);
+    return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_copytable_create(pg_ctx *ctx, int k, uint64_t capacity_keys, uint32_t nplanes, pg_copytable **out) {
+    PG_API_BEGIN
+    if (!ctx || !out) return fail(PG_E_INVALID, "pg_copytable_create: NULL argument");
+    return copytable_create(ctx, k, capacity_keys, nplanes, out);
+    PG_API_END
+}
+
+extern "C" int pg_copytable_destroy(pg_copytable *ct) {
+    PG_API_BEGIN
+    if (ct) copytable_free(ct);
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_copytable_insert_seqset(pg_copytable *ct, const pg_seqset *targets, uint64_t *distinct) {
+    PG_API_BEGIN
+    if (!ct || !targets || !distinct) return fail(PG_E_INVALID, "pg_copytable_insert_seqset: NULL argument");
+    return copytable_insert(ct, targets, distinct);
+    PG_API_END
+}
+
+extern "C" int pg_copytable_count_seqset(pg_copytable *ct, uint32_t plane, const pg_seqset *genome, uint64_t *hits) {
+    PG_API_BEGIN
+    if (!ct || !genome || !hits) return fail(PG_E_INVALID, "pg_copytable_count_seqset: NULL argument");
+    return copytable_count(ct, plane, genome, hits);
+    PG_API_END
+}
+
+extern "C" int pg_copytable_clear_plane(pg_copytable *ct, uint32_t plane) {
+    PG_API_BEGIN
+    if (!ct) return fail(PG_E_INVALID, "pg_copytable_clear_plane: NULL argument");
+    if (plane >= ct->nplanes) return fail(PG_E_INVALID, "pg_copytable_clear_plane: plane %u of %u", plane, ct->nplanes);
+    if (int r = use_device(ct->ctx)) return r;
+    HIP_TRY(hipMemsetAsync(ct->d_planes + (size_t)plane * ct->nslots, 0, ct->nslots * 4, ct->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ct->ctx->stream));
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_copytable_profile(pg_copytable *ct, const pg_seqset *seqs, uint32_t plane0, uint32_t nplanes, uint64_t *hist_out,
+                                    uint64_t *valid_out, uint16_t *depth_out) {
+    PG_API_BEGIN
+    if (!ct || !seqs || !hist_out || !valid_out) return fail(PG_E_INVALID, "pg_copytable_profile: NULL argument");
+    return copytable_profile(ct, seqs, plane0, nplanes, hist_out, valid_out, depth_out);
+    PG_API_END
+}
+
+extern "C" int pg_copies_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_copies_last_timing: NULL argument");
+    std::copy(g_copies_ms, g_copies_ms + 3, ms_out);
+    return PG_OK;
+    PG_API_END
+}

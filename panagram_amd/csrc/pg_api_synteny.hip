@@ -23,22 +23,6 @@ struct pg_postable {
 
 namespace {
 
-// the HIP-event time of one launch, for pg_synteny_last_timing: armed only where the caller hands in a place for it
-struct LaunchTimer {
-    float *ms;
-    Event a, b;
-    explicit LaunchTimer(float *out) : ms(out) {}
-    hipError_t start(hipStream_t st) {
-        if (!ms) return hipSuccess;
-        hipError_t e = a.create(hipEventDefault);
-        if (e == hipSuccess) e = b.create(hipEventDefault);
-        return e == hipSuccess ? hipEventRecord(a.get(), st) : e;
-    }
-    hipError_t stop(hipStream_t st) { return ms ? hipEventRecord(b.get(), st) : hipSuccess; }
-    void read() {  // (behind the stream's synchronise)
-        if (ms && hipEventElapsedTime(ms, a.get(), b.get()) != hipSuccess) *ms = -1.0f;
-    }
-};
 thread_local float g_last_ms[5] = {0, 0, 0, 0, 0};  // insert A, insert B, mates, runs (count), runs (emit) of the last pg_synteny_segments
 thread_local float g_blocks_ms[7] = {0, 0, 0, 0, 0, 0, 0};  // those five, blocks (count), blocks (emit) of the last pg_synteny_blocks
 thread_local float g_variants_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // those seven, variants (count), variants (emit) of the last pg_synteny_variants

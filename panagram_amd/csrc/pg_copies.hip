@@ -1,0 +1,242 @@
+// pg_copies.hip — HOW OFTEN does a genome hold the k-mer at a position of a target sequence (gfx950)?  The bitmap rows answer
+// whether; the position table of pg_synteny.hip answers where, for k-mers that occur once.  This unit counts: a hash table of the
+// targets' canonical k-mers with counter planes beside it, a genome streamed through it per plane, and the counts reduced along
+// the targets into a histogram of depths per target contig and genome.
+//
+// Definitions (tests/copies_ref.py is the same in numpy):
+//   valid window   as everywhere: a window holding a non-ACGT base does not exist, a contig shorter than k has none.
+//   depth_G(key)   the valid windows of genome G, over all its contigs, whose canonical key is `key` — both strands count through
+//                  the canonical form.
+//   d(p)           of position p of a target contig: depth_G(key(p)) when the window at p is valid; the position is invalid
+//                  otherwise.  Targets are not deduplicated: a key repeated inside the targets has one slot, and every position
+//                  that has the key reads the same depth.
+//   hist[t][G][c]  the valid positions of target contig t with min(d, COPIES_BINS - 1) == c;  valid[t] = their number.
+//   track          depth[G][koff[t] + p] = min(d, 65534) as u16, 65535 at an invalid position (koff: the k-mer positions of the
+//                  contigs before t).
+//
+// The table: `nslots` (a power of two, at most 2^31) 8-byte keys, EMPTY_KEY when free (no canonical k-mer, pg_device.h), home slot
+// = sketch_hash(key) & (nslots - 1), linear probing over at most `max_probe` slots — no loop here is unbounded.  Beside the keys,
+// planes of nslots u32 counters: plane g of slot s at planes[g * nslots + s].
+//   k_copy_insert   one launch over (contig, chunk) jobs of the targets, as k_pos_insert walks them.  A lane claims its key by a
+//                   64-bit CAS (EMPTY -> key) or finds it claimed already; a lane that runs out of probes sets ctr[0].  The keys
+//                   newly claimed are counted: a ballot per wave, one atomic per block (ctr[1]).
+//   k_copy_count    the same walk over a whole genome, the table read-only: a valid window probes until EMPTY_KEY (its key is no
+//                   target's: nothing to do) or its key, and adds 1 to the plane's counter of that slot.  Integer atomic adds:
+//                   the result is exact whatever order and contention.  Equal slots are folded inside a wave first, in up to
+//                   COPY_FOLD_TURNS turns: the first lane with a hit takes every lane that has its slot — a homopolymer puts all 64
+//                   on one, a satellite of period p on at most p — and adds their number in ONE atomic; a turn that finds its lane
+//                   alone ends the folding, and the lanes left add 1 each.  A wave without a hit skips all of it.  Measured
+//                   (profiles/copies_rate.txt): 100 Mb with a fifth in repeats 1.81 ms, against 56.6 ms with one atomic per lane
+//                   and 29.0 ms when only runs of neighbouring lanes are folded; no cost where every hit has a slot of its own.
+//                   Hits: a ballot per wave, one atomic per block, as k_pos_mates counts mates.
+//   k_copy_profile  the structure of k_presence_profile: one block per chunk of COPIES_CHUNK positions of one target contig, no
+//                   block waits for another, no global atomic.  A lane resolves the slot of its 16 positions once (LDS: a slot
+//                   number, or the marks INVALID / ABSENT — a key that is not in the table reads depth 0).  Then per plane: the
+//                   depths from the plane, the 64-bin histogram in LDS — per wave, one plain add by lane 0 per distinct bin among
+//                   the wave's lanes (ballot match: depths along a gene are few) — the four waves' sums to partial[], and the u16
+//                   depths to the track when one is asked for.  The host sums a contig's chunks (pg_copies_host.h).
+// Every write to HBM is a vector store or a vector atomic.
+#include "pg_kernels.h"
+
+namespace pg {
+
+constexpr uint32_t COPY_FOLD_TURNS = 8;  // slots a wave folds before its lanes add for themselves (a satellite of period p: at most p)
+constexpr uint32_t SLOT_INVALID = 0xFFFFFFFFu, SLOT_ABSENT = 0xFFFFFFFEu;  // (slots are below 2^31)
+static_assert(COPIES_CHUNK % 256 == 0, "a chunk is a whole number of tiles");
+static_assert(COPIES_BINS == 64, "one bin per lane of a wave");
+
+__device__ __forceinline__ uint64_t copy_key(const uint64_t *seqw, uint64_t p, int k) { return canonical_from_le(extract_bases(seqw, p), k); }
+
+// the slot of `key` in a table that is not being written: its number, or SLOT_ABSENT
+__device__ __forceinline__ uint32_t copy_lookup(const unsigned long long *__restrict__ keys, uint64_t smask, uint32_t max_probe, uint64_t key) {
+    uint64_t s = sketch_hash(key) & smask;
+    for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
+        const unsigned long long cur = keys[s];
+        if (cur == EMPTY_KEY) break;
+        if (cur == key) return (uint32_t)s;
+    }
+    return SLOT_ABSENT;
+}
+
+// job = positions [y * COPIES_JOB, (y + 1) * COPIES_JOB) of contig x, which holds at least k bases
+__global__ __launch_bounds__(256) void k_copy_insert(int k, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ jobs,
+                                                     const uint64_t *seqw_all, const uint32_t *nmw_all, const uint32_t *has_n,
+                                                     unsigned long long *keys, uint64_t nslots, uint32_t max_probe,
+                                                     unsigned long long *ctr) {
+    __shared__ uint32_t wsum[4];
+    const uint2 job = jobs[blockIdx.x];
+    const SeqDesc d = sd[job.x];
+    const uint64_t nkmers = d.len - (uint64_t)k + 1, p0 = (uint64_t)job.y * COPIES_JOB, p1 = min(nkmers, p0 + COPIES_JOB);
+    const uint64_t *seqw = seqw_all + d.seq_off;
+    const uint32_t *nmw = nmw_all + d.seq_off;
+    const bool hasn = has_n[job.x] != 0;
+    const uint64_t smask = nslots - 1;
+    uint32_t nclaimed = 0;  // (per wave: every lane of a wave holds the same sum)
+    for (uint64_t q = p0; q < p1; q += 256) {  // (bounds uniform over the block: every lane reaches the ballot)
+        const uint64_t p = q + threadIdx.x;
+        bool claimed = false;
+        if (p < p1 && !(hasn && extract_nmask(nmw, p, k))) {
+            const uint64_t key = copy_key(seqw, p, k);
+            uint64_t s = sketch_hash(key) & smask;
+            bool done = false;
+            for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
+                unsigned long long cur = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (cur == EMPTY_KEY) {
+                    cur = atomicCAS(&keys[s], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
+                    if (cur == EMPTY_KEY) {
+                        claimed = true;
+                        cur = key;
+                    }
+                }
+                if (cur != key) continue;
+                done = true;
+                break;
+            }
+            if (!done) atomicOr(reinterpret_cast<unsigned int *>(ctr), 1u);
+        }
+        nclaimed += (uint32_t)__popcll(__ballot(claimed));
+    }
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = nclaimed;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (n) atomicAdd(ctr + 1, (unsigned long long)n);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_copy_count(int k, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ jobs,
+                                                    const uint64_t *seqw_all, const uint32_t *nmw_all, const uint32_t *has_n,
+                                                    const unsigned long long *__restrict__ keys, uint64_t nslots, uint32_t max_probe,
+                                                    uint32_t *plane, unsigned long long *hits) {
+    __shared__ uint32_t wsum[4];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint2 job = jobs[blockIdx.x];
+    const SeqDesc d = sd[job.x];
+    const uint64_t nkmers = d.len - (uint64_t)k + 1, p0 = (uint64_t)job.y * COPIES_JOB, p1 = min(nkmers, p0 + COPIES_JOB);
+    const uint64_t *seqw = seqw_all + d.seq_off;
+    const uint32_t *nmw = nmw_all + d.seq_off;
+    const bool hasn = has_n[job.x] != 0;
+    const uint64_t smask = nslots - 1;
+    uint32_t found = 0;  // (per wave)
+    for (uint64_t q = p0; q < p1; q += 256) {  // (bounds uniform over the block)
+        const uint64_t p = q + threadIdx.x;
+        uint32_t slot = SLOT_ABSENT;
+        if (p < p1 && !(hasn && extract_nmask(nmw, p, k))) slot = copy_lookup(keys, smask, max_probe, copy_key(seqw, p, k));
+        const bool hit = slot != SLOT_ABSENT;
+        const uint64_t hm = __ballot(hit);
+        found += (uint32_t)__popcll(hm);
+        if (hm == 0) continue;  // (wave-uniform)
+        // turns: the first lane left takes every lane that has its slot and adds their number.  A turn that finds the lane alone —
+        // hits scattered over the table — ends the folding, as the last turn does: the lanes left add for themselves
+        uint64_t todo = hm;
+        for (uint32_t turn = 0; turn < COPY_FOLD_TURNS && todo; ++turn) {
+            const uint32_t first = (uint32_t)__builtin_ctzll(todo);
+            const uint32_t s0 = (uint32_t)__shfl((int)slot, (int)first);
+            const uint64_t m = __ballot(hit && slot == s0);
+            const uint32_t n = (uint32_t)__popcll(m);
+            if (lane == first) atomicAdd(&plane[s0], n);
+            todo &= ~m;
+            if (n == 1) break;
+        }
+        if ((todo >> lane) & 1ull) atomicAdd(&plane[slot], 1u);
+    }
+    if (lane == 0) wsum[threadIdx.x >> 6] = found;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (n) atomicAdd(hits, (unsigned long long)n);
+    }
+}
+
+// chunk = positions [y * COPIES_CHUNK, (y + 1) * COPIES_CHUNK) of contig x, which holds at least k bases
+__global__ __launch_bounds__(256) void k_copy_profile(int k, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ chunks,
+                                                      const uint64_t *__restrict__ koff, const uint64_t *seqw_all,
+                                                      const uint32_t *nmw_all, const uint32_t *has_n,
+                                                      const unsigned long long *__restrict__ keys, uint64_t nslots, uint32_t max_probe,
+                                                      const uint32_t *__restrict__ planes, uint32_t nplanes,
+                                                      uint32_t *__restrict__ partial, uint32_t *__restrict__ valid_partial,
+                                                      uint16_t *__restrict__ depth, uint64_t depth_stride) {
+    __shared__ uint32_t slot[COPIES_CHUNK];
+    __shared__ uint32_t whist[4][COPIES_BINS];
+    __shared__ uint32_t wvalid[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint2 ck = chunks[blockIdx.x];
+    const SeqDesc d = sd[ck.x];
+    const uint64_t nkmers = d.len - (uint64_t)k + 1, c0 = (uint64_t)ck.y * COPIES_CHUNK, ce = min(nkmers, c0 + COPIES_CHUNK);
+    const uint64_t *seqw = seqw_all + d.seq_off;
+    const uint32_t *nmw = nmw_all + d.seq_off;
+    const bool hasn = has_n[ck.x] != 0;
+    const uint64_t smask = nslots - 1;
+    // the slots: entry i of the chunk is written and read by thread i & 255 alone
+    uint32_t nvalid = 0;  // (per wave)
+    for (uint32_t i = tid; i < COPIES_CHUNK; i += 256) {
+        const uint64_t p = c0 + i;
+        uint32_t s = SLOT_INVALID;
+        if (p < ce && !(hasn && extract_nmask(nmw, p, k))) s = copy_lookup(keys, smask, max_probe, copy_key(seqw, p, k));
+        slot[i] = s;
+        nvalid += (uint32_t)__popcll(__ballot(s != SLOT_INVALID));
+    }
+    if (lane == 0) wvalid[wave] = nvalid;
+    __syncthreads();
+    if (tid == 0) valid_partial[blockIdx.x] = wvalid[0] + wvalid[1] + wvalid[2] + wvalid[3];
+    uint16_t *track = depth ? depth + koff[ck.x] + c0 : nullptr;
+    for (uint32_t g = 0; g < nplanes; ++g) {
+        const uint32_t *pl = planes + (uint64_t)g * nslots;
+        whist[wave][lane] = 0;
+        __syncthreads();
+        for (uint32_t i = tid; i < COPIES_CHUNK; i += 256) {
+            const uint32_t s = slot[i];
+            const bool valid = s != SLOT_INVALID;
+            const uint32_t dp = valid && s != SLOT_ABSENT ? pl[s] : 0u;
+            if (track && c0 + i < ce) track[(uint64_t)g * depth_stride + i] = (uint16_t)(valid ? min(dp, COPIES_DEPTH_MAX) : COPIES_DEPTH_INVALID);
+            const uint32_t bin = min(dp, COPIES_BINS - 1);
+            uint64_t todo = __ballot(valid);
+            while (todo) {  // (wave-uniform: one turn per distinct bin among the wave's valid lanes, 64 at the most)
+                const uint32_t b = (uint32_t)__shfl((int)bin, (int)__builtin_ctzll(todo));
+                const uint64_t m = __ballot(valid && bin == b);
+                if (lane == 0) whist[wave][b] += (uint32_t)__popcll(m);
+                todo &= ~m;
+            }
+        }
+        __syncthreads();
+        if (tid < COPIES_BINS)
+            partial[((uint64_t)blockIdx.x * nplanes + g) * COPIES_BINS + tid] = whist[0][tid] + whist[1][tid] + whist[2][tid] + whist[3][tid];
+        __syncthreads();
+    }
+}
+
+static bool table_ok(int k, uint64_t nslots, const void *keys) {
+    return k >= 1 && k <= 32 && nslots != 0 && !(nslots & (nslots - 1)) && nslots <= COPIES_MAX_SLOTS && keys;
+}
+
+hipError_t launch_copy_insert(hipStream_t st, int k, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint64_t *seqw,
+                              const uint32_t *nmw, const uint32_t *has_n, unsigned long long *keys, uint64_t nslots,
+                              uint32_t max_probe, unsigned long long *ctr) {
+    if (njobs == 0) return hipSuccess;
+    if (!table_ok(k, nslots, keys) || !ctr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_copy_insert, dim3(njobs), dim3(256), 0, st, k, sd, jobs, seqw, nmw, has_n, keys, nslots, max_probe, ctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_copy_count(hipStream_t st, int k, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint64_t *seqw,
+                             const uint32_t *nmw, const uint32_t *has_n, const unsigned long long *keys, uint64_t nslots,
+                             uint32_t max_probe, uint32_t *plane, unsigned long long *hits) {
+    if (njobs == 0) return hipSuccess;
+    if (!table_ok(k, nslots, keys) || !plane || !hits) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_copy_count, dim3(njobs), dim3(256), 0, st, k, sd, jobs, seqw, nmw, has_n, keys, nslots,
+                       max_probe, plane, hits);
+    return hipGetLastError();
+}
+
+hipError_t launch_copy_profile(hipStream_t st, int k, const SeqDesc *sd, const uint2 *chunks, uint32_t nchunks, const uint64_t *koff,
+                               const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n, const unsigned long long *keys,
+                               uint64_t nslots, uint32_t max_probe, const uint32_t *planes, uint32_t nplanes, uint32_t *partial,
+                               uint32_t *valid_partial, uint16_t *depth, uint64_t depth_stride) {
+    if (nchunks == 0) return hipSuccess;
+    if (!table_ok(k, nslots, keys) || !planes || nplanes == 0 || !partial || !valid_partial || !koff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_copy_profile, dim3(nchunks), dim3(256), 0, st, k, sd, chunks, koff, seqw, nmw, has_n, keys, nslots, max_probe,
+                       planes, nplanes, partial, valid_partial, depth, depth_stride);
+    return hipGetLastError();
+}
+
+}  // namespace pg

@@ -227,6 +227,23 @@ struct Event {
     hipEvent_t get() const { return ev; }
 };
 
+// the HIP-event time of one launch, for the *_last_timing calls: armed only where the caller hands in a place for it
+struct LaunchTimer {
+    float *ms;
+    Event a, b;
+    explicit LaunchTimer(float *out) : ms(out) {}
+    hipError_t start(hipStream_t st) {
+        if (!ms) return hipSuccess;
+        hipError_t e = a.create(hipEventDefault);
+        if (e == hipSuccess) e = b.create(hipEventDefault);
+        return e == hipSuccess ? hipEventRecord(a.get(), st) : e;
+    }
+    hipError_t stop(hipStream_t st) { return ms ? hipEventRecord(b.get(), st) : hipSuccess; }
+    void read() {  // (behind the stream's synchronise)
+        if (ms && hipEventElapsedTime(ms, a.get(), b.get()) != hipSuccess) *ms = -1.0f;
+    }
+};
+
 static constexpr uint32_t MAX_PROBE = 512;  // lines an insert may walk before the table is grown
 static constexpr double GROW_AT = 0.55;     // grow when keys > GROW_AT * slots
 #ifndef PG_INLINE_LAYOUT

@@ -325,6 +325,29 @@ hipError_t launch_link_variants(hipStream_t st, const uint32_t *run_start, const
                                 const SeqDesc *sdA, const uint64_t *seqwA, const uint32_t *nmwA, const SeqDesc *sdB, uint32_t ncb,
                                 const uint64_t *seqwB, const uint32_t *nmwB, VariantChunkCount *counts, const uint64_t *voffs,
                                 uint64_t total, uint32_t *out32, uint64_t *out64);
+// copy number (pg_copies.hip; the definitions are there): a count table of `nslots` (a power of two, at most COPIES_MAX_SLOTS)
+// 8-byte keys, EMPTY_KEY when free, and beside it counter planes of nslots u32 each.  jobs[j] = (contig, chunk): k-mer positions
+// [chunk, chunk + 1) x COPIES_JOB of a contig of at least k bases.  A lane walks at most max_probe slots.
+//   insert   claims a slot for every valid k-mer's key; ctr[0] (zeroed by the caller) becomes nonzero when an insert gave up,
+//            ctr[1] += the keys newly claimed
+//   count    plane[slot] += 1 for every valid window whose key is in the table (which it only reads); *hits (zeroed) += them
+//   profile  chunk = (contig, chunk number): the COPIES_CHUNK positions from there, cut at the contig's end.  Per plane g of
+//            planes[g * nslots + slot], g < nplanes: partial[(chunk * nplanes + g) * COPIES_BINS + c] = the chunk's valid positions
+//            with min(depth, COPIES_BINS - 1) == c; valid_partial[chunk] = its valid positions; depth != NULL: depth[g *
+//            depth_stride + koff[contig] + p] = min(depth, COPIES_DEPTH_MAX), COPIES_DEPTH_INVALID at an invalid position
+constexpr uint32_t COPIES_BINS = 64, COPIES_CHUNK = 4096, COPIES_JOB = 1u << 14;
+constexpr uint32_t COPIES_DEPTH_MAX = 65534, COPIES_DEPTH_INVALID = 65535;
+constexpr uint64_t COPIES_MAX_SLOTS = 1ull << 31;  // a slot number and the two marks of k_copy_profile fit 32 bits
+hipError_t launch_copy_insert(hipStream_t st, int k, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint64_t *seqw,
+                              const uint32_t *nmw, const uint32_t *has_n, unsigned long long *keys, uint64_t nslots,
+                              uint32_t max_probe, unsigned long long *ctr);
+hipError_t launch_copy_count(hipStream_t st, int k, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint64_t *seqw,
+                             const uint32_t *nmw, const uint32_t *has_n, const unsigned long long *keys, uint64_t nslots,
+                             uint32_t max_probe, uint32_t *plane, unsigned long long *hits);
+hipError_t launch_copy_profile(hipStream_t st, int k, const SeqDesc *sd, const uint2 *chunks, uint32_t nchunks, const uint64_t *koff,
+                               const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n, const unsigned long long *keys,
+                               uint64_t nslots, uint32_t max_probe, const uint32_t *planes, uint32_t nplanes, uint32_t *partial,
+                               uint32_t *valid_partial, uint16_t *depth, uint64_t depth_stride);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

@@ -709,6 +709,80 @@ def synteny_variants_last_timing() -> dict:
                      "variants_count_ms", "variants_emit_ms"), (float(x) for x in ms)))
 
 
+COPIES_BINS = 64  # depth bins of a copy-number histogram: bin c = depth c, the last = that depth and beyond
+COPIES_CHUNK = 4096
+DEPTH_INVALID = 0xFFFF  # a position of a depth track whose window holds a non-ACGT base
+
+
+class CopyTable:
+    """Count table of target k-mers in HBM (pg_copies.hip): the distinct canonical k-mers of the inserted sequence sets, and
+    ``nplanes`` planes of one 32-bit counter per key — one plane per genome counted.  ``capacity_keys``: the distinct keys it must
+    hold — the targets' k-mer positions always suffice.  Targets whose keys do not fit raise with code -4 (PG_E_CAPACITY); the
+    table is then of no further use."""
+
+    def __init__(self, ctx: Context, k: int, capacity_keys: int, nplanes: int = 1):
+        self.ctx, self._lib, self.k, self.nplanes = ctx, ctx._lib, int(k), int(nplanes)
+        h = C.c_void_p()
+        check(self._lib.pg_copytable_create(ctx._h, int(k), int(capacity_keys), int(nplanes), C.byref(h)))
+        self._h = h
+        ctx._adopt(self)
+
+    def insert(self, targets: SeqSet) -> int:
+        """the keys of ``targets``' valid k-mers into the table (keys accumulate over calls); the keys this call added"""
+        n = C.c_uint64()
+        check(self._lib.pg_copytable_insert_seqset(self._h, targets._h, C.byref(n)))
+        return int(n.value)
+
+    def count(self, plane: int, genome: SeqSet) -> int:
+        """every valid k-mer of ``genome`` whose key the table holds adds 1 to that key's counter in ``plane``; how many did"""
+        if plane < 0:
+            raise ValueError(f"plane {plane}")
+        n = C.c_uint64()
+        check(self._lib.pg_copytable_count_seqset(self._h, int(plane), genome._h, C.byref(n)))
+        return int(n.value)
+
+    def clear(self, plane: int) -> None:
+        if plane < 0:
+            raise ValueError(f"plane {plane}")
+        check(self._lib.pg_copytable_clear_plane(self._h, int(plane)))
+
+    def profile(self, seqs: SeqSet, plane0: int = 0, nplanes: Optional[int] = None, track: bool = False):
+        """(hist [contigs, planes, COPIES_BINS] uint64, valid [contigs] uint64[, depths [planes, k-mer positions] uint16]) of the
+        contigs of ``seqs`` — any sequence set, a key the table does not hold reads depth 0 — in planes ``plane0 .. plane0 +
+        nplanes - 1`` (None: all from plane0 on).  hist[t, g, c] = the valid positions of contig t whose k-mer genome g holds
+        min(depth, 63) == c times; depths: min(depth, 65534) per position, the contigs back to back, DEPTH_INVALID where the
+        window holds a non-ACGT base."""
+        npl = self.nplanes - int(plane0) if nplanes is None else int(nplanes)
+        if plane0 < 0 or npl < 0:
+            raise ValueError(f"planes {plane0}, {nplanes}")
+        n = len(seqs.lens)
+        hist, valid = np.zeros((n, max(npl, 0), COPIES_BINS), np.uint64), np.zeros(n, np.uint64)
+        total = seqs.total_kmers(self.k)
+        depths = np.zeros((max(npl, 0), total), np.uint16) if track else None
+        pad = np.zeros(1, np.uint64)  # (a set without a contig: the library still wants somewhere to point)
+        check(self._lib.pg_copytable_profile(self._h, seqs._h, int(plane0), npl, _ptr(hist if hist.size else pad),
+                                             _ptr(valid if n else pad), _ptr(depths if depths is None or depths.size else pad)))
+        return (hist, valid, depths) if track else (hist, valid)
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.pg_copytable_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def copies_last_timing() -> dict:
+    """HIP-event milliseconds of k_copy_insert, k_copy_count and k_copy_profile in this thread's last ``CopyTable`` calls"""
+    ms = (C.c_float * 3)()
+    check(_lib.load().pg_copies_last_timing(ms))
+    return dict(zip(("insert_ms", "count_ms", "profile_ms"), (float(x) for x in ms)))
+
+
 class PanTable(_Owner):
     """GPU-resident k-mer -> genome-mask table (replaces kmc/bitvec{i})."""
 

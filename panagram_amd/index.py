@@ -1417,6 +1417,70 @@ class Index:
                 ss.close()
         return srch.frames(qnames, qlens, k, [names[c] for c in cols], profile[:, cols], rows, min_frac, by)
 
+    def copies(self, targets, genomes=None, k=None, track: bool = False):
+        """(long, matrix, summary) — ``copies.frames`` — of target sequences: how many copies of each target the assemblies of
+        the ``genomes`` (names; None: all) hold.  ``targets``: a FASTA path (plain or ``.gz``), FASTA bytes, or a list of (name,
+        sequence).  Per target and genome: the histogram of the depth — how often the genome holds the canonical k-mer — over
+        the target's valid k-mer positions, reduced to ``present``, ``copies`` (its lower median), ``copies_nz``, ``mean`` and
+        ``max_bin``.  ``track=True`` adds a fourth value, the depth of every position [genomes, the targets' k-mer positions back
+        to back] (``copies.track_lines`` prints its runs).
+        One count table is sized from the targets' k-mer positions (``engine.CopyTable``); the genomes are taken in batches of
+        as many planes as the free memory holds, each streamed once through the table (k_copy_count) from its packed assembly
+        (``seqset_for``; dropped again when this call loaded it), the batch's histograms taken in one pass over the targets
+        (k_copy_profile).  A target shorter than k, or without a valid window, is reported with zeros.  Targets stay in order;
+        duplicate names are kept.  KeyError: an unknown genome name; ValueError: a genome without an assembly FASTA (a FASTQ
+        sample, or no sequence file), k outside 1..32."""
+        from . import copies as cp, search as srch
+        names = list(self.genome_names)
+        cols = srch.pick_genomes(names, genomes)
+        k = int(self.k) if k is None else int(k)
+        if not 1 <= k <= 32:
+            raise ValueError(f"copies: k={k} (1 to 32)")
+        chosen = [names[c] for c in cols]
+        for g in chosen:
+            fa = self.genomes[g].fasta
+            if fa is None or pd.isna(fa) or is_fastq(fa):
+                raise ValueError(f"copies: genome {g!r} has no assembly FASTA to count k-mers in ({fa})")
+        text, tnames, tlens, offs = srch.read_queries(targets)
+        nt, ng = len(tnames), len(chosen)
+        total = int(np.maximum(tlens - k + 1, 0).sum())
+        hist, valid = np.zeros((nt, ng, cp.BINS), np.uint64), np.zeros(nt, np.uint64)
+        depths = np.full((ng, total), cp.DEPTH_INVALID, np.uint16) if track else None
+        if total and ng:
+            at = np.flatnonzero(tlens >= k)  # (a target shorter than k has no position: it stays on the host)
+            tss = engine.SeqSet.from_fasta(self.context, text if len(at) == nt else np.concatenate([text[offs[t]:offs[t + 1]] for t in at]))
+            table = None
+            try:
+                if list(tss.names) != [tnames[t] for t in at] or not np.array_equal(np.asarray(tss.lens, np.int64), tlens[at]):
+                    raise RuntimeError("copies: the targets were read differently on the host and on the GPU")
+                slots = 2
+                while slots < 2 * total:
+                    slots *= 2
+                per = cp.planes_for(self.context.mem_info()[0], slots, ng, total if track else 0)
+                table = engine.CopyTable(self.context, k, total, per)
+                table.insert(tss)
+                for g0 in range(0, ng, per):
+                    batch = chosen[g0:g0 + per]
+                    for plane, g in enumerate(batch):
+                        if g0:
+                            table.clear(plane)
+                        mine = g not in self._seqsets
+                        try:
+                            table.count(plane, self.seqset_for(g))
+                        finally:
+                            if mine:
+                                self.drop_seqset(g)
+                    got = table.profile(tss, 0, len(batch), track)
+                    hist[at, g0:g0 + len(batch)], valid[at] = got[0], got[1]
+                    if track:
+                        depths[g0:g0 + len(batch)] = got[2]
+            finally:
+                if table is not None:
+                    table.close()
+                tss.close()
+        out = cp.frames(tnames, tlens, k, chosen, hist, valid)
+        return (*out, depths) if track else out
+
     def _synteny_sides(self, a, b, chroms_a, chroms_b, k, run):
         """``run(k, seqs_a, seqs_b)`` on the two genomes' sequence sets, narrowed to the chosen chromosomes: (its result, k, per
         side (names, lengths) of the chromosomes taken)"""
@@ -1575,6 +1639,37 @@ class Genome:
                          usecols=["chr", "type", "start", "end"], dtype={"chr": str})
         df = df[df["type"].isin(self.index.gff_gene_types)]
         return df.sort_values(["chr", "start"], kind="stable").reset_index(drop=True)
+
+    def gene_copies(self, genomes=None, k=None, track: bool = False):
+        """``Index.copies`` with this annotated anchor's genes as the targets: ``load_genes`` gives chromosome, start and end —
+        bases [start, end) as they stand in the GFF, cut at the chromosome's end — and a gene is named ``chr:start-end``.  The
+        genes are cut from the anchor's packed sequence set on the GPU (``SeqSet.slice``, whose pieces start at multiples of 32:
+        the up to 31 bases in front are trimmed on the host).  A gene on a chromosome the FASTA lacks, or with end <= start, is an
+        empty target: it stays in the tables with zeros.  ValueError: no GFF."""
+        from . import copies as cp
+        if not self.annotated:
+            raise ValueError(f"copies: genome {self.name!r} has no GFF to take genes from")
+        genes = self.load_genes()
+        idx = self.index
+        mine = self.name not in idx._seqsets
+        ss = idx.seqset_for(self.name)
+        try:
+            contig = {n: i for i, n in reversed(list(enumerate(ss.names)))}
+            spans = [(contig[c], max(0, int(s)), min(int(e), int(ss.lens[contig[c]]))) if c in contig else (0, 0, 0)
+                     for c, s, e in zip(genes["chr"], genes["start"], genes["end"])]  # (a chromosome the FASTA lacks: an empty target)
+            seqs = [b""] * len(spans)
+            cut = [i for i, (_, s, e) in enumerate(spans) if e > s]
+            if cut:
+                pieces = ss.slice([(spans[i][0], spans[i][1] & ~31, spans[i][2] - (spans[i][1] & ~31)) for i in cut])
+                try:
+                    for j, i in enumerate(cut):
+                        seqs[i] = pieces.unpack(j)[spans[i][1] & 31:]
+                finally:
+                    pieces.close()
+        finally:
+            if mine:
+                idx.drop_seqset(self.name)
+        return idx.copies(list(zip(cp.gene_names(genes), seqs)), genomes, k, track)
 
     @property
     def bins_fname(self):

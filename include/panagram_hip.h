@@ -659,6 +659,51 @@ int pg_synteny_variants(pg_ctx *ctx, int k, const pg_seqset *seqsA, const pg_seq
 /* the HIP-event times of this host thread's last pg_synteny_variants: ms_out[9] = the seven of pg_synteny_blocks_last_timing (the
  * blocks' emit pass does not run: 0), then k_link_variants counting and k_link_variants emitting. */
 int pg_synteny_variants_last_timing(float *ms_out);
+/* locate: WHERE in a genome do query sequences lie — chromosome, range, strand, every copy?  The mates above demand a k-mer that
+ * occurs once on BOTH sides and cost a word per position of the streamed side; these calls demand it of the queries alone, stream
+ * a genome of any size through the table and write only runs.  They work on a position table whose side 1 holds the queries Q
+ * (pg_postable_insert_seqset(pt, 1, Q); side 0 stays empty and is ignored) and on these definitions:
+ *   hit word  of k-mer position p of contig c of a streamed sequence set G: defined when the window is valid and the side-1 field w
+ *             of its canonical key is a position — the key occurs exactly once in Q.  Then h = w xor rcG = posQ << 1 | (rcG xor
+ *             rcQ), posQ global in Q's contigs laid end to end; 0xFFFFFFFF otherwise.  Nothing is required of the key's
+ *             multiplicity in G: a key once in Q and three times in G gives three hits.
+ *   hit run   the run of the synteny section with hit words in place of mates: a maximal [a, b) of consecutive k-mer positions of
+ *             ONE contig of G, each continuing its predecessor by + 2 (even words) or - 2 (odd words).  Contig edges of G cut runs.
+ *             For k >= 2 a run cannot span two queries: the global Q positions of neighbouring contigs' k-mers differ by at least k.
+ * Positions of G are contig-relative everywhere: the streamed side has no limit on its total, only a single contig is limited, to
+ * 2^32 - 1 k-mer positions.  Q keeps the limit of a side, 2^31 - 1 bases.
+ * Two limits follow from the definitions.  K-mers that repeat among the queries (overlapping genes, family members given as
+ * separate queries) count for nothing: pg_postable_hit_runs on Q itself says how many of a query's k-mers are left.  A query k-mer
+ * that is a repeat in the genome yields many short runs there, and so many short blocks.
+ * pg_postable_hit_runs: the hit runs of seqsG under the capacity protocol of pg_mate_runs — nruns_per_contig[c], *total (the runs)
+ * and *nhits (the positions with a hit = the sum of the runs' lengths) are always filled, and hits_per_contig[c] = the positions of
+ * contig c with a hit when it is not NULL; nothing is written to the four run arrays when cap == 0 (they may then be NULL) or
+ * *total > cap; otherwise their first *total entries are the runs — contig, first position, exclusive end, hit word of the first
+ * position — sorted by (contig, start), the same on every call.  Called with seqsG = Q itself it counts the queries' unique k-mers
+ * per query.  It may be called any number of times on one table, with any sequence sets of the table's context.
+ * pg_postable_locate: the hit runs kept in HBM, then blocks exactly as pg_run_blocks defines them with A = G and B = Q (the link rule,
+ * the same-contig-of-B condition, min_run, max_gap and max_shift unchanged; mate_first / mate_last are hit words): only the blocks
+ * leave the GPU.  seqsQ must be the set inserted as side 1 — the table remembers that side's base count and contig count.  Blocks
+ * and capacity as pg_run_blocks over the contigs of seqsG; *nhits as above, *nruns = all runs (kept or not).
+ * PG_E_INVALID, before anything is launched: a NULL argument, side 1 not inserted, a sequence set of another context, a contig of
+ * seqsG of more than 2^32 - 1 k-mer positions, more than 2^31 - 1 chunks of 4096 positions; for pg_postable_locate also a seqsQ
+ * that differs from side 1 in bases or contigs and the three parameters as pg_run_blocks.  PG_E_CAPACITY, before anything is
+ * launched: the table overflowed.  (One answer cannot come before the count: pg_postable_locate on more than 2^31 - 1 runs is
+ * PG_E_CAPACITY.)
+ * Two launches of k_hit_runs (count, then emit; one when nothing is emitted) over chunks of 4096 positions — both probe the table,
+ * which is only read — then pg_postable_locate's two of k_run_blocks; no atomics; synchronises. */
+int pg_postable_hit_runs(pg_postable *pt, const pg_seqset *seqsG, uint64_t cap,
+                         uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end, uint32_t *run_hit,
+                         uint64_t *nruns_per_contig, uint64_t *hits_per_contig, uint64_t *total, uint64_t *nhits);
+int pg_postable_locate(pg_postable *pt, const pg_seqset *seqsG, const pg_seqset *seqsQ, uint32_t min_run, uint32_t max_gap,
+                       uint32_t max_shift, uint64_t cap,
+                       uint32_t *blk_contig, uint32_t *blk_start, uint32_t *blk_end, uint32_t *blk_hit_first, uint32_t *blk_hit_last,
+                       uint32_t *blk_kmers, uint32_t *blk_runs, uint32_t *blk_shifted, uint64_t *nblocks_per_contig, uint64_t *total,
+                       uint64_t *nhits, uint64_t *nruns);
+/* the HIP-event times of this host thread's last pg_postable_locate: ms_out[4] = k_hit_runs counting, k_hit_runs emitting,
+ * k_run_blocks counting, k_run_blocks emitting (0 where a kernel did not run; after pg_postable_hit_runs the first two) — what
+ * tools/locate_rate.py reports. */
+int pg_locate_last_timing(float *ms_out);
 /* copies: HOW OFTEN does a genome hold the k-mer at a position of a target sequence?  Every answer above is about presence (one bit
  * per genome and k-mer) or about k-mers that occur once (the position table); nothing in the reference counts the occurrences of a
  * k-mer along a sequence (scripts/pairwise_comp.py stops at column sums of presence bits).  These calls work on sequence sets —

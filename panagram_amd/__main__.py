@@ -27,7 +27,11 @@ against the table of every sample's k-mers and their rows reduced per query and 
 `copies <index_dir> [targets.fa] [--genes GENOME] [--genomes A,B] [-k K] [--matrix FILE] [--summary FILE] [--track FILE]` says how MANY
 copies of each target sequence — the records of a FASTA, or the annotated genes of a genome — the genomes' assemblies hold: the
 targets' k-mers go into a count table, every genome is streamed through it, and the depths along each target are reduced to a
-histogram and its median on the GPU."""
+histogram and its median on the GPU; and
+`locate <index_dir> [queries.fa] [--genes GENOME] [--genomes A,B] [-k K] [--min-run N] [--max-gap G] [--max-shift S] [--min-kmers N]
+[--min-frac F] [--paf] [--matrix FILE] [--summary FILE]` says WHERE each query lies in every genome — chromosome, start, end, strand,
+every copy: the queries' k-mers go into a position table, every genome's assembly is streamed through it, and the collinear runs of
+its hits are chained into loci on the GPU; only the loci leave it."""
 import argparse
 import os
 import sys
@@ -191,6 +195,24 @@ def main(argv=None):
     cp.add_argument("--track", metavar="FILE", default=None, help="also write the runs of equal depth along every target: target genome start end depth")
     cp.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     cp.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    lo = sub.add_parser("locate", help="where each query sequence lies in every genome's assembly, every copy: the genomes streamed through "
+                                       "a position table of the queries' k-mers, the runs of hits chained into loci on the GPU: tab-separated, "
+                                       "with a header, query genome chrom start end strand qstart qend kmers frac runs shifted")
+    lo.add_argument("index_dir")
+    lo.add_argument("queries", metavar="queries.fa", nargs="?", default=None, help="FASTA, plain or .gz (or --genes)")
+    lo.add_argument("--genes", metavar="GENOME", default=None, help="the queries are the annotated genes of this genome (in place of queries.fa)")
+    lo.add_argument("--genomes", default="", metavar="A,B", help="the genomes to look in (default: all of them)")
+    lo.add_argument("-k", type=int, default=None, help="k-mer length, 1 to 32 (default: the index's)")
+    lo.add_argument("--min-run", type=int, default=1, metavar="N", help="drop runs of fewer than N k-mers before chaining (default 1)")
+    lo.add_argument("--max-gap", type=int, default=1000, metavar="G", help="a locus bridges at most G positions on genome and query (default 1000)")
+    lo.add_argument("--max-shift", type=int, default=100, metavar="S", help="... whose two distances differ by at most S (default 100)")
+    lo.add_argument("--min-kmers", type=int, default=1, metavar="N", help="drop loci of fewer than N matched k-mers (default 1)")
+    lo.add_argument("--min-frac", type=float, default=0.0, metavar="F", help="drop loci that hold less than F of the query's unique k-mers")
+    lo.add_argument("--paf", action="store_true", help="write PAF lines (query = the query, target = the chromosome; tags rn, sh, gn) in place of the table")
+    lo.add_argument("--matrix", metavar="FILE", default=None, help="also write the queries x genomes table of loci")
+    lo.add_argument("--summary", metavar="FILE", default=None, help="also write one line per query: query length kmers unique loci genomes_hit best_genome best_frac")
+    lo.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    lo.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -397,6 +419,53 @@ def main(argv=None):
                 f.writelines(line + "\n" for line in copies.track_lines(list(matrix.index), out["length"].to_numpy()[::ng], idx.k if a.k is None else a.k,
                                                                         list(matrix.columns), got[3]))
         copies.long_text(out).to_csv(a.output if a.output else sys.stdout, sep="\t", index=False)
+        return 0
+    if a.cmd == "locate":
+        if (a.queries is None) == (a.genes is None):
+            ap.error("locate: give exactly one of queries.fa and --genes GENOME")
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"locate: {a.index_dir!r} is not an index directory")
+        if a.queries is not None and not os.path.isfile(a.queries):
+            ap.error(f"locate: no query file {a.queries!r}")
+        if a.k is not None and not 1 <= a.k <= 32:
+            ap.error(f"locate: k={a.k} (1 to 32)")
+        if a.min_kmers < 1:
+            ap.error("locate: --min-kmers must be at least 1")
+        if not 0.0 <= a.min_frac <= 1.0:
+            ap.error("locate: --min-frac is a fraction, 0 to 1")
+        from .index import Index
+        from . import locate
+        chosen = [g for g in a.genomes.split(",") if g]
+        try:
+            idx = Index(a.index_dir, mode="r", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"locate: {e}")
+        try:
+            if a.genes is not None and a.genes not in idx.genomes:
+                ap.error(f"locate: unknown genome {a.genes!r} (the index has {', '.join(idx.genome_names)})")
+            params = (a.k, a.min_run, a.max_gap, a.max_shift, a.min_kmers, a.min_frac)
+            try:
+                if a.genes is not None:
+                    loci, matrix, summary = idx[a.genes].gene_loci(chosen or None, *params)
+                else:
+                    loci, matrix, summary = idx.locate(a.queries, chosen or None, *params)
+            except (ValueError, KeyError) as e:
+                ap.error(f"locate: {e}")
+        finally:
+            idx.close()
+        if a.matrix:
+            matrix.to_csv(a.matrix, sep="\t", index_label="query")
+        if a.summary:
+            summary.to_csv(a.summary, sep="\t", index=False)
+        if a.paf:
+            text = "".join(line + "\n" for line in locate.paf_lines(loci, loci.attrs["chrom_lens"]))
+            if a.output:
+                with open(a.output, "w") as f:
+                    f.write(text)
+            else:
+                sys.stdout.write(text)
+        else:
+            loci.to_csv(a.output if a.output else sys.stdout, sep="\t", index=False)
         return 0
     if a.cmd == "synteny":
         if a.min_len < 1:

@@ -146,6 +146,10 @@ PROTOTYPES = {
     "pg_synteny_variants": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p]),
     "pg_synteny_variants_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
+    "pg_postable_hit_runs": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _u64p, _u64p]),
+    "pg_postable_locate": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _u64p, _u64p, _u64p]),
+    "pg_locate_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
     "pg_copytable_create": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint32, _vpp]),
     "pg_copytable_destroy": (C.c_int, [_vp]),
     "pg_copytable_insert_seqset": (C.c_int, [_vp, _vp, _u64p]),

@@ -1,6 +1,6 @@
 // pg_api_synteny.hip — host side of the C-ABI: the position table of two genomes, the mates of A's positions and their collinear
-// runs (pg_synteny.hip), the runs chained into blocks (pg_blocks.hip, pg_blocks_host.h), and the blocks' links as variants of B
-// against A (pg_variants.hip).
+// runs (pg_synteny.hip), the runs chained into blocks (pg_blocks.hip, pg_blocks_host.h), the blocks' links as variants of B
+// against A (pg_variants.hip), and the hit runs and loci of queries in a streamed genome (pg_locate.hip).
 #include "pg_host.h"
 
 #include "pg_blocks_host.h"
@@ -18,6 +18,8 @@ struct pg_postable {
     uint32_t *d_mates = nullptr;  // of the last pg_postable_mates: kept in HBM for the runs
     uint64_t nmates = 0;
     bool inserted[2] = {false, false};
+    uint64_t side_bases[2] = {0, 0};  // of the sequence set inserted as each side, and its contigs: pg_postable_locate's seqsQ is
+    uint32_t side_contigs[2] = {0, 0};  // held against them
     bool overflowed = false;  // an insert gave up: the table holds a part of a side and answers nothing any more
 };
 
@@ -25,6 +27,7 @@ namespace {
 
 thread_local float g_last_ms[5] = {0, 0, 0, 0, 0};  // insert A, insert B, mates, runs (count), runs (emit) of the last pg_synteny_segments
 thread_local float g_blocks_ms[7] = {0, 0, 0, 0, 0, 0, 0};  // those five, blocks (count), blocks (emit) of the last pg_synteny_blocks
+thread_local float g_locate_ms[4] = {0, 0, 0, 0};  // k_hit_runs (count), (emit), k_run_blocks (count), (emit) of the last hit call
 thread_local float g_variants_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // those seven, variants (count), variants (emit) of the last pg_synteny_variants
 
 // the (contig, chunk) jobs of a seqset's k-mer positions, the base offset of every contig in the concatenation and its first
@@ -101,6 +104,8 @@ int postable_insert(pg_postable *pt, int side, const pg_seqset *sq, float *ms = 
     if (int r = walk_side(sq, pt->k, "pg_postable_insert_seqset", w)) return r;
     if (int r = use_device(pt->ctx)) return r;
     pt->inserted[side] = true;
+    pt->side_bases[side] = w.bases;
+    pt->side_contigs[side] = sq->n;
     if (w.jobs.empty()) return PG_OK;
     hipStream_t st = pt->ctx->stream;
     DevBuf<uint2> d_jobs;
@@ -182,13 +187,72 @@ struct RunsOut {
     DevBuf<uint32_t> *keep = nullptr;
 };
 
+// the two passes of a run kernel over its chunks (k_mate_runs, k_hit_runs): count, the host's exclusive scans of the chunks' run starts
+// and run ends, emit.  launch(counts, offs, total, run_start, run_end, run_word) enqueues one pass — offs NULL: the count pass —
+// over nchunks chunks, the chunks of contig c being first[c] .. first[c + 1].  nruns[c], marked[c] (the contig's marked positions,
+// when given), *total_out and *nmarked always; the runs under `out`; ms[0] the count launch, ms[1] the emit launch
+template <class Launch>
+int runs_two_pass(pg_ctx *ctx, const char *fn, uint32_t ncontigs, const std::vector<uint64_t> &first, uint32_t nchunks, Launch launch,
+                  const RunsOut &out, uint64_t *nruns, uint64_t *marked, uint64_t *total_out, uint64_t *nmarked, float *ms) {
+    hipStream_t st = ctx->stream;
+    DevBuf<uint4> d_counts;
+    std::vector<uint4> counts(nchunks);
+    LaunchTimer tc(ms), te(ms ? ms + 1 : nullptr);
+    hipError_t e = d_counts.alloc(nchunks);
+    if (e == hipSuccess) e = tc.start(st);
+    if (e == hipSuccess) e = launch(d_counts.get(), nullptr, 0, nullptr, nullptr, nullptr);
+    if (e == hipSuccess) e = tc.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    tc.read();
+    // per contig: the sums; per chunk: the starts and the ends of all chunks before it
+    std::vector<ulonglong2> offs(nchunks);
+    uint64_t nstarts = 0, nends = 0, nm = 0;
+    for (uint32_t c = 0; c < ncontigs; ++c) {
+        const uint64_t s0 = nstarts, m0 = nm;
+        for (uint64_t i = first[c]; i < first[c + 1]; ++i) {
+            offs[i] = make_ulonglong2(nstarts, nends);
+            nm += counts[i].x;
+            nstarts += counts[i].y;
+            nends += counts[i].z;
+        }
+        nruns[c] = nstarts - s0;
+        if (marked) marked[c] = nm - m0;
+        if (nstarts != nends)  // (every run of a contig starts and ends inside it)
+            return fail(PG_E_HIP, "%s: contig %u: %llu run starts, %llu run ends", fn, c, (unsigned long long)nstarts, (unsigned long long)nends);
+    }
+    const uint64_t total = nstarts;
+    *total_out = total;
+    if (nmarked) *nmarked = nm;
+    if (total == 0 || (!out.keep && (out.cap == 0 || total > out.cap))) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
+    DevBuf<ulonglong2> d_offs;
+    DevBuf<uint32_t> d_runs;
+    e = d_offs.upload(offs, st);
+    if (e == hipSuccess) e = d_runs.alloc((size_t)3 * total);
+    if (e == hipSuccess) e = te.start(st);
+    if (e == hipSuccess) e = launch(nullptr, d_offs.get(), total, d_runs.get(), d_runs.get() + total, d_runs.get() + 2 * total);
+    if (e == hipSuccess) e = te.stop(st);
+    if (e == hipSuccess && !out.keep) e = hipMemcpyAsync(out.start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !out.keep) e = hipMemcpyAsync(out.end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !out.keep) e = hipMemcpyAsync(out.mate, d_runs.get() + 2 * total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    te.read();
+    if (out.keep) {
+        std::swap(out.keep->p, d_runs.p);
+        return PG_OK;
+    }
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < ncontigs; ++c)
+        for (uint64_t i = 0; i < nruns[c]; ++i) out.contig[at++] = c;
+    return PG_OK;
+}
+
 // the runs of a mates array in HBM (ncontigs contigs of nkmers[c] entries, back to back); nruns[c] and *total_out always,
 // *mated: the mated positions counted
 int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t ncontigs, const uint64_t *nkmers, const RunsOut &out,
                   uint64_t *nruns, uint64_t *total_out, uint64_t *mated, float *ms = nullptr) {
-    DevBuf<uint32_t> *const keep = out.keep;
-    const uint64_t cap = out.cap;
-    uint32_t *const run_contig = out.contig, *const run_start = out.start, *const run_end = out.end, *const run_mate = out.mate;
     std::vector<uint2> contigs(ncontigs), chunks;
     std::vector<uint64_t> first(ncontigs + 1, 0);
     uint64_t tot = 0;
@@ -209,62 +273,16 @@ int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t
     if (int r = use_device(ctx)) return r;
     hipStream_t st = ctx->stream;
     DevBuf<uint2> d_contigs, d_chunks;
-    DevBuf<uint4> d_counts;
-    std::vector<uint4> counts(nchunks);
-    LaunchTimer tc(ms), te(ms ? ms + 1 : nullptr);
     hipError_t e = d_contigs.upload(contigs, st);
     if (e == hipSuccess) e = d_chunks.upload(chunks, st);
-    if (e == hipSuccess) e = d_counts.alloc(nchunks);
-    if (e == hipSuccess) e = tc.start(st);
-    if (e == hipSuccess)
-        e = launch_mate_runs(st, d_mates, d_contigs.get(), d_chunks.get(), nchunks, d_counts.get(), nullptr, 0, nullptr, nullptr, nullptr);
-    if (e == hipSuccess) e = tc.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    tc.read();
-    // per contig: the sums; per chunk: the starts and the ends of all chunks before it
-    std::vector<ulonglong2> offs(nchunks);
-    uint64_t nstarts = 0, nends = 0, nm = 0;
-    for (uint32_t c = 0; c < ncontigs; ++c) {
-        const uint64_t s0 = nstarts;
-        for (uint64_t i = first[c]; i < first[c + 1]; ++i) {
-            offs[i] = make_ulonglong2(nstarts, nends);
-            nm += counts[i].x;
-            nstarts += counts[i].y;
-            nends += counts[i].z;
-        }
-        nruns[c] = nstarts - s0;
-        if (nstarts != nends)  // (every run of a contig starts and ends inside it)
-            return fail(PG_E_HIP, "%s: contig %u: %llu run starts, %llu run ends", fn, c, (unsigned long long)nstarts, (unsigned long long)nends);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);  // (the uploads' sources go with this scope)
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     }
-    const uint64_t total = nstarts;
-    *total_out = total;
-    if (mated) *mated = nm;
-    if (total == 0 || (!keep && (cap == 0 || total > cap))) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
-    DevBuf<ulonglong2> d_offs;
-    DevBuf<uint32_t> d_runs;
-    e = d_offs.upload(offs, st);
-    if (e == hipSuccess) e = d_runs.alloc((size_t)3 * total);
-    if (e == hipSuccess) e = te.start(st);
-    if (e == hipSuccess)
-        e = launch_mate_runs(st, d_mates, d_contigs.get(), d_chunks.get(), nchunks, nullptr, d_offs.get(), total, d_runs.get(),
-                             d_runs.get() + total, d_runs.get() + 2 * total);
-    if (e == hipSuccess) e = te.stop(st);
-    if (e == hipSuccess && !keep) e = hipMemcpyAsync(run_start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && !keep) e = hipMemcpyAsync(run_end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && !keep) e = hipMemcpyAsync(run_mate, d_runs.get() + 2 * total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    te.read();
-    if (keep) {
-        std::swap(keep->p, d_runs.p);
-        return PG_OK;
-    }
-    uint64_t at = 0;
-    for (uint32_t c = 0; c < ncontigs; ++c)
-        for (uint64_t i = 0; i < nruns[c]; ++i) run_contig[at++] = c;
-    return PG_OK;
+    const auto launch = [&](uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *rs, uint32_t *re, uint32_t *rm) {
+        return launch_mate_runs(st, d_mates, d_contigs.get(), d_chunks.get(), nchunks, counts, offs, total, rs, re, rm);
+    };
+    return runs_two_pass(ctx, fn, ncontigs, first, nchunks, launch, out, nruns, nullptr, total_out, mated, ms);
 }
 
 bool runs_args_ok(uint32_t ncontigs, uint64_t cap, const uint32_t *run_contig, const uint32_t *run_start, const uint32_t *run_end,
@@ -528,6 +546,63 @@ int runs_ok(const char *fn, const uint32_t *run_contig, const uint32_t *run_star
         per[c] += 1;
     }
     return PG_OK;
+}
+
+static constexpr uint64_t HIT_MAX_CONTIG = 0xFFFFFFFFull;  // k-mer positions of one streamed contig: a run's exclusive end is a word
+static constexpr uint64_t HIT_MAX_CHUNKS = 0x7FFFFFFFull;  // one block per chunk
+
+// what both hit calls check before anything is launched, and the chunks of the streamed set's k-mer positions
+struct HitWalk {
+    std::vector<uint2> chunks;
+    std::vector<uint64_t> first;  // [n + 1]: the first chunk of every contig
+};
+
+int hit_walk(const pg_postable *pt, const pg_seqset *sq, const char *fn, HitWalk &w) {
+    if (pt->ctx != sq->ctx) return fail(PG_E_INVALID, "%s: table and seqset belong to different contexts", fn);
+    if (pt->overflowed) return fail(PG_E_CAPACITY, "%s: the table overflowed", fn);
+    if (!pt->inserted[1]) return fail(PG_E_INVALID, "%s: side 1 (the queries) has not been inserted", fn);
+    w.first.assign((size_t)sq->n + 1, 0);
+    uint64_t nchunks = 0;
+    for (uint32_t c = 0; c < sq->n; ++c) {
+        const uint64_t len = sq->desc[c].len, nk = len >= (uint64_t)pt->k ? len - pt->k + 1 : 0;
+        if (nk > HIT_MAX_CONTIG) return fail(PG_E_INVALID, "%s: contig %u holds more than 2^32 - 1 k-mer positions", fn, c);
+        nchunks += (nk + LOCATE_CHUNK - 1) / LOCATE_CHUNK;
+    }
+    if (nchunks > HIT_MAX_CHUNKS) return fail(PG_E_INVALID, "%s: more than 2^31 - 1 chunks of %u positions", fn, LOCATE_CHUNK);
+    w.chunks.reserve(nchunks);
+    for (uint32_t c = 0; c < sq->n; ++c) {
+        const uint64_t len = sq->desc[c].len, nk = len >= (uint64_t)pt->k ? len - pt->k + 1 : 0;
+        w.first[c] = w.chunks.size();
+        for (uint64_t p = 0; p < nk; p += LOCATE_CHUNK) w.chunks.push_back(make_uint2(c, (uint32_t)p));
+    }
+    w.first[sq->n] = w.chunks.size();
+    return PG_OK;
+}
+
+// the hit runs of sq streamed through pt (k_hit_runs): nruns[c], hits[c] (when given), *total_out and *nhits always, the runs as
+// mate_runs_dev leaves them; ms[0] the count launch, ms[1] the emit launch
+int hit_runs_dev(pg_postable *pt, const char *fn, const pg_seqset *sq, const HitWalk &w, const RunsOut &out, uint64_t *nruns,
+                 uint64_t *hits, uint64_t *total_out, uint64_t *nhits, float *ms = nullptr) {
+    for (uint32_t c = 0; c < sq->n; ++c) {
+        nruns[c] = 0;
+        if (hits) hits[c] = 0;
+    }
+    *total_out = *nhits = 0;
+    if (w.chunks.empty()) return PG_OK;
+    const uint32_t nchunks = (uint32_t)w.chunks.size();
+    if (int r = use_device(pt->ctx)) return r;
+    hipStream_t st = pt->ctx->stream;
+    DevBuf<uint2> d_chunks;
+    const hipError_t e = d_chunks.upload(w.chunks, st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);  // (the upload's source is the caller's)
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    const auto launch = [&](uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *rs, uint32_t *re, uint32_t *rh) {
+        return launch_hit_runs(st, pt->k, sq->d_desc, d_chunks.get(), nchunks, sq->d_seqw, sq->d_nmw, sq->d_has_n, pt->d_slots, pt->nslots,
+                               pt->max_probe, counts, offs, total, rs, re, rh);
+    };
+    return runs_two_pass(pt->ctx, fn, sq->n, w.first, nchunks, launch, out, nruns, hits, total_out, nhits, ms);
 }
 
 }  // namespace
@@ -821,6 +896,64 @@ extern "C" int pg_synteny_variants_last_timing(float *ms_out) {
     PG_API_BEGIN
     if (!ms_out) return fail(PG_E_INVALID, "pg_synteny_variants_last_timing: NULL argument");
     std::copy(g_variants_ms, g_variants_ms + 9, ms_out);
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_postable_hit_runs(pg_postable *pt, const pg_seqset *seqsG, uint64_t cap, uint32_t *run_contig, uint32_t *run_start,
+                                    uint32_t *run_end, uint32_t *run_hit, uint64_t *nruns_per_contig, uint64_t *hits_per_contig,
+                                    uint64_t *total, uint64_t *nhits) {
+    PG_API_BEGIN
+    if (!pt || !seqsG || !nhits || !runs_args_ok(seqsG->n, cap, run_contig, run_start, run_end, run_hit, nruns_per_contig, total))
+        return fail(PG_E_INVALID, "pg_postable_hit_runs: NULL argument");
+    HitWalk w;
+    if (int r = hit_walk(pt, seqsG, "pg_postable_hit_runs", w)) return r;
+    std::fill(g_locate_ms, g_locate_ms + 4, 0.0f);
+    const RunsOut out{cap, run_contig, run_start, run_end, run_hit, nullptr};
+    return hit_runs_dev(pt, "pg_postable_hit_runs", seqsG, w, out, nruns_per_contig, hits_per_contig, total, nhits, g_locate_ms);
+    PG_API_END
+}
+
+extern "C" int pg_postable_locate(pg_postable *pt, const pg_seqset *seqsG, const pg_seqset *seqsQ, uint32_t min_run, uint32_t max_gap,
+                                  uint32_t max_shift, uint64_t cap, uint32_t *blk_contig, uint32_t *blk_start, uint32_t *blk_end,
+                                  uint32_t *blk_hit_first, uint32_t *blk_hit_last, uint32_t *blk_kmers, uint32_t *blk_runs,
+                                  uint32_t *blk_shifted, uint64_t *nblocks_per_contig, uint64_t *total, uint64_t *nhits, uint64_t *nruns) {
+    PG_API_BEGIN
+    const BlockArrays out{blk_contig, blk_start, blk_end, blk_hit_first, blk_hit_last, blk_kmers, blk_runs, blk_shifted};
+    if (!pt || !seqsG || !seqsQ || !total || !nhits || !nruns || (seqsG->n && !nblocks_per_contig) || (cap && !out.all()))
+        return fail(PG_E_INVALID, "pg_postable_locate: NULL argument");
+    const BlockParams p{min_run, max_gap, max_shift};
+    if (int r = block_params_ok("pg_postable_locate", p)) return r;
+    if (seqsQ->ctx != pt->ctx) return fail(PG_E_INVALID, "pg_postable_locate: table and queries belong to different contexts");
+    HitWalk w;
+    if (int r = hit_walk(pt, seqsG, "pg_postable_locate", w)) return r;
+    // the queries: the set inserted as side 1, whose contigs' offsets the same-contig condition needs
+    std::vector<uint64_t> lensQ(seqsQ->n), boff, per(seqsG->n, 0);
+    uint64_t basesQ = 0;
+    for (uint32_t c = 0; c < seqsQ->n; ++c) basesQ += (lensQ[c] = seqsQ->desc[c].len);
+    if (seqsQ->n != pt->side_contigs[1] || basesQ != pt->side_bases[1])
+        return fail(PG_E_INVALID, "pg_postable_locate: seqsQ (%u contigs, %llu bases) is not the set inserted as side 1 (%u, %llu)", seqsQ->n,
+                    (unsigned long long)basesQ, pt->side_contigs[1], (unsigned long long)pt->side_bases[1]);
+    contig_offsets(seqsQ->n, lensQ.data(), boff);  // (a side of at most 2^31 - 1 bases: checked when it was inserted)
+    *total = *nhits = *nruns = 0;
+    for (uint32_t c = 0; c < seqsG->n; ++c) nblocks_per_contig[c] = 0;
+    std::fill(g_locate_ms, g_locate_ms + 4, 0.0f);
+    DevBuf<uint32_t> d_runs;  // the runs: emitted into HBM and read there
+    RunsOut runs_out;
+    runs_out.keep = &d_runs;
+    if (int r = hit_runs_dev(pt, "pg_postable_locate", seqsG, w, runs_out, per.data(), nullptr, nruns, nhits, g_locate_ms)) return r;
+    if (*nruns == 0) return PG_OK;
+    if (*nruns > POS_MAX_BASES)  // (the run kernels number a contig's runs in 32 bits; known only once they are counted)
+        return fail(PG_E_CAPACITY, "pg_postable_locate: more than %llu runs (stream fewer contigs at a time)", (unsigned long long)POS_MAX_BASES);
+    return run_blocks_dev(pt->ctx, "pg_postable_locate", d_runs.get(), *nruns, seqsG->n, per.data(), boff, p, cap, out, nblocks_per_contig,
+                          total, g_locate_ms + 2);
+    PG_API_END
+}
+
+extern "C" int pg_locate_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_locate_last_timing: NULL argument");
+    std::copy(g_locate_ms, g_locate_ms + 4, ms_out);
     return PG_OK;
     PG_API_END
 }

@@ -301,6 +301,16 @@ constexpr uint32_t MATE_CHUNK = 4096;  // positions per chunk, a multiple of 256
 hipError_t launch_mate_runs(hipStream_t st, const uint32_t *mates, const uint2 *contigs, const uint2 *chunks, uint32_t nchunks,
                             uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *run_start, uint32_t *run_end,
                             uint32_t *run_mate);
+// runs of hits (pg_locate.hip; the definitions are there): the sequences sd / seqw / nmw / has_n streamed through a position table
+// whose side 1 holds the queries.  chunk = {contig, first position}: the LOCATE_CHUNK k-mer positions from there, cut at the
+// contig's end, a contig's chunks consecutive and in order; every contig named holds at least k bases and at most 2^32 - 1
+// k-mer positions.  counts, offs, total and the three run arrays as launch_mate_runs takes them (counts[c] = {hits, run starts,
+// run ends, 0}); positions are contig-relative.
+constexpr uint32_t LOCATE_CHUNK = 4096;  // positions per chunk, a multiple of 256
+hipError_t launch_hit_runs(hipStream_t st, int k, const SeqDesc *sd, const uint2 *chunks, uint32_t nchunks, const uint64_t *seqw,
+                           const uint32_t *nmw, const uint32_t *has_n, const void *slots, uint64_t nslots, uint32_t max_probe,
+                           uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *run_start, uint32_t *run_end,
+                           uint32_t *run_hit);
 // blocks of runs (pg_blocks.hip; the definitions are there): run_start / run_end / run_mate as launch_mate_runs emits them,
 // contigs[c] = {first run of contig c of A, its runs}, chunk = {contig, first run inside it}: the RUN_CHUNK runs from there, a
 // contig's chunks consecutive and in order.  boff: the nb ascending offsets of B's contigs (for the same-contig condition).

@@ -1,0 +1,159 @@
+// pg_locate.hip — WHERE in a genome G do query sequences Q lie (gfx950)?  pg_synteny.hip answers that for k-mers unique on both
+// sides and writes a mate word per position of the streamed side; here only Q must hold a k-mer once, G is streamed through the
+// table and nothing but the collinear runs of its hits is written: a genome of any size, every copy of a query.
+//
+// Definitions (tests/locate_ref.py is the same in numpy):
+//   table      a position table (pg_synteny.hip) whose side 1 holds the queries Q; side 0 is ignored.
+//   hit word   of k-mer position p of contig c of a streamed sequence set G: defined when the window is valid and the side-1
+//              field w of its canonical key is a position (neither POS_EMPTY nor POS_MULTI): h = w ^ rcG = posQ << 1 | (rcG ^ rcQ),
+//              posQ global in Q's contigs laid end to end.  NO_MATE otherwise.  Nothing is asked of the key's multiplicity in G.
+//   hit run    the run of pg_synteny.hip with hit words in place of mates: a maximal [a, b) of consecutive k-mer positions of
+//              ONE contig of G, each continuing its predecessor under mate_continues (pg_postable_dev.h).  Contig edges of G cut
+//              runs.  For k >= 2 a run lies inside one query: the global Q positions of two neighbouring contigs' k-mers differ
+//              by at least k.
+// Positions of G are contig-relative everywhere: G's total is unlimited, one contig holds at most 2^32 - 1 k-mer positions.
+//   k_hit_runs  the structure of k_mate_runs with the mate load replaced by the probe (the walk of k_pos_mates without its
+//               condition on side 0): chunks of LOCATE_CHUNK positions of one contig, tiles of 256, the predecessor's word from
+//               the lane below, the wave below (LDS), the tile before, and at a chunk's first position from ONE extra probe of
+//               position c0 - 1 — none at a contig's first.  With H = hit, P = predecessor hit, C = continues:
+//                 run starts  H & ~C        run ends (exclusive)  P & ~C, and one at the contig's end when its last is a hit
+//               count (EMIT = false): counts[chunk] = {hits, starts, ends, 0}; the host takes exclusive scans.
+//               emit: starts and ends are numbered separately (the i-th start and the i-th end of a contig are one run), so the
+//               output is sorted by (contig, start) by construction and the same on every call.
+// Both passes probe: the table is only read, so both see the same words.  A lane walks at most max_probe slots and then has no
+// hit (an insert that walked as far failed, and the host refuses such a table): no loop here is unbounded.  No atomics; every
+// write to HBM is a vector store.
+#include "pg_kernels.h"
+
+#include "pg_postable_dev.h"  // PosSlot, kmer_key_rc, mate_continues
+
+namespace pg {
+
+constexpr uint32_t LOCATE_TILE = 256;
+static_assert(LOCATE_CHUNK % LOCATE_TILE == 0, "a chunk is a whole number of tiles");
+
+// the hit word of position p of a contig (p below its k-mer positions)
+__device__ __forceinline__ uint32_t hit_word(int k, const uint64_t *seqw, const uint32_t *nmw, bool hasn, uint64_t p,
+                                             const PosSlot *__restrict__ slots, uint64_t smask, uint32_t max_probe) {
+    if (hasn && extract_nmask(nmw, p, k)) return NO_MATE;
+    uint64_t key;
+    const uint32_t rc = kmer_key_rc(seqw, p, k, key) ? 1u : 0u;
+    uint64_t s = sketch_hash(key) & smask;
+    for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
+        const unsigned long long cur = slots[s].key;
+        if (cur == EMPTY_KEY) break;
+        if (cur != key) continue;
+        const uint32_t w = slots[s].word[1];
+        return w != POS_EMPTY && w != POS_MULTI ? w ^ rc : NO_MATE;
+    }
+    return NO_MATE;
+}
+
+// chunk = {contig, first position}: a contig of at least k bases, 0 <= first position < its k-mer positions
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_hit_runs(int k, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ chunks,
+                                                  const uint64_t *seqw_all, const uint32_t *nmw_all, const uint32_t *has_n,
+                                                  const PosSlot *__restrict__ slots, uint64_t nslots, uint32_t max_probe,
+                                                  uint4 *__restrict__ counts, const ulonglong2 *__restrict__ offs, uint64_t total,
+                                                  uint32_t *__restrict__ run_start, uint32_t *__restrict__ run_end,
+                                                  uint32_t *__restrict__ run_hit) {
+    __shared__ uint32_t lasth[4];  // the hit word of every wave's last lane
+    __shared__ uint4 wcnt[4];      // {starts, ends, hits, 0} of every wave
+    __shared__ uint32_t tailh;     // the hit word of the chunk's last position
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint2 ck = chunks[blockIdx.x];
+    const SeqDesc d = sd[ck.x];
+    const uint64_t *seqw = seqw_all + d.seq_off;
+    const uint32_t *nmw = nmw_all + d.seq_off;
+    const bool hasn = has_n[ck.x] != 0;
+    const uint64_t smask = nslots - 1;
+    // this chunk: positions [c0, ce), 0 <= c0 < ce <= nk <= 2^32 - 1 (64-bit: c0 + LOCATE_CHUNK may pass 2^32)
+    const uint64_t nk = d.len - (uint64_t)k + 1, c0 = ck.y, ce = min(c0 + LOCATE_CHUNK, nk);
+    // the chunk's halo: the hit word of position c0 - 1 (every lane the same probe: broadcast loads)
+    uint32_t carry = c0 > 0 ? hit_word(k, seqw, nmw, hasn, c0 - 1, slots, smask, max_probe) : NO_MATE;
+    uint32_t nhits = 0, nstarts = 0, nends = 0;
+    uint64_t soff = 0, eoff = 0;
+    if (EMIT) {
+        const ulonglong2 o = offs[blockIdx.x];
+        soff = o.x;
+        eoff = o.y;
+    }
+    for (uint64_t t0 = c0; t0 < ce; t0 += LOCATE_TILE) {  // (bounds uniform over the block: every lane reaches the barriers)
+        const uint64_t j = t0 + tid;
+        const bool act = j < ce;
+        const uint32_t h = act ? hit_word(k, seqw, nmw, hasn, j, slots, smask, max_probe) : NO_MATE;
+        if (lane == 63) lasth[wave] = h;
+        if (j == ce - 1) tailh = h;
+        __syncthreads();
+        uint32_t prev = (uint32_t)__shfl_up((int)h, 1);
+        if (lane == 0) prev = wave ? lasth[wave - 1] : carry;
+        carry = lasth[3];
+        const bool cont = act && mate_continues(prev, h);
+        const uint64_t sm = __ballot(act && h != NO_MATE && !cont);
+        const uint64_t em = __ballot(act && prev != NO_MATE && !cont);
+        const uint64_t hm = __ballot(act && h != NO_MATE);
+        if (lane == 0) wcnt[wave] = make_uint4((uint32_t)__popcll(sm), (uint32_t)__popcll(em), (uint32_t)__popcll(hm), 0u);
+        __syncthreads();
+        // (one buffer each: lasth is read between the two barriers and written again behind the second, wcnt is read behind
+        // the second and written again behind the next tile's first)
+        uint32_t sbelow = 0, ebelow = 0, stile = 0, etile = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < 4; ++w) {
+            const uint4 c = wcnt[w];
+            if (w == wave) {
+                sbelow = stile;
+                ebelow = etile;
+            }
+            stile += c.x;
+            etile += c.y;
+            nhits += c.z;
+        }
+        if (EMIT) {
+            const uint64_t below = (1ull << lane) - 1ull;
+            if ((sm >> lane) & 1ull) {
+                const uint64_t at = soff + nstarts + sbelow + (uint32_t)__popcll(sm & below);
+                if (at < total) {
+                    run_start[at] = (uint32_t)j;
+                    run_hit[at] = h;
+                }
+            }
+            if ((em >> lane) & 1ull) {
+                const uint64_t at = eoff + nends + ebelow + (uint32_t)__popcll(em & below);
+                if (at < total) run_end[at] = (uint32_t)j;
+            }
+        }
+        nstarts += stile;
+        nends += etile;
+    }
+    // the contig's last chunk: a run that reaches the contig's last position ends at nk (tailh: written in front of the last
+    // tile's first barrier, which every lane has passed)
+    if (ce == nk && tailh != NO_MATE) {
+        if (EMIT && tid == 0) {
+            const uint64_t at = eoff + nends;
+            if (at < total) run_end[at] = (uint32_t)nk;
+        }
+        nends += 1;
+    }
+    if (!EMIT && tid == 0) counts[blockIdx.x] = make_uint4(nhits, nstarts, nends, 0u);
+}
+
+hipError_t launch_hit_runs(hipStream_t st, int k, const SeqDesc *sd, const uint2 *chunks, uint32_t nchunks, const uint64_t *seqw,
+                           const uint32_t *nmw, const uint32_t *has_n, const void *slots, uint64_t nslots, uint32_t max_probe,
+                           uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *run_start, uint32_t *run_end,
+                           uint32_t *run_hit) {
+    if (nchunks == 0) return hipSuccess;
+    const bool emit = offs != nullptr;
+    if (k < 1 || k > 32 || nslots == 0 || (nslots & (nslots - 1)) || !slots || !sd || !chunks || !seqw || !nmw || !has_n ||
+        (emit ? (!run_start || !run_end || !run_hit) : !counts))
+        return hipErrorInvalidValue;
+    const PosSlot *ps = static_cast<const PosSlot *>(slots);
+    if (emit)
+        hipLaunchKernelGGL(k_hit_runs<true>, dim3(nchunks), dim3(256), 0, st, k, sd, chunks, seqw, nmw, has_n, ps, nslots, max_probe,
+                           counts, offs, total, run_start, run_end, run_hit);
+    else
+        hipLaunchKernelGGL(k_hit_runs<false>, dim3(nchunks), dim3(256), 0, st, k, sd, chunks, seqw, nmw, has_n, ps, nslots, max_probe,
+                           counts, offs, total, run_start, run_end, run_hit);
+    return hipGetLastError();
+}
+
+}  // namespace pg

@@ -32,24 +32,12 @@
 // Every write to HBM is a vector store or a vector atomic.
 #include "pg_kernels.h"
 
+#include "pg_postable_dev.h"  // PosSlot, kmer_key_rc, mate_continues
+
 namespace pg {
 
 constexpr uint32_t MATE_TILE = 256;
 static_assert(MATE_CHUNK % MATE_TILE == 0, "a chunk is a whole number of tiles");
-
-struct PosSlot {
-    unsigned long long key;
-    uint32_t word[2];
-};
-static_assert(sizeof(PosSlot) == POS_SLOT_BYTES, "16-byte slots");
-
-// X > B: the reverse complement's value is the smaller one
-__device__ __forceinline__ bool kmer_key_rc(const uint64_t *seqw, uint64_t p, int k, uint64_t &key) {
-    const uint64_t X = extract_bases(seqw, p) & kmer_mask(k);
-    const uint64_t B = revcomp_le(X, k);
-    key = canonical_from_xb(X, B, k);
-    return X > B;
-}
 
 // job = positions [y * SYNTENY_JOB, (y + 1) * SYNTENY_JOB) of contig x, which holds at least k bases
 __global__ __launch_bounds__(256) void k_pos_insert(int k, uint32_t side, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ jobs,
@@ -130,12 +118,6 @@ __global__ __launch_bounds__(256) void k_pos_mates(int k, const SeqDesc *__restr
         const uint32_t n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
         if (n) atomicAdd(nmated, (unsigned long long)n);
     }
-}
-
-// does the mate `m` of a position continue the run of its predecessor's mate `prev`?  (64-bit sums: nothing wraps)
-__device__ __forceinline__ bool mate_continues(uint32_t prev, uint32_t m) {
-    if (m == NO_MATE || prev == NO_MATE) return false;
-    return (m & 1u) ? (uint64_t)m + 2 == (uint64_t)prev : (uint64_t)m == (uint64_t)prev + 2;
 }
 
 // contigs[c] = {first entry of contig c in mates, its k-mer positions}; chunk = {contig, first position}

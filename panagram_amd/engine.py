@@ -492,7 +492,8 @@ class PosTable:
     """Position table of two sequence sets in HBM (pg_synteny.hip): per distinct canonical k-mer the position of its one
     occurrence in side 0 (A) and in side 1 (B), or a mark that the side holds it more than once.  ``capacity_keys``: the distinct
     keys it must hold — the k-mer positions of both sides always suffice.  A side whose keys do not fit raises with code -4
-    (PG_E_CAPACITY); the table is then of no further use."""
+    (PG_E_CAPACITY); the table is then of no further use.  For ``hit_runs`` and ``locate`` (pg_locate.hip) side 1 holds query
+    sequences, side 0 stays empty, and any sequence set is streamed through the table: the queries' k-mer positions suffice."""
 
     def __init__(self, ctx: Context, k: int, capacity_keys: int):
         self.ctx, self._lib, self.k = ctx, ctx._lib, int(k)
@@ -512,6 +513,46 @@ class PosTable:
         n = C.c_uint64()
         check(self._lib.pg_postable_mates(self._h, seqs_a._h, _ptr(out), C.byref(n)))
         return out, int(n.value)
+
+    def hit_runs(self, seqs: SeqSet, cap: Optional[int] = None):
+        """(run_contig, run_start, run_end, run_hit, runs per contig, hit positions per contig): the maximal collinear runs of the
+        hits of ``seqs`` — any sequence set, streamed through the table — in side 1 (the queries).  A position has a hit when its
+        k-mer occurs exactly once in side 1, however often ``seqs`` holds it: ``run_hit`` = ``posQ << 1 | strand`` of the run's
+        first position, positions of ``seqs`` contig-relative; sorted by (contig, start).  The queries themselves as ``seqs``: hits
+        per contig = every query's unique k-mers.  ``cap`` (tests of the capacity protocol): ONE call with arrays of ``cap``
+        entries, returned whole behind the total and the hits."""
+        n = len(seqs.lens)
+        per, hits, total, nhits = np.zeros(n, np.uint64), np.zeros(n, np.uint64), C.c_uint64(), C.c_uint64()
+
+        def call(m):
+            arrs = [np.full(m, NO_MATE, np.uint32) for _ in range(4)]
+            check(self._lib.pg_postable_hit_runs(self._h, seqs._h, m, *[_ptr(a) if m else None for a in arrs], _ptr(per) if n else None,
+                                                 _ptr(hits) if n else None, C.byref(total), C.byref(nhits)))
+            return arrs
+        if cap is not None:
+            arrs = call(int(cap))
+            return (*arrs, per, hits, int(total.value), int(nhits.value))
+        call(0)
+        arrs = call(int(total.value))
+        return (*arrs, per, hits)
+
+    def locate(self, seqs_g: SeqSet, seqs_q: SeqSet, min_run: int = 1, max_gap: int = 1000, max_shift: int = 100,
+               cap: Optional[int] = None):
+        """(the eight block arrays of ``run_blocks``, blocks per contig of ``seqs_g``, hit positions, runs): the hit runs of
+        ``seqs_g`` chained into blocks against ``seqs_q``, which must be the set inserted as side 1 — A is ``seqs_g``, B the
+        queries; runs and hits never leave HBM.  ``cap``: the blocks expected (a second call follows when there are more)."""
+        params = _block_params(min_run, max_gap, max_shift)
+        ng = len(seqs_g.lens)
+        per, total, nhits, nruns = np.zeros(ng, np.uint64), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        n = int(cap) if cap is not None else 4096
+        while True:
+            arrs = [np.empty(n, np.uint32) for _ in range(8)]
+            check(self._lib.pg_postable_locate(self._h, seqs_g._h, seqs_q._h, *params, n, *[_ptr(a) if n else None for a in arrs],
+                                               _ptr(per) if ng else None, C.byref(total), C.byref(nhits), C.byref(nruns)))
+            if int(total.value) <= n:
+                break
+            n = int(total.value)
+        return (*[a[:total.value].copy() for a in arrs], per, int(nhits.value), int(nruns.value))
 
     def close(self) -> None:
         if self._h:
@@ -707,6 +748,13 @@ def synteny_variants_last_timing() -> dict:
     check(_lib.load().pg_synteny_variants_last_timing(ms))
     return dict(zip(("insert_a_ms", "insert_b_ms", "mates_ms", "runs_count_ms", "runs_emit_ms", "blocks_count_ms", "blocks_emit_ms",
                      "variants_count_ms", "variants_emit_ms"), (float(x) for x in ms)))
+
+
+def locate_last_timing() -> dict:
+    """HIP-event milliseconds of the kernels of this thread's last ``PosTable.locate`` (``hit_runs``: the first two)"""
+    ms = (C.c_float * 4)()
+    check(_lib.load().pg_locate_last_timing(ms))
+    return dict(zip(("hits_count_ms", "hits_emit_ms", "blocks_count_ms", "blocks_emit_ms"), (float(x) for x in ms)))
 
 
 COPIES_BINS = 64  # depth bins of a copy-number histogram: bin c = depth c, the last = that depth and beyond

@@ -1481,6 +1481,74 @@ class Index:
         out = cp.frames(tnames, tlens, k, chosen, hist, valid)
         return (*out, depths) if track else out
 
+    def locate(self, queries, genomes=None, k=None, min_run: int = 1, max_gap: int = 1000, max_shift: int = 100, min_kmers: int = 1,
+               min_frac: float = 0.0):
+        """(loci, matrix, summary) — ``locate.frames`` — of query sequences: WHERE each lies in the assemblies of the ``genomes``
+        (names; None: all) — chromosome, start, end, strand, every copy.  ``queries``: a FASTA path (plain or ``.gz``), FASTA
+        bytes, or a list of (name, sequence).  A locus is a block of collinear hits (``synteny --blocks``' chaining with
+        ``min_run``, ``max_gap``, ``max_shift``; the genome is A, the queries are B) of k-mers that occur exactly once among the
+        queries, however often the genome holds them; ``frac`` = its k-mers / the query's unique k-mers; ``min_kmers`` and
+        ``min_frac`` drop loci below them.
+        One position table is sized from the queries' k-mer positions and the queries are inserted once (``engine.PosTable``,
+        side 1); the queries streamed through it give ``unique``; then every genome is streamed once from its packed assembly
+        (``seqset_for``; dropped again when this call loaded it) and only its blocks leave the GPU (k_hit_runs, k_run_blocks).
+        A query shorter than k stays in matrix and summary with zeros.  Queries stay in order; duplicate names are kept.  The
+        chromosomes' lengths ride in ``loci.attrs["chrom_lens"]`` (genome -> chromosome -> bases) for ``locate.paf_lines``.
+        KeyError: an unknown genome name; ValueError: a genome without an assembly FASTA (a FASTQ sample, or no sequence file),
+        k outside 1..32, a parameter outside its range."""
+        from . import locate as loc, search as srch
+        names = list(self.genome_names)
+        cols = srch.pick_genomes(names, genomes)
+        k = int(self.k) if k is None else int(k)
+        if not 1 <= k <= 32:
+            raise ValueError(f"locate: k={k} (1 to 32)")
+        for name, v, lo in (("min_run", min_run, 1), ("max_gap", max_gap, 1), ("max_shift", max_shift, 0)):
+            if not lo <= int(v) <= 0x7FFFFFFF:
+                raise ValueError(f"locate: {name}={v} ({lo} to 2^31 - 1)")
+        if int(min_kmers) < 1 or not 0.0 <= float(min_frac) <= 1.0:
+            raise ValueError(f"locate: min_kmers={min_kmers} (at least 1), min_frac={min_frac} (0 to 1)")
+        chosen = [names[c] for c in cols]
+        for g in chosen:
+            fa = self.genomes[g].fasta
+            if fa is None or pd.isna(fa) or is_fastq(fa):
+                raise ValueError(f"locate: genome {g!r} has no assembly FASTA to look in ({fa})")
+        text, qnames, qlens, offs = srch.read_queries(queries)
+        nq = len(qnames)
+        total = int(np.maximum(qlens - k + 1, 0).sum())
+        unique = np.zeros(nq, np.int64)
+        per_genome, chrom_lens = [], {}
+        at = np.flatnonzero(qlens >= k)  # (a query shorter than k has no position: it stays on the host)
+        if total and chosen:
+            qss = engine.SeqSet.from_fasta(self.context, text if len(at) == nq else np.concatenate([text[offs[q]:offs[q + 1]] for q in at]))
+            table = None
+            try:
+                if list(qss.names) != [qnames[q] for q in at] or not np.array_equal(np.asarray(qss.lens, np.int64), qlens[at]):
+                    raise RuntimeError("locate: the queries were read differently on the host and on the GPU")
+                table = engine.PosTable(self.context, k, total)
+                table.insert(1, qss)
+                unique[at] = table.hit_runs(qss)[5]
+                for g in chosen:
+                    mine = g not in self._seqsets
+                    try:
+                        ss = self.seqset_for(g)
+                        got = table.locate(ss, qss, min_run, max_gap, max_shift)
+                        blk = loc.genome_loci(got[:8], k, len(ss.lens), qlens[at])
+                        blk["chrB"] = at[blk["chrB"].to_numpy(np.int64)]  # (the query's number among all of them)
+                        per_genome.append((list(ss.names), blk))
+                        chrom_lens[g] = dict(zip(ss.names, (int(n) for n in ss.lens)))
+                    finally:
+                        if mine:
+                            self.drop_seqset(g)
+            finally:
+                if table is not None:
+                    table.close()
+                qss.close()
+        else:
+            per_genome = [([], loc.genome_loci([np.zeros(0, np.uint32)] * 8, k, 0, [])) for _ in chosen]
+        loci, matrix, summary = loc.frames(qnames, qlens, k, unique, chosen, per_genome, min_kmers, min_frac)
+        loci.attrs["chrom_lens"] = chrom_lens
+        return loci, matrix, summary
+
     def _synteny_sides(self, a, b, chroms_a, chroms_b, k, run):
         """``run(k, seqs_a, seqs_b)`` on the two genomes' sequence sets, narrowed to the chosen chromosomes: (its result, k, per
         side (names, lengths) of the chromosomes taken)"""
@@ -1646,9 +1714,20 @@ class Genome:
         genes are cut from the anchor's packed sequence set on the GPU (``SeqSet.slice``, whose pieces start at multiples of 32:
         the up to 31 bases in front are trimmed on the host).  A gene on a chromosome the FASTA lacks, or with end <= start, is an
         empty target: it stays in the tables with zeros.  ValueError: no GFF."""
+        return self.index.copies(self._gene_targets("copies"), genomes, k, track)
+
+    def gene_loci(self, genomes=None, k=None, min_run: int = 1, max_gap: int = 1000, max_shift: int = 100, min_kmers: int = 1,
+                  min_frac: float = 0.0):
+        """``Index.locate`` with this annotated anchor's genes as the queries, cut and named as ``gene_copies`` does: where every
+        gene lies in the ``genomes``' assemblies.  ValueError: no GFF."""
+        return self.index.locate(self._gene_targets("locate"), genomes, k, min_run, max_gap, max_shift, min_kmers, min_frac)
+
+    def _gene_targets(self, what: str) -> list:
+        """(name, sequence) of every gene of ``load_genes``, for ``gene_copies`` and ``gene_loci`` (``what``: the caller, for the
+        error's text)"""
         from . import copies as cp
         if not self.annotated:
-            raise ValueError(f"copies: genome {self.name!r} has no GFF to take genes from")
+            raise ValueError(f"{what}: genome {self.name!r} has no GFF to take genes from")
         genes = self.load_genes()
         idx = self.index
         mine = self.name not in idx._seqsets
@@ -1669,7 +1748,7 @@ class Genome:
         finally:
             if mine:
                 idx.drop_seqset(self.name)
-        return idx.copies(list(zip(cp.gene_names(genes), seqs)), genomes, k, track)
+        return list(zip(cp.gene_names(genes), seqs))
 
     @property
     def bins_fname(self):

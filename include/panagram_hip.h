@@ -273,6 +273,23 @@ uint64_t pg_seqset_total_kmers(const pg_seqset *s, int k);
  * path differs only in keeping '\r').  The host only locates the header lines; the GPU strips the
  * line breaks and packs.  Text before the first header is ignored.  Synchronises. */
 int pg_seqset_from_fasta(pg_ctx *ctx, const void *text, uint64_t nbytes, pg_seqset **out);
+/* FASTQ text (host memory, starting at the first byte of a record) -> a seqset of ONE contig, on the GPU: the sequence lines of all
+ * complete records joined by a single 'N', so that no k-mer window spans two reads and every kernel that streams a seqset runs on
+ * reads without a descriptor per read.  What read_fastq_joined of panagram_amd/index.py does with a Python split of the whole file.
+ * Records are four lines each, as kmc -fq assumes; MULTI-LINE FASTQ (a sequence wrapped over several lines) IS NOT SUPPORTED.  Only
+ * the line count decides what a line is: quality lines may begin with '@' or '+'.
+ *   *nreads    the complete records: (line feeds in the text) / 4
+ *   *consumed  the offset just past the line feed that ends the last complete record (0 without one); the bytes from there on — a
+ *              torn record — contribute nothing and are not checked: hand them in again in front of the next batch
+ *   *out       one contig, its name "": per complete record the bytes of line 1 without the line feed and without a '\r' right
+ *              before it, an 'N' between two records (also around an empty sequence line); packed as every seqset is (lower case
+ *              folded, every byte outside ACGT an N).  Without a complete record (consumed == 0, zero bytes of text included) the
+ *              contig has length 0.
+ * PG_E_INVALID, and no seqset: a complete record whose line 0 does not begin with '@' or whose line 2 does not begin with '+' (the
+ * message names the record number of one of them); 2^43 bytes of text or more.  k_fastq_scan over tiles of 4096 bytes (line feeds,
+ * and output bytes and malformed lines for each of the four line phases a tile may start in), k_fastq_offsets (the tiles' scan),
+ * k_fastq_join (the ASCII, in device memory), k_pack; no tile waits for another, no global atomics.  Synchronises. */
+int pg_seqset_from_fastq(pg_ctx *ctx, const void *text, uint64_t nbytes, pg_seqset **out, uint64_t *nreads, uint64_t *consumed);
 /* one seqset holding the contigs of all `sets`, in order (packed planes copied device to device):
  * lets ONE result anchor every anchor genome of a pangenome, see pg_result_coschedule */
 int pg_seqset_concat(pg_ctx *ctx, const pg_seqset *const *sets, uint32_t nsets, pg_seqset **out);
@@ -744,6 +761,31 @@ int pg_copytable_clear_plane(pg_copytable *ct, uint32_t plane);
  * the chunks' partial histograms summed on the host in 64 bits; synchronises. */
 int pg_copytable_profile(pg_copytable *ct, const pg_seqset *seqs, uint32_t plane0, uint32_t nplanes, uint64_t *hist_out,
                          uint64_t *valid_out, uint16_t *depth_out);
+/* place: WHICH of the indexed genomes does an unassembled sample resemble along an anchor?  The sample's reads have been counted into
+ * `plane` of a count table that holds the anchor's k-mers (pg_copytable_insert_seqset of `anchor`, pg_copytable_count_seqset of the
+ * reads); `rows` holds the anchor's finished bitmap rows.  Window i = rows [starts[i], ends[i]) of contig contig[i] of the result, as
+ * for pg_result_presence_profile.  With k the table's k:
+ *   row correspondence  row r of contig c is the k-mer at bases [r, r + k) of contig c of `anchor`
+ *   validity            row r is valid when that window of the anchor holds no non-ACGT base
+ *   sample column       s(r) = 1 when the plane's counter of the row's canonical k-mer is >= min_count; a key the table does not
+ *                       hold reads 0, as in pg_copytable_profile
+ *   valid_out[i]                 the valid rows of window i
+ *   held_out[i]                  the valid rows with s(r) = 1
+ *   col_out[i*ngenomes + g]      the valid rows with bit g set
+ *   both_out[i*ngenomes + g]     the valid rows with bit g set and s(r) = 1
+ * The bits at and past ngenomes in a row's last byte never count; an empty window (starts[i] == ends[i]) gives zeros.
+ * PG_E_INVALID before anything is launched: a NULL argument, min_count == 0, a plane >= nplanes, handles of different contexts,
+ * fewer than 1 or more than 512 genomes, rows of a k that is not the table's, an anchor whose number of contigs is not the rows', a
+ * contig whose row count is not len - k + 1 (0 for len < k), a window outside its contig, a result without readable rows.  Launches
+ * of k_sample_agree over chunks of 4096 rows (one lookup and one row read per position, all columns followed together by ballot
+ * transpose; no atomics, no block waits for another), the chunks' 32-bit partials summed on the host in 64 bits; synchronises. */
+int pg_copytable_sample_agree(pg_copytable *ct, uint32_t plane, uint32_t min_count, const pg_seqset *anchor, pg_result *rows,
+                              uint32_t nwin, const uint32_t *contig, const uint64_t *starts, const uint64_t *ends,
+                              uint64_t *valid_out, uint64_t *held_out, uint64_t *col_out, uint64_t *both_out);
+/* the HIP-event times, in milliseconds, of this host thread's last calls: ms_out[2] = the kernels of the last pg_seqset_from_fastq
+ * (scan, offsets, join and pack together), k_sample_agree (all its launches) of the last pg_copytable_sample_agree — what
+ * tools/place_rate.py reports. */
+int pg_place_last_timing(float *ms_out);
 /* the HIP-event times, in milliseconds, of this host thread's last calls: ms_out[3] = k_copy_insert of the last insert, k_copy_count
  * of the last count, k_copy_profile (all its launches) of the last profile — what tools/copies_rate.py reports. */
 int pg_copies_last_timing(float *ms_out);

@@ -213,6 +213,21 @@ def main(argv=None):
     lo.add_argument("--summary", metavar="FILE", default=None, help="also write one line per query: query length kmers unique loci genomes_hit best_genome best_frac")
     lo.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     lo.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    plc = sub.add_parser("place", help="which indexed genome an unassembled read set resembles along an anchor genome, bin by bin: the reads "
+                                       "joined and counted against the anchor's k-mers and that column joined with the anchor's bitmap rows on "
+                                       "the GPU: tab-separated, with a header, chrom start end valid held best best_jaccard second second_jaccard")
+    plc.add_argument("index_dir")
+    plc.add_argument("anchor", metavar="GENOME", help="the anchor genome (an assembly of the index with bitmap.1)")
+    plc.add_argument("reads", metavar="reads.fq", nargs="+", help="FASTQ, four lines per record, plain or .gz")
+    plc.add_argument("--chroms", default="", metavar="X,Y", help="the anchor's chromosomes to walk (default: all of them)")
+    plc.add_argument("--bin-size", type=int, default=100000, metavar="N", help="positions per bin (default 100000)")
+    plc.add_argument("--min-count", type=int, default=2, metavar="C", help="the sample holds a k-mer its reads hold at least C times (default 2)")
+    plc.add_argument("--genomes", default="", metavar="A,B", help="the genomes that take part (default: all of them)")
+    plc.add_argument("--matrix", metavar="FILE", default=None, help="also write the bins x genomes table of Jaccard indices")
+    plc.add_argument("--summary", metavar="FILE", default=None, help="also write one line per genome: genome col both jaccard cont_g cont_s bins_best")
+    plc.add_argument("--batch-bytes", type=int, default=None, metavar="N", help="FASTQ text bytes joined at a time (default 2^28)")
+    plc.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    plc.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -419,6 +434,34 @@ def main(argv=None):
                 f.writelines(line + "\n" for line in copies.track_lines(list(matrix.index), out["length"].to_numpy()[::ng], idx.k if a.k is None else a.k,
                                                                         list(matrix.columns), got[3]))
         copies.long_text(out).to_csv(a.output if a.output else sys.stdout, sep="\t", index=False)
+        return 0
+    if a.cmd == "place":
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"place: {a.index_dir!r} is not an index directory")
+        for r in a.reads:
+            if not os.path.isfile(r):
+                ap.error(f"place: no read file {r!r}")
+        if a.bin_size < 1 or a.min_count < 1 or (a.batch_bytes is not None and a.batch_bytes < 1):
+            ap.error("place: --bin-size, --min-count and --batch-bytes must be positive")
+        from .index import Index
+        from . import place
+        try:
+            idx = Index(a.index_dir, mode="r", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"place: {e}")
+        try:
+            try:
+                main_, matrix, summary, stats = idx.place(a.anchor, a.reads, [c for c in a.chroms.split(",") if c] or None, a.bin_size,
+                                                          a.min_count, [g for g in a.genomes.split(",") if g] or None, a.batch_bytes)
+            except (ValueError, KeyError) as e:
+                ap.error(f"place: {e}")
+        finally:
+            idx.close()
+        if a.matrix:
+            place.write_matrix(matrix, a.matrix)
+        if a.summary:
+            place.write_summary(summary, stats, a.summary)
+        place.write_main(main_, a.output if a.output else sys.stdout)
         return 0
     if a.cmd == "locate":
         if (a.queries is None) == (a.genes is None):

@@ -88,6 +88,7 @@ PROTOTYPES = {
     "pg_seqset_load_dev": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64]),
     "pg_seqset_total_kmers": (C.c_uint64, [_vp, C.c_int]),
     "pg_seqset_from_fasta": (C.c_int, [_vp, _vp, C.c_uint64, _vpp]),
+    "pg_seqset_from_fastq": (C.c_int, [_vp, _vp, C.c_uint64, _vpp, _u64p, _u64p]),
     "pg_seqset_concat": (C.c_int, [_vp, _vp, C.c_uint32, _vpp]),
     "pg_seqset_ncontigs": (C.c_uint32, [_vp]),
     "pg_seqset_unpack": (C.c_int, [_vp, C.c_uint32, _vp]),
@@ -157,6 +158,8 @@ PROTOTYPES = {
     "pg_copytable_clear_plane": (C.c_int, [_vp, C.c_uint32]),
     "pg_copytable_profile": (C.c_int, [_vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "pg_copies_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
+    "pg_copytable_sample_agree": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pg_place_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
     "pg_knn_rows": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "pg_result_write_bgzf": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "pg_bgzf_inflate": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),

@@ -1,5 +1,6 @@
 // pg_api_copies.hip — host side of the C-ABI: the count table of target k-mers, a genome counted into one of its planes, and the
-// depth histograms of sequences along the planes (pg_copies.hip, pg_copies_host.h).
+// depth histograms of sequences along the planes (pg_copies.hip, pg_copies_host.h); one plane joined with finished bitmap rows
+// (pg_place.hip).
 #include "pg_host.h"
 
 #include "pg_copies_host.h"
@@ -8,6 +9,11 @@ static constexpr uint64_t COPIES_MAX_KEYS = COPIES_MAX_SLOTS / 2;   // slots = t
 static constexpr uint64_t COPIES_MAX_POSITIONS = 0xFFFFFFFFull;     // of one genome: a counter is 32 bits
 static constexpr uint32_t COPIES_MAX_PROBE = 4096;                  // slots a lane walks before it gives up (load <= 0.5: tens at the most)
 static constexpr size_t COPIES_PARTIAL_BYTES = (size_t)256 << 20;   // partials of one profile launch (a longer chunk list goes in pieces)
+
+float *pg::place_ms() {
+    static thread_local float ms[2] = {0, 0};
+    return ms;
+}
 
 struct pg_copytable {
     pg_ctx *ctx;
@@ -212,6 +218,87 @@ int copytable_profile(pg_copytable *ct, const pg_seqset *sq, uint32_t plane0, ui
     return PG_OK;
 }
 
+// the sample's column (plane >= min_count) joined with the rows of `r` over windows of its contigs: launches of k_sample_agree over
+// the chunks of all windows, the chunks' partials summed per window on the host
+int copytable_sample_agree(pg_copytable *ct, uint32_t plane, uint32_t min_count, const pg_seqset *anchor, pg_result *r, uint32_t nwin,
+                           const uint32_t *contig, const uint64_t *starts, const uint64_t *ends, uint64_t *valid_out, uint64_t *held_out,
+                           uint64_t *col_out, uint64_t *both_out) {
+    const char *fn = "pg_copytable_sample_agree";
+    if (min_count == 0) return fail(PG_E_INVALID, "%s: min_count must be >= 1", fn);
+    if (plane >= ct->nplanes) return fail(PG_E_INVALID, "%s: plane %u of %u", fn, plane, ct->nplanes);
+    if (ct->ctx != anchor->ctx || ct->ctx != r->ctx) return fail(PG_E_INVALID, "%s: table, anchor and rows belong to different contexts", fn);
+    if (ct->overflowed) return fail(PG_E_CAPACITY, "%s: the table overflowed", fn);
+    if (int e = check_window_call(r, 1, 1, nwin, fn, "windows")) return e;
+    const uint32_t N = r->N;
+    if (N < 1 || N > PROFILE_MAX_GENOMES) return fail(PG_E_INVALID, "%s: %u genomes (1 to %u)", fn, N, PROFILE_MAX_GENOMES);
+    if (r->k != ct->k) return fail(PG_E_INVALID, "%s: rows of k = %d, a table of k = %d", fn, r->k, ct->k);
+    if (anchor->n != r->ad.size())
+        return fail(PG_E_INVALID, "%s: the anchor has %u contigs, the rows %zu", fn, anchor->n, r->ad.size());
+    for (uint32_t c = 0; c < anchor->n; ++c) {
+        const uint64_t len = anchor->desc[c].len, nk = len >= (uint64_t)ct->k ? len - ct->k + 1 : 0;
+        if (r->ad[c].nkmers != nk)
+            return fail(PG_E_INVALID, "%s: contig %u has %u rows, its %llu bases hold %llu k-mers", fn, c, r->ad[c].nkmers,
+                        (unsigned long long)len, (unsigned long long)nk);
+    }
+    Windows w;
+    if (int e = gather_windows(r, 1, 1, nwin, contig, starts, ends, "window", w)) return e;
+    place_ms()[1] = 0;
+    if (nwin == 0) return PG_OK;
+    std::fill(valid_out, valid_out + nwin, 0ull);
+    std::fill(held_out, held_out + nwin, 0ull);
+    std::fill(col_out, col_out + (size_t)nwin * N, 0ull);
+    std::fill(both_out, both_out + (size_t)nwin * N, 0ull);
+    std::vector<uint2> chunks;
+    std::vector<uint64_t> first;
+    if (int e = cut_chunks(fn, nwin, starts, ends, PLACE_CHUNK, chunks, &first)) return e;
+    if (chunks.empty()) return PG_OK;  // (every window empty: zeros)
+    const size_t nchunks = chunks.size();
+    if (int e = use_device(r->ctx)) return e;
+    if (int e = join_result(r)) return e;
+    hipStream_t st = r->ctx->stream;
+    const size_t per = std::max<size_t>(1, COPIES_PARTIAL_BYTES / ((size_t)(N + 1) * sizeof(uint2)));  // chunks per launch
+    const std::vector<uint32_t> wc(contig, contig + nwin);
+    DevBuf<uint2> d_chunks, d_part;  // [n][N] {col, both}, then [n] {valid, held}
+    DevBuf<uint32_t> d_wc;
+    std::vector<uint2> part(std::min(per, nchunks) * (N + 1));
+    hipError_t e = w.upload(st);
+    if (e == hipSuccess) e = d_chunks.upload(chunks, st);
+    if (e == hipSuccess) e = d_wc.upload(wc, st);
+    if (e == hipSuccess) e = d_part.alloc(part.size());
+    if (e == hipErrorOutOfMemory) return fail(PG_E_CAPACITY, "%s: no memory for %zu chunks of %u genomes", fn, nchunks, N);
+    float total_ms = 0;
+    uint32_t win = 0;  // (the chunks are in window order)
+    for (size_t c0 = 0; c0 < nchunks && e == hipSuccess; c0 += per) {
+        const size_t n = std::min(per, nchunks - c0);
+        float ms = 0;
+        LaunchTimer tm(&ms);
+        e = tm.start(st);
+        if (e == hipSuccess)
+            e = launch_sample_agree(st, N, ct->k, r->d_out1, w.base(), w.ends(), d_chunks.get() + c0, (uint32_t)n, d_wc.get(), anchor->d_desc,
+                                    anchor->d_seqw, anchor->d_nmw, anchor->d_has_n, ct->d_keys, ct->nslots, ct->max_probe,
+                                    ct->d_planes + (size_t)plane * ct->nslots, min_count, d_part.get(), d_part.get() + n * N);
+        if (e == hipSuccess) e = tm.stop(st);
+        if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_part.get(), n * (N + 1) * sizeof(uint2), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+        tm.read();
+        total_ms += ms;
+        for (size_t c = 0; c < n; ++c) {
+            while (c0 + c >= first[win + 1]) ++win;
+            const uint2 *p = part.data() + c * N;
+            for (uint32_t g = 0; g < N; ++g) {
+                col_out[(size_t)win * N + g] += p[g].x;
+                both_out[(size_t)win * N + g] += p[g].y;
+            }
+            valid_out[win] += part[n * N + c].x;
+            held_out[win] += part[n * N + c].y;
+        }
+    }
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    place_ms()[1] = total_ms;
+    return PG_OK;
+}
+
 }  // namespace
 
 extern "C" int pg_copytable_create(pg_ctx *ctx, int k, uint64_t capacity_keys, uint32_t nplanes, pg_copytable **out) {
@@ -258,6 +345,24 @@ extern "C" int pg_copytable_profile(pg_copytable *ct, const pg_seqset *seqs, uin
     PG_API_BEGIN
     if (!ct || !seqs || !hist_out || !valid_out) return fail(PG_E_INVALID, "pg_copytable_profile: NULL argument");
     return copytable_profile(ct, seqs, plane0, nplanes, hist_out, valid_out, depth_out);
+    PG_API_END
+}
+
+extern "C" int pg_copytable_sample_agree(pg_copytable *ct, uint32_t plane, uint32_t min_count, const pg_seqset *anchor, pg_result *rows,
+                                         uint32_t nwin, const uint32_t *contig, const uint64_t *starts, const uint64_t *ends,
+                                         uint64_t *valid_out, uint64_t *held_out, uint64_t *col_out, uint64_t *both_out) {
+    PG_API_BEGIN
+    if (!ct || !anchor || !rows || (nwin && (!contig || !starts || !ends || !valid_out || !held_out || !col_out || !both_out)))
+        return fail(PG_E_INVALID, "pg_copytable_sample_agree: NULL argument");
+    return copytable_sample_agree(ct, plane, min_count, anchor, rows, nwin, contig, starts, ends, valid_out, held_out, col_out, both_out);
+    PG_API_END
+}
+
+extern "C" int pg_place_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_place_last_timing: NULL argument");
+    std::copy(place_ms(), place_ms() + 2, ms_out);
+    return PG_OK;
     PG_API_END
 }
 

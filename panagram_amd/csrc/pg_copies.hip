@@ -37,26 +37,13 @@
 //                   depths to the track when one is asked for.  The host sums a contig's chunks (pg_copies_host.h).
 // Every write to HBM is a vector store or a vector atomic.
 #include "pg_kernels.h"
+#include "pg_copies_dev.h"
 
 namespace pg {
 
 constexpr uint32_t COPY_FOLD_TURNS = 8;  // slots a wave folds before its lanes add for themselves (a satellite of period p: at most p)
-constexpr uint32_t SLOT_INVALID = 0xFFFFFFFFu, SLOT_ABSENT = 0xFFFFFFFEu;  // (slots are below 2^31)
 static_assert(COPIES_CHUNK % 256 == 0, "a chunk is a whole number of tiles");
 static_assert(COPIES_BINS == 64, "one bin per lane of a wave");
-
-__device__ __forceinline__ uint64_t copy_key(const uint64_t *seqw, uint64_t p, int k) { return canonical_from_le(extract_bases(seqw, p), k); }
-
-// the slot of `key` in a table that is not being written: its number, or SLOT_ABSENT
-__device__ __forceinline__ uint32_t copy_lookup(const unsigned long long *__restrict__ keys, uint64_t smask, uint32_t max_probe, uint64_t key) {
-    uint64_t s = sketch_hash(key) & smask;
-    for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
-        const unsigned long long cur = keys[s];
-        if (cur == EMPTY_KEY) break;
-        if (cur == key) return (uint32_t)s;
-    }
-    return SLOT_ABSENT;
-}
 
 // job = positions [y * COPIES_JOB, (y + 1) * COPIES_JOB) of contig x, which holds at least k bases
 __global__ __launch_bounds__(256) void k_copy_insert(int k, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ jobs,

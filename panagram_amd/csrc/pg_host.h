@@ -295,4 +295,7 @@ PG_INTERNAL int cut_chunks(const char *fn, uint32_t nwin, const uint64_t *starts
                            std::vector<uint2> &chunks, std::vector<uint64_t> *first = nullptr);
 // pg_api_bgzf.hip
 PG_INTERNAL void df_free_buffers(pg_ctx::DfSet &d);
+// pg_api_copies.hip: this thread's last pg_seqset_from_fastq (its kernels) and pg_copytable_sample_agree, in milliseconds (a
+// function, not an extern thread_local: another unit would call the variable's absent initialiser)
+PG_INTERNAL float *place_ms();
 }  // namespace pg

@@ -358,6 +358,30 @@ hipError_t launch_copy_profile(hipStream_t st, int k, const SeqDesc *sd, const u
                                const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n, const unsigned long long *keys,
                                uint64_t nslots, uint32_t max_probe, const uint32_t *planes, uint32_t nplanes, uint32_t *partial,
                                uint32_t *valid_partial, uint16_t *depth, uint64_t depth_stride);
+// FASTQ text to the ASCII of one contig (pg_fastq.hip; the definitions are there): `text` is readable, and zero past nbytes, up to
+// ntiles * FASTQ_TILE + 16 bytes, ntiles = ceil(nbytes / FASTQ_TILE).
+//   scan  sums[tile] per tile (k_fastq_scan), then bases[tile] = {first output byte, first line number} and summary[3] = {line
+//         feeds L, the number of the first malformed line below 4 (L / 4) or ~0, output bytes of the whole text} (k_fastq_offsets)
+//   join  limit = 4 (L / 4) != 0: the output bytes of the lines below `limit` to out (never at or past out_cap; nbytes always
+//         suffices), fin[2] = {len, consumed}
+constexpr uint32_t FASTQ_TILE = 4096;
+struct FastqTileSum {
+    uint32_t nlf, out[4], nbad[4], firstbad[4], pad[3];  // out, nbad, firstbad: by the line number & 3 of the tile's first byte
+};
+hipError_t launch_fastq_scan(hipStream_t st, const uint8_t *text, uint64_t nbytes, uint32_t ntiles, FastqTileSum *sums, ulonglong2 *bases,
+                             uint64_t *summary);
+hipError_t launch_fastq_join(hipStream_t st, const uint8_t *text, uint64_t nbytes, uint32_t ntiles, const ulonglong2 *bases, uint64_t limit,
+                             uint8_t *out, uint64_t out_cap, uint64_t *fin);
+// the sample's column joined with finished rows (pg_place.hip; the definitions are there): windows (base, ends) and chunks as for
+// the presence profile at stride 1, PLACE_CHUNK rows each, wcontig[window] = its contig in sd; row r of a contig is the k-mer at
+// its bases [r, r + k), and every chunk lies within the contig's len - k + 1 positions.  The count table and `plane` as
+// launch_copy_profile takes them.  One block per chunk, no block waits for another, no atomics: partial[chunk * N + g] = {col,
+// both}, vh[chunk] = {valid, held}.  1 <= N <= PROFILE_MAX_GENOMES, min_count >= 1.
+constexpr uint32_t PLACE_CHUNK = 4096;  // rows per chunk, a multiple of 256
+hipError_t launch_sample_agree(hipStream_t st, uint32_t ngenomes, int k, const uint8_t *rows, const uint64_t *base, const uint64_t *ends,
+                               const uint2 *chunks, uint32_t nchunks, const uint32_t *wcontig, const SeqDesc *sd, const uint64_t *seqw,
+                               const uint32_t *nmw, const uint32_t *has_n, const unsigned long long *keys, uint64_t nslots,
+                               uint32_t max_probe, const uint32_t *plane, uint32_t min_count, uint2 *partial, uint2 *vh);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

@@ -70,6 +70,7 @@ GAPS_FIRST_CAP = 1 << 16
 # presence profile (pg_profile.hip).  PROFILE_CHUNK: rows per workgroup — pg_kernels.h's constant, restated for the tests that aim
 # at chunk edges (tests/test_search_cpu.py holds the two together)
 PROFILE_CHUNK = 4096
+PROFILE_MAX_GENOMES = 512  # columns k_presence_profile and k_sample_agree follow (tests/test_place_cpu.py holds it to the header)
 
 
 def tile_positions() -> int:
@@ -269,6 +270,26 @@ class SeqSet(_Owner):
         names = buf[:need.value].tobytes().decode("latin-1").split("\0")[:n] if n else []
         ss.names, ss.lens = names, lens
         return ss
+
+    @classmethod
+    def from_fastq(cls, ctx: Context, source) -> Tuple["SeqSet", int, int]:
+        """``(seqset, nreads, consumed)`` of FASTQ text (bytes / uint8 array) that starts at the first byte of a record, four
+        lines per record (multi-line FASTQ is not supported): ONE contig, the sequence lines of all complete records joined by a
+        single ``N`` on the GPU (pg_fastq.hip), ``names == [""]``; ``consumed`` = the offset just past the last complete record —
+        the rest is a torn record for the next batch.  Without a complete record the contig has length 0.  A complete record
+        whose line 0 does not begin with ``@`` or whose line 2 does not begin with ``+`` raises with code -1."""
+        text = _bytes_view(source)
+        ss = cls.__new__(cls)
+        ss.ctx, ss._lib = ctx, ctx._lib
+        h, nreads, consumed = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        check(ss._lib.pg_seqset_from_fastq(ctx._h, _ptr(text) if len(text) else None, len(text), C.byref(h), C.byref(nreads),
+                                           C.byref(consumed)))
+        ss._h = h
+        ctx._adopt(ss)
+        lens = np.zeros(1, np.uint64)
+        check(ss._lib.pg_seqset_describe(h, _ptr(lens), None, 0, None))
+        ss.names, ss.lens = [""], lens
+        return ss, int(nreads.value), int(consumed.value)
 
     @classmethod
     def concat(cls, ctx: Context, sets: Sequence["SeqSet"]) -> "SeqSet":
@@ -759,6 +780,8 @@ def locate_last_timing() -> dict:
 
 COPIES_BINS = 64  # depth bins of a copy-number histogram: bin c = depth c, the last = that depth and beyond
 COPIES_CHUNK = 4096
+PLACE_CHUNK = 4096   # rows a workgroup of k_sample_agree takes
+FASTQ_TILE = 4096    # bytes of text a workgroup of k_fastq_scan / k_fastq_join takes
 DEPTH_INVALID = 0xFFFF  # a position of a depth track whose window holds a non-ACGT base
 
 
@@ -812,6 +835,21 @@ class CopyTable:
                                              _ptr(valid if n else pad), _ptr(depths if depths is None or depths.size else pad)))
         return (hist, valid, depths) if track else (hist, valid)
 
+    def sample_agree(self, plane: int, min_count: int, anchor: SeqSet, rows: "AnchorResult", contigs, starts, ends):
+        """(valid [windows], held [windows], col [windows, genomes], both [windows, genomes]) uint64 of windows ``[starts[i],
+        ends[i])`` of the rows of contig ``contigs[i]`` of ``rows``, whose row r is the k-mer at bases ``[r, r + k)`` of that
+        contig of ``anchor``: the valid rows, those whose k-mer ``plane`` counted at least ``min_count`` times (the sample holds
+        it), those with genome g's bit, and those with both (pg_place.hip: one launch family, nothing per position comes back)."""
+        if plane < 0 or min_count < 0:
+            raise ValueError(f"plane {plane}, min_count {min_count}")
+        contigs, starts, ends = _windows(contigs, starts, ends, "window")
+        n, N = len(contigs), rows.ngenomes
+        valid, held = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        col, both = np.zeros((n, N), np.uint64), np.zeros((n, N), np.uint64)
+        check(self._lib.pg_copytable_sample_agree(self._h, int(plane), int(min_count), anchor._h, rows._h, n, _ptr(contigs), _ptr(starts),
+                                                  _ptr(ends), _ptr(valid), _ptr(held), _ptr(col), _ptr(both)))
+        return valid, held, col, both
+
     def close(self) -> None:
         if self._h:
             self._lib.pg_copytable_destroy(self._h)
@@ -829,6 +867,14 @@ def copies_last_timing() -> dict:
     ms = (C.c_float * 3)()
     check(_lib.load().pg_copies_last_timing(ms))
     return dict(zip(("insert_ms", "count_ms", "profile_ms"), (float(x) for x in ms)))
+
+
+def place_last_timing() -> dict:
+    """HIP-event milliseconds of the kernels of this thread's last ``SeqSet.from_fastq`` (scan, offsets, join and pack together)
+    and of k_sample_agree in its last ``CopyTable.sample_agree``"""
+    ms = (C.c_float * 2)()
+    check(_lib.load().pg_place_last_timing(ms))
+    return dict(zip(("fastq_ms", "agree_ms"), (float(x) for x in ms)))
 
 
 class PanTable(_Owner):

@@ -1481,6 +1481,25 @@ class Index:
         out = cp.frames(tnames, tlens, k, chosen, hist, valid)
         return (*out, depths) if track else out
 
+    def place(self, anchor: str, reads, chroms=None, bin_size: int = 100000, min_count: int = 2, genomes=None,
+              batch_bytes: Optional[int] = None):
+        """(main, matrix, summary, stats) — ``place.frames`` — of an unassembled sample along the anchor genome ``anchor``: per bin
+        of ``bin_size`` positions which of the indexed genomes the sample resembles.  ``reads``: FASTQ paths (plain or ``.gz``,
+        four lines per record).  The comparison is about the index's k-mers: a k-mer of the anchor counts as held by the sample
+        when the reads hold it at least ``min_count`` times (both strands; the only error filter), and per bin and genome the
+        Jaccard index of the sample's column and the genome's is taken over the anchor's valid positions.  ``genomes`` (names;
+        None: all): the genomes that take part — the anchor's own column included, a sample that is the anchor is called the
+        anchor.  The GPU side is ``Genome.place_counts``: the read files are read again for every batch of the anchor's
+        chromosomes.  KeyError: an unknown anchor, chromosome or genome; ValueError: a FASTQ anchor, an anchor without
+        bitmap.1, a FASTA that disagrees with chrs.tsv, a missing read file, a torn last record."""
+        from . import place as pl
+        if anchor not in self.genomes:
+            raise KeyError(f"place: unknown genome {anchor!r} (the index has {', '.join(self.genome_names)})")
+        names = list(self.genome_names)
+        pl.pick_columns(names, genomes)  # (refused before any work)
+        bins, valid, held, col, both, stats = self[anchor].place_counts(reads, chroms, bin_size, min_count, batch_bytes)
+        return (*pl.frames(bins, valid, held, col, both, names, genomes), stats)
+
     def locate(self, queries, genomes=None, k=None, min_run: int = 1, max_gap: int = 1000, max_shift: int = 100, min_kmers: int = 1,
                min_frac: float = 0.0):
         """(loci, matrix, summary) — ``locate.frames`` — of query sequences: WHERE each lies in the assemblies of the ``genomes``
@@ -2051,6 +2070,118 @@ class Genome:
         return engine.AnchorResult.from_bgzf(self.index.context, int(self.index.k), self.ngenomes, nkmers, self.bitmap_gz_fname(step),
                                              self.bitmap_gzi_fname(step), file_row0=row0, step=step,
                                              lowres_step=int(self.index.lowres_step))
+
+    # ---- PLACE: a read set's column joined with this anchor's rows (pg_place.hip) ----
+    place_budget = 8 << 30            # bitmap.1 bytes of one batch of chromosomes read back into HBM
+    PLACE_MAX_POSITIONS = 1 << 30     # k-mer positions of one batch: the keys a count table holds
+
+    def _place_batches(self, chroms: List[str]) -> List[List[str]]:
+        """``_annotate_batches`` under ``place_budget``, each run cut further so that a batch has at most PLACE_MAX_POSITIONS k-mer
+        positions and its count table (8-byte keys and one 4-byte plane per slot) and rows fit the free memory"""
+        free = self.index.context.mem_info()[0]
+        nb = self.nbytes
+
+        def cost(pos: int) -> int:
+            slots = 2
+            while slots < 2 * pos:
+                slots *= 2
+            return slots * 12 + pos * nb
+        out = []
+        for run in self._annotate_batches(chroms, self.place_budget):
+            cur, pos = [], 0
+            for c in run:
+                p = int(self.chrs.loc[c, "size"])
+                if cur and (pos + p > self.PLACE_MAX_POSITIONS or cost(pos + p) > 0.8 * free):
+                    out.append(cur)
+                    cur, pos = [], 0
+                cur.append(c)
+                pos += p
+            if cur:
+                out.append(cur)
+        return out
+
+    def place_counts(self, reads, chroms=None, bin_size: int = 100000, min_count: int = 2, batch_bytes: Optional[int] = None):
+        """(bins, valid, held, col, both, stats) of the read set ``reads`` (FASTQ paths, plain or ``.gz``, four lines per record)
+        along this anchor: ``bins`` = chrom, start, end of the bins of ``similarity_bin_geometry`` at step 1 over ``chroms`` (None:
+        all, in chrs.tsv order), and per bin the valid rows, the rows whose k-mer the reads hold at least ``min_count`` times, and
+        per genome of the index the rows with its bit and with both.  ``stats``: reads, read_bases, hits, depth_hist, depth_mode,
+        min_count.  Per batch of chromosomes (``_place_batches``): the chromosomes packed from the FASTA, their k-mers into a count
+        table of one plane, every FASTQ batch of ``batch_bytes`` text bytes joined on the GPU (``SeqSet.from_fastq``) and streamed
+        through it, one depth profile of the anchor, the rows inflated from bitmap.1, one ``sample_agree`` over the bins.  THE READ
+        FILES ARE READ AGAIN FOR EVERY BATCH OF CHROMOSOMES: packed reads are not kept."""
+        from . import place as pl
+        idx, ctx, k = self.index, self.index.context, int(self.index.k)
+        bin_size, min_count = int(bin_size), int(min_count)
+        if min_count < 1:
+            raise ValueError(f"place: min_count must be at least 1, got {min_count}")
+        if self.fasta is None or pd.isna(self.fasta) or is_fastq(self.fasta):
+            raise ValueError(f"place: anchor {self.name!r} has no assembly FASTA ({self.fasta})")
+        if not os.path.exists(self.bitmap_gz_fname(1)):
+            raise ValueError(f"place: anchor {self.name!r} has no {os.path.basename(self.bitmap_gz_fname(1))}: it was not anchored")
+        chroms = self._checked_chroms(1, bin_size, chroms=chroms)
+        reads = [reads] if isinstance(reads, (str, os.PathLike)) else list(reads)
+        for r in reads:
+            if not os.path.isfile(r):
+                raise ValueError(f"place: no read file {os.fspath(r)!r}")
+        batch_bytes = pl.DEFAULT_BATCH_BYTES if batch_bytes is None else int(batch_bytes)
+        N = self.ngenomes
+        mine = self.name not in idx._seqsets
+        ss = idx.seqset_for(self.name)
+        frames, counts = [], []
+        stats = {"reads": 0, "read_bases": 0, "hits": 0, "depth_hist": np.zeros(engine.COPIES_BINS, np.uint64), "min_count": min_count}
+        try:
+            # the FASTA's records are the chromosomes of chrs.tsv, in its order
+            if len(ss.names) != len(self.chrs.index):
+                raise ValueError(f"place: {self.fasta} holds {len(ss.names)} records, chrs.tsv {len(self.chrs.index)} chromosomes")
+            for i, (c, size) in enumerate(zip(self.chrs.index, self.chrs["size"])):
+                want = max(0, int(ss.lens[i]) - k + 1)
+                if str(ss.names[i]) != str(c) or want != int(size):
+                    raise ValueError(f"place: record {i} of {self.fasta} is {ss.names[i]!r} with {want} k-mers, chromosome {i} of "
+                                     f"chrs.tsv is {c!r} with {int(size)}")
+            order = {c: i for i, c in enumerate(self.chrs.index)}
+            for bi, batch in enumerate(self._place_batches(chroms)):
+                sizes = [int(self.chrs.loc[c, "size"]) for c in batch]
+                geo = [self.similarity_bin_geometry(sz, 1, bin_size) for sz in sizes]
+                if sum(sizes) == 0:
+                    continue
+                ass = engine.SeqSet.concat_ranges(ctx, [(ss, order[batch[0]], len(batch))])
+                table = res = None
+                try:
+                    table = engine.CopyTable(ctx, k, sum(sizes), 1)
+                    table.insert(ass)
+                    for path in reads:
+                        fb = pl.FastqBatches(path, batch_bytes)
+                        for buf in fb:
+                            rs, n, used = engine.SeqSet.from_fastq(ctx, buf)
+                            try:
+                                stats["hits"] += table.count(0, rs)
+                                if bi == 0:
+                                    stats["reads"] += n
+                                    stats["read_bases"] += int(rs.lens[0]) - max(n - 1, 0)
+                            finally:
+                                rs.close()
+                            fb.advance(used)
+                    stats["depth_hist"] += table.profile(ass)[0][:, 0, :].sum(axis=0)
+                    res = self._rows_from_disk(batch)
+                    ci = np.concatenate([np.full(len(g[0]), i, np.uint32) for i, g in enumerate(geo)])
+                    st = np.concatenate([g[1] for g in geo])
+                    en = np.concatenate([g[2] for g in geo])
+                    counts.append(table.sample_agree(0, min_count, ass, res, ci, st, en))
+                finally:
+                    if res is not None:
+                        res.close()
+                    if table is not None:
+                        table.close()
+                    ass.close()
+                for c, sz, g in zip(batch, sizes, geo):
+                    frames.append(pd.DataFrame({"chrom": c, "start": g[0] * bin_size, "end": np.minimum((g[0] + 1) * bin_size, sz)}))
+        finally:
+            if mine:
+                idx.drop_seqset(self.name)
+        bins = pd.concat(frames, ignore_index=True) if frames else pd.DataFrame({"chrom": [], "start": [], "end": []})
+        cat = lambda j, shape: np.concatenate([c[j] for c in counts]) if counts else np.zeros(shape, np.uint64)
+        stats["depth_mode"] = pl.depth_mode(stats["depth_hist"])
+        return bins, cat(0, 0), cat(1, 0), cat(2, (0, N)), cat(3, (0, N)), stats
 
     # ---- INTROGRESSIONS: binned k-mer similarity (call_introgressions.py: bitmap_to_bins) ----
     # HBM of one batch of chromosomes read back: their bitmap.1 rows (the container holds them, and zeroes them, when the

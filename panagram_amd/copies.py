@@ -119,8 +119,18 @@ def track_lines(names: Sequence[str], lens: Sequence[int], k: int, genomes: Sequ
                 yield f"{name}\t{genome}\t{s}\t{e}\t{'.' if x == DEPTH_INVALID else f'{DEPTH_MAX}+' if x == DEPTH_MAX else x}"
 
 
+def table_slots(capacity: int) -> int:
+    """the slots of a key table made for ``capacity`` keys, as the library sizes it: the power of two at or above twice the
+    capacity, two at the least"""
+    slots = 2
+    while slots < 2 * int(capacity):
+        slots *= 2
+    return slots
+
+
 def planes_for(free_bytes: int, slots: int, genomes: int, track_kmers: int = 0) -> int:
-    """the planes of one batch of genomes: what half the free memory holds beside the keys (8 bytes a slot; a plane 4, and with a
+    """the planes of one batch of genomes beside a table of ``slots`` slots (``table_slots`` of its keys): what half the free
+    memory holds beside the keys (8 bytes a slot; a plane 4, and with a
     track 2 bytes per target position), at least 1 and at most ``genomes``"""
     room = int(free_bytes) // 2 - 8 * int(slots)
     return int(max(1, min(int(genomes), room // max(1, 4 * int(slots) + 2 * int(track_kmers)))))

@@ -4,10 +4,10 @@
 #include "pg_host.h"
 
 #include "pg_copies_host.h"
+#include "pg_keytable_host.h"
 
-static constexpr uint64_t COPIES_MAX_KEYS = COPIES_MAX_SLOTS / 2;   // slots = the power of two at or above 2 * capacity
+static constexpr uint64_t COPIES_MAX_KEYS = COPIES_MAX_SLOTS / 2;   // (table_slots: the power of two at or above 2 * capacity)
 static constexpr uint64_t COPIES_MAX_POSITIONS = 0xFFFFFFFFull;     // of one genome: a counter is 32 bits
-static constexpr uint32_t COPIES_MAX_PROBE = 4096;                  // slots a lane walks before it gives up (load <= 0.5: tens at the most)
 static constexpr size_t COPIES_PARTIAL_BYTES = (size_t)256 << 20;   // partials of one profile launch (a longer chunk list goes in pieces)
 
 float *pg::place_ms() {
@@ -29,30 +29,6 @@ namespace {
 
 thread_local float g_copies_ms[3] = {0, 0, 0};  // k_copy_insert, k_copy_count, k_copy_profile of this thread's last calls
 
-// the (contig, piece) jobs of a seqset's k-mer positions in pieces of `piece`, and the first entry of every contig in a back-to-back
-// array of k-mer positions; first[c] = the first job of contig c
-struct CopyWalk {
-    std::vector<uint2> jobs;
-    std::vector<uint64_t> koff, first;  // [n], [n + 1]
-    uint64_t nkmers = 0;
-};
-
-int walk_seqs(const pg_seqset *sq, int k, uint32_t piece, const char *fn, CopyWalk &w) {
-    w.koff.resize(sq->n);
-    w.first.assign((size_t)sq->n + 1, 0);
-    for (uint32_t c = 0; c < sq->n; ++c) {
-        const uint64_t len = sq->desc[c].len, nk = len >= (uint64_t)k ? len - k + 1 : 0;
-        w.koff[c] = w.nkmers;
-        w.first[c] = w.jobs.size();
-        if ((nk + piece - 1) / piece + w.jobs.size() > 0x7FFFFFFFull)
-            return fail(PG_E_INVALID, "%s: more than 2^31 - 1 pieces of %u positions", fn, piece);
-        for (uint64_t q = 0; q * piece < nk; ++q) w.jobs.push_back(make_uint2(c, (uint32_t)q));
-        w.nkmers += nk;
-    }
-    w.first[sq->n] = w.jobs.size();
-    return PG_OK;
-}
-
 void copytable_free(pg_copytable *ct) {
     hipSetDevice(ct->ctx->device);
     hipStreamSynchronize(ct->ctx->stream);
@@ -73,9 +49,8 @@ int copytable_create(pg_ctx *ctx, int k, uint64_t capacity, uint32_t nplanes, pg
     ct->ctx = ctx;
     ct->k = k;
     ct->capacity = capacity;
-    ct->nslots = 2;
-    while (ct->nslots < 2 * capacity) ct->nslots <<= 1;
-    ct->max_probe = (uint32_t)std::min<uint64_t>(ct->nslots, COPIES_MAX_PROBE);
+    ct->nslots = table_slots(capacity);
+    ct->max_probe = table_max_probe(ct->nslots);
     ct->nplanes = nplanes;
     DevBuf<unsigned long long> keys;
     DevBuf<uint32_t> planes;
@@ -98,29 +73,19 @@ int copytable_create(pg_ctx *ctx, int k, uint64_t capacity, uint32_t nplanes, pg
 int copytable_insert(pg_copytable *ct, const pg_seqset *sq, uint64_t *distinct) {
     if (ct->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_copytable_insert_seqset: table and seqset belong to different contexts");
     if (ct->overflowed) return fail(PG_E_CAPACITY, "pg_copytable_insert_seqset: the table overflowed before");
-    CopyWalk w;
-    if (int r = walk_seqs(sq, ct->k, COPIES_JOB, "pg_copytable_insert_seqset", w)) return r;
+    KmerWalk w;
+    if (int r = walk_kmers(sq, ct->k, COPIES_JOB, "pg_copytable_insert_seqset", w)) return r;
     if (int r = use_device(ct->ctx)) return r;
     *distinct = 0;
     g_copies_ms[0] = 0;
     if (w.jobs.empty()) return PG_OK;
     hipStream_t st = ct->ctx->stream;
-    DevBuf<uint2> d_jobs;
-    DevBuf<unsigned long long> d_ctr;
     unsigned long long ctr[2] = {0, 0};
-    LaunchTimer tm(&g_copies_ms[0]);
-    hipError_t e = d_jobs.upload(w.jobs, st);
-    if (e == hipSuccess) e = d_ctr.alloc(2);
-    if (e == hipSuccess) e = hipMemsetAsync(d_ctr.get(), 0, 16, st);
-    if (e == hipSuccess) e = tm.start(st);
-    if (e == hipSuccess)
-        e = launch_copy_insert(st, ct->k, sq->d_desc, d_jobs.get(), (uint32_t)w.jobs.size(), sq->d_seqw, sq->d_nmw, sq->d_has_n, ct->d_keys,
-                               ct->nslots, ct->max_probe, d_ctr.get());
-    if (e == hipSuccess) e = tm.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr.get(), 16, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    const hipError_t e = counted_launch(st, w.jobs, ctr, 2, &g_copies_ms[0], [&](const uint2 *jobs, uint32_t njobs, unsigned long long *d_ctr) {
+        return launch_copy_insert(st, ct->k, sq->d_desc, jobs, njobs, sq->d_seqw, sq->d_nmw, sq->d_has_n, ct->d_keys, ct->nslots,
+                                  ct->max_probe, d_ctr);
+    });
     if (e != hipSuccess) return fail(PG_E_HIP, "pg_copytable_insert_seqset: %s", hipGetErrorString(e));
-    tm.read();
     *distinct = ctr[1];
     if (ctr[0]) {
         ct->overflowed = true;
@@ -134,8 +99,8 @@ int copytable_count(pg_copytable *ct, uint32_t plane, const pg_seqset *sq, uint6
     if (plane >= ct->nplanes) return fail(PG_E_INVALID, "pg_copytable_count_seqset: plane %u of %u", plane, ct->nplanes);
     if (ct->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_copytable_count_seqset: table and seqset belong to different contexts");
     if (ct->overflowed) return fail(PG_E_CAPACITY, "pg_copytable_count_seqset: the table overflowed");
-    CopyWalk w;
-    if (int r = walk_seqs(sq, ct->k, COPIES_JOB, "pg_copytable_count_seqset", w)) return r;
+    KmerWalk w;
+    if (int r = walk_kmers(sq, ct->k, COPIES_JOB, "pg_copytable_count_seqset", w)) return r;
     if (w.nkmers > COPIES_MAX_POSITIONS)
         return fail(PG_E_INVALID, "pg_copytable_count_seqset: %llu k-mer positions in one genome (the counters hold 2^32 - 1)",
                     (unsigned long long)w.nkmers);
@@ -144,22 +109,12 @@ int copytable_count(pg_copytable *ct, uint32_t plane, const pg_seqset *sq, uint6
     g_copies_ms[1] = 0;
     if (w.jobs.empty()) return PG_OK;
     hipStream_t st = ct->ctx->stream;
-    DevBuf<uint2> d_jobs;
-    DevBuf<unsigned long long> d_n;
     unsigned long long n = 0;
-    LaunchTimer tm(&g_copies_ms[1]);
-    hipError_t e = d_jobs.upload(w.jobs, st);
-    if (e == hipSuccess) e = d_n.alloc(1);
-    if (e == hipSuccess) e = hipMemsetAsync(d_n.get(), 0, 8, st);
-    if (e == hipSuccess) e = tm.start(st);
-    if (e == hipSuccess)
-        e = launch_copy_count(st, ct->k, sq->d_desc, d_jobs.get(), (uint32_t)w.jobs.size(), sq->d_seqw, sq->d_nmw, sq->d_has_n, ct->d_keys,
-                              ct->nslots, ct->max_probe, ct->d_planes + (size_t)plane * ct->nslots, d_n.get());
-    if (e == hipSuccess) e = tm.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&n, d_n.get(), 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    const hipError_t e = counted_launch(st, w.jobs, &n, 1, &g_copies_ms[1], [&](const uint2 *jobs, uint32_t njobs, unsigned long long *d_n) {
+        return launch_copy_count(st, ct->k, sq->d_desc, jobs, njobs, sq->d_seqw, sq->d_nmw, sq->d_has_n, ct->d_keys, ct->nslots,
+                                 ct->max_probe, ct->d_planes + (size_t)plane * ct->nslots, d_n);
+    });
     if (e != hipSuccess) return fail(PG_E_HIP, "pg_copytable_count_seqset: %s", hipGetErrorString(e));
-    tm.read();
     *hits = n;
     return PG_OK;
 }
@@ -170,8 +125,8 @@ int copytable_profile(pg_copytable *ct, const pg_seqset *sq, uint32_t plane0, ui
         return fail(PG_E_INVALID, "pg_copytable_profile: planes [%u, %u + %u) of %u", plane0, plane0, nplanes, ct->nplanes);
     if (ct->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_copytable_profile: table and seqset belong to different contexts");
     if (ct->overflowed) return fail(PG_E_CAPACITY, "pg_copytable_profile: the table overflowed");
-    CopyWalk w;
-    if (int r = walk_seqs(sq, ct->k, COPIES_CHUNK, "pg_copytable_profile", w)) return r;
+    KmerWalk w;
+    if (int r = walk_kmers(sq, ct->k, COPIES_CHUNK, "pg_copytable_profile", w)) return r;
     if (int r = use_device(ct->ctx)) return r;
     const size_t row = (size_t)nplanes * COPIES_BINS;
     std::fill(hist_out, hist_out + (size_t)sq->n * row, 0ull);

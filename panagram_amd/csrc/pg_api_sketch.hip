@@ -1,6 +1,8 @@
 // pg_api_sketch.hip — host side of the C-ABI: distinct-k-mer sketch, MinHash sketches and their distances.
 #include "pg_host.h"
 
+#include "pg_keytable_host.h"  // walk_kmers
+
 // ---------------------------------------------------------------------------
 // distinct-k-mer sketch (sizes a table before it is built)
 // ---------------------------------------------------------------------------
@@ -48,13 +50,9 @@ extern "C" int pg_sketch_add_seqset(pg_sketch *sk, const pg_seqset *sq) {
     if (sk->ctx != sq->ctx) return fail(PG_E_INVALID, "sketch and seqset belong to different contexts");
     if (int r = use_device(sk->ctx)) return r;
     // one launch over all contigs (a launch per contig was 76 ms per genome of 20 000 contigs)
-    std::vector<uint2> jobs;
-    for (uint32_t c = 0; c < sq->n; ++c) {
-        const SeqDesc &sd = sq->desc[c];
-        if (sd.len < (uint64_t)sk->k) continue;
-        const uint64_t nk = sd.len - sk->k + 1;
-        for (uint64_t q = 0; q * SKETCH_JOB < nk; ++q) jobs.push_back(make_uint2(c, (uint32_t)q));
-    }
+    KmerWalk w;
+    if (int r = walk_kmers(sq, sk->k, SKETCH_JOB, "pg_sketch_add_seqset", w)) return r;
+    const std::vector<uint2> &jobs = w.jobs;
     if (jobs.empty()) return PG_OK;
     hipStream_t st = sk->ctx->stream;
     DevBuf<uint2> d_jobs;

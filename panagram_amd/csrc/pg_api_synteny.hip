@@ -4,10 +4,10 @@
 #include "pg_host.h"
 
 #include "pg_blocks_host.h"
+#include "pg_keytable_host.h"
 
 static constexpr uint64_t POS_MAX_BASES = 0x7FFFFFFFull;  // a side's bases: the word pos << 1 | rc stays below POS_MULTI
 static constexpr uint64_t POS_MAX_KEYS = 1ull << 32;      // two sides of 2^31 k-mers
-static constexpr uint32_t POS_MAX_PROBE = 4096;           // slots a lane walks before it gives up (load <= 0.5: tens at the most)
 
 struct pg_postable {
     pg_ctx *ctx;
@@ -30,34 +30,13 @@ thread_local float g_blocks_ms[7] = {0, 0, 0, 0, 0, 0, 0};  // those five, block
 thread_local float g_locate_ms[4] = {0, 0, 0, 0};  // k_hit_runs (count), (emit), k_run_blocks (count), (emit) of the last hit call
 thread_local float g_variants_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // those seven, variants (count), variants (emit) of the last pg_synteny_variants
 
-// the (contig, chunk) jobs of a seqset's k-mer positions, the base offset of every contig in the concatenation and its first
-// entry in a back-to-back array of k-mer positions
-struct SideWalk {
-    std::vector<uint2> jobs;
-    std::vector<uint32_t> off, koff;  // [n] each
-    uint64_t bases = 0, nkmers = 0;
-};
-
-int walk_side(const pg_seqset *sq, int k, const char *fn, SideWalk &w) {
-    w.off.resize(sq->n);
-    w.koff.resize(sq->n);
-    for (uint32_t c = 0; c < sq->n; ++c) {
-        const uint64_t len = sq->desc[c].len, nk = len >= (uint64_t)k ? len - k + 1 : 0;
-        if (w.bases + len > POS_MAX_BASES)
-            return fail(PG_E_INVALID, "%s: more than %llu bases in one side (take fewer chromosomes)", fn, (unsigned long long)POS_MAX_BASES);
-        w.off[c] = (uint32_t)w.bases;
-        w.koff[c] = (uint32_t)w.nkmers;
-        for (uint64_t q = 0; q * SYNTENY_JOB < nk; ++q) w.jobs.push_back(make_uint2(c, (uint32_t)q));
-        w.bases += len;
-        w.nkmers += nk;
-    }
+// the (contig, chunk) jobs of a side's k-mer positions (walk_kmers), held to the side's limit: behind it the base offsets and
+// the k-mer offsets of the contigs fit 32 bits
+int walk_side(const pg_seqset *sq, int k, const char *fn, KmerWalk &w) {
+    if (int r = walk_kmers(sq, k, SYNTENY_JOB, fn, w)) return r;
+    if (w.bases > POS_MAX_BASES)
+        return fail(PG_E_INVALID, "%s: more than %llu bases in one side (take fewer chromosomes)", fn, (unsigned long long)POS_MAX_BASES);
     return PG_OK;
-}
-
-uint64_t slots_for(uint64_t capacity) {
-    uint64_t n = 2;
-    while (n < 2 * capacity) n <<= 1;
-    return n;
 }
 
 int postable_create(pg_ctx *ctx, int k, uint64_t capacity, std::unique_ptr<pg_postable> &out) {
@@ -69,8 +48,8 @@ int postable_create(pg_ctx *ctx, int k, uint64_t capacity, std::unique_ptr<pg_po
     pt->ctx = ctx;
     pt->k = k;
     pt->capacity = capacity;
-    pt->nslots = slots_for(capacity);
-    pt->max_probe = (uint32_t)std::min<uint64_t>(pt->nslots, POS_MAX_PROBE);
+    pt->nslots = table_slots(capacity);
+    pt->max_probe = table_max_probe(pt->nslots);
     hipError_t e = hipMalloc(&pt->d_slots, pt->nslots * POS_SLOT_BYTES);
     if (e != hipSuccess)
         return fail(e == hipErrorOutOfMemory ? PG_E_CAPACITY : PG_E_HIP, "pg_postable_create: %llu slots: %s", (unsigned long long)pt->nslots,
@@ -100,7 +79,7 @@ int postable_insert(pg_postable *pt, int side, const pg_seqset *sq, float *ms = 
     if (pt->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_postable_insert_seqset: table and seqset belong to different contexts");
     if (pt->overflowed) return fail(PG_E_CAPACITY, "pg_postable_insert_seqset: the table overflowed before");
     if (pt->inserted[side]) return fail(PG_E_INVALID, "pg_postable_insert_seqset: side %d is inserted already", side);
-    SideWalk w;
+    KmerWalk w;
     if (int r = walk_side(sq, pt->k, "pg_postable_insert_seqset", w)) return r;
     if (int r = use_device(pt->ctx)) return r;
     pt->inserted[side] = true;
@@ -108,24 +87,16 @@ int postable_insert(pg_postable *pt, int side, const pg_seqset *sq, float *ms = 
     pt->side_contigs[side] = sq->n;
     if (w.jobs.empty()) return PG_OK;
     hipStream_t st = pt->ctx->stream;
-    DevBuf<uint2> d_jobs;
+    const std::vector<uint32_t> off(w.off.begin(), w.off.end());
     DevBuf<uint32_t> d_off;
-    DevBuf<unsigned long long> d_flags;
     unsigned long long flags = 0;
-    LaunchTimer tm(ms);
-    hipError_t e = d_jobs.upload(w.jobs, st);
-    if (e == hipSuccess) e = d_off.upload(w.off, st);
-    if (e == hipSuccess) e = d_flags.alloc(1);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flags.get(), 0, 8, st);
-    if (e == hipSuccess) e = tm.start(st);
+    hipError_t e = d_off.upload(off, st);
     if (e == hipSuccess)
-        e = launch_pos_insert(st, pt->k, (uint32_t)side, sq->d_desc, d_jobs.get(), (uint32_t)w.jobs.size(), d_off.get(), sq->d_seqw,
-                              sq->d_nmw, sq->d_has_n, pt->d_slots, pt->nslots, pt->max_probe, d_flags.get());
-    if (e == hipSuccess) e = tm.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&flags, d_flags.get(), 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+        e = counted_launch(st, w.jobs, &flags, 1, ms, [&](const uint2 *jobs, uint32_t njobs, unsigned long long *d_flags) {
+            return launch_pos_insert(st, pt->k, (uint32_t)side, sq->d_desc, jobs, njobs, d_off.get(), sq->d_seqw, sq->d_nmw, sq->d_has_n,
+                                     pt->d_slots, pt->nslots, pt->max_probe, d_flags);
+        });
     if (e != hipSuccess) return fail(PG_E_HIP, "pg_postable_insert_seqset: %s", hipGetErrorString(e));
-    tm.read();
     if (flags) {
         pt->overflowed = true;
         return fail(PG_E_CAPACITY, "pg_postable_insert_seqset: %llu slots (created for %llu keys) do not hold side %d's k-mers",
@@ -139,7 +110,7 @@ int postable_mates(pg_postable *pt, const pg_seqset *sq, uint32_t *mates_out, ui
     if (pt->ctx != sq->ctx) return fail(PG_E_INVALID, "pg_postable_mates: table and seqset belong to different contexts");
     if (pt->overflowed) return fail(PG_E_CAPACITY, "pg_postable_mates: the table overflowed");
     if (!pt->inserted[0]) return fail(PG_E_INVALID, "pg_postable_mates: side 0 has not been inserted");
-    SideWalk w;
+    KmerWalk w;
     if (int r = walk_side(sq, pt->k, "pg_postable_mates", w)) return r;
     if (int r = use_device(pt->ctx)) return r;
     hipStream_t st = pt->ctx->stream;
@@ -151,27 +122,22 @@ int postable_mates(pg_postable *pt, const pg_seqset *sq, uint32_t *mates_out, ui
         pt->nmates = 0;
     }
     if (w.jobs.empty()) return PG_OK;
-    DevBuf<uint2> d_jobs;
+    const std::vector<uint32_t> off(w.off.begin(), w.off.end()), koff(w.koff.begin(), w.koff.end());
     DevBuf<uint32_t> d_off, d_koff, d_m;
-    DevBuf<unsigned long long> d_n;
     unsigned long long n = 0;
-    LaunchTimer tm(ms);
-    hipError_t e = d_jobs.upload(w.jobs, st);
-    if (e == hipSuccess) e = d_off.upload(w.off, st);
-    if (e == hipSuccess) e = d_koff.upload(w.koff, st);
+    hipError_t e = d_off.upload(off, st);
+    if (e == hipSuccess) e = d_koff.upload(koff, st);
     if (e == hipSuccess) e = d_m.alloc(w.nkmers);
-    if (e == hipSuccess) e = d_n.alloc(1);
-    if (e == hipSuccess) e = hipMemsetAsync(d_n.get(), 0, 8, st);
-    if (e == hipSuccess) e = tm.start(st);
     if (e == hipSuccess)
-        e = launch_pos_mates(st, pt->k, sq->d_desc, d_jobs.get(), (uint32_t)w.jobs.size(), d_off.get(), d_koff.get(), sq->d_seqw,
-                             sq->d_nmw, sq->d_has_n, pt->d_slots, pt->nslots, pt->max_probe, d_m.get(), d_n.get());
-    if (e == hipSuccess) e = tm.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&n, d_n.get(), 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && mates_out) e = hipMemcpyAsync(mates_out, d_m.get(), w.nkmers * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+        e = counted_launch(st, w.jobs, &n, 1, ms, [&](const uint2 *jobs, uint32_t njobs, unsigned long long *d_n) {
+            return launch_pos_mates(st, pt->k, sq->d_desc, jobs, njobs, d_off.get(), d_koff.get(), sq->d_seqw, sq->d_nmw, sq->d_has_n,
+                                    pt->d_slots, pt->nslots, pt->max_probe, d_m.get(), d_n);
+        });
+    if (e == hipSuccess && mates_out) {
+        e = hipMemcpyAsync(mates_out, d_m.get(), w.nkmers * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
     if (e != hipSuccess) return fail(PG_E_HIP, "pg_postable_mates: %s", hipGetErrorString(e));
-    tm.read();
     pt->d_mates = d_m.p;
     d_m.p = nullptr;
     pt->nmates = w.nkmers;
@@ -549,51 +515,37 @@ int runs_ok(const char *fn, const uint32_t *run_contig, const uint32_t *run_star
 }
 
 static constexpr uint64_t HIT_MAX_CONTIG = 0xFFFFFFFFull;  // k-mer positions of one streamed contig: a run's exclusive end is a word
-static constexpr uint64_t HIT_MAX_CHUNKS = 0x7FFFFFFFull;  // one block per chunk
 
-// what both hit calls check before anything is launched, and the chunks of the streamed set's k-mer positions
-struct HitWalk {
-    std::vector<uint2> chunks;
-    std::vector<uint64_t> first;  // [n + 1]: the first chunk of every contig
-};
-
-int hit_walk(const pg_postable *pt, const pg_seqset *sq, const char *fn, HitWalk &w) {
+// what both hit calls check before anything is launched, and the chunks of the streamed set's k-mer positions: w.jobs[i] =
+// {contig, first position}, the chunks of contig c being w.first[c] .. w.first[c + 1]
+int hit_walk(const pg_postable *pt, const pg_seqset *sq, const char *fn, KmerWalk &w) {
     if (pt->ctx != sq->ctx) return fail(PG_E_INVALID, "%s: table and seqset belong to different contexts", fn);
     if (pt->overflowed) return fail(PG_E_CAPACITY, "%s: the table overflowed", fn);
     if (!pt->inserted[1]) return fail(PG_E_INVALID, "%s: side 1 (the queries) has not been inserted", fn);
-    w.first.assign((size_t)sq->n + 1, 0);
-    uint64_t nchunks = 0;
-    for (uint32_t c = 0; c < sq->n; ++c) {
-        const uint64_t len = sq->desc[c].len, nk = len >= (uint64_t)pt->k ? len - pt->k + 1 : 0;
-        if (nk > HIT_MAX_CONTIG) return fail(PG_E_INVALID, "%s: contig %u holds more than 2^32 - 1 k-mer positions", fn, c);
-        nchunks += (nk + LOCATE_CHUNK - 1) / LOCATE_CHUNK;
-    }
-    if (nchunks > HIT_MAX_CHUNKS) return fail(PG_E_INVALID, "%s: more than 2^31 - 1 chunks of %u positions", fn, LOCATE_CHUNK);
-    w.chunks.reserve(nchunks);
-    for (uint32_t c = 0; c < sq->n; ++c) {
-        const uint64_t len = sq->desc[c].len, nk = len >= (uint64_t)pt->k ? len - pt->k + 1 : 0;
-        w.first[c] = w.chunks.size();
-        for (uint64_t p = 0; p < nk; p += LOCATE_CHUNK) w.chunks.push_back(make_uint2(c, (uint32_t)p));
-    }
-    w.first[sq->n] = w.chunks.size();
+    w.noun = "chunks";
+    if (int r = walk_kmers(sq, pt->k, LOCATE_CHUNK, fn, w)) return r;
+    for (uint32_t c = 0; c < sq->n; ++c)
+        if ((c + 1 < sq->n ? w.koff[c + 1] : w.nkmers) - w.koff[c] > HIT_MAX_CONTIG)
+            return fail(PG_E_INVALID, "%s: contig %u holds more than 2^32 - 1 k-mer positions", fn, c);
+    for (uint2 &ck : w.jobs) ck.y *= LOCATE_CHUNK;  // (k_hit_runs takes a chunk's first position, below 2^32 behind the check above)
     return PG_OK;
 }
 
 // the hit runs of sq streamed through pt (k_hit_runs): nruns[c], hits[c] (when given), *total_out and *nhits always, the runs as
 // mate_runs_dev leaves them; ms[0] the count launch, ms[1] the emit launch
-int hit_runs_dev(pg_postable *pt, const char *fn, const pg_seqset *sq, const HitWalk &w, const RunsOut &out, uint64_t *nruns,
+int hit_runs_dev(pg_postable *pt, const char *fn, const pg_seqset *sq, const KmerWalk &w, const RunsOut &out, uint64_t *nruns,
                  uint64_t *hits, uint64_t *total_out, uint64_t *nhits, float *ms = nullptr) {
     for (uint32_t c = 0; c < sq->n; ++c) {
         nruns[c] = 0;
         if (hits) hits[c] = 0;
     }
     *total_out = *nhits = 0;
-    if (w.chunks.empty()) return PG_OK;
-    const uint32_t nchunks = (uint32_t)w.chunks.size();
+    if (w.jobs.empty()) return PG_OK;
+    const uint32_t nchunks = (uint32_t)w.jobs.size();
     if (int r = use_device(pt->ctx)) return r;
     hipStream_t st = pt->ctx->stream;
     DevBuf<uint2> d_chunks;
-    const hipError_t e = d_chunks.upload(w.chunks, st);
+    const hipError_t e = d_chunks.upload(w.jobs, st);
     if (e != hipSuccess) {
         hipStreamSynchronize(st);  // (the upload's source is the caller's)
         return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
@@ -676,7 +628,7 @@ extern "C" int pg_synteny_segments(pg_ctx *ctx, int k, const pg_seqset *seqsA, c
     if (seqsA->ctx != ctx || seqsB->ctx != ctx) return fail(PG_E_INVALID, "pg_synteny_segments: a seqset of another context");
     // both sides' limits before anything is launched
     std::vector<uint64_t> nk(seqsA->n);
-    SideWalk a, b;
+    KmerWalk a, b;
     if (int r = walk_side(seqsA, k, "pg_synteny_segments", a)) return r;
     if (int r = walk_side(seqsB, k, "pg_synteny_segments", b)) return r;
     for (uint32_t c = 0; c < seqsA->n; ++c) nk[c] = seqsA->desc[c].len >= (uint64_t)k ? seqsA->desc[c].len - k + 1 : 0;
@@ -756,7 +708,7 @@ extern "C" int pg_synteny_blocks(pg_ctx *ctx, int k, const pg_seqset *seqsA, con
     if (int r = block_params_ok("pg_synteny_blocks", p)) return r;
     // both sides' limits before anything is launched
     std::vector<uint64_t> nk(seqsA->n), per(seqsA->n, 0), lensB(seqsB->n), boff;
-    SideWalk a, b;
+    KmerWalk a, b;
     if (int r = walk_side(seqsA, k, "pg_synteny_blocks", a)) return r;
     if (int r = walk_side(seqsB, k, "pg_synteny_blocks", b)) return r;
     for (uint32_t c = 0; c < seqsA->n; ++c) nk[c] = seqsA->desc[c].len >= (uint64_t)k ? seqsA->desc[c].len - k + 1 : 0;
@@ -807,7 +759,7 @@ extern "C" int pg_run_variants(pg_ctx *ctx, int k, const pg_seqset *seqsA, const
     const BlockParams p{min_run, max_gap, max_shift};
     if (int r = variant_params_ok("pg_run_variants", p)) return r;
     if (nruns > POS_MAX_BASES) return fail(PG_E_INVALID, "pg_run_variants: more than %llu runs", (unsigned long long)POS_MAX_BASES);
-    SideWalk wa, wb;  // (a side of at most 2^31 - 1 bases)
+    KmerWalk wa, wb;  // (a side of at most 2^31 - 1 bases)
     if (int r = walk_side(seqsA, k, "pg_run_variants", wa)) return r;
     if (int r = walk_side(seqsB, k, "pg_run_variants", wb)) return r;
     std::vector<uint64_t> lensB(seqsB->n), boff, per, nblocks(seqsA->n, 0);
@@ -861,7 +813,7 @@ extern "C" int pg_synteny_variants(pg_ctx *ctx, int k, const pg_seqset *seqsA, c
     if (int r = variant_params_ok("pg_synteny_variants", p)) return r;
     // both sides' limits before anything is launched
     std::vector<uint64_t> nk(seqsA->n), per(seqsA->n, 0), perblk(seqsA->n, 0), lensB(seqsB->n), boff;
-    SideWalk a, b;
+    KmerWalk a, b;
     if (int r = walk_side(seqsA, k, "pg_synteny_variants", a)) return r;
     if (int r = walk_side(seqsB, k, "pg_synteny_variants", b)) return r;
     for (uint32_t c = 0; c < seqsA->n; ++c) nk[c] = seqsA->desc[c].len >= (uint64_t)k ? seqsA->desc[c].len - k + 1 : 0;
@@ -906,7 +858,7 @@ extern "C" int pg_postable_hit_runs(pg_postable *pt, const pg_seqset *seqsG, uin
     PG_API_BEGIN
     if (!pt || !seqsG || !nhits || !runs_args_ok(seqsG->n, cap, run_contig, run_start, run_end, run_hit, nruns_per_contig, total))
         return fail(PG_E_INVALID, "pg_postable_hit_runs: NULL argument");
-    HitWalk w;
+    KmerWalk w;
     if (int r = hit_walk(pt, seqsG, "pg_postable_hit_runs", w)) return r;
     std::fill(g_locate_ms, g_locate_ms + 4, 0.0f);
     const RunsOut out{cap, run_contig, run_start, run_end, run_hit, nullptr};
@@ -925,7 +877,7 @@ extern "C" int pg_postable_locate(pg_postable *pt, const pg_seqset *seqsG, const
     const BlockParams p{min_run, max_gap, max_shift};
     if (int r = block_params_ok("pg_postable_locate", p)) return r;
     if (seqsQ->ctx != pt->ctx) return fail(PG_E_INVALID, "pg_postable_locate: table and queries belong to different contexts");
-    HitWalk w;
+    KmerWalk w;
     if (int r = hit_walk(pt, seqsG, "pg_postable_locate", w)) return r;
     // the queries: the set inserted as side 1, whose contigs' offsets the same-contig condition needs
     std::vector<uint64_t> lensQ(seqsQ->n), boff, per(seqsG->n, 0);

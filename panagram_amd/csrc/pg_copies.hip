@@ -14,14 +14,13 @@
 //   track          depth[G][koff[t] + p] = min(d, 65534) as u16, 65535 at an invalid position (koff: the k-mer positions of the
 //                  contigs before t).
 //
-// The table: `nslots` (a power of two, at most 2^31) 8-byte keys, EMPTY_KEY when free (no canonical k-mer, pg_device.h), home slot
-// = sketch_hash(key) & (nslots - 1), linear probing over at most `max_probe` slots — no loop here is unbounded.  Beside the keys,
-// planes of nslots u32 counters: plane g of slot s at planes[g * nslots + s].
-//   k_copy_insert   one launch over (contig, chunk) jobs of the targets, as k_pos_insert walks them.  A lane claims its key by a
-//                   64-bit CAS (EMPTY -> key) or finds it claimed already; a lane that runs out of probes sets ctr[0].  The keys
+// The table: `nslots` (a power of two, at most 2^31) 8-byte keys — a key table, laid out and walked as pg_keytable_dev.h says.
+// Beside the keys, planes of nslots u32 counters: plane g of slot s at planes[g * nslots + s].
+//   k_copy_insert   one launch over (contig, chunk) jobs of the targets, as k_pos_insert walks them.  A lane claims its key's
+//                   slot or finds it claimed already (key_claim); a lane that runs out of probes sets ctr[0].  The keys
 //                   newly claimed are counted: a ballot per wave, one atomic per block (ctr[1]).
-//   k_copy_count    the same walk over a whole genome, the table read-only: a valid window probes until EMPTY_KEY (its key is no
-//                   target's: nothing to do) or its key, and adds 1 to the plane's counter of that slot.  Integer atomic adds:
+//   k_copy_count    the same walk over a whole genome, the table read-only: a valid window looks its key up (no target's key:
+//                   nothing to do) and adds 1 to the plane's counter of its slot.  Integer atomic adds:
 //                   the result is exact whatever order and contention.  Equal slots are folded inside a wave first, in up to
 //                   COPY_FOLD_TURNS turns: the first lane with a hit takes every lane that has its slot — a homopolymer puts all 64
 //                   on one, a satellite of period p on at most p — and adds their number in ONE atomic; a turn that finds its lane
@@ -37,7 +36,7 @@
 //                   depths to the track when one is asked for.  The host sums a contig's chunks (pg_copies_host.h).
 // Every write to HBM is a vector store or a vector atomic.
 #include "pg_kernels.h"
-#include "pg_copies_dev.h"
+#include "pg_keytable_dev.h"  // the walk, copy_key, copy_lookup and the slot marks
 
 namespace pg {
 
@@ -50,65 +49,35 @@ __global__ __launch_bounds__(256) void k_copy_insert(int k, const SeqDesc *__res
                                                      const uint64_t *seqw_all, const uint32_t *nmw_all, const uint32_t *has_n,
                                                      unsigned long long *keys, uint64_t nslots, uint32_t max_probe,
                                                      unsigned long long *ctr) {
-    __shared__ uint32_t wsum[4];
     const uint2 job = jobs[blockIdx.x];
-    const SeqDesc d = sd[job.x];
-    const uint64_t nkmers = d.len - (uint64_t)k + 1, p0 = (uint64_t)job.y * COPIES_JOB, p1 = min(nkmers, p0 + COPIES_JOB);
-    const uint64_t *seqw = seqw_all + d.seq_off;
-    const uint32_t *nmw = nmw_all + d.seq_off;
-    const bool hasn = has_n[job.x] != 0;
+    const ContigView v = contig_view(sd, job.x, seqw_all, nmw_all, has_n, k);
+    const uint64_t p0 = (uint64_t)job.y * COPIES_JOB, p1 = min(v.nkmers, p0 + COPIES_JOB);
     const uint64_t smask = nslots - 1;
     uint32_t nclaimed = 0;  // (per wave: every lane of a wave holds the same sum)
     for (uint64_t q = p0; q < p1; q += 256) {  // (bounds uniform over the block: every lane reaches the ballot)
         const uint64_t p = q + threadIdx.x;
         bool claimed = false;
-        if (p < p1 && !(hasn && extract_nmask(nmw, p, k))) {
-            const uint64_t key = copy_key(seqw, p, k);
-            uint64_t s = sketch_hash(key) & smask;
-            bool done = false;
-            for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
-                unsigned long long cur = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == EMPTY_KEY) {
-                    cur = atomicCAS(&keys[s], (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-                    if (cur == EMPTY_KEY) {
-                        claimed = true;
-                        cur = key;
-                    }
-                }
-                if (cur != key) continue;
-                done = true;
-                break;
-            }
-            if (!done) atomicOr(reinterpret_cast<unsigned int *>(ctr), 1u);
-        }
+        if (p < p1 && window_valid(v, p, k) && key_claim(keys, smask, max_probe, copy_key(v.seqw, p, k), claimed) == KEY_ABSENT)
+            atomicOr(reinterpret_cast<unsigned int *>(ctr), 1u);
         nclaimed += (uint32_t)__popcll(__ballot(claimed));
     }
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = nclaimed;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (n) atomicAdd(ctr + 1, (unsigned long long)n);
-    }
+    block_add(nclaimed, ctr + 1);
 }
 
 __global__ __launch_bounds__(256) void k_copy_count(int k, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ jobs,
                                                     const uint64_t *seqw_all, const uint32_t *nmw_all, const uint32_t *has_n,
                                                     const unsigned long long *__restrict__ keys, uint64_t nslots, uint32_t max_probe,
                                                     uint32_t *plane, unsigned long long *hits) {
-    __shared__ uint32_t wsum[4];
     const uint32_t lane = threadIdx.x & 63;
     const uint2 job = jobs[blockIdx.x];
-    const SeqDesc d = sd[job.x];
-    const uint64_t nkmers = d.len - (uint64_t)k + 1, p0 = (uint64_t)job.y * COPIES_JOB, p1 = min(nkmers, p0 + COPIES_JOB);
-    const uint64_t *seqw = seqw_all + d.seq_off;
-    const uint32_t *nmw = nmw_all + d.seq_off;
-    const bool hasn = has_n[job.x] != 0;
+    const ContigView v = contig_view(sd, job.x, seqw_all, nmw_all, has_n, k);
+    const uint64_t p0 = (uint64_t)job.y * COPIES_JOB, p1 = min(v.nkmers, p0 + COPIES_JOB);
     const uint64_t smask = nslots - 1;
     uint32_t found = 0;  // (per wave)
     for (uint64_t q = p0; q < p1; q += 256) {  // (bounds uniform over the block)
         const uint64_t p = q + threadIdx.x;
         uint32_t slot = SLOT_ABSENT;
-        if (p < p1 && !(hasn && extract_nmask(nmw, p, k))) slot = copy_lookup(keys, smask, max_probe, copy_key(seqw, p, k));
+        if (p < p1 && window_valid(v, p, k)) slot = copy_lookup(keys, smask, max_probe, copy_key(v.seqw, p, k));
         const bool hit = slot != SLOT_ABSENT;
         const uint64_t hm = __ballot(hit);
         found += (uint32_t)__popcll(hm);
@@ -127,12 +96,7 @@ __global__ __launch_bounds__(256) void k_copy_count(int k, const SeqDesc *__rest
         }
         if ((todo >> lane) & 1ull) atomicAdd(&plane[slot], 1u);
     }
-    if (lane == 0) wsum[threadIdx.x >> 6] = found;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (n) atomicAdd(hits, (unsigned long long)n);
-    }
+    block_add(found, hits);
 }
 
 // chunk = positions [y * COPIES_CHUNK, (y + 1) * COPIES_CHUNK) of contig x, which holds at least k bases
@@ -148,18 +112,15 @@ __global__ __launch_bounds__(256) void k_copy_profile(int k, const SeqDesc *__re
     __shared__ uint32_t wvalid[4];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint2 ck = chunks[blockIdx.x];
-    const SeqDesc d = sd[ck.x];
-    const uint64_t nkmers = d.len - (uint64_t)k + 1, c0 = (uint64_t)ck.y * COPIES_CHUNK, ce = min(nkmers, c0 + COPIES_CHUNK);
-    const uint64_t *seqw = seqw_all + d.seq_off;
-    const uint32_t *nmw = nmw_all + d.seq_off;
-    const bool hasn = has_n[ck.x] != 0;
+    const ContigView v = contig_view(sd, ck.x, seqw_all, nmw_all, has_n, k);
+    const uint64_t c0 = (uint64_t)ck.y * COPIES_CHUNK, ce = min(v.nkmers, c0 + COPIES_CHUNK);
     const uint64_t smask = nslots - 1;
     // the slots: entry i of the chunk is written and read by thread i & 255 alone
     uint32_t nvalid = 0;  // (per wave)
     for (uint32_t i = tid; i < COPIES_CHUNK; i += 256) {
         const uint64_t p = c0 + i;
         uint32_t s = SLOT_INVALID;
-        if (p < ce && !(hasn && extract_nmask(nmw, p, k))) s = copy_lookup(keys, smask, max_probe, copy_key(seqw, p, k));
+        if (p < ce && window_valid(v, p, k)) s = copy_lookup(keys, smask, max_probe, copy_key(v.seqw, p, k));
         slot[i] = s;
         nvalid += (uint32_t)__popcll(__ballot(s != SLOT_INVALID));
     }

@@ -12,6 +12,7 @@
 // complex -ocsum (workflow/Snakefile:54-110, index.py:407-426) and CKMCFile::OpenForRA /
 // GetCountersForRead (cpp/anchor.cpp:28-31,148; index.py:855-860,934-935).
 #include "pg_kernels.h"
+#include "pg_keytable_dev.h"  // ContigView (k_sketch_set)
 
 namespace pg {
 
@@ -275,14 +276,11 @@ __global__ __launch_bounds__(256) void k_sketch_set(int k, const SeqDesc *__rest
                                                     const uint64_t *seqw_all, const uint32_t *nmw_all, const uint32_t *has_n,
                                                     uint32_t *regs) {
     const uint2 job = jobs[blockIdx.x];
-    const SeqDesc d = sd[job.x];
-    const uint64_t nkmers = d.len - (uint64_t)k + 1, p0 = (uint64_t)job.y * SKETCH_JOB, p1 = min(nkmers, p0 + SKETCH_JOB);
-    const uint64_t *seqw = seqw_all + d.seq_off;
-    const uint32_t *nmw = nmw_all + d.seq_off;
-    const bool hasn = has_n[job.x] != 0;
+    const ContigView v = contig_view(sd, job.x, seqw_all, nmw_all, has_n, k);
+    const uint64_t p0 = (uint64_t)job.y * SKETCH_JOB, p1 = min(v.nkmers, p0 + SKETCH_JOB);
     for (uint64_t p = p0 + threadIdx.x; p < p1; p += 256) {
-        if (hasn && extract_nmask(nmw, p, k)) continue;
-        const uint64_t h = sketch_hash(canonical_from_le(extract_bases(seqw, p), k));
+        if (!window_valid(v, p, k)) continue;
+        const uint64_t h = sketch_hash(canonical_from_le(extract_bases(v.seqw, p), k));
         const uint32_t idx = (uint32_t)(h >> (64 - SKETCH_BITS));
         const uint64_t rest = h << SKETCH_BITS;
         const uint32_t rho = rest ? (uint32_t)__clzll((long long)rest) + 1u : (65u - SKETCH_BITS);

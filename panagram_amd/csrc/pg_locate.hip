@@ -20,24 +20,27 @@
 //               count (EMIT = false): counts[chunk] = {hits, starts, ends, 0}; the host takes exclusive scans.
 //               emit: starts and ends are numbered separately (the i-th start and the i-th end of a contig are one run), so the
 //               output is sorted by (contig, start) by construction and the same on every call.
-// Both passes probe: the table is only read, so both see the same words.  A lane walks at most max_probe slots and then has no
-// hit (an insert that walked as far failed, and the host refuses such a table): no loop here is unbounded.  No atomics; every
-// write to HBM is a vector store.
+// Both passes probe: the table is only read, so both see the same words.  The table's policy stands in pg_keytable_dev.h; the
+// walk here is key_find's, kept as a copy of its own in hit_word for its speed.  No atomics; every write to HBM is a vector store.
 #include "pg_kernels.h"
 
-#include "pg_postable_dev.h"  // PosSlot, kmer_key_rc, mate_continues
+#include "pg_postable_dev.h"  // PosSlot, kmer_key_rc, mate_continues; with it pg_keytable_dev.h
 
 namespace pg {
 
 constexpr uint32_t LOCATE_TILE = 256;
 static_assert(LOCATE_CHUNK % LOCATE_TILE == 0, "a chunk is a whole number of tiles");
 
-// the hit word of position p of a contig (p below its k-mer positions)
-__device__ __forceinline__ uint32_t hit_word(int k, const uint64_t *seqw, const uint32_t *nmw, bool hasn, uint64_t p,
-                                             const PosSlot *__restrict__ slots, uint64_t smask, uint32_t max_probe) {
-    if (hasn && extract_nmask(nmw, p, k)) return NO_MATE;
+// the hit word of position p of a contig (p below its k-mer positions).  (The view by value: by reference the kernel comes out
+// a few instructions different.)
+__device__ __forceinline__ uint32_t hit_word(int k, const ContigView v, uint64_t p, const PosSlot *__restrict__ slots, uint64_t smask,
+                                             uint32_t max_probe) {
+    if (!window_valid(v, p, k)) return NO_MATE;
     uint64_t key;
-    const uint32_t rc = kmer_key_rc(seqw, p, k, key) ? 1u : 0u;
+    const uint32_t rc = kmer_key_rc(v.seqw, p, k, key) ? 1u : 0u;
+    // key_find's walk (pg_keytable_dev.h), written out: through key_find this kernel was up to 2 % slower on the MI355X, whether the
+    // word was read behind the walk or handed back by it (profiles/keytable_ab.txt); as it stands here its assembly is what it was.
+    // A change to the table's policy comes here too.
     uint64_t s = sketch_hash(key) & smask;
     for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
         const unsigned long long cur = slots[s].key;
@@ -62,15 +65,12 @@ __global__ __launch_bounds__(256) void k_hit_runs(int k, const SeqDesc *__restri
     __shared__ uint32_t tailh;     // the hit word of the chunk's last position
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint2 ck = chunks[blockIdx.x];
-    const SeqDesc d = sd[ck.x];
-    const uint64_t *seqw = seqw_all + d.seq_off;
-    const uint32_t *nmw = nmw_all + d.seq_off;
-    const bool hasn = has_n[ck.x] != 0;
+    const ContigView v = contig_view(sd, ck.x, seqw_all, nmw_all, has_n, k);
     const uint64_t smask = nslots - 1;
     // this chunk: positions [c0, ce), 0 <= c0 < ce <= nk <= 2^32 - 1 (64-bit: c0 + LOCATE_CHUNK may pass 2^32)
-    const uint64_t nk = d.len - (uint64_t)k + 1, c0 = ck.y, ce = min(c0 + LOCATE_CHUNK, nk);
+    const uint64_t nk = v.nkmers, c0 = ck.y, ce = min(c0 + LOCATE_CHUNK, nk);
     // the chunk's halo: the hit word of position c0 - 1 (every lane the same probe: broadcast loads)
-    uint32_t carry = c0 > 0 ? hit_word(k, seqw, nmw, hasn, c0 - 1, slots, smask, max_probe) : NO_MATE;
+    uint32_t carry = c0 > 0 ? hit_word(k, v, c0 - 1, slots, smask, max_probe) : NO_MATE;
     uint32_t nhits = 0, nstarts = 0, nends = 0;
     uint64_t soff = 0, eoff = 0;
     if (EMIT) {
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_hit_runs(int k, const SeqDesc *__restri
     for (uint64_t t0 = c0; t0 < ce; t0 += LOCATE_TILE) {  // (bounds uniform over the block: every lane reaches the barriers)
         const uint64_t j = t0 + tid;
         const bool act = j < ce;
-        const uint32_t h = act ? hit_word(k, seqw, nmw, hasn, j, slots, smask, max_probe) : NO_MATE;
+        const uint32_t h = act ? hit_word(k, v, j, slots, smask, max_probe) : NO_MATE;
         if (lane == 63) lasth[wave] = h;
         if (j == ce - 1) tailh = h;
         __syncthreads();

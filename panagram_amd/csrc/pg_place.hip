@@ -16,7 +16,7 @@
 //
 // Windows and chunks as in pg_profile.hip: the host cuts a window into chunks of PLACE_CHUNK consecutive rows (chunk = {window,
 // first row}), grid = chunks (of all windows), 256 threads; a block takes its chunk tile by tile (256 rows, one per lane).
-//   lookup     a lane resolves its position's validity (extract_nmask), key and slot (copy_key, copy_lookup: pg_copies_dev.h) and
+//   lookup     a lane resolves its position's validity (window_valid), key and slot (copy_key, copy_lookup: pg_keytable_dev.h) and
 //              reads the plane's counter: the ballot of valid & s over the wave IS the 64-row sample word.
 //   transpose  as k_presence_profile: the lane loads its row (pg_rowread.h; an invalid row reads as zeros), the ballot of bit c is
 //              the 64-row word of column c (pairs_ballot_word), the four waves leave their words — and their sample words — in
@@ -28,7 +28,7 @@
 // N <= 128 (k_sample_agree<4, 1>): a lane loads its row's words once, into registers, before the ballots; beyond, up to
 // PROFILE_MAX_GENOMES, word by word (<0, 1> up to 256 columns, <0, 2> two columns per thread).
 #include "pg_kernels.h"
-#include "pg_copies_dev.h"
+#include "pg_keytable_dev.h"
 #include "pg_rowread.h"
 #include "pg_pairblocks.h"
 
@@ -56,11 +56,7 @@ __global__ __launch_bounds__(256) void k_sample_agree(uint32_t N, int k, const u
     const uint32_t win = ck.x;
     const uint8_t *crow = rows + base[win];
     const uint64_t c0 = ck.y, ce = min(c0 + (uint64_t)PLACE_CHUNK, ends[win]);  // this chunk: rows [c0, ce), c0 < ce
-    const uint32_t contig = wcontig[win];
-    const SeqDesc d = sd[contig];
-    const uint64_t *seqw = seqw_all + d.seq_off;
-    const uint32_t *nmw = nmw_all + d.seq_off;
-    const bool hasn = has_n[contig] != 0;
+    const ContigView v = contig_view(sd, wcontig[win], seqw_all, nmw_all, has_n, k);
     const uint64_t smask = nslots - 1;
     uint32_t col[NQ], both[NQ];
 #pragma unroll
@@ -69,10 +65,10 @@ __global__ __launch_bounds__(256) void k_sample_agree(uint32_t N, int k, const u
     uint32_t buf = 0;
     for (uint64_t t0 = c0; t0 < ce; t0 += PLACE_TILE, buf ^= 1) {
         const uint64_t j = t0 + tid;
-        const bool valid = j < ce && !(hasn && extract_nmask(nmw, j, k));
+        const bool valid = j < ce && window_valid(v, j, k);
         bool s = false;
         if (valid) {
-            const uint32_t slot = copy_lookup(keys, smask, max_probe, copy_key(seqw, j, k));
+            const uint32_t slot = copy_lookup(keys, smask, max_probe, copy_key(v.seqw, j, k));
             s = slot != SLOT_ABSENT && plane[slot] >= min_count;
         }
         const uint64_t sword = __ballot(s);

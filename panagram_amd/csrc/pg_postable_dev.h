@@ -1,7 +1,8 @@
 // pg_postable_dev.h — what the kernels on a position table share: the slot, the canonical key with its strand bit, and the rule by
-// which a word continues its predecessor's run (k_mate_runs in pg_synteny.hip, k_hit_runs in pg_locate.hip).  Device code only.
+// which a word continues its predecessor's run (k_mate_runs in pg_synteny.hip, k_hit_runs in pg_locate.hip).  How the table is
+// walked: pg_keytable_dev.h.  Device code only.
 #pragma once
-#include "pg_kernels.h"
+#include "pg_keytable_dev.h"
 
 namespace pg {
 
@@ -10,6 +11,7 @@ struct PosSlot {
     uint32_t word[2];
 };
 static_assert(sizeof(PosSlot) == POS_SLOT_BYTES, "16-byte slots");
+__device__ __forceinline__ const unsigned long long &slot_key(const PosSlot &slot) { return slot.key; }
 
 // X > B: the reverse complement's value is the smaller one
 __device__ __forceinline__ bool kmer_key_rc(const uint64_t *seqw, uint64_t p, int k, uint64_t &key) {

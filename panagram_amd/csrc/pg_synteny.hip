@@ -14,10 +14,9 @@
 //              posB advances by +1 per position on strand 0, by -1 on strand 1: mate[j] == mate[j - 1] + 2 / - 2.
 //
 // The table: `slots` (a power of two) 16-byte slots {u64 key, u32 word of side 0, u32 word of side 1}, all bytes 0xFF when empty
-// (EMPTY_KEY is no canonical k-mer, pg_device.h).  Home slot = sketch_hash(key) & (slots - 1), linear probing, at most
-// `max_probe` slots: reaching the bound sets flags[0] and the lane gives up — no loop here is unbounded.
-//   k_pos_insert   one launch per side over (contig, chunk) jobs as k_sketch_set.  A lane claims its key by a 64-bit CAS
-//                  (EMPTY -> key) and then  old = atomicCAS(&word[side], POS_EMPTY, mine): old a position -> the field becomes
+// — a key table, laid out and walked as pg_keytable_dev.h says: a lane whose claim reaches the bound sets flags[0] and gives up.
+//   k_pos_insert   one launch per side over (contig, chunk) jobs as k_sketch_set.  A lane claims its key's slot (key_claim)
+//                  and then  old = atomicCAS(&word[side], POS_EMPTY, mine): old a position -> the field becomes
 //                  POS_MULTI.  A field only ever goes EMPTY -> word -> MULTI, whoever comes first: after the launch it holds
 //                  the single occurrence's word or MULTI, whatever the order the lanes ran in.
 //   k_pos_mates    the same walk over A; mates[koff[c] + p] for k-mer position p of contig c (contigs back to back), and the
@@ -32,7 +31,7 @@
 // Every write to HBM is a vector store or a vector atomic.
 #include "pg_kernels.h"
 
-#include "pg_postable_dev.h"  // PosSlot, kmer_key_rc, mate_continues
+#include "pg_postable_dev.h"  // PosSlot, kmer_key_rc, mate_continues; with it pg_keytable_dev.h
 
 namespace pg {
 
@@ -45,33 +44,23 @@ __global__ __launch_bounds__(256) void k_pos_insert(int k, uint32_t side, const 
                                                     const uint32_t *has_n, PosSlot *slots, uint64_t nslots, uint32_t max_probe,
                                                     unsigned long long *flags) {
     const uint2 job = jobs[blockIdx.x];
-    const SeqDesc d = sd[job.x];
-    const uint64_t nkmers = d.len - (uint64_t)k + 1, p0 = (uint64_t)job.y * SYNTENY_JOB, p1 = min(nkmers, p0 + SYNTENY_JOB);
-    const uint64_t *seqw = seqw_all + d.seq_off;
-    const uint32_t *nmw = nmw_all + d.seq_off;
-    const bool hasn = has_n[job.x] != 0;
+    const ContigView v = contig_view(sd, job.x, seqw_all, nmw_all, has_n, k);
+    const uint64_t p0 = (uint64_t)job.y * SYNTENY_JOB, p1 = min(v.nkmers, p0 + SYNTENY_JOB);
     const uint32_t base = off[job.x];
     const uint64_t smask = nslots - 1;
     for (uint64_t p = p0 + threadIdx.x; p < p1; p += 256) {
-        if (hasn && extract_nmask(nmw, p, k)) continue;
+        if (!window_valid(v, p, k)) continue;
         uint64_t key;
-        const uint32_t rc = kmer_key_rc(seqw, p, k, key) ? 1u : 0u;
+        const uint32_t rc = kmer_key_rc(v.seqw, p, k, key) ? 1u : 0u;
         const uint32_t mine = ((base + (uint32_t)p) << 1) | rc;
-        uint64_t s = sketch_hash(key) & smask;
-        bool done = false;
-        for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
-            unsigned long long cur = __hip_atomic_load(&slots[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == EMPTY_KEY) {
-                cur = atomicCAS(&slots[s].key, (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-                if (cur == EMPTY_KEY) cur = key;
-            }
-            if (cur != key) continue;
-            const uint32_t old = atomicCAS(&slots[s].word[side], POS_EMPTY, mine);
-            if (old != POS_EMPTY && old != POS_MULTI) atomicExch(&slots[s].word[side], POS_MULTI);
-            done = true;
-            break;
+        bool claimed;
+        const uint64_t s = key_claim(slots, smask, max_probe, key, claimed);
+        if (s == KEY_ABSENT) {
+            atomicOr(reinterpret_cast<unsigned int *>(flags), 1u);
+            continue;
         }
-        if (!done) atomicOr(reinterpret_cast<unsigned int *>(flags), 1u);
+        const uint32_t old = atomicCAS(&slots[s].word[side], POS_EMPTY, mine);
+        if (old != POS_EMPTY && old != POS_MULTI) atomicExch(&slots[s].word[side], POS_MULTI);
     }
 }
 
@@ -80,13 +69,9 @@ __global__ __launch_bounds__(256) void k_pos_mates(int k, const SeqDesc *__restr
                                                    const uint64_t *seqw_all, const uint32_t *nmw_all, const uint32_t *has_n,
                                                    const PosSlot *slots, uint64_t nslots, uint32_t max_probe,
                                                    uint32_t *__restrict__ mates, unsigned long long *nmated) {
-    __shared__ uint32_t wsum[4];
     const uint2 job = jobs[blockIdx.x];
-    const SeqDesc d = sd[job.x];
-    const uint64_t nkmers = d.len - (uint64_t)k + 1, p0 = (uint64_t)job.y * SYNTENY_JOB, p1 = min(nkmers, p0 + SYNTENY_JOB);
-    const uint64_t *seqw = seqw_all + d.seq_off;
-    const uint32_t *nmw = nmw_all + d.seq_off;
-    const bool hasn = has_n[job.x] != 0;
+    const ContigView v = contig_view(sd, job.x, seqw_all, nmw_all, has_n, k);
+    const uint64_t p0 = (uint64_t)job.y * SYNTENY_JOB, p1 = min(v.nkmers, p0 + SYNTENY_JOB);
     const uint32_t base = off[job.x];
     uint32_t *out = mates + koff[job.x];
     const uint64_t smask = nslots - 1;
@@ -94,30 +79,21 @@ __global__ __launch_bounds__(256) void k_pos_mates(int k, const SeqDesc *__restr
     for (uint64_t q = p0; q < p1; q += 256) {  // (bounds uniform over the block: every lane reaches the ballot)
         const uint64_t p = q + threadIdx.x;
         uint32_t mate = NO_MATE;
-        if (p < p1 && !(hasn && extract_nmask(nmw, p, k))) {
+        if (p < p1 && window_valid(v, p, k)) {
             uint64_t key;
-            const uint32_t rc = kmer_key_rc(seqw, p, k, key) ? 1u : 0u;
+            const uint32_t rc = kmer_key_rc(v.seqw, p, k, key) ? 1u : 0u;
             const uint32_t mine = ((base + (uint32_t)p) << 1) | rc;
-            uint64_t s = sketch_hash(key) & smask;
-            for (uint32_t probes = 0; probes < max_probe; ++probes, s = (s + 1) & smask) {
-                const unsigned long long cur = slots[s].key;
-                if (cur == EMPTY_KEY) break;
-                if (cur != key) continue;
+            PosSlot hit;
+            if (key_find(slots, smask, max_probe, key, KEY_ABSENT, &hit) != KEY_ABSENT) {
                 // unique in A: the field of side 0 is this very position; unique in B: the field of side 1 is a position
-                const uint32_t a = slots[s].word[0], b = slots[s].word[1];
+                const uint32_t a = hit.word[0], b = hit.word[1];
                 if (a == mine && b != POS_EMPTY && b != POS_MULTI) mate = b ^ rc;
-                break;
             }
         }
         if (p < p1) out[p] = mate;
         found += (uint32_t)__popcll(__ballot(mate != NO_MATE));
     }
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = found;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (n) atomicAdd(nmated, (unsigned long long)n);
-    }
+    block_add(found, nmated);
 }
 
 // contigs[c] = {first entry of contig c in mates, its k-mer positions}; chunk = {contig, first position}

@@ -1453,10 +1453,7 @@ class Index:
             try:
                 if list(tss.names) != [tnames[t] for t in at] or not np.array_equal(np.asarray(tss.lens, np.int64), tlens[at]):
                     raise RuntimeError("copies: the targets were read differently on the host and on the GPU")
-                slots = 2
-                while slots < 2 * total:
-                    slots *= 2
-                per = cp.planes_for(self.context.mem_info()[0], slots, ng, total if track else 0)
+                per = cp.planes_for(self.context.mem_info()[0], cp.table_slots(total), ng, total if track else 0)
                 table = engine.CopyTable(self.context, k, total, per)
                 table.insert(tss)
                 for g0 in range(0, ng, per):
@@ -2078,14 +2075,12 @@ class Genome:
     def _place_batches(self, chroms: List[str]) -> List[List[str]]:
         """``_annotate_batches`` under ``place_budget``, each run cut further so that a batch has at most PLACE_MAX_POSITIONS k-mer
         positions and its count table (8-byte keys and one 4-byte plane per slot) and rows fit the free memory"""
+        from .copies import table_slots
         free = self.index.context.mem_info()[0]
         nb = self.nbytes
 
         def cost(pos: int) -> int:
-            slots = 2
-            while slots < 2 * pos:
-                slots *= 2
-            return slots * 12 + pos * nb
+            return table_slots(pos) * 12 + pos * nb
         out = []
         for run in self._annotate_batches(chroms, self.place_budget):
             cur, pos = [], 0

@@ -242,6 +242,20 @@ def small_cases():
     return cases
 
 
+def wrap_cases():
+    """eight (k, q, g): two queries of 12 and 20 k-mer positions, 32 distinct keys — a table made for them has 64 slots and is half
+    full, and over eight key sets a key whose home is one of the last slots walks on at slot 0.  The genome holds each query forward
+    and reverse-complemented between random flanks."""
+    k, cases = 21, []
+    for seed in range(8):
+        rng = np.random.default_rng(100 + seed)
+        q = [_rand(rng, 12 + k - 1), _rand(rng, 20 + k - 1)]
+        g = [_rand(rng, 50) + q[0] + _rand(rng, 31) + revcomp(q[1]) + _rand(rng, 40), _rand(rng, 9) + revcomp(q[0]) + _rand(rng, 64) + q[1]]
+        assert unique_per_query(q, k).tolist() == [12, 20]  # (every position's key is held once: 32 distinct keys)
+        cases.append((k, q, g))
+    return cases
+
+
 # ---------------------------------------------------------------------------
 # three small genomes with planted genes, shared by tests/test_locate_cpu.py and tests/test_gpu_locate_e2e.py
 # ---------------------------------------------------------------------------

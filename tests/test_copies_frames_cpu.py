@@ -129,6 +129,11 @@ def test_planes_for():
     assert cp.planes_for(1 << 30, 1 << 20, 100, track_kmers=1 << 28) == 1
 
 
+def test_table_slots():
+    """the power of two at or above twice the capacity, as pg_copytable_create and pg_postable_create size their tables"""
+    assert [cp.table_slots(c) for c in (1, 2, 3, 1 << 30)] == [2, 4, 8, 1 << 31]
+
+
 @pytest.mark.parametrize("argv", [["copies", "idx"], ["copies", "idx", "t.fa", "--genes", "G"]])
 def test_cli_wants_exactly_one_of_targets_and_genes(argv, capsys):
     from panagram_amd.__main__ import main

@@ -77,16 +77,17 @@ def test_the_queries_against_their_own_table_give_unique(crafted):
     _same_runs(got, *lr.hit_runs(crafted.q, crafted.q, crafted.k))
 
 
-@pytest.mark.parametrize("name", ["k6", "k31", "k32", "1025 queries"])
+@pytest.mark.parametrize("name", ["k6", "k31", "k32", "1025 queries", "64 slots"])
 def test_small_cases(ctx, name):
-    k, q, g = lr.small_cases()[name]
-    case = Case(ctx, k, q, g)
-    try:
-        _same_runs(case.pt.hit_runs(case.gs), case.runs, case.per, case.hits, name)
-        _same_blocks(case.pt.locate(case.gs, case.qs), lr.blocks(g, q, k), name)
-        assert np.array_equal(case.pt.hit_runs(case.qs)[5].astype(np.int64), lr.unique_per_query(q, k)), name
-    finally:
-        case.close()
+    """"64 slots": eight sets of 32 keys in a table made for 32 — the walk passes the table's end (lr.wrap_cases)"""
+    for k, q, g in (lr.wrap_cases() if name == "64 slots" else [lr.small_cases()[name]]):
+        case = Case(ctx, k, q, g, capacity=32 if name == "64 slots" else None)
+        try:
+            _same_runs(case.pt.hit_runs(case.gs), case.runs, case.per, case.hits, name)
+            _same_blocks(case.pt.locate(case.gs, case.qs), lr.blocks(g, q, k), name)
+            assert np.array_equal(case.pt.hit_runs(case.qs)[5].astype(np.int64), lr.unique_per_query(q, k)), name
+        finally:
+            case.close()
 
 
 def test_capacity_protocol(crafted):

@@ -265,6 +265,18 @@ def test_table_at_its_minimum_size_with_clustered_keys(ctx):
     for cap in (6000 - k + 1 + 5000 - k + 1, 8192, 8193):
         _check_mates(ctx, a, b, k, capacity=cap, tag=cap)
     _check_mates(ctx, a, a, k, capacity=2 * (6000 - k + 1))
+    # 32 distinct keys in 64 slots, eight sets of them: a key whose home is one of the last slots walks on at slot 0, in the
+    # insert of either side and in the lookup.  Against itself (every position mated, strand +) and its reverse complement (strand -)
+    for seed in range(8):
+        codes = sr.random_codes(32 + k - 1, 100 + seed)
+        s, rc = sr.ascii_of(codes), sr.ascii_of(sr.revcomp(codes))
+        assert len(np.unique(sr.side_kmers([s], k)[0])) == 32, seed
+        for other in (s, rc):
+            want = _check_mates(ctx, [s], [other], k, capacity=32, tag=("64 slots", seed, other is rc))
+            assert (want != NO).all() and (want & 1 == (other is rc)).all(), seed
+    # capacity 1: two slots, one key — the homopolymer's, held ten times by each side: no mate
+    want = _check_mates(ctx, [b"A" * 30], [b"A" * 30], k, capacity=1, tag="two slots")
+    assert len(want) == 10 and (want == NO).all()
 
 
 def test_capacity_too_small_is_an_error_code(ctx):

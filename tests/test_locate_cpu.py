@@ -102,6 +102,12 @@ def test_small_cases_against_the_dict_search():
     assert len(q) == 1025 and per.tolist() == [5, 1, 0]
     assert (runs[:, 3] >> 1).tolist() == [0, 511 * 40, 512 * 40, 1023 * 40, 1024 * 40, 700 * 40 + 19]
     assert lr.unique_per_query(q, k).tolist() == [20] * 1025
+    # the eight key sets of a 64-slot table: every position of both queries is hit on both strands, two runs each
+    for seed, (k, q, g) in enumerate(lr.wrap_cases()):
+        words, nk = lr.hit_words(g, q, k)
+        assert np.array_equal(words, brute_hit_words(g, q, k)), seed
+        runs, per, hits = lr.hit_runs(g, q, k)
+        assert per.tolist() == [2, 2] and hits.tolist() == [32, 32] and sorted(runs[:, 3] & 1) == [0, 0, 1, 1], seed
 
 
 @pytest.fixture(scope="module")

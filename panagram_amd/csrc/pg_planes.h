@@ -11,7 +11,11 @@
 // who keep it beside the planes of their words): odd4 / odd8 below.
 //
 // The integer part compiles as plain C++ as well (tools/planes_check.cpp); the two ways to empty the planes into a
-// workgroup's LDS column counters — the wave exchange and the per-lane adds — are device code.
+// workgroup's LDS column counters — the wave exchange and the per-lane adds — are device code.  The kernels' flushes in the
+// MIDDLE of a contig (after PLANES_FLUSH rows of a thread; k_epilogue_w: once another group would pass PLANES_CEIL, at 248 or
+// 252 rows with carries held back) run in the suite on the device: tests/test_gpu_planes_flush.py bounds the statistics
+// launch to one and two workgroups (PG_EPI_WORKGROUPS, pg_rows.hip), so that contigs of 1.4 x 10^5 rows reach them at every row
+// width; tests/epi_walk.py states which thread meets which flush.
 #pragma once
 #include <stdint.h>
 

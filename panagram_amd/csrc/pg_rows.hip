@@ -20,6 +20,7 @@
 //                (FuseArgs, pg_kernels.h) into the bins and column sums.
 #include "pg_kernels.h"
 #include "pg_planes.h"
+#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -1678,8 +1679,21 @@ hipError_t launch_rows_epilogue(hipStream_t st, uint32_t ngenomes, const AnchorD
         }
         if (grid > it->second) grid = it->second;
     };
+    // A TEST SWITCH, PG_EPI_WORKGROUPS=n in the environment (read at every launch, so that one process can run both shapes): no
+    // more than n >= 1 workgroups.  The formula above gives a workgroup about 16 tiles until a launch holds more than 16 384 of
+    // them, so the kernels' flushes of the counter planes in the middle of a contig (60 tiles of one contig in one workgroup for
+    // rows of 2..16 bytes, 30 for 17..32) need 6 x 10^7 rows in one launch; under a bound of 1 or 2 a contig of 1.4 x 10^5 rows
+    // reaches them (tests/test_gpu_planes_flush.py, tests/epi_walk.py).  Unset or empty: the shape above, untouched.  With tile
+    // ranges every range still gets max(1, grid / nranges) workgroups.
+    auto bound = [&]() {
+        const char *e = getenv("PG_EPI_WORKGROUPS");
+        if (!e || !*e) return;
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        grid = std::min(grid, (uint32_t)std::min<unsigned long long>(std::max(v, 1ull), maxg));
+    };
     auto launch = [&](decltype(&k_epilogue_b1) kern, size_t lds_bytes) {
         fit(reinterpret_cast<const void *>(kern), lds_bytes);
+        bound();
         per_range();
         hipLaunchKernelGGL(kern, dim3(grid), dim3(EPI_THREADS), lds_bytes, st, ngenomes, ad, tile_contig, ntiles, out1, out100, bins,
                            colsums, flags, d_ranges, wpr);

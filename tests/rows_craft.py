@@ -223,15 +223,20 @@ def classes(rows, n, keep_words, starts=None, ends=None, stride=1):
 # ---------------------------------------------------------------------------
 # the planted cases, shared by the CPU test that checks their coverage and the GPU tests that run them
 # ---------------------------------------------------------------------------
-# row widths 1..16, 17, 38 and 65 bytes.  (65 bytes: five lanes per row in k_epilogue_chunks, 21 rows per lane and tile — the
+# row widths 1..16, 17, 32, 38, 50, 64 and 65 bytes.  (65 bytes: five lanes per row in k_epilogue_chunks, 21 rows per lane and tile — the
 # width at which a workgroup's 16 to 20 tiles of ones bring a lane far past the 255 rows its planes hold; at 38 bytes they
 # bring it 260, at 17 bytes 160.)
-# OPEN GAP: for rows of 2..16 bytes (k_epilogue_n, k_epilogue_w) no case here, and none in the suite, reaches the flush of the
-# column sums' counter planes after 240 rows of a thread: the launcher gives a workgroup 16 tiles (64 rows per thread) until a
-# launch holds more than 16 384 tiles, so it takes 60 tiles of one contig per workgroup — about 6 x 10^7 rows in one launch, too
-# many for a test of a few seconds.  That flush is covered by tools/planes_check.cpp (the planes' arithmetic up to 252 rows) and is
-# reached at bench sizes only (profiles/stats_share_ab.txt), not by a test.
-STATS_N = [1, 8, 13, 24, 29, 40, 45, 56, 61, 72, 77, 88, 93, 104, 109, 120, 128, 130, 300, 520]
+# 256, 400 and 512: the instantiations k_epilogue_chunks<2, true>, <4, false> and <4, true> (EXACT: aligned loads, no tail mask,
+# the `full` shortcut).
+# The flush of the column sums' counter planes in the MIDDLE of a contig — after 240 rows of a thread, 248 or 252 in k_epilogue_w
+# — is NOT reached by these cases for rows of 2..16 bytes (k_epilogue_n, k_epilogue_w), nor for 17..32 bytes: the launcher gives a
+# workgroup 16 to 20 tiles (64 rows per thread) until a launch holds more than 16 384 tiles, and the flush takes 60 tiles of one
+# contig in one workgroup (30 at 17..32 bytes).  It is covered by the flush cases below (FLUSH_*): the same kernels under
+# PG_EPI_WORKGROUPS = 1 and 2, launch_rows_epilogue's bound on the grid, over a contig of 131 tiles — tests/
+# test_gpu_planes_flush.py; tests/epi_walk.py restates which thread meets which flush, and tests/test_rows_craft_cpu.py holds
+# the cases to that model, the absence of any such flush without the bound included.  (tools/planes_check.cpp checks the planes'
+# integer arithmetic alone, on the host.)
+STATS_N = [1, 8, 13, 24, 29, 40, 45, 56, 61, 72, 77, 88, 93, 104, 109, 120, 128, 130, 256, 300, 400, 512, 520]
 STATS_NK = [1, 99, 100, 101, 255, 256, 257, 1023, 1024, 1025, 8 * 1024 + 1, 20000, 70001]
 STATS_GEOMETRY = {
     "default": {},
@@ -259,7 +264,54 @@ def stats_rows(n):
     return rows
 
 
-WINDOW_N = [1, 8, 33, 64, 128, 130, 300]
+# The flush of the counter planes in the MIDDLE of a contig (tests/test_gpu_planes_flush.py; which thread meets which flush:
+# tests/epi_walk.py).  Every row width of 2..16 bytes, 17 and 32 bytes (k_epilogue_chunks<2, false> and <2, true>, 8 rows per
+# lane and tile) and one byte (accumulators of its own: it must equal the reference all the same).
+FLUSH_N = [8, 13, 24, 29, 40, 45, 56, 61, 72, 77, 88, 93, 104, 109, 120, 128, 130, 256]
+FLUSH_BOUNDS = [1, 2]  # PG_EPI_WORKGROUPS: one workgroup walks every contig; a second one starts inside the long contig
+# a contig of exactly the 60 tiles of one flush and a partial tile; the long one, 131 tiles and a partial one (two flushes and rows
+# behind them); a short one behind it (its end-of-contig flush follows a mid-contig one and starts from clean planes).  In this
+# order a second workgroup starts at tile 35 of the long contig and has 97 of its tiles.
+FLUSH_NK = [60 * 1024 + 77, 131 * 1024 + 300, 2500]
+FLUSH_ONES_TILES = 64  # of the long contig: all N bits, so that every column of every thread stands at the count at which the first flush comes
+
+
+def flush_rows(n):
+    long_nk = FLUSH_NK[1] - FLUSH_ONES_TILES * 1024
+    long_rest = back_to_back(long_nk, [(1, lambda m: ramp(m, n)), (1, lambda m: bursts(m, n, 255)), (1, lambda m: bursts(m, n, 256)),
+                                       (1, lambda m: bursts(m, n, 257)), (1, lambda m: column(m, n, n - 1)),
+                                       (1, lambda m: dense(m, n, 11))])
+    rows = [np.concatenate([ones(60 * 1024, n), dense(77, n, 10)]),
+            np.concatenate([ones(FLUSH_ONES_TILES * 1024, n), long_rest]),
+            back_to_back(FLUSH_NK[2], [(1, lambda m: ramp(m, n)), (1, lambda m: ones(m, n)), (1, lambda m: dense(m, n, 12))])]
+    assert [len(r) for r in rows] == FLUSH_NK
+    return rows
+
+
+def flush_geometries(n):
+    """{name: geometry} of the flush cases of N: the default bins (nkmers / 100 rows), bins longer than a tile, and what the walk
+    needs to reach the sites those two do not — k_epilogue_n's one-tile site (bins the window holds, groups of 4 tiles refused)
+    and k_epilogue_w's flush at 252 rows (groups and single tiles in turn), both found by the model of the walk"""
+    from tests import epi_walk as ew
+    geoms = {"default": {}, "long_bins": dict(max_bin_len=5000, min_bin_count=1)}
+    if ew.kernel_of(n) == "n":
+        geoms["one_tile"] = ew.one_tile_bins(n, FLUSH_NK)
+    elif ew.kernel_of(n) == "w":
+        # (uniform bins mix groups and single tiles at ONE bin length per N, about 2048 / MAXB rows; at N = 77 — 53 rows — the
+        # single tiles come in pairs under both bounds and every flush stays at 248: no such case for rows of 10 bytes)
+        geom = ew.carry_bins(n, FLUSH_NK)
+        if geom is not None:
+            geoms["carry252"] = geom
+    return geoms
+
+
+def flush_cases():
+    """(N, geometry name) of every flush case (a geometry the model of the walk does not find — None — is no case: tests/
+    test_rows_craft_cpu.py fails then)"""
+    return [(n, name) for n in FLUSH_N for name, geom in flush_geometries(n).items() if geom is not None]
+
+
+WINDOW_N =[1, 8, 33, 64, 128, 130, 300]
 WINDOW_NK = [200000, 300]
 
 

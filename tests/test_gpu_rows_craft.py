@@ -6,8 +6,10 @@ oracle.pyoracle.window_stats and tests/intros_ref.bitmap_to_bins (tests/test_row
 
 Which kernel runs for which N (bytes per row = ceil(N / 8)):
   rows_epilogue   1 byte k_epilogue_b1; 2..8 bytes k_epilogue_n<2..8>; 9..16 bytes k_epilogue_w<9..16>; 17 bytes (N = 130)
-                  k_epilogue_chunks<2,false>; 38 bytes (N = 300) k_epilogue_chunks<3,false>; 65 bytes (N = 520)
-                  k_epilogue_chunks<0,false>; k_lowres with lowres_step=7
+                  k_epilogue_chunks<2,false>; 32 bytes (N = 256) k_epilogue_chunks<2,true>; 38 bytes (N = 300)
+                  k_epilogue_chunks<3,false>; 50 bytes (N = 400) k_epilogue_chunks<4,false>; 64 bytes (N = 512)
+                  k_epilogue_chunks<4,true>; 65 bytes (N = 520) k_epilogue_chunks<0,false>; k_lowres with lowres_step=7
+                  (the flushes of the counter planes in the middle of a contig: tests/test_gpu_planes_flush.py)
   window_stats    k_window_stats
   bin_colsums     N <= 128 k_bin_colsums<4>, beyond k_bin_colsums<0>
 with_pad_bits (bits past N) is planted for k_bin_colsums only, whose header states the rule for them; the statistics

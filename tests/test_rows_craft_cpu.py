@@ -1,12 +1,15 @@
 """CPU: the crafted-rows helper (tests/rows_craft.py) — its references against the restatements the suite already trusts
 (oracle.pyoracle.window_stats, tests/intros_ref.bitmap_to_bins), its pattern generators, and the coverage the GPU tests
-(tests/test_gpu_rows_craft.py) claim for the rows they plant."""
+(tests/test_gpu_rows_craft.py) claim for the rows they plant; and the model of the statistics kernels' walk (tests/epi_walk.py):
+which mid-contig flush of the column sums' counter planes the cases of tests/test_gpu_planes_flush.py reach under the bound on the
+grid, and that the default launch shape reaches none."""
 import numpy as np
 import pandas as pd
 import pytest
 
 from oracle import pyoracle as po
 from panagram_amd.index import Genome
+from tests import epi_walk as ew
 from tests import intros_ref as ref
 from tests import rows_craft as rc
 
@@ -150,3 +153,128 @@ def test_planted_statistics_rows_cover_the_ceilings():
         edges = np.flatnonzero(np.diff(full))
         runs = set(edges[1::2] - edges[0::2])
         assert {255, 256, 257} <= runs
+
+
+# ---------------------------------------------------------------------------
+# the flush of the counter planes in the middle of a contig: the model of the walk (tests/epi_walk.py) and what
+# tests/test_gpu_planes_flush.py claims to reach
+# ---------------------------------------------------------------------------
+def _mid(w):
+    return [f for f in w.flushes if f.site != "end"]
+
+
+def test_walk_model_restates_the_launch_shape():
+    assert [ew.kernel_of(n) for n in (1, 8, 9, 64, 65, 128, 129, 256)] == ["b1", "b1", "n", "n", "w", "w", "chunks", "chunks"]
+    assert [ew.maxb_for(n) for n in (8, 13, 61, 72, 128, 130, 520)] == [128, 128, 49, 42, 23, 23, 16]
+    assert [ew.minbin(m) for m in (128, 49, 42, 23, 16)] == [9, 22, 26, 49, 74]
+    # about 16 tiles per workgroup until a launch holds more than 16 384 tiles, then 128 at the most
+    assert [ew.grid_for(t) for t in (1, 15, 16, 196, 16384, 16400, 131072, 10 ** 6)] == [1, 1, 1, 12, 1024, 1024, 1024, 2048]
+    assert [ew.grid_for(196, b) for b in (0, 1, 2, 12, 13, 10 ** 9)] == [1, 1, 2, 12, 12, 12]
+    for gt in (4, 8):
+        for ntiles, grid in ((196, 1), (196, 2), (196, 12), (5, 3), (1, 1)):
+            rg = [ew.epi_range(gt, ntiles, j, grid) for j in range(grid)]
+            assert rg[0][0] == 0 and rg[-1][1] == ntiles and all(a[1] == b[0] for a, b in zip(rg, rg[1:]))
+            assert all(b % gt == 0 for b, _ in rg)
+    assert ew.epi_range(4, 196, 1, 2) == (96, 196)
+    # rows per lane and tile of the chunk kernel: 4 * IPT (a partial tile: its iterations of 4 steps that hold a row)
+    assert [ew.chunk_rows_per_tile(n) for n in (130, 256, 300, 400, 512, 520)] == [8, 8, 16, 16, 16, 24]
+    assert ew.chunk_rows_per_tile(130, 300) == 4 and ew.chunk_rows_per_tile(130, 513) == 8
+    for nk in rc.FLUSH_NK + rc.STATS_NK:
+        for g in ({}, dict(max_bin_len=5000, min_bin_count=1), dict(max_bin_len=22, min_bin_count=1)):
+            assert ew.bin_length(nk, **g) == rc.bin_length(nk, **g)
+    assert ew.tiles_of([1, 1024, 1025])[0] == [0, 1, 2, 2] and ew.tiles_of(rc.FLUSH_NK)[1] == [0, 61, 193]
+    assert (ew.PLANES_FLUSH, ew.PLANES_CEIL) == (240, 255)
+
+
+def test_planted_flush_rows_stand_at_the_ceiling():
+    """every column of every row set over the 60 full tiles of the first contig and the first 64 tiles of the long one (a thread's
+    planes hold the highest count at the first flush), runs of ones of 255, 256 and 257 rows behind, every slot hit"""
+    assert rc.FLUSH_NK[0] == 60 * 1024 + 77 and rc.FLUSH_NK[1] > 130 * 1024 and rc.FLUSH_NK[1] % 1024
+    for n in (8, 13, 128, 130):
+        rows = rc.flush_rows(n)
+        assert [len(r) for r in rows] == rc.FLUSH_NK
+        popc = [rc.unpack(r, n).sum(axis=1) for r in rows]
+        assert (popc[0][:60 * 1024] == n).all() and (popc[1][:64 * 1024] == n).all()
+        rest = popc[1][64 * 1024:]
+        full = np.concatenate([[0], (rest == n).astype(np.int8), [0]])
+        edges = np.flatnonzero(np.diff(full))
+        assert {255, 256, 257} <= set(edges[1::2] - edges[0::2])
+        assert set(rest) == set(range(n + 1))
+        assert rc.unpack(rows[1], n).sum(axis=0).min() > 64 * 1024 + 10000 > rc.unpack(rows[1], n)[64 * 1024:].sum(axis=0).min()
+
+
+@pytest.mark.parametrize("n", rc.FLUSH_N)
+def test_flush_cases_reach_their_sites_under_the_bound(n):
+    """the reach tests/test_gpu_planes_flush.py rests on, by the model of the walk: under PG_EPI_WORKGROUPS = 1 every site of the
+    width's kernel is met at least twice inside one contig with rows of that contig behind the last flush; under 2 the second
+    workgroup starts inside the long contig, has more than 60 of its tiles and meets the site again"""
+    kern = ew.kernel_of(n)
+    geoms = rc.flush_geometries(n)
+    assert all(g is not None for g in geoms.values()), geoms
+    # (rows of 10 bytes: the one bin length that mixes groups and single tiles, 53 rows, pairs the single tiles up under both
+    # bounds — no flush at 252 rows there; every other width of k_epilogue_w, both group sizes' instantiations, has one)
+    assert set(geoms) == {"b1": {"default", "long_bins"}, "n": {"default", "long_bins", "one_tile"},
+                          "w": {"default", "long_bins"} | ({"carry252"} if n != 77 else set()),
+                          "chunks": {"default", "long_bins"}}[kern]
+    assert [(m, g) for m, g in rc.flush_cases() if m == n] == [(n, g) for g in geoms]
+    _, tile0 = ew.tiles_of(rc.FLUSH_NK)
+    walks = {(g, b): ew.walk(n, rc.FLUSH_NK, b, **geom) for g, geom in geoms.items() for b in rc.FLUSH_BOUNDS}
+    for (g, b), w in walks.items():
+        assert len(w.ranges) == b and all(f.vrows % 4 == 0 and 0 < f.vrows <= ew.PLANES_CEIL for f in w.flushes), (g, b)
+        if b == 2:
+            begin, end = w.ranges[1]
+            assert tile0[1] < begin < tile0[2] and min(end, tile0[2]) - begin > 60, w.ranges
+    if kern == "b1":
+        assert not any(w.flushes for w in walks.values())  # (accumulators of its own)
+        return
+    plain = {"n": "n.group", "w": "w", "chunks": "chunks"}[kern]
+    site_of = {"default": plain, "long_bins": plain, "one_tile": "n.tile", "carry252": "w"}
+    for g in geoms:
+        w1, w2 = walks[g, 1], walks[g, 2]
+        site = site_of[g]
+        assert {f.site for f in _mid(w1)} == {site}, (g, _mid(w1))
+        if g != "carry252":  # (with groups and single tiles in turn the two flushes of the long contig may come under either bound)
+            assert ew.reaches(w1, site, times=2), (g, w1.flushes)
+            assert len(ew.mid_contig(w1, site)[0, 1]) >= 2  # (workgroup 0, the long contig)
+        assert any(f.wg == 1 and f.contig == 1 for f in _mid(w2)), (g, w2.flushes)  # the workgroup that starts inside the long contig
+    if kern == "n":
+        # the contig of exactly 60 tiles: the flush comes with its last full tile, the partial tile's 4 rows leave at the contig's end
+        for g in ("default", "one_tile"):
+            fl = [f for f in walks[g, 1].flushes if f.contig == 0]
+            assert [(f.site, f.vrows) for f in fl] == [(site_of[g], 240), ("end", 4)], fl
+        assert set(walks["one_tile", 1].paths.values()) == {"tile"} and "unwindowed" not in walks["default", 1].paths.values()
+    if kern == "w":
+        # the plain group walk (two tiles = 8 rows a group) flushes at 248: the carry of weight 8 held back
+        for g in ("default", "long_bins"):
+            assert {f.vrows for f in _mid(walks[g, 1])} == {248}, g
+        if "carry252" not in geoms:
+            return
+        # groups and single tiles in turn: 252 rows, the carries of weight 4 and 8 held back — under one of the bounds
+        both = _mid(walks["carry252", 1]) + _mid(walks["carry252", 2])
+        assert 252 in {f.vrows for f in both}, both
+        long_paths = [walks["carry252", 1].paths[t] for t in range(tile0[1], tile0[2])]
+        assert {"group", "tile"} <= set(long_paths)
+    if kern == "chunks":
+        assert ew.chunk_rows_per_tile(n) == 8 and len(_mid(walks["default", 1])) >= 6
+
+
+def test_carry_geometry_of_128_genomes():
+    """bins of 90 rows at N = 128: a group of two tiles spans MAXB = 23 or 24 bins in turn, so groups and single tiles
+    alternate inside the long contig and a flush comes at 252 rows (the shortest such bins the model finds)"""
+    assert ew.carry_bins(128, rc.FLUSH_NK) == dict(max_bin_len=90, min_bin_count=1)
+    w = ew.walk(128, rc.FLUSH_NK, 1, max_bin_len=90, min_bin_count=1)
+    assert sorted(f.vrows for f in _mid(w) if f.contig == 1) == [248, 252]
+    assert ew.reaches(w, "w", times=1, vrows=252)
+
+
+@pytest.mark.parametrize("n", [m for m in rc.STATS_N if ew.kernel_of(m) in ("n", "w")] + [130, 256])
+def test_default_launch_shape_reaches_no_mid_contig_flush(n):
+    """THE GAP the bound closes, written down: with PG_EPI_WORKGROUPS unset neither the flush cases nor the statistics cases of
+    tests/test_gpu_rows_craft.py meet a single mid-contig flush at rows of 2..16 bytes (nor at 17 and 32 bytes) — a workgroup
+    gets 16 to 20 tiles.  Nobody should believe the default-shaped tests cover these lines."""
+    for geom in (rc.flush_geometries(n) if n in rc.FLUSH_N else {}).values():
+        w = ew.walk(n, rc.FLUSH_NK, None, **geom)
+        assert len(w.ranges) == 12 and not _mid(w), (geom, _mid(w))
+        assert max(f.vrows for f in w.flushes) <= 4 * 20 * (2 if ew.kernel_of(n) == "chunks" else 1)
+    for geom in rc.STATS_GEOMETRY.values():
+        assert not _mid(ew.walk(n, rc.STATS_NK, None, **geom)), geom

@@ -789,6 +789,43 @@ int pg_place_last_timing(float *ms_out);
 /* the HIP-event times, in milliseconds, of this host thread's last calls: ms_out[3] = k_copy_insert of the last insert, k_copy_count
  * of the last count, k_copy_profile (all its launches) of the last profile — what tools/copies_rate.py reports. */
 int pg_copies_last_timing(float *ms_out);
+/* screen: WHICH of the indexed genomes does a sample hold, and how much of each?  The sample — read sets joined by
+ * pg_seqset_from_fastq, or the contigs of an assembly — is streamed through the pan table itself and counted per slot; one pass over
+ * the slots joins the counts with the presence masks (pg_screen.hip).  With k the table's k (a sequence set carries none: its
+ * windows are cut at the table's), N its genomes:
+ *   depth(key)   the valid windows of the sample whose canonical k-mer is key, both strands, summed over every sequence set added
+ *                since the screen was created or cleared; it saturates at 255.  Windows holding a non-ACGT byte do not exist,
+ *                contigs shorter than k have none.
+ * A screen owns one byte per slot of the table, zero at creation, and holds the table as a result does (a destroyed table goes when
+ * its last screen does).  The bytes belong to ONE geometry of ONE table: the screen records the table's lines (their address, their
+ * number, the slots of a line, the layout) and its key count, and pg_screen_add_seqset / pg_screen_result return PG_E_INVALID once
+ * any of them differs — after a re-hash, an insert that added keys, a clear or a regrow behind the handle.  Create a new screen then.
+ * The table itself is only read.  PG_E_CAPACITY: no memory for the bytes.  A screen is used by one host thread at a time. */
+typedef struct pg_screen pg_screen;
+int pg_screen_create(pg_table *tbl, pg_screen **out);
+int pg_screen_destroy(pg_screen *s);
+/* the byte of the slot of every valid window of `seqs` whose key the table holds += 1, saturating at 255 — exactly, whatever the
+ * contention (a homopolymer puts every lane on one byte; a byte's three neighbours in its dword are never touched).  *windows = the
+ * valid windows of seqs, *hits = those whose key the table holds.  PG_E_INVALID before anything is launched: a NULL argument, a
+ * sequence set of another context, a stale screen.  One launch of k_table_mark; synchronises. */
+int pg_screen_add_seqset(pg_screen *s, const pg_seqset *seqs, uint64_t *windows, uint64_t *hits);
+/* one pass over the table's slots (those pg_table_pair_counts counts: a key, neither empty nor retired), M = the slot's mask with
+ * the bits at and past N cleared, n = popcount(M), d = its depth:
+ *   distinct[g]  g < N: the keys with bit g            seen[g]          those of them with d >= min_count
+ *   priv[g]      the keys whose only bit is g          priv_seen[g]     those of them with d >= min_count
+ *   occ[n]       n <= N: the keys of exactly n genomes seen_occ[n]      those of them with d >= min_count
+ *   depth_hist[c]  c < 64: the keys with min(d, 63) == c                core_depth_hist[c]  the same of the keys with n == N
+ *   *nkeys       the keys counted
+ * Any output may be NULL.  The bytes stay as they are: results at several min_count come from one plane.  PG_E_INVALID before
+ * anything is launched: min_count outside 1..255, more than 512 genomes, a stale screen.  One launch of k_table_screen on the
+ * context's stream; synchronises. */
+int pg_screen_result(pg_screen *s, uint32_t min_count, uint64_t *distinct, uint64_t *seen, uint64_t *priv, uint64_t *priv_seen,
+                     uint64_t *occ, uint64_t *seen_occ, uint64_t *depth_hist, uint64_t *core_depth_hist, uint64_t *nkeys);
+/* every byte back to zero (the next sample) */
+int pg_screen_clear(pg_screen *s);
+/* the HIP-event times, in milliseconds, of this host thread's last calls: ms_out[2] = k_table_mark of the last pg_screen_add_seqset,
+ * k_table_screen of the last pg_screen_result — what tools/screen_rate.py reports. */
+int pg_screen_last_timing(float *ms_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

@@ -31,7 +31,11 @@ histogram and its median on the GPU; and
 `locate <index_dir> [queries.fa] [--genes GENOME] [--genomes A,B] [-k K] [--min-run N] [--max-gap G] [--max-shift S] [--min-kmers N]
 [--min-frac F] [--paf] [--matrix FILE] [--summary FILE]` says WHERE each query lies in every genome — chromosome, start, end, strand,
 every copy: the queries' k-mers go into a position table, every genome's assembly is streamed through it, and the collinear runs of
-its hits are chained into loci on the GPU; only the loci leave it."""
+its hits are chained into loci on the GPU; only the loci leave it; and
+`screen <index_dir> <sample.fq|sample.fa> [more ...] [--min-count N] [--genomes A,B] [--occupancy FILE] [--summary FILE]` says which
+of the indexed genomes a sample from outside the index holds and how much of each: the reads, or an assembly, are streamed once
+through the table of every sample's k-mers and counted per k-mer, and one pass over the table joins the counts with the presence
+masks on the GPU."""
 import argparse
 import os
 import sys
@@ -228,6 +232,20 @@ def main(argv=None):
     plc.add_argument("--batch-bytes", type=int, default=None, metavar="N", help="FASTQ text bytes joined at a time (default 2^28)")
     plc.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     plc.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    scn = sub.add_parser("screen", help="which indexed genomes a sample from outside the index holds, and how much of each: the reads (or "
+                                        "an assembly) streamed through the table of all genomes' k-mers and counted per k-mer on the GPU: "
+                                        "tab-separated, with a header, genome distinct seen containment identity private private_seen "
+                                        "private_containment rank")
+    scn.add_argument("index_dir")
+    scn.add_argument("samples", metavar="sample.fq|sample.fa", nargs="+", help="the sample's files: FASTQ (four lines per record) or FASTA, plain or .gz")
+    scn.add_argument("--min-count", type=int, default=None, metavar="C",
+                     help="the sample holds a k-mer it holds at least C times, 1 to 255 (default: 2 when a file is FASTQ, else 1)")
+    scn.add_argument("--genomes", default="", metavar="A,B", help="the genomes to print (default: all of them; ranks are among all)")
+    scn.add_argument("--occupancy", metavar="FILE", default=None, help="also write n, kmers, seen: the k-mers held by exactly n genomes")
+    scn.add_argument("--summary", metavar="FILE", default=None, help="also write one comment line per statistic: reads, windows, hits, novel_frac, ...")
+    scn.add_argument("--batch-bytes", type=int, default=None, metavar="N", help="FASTQ text bytes joined at a time (default 2^28)")
+    scn.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    scn.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -462,6 +480,38 @@ def main(argv=None):
         if a.summary:
             place.write_summary(summary, stats, a.summary)
         place.write_main(main_, a.output if a.output else sys.stdout)
+        return 0
+    if a.cmd == "screen":
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"screen: {a.index_dir!r} is not an index directory")
+        for r in a.samples:
+            if not os.path.isfile(r):
+                ap.error(f"screen: no sample file {r!r}")
+        if (a.min_count is not None and not 1 <= a.min_count <= 255) or (a.batch_bytes is not None and a.batch_bytes < 1):
+            ap.error("screen: --min-count is 1 to 255, --batch-bytes positive")
+        from .index import Index
+        from . import screen
+        try:
+            idx = Index(a.index_dir, mode="r", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"screen: {e}")
+        try:
+            import pandas as pd
+            for n in idx.genome_names:  # (the table is built from the samples' sequences)
+                fa = idx[n].fasta
+                if pd.isna(fa) or not os.path.isfile(str(fa)):
+                    ap.error(f"screen: sample {n!r} of {a.index_dir} has no sequence file to take k-mers of ({fa})")
+            try:
+                main_, occupancy, stats = idx.screen(a.samples, a.min_count, [g for g in a.genomes.split(",") if g] or None, a.batch_bytes)
+            except (ValueError, KeyError) as e:
+                ap.error(f"screen: {e}")
+        finally:
+            idx.close()
+        if a.occupancy:
+            screen.write_occupancy(occupancy, a.occupancy)
+        if a.summary:
+            screen.write_summary(stats, a.summary)
+        screen.write_main(main_, a.output if a.output else sys.stdout)
         return 0
     if a.cmd == "locate":
         if (a.queries is None) == (a.genes is None):

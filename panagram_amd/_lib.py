@@ -160,6 +160,12 @@ PROTOTYPES = {
     "pg_copies_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
     "pg_copytable_sample_agree": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pg_place_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
+    "pg_screen_create": (C.c_int, [_vp, _vpp]),
+    "pg_screen_destroy": (C.c_int, [_vp]),
+    "pg_screen_add_seqset": (C.c_int, [_vp, _vp, _u64p, _u64p]),
+    "pg_screen_result": (C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64p]),
+    "pg_screen_clear": (C.c_int, [_vp]),
+    "pg_screen_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
     "pg_knn_rows": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "pg_result_write_bgzf": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "pg_bgzf_inflate": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),

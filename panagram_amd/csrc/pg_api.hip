@@ -459,7 +459,7 @@ static void table_free(pg_table *t) {
     delete t;
     ctx_release(c);
 }
-static void table_release(pg_table *t) {
+void pg::table_release(pg_table *t) {
     if (--t->refs == 0 && t->dead) table_free(t);
 }
 

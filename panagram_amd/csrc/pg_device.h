@@ -420,8 +420,9 @@ __device__ __forceinline__ uint64_t extract_nmask64(P words, uint64_t p) {
     return (lo >> sh) | ((hi << 1) << (63 - sh));
 }
 
-// Single-lane lookup (GetCountersForRead kernel): mask word w of `key`, 0 if absent.
-__device__ __forceinline__ bool lane_lookup(const SubTable &st, uint64_t key, uint32_t w, uint32_t &out) {
+// Single-lane walk of a table that is not being written: the line and the slot (0 .. st.slots - 1) that hold `key`; false when
+// the table does not hold it.
+__device__ __forceinline__ bool lane_find(const SubTable &st, uint64_t key, uint32_t &line, uint32_t &slot) {
     const uint32_t grp = group_of(st, key);
     uint32_t b = home_of_group(grp, st.nbuckets);
     uint32_t step = step_of_group(grp, st.nbuckets);
@@ -433,7 +434,8 @@ __device__ __forceinline__ bool lane_lookup(const SubTable &st, uint64_t key, ui
         for (uint32_t s = s_lo; s < s_hi; ++s) {
             const uint64_t cur = *key_ptr(st, b, s);
             if (cur == key) {
-                out = mask_load(st, b, s, w);
+                line = b;
+                slot = s;
                 return true;
             }
             empty_seen |= (cur == EMPTY_KEY);
@@ -441,8 +443,15 @@ __device__ __forceinline__ bool lane_lookup(const SubTable &st, uint64_t key, ui
         if (empty_seen) break;
         advance_line(key, (uint32_t)min(probes + 1, (uint64_t)GROUP_CHAIN + 1), st.nbuckets, b, step);
     }
-    out = 0;
     return false;
+}
+
+// Single-lane lookup (GetCountersForRead kernel): mask word w of `key`, 0 if absent.
+__device__ __forceinline__ bool lane_lookup(const SubTable &st, uint64_t key, uint32_t w, uint32_t &out) {
+    uint32_t line, slot;
+    const bool found = lane_find(st, key, line, slot);
+    out = found ? mask_load(st, line, slot, w) : 0u;
+    return found;
 }
 
 // Insert-or-find `key`, OR `bits` into mask word w.  Returns 0 = existed,

@@ -273,6 +273,7 @@ PG_INTERNAL int fail(int code, const char *fmt, ...);
 PG_INTERNAL int use_device(const pg_ctx *c);
 PG_INTERNAL int check_step(const pg_result *r, int step);
 PG_INTERNAL void ctx_release(pg_ctx *c);
+PG_INTERNAL void table_release(pg_table *t);  // a dependant of the table (a result, a screen) lets go of it
 PG_INTERNAL hipError_t row_alloc(pg_ctx *c, uint64_t bytes, uint8_t **out, uint64_t *cap);
 PG_INTERNAL void row_free(pg_ctx *c, uint8_t *p, uint64_t cap);
 PG_INTERNAL uint32_t window_cap(int ngenomes = 0);  // (PG_TABLE_WMAX)

@@ -382,6 +382,22 @@ hipError_t launch_sample_agree(hipStream_t st, uint32_t ngenomes, int k, const u
                                const uint2 *chunks, uint32_t nchunks, const uint32_t *wcontig, const SeqDesc *sd, const uint64_t *seqw,
                                const uint32_t *nmw, const uint32_t *has_n, const unsigned long long *keys, uint64_t nslots,
                                uint32_t max_probe, const uint32_t *plane, uint32_t min_count, uint2 *partial, uint2 *vh);
+// a sample screened against the pan table (pg_screen.hip; the definitions are there).  `plane`: one byte per slot of t, the byte
+// of line l, slot s at l * t.slots + s, 4-byte aligned and readable up to the next multiple of 4 bytes.
+//   mark    jobs[j] = (contig, piece): k-mer positions [piece, piece + 1) x SCREEN_JOB of a contig of at least t.k bases.  The byte
+//           of every valid window's slot += 1, saturating at SCREEN_DEPTH_MAX; the table is only read.  ctr (zeroed by the caller):
+//           ctr[0] += the valid windows, ctr[1] += those whose key t holds
+//   screen  one pass over every slot of t whose key is below TOMB_KEY, M = its mask cut to N bits, d = its byte.  out (zeroed by
+//           the caller, accumulated into): distinct [N], seen [N] (bit g, and d >= min_count), private [N] (only bit g),
+//           private_seen [N], occ [N + 1] (by popcount), seen_occ [N + 1], depth_hist [SCREEN_BINS] (by min(d, SCREEN_BINS - 1)),
+//           core_depth_hist [SCREEN_BINS] (the same of keys with all N bits), nkeys [1] — screen_out_words(N) words.
+//           1 <= N <= PAIRS_MAX_GENOMES, N <= 32 t.W, 1 <= min_count <= SCREEN_DEPTH_MAX
+constexpr uint32_t SCREEN_BINS = 64, SCREEN_DEPTH_MAX = 255, SCREEN_JOB = 1u << 14;
+__host__ __device__ __forceinline__ size_t screen_out_words(uint32_t N) { return (size_t)4 * N + 2 * ((size_t)N + 1) + 2 * SCREEN_BINS + 1; }
+hipError_t launch_table_mark(hipStream_t st, const SubTable &t, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint64_t *seqw,
+                             const uint32_t *nmw, const uint32_t *has_n, uint8_t *plane, unsigned long long *ctr);
+hipError_t launch_table_screen(hipStream_t st, const SubTable &t, uint32_t ngenomes, const uint8_t *plane, uint32_t min_count,
+                               unsigned long long *out);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

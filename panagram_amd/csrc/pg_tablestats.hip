@@ -8,7 +8,8 @@
 // (workflow/Snakefile:124-149) estimates it from a sketch at k = 21.
 //
 // A slot counts when its key < TOMB_KEY (empty and retired slots are skipped, as in k_export / k_rehash); only its W words in
-// use are read, and the bits at and past N are masked off.  Keys and masks are addressed through key_ptr / mask_ptr — a lane's
+// use are read, and the bits at and past N are masked off.  Keys and masks are addressed through key_ptr / mask_ptr (SlotWalk of
+// pg_tablescan.h, which k_table_screen of pg_screen.hip walks the table with too) — a lane's
 // slot of chunk 0 and the distance from one chunk to the next, both layouts' arrays being affine in the line number — so the
 // kernel is the same in the slots (W = 1, 2), inline (W = 3) and split (W >= 4) layouts.
 //
@@ -42,24 +43,15 @@
 #include "pg_kernels.h"
 #include "pg_rowread.h"
 #include "pg_pairblocks.h"
+#include "pg_tablescan.h"  // the chunks, a lane's walk over its slots, the grid
 #include <algorithm>
 
 namespace pg {
-
-constexpr uint32_t TABLESTATS_BLOCKS = 2048;  // blocks per slice: 8 per CU of an MI355X
-constexpr uint32_t TS_QCAP = 128;             // entries of a wave's queue: fewer than 64 left over + up to 64 of one chunk
 
 // LDS of one block, in 32-bit words behind the column words: the four queues, the round flags, the four waves' counters
 __host__ __device__ __forceinline__ size_t ts_lds_bytes(uint32_t N, uint32_t W, bool priv_mode) {
     const uint32_t NC = (N + 63) & ~63u;
     return (size_t)(priv_mode ? 1 : 2) * 4 * NC * 8 + ((size_t)4 * TS_QCAP * W + 8 + (size_t)4 * (2 * N + 1)) * 4;
-}
-
-// LDS writes of this wave's lanes before, its lanes' reads of them behind
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 template <uint32_t MAXW, uint32_t ROUNDS, bool PRIVATE>
@@ -81,22 +73,11 @@ __global__ __launch_bounds__(256) void k_table_pair_counts(SubTable st, uint32_t
     PairBlocks<ROUNDS> pb;
     if (PRIVATE) pb.init(lane, 0, N, 64);
     else pb.init(tid, blockIdx.z, N);
-    // this lane's slot of a chunk: slot s of the chunk's line number l; its key and mask words in chunk 0, and the way from one
-    // chunk to the next
-    const uint32_t l = lane / st.slots, s = lane - l * st.slots;
-    const bool mine = l < chunk_lines;
-    const uint8_t *key0 = reinterpret_cast<const uint8_t *>(key_ptr(st, mine ? l : 0, s));
-    // (byte-mask layout: a slot's mask is one byte in its line — the same walk by pointer steps, a byte read where the others read words)
-    const bool bm = st.layout == LAYOUT_BYTEMASK;
-    const uint8_t *mask0 = bm ? mask_byte_ptr(st, mine ? l : 0, s) : reinterpret_cast<const uint8_t *>(mask_ptr(st, mine ? l : 0, s, 0));
-    const uint64_t key_step = reinterpret_cast<const uint8_t *>(key_ptr(st, chunk_lines, 0)) - reinterpret_cast<const uint8_t *>(key_ptr(st, 0, 0));
-    const uint64_t mask_step = bm ? key_step : reinterpret_cast<const uint8_t *>(mask_ptr(st, chunk_lines, 0, 0)) - reinterpret_cast<const uint8_t *>(mask_ptr(st, 0, 0, 0));
-    auto key_of = [&](uint64_t c) -> uint64_t {  // (empty where the chunk has no such slot)
-        return c < nchunks && mine && c * chunk_lines + l < st.nbuckets ? *reinterpret_cast<const unsigned long long *>(key0 + c * key_step) : EMPTY_KEY;
-    };
+    // this lane's slot of every chunk (byte-mask layout: the same walk by pointer steps, a byte read where the others read words)
+    const SlotWalk sw(st, lane, nchunks, chunk_lines);
     const uint64_t cstride = (uint64_t)gridDim.x * 4;
     uint64_t c = (uint64_t)blockIdx.x * 4 + wave;
-    uint64_t next_key = key_of(c);
+    uint64_t next_key = sw.key_of(c);
     uint32_t qh = 0, qn = 0;  // the queue's head and its entries (wave-uniform)
     uint32_t nk = 0;          // keys popped (wave-uniform)
     uint32_t buf = 0;
@@ -107,14 +88,14 @@ __global__ __launch_bounds__(256) void k_table_pair_counts(SubTable st, uint32_t
             const bool act = next_key < TOMB_KEY;  // (neither empty nor a retired copy)
             const uint64_t cur = c;
             c += cstride;
-            next_key = key_of(c);
+            next_key = sw.key_of(c);
             const uint64_t keys = __ballot(act);
             if (keys == 0) continue;  // (wave-uniform)
             if (act) {
                 const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(keys >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)keys, 0u));
                 uint32_t *e = queue + ((qh + qn + rank) & (TS_QCAP - 1)) * W;
-                const uint32_t *m = reinterpret_cast<const uint32_t *>(mask0 + cur * mask_step);
-                if (bm) e[0] = (uint32_t)mask0[cur * mask_step] & valid_bits(N, 0);
+                const uint32_t *m = sw.mask_words(cur);
+                if (sw.bm) e[0] = sw.mask_byte(cur) & valid_bits(N, 0);
                 else for (uint32_t d = 0; d < W; ++d) e[d] = m[d] & valid_bits(N, d);
             }
             qn += (uint32_t)__popcll(keys);
@@ -217,12 +198,11 @@ hipError_t launch_table_pair_counts(hipStream_t st, const SubTable &t, uint32_t 
     if (ngenomes < 1 || ngenomes > PAIRS_MAX_GENOMES || t.slots < 1 || t.slots > 64 || 32ull * t.W < ngenomes)
         return hipErrorInvalidValue;
     if (t.nbuckets == 0) return hipSuccess;
-    const uint32_t chunk_lines = 64 / t.slots;
-    const uint64_t nchunks = (t.nbuckets + chunk_lines - 1) / chunk_lines;
     // fewer than 2^24 chunks per wave, so fewer than 2^32 slots per block (the file header)
-    const uint64_t per_wave_cap = (1ull << 24) - 1;
-    const uint64_t blocks = std::max<uint64_t>(std::min<uint64_t>((nchunks + 3) / 4, TABLESTATS_BLOCKS), (nchunks + 4 * per_wave_cap - 1) / (4 * per_wave_cap));
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    uint32_t chunk_lines;
+    uint64_t nchunks;
+    const uint64_t blocks = tablescan_blocks(t, chunk_lines, nchunks);
+    if (blocks == 0) return hipErrorInvalidValue;
     const uint32_t W = std::min<uint32_t>(t.W, (ngenomes + 31) / 32), NB = (ngenomes + 3) / 4, nblk = NB * (NB + 1) / 2;
     const bool priv_mode = ngenomes <= 64;
     const uint32_t slices = priv_mode ? 1 : (nblk + PAIRS_ROUNDS * 256 - 1) / (PAIRS_ROUNDS * 256);

@@ -1072,6 +1072,69 @@ class PanTable(_Owner):
             pass
 
 
+SCREEN_BINS = 64        # depth bins of a screen: bin c = depth c, the last = that depth and beyond
+SCREEN_DEPTH_MAX = 255  # a screen's depth saturates there
+
+
+class TableScreen:
+    """A sample screened against a pan table (pg_screen.hip): one byte per slot of ``table`` in HBM, the depth at which the sample
+    holds the slot's k-mer — the valid windows of every sequence set added whose canonical k-mer it is, both strands, saturating at
+    SCREEN_DEPTH_MAX.  The table is only read.  The bytes belong to the table as it is now: after a re-hash, an insert that added
+    keys, a clear or a regrow ``add`` and ``result`` raise (PG_E_INVALID) — make a new screen.  Closed before its table."""
+
+    def __init__(self, table: "PanTable"):
+        self.table, self._lib = table, table._lib
+        h = C.c_void_p()
+        check(self._lib.pg_screen_create(table._h, C.byref(h)))
+        self._h = h
+        table._adopt(self)
+
+    def add(self, seqs: SeqSet) -> Tuple[int, int]:
+        """stream ``seqs`` through the table: (its valid windows, those whose k-mer the table holds); depths accumulate over calls"""
+        windows, hits = C.c_uint64(), C.c_uint64()
+        check(self._lib.pg_screen_add_seqset(self._h, seqs._h, C.byref(windows), C.byref(hits)))
+        return int(windows.value), int(hits.value)
+
+    def result(self, min_count: int = 1) -> dict:
+        """one pass over the table's k-mers, a k-mer SEEN when its depth is at least ``min_count`` (1 to SCREEN_DEPTH_MAX): int64
+        arrays ``distinct``, ``seen``, ``private``, ``private_seen`` [genomes]; ``occ``, ``seen_occ`` [genomes + 1] by the number of
+        genomes that hold a k-mer; ``depth_hist``, ``core_depth_hist`` [SCREEN_BINS] by min(depth, 63), of all k-mers and of those
+        every genome holds; and ``nkeys``.  The depths stay: ask again at another ``min_count``."""
+        if not 1 <= int(min_count) <= SCREEN_DEPTH_MAX:
+            raise ValueError(f"min_count {min_count} (1 to {SCREEN_DEPTH_MAX})")
+        n = self.table.ngenomes
+        out = {name: np.zeros(size, np.uint64) for name, size in (("distinct", n), ("seen", n), ("private", n), ("private_seen", n),
+                                                                  ("occ", n + 1), ("seen_occ", n + 1), ("depth_hist", SCREEN_BINS),
+                                                                  ("core_depth_hist", SCREEN_BINS))}
+        nkeys = C.c_uint64()
+        check(self._lib.pg_screen_result(self._h, int(min_count), *[_ptr(a) for a in out.values()], C.byref(nkeys)))
+        out = {name: a.astype(np.int64) for name, a in out.items()}
+        out["nkeys"] = int(nkeys.value)
+        return out
+
+    def clear(self) -> None:
+        """every depth back to zero: the next sample"""
+        check(self._lib.pg_screen_clear(self._h))
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.pg_screen_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def screen_last_timing() -> dict:
+    """HIP-event milliseconds of k_table_mark and k_table_screen in this thread's last ``TableScreen.add`` and ``.result``"""
+    ms = (C.c_float * 2)()
+    check(_lib.load().pg_screen_last_timing(ms))
+    return dict(zip(("mark_ms", "screen_ms"), (float(x) for x in ms)))
+
+
 def homology_classes(name_lists: Sequence[Sequence[str]]) -> np.ndarray:
     """``contig_class`` for ``AnchorResult.coschedule`` from the genomes' record ids: contigs with the same id (the same
     chromosome name in different FASTAs) form one class, classes numbered in order of first appearance.  A genome

@@ -1497,6 +1497,59 @@ class Index:
         bins, valid, held, col, both, stats = self[anchor].place_counts(reads, chroms, bin_size, min_count, batch_bytes)
         return (*pl.frames(bins, valid, held, col, both, names, genomes), stats)
 
+    def screen(self, samples, min_count: Optional[int] = None, genomes=None, batch_bytes: Optional[int] = None):
+        """(main, occupancy, stats) — ``screen.frames`` — of ONE sample from outside the index: which of the indexed genomes it
+        holds, how much of each it recovers, whose private k-mers it carries, how deep it is sequenced and how much of it is in no
+        indexed genome.  ``samples``: the sample's files, FASTQ (four lines per record) or FASTA, plain or ``.gz``, streamed one
+        after the other; each is read ONCE.  The sample's k-mers are counted per k-mer of the table of every sample's k-mers
+        (built from the samples' sequence files on first use and cached; ``engine.TableScreen``): FASTQ text ``batch_bytes`` at
+        a time, joined on the GPU; a FASTA as one sequence set.  A k-mer is seen when the sample holds it at least ``min_count``
+        times (1 to 255; None: 2 when any file is FASTQ, else 1).  ``genomes`` (names; None: all) selects the lines of the main
+        table only: ranks are among all genomes.  ``stats["novel_frac"]`` counts window instances, sequencing errors among them.
+        KeyError: an unknown genome name; ValueError: a missing file, a torn last record, a ``min_count`` outside 1..255;
+        RuntimeError: the cached table holds some anchors' k-mers only."""
+        from . import place as pl, screen as scr
+        names = list(self.genome_names)
+        scr.pick_genomes(names, genomes)  # (refused before any work)
+        samples = [samples] if isinstance(samples, (str, os.PathLike)) else list(samples)
+        paths = [os.fspath(p) for p in samples]
+        for p in paths:
+            if not os.path.isfile(p):
+                raise ValueError(f"screen: no sample file {p!r}")
+        min_count = scr.check_min_count(scr.default_min_count(any(is_fastq(p) for p in paths)) if min_count is None else min_count)
+        batch_bytes = pl.DEFAULT_BATCH_BYTES if batch_bytes is None else int(batch_bytes)
+        if batch_bytes < 1:
+            raise ValueError(f"screen: batch_bytes must be positive, got {batch_bytes}")
+        ctx = self.context
+        sc = engine.TableScreen(self._full_table())
+        tot = {"windows": 0, "hits": 0, "reads": 0, "read_bases": 0}
+
+        def add(ss, reads, bases):
+            w, h = sc.add(ss)
+            for f, v in (("windows", w), ("hits", h), ("reads", reads), ("read_bases", bases)):
+                tot[f] += int(v)
+        try:
+            for p in paths:
+                if is_fastq(p):
+                    fb = pl.FastqBatches(p, batch_bytes)
+                    for buf in fb:
+                        rs, n, used = engine.SeqSet.from_fastq(ctx, buf)
+                        try:
+                            add(rs, n, int(rs.lens[0]) - max(n - 1, 0))
+                        finally:
+                            rs.close()
+                        fb.advance(used)
+                else:
+                    ss = engine.SeqSet.from_fasta(ctx, p)
+                    try:
+                        add(ss, len(ss.lens), int(np.asarray(ss.lens, np.uint64).sum()))
+                    finally:
+                        ss.close()
+            counts = sc.result(min_count)
+        finally:
+            sc.close()
+        return scr.frames(counts, names, int(self.k), min_count, tot["windows"], tot["hits"], tot["reads"], tot["read_bases"], genomes)
+
     def locate(self, queries, genomes=None, k=None, min_run: int = 1, max_gap: int = 1000, max_shift: int = 100, min_kmers: int = 1,
                min_frac: float = 0.0):
         """(loci, matrix, summary) — ``locate.frames`` — of query sequences: WHERE each lies in the assemblies of the ``genomes``

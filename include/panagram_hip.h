@@ -826,6 +826,54 @@ int pg_screen_clear(pg_screen *s);
 /* the HIP-event times, in milliseconds, of this host thread's last calls: ms_out[2] = k_table_mark of the last pg_screen_add_seqset,
  * k_table_screen of the last pg_screen_result — what tools/screen_rate.py reports. */
 int pg_screen_last_timing(float *ms_out);
+/* novel: WHAT does a sample hold that no indexed genome does?  The reverse of the screen: the sample is streamed through the pan
+ * table once, and the windows that MISS it are counted in a key table of the sample's own (pg_novel.hip), which is built while the
+ * sample streams and grows in front of every sequence set.  With k the table's k:
+ *   novel key    the canonical k-mer of a valid window of the sample that the pan table does not hold
+ *   depth(key)   the valid windows of the sample with that key, both strands, summed over every sequence set added since the handle
+ *                was created or cleared; exact in 32 bits.  solid: depth >= min_count.
+ *   novel run    a maximal run [start, end) of consecutive valid k-mer positions of one contig whose keys are all novel; contig
+ *                ends and invalid windows cut runs.  left_held = position start - 1 exists, is valid and the pan table holds its
+ *                key; right_held the same of position end.
+ * A handle owns 12 bytes per slot (an 8-byte key, a 32-bit depth), the power of two at or above 2 capacity_keys slots at creation,
+ * and holds the pan table as a screen does: it records the table's geometry and key count and pg_novel_add_seqset, pg_novel_result
+ * and pg_novel_keys return PG_E_INVALID once any of them differs (keys filtered by another table answer nothing).  The pan table is
+ * only read.  PG_E_INVALID: capacity_keys outside 1..2^30; PG_E_CAPACITY: no memory.  A handle is used by one host thread at a time. */
+typedef struct pg_novel pg_novel;
+int pg_novel_create(pg_table *tbl, uint64_t capacity_keys, pg_novel **out);
+int pg_novel_destroy(pg_novel *nv);
+/* every slot free again, the windows counted back to zero (the next sample); the slots stay as many as they have grown to */
+int pg_novel_clear(pg_novel *nv);
+/* every valid window of `seqs` whose key the pan table lacks: its key claimed in the novel table, its depth += 1 — exactly, whatever
+ * the contention.  *windows = the valid windows of seqs, *hits = those whose key the pan table holds, *new_keys = the keys this call
+ * claimed.  The call reserves before it launches: when the keys held plus the set's k-mer positions pass half the slots the table
+ * is re-hashed on the device into one that holds them at a load of 0.5 at the most (k_novel_grow), so an add never overflows.
+ * Before anything is launched, the handle usable afterwards: PG_E_CAPACITY when that takes more than 2^31 slots (2^30 keys and
+ * positions: add smaller sequence sets) or the memory is not there; PG_E_INVALID for a NULL argument, a sequence set of another
+ * context, a stale handle, or when the windows added so far plus this set's positions pass 2^32 - 1 (the depths are 32 bits).  A
+ * claim that gives up all the same makes the handle answer PG_E_CAPACITY until it is cleared.  One launch of k_novel_count;
+ * synchronises. */
+int pg_novel_add_seqset(pg_novel *nv, const pg_seqset *seqs, uint64_t *windows, uint64_t *hits, uint64_t *new_keys);
+/* *nkeys = the novel keys held, *nslots = the slots, *grown = the times the table has grown.  Any output may be NULL. */
+int pg_novel_stats(pg_novel *nv, uint64_t *nkeys, uint64_t *nslots, uint64_t *grown);
+/* one pass over the slots (k_novel_scan): *nkeys = the novel keys, *solid = those with depth >= min_count, *solid_windows = the sum
+ * of their depths, depth_hist[c], c < 64 = the keys with min(depth, 63) == c.  Any output may be NULL; the table stays as it is:
+ * results at several min_count come from one table.  PG_E_INVALID: min_count == 0. */
+int pg_novel_result(pg_novel *nv, uint32_t min_count, uint64_t *nkeys, uint64_t *solid, uint64_t *solid_windows, uint64_t *depth_hist);
+/* the solid keys and their depths, in slot order — the same on every call between two adds, no particular order otherwise: the
+ * first min(cap, *n) of them to keys / depths, *n = all of them always (cap 0: only counted). */
+int pg_novel_keys(pg_novel *nv, uint32_t min_count, uint64_t cap, uint64_t *keys, uint32_t *depths, uint64_t *n);
+/* the novel runs of the contigs of `seqs` against the pan table (k_novel_runs; no handle: the novel table is not touched), sorted by
+ * (contig, start): the first min(cap, *nruns) of them to the five arrays, positions contig-relative; *nruns = all of them, *windows
+ * = the valid windows of seqs, *novel_windows = those whose key the table lacks = the sum of the runs' lengths — always.
+ * PG_E_INVALID before anything is launched: a NULL argument, a sequence set of another context, a contig of more than 2^32 - 1
+ * k-mer positions. */
+int pg_novel_runs(pg_table *tbl, const pg_seqset *seqs, uint64_t cap, uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end,
+                  uint8_t *left_held, uint8_t *right_held, uint64_t *nruns, uint64_t *windows, uint64_t *novel_windows);
+/* the HIP-event times, in milliseconds, of this host thread's last calls: ms_out[4] = k_novel_count and k_novel_grow of the last
+ * pg_novel_add_seqset (0: it did not grow, or grew an empty table), k_novel_scan of the last pg_novel_result or pg_novel_keys (both
+ * passes), k_novel_runs of the last pg_novel_runs (both passes) — what tools/novel_rate.py reports. */
+int pg_novel_last_timing(float *ms_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

@@ -35,7 +35,10 @@ its hits are chained into loci on the GPU; only the loci leave it; and
 `screen <index_dir> <sample.fq|sample.fa> [more ...] [--min-count N] [--genomes A,B] [--occupancy FILE] [--summary FILE]` says which
 of the indexed genomes a sample from outside the index holds and how much of each: the reads, or an assembly, are streamed once
 through the table of every sample's k-mers and counted per k-mer, and one pass over the table joins the counts with the presence
-masks on the GPU."""
+masks on the GPU; and
+`novel <index_dir> <sample.fq|sample.fa> [more ...] [--min-count N] [--spectrum FILE] [--kmers FILE] [--regions FILE] [--min-bases B]
+[--summary FILE]` says the reverse: the distinct k-mers of the sample that NO indexed genome holds, their depth spectrum, and for an
+assembly where they lie — the sample's windows that miss the table are counted in a key table of their own that grows on the GPU."""
 import argparse
 import os
 import sys
@@ -246,6 +249,21 @@ def main(argv=None):
     scn.add_argument("--batch-bytes", type=int, default=None, metavar="N", help="FASTQ text bytes joined at a time (default 2^28)")
     scn.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     scn.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    nvl = sub.add_parser("novel", help="what a sample from outside the index holds that no indexed genome does: the distinct k-mers of the "
+                                       "reads (or an assembly) that miss the table of all genomes' k-mers, counted on the GPU; prints "
+                                       "name<TAB>value per statistic: novel_kmers, solid_kmers, solid_windows, error_windows, ...")
+    nvl.add_argument("index_dir")
+    nvl.add_argument("samples", metavar="sample.fq|sample.fa", nargs="+", help="the sample's files: FASTQ (four lines per record) or FASTA, plain or .gz")
+    nvl.add_argument("--min-count", type=int, default=None, metavar="C",
+                     help="a k-mer is solid when the sample holds it at least C times: the only error filter (default: 2 when a file is FASTQ, else 1)")
+    nvl.add_argument("--spectrum", metavar="FILE", default=None, help="also write depth, kmers: the novel k-mers at every depth 1 to 63 (63: and beyond)")
+    nvl.add_argument("--kmers", metavar="FILE", default=None, help="also write kmer, depth: the solid novel k-mers, sorted")
+    nvl.add_argument("--regions", metavar="FILE", default=None,
+                     help="also write file contig start end kmers bases left_held right_held: the runs of novel k-mers along an assembly (no FASTQ)")
+    nvl.add_argument("--min-bases", type=int, default=0, metavar="B", help="regions of at least B bases that lie in novel k-mers only (default 0)")
+    nvl.add_argument("--summary", metavar="FILE", default=None, help="also write the statistics to FILE")
+    nvl.add_argument("--batch-bytes", type=int, default=None, metavar="N", help="FASTQ text bytes joined at a time (default 2^28)")
+    nvl.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -512,6 +530,45 @@ def main(argv=None):
         if a.summary:
             screen.write_summary(stats, a.summary)
         screen.write_main(main_, a.output if a.output else sys.stdout)
+        return 0
+    if a.cmd == "novel":
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"novel: {a.index_dir!r} is not an index directory")
+        for r in a.samples:
+            if not os.path.isfile(r):
+                ap.error(f"novel: no sample file {r!r}")
+        if (a.min_count is not None and not 1 <= a.min_count <= 0xFFFFFFFF) or (a.batch_bytes is not None and a.batch_bytes < 1) or a.min_bases < 0:
+            ap.error("novel: --min-count is 1 to 2^32 - 1, --batch-bytes positive, --min-bases not negative")
+        from .index import Index, is_fastq
+        from . import novel
+        if a.regions and any(is_fastq(r) for r in a.samples):
+            ap.error("novel: --regions needs an assembly: " + ", ".join(repr(r) for r in a.samples if is_fastq(r)) + " is FASTQ")
+        try:
+            idx = Index(a.index_dir, mode="r", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"novel: {e}")
+        try:
+            import pandas as pd
+            for n in idx.genome_names:  # (the table is built from the samples' sequences)
+                fa = idx[n].fasta
+                if pd.isna(fa) or not os.path.isfile(str(fa)):
+                    ap.error(f"novel: sample {n!r} of {a.index_dir} has no sequence file to take k-mers of ({fa})")
+            try:
+                stats, spectrum, kmers, regions = idx.novel(a.samples, a.min_count, a.batch_bytes, kmers=bool(a.kmers), regions=bool(a.regions),
+                                                            min_bases=a.min_bases)
+            except ValueError as e:
+                ap.error(f"novel: {e}")
+        finally:
+            idx.close()
+        if a.spectrum:
+            novel.write_spectrum(spectrum, a.spectrum)
+        if a.kmers:
+            novel.write_kmers(kmers, a.kmers)
+        if a.regions:
+            novel.write_regions(regions, a.regions)
+        if a.summary:
+            novel.write_summary(stats, a.summary)
+        novel.write_stats(stats, sys.stdout)
         return 0
     if a.cmd == "locate":
         if (a.queries is None) == (a.genes is None):

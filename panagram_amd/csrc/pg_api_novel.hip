@@ -1,0 +1,449 @@
+// pg_api_novel.hip — host side of the C-ABI: what a sample holds that the pan table does not (pg_novel.hip): the novel key table
+// that sequence sets are counted into and that grows in front of them, the pass over its slots, and the novel runs of an assembly.
+#include "pg_host.h"
+
+#include "pg_keytable_host.h"
+
+static constexpr uint64_t NOVEL_MAX_KEYS = COPIES_MAX_SLOTS / 2;  // (table_slots: the power of two at or above 2 * keys)
+static constexpr uint64_t NOVEL_MAX_WINDOWS = 0xFFFFFFFFull;      // of one handle: a depth is 32 bits
+static constexpr uint64_t NOVEL_MAX_CONTIG = 0xFFFFFFFFull;       // k-mer positions of one contig of pg_novel_runs: a run's end is a word
+
+struct pg_novel {
+    pg_ctx *ctx;
+    pg_table *tbl;
+    unsigned long long *d_keys = nullptr;
+    uint32_t *d_depth = nullptr;
+    uint64_t nslots = 0, nkeys = 0, windows = 0;  // windows: the valid windows added since the last clear
+    uint32_t max_probe = 0, grown = 0;
+    bool overflowed = false;  // a claim gave up (the reservation makes that impossible): the depths are short and answer nothing
+    // the geometry of the pan table the keys were filtered by (pg_screen's rule: a re-hash, an insert of new keys, a clear or a
+    // regrow behind the handle changes one of them)
+    const uint8_t *buckets;
+    uint64_t nbuckets, count;
+    uint32_t slots, layout;
+};
+
+namespace {
+
+thread_local float g_novel_ms[4] = {0, 0, 0, 0};  // k_novel_count, k_novel_grow, k_novel_scan (both passes), k_novel_runs (both passes)
+
+void novel_free(pg_novel *nv) {
+    hipSetDevice(nv->ctx->device);
+    hipStreamSynchronize(nv->ctx->stream);
+    if (nv->d_depth) hipFree(nv->d_depth);
+    if (nv->d_keys) hipFree(nv->d_keys);
+    pg_table *t = nv->tbl;
+    delete nv;
+    table_release(t);
+}
+
+// the pan table as a caller may read it (its writer lock held), or an error
+int pan_table(const pg_table *t, const char *fn, const SubTable **out) {
+    if (t->dead) return fail(PG_E_INVALID, "%s: the table was destroyed", fn);
+    if (t->subs.size() != 1) return fail(PG_E_INVALID, "%s: a table of %zu sub-tables", fn, t->subs.size());
+    const SubTable &d = t->subs[0].d;
+    if ((int)d.k != t->k || t->k < 1 || t->k > 32) return fail(PG_E_INVALID, "%s: a table of k = %d whose lines are of k = %u", fn, t->k, d.k);
+    *out = &d;
+    return PG_OK;
+}
+
+// ... as the handle knows it: keys filtered by another geometry or key count must not be added to
+int novel_table(const pg_novel *nv, const char *fn, const SubTable **out) {
+    if (int r = pan_table(nv->tbl, fn, out)) return r;
+    const SubHost &h = nv->tbl->subs[0];
+    if (h.d.buckets != nv->buckets || h.d.nbuckets != nv->nbuckets || h.d.slots != nv->slots || h.d.layout != nv->layout || h.count != nv->count)
+        return fail(PG_E_INVALID,
+                    "%s: the table changed behind the novel table (%llu lines of %u slots and %llu keys when it was created, %llu of %u and "
+                    "%llu now): create a new one",
+                    fn, (unsigned long long)nv->nbuckets, nv->slots, (unsigned long long)nv->count, (unsigned long long)h.d.nbuckets, h.d.slots,
+                    (unsigned long long)h.count);
+    return PG_OK;
+}
+
+// keys and depths of `nslots` free slots
+hipError_t novel_alloc(hipStream_t st, uint64_t nslots, DevBuf<unsigned long long> &keys, DevBuf<uint32_t> &depth) {
+    hipError_t e = keys.alloc(nslots);
+    if (e == hipSuccess) e = depth.alloc(nslots);
+    if (e == hipSuccess) e = hipMemsetAsync(keys.get(), 0xFF, nslots * 8, st);
+    if (e == hipSuccess) e = hipMemsetAsync(depth.get(), 0, nslots * 4, st);
+    return e;
+}
+
+int novel_create(pg_table *t, uint64_t capacity, pg_novel **out) {
+    const char *fn = "pg_novel_create";
+    if (capacity < 1 || capacity > NOVEL_MAX_KEYS) return fail(PG_E_INVALID, "%s: capacity of %llu keys (1 to 2^30)", fn, (unsigned long long)capacity);
+    if (int r = use_device(t->ctx)) return r;
+    TABLE_WRITER(t);  // (a reader of the geometry: no re-hash swaps the lines meanwhile)
+    const SubTable *st = nullptr;
+    if (int r = pan_table(t, fn, &st)) return r;
+    const SubHost &h = t->subs[0];
+    std::unique_ptr<pg_novel> nv(new pg_novel);
+    nv->ctx = t->ctx;
+    nv->tbl = t;
+    nv->buckets = h.d.buckets;
+    nv->nbuckets = h.d.nbuckets;
+    nv->slots = h.d.slots;
+    nv->layout = h.d.layout;
+    nv->count = h.count;
+    nv->nslots = table_slots(capacity);
+    nv->max_probe = table_max_probe(nv->nslots);
+    DevBuf<unsigned long long> keys;
+    DevBuf<uint32_t> depth;
+    hipError_t e = novel_alloc(t->ctx->stream, nv->nslots, keys, depth);
+    if (e == hipSuccess) e = hipStreamSynchronize(t->ctx->stream);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? PG_E_CAPACITY : PG_E_HIP, "%s: %llu slots: %s", fn, (unsigned long long)nv->nslots, hipGetErrorString(e));
+    std::swap(nv->d_keys, keys.p);
+    std::swap(nv->d_depth, depth.p);
+    ++t->refs;
+    *out = nv.release();
+    return PG_OK;
+}
+
+// room for `incoming` more keys at a load of 0.5 at the most: the table re-hashed into one of twice the slots or more (k_novel_grow).
+// Nothing of the handle changes when a reservation is refused
+int novel_reserve(pg_novel *nv, uint64_t incoming, const char *fn) {
+    g_novel_ms[1] = 0;
+    const uint64_t need = nv->nkeys + incoming;
+    if (2 * need <= nv->nslots) return PG_OK;
+    if (need > NOVEL_MAX_KEYS)
+        return fail(PG_E_CAPACITY,
+                    "%s: %llu novel keys and %llu k-mer positions to add (a novel table holds 2^30 keys with the positions of one sequence set): "
+                    "lower --batch-bytes",
+                    fn, (unsigned long long)nv->nkeys, (unsigned long long)incoming);
+    const uint64_t nslots = table_slots(need);
+    const uint32_t max_probe = table_max_probe(nslots);
+    hipStream_t st = nv->ctx->stream;
+    DevBuf<unsigned long long> keys, d_flag;
+    DevBuf<uint32_t> depth;
+    unsigned long long flag = 0;
+    LaunchTimer tm(&g_novel_ms[1]);
+    hipError_t e = novel_alloc(st, nslots, keys, depth);
+    if (e == hipErrorOutOfMemory) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_CAPACITY, "%s: no memory for a novel table of %llu slots: lower --batch-bytes", fn, (unsigned long long)nslots);
+    }
+    if (e == hipSuccess && nv->nkeys) {
+        e = d_flag.alloc(1);
+        if (e == hipSuccess) e = hipMemsetAsync(d_flag.get(), 0, 8, st);
+        if (e == hipSuccess) e = tm.start(st);
+        if (e == hipSuccess) e = launch_novel_grow(st, nv->d_keys, nv->d_depth, nv->nslots, keys.get(), depth.get(), nslots, max_probe, d_flag.get());
+        if (e == hipSuccess) e = tm.stop(st);
+        if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag.get(), 8, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_HIP, "%s: growing to %llu slots: %s", fn, (unsigned long long)nslots, hipGetErrorString(e));
+    }
+    if (nv->nkeys) tm.read();
+    if (flag) {  // (a load below 0.25: a walk of max_probe slots never fills)
+        nv->overflowed = true;
+        return fail(PG_E_CAPACITY, "%s: %llu slots did not take the table's %llu keys", fn, (unsigned long long)nslots, (unsigned long long)nv->nkeys);
+    }
+    std::swap(nv->d_keys, keys.p);  // (the old arrays go with this scope)
+    std::swap(nv->d_depth, depth.p);
+    nv->nslots = nslots;
+    nv->max_probe = max_probe;
+    ++nv->grown;
+    return PG_OK;
+}
+
+int novel_add(pg_novel *nv, const pg_seqset *sq, uint64_t *windows, uint64_t *hits, uint64_t *new_keys) {
+    const char *fn = "pg_novel_add_seqset";
+    if (nv->ctx != sq->ctx) return fail(PG_E_INVALID, "%s: novel table and seqset belong to different contexts", fn);
+    if (nv->overflowed) return fail(PG_E_CAPACITY, "%s: the novel table overflowed before", fn);
+    pg_table *t = nv->tbl;
+    TABLE_WRITER(t);  // (a reader: it keeps a second host thread's re-hash from freeing the lines under the kernel)
+    const SubTable *st = nullptr;
+    if (int r = novel_table(nv, fn, &st)) return r;
+    KmerWalk w;
+    if (int r = walk_kmers(sq, t->k, NOVEL_JOB, fn, w)) return r;
+    if (nv->windows + w.nkmers > NOVEL_MAX_WINDOWS)
+        return fail(PG_E_INVALID, "%s: %llu windows added and %llu k-mer positions in this set (the depths hold 2^32 - 1 per handle)", fn,
+                    (unsigned long long)nv->windows, (unsigned long long)w.nkmers);
+    if (int r = use_device(nv->ctx)) return r;
+    *windows = *hits = *new_keys = 0;
+    g_novel_ms[0] = g_novel_ms[1] = 0;
+    if (w.jobs.empty()) return PG_OK;
+    if (int r = novel_reserve(nv, w.nkmers, fn)) return r;
+    hipStream_t stream = nv->ctx->stream;
+    unsigned long long ctr[4] = {0, 0, 0, 0};
+    const hipError_t e = counted_launch(stream, w.jobs, ctr, 4, &g_novel_ms[0], [&](const uint2 *jobs, uint32_t njobs, unsigned long long *d_ctr) {
+        return launch_novel_count(stream, *st, sq->d_desc, jobs, njobs, sq->d_seqw, sq->d_nmw, sq->d_has_n, nv->d_keys, nv->d_depth, nv->nslots,
+                                  nv->max_probe, d_ctr);
+    });
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    *windows = ctr[0];
+    *hits = ctr[1];
+    *new_keys = ctr[2];
+    nv->windows += ctr[0];
+    nv->nkeys += ctr[2];
+    if (ctr[3]) {
+        nv->overflowed = true;
+        return fail(PG_E_CAPACITY, "%s: %llu claims found no slot among %llu", fn, (unsigned long long)ctr[3], (unsigned long long)nv->nslots);
+    }
+    return PG_OK;
+}
+
+// the count pass of k_novel_scan: h = its NOVEL_SCAN_WORDS words, block_solid (when asked for) the solid keys of every block
+int novel_scan_count(pg_novel *nv, const char *fn, uint32_t min_count, uint64_t *h, std::vector<uint32_t> *block_solid, float *ms) {
+    if (min_count < 1) return fail(PG_E_INVALID, "%s: min_count must be >= 1", fn);
+    if (nv->overflowed) return fail(PG_E_CAPACITY, "%s: the novel table overflowed", fn);
+    {
+        TABLE_WRITER(nv->tbl);  // (a reader of the geometry)
+        const SubTable *pan = nullptr;
+        if (int r = novel_table(nv, fn, &pan)) return r;  // (keys filtered by a table that is gone answer nothing)
+    }
+    if (int r = use_device(nv->ctx)) return r;
+    hipStream_t st = nv->ctx->stream;
+    const uint32_t nblocks = novel_scan_blocks(nv->nslots);
+    DevBuf<unsigned long long> d_out;
+    DevBuf<uint32_t> d_bs;
+    if (block_solid) block_solid->assign(nblocks, 0);
+    LaunchTimer tm(ms);
+    hipError_t e = d_out.alloc(NOVEL_SCAN_WORDS);
+    if (e == hipSuccess) e = d_bs.alloc(nblocks);
+    if (e == hipSuccess) e = hipMemsetAsync(d_out.get(), 0, NOVEL_SCAN_WORDS * 8, st);
+    if (e == hipSuccess) e = tm.start(st);
+    if (e == hipSuccess) e = launch_novel_scan(st, nv->d_keys, nv->d_depth, nv->nslots, min_count, d_out.get(), d_bs.get(), nullptr, 0, nullptr, nullptr);
+    if (e == hipSuccess) e = tm.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(h, d_out.get(), NOVEL_SCAN_WORDS * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && block_solid) e = hipMemcpyAsync(block_solid->data(), d_bs.get(), (size_t)nblocks * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);  // (the copies' targets are the caller's)
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    tm.read();
+    if (h[0] != nv->nkeys)
+        return fail(PG_E_HIP, "%s: the pass counted %llu keys, the adds claimed %llu", fn, (unsigned long long)h[0], (unsigned long long)nv->nkeys);
+    return PG_OK;
+}
+
+int novel_result(pg_novel *nv, uint32_t min_count, uint64_t *nkeys, uint64_t *solid, uint64_t *solid_windows, uint64_t *depth_hist) {
+    uint64_t h[NOVEL_SCAN_WORDS];
+    g_novel_ms[2] = 0;
+    if (int r = novel_scan_count(nv, "pg_novel_result", min_count, h, nullptr, &g_novel_ms[2])) return r;
+    if (nkeys) *nkeys = h[0];
+    if (solid) *solid = h[1];
+    if (solid_windows) *solid_windows = h[2];
+    if (depth_hist) std::copy(h + 3, h + 3 + NOVEL_BINS, depth_hist);
+    return PG_OK;
+}
+
+int novel_keys(pg_novel *nv, uint32_t min_count, uint64_t cap, uint64_t *keys_out, uint32_t *depths_out, uint64_t *n) {
+    const char *fn = "pg_novel_keys";
+    uint64_t h[NOVEL_SCAN_WORDS];
+    std::vector<uint32_t> block_solid;
+    float ms_count = 0, ms_emit = 0;
+    g_novel_ms[2] = 0;
+    if (int r = novel_scan_count(nv, fn, min_count, h, &block_solid, &ms_count)) return r;
+    g_novel_ms[2] = ms_count;
+    *n = h[1];
+    const uint64_t take = std::min<uint64_t>(h[1], cap);
+    if (take == 0) return PG_OK;
+    std::vector<uint64_t> offs(block_solid.size());
+    uint64_t sum = 0;
+    for (size_t b = 0; b < block_solid.size(); ++b) {
+        offs[b] = sum;
+        sum += block_solid[b];
+    }
+    if (sum != h[1]) return fail(PG_E_HIP, "%s: %llu solid keys by block, %llu in all", fn, (unsigned long long)sum, (unsigned long long)h[1]);
+    hipStream_t st = nv->ctx->stream;
+    DevBuf<uint64_t> d_offs;
+    DevBuf<unsigned long long> d_k;
+    DevBuf<uint32_t> d_d;
+    LaunchTimer tm(&ms_emit);
+    hipError_t e = d_offs.upload(offs, st);
+    if (e == hipSuccess) e = d_k.alloc(take);
+    if (e == hipSuccess) e = d_d.alloc(take);
+    if (e == hipErrorOutOfMemory) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_CAPACITY, "%s: no memory for %llu keys", fn, (unsigned long long)take);
+    }
+    if (e == hipSuccess) e = tm.start(st);
+    if (e == hipSuccess) e = launch_novel_scan(st, nv->d_keys, nv->d_depth, nv->nslots, min_count, nullptr, nullptr, d_offs.get(), take, d_k.get(), d_d.get());
+    if (e == hipSuccess) e = tm.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(keys_out, d_k.get(), take * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(depths_out, d_d.get(), take * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    tm.read();
+    g_novel_ms[2] = ms_count + ms_emit;
+    return PG_OK;
+}
+
+int novel_runs(pg_table *t, const pg_seqset *sq, uint64_t cap, uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end, uint8_t *left_held,
+               uint8_t *right_held, uint64_t *nruns, uint64_t *windows, uint64_t *novel_windows) {
+    const char *fn = "pg_novel_runs";
+    if (t->ctx != sq->ctx) return fail(PG_E_INVALID, "%s: table and seqset belong to different contexts", fn);
+    TABLE_WRITER(t);  // (a reader, as pg_novel_add_seqset is)
+    const SubTable *pan = nullptr;
+    if (int r = pan_table(t, fn, &pan)) return r;
+    KmerWalk w;
+    w.noun = "chunks";
+    if (int r = walk_kmers(sq, t->k, NOVEL_CHUNK, fn, w)) return r;
+    for (uint32_t c = 0; c < sq->n; ++c)
+        if ((c + 1 < sq->n ? w.koff[c + 1] : w.nkmers) - w.koff[c] > NOVEL_MAX_CONTIG)
+            return fail(PG_E_INVALID, "%s: contig %u holds more than 2^32 - 1 k-mer positions", fn, c);
+    for (uint2 &ck : w.jobs) ck.y *= NOVEL_CHUNK;  // (k_novel_runs takes a chunk's first position, below 2^32 behind the check above)
+    *nruns = *windows = *novel_windows = 0;
+    g_novel_ms[3] = 0;
+    if (w.jobs.empty()) return PG_OK;
+    if (int r = use_device(t->ctx)) return r;
+    const uint32_t nchunks = (uint32_t)w.jobs.size();
+    hipStream_t st = t->ctx->stream;
+    DevBuf<uint2> d_chunks;
+    DevBuf<uint4> d_counts;
+    std::vector<uint4> counts(nchunks);
+    float ms_count = 0, ms_emit = 0;
+    LaunchTimer tc(&ms_count), te(&ms_emit);
+    hipError_t e = d_chunks.upload(w.jobs, st);
+    if (e == hipSuccess) e = d_counts.alloc(nchunks);
+    if (e == hipSuccess) e = tc.start(st);
+    if (e == hipSuccess)
+        e = launch_novel_runs(st, *pan, sq->d_desc, d_chunks.get(), nchunks, sq->d_seqw, sq->d_nmw, sq->d_has_n, d_counts.get(), nullptr, 0, nullptr,
+                              nullptr, nullptr, nullptr);
+    if (e == hipSuccess) e = tc.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);  // (the upload's source and the copy's target go with this scope)
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    tc.read();
+    g_novel_ms[3] = ms_count;
+    // per chunk: the starts and the ends of all chunks before it; per contig: its runs
+    std::vector<ulonglong2> offs(nchunks);
+    std::vector<uint64_t> per(sq->n, 0);
+    uint64_t nstarts = 0, nends = 0, nvalid = 0, nnovel = 0;
+    for (uint32_t c = 0; c < sq->n; ++c) {
+        const uint64_t s0 = nstarts;
+        for (uint64_t i = w.first[c]; i < w.first[c + 1]; ++i) {
+            offs[i] = make_ulonglong2(nstarts, nends);
+            nstarts += counts[i].x;
+            nends += counts[i].y;
+            nvalid += counts[i].z;
+            nnovel += counts[i].w;
+        }
+        per[c] = nstarts - s0;
+        if (nstarts != nends)  // (every run of a contig starts and ends inside it)
+            return fail(PG_E_HIP, "%s: contig %u: %llu run starts, %llu run ends", fn, c, (unsigned long long)nstarts, (unsigned long long)nends);
+    }
+    *nruns = nstarts;
+    *windows = nvalid;
+    *novel_windows = nnovel;
+    const uint64_t take = std::min<uint64_t>(nstarts, cap);  // (the first `take` runs in (contig, start) order)
+    if (take == 0) return PG_OK;
+    DevBuf<ulonglong2> d_offs;
+    DevBuf<uint32_t> d_se;  // starts, then ends
+    DevBuf<uint8_t> d_lr;   // left_held, then right_held
+    e = d_offs.upload(offs, st);
+    if (e == hipSuccess) e = d_se.alloc(2 * take);
+    if (e == hipSuccess) e = d_lr.alloc(2 * take);
+    if (e == hipErrorOutOfMemory) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_CAPACITY, "%s: no memory for %llu runs", fn, (unsigned long long)take);
+    }
+    if (e == hipSuccess) e = te.start(st);
+    if (e == hipSuccess)
+        e = launch_novel_runs(st, *pan, sq->d_desc, d_chunks.get(), nchunks, sq->d_seqw, sq->d_nmw, sq->d_has_n, nullptr, d_offs.get(), take,
+                              d_se.get(), d_se.get() + take, d_lr.get(), d_lr.get() + take);
+    if (e == hipSuccess) e = te.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(run_start, d_se.get(), take * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(run_end, d_se.get() + take, take * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(left_held, d_lr.get(), take, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(right_held, d_lr.get() + take, take, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    te.read();
+    g_novel_ms[3] = ms_count + ms_emit;
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < sq->n && at < take; ++c)
+        for (uint64_t i = 0; i < per[c] && at < take; ++i) run_contig[at++] = c;
+    return PG_OK;
+}
+
+}  // namespace
+
+extern "C" int pg_novel_create(pg_table *tbl, uint64_t capacity_keys, pg_novel **out) {
+    PG_API_BEGIN
+    if (!tbl || !out) return fail(PG_E_INVALID, "pg_novel_create: NULL argument");
+    return novel_create(tbl, capacity_keys, out);
+    PG_API_END
+}
+
+extern "C" int pg_novel_destroy(pg_novel *nv) {
+    PG_API_BEGIN
+    if (nv) novel_free(nv);
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_novel_clear(pg_novel *nv) {
+    PG_API_BEGIN
+    if (!nv) return fail(PG_E_INVALID, "pg_novel_clear: NULL argument");
+    if (int r = use_device(nv->ctx)) return r;
+    HIP_TRY(hipMemsetAsync(nv->d_keys, 0xFF, nv->nslots * 8, nv->ctx->stream));
+    HIP_TRY(hipMemsetAsync(nv->d_depth, 0, nv->nslots * 4, nv->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(nv->ctx->stream));
+    nv->nkeys = nv->windows = 0;
+    nv->overflowed = false;  // (nothing short is left)
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_novel_add_seqset(pg_novel *nv, const pg_seqset *seqs, uint64_t *windows, uint64_t *hits, uint64_t *new_keys) {
+    PG_API_BEGIN
+    if (!nv || !seqs || !windows || !hits || !new_keys) return fail(PG_E_INVALID, "pg_novel_add_seqset: NULL argument");
+    return novel_add(nv, seqs, windows, hits, new_keys);
+    PG_API_END
+}
+
+extern "C" int pg_novel_stats(pg_novel *nv, uint64_t *nkeys, uint64_t *nslots, uint64_t *grown) {
+    PG_API_BEGIN
+    if (!nv) return fail(PG_E_INVALID, "pg_novel_stats: NULL argument");
+    if (nkeys) *nkeys = nv->nkeys;
+    if (nslots) *nslots = nv->nslots;
+    if (grown) *grown = nv->grown;
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_novel_result(pg_novel *nv, uint32_t min_count, uint64_t *nkeys, uint64_t *solid, uint64_t *solid_windows, uint64_t *depth_hist) {
+    PG_API_BEGIN
+    if (!nv) return fail(PG_E_INVALID, "pg_novel_result: NULL argument");
+    return novel_result(nv, min_count, nkeys, solid, solid_windows, depth_hist);
+    PG_API_END
+}
+
+extern "C" int pg_novel_keys(pg_novel *nv, uint32_t min_count, uint64_t cap, uint64_t *keys, uint32_t *depths, uint64_t *n) {
+    PG_API_BEGIN
+    if (!nv || !n || (cap && (!keys || !depths))) return fail(PG_E_INVALID, "pg_novel_keys: NULL argument");
+    return novel_keys(nv, min_count, cap, keys, depths, n);
+    PG_API_END
+}
+
+extern "C" int pg_novel_runs(pg_table *tbl, const pg_seqset *seqs, uint64_t cap, uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end,
+                             uint8_t *left_held, uint8_t *right_held, uint64_t *nruns, uint64_t *windows, uint64_t *novel_windows) {
+    PG_API_BEGIN
+    if (!tbl || !seqs || !nruns || !windows || !novel_windows || (cap && (!run_contig || !run_start || !run_end || !left_held || !right_held)))
+        return fail(PG_E_INVALID, "pg_novel_runs: NULL argument");
+    return novel_runs(tbl, seqs, cap, run_contig, run_start, run_end, left_held, right_held, nruns, windows, novel_windows);
+    PG_API_END
+}
+
+extern "C" int pg_novel_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_novel_last_timing: NULL argument");
+    std::copy(g_novel_ms, g_novel_ms + 4, ms_out);
+    return PG_OK;
+    PG_API_END
+}

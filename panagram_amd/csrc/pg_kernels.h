@@ -398,6 +398,51 @@ hipError_t launch_table_mark(hipStream_t st, const SubTable &t, const SeqDesc *s
                              const uint32_t *nmw, const uint32_t *has_n, uint8_t *plane, unsigned long long *ctr);
 hipError_t launch_table_screen(hipStream_t st, const SubTable &t, uint32_t ngenomes, const uint8_t *plane, uint32_t min_count,
                                unsigned long long *out);
+// what a sample holds that the pan table does not (pg_novel.hip; the definitions are there).  The novel table: `nslots` (a power of
+// two, at most COPIES_MAX_SLOTS) 8-byte keys, EMPTY_KEY when free, and nslots u32 depths beside them.  A lane walks at most
+// max_probe slots.
+//   count  jobs[j] = (contig, piece): k-mer positions [piece, piece + 1) x NOVEL_JOB of a contig of at least t.k bases; t is only
+//          read.  A valid window whose key t lacks claims the key's slot and adds 1 to its depth.  ctr (zeroed by the caller):
+//          ctr[0] += the valid windows, ctr[1] += those whose key t holds, ctr[2] += the keys newly claimed, ctr[3] += the claims
+//          that gave up (none while the caller keeps keys + positions <= nslots / 2)
+//   grow   every key of the old table claimed in the new one (nslots >= 2 old_slots, all EMPTY_KEY, depths zero) with its depth;
+//          flag[0] (zeroed) becomes nonzero when a claim gave up
+//   scan   offs == NULL  count: out (zeroed, accumulated into) = nkeys, solid (depth >= min_count), solid_windows (the sum of the
+//                        solid depths), depth_hist [NOVEL_BINS] by min(depth, NOVEL_BINS - 1) — NOVEL_SCAN_WORDS words;
+//                        block_solid[b] = the solid keys of slots [b, b + 1) x novel_scan_per_block(nslots), b < novel_scan_blocks(nslots)
+//          offs != NULL  emit: offs[b] = the solid keys of all blocks before b; the solid keys and their depths in slot order to
+//                        out_keys / out_depth (entries at or past cap are never written)
+//   runs   chunk = {contig, first position}: the NOVEL_CHUNK k-mer positions from there, cut at the contig's end, a contig's
+//          chunks consecutive and in order; every contig named holds at least t.k bases and at most 2^32 - 1 k-mer positions.
+//          offs == NULL  count: counts[c] = {run starts, run ends, valid windows, novel windows} of chunk c
+//          offs != NULL  emit: offs[c] = {starts, ends} of all chunks before c; the contig-relative positions of the run starts
+//                        (with left_held) / the exclusive run ends (with right_held) from there on (entries at or past `total`
+//                        are never written)
+constexpr uint32_t NOVEL_BINS = 64, NOVEL_JOB = 1u << 14, NOVEL_CHUNK = 4096, NOVEL_SCAN_SLOTS = 4096, NOVEL_SCAN_WORDS = 3 + NOVEL_BINS;
+#ifndef PG_NOVEL_SCAN_BLOCKS
+#define PG_NOVEL_SCAN_BLOCKS 2048  // (a power of two; tools/novel_rate.py --lib measures another: profiles/novel_rate.txt)
+#endif
+constexpr uint32_t NOVEL_SCAN_BLOCKS = PG_NOVEL_SCAN_BLOCKS;  // blocks of a scan of a large table: every block ends in atomics on the same few words of `out`
+// the consecutive slots one block of the scan takes: a multiple of NOVEL_SCAN_SLOTS, about nslots / NOVEL_SCAN_BLOCKS (at most 2^20)
+__host__ __device__ __forceinline__ uint64_t novel_scan_per_block(uint64_t nslots) {
+    const uint64_t per = (nslots + NOVEL_SCAN_BLOCKS - 1) / NOVEL_SCAN_BLOCKS;
+    return (per + NOVEL_SCAN_SLOTS - 1) / NOVEL_SCAN_SLOTS * NOVEL_SCAN_SLOTS;
+}
+__host__ __device__ __forceinline__ uint32_t novel_scan_blocks(uint64_t nslots) {
+    const uint64_t per = novel_scan_per_block(nslots);
+    return (uint32_t)((nslots + per - 1) / per);
+}
+hipError_t launch_novel_count(hipStream_t st, const SubTable &t, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs, const uint64_t *seqw,
+                              const uint32_t *nmw, const uint32_t *has_n, unsigned long long *keys, uint32_t *depth, uint64_t nslots,
+                              uint32_t max_probe, unsigned long long *ctr);
+hipError_t launch_novel_grow(hipStream_t st, const unsigned long long *old_keys, const uint32_t *old_depth, uint64_t old_slots,
+                             unsigned long long *keys, uint32_t *depth, uint64_t nslots, uint32_t max_probe, unsigned long long *flag);
+hipError_t launch_novel_scan(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t min_count,
+                             unsigned long long *out, uint32_t *block_solid, const uint64_t *offs, uint64_t cap,
+                             unsigned long long *out_keys, uint32_t *out_depth);
+hipError_t launch_novel_runs(hipStream_t st, const SubTable &t, const SeqDesc *sd, const uint2 *chunks, uint32_t nchunks, const uint64_t *seqw,
+                             const uint32_t *nmw, const uint32_t *has_n, uint4 *counts, const ulonglong2 *offs, uint64_t total,
+                             uint32_t *run_start, uint32_t *run_end, uint8_t *left_held, uint8_t *right_held);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

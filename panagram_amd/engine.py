@@ -1135,6 +1135,111 @@ def screen_last_timing() -> dict:
     return dict(zip(("mark_ms", "screen_ms"), (float(x) for x in ms)))
 
 
+NOVEL_BINS = 64  # depth bins of a novel table: bin c = depth c, the last = that depth and beyond
+
+
+class NovelTable:
+    """What a sample holds that a pan table does not (pg_novel.hip): a key table in HBM of the canonical k-mers of the sample's
+    valid windows that ``table`` lacks, a 32-bit depth beside every key — the windows of every sequence set added, both strands,
+    exact.  It starts at ``capacity_keys`` and grows on the device in front of every ``add``; the pan table is only read.  After a
+    re-hash, an insert that added keys, a clear or a regrow of the pan table ``add`` raises (PG_E_INVALID) — make a new one.
+    Closed before its table."""
+
+    def __init__(self, table: "PanTable", capacity_keys: int = 1 << 20):
+        self.table, self._lib = table, table._lib
+        h = C.c_void_p()
+        check(self._lib.pg_novel_create(table._h, int(capacity_keys), C.byref(h)))
+        self._h = h
+        table._adopt(self)
+
+    def add(self, seqs: SeqSet) -> Tuple[int, int, int]:
+        """stream ``seqs`` through the pan table: (its valid windows, those whose k-mer the pan table holds, the novel k-mers
+        this call claimed); depths accumulate over calls"""
+        windows, hits, new = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self._lib.pg_novel_add_seqset(self._h, seqs._h, C.byref(windows), C.byref(hits), C.byref(new)))
+        return int(windows.value), int(hits.value), int(new.value)
+
+    def result(self, min_count: int = 1) -> dict:
+        """one pass over the novel k-mers, a k-mer SOLID when its depth is at least ``min_count``: ``nkeys``, ``solid``,
+        ``solid_windows`` (the sum of the solid depths) and the int64 array ``depth_hist`` [NOVEL_BINS] by min(depth, 63).  The
+        table stays: ask again at another ``min_count``."""
+        if not 1 <= int(min_count) <= 0xFFFFFFFF:
+            raise ValueError(f"min_count {min_count} (1 to 2^32 - 1)")
+        nkeys, solid, sw = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        hist = np.zeros(NOVEL_BINS, np.uint64)
+        check(self._lib.pg_novel_result(self._h, int(min_count), C.byref(nkeys), C.byref(solid), C.byref(sw), _ptr(hist)))
+        return {"nkeys": int(nkeys.value), "solid": int(solid.value), "solid_windows": int(sw.value), "depth_hist": hist.astype(np.int64)}
+
+    def keys(self, min_count: int = 1, cap: Optional[int] = None):
+        """(keys [uint64], depths [uint32]) of the solid k-mers, sorted by key.  ``cap`` (tests of the capacity protocol): ONE call
+        with arrays of ``cap`` entries — the first of them in the table's slot order — returned behind the full number."""
+        if not 1 <= int(min_count) <= 0xFFFFFFFF:
+            raise ValueError(f"min_count {min_count} (1 to 2^32 - 1)")
+        n = C.c_uint64()
+
+        def call(m):
+            k, d = np.zeros(m, np.uint64), np.zeros(m, np.uint32)
+            check(self._lib.pg_novel_keys(self._h, int(min_count), m, _ptr(k) if m else None, _ptr(d) if m else None, C.byref(n)))
+            return k, d
+        if cap is not None:
+            k, d = call(int(cap))
+            return k, d, int(n.value)
+        call(0)
+        k, d = call(int(n.value))
+        order = np.argsort(k, kind="stable")
+        return k[order], d[order]
+
+    def stats(self) -> dict:
+        """``nkeys`` (the novel k-mers held), ``nslots``, ``grown`` (the times the table has grown)"""
+        v = [C.c_uint64() for _ in range(3)]
+        check(self._lib.pg_novel_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("nkeys", "nslots", "grown"), (int(x.value) for x in v)))
+
+    def clear(self) -> None:
+        """every k-mer gone: the next sample"""
+        check(self._lib.pg_novel_clear(self._h))
+
+    def close(self) -> None:
+        if self._h:
+            self._lib.pg_novel_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def novel_runs(table: "PanTable", seqs: SeqSet, cap: Optional[int] = None):
+    """(run_contig, run_start, run_end [uint32], left_held, right_held [uint8], windows, novel_windows): the maximal runs of
+    consecutive valid k-mer positions of the contigs of ``seqs`` whose k-mers ``table`` lacks, positions contig-relative, sorted by
+    (contig, start); ``left_held`` / ``right_held``: the position in front of / behind the run is valid and its k-mer is in the
+    table.  ``cap`` (tests of the capacity protocol): ONE call with arrays of ``cap`` entries, and the full number of runs behind
+    the two window counts."""
+    lib = table._lib
+    nruns, windows, novel = C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+    def call(m):
+        arrs = [np.zeros(m, np.uint32) for _ in range(3)] + [np.zeros(m, np.uint8) for _ in range(2)]
+        check(lib.pg_novel_runs(table._h, seqs._h, m, *[_ptr(a) if m else None for a in arrs], C.byref(nruns), C.byref(windows), C.byref(novel)))
+        return arrs
+    if cap is not None:
+        arrs = call(int(cap))
+        return (*arrs, int(windows.value), int(novel.value), int(nruns.value))
+    call(0)
+    arrs = call(int(nruns.value))
+    return (*arrs, int(windows.value), int(novel.value))
+
+
+def novel_last_timing() -> dict:
+    """HIP-event milliseconds of k_novel_count and k_novel_grow in this thread's last ``NovelTable.add``, of k_novel_scan in its last
+    ``.result`` or ``.keys`` and of k_novel_runs in its last ``novel_runs``"""
+    ms = (C.c_float * 4)()
+    check(_lib.load().pg_novel_last_timing(ms))
+    return dict(zip(("count_ms", "grow_ms", "scan_ms", "runs_ms"), (float(x) for x in ms)))
+
+
 def homology_classes(name_lists: Sequence[Sequence[str]]) -> np.ndarray:
     """``contig_class`` for ``AnchorResult.coschedule`` from the genomes' record ids: contigs with the same id (the same
     chromosome name in different FASTAs) form one class, classes numbered in order of first appearance.  A genome

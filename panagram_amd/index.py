@@ -1550,6 +1550,68 @@ class Index:
             sc.close()
         return scr.frames(counts, names, int(self.k), min_count, tot["windows"], tot["hits"], tot["reads"], tot["read_bases"], genomes)
 
+    def novel(self, samples, min_count: Optional[int] = None, batch_bytes: Optional[int] = None, kmers: bool = False,
+              regions: bool = False, min_bases: int = 0):
+        """(stats, spectrum, kmers, regions) — ``novel.stats``, ``novel.spectrum_frame``, ``novel.kmers_frame`` (None unless
+        ``kmers``), ``novel.regions_frame`` filtered by ``min_bases`` (None unless ``regions``) — of ONE sample from outside the
+        index: the distinct k-mers it holds that NO indexed genome does, their depth spectrum, and for an assembly where they
+        lie.  ``samples``, ``batch_bytes`` and the default of ``min_count`` as ``screen`` takes them; the sample is streamed once
+        through the table of every sample's k-mers and its missing windows are counted in a table of their own that grows on the
+        GPU (``engine.NovelTable``).  A k-mer is solid when the sample holds it at least ``min_count`` times — the only error
+        filter.  ValueError: a missing file, a torn last record, ``min_count`` outside 1..2^32 - 1, a negative ``min_bases``,
+        ``regions`` with a FASTQ file (regions need an assembly); RuntimeError: the cached table holds some anchors' k-mers
+        only."""
+        from . import novel as nov, place as pl
+        samples = [samples] if isinstance(samples, (str, os.PathLike)) else list(samples)
+        paths = [os.fspath(p) for p in samples]
+        for p in paths:
+            if not os.path.isfile(p):
+                raise ValueError(f"novel: no sample file {p!r}")
+        if regions and any(is_fastq(p) for p in paths):
+            raise ValueError("novel: regions need an assembly: " + ", ".join(repr(p) for p in paths if is_fastq(p)) + " is FASTQ")
+        if int(min_bases) < 0:
+            raise ValueError(f"novel: min_bases={min_bases} must not be negative")
+        min_count = nov.check_min_count(nov.default_min_count(any(is_fastq(p) for p in paths)) if min_count is None else min_count)
+        batch_bytes = pl.DEFAULT_BATCH_BYTES if batch_bytes is None else int(batch_bytes)
+        if batch_bytes < 1:
+            raise ValueError(f"novel: batch_bytes must be positive, got {batch_bytes}")
+        ctx, k = self.context, int(self.k)
+        table = self._full_table()
+        nt = engine.NovelTable(table)
+        tot = {"windows": 0, "hits": 0, "reads": 0, "read_bases": 0}
+        found = []
+
+        def add(ss, reads, bases):
+            w, h, _ = nt.add(ss)
+            for f, v in (("windows", w), ("hits", h), ("reads", reads), ("read_bases", bases)):
+                tot[f] += int(v)
+        try:
+            for p in paths:
+                if is_fastq(p):
+                    fb = pl.FastqBatches(p, batch_bytes)
+                    for buf in fb:
+                        rs, n, used = engine.SeqSet.from_fastq(ctx, buf)
+                        try:
+                            add(rs, n, int(rs.lens[0]) - max(n - 1, 0))
+                        finally:
+                            rs.close()
+                        fb.advance(used)
+                else:
+                    ss = engine.SeqSet.from_fasta(ctx, p)
+                    try:
+                        add(ss, len(ss.lens), int(np.asarray(ss.lens, np.uint64).sum()))
+                        if regions:
+                            found.append(nov.regions_frame(p, ss.names, *engine.novel_runs(table, ss)[:5], k))
+                    finally:
+                        ss.close()
+            counts = nt.result(min_count)
+            kmers_df = nov.kmers_frame(*nt.keys(min_count), k) if kmers else None
+        finally:
+            nt.close()
+        regions_df = nov.filter_regions(pd.concat(found, ignore_index=True) if found else nov.no_regions(), min_bases) if regions else None
+        st = nov.stats(counts, min_count, tot["windows"], tot["hits"], tot["reads"], tot["read_bases"], regions_df)
+        return st, nov.spectrum_frame(counts["depth_hist"]), kmers_df, regions_df
+
     def locate(self, queries, genomes=None, k=None, min_run: int = 1, max_gap: int = 1000, max_shift: int = 100, min_kmers: int = 1,
                min_frac: float = 0.0):
         """(loci, matrix, summary) — ``locate.frames`` — of query sequences: WHERE each lies in the assemblies of the ``genomes``

@@ -389,6 +389,16 @@ int pg_result_extract_columns_range(pg_result *r, uint32_t g0, uint32_t width, u
                                     void *d_dst);
 int pg_result_merge_columns_range(pg_result *r, const void *d_src, uint32_t part0, uint32_t nparts, uint32_t per,
                                   uint32_t first_contig, uint32_t ncontigs, int accumulate, uint64_t part_stride_bytes);
+/* Appending genomes to finished rows (no reference counterpart: to add a genome the reference re-runs its whole
+ * workflow).  src holds the rows of N_old genomes — e.g. read back from bitmap.1.gz (pg_result_inflate_bgzf) — and
+ * d_cols nparts column blocks of `per` genomes each in the layout of pg_result_extract_columns_range /
+ * pg_anchor_run_columns_range over src's contigs (part_stride_bytes apart; 0: the block's own size).  dst, a result of
+ * N_new genomes with N_old <= N_new <= N_old + nparts*per, gets its rows of contigs dst_first_contig .. dst_first_contig
+ * + n - 1 (n = src's contigs; they must have the same k-mer counts as dst's, PG_E_INVALID otherwise) written whole in one
+ * pass: bits below N_old copied, genome j of block i as bit N_old + i*per + j, bits at and past N_new zero.  Bits at and
+ * past N_old in the source's last byte are ignored.  Finish with pg_rows_epilogue.  Asynchronous on the context's stream. */
+int pg_result_append_columns_range(pg_result *dst, uint32_t dst_first_contig, const pg_result *src, const void *d_cols,
+                                   uint32_t nparts, uint32_t per, uint64_t part_stride_bytes);
 /* bitmap.100 rows, bin histograms and column sums from the (combined) bitmap.1 rows in the
  * result's device buffer; async.  Same outputs as the fused pg_anchor_run path. */
 int pg_rows_epilogue(pg_result *r);

@@ -38,7 +38,10 @@ through the table of every sample's k-mers and counted per k-mer, and one pass o
 masks on the GPU; and
 `novel <index_dir> <sample.fq|sample.fa> [more ...] [--min-count N] [--spectrum FILE] [--kmers FILE] [--regions FILE] [--min-bases B]
 [--summary FILE]` says the reverse: the distinct k-mers of the sample that NO indexed genome holds, their depth spectrum, and for an
-assembly where they lie — the sample's windows that miss the table are counted in a key table of their own that grows on the GPU."""
+assembly where they lie — the sample's windows that miss the table are counted in a key table of their own that grows on the GPU; and
+`add <index_dir> <new_samples.tsv>` appends samples to a finished index without re-anchoring it: every anchor already there is probed
+against the new samples' k-mers alone, its rows come back from bitmap.1.gz, and one kernel pass writes the wider rows; new anchors are
+anchored the ordinary way, and the tree is staged and renamed at the end, samples.tsv last."""
 import argparse
 import os
 import sys
@@ -264,6 +267,11 @@ def main(argv=None):
     nvl.add_argument("--summary", metavar="FILE", default=None, help="also write the statistics to FILE")
     nvl.add_argument("--batch-bytes", type=int, default=None, metavar="N", help="FASTQ text bytes joined at a time (default 2^28)")
     nvl.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    ad = sub.add_parser("add", help="append the samples of a samples table to an existing index without re-anchoring it: the anchors "
+                                    "already there get their rows widened on the GPU by the new samples' columns, new anchors are anchored")
+    ad.add_argument("index_dir")
+    ad.add_argument("new_samples", metavar="new_samples.tsv", help="name, fasta, optional gff and anchor columns: the NEW samples only")
+    ad.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -283,6 +291,26 @@ def main(argv=None):
                     kmc=KMC(use_existing=a.use_existing), genome_dist=a.genome_dist, annotate=a.annotate, umaps=a.umaps,
                     kmer_stats=a.kmer_stats)
         idx.run()
+        return 0
+    if a.cmd == "add":
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"add: {a.index_dir!r} is not an index directory")
+        if not os.path.isfile(a.new_samples):
+            ap.error(f"add: no samples table {a.new_samples!r}")
+        from .index import Index
+        try:
+            idx = Index(a.index_dir, mode="w", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"add: {e}")
+        try:
+            try:
+                lines = idx.add(a.new_samples)
+            except ValueError as e:
+                ap.error(str(e))
+        finally:
+            idx.close()
+        for line in lines:
+            print(line)
         return 0
     if a.cmd == "dist":
         from .index import Index

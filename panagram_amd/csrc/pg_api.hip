@@ -1728,6 +1728,39 @@ extern "C" int pg_result_merge_columns(pg_result *r, const void *d_src, uint32_t
     PG_API_END
 }
 
+// `add`: src's rows of src->N genomes + column blocks -> dst's rows of dst->N genomes, src's contigs 0..n-1 being dst's from
+// dst_first_contig on (an anchor's old rows come back from its file in batches of chromosomes; dst holds the whole anchor)
+static int append_columns_range(pg_result *dst, uint32_t dst_first_contig, const pg_result *src, const void *d_cols, uint32_t nparts,
+                                uint32_t per, uint64_t part_stride_bytes) {
+    const char *fn = "pg_result_append_columns_range";
+    if (!dst || !src || !d_cols) return fail(PG_E_INVALID, "%s: NULL argument", fn);
+    if (dst == src || dst->ctx != src->ctx) return fail(PG_E_INVALID, "%s: source and destination must be two results of one context", fn);
+    if (per == 0 || nparts == 0) return fail(PG_E_INVALID, "%s: empty block", fn);
+    if ((src->flags | dst->flags) & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "%s: a columns-only result has no rows", fn);
+    if (!src->ev_ok && !src->rows_valid) return fail(PG_E_INVALID, "%s: the source holds no rows yet", fn);
+    if (src->N > dst->N || (uint64_t)src->N + (uint64_t)nparts * per < dst->N)
+        return fail(PG_E_INVALID, "%s: %u genomes and %u blocks of %u do not make the destination's %u", fn, src->N, nparts, per, dst->N);
+    const size_t n = src->ad.size();
+    if ((uint64_t)dst_first_contig + n > dst->ad.size())
+        return fail(PG_E_INVALID, "%s: contigs %u..%zu out of range (the destination has %zu)", fn, dst_first_contig, dst_first_contig + n, dst->ad.size());
+    for (size_t c = 0; c < n; ++c)  // the same geometry on both sides: the source's tiles line up with the destination's
+        if (src->ad[c].nkmers != dst->ad[dst_first_contig + c].nkmers)
+            return fail(PG_E_INVALID, "%s: contig %zu has %u k-mers in the source, %u in the destination", fn, c, src->ad[c].nkmers,
+                        dst->ad[dst_first_contig + c].nkmers);
+    const uint64_t own = (uint64_t)src->ntiles * (PROBE_TILE / 8) * per;
+    if (part_stride_bytes == 0) part_stride_bytes = own;
+    if (part_stride_bytes < own || part_stride_bytes % 8) return fail(PG_E_INVALID, "%s: bad block stride", fn);
+    if (int e = use_device(dst->ctx)) return e;
+    if (int e = join_result(dst)) return e;
+    if (int e = join_result(const_cast<pg_result *>(src))) return e;
+    HIP_TRY(launch_rows_append(dst->ctx->stream, src->N, dst->N, src->d_ad, src->d_tile_contig, src->ntiles, src->d_out1, dst->d_ad,
+                               dst_first_contig, dst->d_out1, d_cols, nparts, part_stride_bytes / 8, per));
+    dst->rows_valid = true;
+    return PG_OK;
+}
+
+extern "C" int pg_result_append_columns_range(pg_result *dst, uint32_t dst_first_contig, const pg_result *src, const void *d_cols, uint32_t nparts, uint32_t per, uint64_t part_stride_bytes) { return pg::guarded([&]() -> int { return append_columns_range(dst, dst_first_contig, src, d_cols, nparts, per, part_stride_bytes); }); }
+
 extern "C" int pg_rows_epilogue(pg_result *r) {
     PG_API_BEGIN
     if (!r) return fail(PG_E_INVALID, "result is NULL");

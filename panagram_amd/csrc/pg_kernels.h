@@ -167,6 +167,11 @@ hipError_t launch_cols_extract(hipStream_t st, uint32_t ngenomes, const AnchorDe
 hipError_t launch_cols_merge(hipStream_t st, uint32_t ngenomes, const AnchorDesc *ad, const uint32_t *tile_contig,
                              uint32_t tile_base, uint32_t ntiles, uint8_t *out1, const void *src, uint32_t part0,
                              uint32_t nparts, uint64_t part_words, uint32_t per, uint32_t accumulate);
+// the rows of n_old genomes of one result (all of its ntiles tiles) + nparts column blocks of `per` genomes, indexed by those
+// tiles -> the rows of n_new genomes of another result from contig dst_first_contig on (contigs of the same nkmers)
+hipError_t launch_rows_append(hipStream_t st, uint32_t n_old, uint32_t n_new, const AnchorDesc *src_ad, const uint32_t *src_tile_contig,
+                              uint32_t ntiles, const uint8_t *src_rows, const AnchorDesc *dst_ad, uint32_t dst_first_contig,
+                              uint8_t *dst_rows, const void *cols, uint32_t nparts, uint64_t part_words, uint32_t per);
 // every step-th row of bitmap.1 -> low-resolution bitmap (steps other than 100)
 hipError_t launch_lowres(hipStream_t st, uint32_t ngenomes, const AnchorDesc *ad, const uint32_t *tile_contig,
                          uint32_t ntiles, const uint8_t *out1, uint8_t *outlow, uint32_t step);

@@ -16,6 +16,7 @@
 //                16-byte chunk of the rows it visits, one launch reads every row once.
 //   k_window_stats, k_cols_extract / k_cols_merge: side paths (gene / bin windows; the
 //                genome-sharded exchange).
+//   k_rows_append*  finished rows of N genomes + column blocks of m more -> rows of N + m genomes in one pass (`add`).
 //   k_lowres, k_tile_reduce: the low-resolution bitmap for steps other than 100; the per-tile counters of a fused k_probe launch
 //                (FuseArgs, pg_kernels.h) into the bins and column sums.
 #include "pg_kernels.h"
@@ -1620,6 +1621,166 @@ __global__ __launch_bounds__(256) void k_cols_merge(uint32_t N, const AnchorDesc
     }
 }
 
+// ---------------------------------------------------------------------------
+// append (no reference counterpart: the reference re-runs its whole workflow to add a genome): the finished rows of n_old
+// genomes of ONE result plus column blocks of further genomes (the layout above: what the probe of a narrow table or
+// k_cols_extract* writes) -> the rows of n_new genomes of ANOTHER result over contigs of the same lengths.  Every
+// destination row is written whole, once: bits below n_old copied, bits n_old .. n_new - 1 from the blocks (genome j of
+// block i is bit n_old + i * per + j), the rest zero; the bits at and past n_old of the source's last byte are dropped
+// (the source comes from a file).  Composed of what was there before — k_cols_extract of all old genomes, k_cols_merge,
+// k_cols_merge(accumulate) — every row is read and written more than twice, and a column copy of the whole bitmap is
+// needed; here W_old + W_new + m / 8 bytes move per position.
+// The source's tiles 0 .. ntiles - 1 are the destination's from contig dst_c0 on (same nkmers, contig by contig: the
+// host checks it), the blocks are indexed by the source's tiles.
+// ---------------------------------------------------------------------------
+struct AppendArgs {
+    const AnchorDesc *sad;          // the source's contigs, tiles and rows
+    const uint32_t *stile_contig;
+    const uint8_t *src;
+    const AnchorDesc *dad;          // the destination's contigs and rows
+    uint8_t *dst;
+    const unsigned long long *cols;
+    uint64_t part_words;            // distance between two blocks
+    uint32_t ntiles, dst_c0, nparts, per, n_old, n_new;
+};
+
+// One-byte rows on both sides (n_new <= 8), after k_cols_merge_b1: 16 positions per lane, one aligned 16-byte load and
+// store, COLS_TPW tiles per wave.  The up to 7 new genomes' two bytes are all asked for before the first one is used (in
+// a loop over the genomes every load would be waited for in turn), beside the tiles' old rows.
+__global__ __launch_bounds__(256) void k_rows_append_b1(AppendArgs A) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t t0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * COLS_TPW;
+    if (t0 >= A.ntiles) return;  // wave-uniform
+    const uint32_t m = A.n_new - A.n_old;  // (<= 8)
+    uint4 old[COLS_TPW];
+    uint4 *rowp[COLS_TPW];
+    uint32_t valid[COLS_TPW], b2[COLS_TPW][8];
+#pragma unroll
+    for (uint32_t k = 0; k < COLS_TPW; ++k) {
+        old[k] = make_uint4(0, 0, 0, 0);
+        rowp[k] = nullptr;
+        valid[k] = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < 8; ++q) b2[k][q] = 0;
+        if (t0 + k < A.ntiles) {  // (wave-uniform)
+            const uint32_t tile = t0 + k, c = A.stile_contig[tile];
+            const AnchorDesc sa = A.sad[c];
+            const uint32_t p0 = (tile - sa.tile0) * PROBE_TILE + 16 * lane;
+            if (p0 < sa.nkmers) {  // (rows are padded to 16 bytes per contig on both sides: the aligned 16-byte accesses stay inside)
+                old[k] = *reinterpret_cast<const uint4 *>(A.src + sa.out_off + p0);
+                rowp[k] = reinterpret_cast<uint4 *>(A.dst + A.dad[A.dst_c0 + c].out_off + p0);
+                valid[k] = min(16u, sa.nkmers - p0);
+                const uint8_t *in = reinterpret_cast<const uint8_t *>(A.cols) + ((uint64_t)tile * TILE_SLOTS + (lane >> 2)) * A.per * 8 + 2 * (lane & 3);
+#pragma unroll
+                for (uint32_t q = 0; q < 8; ++q)
+                    if (q < m) b2[k][q] = *reinterpret_cast<const uint16_t *>(in + (uint64_t)(q / A.per) * A.part_words * 8 + 8 * (q % A.per));
+            }
+        }
+    }
+    const uint32_t keep = ((1u << A.n_old) - 1u) * 0x01010101u;  // the old genomes' bits of four rows
+#pragma unroll
+    for (uint32_t k = 0; k < COLS_TPW; ++k) {
+        if (!rowp[k]) continue;
+        uint32_t w[4] = {old[k].x & keep, old[k].y & keep, old[k].z & keep, old[k].w & keep};
+#pragma unroll
+        for (uint32_t q = 0; q < 8; ++q) {
+            if (q >= m) break;  // (uniform)
+            const uint32_t g = A.n_old + q;
+            const uint32_t r0 = (b2[k][q] & 0xFFu) * 0x01010101u, r1 = (b2[k][q] >> 8) * 0x01010101u;  // bit i of a byte -> bit 0 of byte i
+            w[0] |= ((((r0 & 0x08040201u) + 0x7F7F7F7Fu) >> 7) & 0x01010101u) << g;
+            w[1] |= ((((r0 & 0x80402010u) + 0x7F7F7F7Fu) >> 7) & 0x01010101u) << g;
+            w[2] |= ((((r1 & 0x08040201u) + 0x7F7F7F7Fu) >> 7) & 0x01010101u) << g;
+            w[3] |= ((((r1 & 0x80402010u) + 0x7F7F7F7Fu) >> 7) & 0x01010101u) << g;
+        }
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {  // positions past the contig's end: the destination's padding stays zero whatever the source's and the blocks hold there
+            const uint32_t nv = valid[k] > 4 * i ? min(4u, valid[k] - 4 * i) : 0u;
+            w[i] &= nv >= 4 ? 0xFFFFFFFFu : (1u << (8 * nv)) - 1u;
+        }
+        *rowp[k] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
+// Every other pair of widths.  A lane owns one position, the wave one slot of 64 — the 64 W_old and 64 W_new bytes of a
+// slot are each one contiguous span that starts on a 16-byte boundary (a contig's rows do; 64 W bytes per slot), and the wave covers it with ceil(W / 4) accesses of
+// one 32-bit word per lane at a stride of W bytes: rows that start off word boundaries (odd widths) are read and written
+// with unaligned words, which global memory serves, the span's cache lines being shared by the wave's few instructions
+// back to back (k_cols_extract reads its rows the same way).  A row's tail of 1..3 bytes is stored as a 16-bit word and /
+// or a byte: the next row belongs to the next lane.  The last word read of a row may reach up to 3 bytes past it — into
+// the next row, the contig's padding or the 16 bytes of slack behind the buffer — and is masked to the old genomes' bits.
+// The new genomes' u64 of a slot are the same for the whole wave: lane l fetches the one of bit l of the row word at hand
+// (one coalesced access per 32 genomes, as in k_cols_merge) and the wave reads them lane by lane.  NW = words per new row,
+// SPW = slots of one tile per wave: all of their loads, old words and column words, are in flight before the first is used;
+// NW = 0: any width, word by word.  (One slot per wave — 1.6 million waves for 10^8 positions, each one waiting for its
+// tile's contig number, then the contig's descriptor, then its rows — took 0.42 / 0.49 / 0.63 ms at 8 -> 9 / 16 -> 17 /
+// 64 -> 65 genomes whatever the bytes: 9 to 34 % of the byte floor; profiles/add_rate.txt.)
+struct __attribute__((packed)) U16 { uint16_t v; };
+template <int NW, int SPW>
+__global__ __launch_bounds__(256) void k_rows_append(AppendArgs A) {
+    static_assert(TILE_SLOTS % SPW == 0, "a wave's slots lie in one tile");
+    constexpr uint32_t WPT = TILE_SLOTS / SPW;  // waves per tile
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wave >= (uint64_t)A.ntiles * WPT) return;  // wave-uniform
+    const uint32_t tile = (uint32_t)(wave / WPT), sub0 = (uint32_t)(wave % WPT) * SPW;
+    const uint32_t c = A.stile_contig[tile];
+    const AnchorDesc sa = A.sad[c];
+    const uint32_t n_old = A.n_old, n_new = A.n_new, wo = (n_old + 7) / 8, wn = (n_new + 7) / 8;
+    const uint32_t p0 = (tile - sa.tile0) * PROBE_TILE + sub0 * 64 + lane;  // this lane's position in the wave's first slot
+    const uint64_t slot0 = (uint64_t)tile * TILE_SLOTS + sub0;
+    const uint8_t *sbase = A.src + sa.out_off;
+    uint8_t *dbase = A.dst + A.dad[A.dst_c0 + c].out_off;
+    auto load_old = [&](uint32_t s, uint32_t d) -> uint32_t {  // word d of the old row of slot s
+        const uint32_t p = p0 + 64u * s;
+        return (p < sa.nkmers && 4u * d < wo) ? reinterpret_cast<const U32 *>(sbase + (uint64_t)p * wo + 4u * d)->v : 0u;
+    };
+    auto load_cols = [&](uint32_t s, uint32_t d) -> unsigned long long {  // lane l: slot s's u64 of genome 32 d + l, if it is a new one
+        const uint32_t gl = 32u * d + ((uint32_t)lane & 31u);
+        if (lane >= 32 || gl < n_old || gl >= n_new) return 0ull;
+        const uint32_t q = gl - n_old;
+        return A.cols[(uint64_t)(q / A.per) * A.part_words + (slot0 + s) * A.per + q % A.per];
+    };
+    auto store_word = [&](uint32_t s, uint32_t d, uint32_t oldw, unsigned long long mine) {
+        const uint32_t lo = 32u * d;
+        const uint32_t vb = n_old > lo ? min(32u, n_old - lo) : 0u;  // bits of this word that are old genomes'
+        uint32_t w = oldw & (vb >= 32u ? 0xFFFFFFFFu : (1u << vb) - 1u);
+        const uint32_t b_lo = vb, b_hi = n_new > lo ? min(32u, n_new - lo) : 0u;
+        for (uint32_t b = b_lo; b < b_hi; ++b) {  // (uniform)
+            const unsigned long long word = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), (int)b) << 32) |
+                                            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, (int)b);
+            w |= (__builtin_amdgcn_inverse_ballot_w64(word) ? 1u : 0u) << b;
+        }
+        const uint32_t p = p0 + 64u * s;
+        if (p >= sa.nkmers) return;
+        uint8_t *o = dbase + (uint64_t)p * wn + 4u * d;
+        const uint32_t n = min(4u, wn - 4u * d);  // (uniform)
+        if (n == 4) {
+            reinterpret_cast<U32 *>(o)->v = w;
+        } else {
+            if (n >= 2) reinterpret_cast<U16 *>(o)->v = (uint16_t)w;
+            if (n & 1) o[n - 1] = (uint8_t)(w >> (8 * (n - 1)));
+        }
+    };
+    if constexpr (NW > 0) {
+        uint32_t oldw[SPW][NW];
+        unsigned long long mine[SPW][NW];
+#pragma unroll
+        for (int s = 0; s < SPW; ++s)
+#pragma unroll
+            for (int d = 0; d < NW; ++d) {
+                oldw[s][d] = load_old(s, d);
+                mine[s][d] = load_cols(s, d);
+            }
+#pragma unroll
+        for (int s = 0; s < SPW; ++s)
+#pragma unroll
+            for (int d = 0; d < NW; ++d) store_word(s, d, oldw[s][d], mine[s][d]);
+    } else {
+        for (uint32_t s = 0; s < (uint32_t)SPW; ++s)
+            for (uint32_t d = 0; 4u * d < wn; ++d) store_word(s, d, load_old(s, d), load_cols(s, d));
+    }
+}
+
 // every step-th row of bitmap.1 -> the low-resolution bitmap, for steps other than the 100 the statistics
 // kernels fuse (index.py:101-106 lowres_step): one wave per tile, a handful of rows each
 __global__ __launch_bounds__(64) void k_lowres(uint32_t N, const AnchorDesc *__restrict__ ad,
@@ -1848,6 +2009,36 @@ hipError_t launch_cols_merge(hipStream_t st, uint32_t ngenomes, const AnchorDesc
         hipLaunchKernelGGL(k_cols_merge, dim3((unsigned)(((uint64_t)ntiles * TILE_SLOTS + 3) / 4)), dim3(256), 0, st, ngenomes, ad,
                            tile_contig, tile_base, ntiles, out1, static_cast<const unsigned long long *>(src), part0, nparts,
                            part_words, per, accumulate);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_append(hipStream_t st, uint32_t n_old, uint32_t n_new, const AnchorDesc *src_ad, const uint32_t *src_tile_contig,
+                              uint32_t ntiles, const uint8_t *src_rows, const AnchorDesc *dst_ad, uint32_t dst_first_contig,
+                              uint8_t *dst_rows, const void *cols, uint32_t nparts, uint64_t part_words, uint32_t per) {
+    if (ntiles == 0) return hipSuccess;
+    AppendArgs A;
+    A.sad = src_ad;
+    A.stile_contig = src_tile_contig;
+    A.src = src_rows;
+    A.dad = dst_ad;
+    A.dst = dst_rows;
+    A.cols = static_cast<const unsigned long long *>(cols);
+    A.part_words = part_words;
+    A.ntiles = ntiles;
+    A.dst_c0 = dst_first_contig;
+    A.nparts = nparts;
+    A.per = per;
+    A.n_old = n_old;
+    A.n_new = n_new;
+    const uint32_t nw = ((n_new + 7) / 8 + 3) / 4;  // words per new row
+    auto grid = [&](uint32_t spw) { return dim3((unsigned)(((uint64_t)ntiles * (TILE_SLOTS / spw) + 3) / 4)); };
+    if (n_new <= 8) hipLaunchKernelGGL(k_rows_append_b1, dim3((unsigned)(((uint64_t)ntiles + 4 * COLS_TPW - 1) / (4 * COLS_TPW))), dim3(256), 0, st, A);
+    else if (nw == 1) hipLaunchKernelGGL((k_rows_append<1, 8>), grid(8), dim3(256), 0, st, A);
+    else if (nw == 2) hipLaunchKernelGGL((k_rows_append<2, 8>), grid(8), dim3(256), 0, st, A);
+    else if (nw == 3) hipLaunchKernelGGL((k_rows_append<3, 4>), grid(4), dim3(256), 0, st, A);
+    else if (nw == 4) hipLaunchKernelGGL((k_rows_append<4, 4>), grid(4), dim3(256), 0, st, A);
+    else if (nw == 5) hipLaunchKernelGGL((k_rows_append<5, 4>), grid(4), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((k_rows_append<0, 4>), grid(4), dim3(256), 0, st, A);
     return hipGetLastError();
 }
 

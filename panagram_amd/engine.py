@@ -1426,6 +1426,16 @@ class AnchorResult:
         check(self._lib.pg_result_merge_columns_range(self._h, C.c_void_p(dev_ptr), part0, nparts, per, first_contig,
                                                       ncontigs, 1 if accumulate else 0, part_stride_bytes))
 
+    def append_columns(self, src: "AnchorResult", dev_ptr: int, nparts: int, per: int, first_contig: int = 0,
+                       part_stride_bytes: int = 0) -> None:
+        """``src``'s finished rows (fewer genomes; its contigs 0..n-1 are this result's from ``first_contig`` on, with the
+        same k-mer counts) + ``nparts`` column blocks of ``per`` genomes at ``dev_ptr`` (the layout of
+        ``extract_columns_range`` / ``run_columns_range`` over ``src``'s contigs, ``part_stride_bytes`` apart; 0: the
+        block's own size) -> this result's rows, written whole in one pass (async): genome j of block i becomes bit
+        ``src.ngenomes + i * per + j``.  ``rows_epilogue`` finishes them."""
+        check(self._lib.pg_result_append_columns_range(self._h, first_contig, src._h, C.c_void_p(dev_ptr), nparts, per,
+                                                       part_stride_bytes))
+
     def rows_tensor(self):
         """Zero-copy torch uint8 view of the device bitmap.1 buffer (for RCCL collectives)."""
         import torch

@@ -569,8 +569,11 @@ class Index:
         write(tmp)
         os.replace(tmp, path)
 
-    def _normalised_samples(self, table: pd.DataFrame) -> pd.DataFrame:
-        """The user's table -> the schema samples.tsv is stored in: index ``name``; columns fasta, gff, id, anchor."""
+    @staticmethod
+    def normalise_samples(table: pd.DataFrame, anchor_genomes=None, first_id: int = 0):
+        """A user's samples table -> (the schema samples.tsv is stored in — index ``name``; columns fasta, gff, id, anchor —
+        and the anchor genomes).  ``anchor_genomes`` None: the table's own anchor column, else every sample with a FASTA.
+        Ids count from ``first_id`` (``add``: they continue from the index's)."""
         if not {"name", "fasta"} <= set(table.columns):
             raise ValueError("Input samples must contain 'name' and 'fasta' column headers")
         bad = [str(n) for n in table["name"] if not re.fullmatch(NAME_REGEX, str(n))]
@@ -578,12 +581,16 @@ class Index:
             raise ValueError("Invalid genome names: '" + "', '".join(bad) + f"'\nMust match r'{NAME_REGEX}'.")
         out = table.reindex(columns=["name", "fasta", "gff"] + (["anchor"] if "anchor" in table else []))
         out = out.set_index("name").dropna(how="all")
-        out["id"] = np.arange(len(out), dtype=int)
-        if self.anchor_genomes is None:  # the table's own anchor column, else every sample with a FASTA
+        out["id"] = np.arange(len(out), dtype=int) + int(first_id)
+        if anchor_genomes is None:
             chosen = out["anchor"].astype(bool) if "anchor" in out else out["fasta"].notna()
-            self.anchor_genomes = list(out.index[chosen])
-        out["anchor"] = out.index.isin(self.anchor_genomes)
-        return out[list(self.SAMPLE_COLUMNS)]
+            anchor_genomes = list(out.index[chosen])
+        out["anchor"] = out.index.isin(anchor_genomes)
+        return out[list(Index.SAMPLE_COLUMNS)], anchor_genomes
+
+    def _normalised_samples(self, table: pd.DataFrame) -> pd.DataFrame:
+        out, self.anchor_genomes = self.normalise_samples(table, self.anchor_genomes)
+        return out
 
     def init_config(self):
         samples = self._normalised_samples(pd.read_table(self.input))
@@ -1097,6 +1104,22 @@ class Index:
         finally:
             if own_group:
                 self._dist().destroy_process_group()
+
+    add_breakdown = False  # ``add``: also time probe / inflate / append / statistics into ``timings`` (a device synchronise after each)
+
+    def add(self, new_samples) -> List[str]:
+        """Append samples to this finished index without re-anchoring it (add.py; no reference counterpart).  ``new_samples``:
+        a table (path or DataFrame) in the input schema of ``samples.tsv`` — name, fasta, optional gff and anchor — listing the
+        NEW samples only; ids continue from this index's.  Every anchor already in the index gets its rows widened by the new
+        samples' columns (its FASTA probed against the new samples' k-mers alone, its old rows read back from bitmap.1.gz, one
+        kernel pass: ``AnchorResult.append_columns``) and all of its files rewritten by the code that writes them in ``run``;
+        new anchors are anchored the ordinary way.  Everything is staged inside the index and renamed at the end, samples.tsv
+        last.  Refused before any file is touched (ValueError): a name already in the index, a missing FASTA, an old anchor
+        without bitmap.1.gz or chrs.tsv, more than one process, a read-only index.  Returns one line per anchor rewritten and
+        per anchor added.  Afterwards this object describes all N + m samples and is left as ``run`` leaves it: ``close()``d —
+        table, packed sequences and GPU context freed; a later call makes a context again."""
+        from . import add as _add
+        return _add.add(self, new_samples)
 
     def _ensure_process_group(self) -> bool:
         """Under a launcher that set up a rendezvous (torchrun: MASTER_ADDR / MASTER_PORT, RANK, WORLD_SIZE) a run with

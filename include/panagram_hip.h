@@ -399,6 +399,16 @@ int pg_result_merge_columns_range(pg_result *r, const void *d_src, uint32_t part
  * past N_old in the source's last byte are ignored.  Finish with pg_rows_epilogue.  Asynchronous on the context's stream. */
 int pg_result_append_columns_range(pg_result *dst, uint32_t dst_first_contig, const pg_result *src, const void *d_cols,
                                    uint32_t nparts, uint32_t per, uint64_t part_stride_bytes);
+/* Selecting genomes out of finished rows (no reference counterpart: to drop or reorder samples the reference re-runs its
+ * whole workflow).  src holds the rows of N_old genomes — e.g. read back from bitmap.1.gz (pg_result_inflate_bgzf) — and
+ * sel, a host array, nsel distinct column numbers below N_old in any order.  dst, a result of N_new = nsel genomes, gets its
+ * rows of contigs dst_first_contig .. dst_first_contig + n - 1 (n = src's contigs; they must have the same k-mer counts as
+ * dst's, PG_E_INVALID otherwise) written whole in one pass: bit j = src's bit sel[j], bits at and past N_new zero.  Bits at
+ * and past N_old in the source's last byte are ignored.  PG_E_INVALID, with nothing launched, also for nsel == 0 or
+ * != N_new, an entry >= N_old or given twice, src == dst, a source that holds no rows.  Finish with pg_rows_epilogue.
+ * Asynchronous on the context's stream (sel is read before the call returns). */
+int pg_result_select_columns_range(pg_result *dst, uint32_t dst_first_contig, const pg_result *src, const uint32_t *sel,
+                                   uint32_t nsel);
 /* bitmap.100 rows, bin histograms and column sums from the (combined) bitmap.1 rows in the
  * result's device buffer; async.  Same outputs as the fused pg_anchor_run path. */
 int pg_rows_epilogue(pg_result *r);

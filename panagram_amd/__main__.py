@@ -41,7 +41,10 @@ masks on the GPU; and
 assembly where they lie — the sample's windows that miss the table are counted in a key table of their own that grows on the GPU; and
 `add <index_dir> <new_samples.tsv>` appends samples to a finished index without re-anchoring it: every anchor already there is probed
 against the new samples' k-mers alone, its rows come back from bitmap.1.gz, and one kernel pass writes the wider rows; new anchors are
-anchored the ordinary way, and the tree is staged and renamed at the end, samples.tsv last."""
+anchored the ordinary way, and the tree is staged and renamed at the end, samples.tsv last; and
+`subset <index_dir> -o <out_dir> (--keep A,B,... | --drop C,D,...) [--anchors A,B] [--no-sequence-files]` writes an index of the
+chosen samples into a new directory: the kept anchors' rows come back from bitmap.1.gz and one kernel pass takes the kept columns
+out of them, in the order asked for; no sequence is read."""
 import argparse
 import os
 import sys
@@ -272,6 +275,17 @@ def main(argv=None):
     ad.add_argument("index_dir")
     ad.add_argument("new_samples", metavar="new_samples.tsv", help="name, fasta, optional gff and anchor columns: the NEW samples only")
     ad.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    sb = sub.add_parser("subset", help="write an index of chosen samples of an existing index into a new directory: the kept anchors get "
+                                       "their rows narrowed on the GPU, no sequence is read")
+    sb.add_argument("index_dir")
+    sb.add_argument("-o", "--out", required=True, metavar="out_dir", help="the new index directory (absent or empty)")
+    sb.add_argument("--keep", default=None, metavar="A,B,...", help="the samples to keep, in this order")
+    sb.add_argument("--drop", default=None, metavar="C,D,...", help="the samples to leave out; the rest keep the index's order")
+    sb.add_argument("--anchors", default=None, metavar="A,B", help="write only these of the kept anchors")
+    sb.add_argument("--no-sequence-files", action="store_true",
+                    help="leave out kmc/bitvec*, genome_dist.tsv, kmer_shared.tsv and kmer_occupancy.tsv instead of refreshing them from the "
+                         "kept samples' FASTA files")
+    sb.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     um = sub.add_parser("umaps", help="write chrom_umaps.csv and genome_umap.csv of an existing index: nearest neighbours of "
                                       "the bins on the GPU, layout and clusters on the host")
     um.add_argument("index_dir")
@@ -305,6 +319,24 @@ def main(argv=None):
         try:
             try:
                 lines = idx.add(a.new_samples)
+            except ValueError as e:
+                ap.error(str(e))
+        finally:
+            idx.close()
+        for line in lines:
+            print(line)
+        return 0
+    if a.cmd == "subset":
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"subset: {a.index_dir!r} is not an index directory")
+        from .index import Index
+        try:
+            idx = Index(a.index_dir, mode="r", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"subset: {e}")
+        try:
+            try:
+                lines = idx.subset(a.out, keep=a.keep, drop=a.drop, anchors=a.anchors, sequence_files=not a.no_sequence_files)
             except ValueError as e:
                 ap.error(str(e))
         finally:

@@ -17,7 +17,7 @@ The move itself is a sequence of renames and NOT atomic for a concurrent reader:
 
 Limits: k <= 32; one process, one GPU; two anchors' new rows (one being written by a host thread, one being made) and one
 batch of old rows must fit the free HBM; the old samples' FASTA files must still be where ``samples.tsv`` says; samples are appended at the end of the sample order;
-removing a sample is out of scope."""
+removing or reordering samples is ``subset``'s job (subset.py: a new directory)."""
 from __future__ import annotations
 
 import logging

@@ -1142,6 +1142,8 @@ extern "C" int pg_result_destroy(pg_result *r) {
     if (r->d_tile_hist) hipFree(r->d_tile_hist);
     if (r->d_tile_cs) hipFree(r->d_tile_cs);
     if (r->d_small) hipFree(r->d_small);
+    if (r->d_sel) hipFree(r->d_sel);
+    if (r->h_sel) hipHostFree(r->h_sel);
     for (auto e : r->chunk_ev) hipEventDestroy(e);
     for (auto *v : {&r->ev_hist, &r->ev_free})
         for (auto &s : *v)
@@ -1760,6 +1762,60 @@ static int append_columns_range(pg_result *dst, uint32_t dst_first_contig, const
 }
 
 extern "C" int pg_result_append_columns_range(pg_result *dst, uint32_t dst_first_contig, const pg_result *src, const void *d_cols, uint32_t nparts, uint32_t per, uint64_t part_stride_bytes) { return pg::guarded([&]() -> int { return append_columns_range(dst, dst_first_contig, src, d_cols, nparts, per, part_stride_bytes); }); }
+
+// `subset`: dst's bit j = src's bit sel[j], src's contigs 0..n-1 being dst's from dst_first_contig on (as above: an anchor's old
+// rows come back from its file in batches of chromosomes)
+static int select_columns_range(pg_result *dst, uint32_t dst_first_contig, const pg_result *src, const uint32_t *sel, uint32_t nsel) {
+    const char *fn = "pg_result_select_columns_range";
+    if (!dst || !src || !sel) return fail(PG_E_INVALID, "%s: NULL argument", fn);
+    if (dst == src || dst->ctx != src->ctx) return fail(PG_E_INVALID, "%s: source and destination must be two results of one context", fn);
+    if (nsel == 0) return fail(PG_E_INVALID, "%s: empty selection", fn);
+    if ((src->flags | dst->flags) & PG_ANCHOR_COLUMNS_ONLY) return fail(PG_E_INVALID, "%s: a columns-only result has no rows", fn);
+    if (!src->ev_ok && !src->rows_valid) return fail(PG_E_INVALID, "%s: the source holds no rows yet", fn);
+    if (nsel != dst->N) return fail(PG_E_INVALID, "%s: %u columns selected, the destination has %u genomes", fn, nsel, dst->N);
+    if (src->N > SELECT_MAX_GENOMES) return fail(PG_E_INVALID, "%s: more than %u genomes", fn, SELECT_MAX_GENOMES);
+    std::vector<bool> taken(src->N, false);
+    for (uint32_t j = 0; j < nsel; ++j) {
+        if (sel[j] >= src->N) return fail(PG_E_INVALID, "%s: column %u selected, the source has %u genomes", fn, sel[j], src->N);
+        if (taken[sel[j]]) return fail(PG_E_INVALID, "%s: column %u selected twice", fn, sel[j]);
+        taken[sel[j]] = true;
+    }
+    const size_t n = src->ad.size();
+    if ((uint64_t)dst_first_contig + n > dst->ad.size())
+        return fail(PG_E_INVALID, "%s: contigs %u..%zu out of range (the destination has %zu)", fn, dst_first_contig, dst_first_contig + n, dst->ad.size());
+    for (size_t c = 0; c < n; ++c)  // the same geometry on both sides: the source's tiles line up with the destination's
+        if (src->ad[c].nkmers != dst->ad[dst_first_contig + c].nkmers)
+            return fail(PG_E_INVALID, "%s: contig %zu has %u k-mers in the source, %u in the destination", fn, c, src->ad[c].nkmers,
+                        dst->ad[dst_first_contig + c].nkmers);
+    const std::vector<SelSeg> segs = select_segments(sel, nsel);
+    if (int e = use_device(dst->ctx)) return e;
+    if (int e = join_result(dst)) return e;
+    if (int e = join_result(const_cast<pg_result *>(src))) return e;
+    // the segments stay with the destination: an anchor's batches bring the same selection, which goes to the device once
+    // (through a page-locked copy, so that the upload waits for nothing and nothing waits for it)
+    if (segs.size() != dst->sel_n || memcmp(segs.data(), dst->h_sel, segs.size() * sizeof(SelSeg)) != 0) {
+        if (dst->sel_n) HIP_TRY(hipStreamSynchronize(dst->ctx->stream));  // another selection's upload or pass may still read the old ones
+        dst->sel_n = 0;
+        if (segs.size() > dst->sel_cap) {
+            if (dst->d_sel) hipFree(dst->d_sel);
+            if (dst->h_sel) hipHostFree(dst->h_sel);
+            dst->d_sel = dst->h_sel = nullptr;
+            dst->sel_cap = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&dst->d_sel), segs.size() * sizeof(SelSeg)));
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&dst->h_sel), segs.size() * sizeof(SelSeg), hipHostMallocDefault));
+            dst->sel_cap = segs.size();
+        }
+        memcpy(dst->h_sel, segs.data(), segs.size() * sizeof(SelSeg));
+        HIP_TRY(hipMemcpyAsync(dst->d_sel, dst->h_sel, segs.size() * sizeof(SelSeg), hipMemcpyHostToDevice, dst->ctx->stream));
+        dst->sel_n = segs.size();
+    }
+    HIP_TRY(launch_rows_select(dst->ctx->stream, src->N, dst->N, src->d_ad, src->d_tile_contig, src->ntiles, src->d_out1, dst->d_ad,
+                               dst_first_contig, dst->d_out1, dst->d_sel, (uint32_t)segs.size(), select_needed_words(segs)));
+    dst->rows_valid = true;
+    return PG_OK;
+}
+
+extern "C" int pg_result_select_columns_range(pg_result *dst, uint32_t dst_first_contig, const pg_result *src, const uint32_t *sel, uint32_t nsel) { return pg::guarded([&]() -> int { return select_columns_range(dst, dst_first_contig, src, sel, nsel); }); }
 
 extern "C" int pg_rows_epilogue(pg_result *r) {
     PG_API_BEGIN

@@ -170,6 +170,8 @@ struct pg_result {
     uint32_t *d_tile_hist = nullptr, *d_tile_cs = nullptr;
     uint2 *d_small = nullptr;
     uint32_t n_small = 0, small_tiles = 0;
+    SelSeg *d_sel = nullptr, *h_sel = nullptr;  // the sel_n segments of the last pg_result_select_columns_range into this result, and their page-locked copy
+    size_t sel_cap = 0, sel_n = 0;
     uint32_t fused_runs = 0;  // whole runs that took the fused path (pg_result_fused_runs: tests and bench.py say which path was timed)
 };
 static constexpr size_t EV_RING = 128;

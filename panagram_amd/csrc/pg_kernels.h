@@ -3,6 +3,7 @@
 #include "pg_device.h"
 
 #include "pg_blocks_link.h"
+#include "pg_select_host.h"
 
 namespace pg {
 
@@ -172,6 +173,11 @@ hipError_t launch_cols_merge(hipStream_t st, uint32_t ngenomes, const AnchorDesc
 hipError_t launch_rows_append(hipStream_t st, uint32_t n_old, uint32_t n_new, const AnchorDesc *src_ad, const uint32_t *src_tile_contig,
                               uint32_t ntiles, const uint8_t *src_rows, const AnchorDesc *dst_ad, uint32_t dst_first_contig,
                               uint8_t *dst_rows, const void *cols, uint32_t nparts, uint64_t part_words, uint32_t per);
+// destination bit j = source bit sel[j] of the rows of n_old genomes of one result (all of its ntiles tiles) -> the rows of n_new
+// genomes of another result from contig dst_first_contig on (contigs of the same nkmers); segs: select_segments(sel) on the device
+hipError_t launch_rows_select(hipStream_t st, uint32_t n_old, uint32_t n_new, const AnchorDesc *src_ad, const uint32_t *src_tile_contig,
+                              uint32_t ntiles, const uint8_t *src_rows, const AnchorDesc *dst_ad, uint32_t dst_first_contig,
+                              uint8_t *dst_rows, const SelSeg *segs, uint32_t nseg, uint32_t need);
 // every step-th row of bitmap.1 -> low-resolution bitmap (steps other than 100)
 hipError_t launch_lowres(hipStream_t st, uint32_t ngenomes, const AnchorDesc *ad, const uint32_t *tile_contig,
                          uint32_t ntiles, const uint8_t *out1, uint8_t *outlow, uint32_t step);

@@ -17,6 +17,7 @@
 //   k_window_stats, k_cols_extract / k_cols_merge: side paths (gene / bin windows; the
 //                genome-sharded exchange).
 //   k_rows_append*  finished rows of N genomes + column blocks of m more -> rows of N + m genomes in one pass (`add`).
+//   k_rows_select*  finished rows of N genomes -> rows of an ordered selection of their columns in one pass (`subset`).
 //   k_lowres, k_tile_reduce: the low-resolution bitmap for steps other than 100; the per-tile counters of a fused k_probe launch
 //                (FuseArgs, pg_kernels.h) into the bins and column sums.
 #include "pg_kernels.h"
@@ -1781,6 +1782,178 @@ __global__ __launch_bounds__(256) void k_rows_append(AppendArgs A) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// select (no reference counterpart: to drop or reorder samples the reference re-runs its whole workflow): the finished rows
+// of n_old genomes of ONE result -> the rows of n_new genomes of ANOTHER result over contigs of the same lengths,
+// destination bit j being source bit sel[j] (distinct, any order: columns dropped, permuted or both).  Every destination
+// row is written whole, once, every source row read once; the bits at and past n_new are zero, the bits at and past n_old
+// of the source's last byte are never looked at (the source comes from a file), and the destination's padding is not
+// touched.  Composed of what was there before — one k_cols_extract per kept genome, then k_cols_merge — the rows are read
+// n_new times and a column copy of the whole bitmap is needed; here W_old + W_new bytes move per position.
+// The host compiles sel into segments (pg_select_host.h): runs of consecutive source bits that go to consecutive
+// destination bits, each inside one destination word and so inside two neighbouring source words.  They are the same for
+// every wave: read through the scalar cache, in a uniform loop whose length is the number of segments, not of genomes.
+// Geometry as in k_rows_append*: the source's tiles 0 .. ntiles - 1 are the destination's from contig dst_c0 on.
+// ---------------------------------------------------------------------------
+struct SelectArgs {
+    const AnchorDesc *sad;          // the source's contigs, tiles and rows
+    const uint32_t *stile_contig;
+    const uint8_t *src;
+    const AnchorDesc *dad;          // the destination's contigs and rows
+    uint8_t *dst;
+    const SelSeg *segs;             // in the order of their destination bits
+    uint32_t nseg, need;            // need: bit d = some segment reads source word d
+    uint32_t ntiles, dst_c0, n_old, n_new;
+};
+
+// One-byte rows on both sides (n_old <= 8), after k_rows_append_b1: 16 positions per lane, one aligned 16-byte load and
+// store, COLS_TPW tiles per wave.  A segment moves its bits of four rows at once: no bit leaves its byte, the mask cuts
+// off what the right shift brings in from the next row.
+__global__ __launch_bounds__(256) void k_rows_select_b1(SelectArgs A) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t t0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * COLS_TPW;
+    if (t0 >= A.ntiles) return;  // wave-uniform
+    uint4 old[COLS_TPW];
+    uint4 *rowp[COLS_TPW];
+    uint32_t valid[COLS_TPW];
+#pragma unroll
+    for (uint32_t k = 0; k < COLS_TPW; ++k) {
+        old[k] = make_uint4(0, 0, 0, 0);
+        rowp[k] = nullptr;
+        valid[k] = 0;
+        if (t0 + k < A.ntiles) {  // (wave-uniform)
+            const uint32_t tile = t0 + k, c = A.stile_contig[tile];
+            const AnchorDesc sa = A.sad[c];
+            const uint32_t p0 = (tile - sa.tile0) * PROBE_TILE + 16 * lane;
+            if (p0 < sa.nkmers) {  // (rows are padded to 16 bytes per contig on both sides: the aligned 16-byte accesses stay inside)
+                old[k] = *reinterpret_cast<const uint4 *>(A.src + sa.out_off + p0);
+                rowp[k] = reinterpret_cast<uint4 *>(A.dst + A.dad[A.dst_c0 + c].out_off + p0);
+                valid[k] = min(16u, sa.nkmers - p0);
+            }
+        }
+    }
+    uint32_t w[COLS_TPW][4];
+#pragma unroll
+    for (uint32_t k = 0; k < COLS_TPW; ++k)
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) w[k][i] = 0;
+    for (uint32_t i = 0; i < A.nseg; ++i) {  // (uniform: at most 8)
+        const SelSeg g = A.segs[i];
+        const uint32_t sh = g.shifts & 0xFFu, dsh = (g.shifts >> 8) & 0xFFu, m = g.mask * 0x01010101u;
+#pragma unroll
+        for (uint32_t k = 0; k < COLS_TPW; ++k) {
+            w[k][0] |= ((old[k].x >> sh) & m) << dsh;
+            w[k][1] |= ((old[k].y >> sh) & m) << dsh;
+            w[k][2] |= ((old[k].z >> sh) & m) << dsh;
+            w[k][3] |= ((old[k].w >> sh) & m) << dsh;
+        }
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < COLS_TPW; ++k) {
+        if (!rowp[k]) continue;
+#pragma unroll
+        for (uint32_t i = 0; i < 4; ++i) {  // positions past the contig's end: the destination's padding stays zero whatever the source's holds
+            const uint32_t nv = valid[k] > 4 * i ? min(4u, valid[k] - 4 * i) : 0u;
+            w[k][i] &= nv >= 4 ? 0xFFFFFFFFu : (1u << (8 * nv)) - 1u;
+        }
+        *rowp[k] = make_uint4(w[k][0], w[k][1], w[k][2], w[k][3]);
+    }
+}
+
+// Every other pair of widths, with k_rows_append's geometry: a lane owns one position, a wave SPW slots of 64 positions of
+// one tile, rows are read and written as (unaligned) 32-bit words at a stride of the row width, a row's tail of 1..3 bytes
+// is stored as a 16-bit word and / or a byte (the next row is the next lane's), and the last word read of a row may reach
+// up to 3 bytes past it, into the next row, the contig's padding or the slack behind the buffer: no segment looks there.
+// NWS = words per source row: the wave asks for every source word that some segment reads (A.need: 64 -> 8 genomes fetches
+// one word of a row's two) of all its slots before it uses the first; the segment loop then picks its one or two words out
+// of the registers by the segment's (uniform) word number.  NWS = 0: any width, the words fetched as the segments ask.
+template <int NWS, int SPW>
+__global__ __launch_bounds__(256) void k_rows_select(SelectArgs A) {
+    static_assert(TILE_SLOTS % SPW == 0, "a wave's slots lie in one tile");
+    constexpr uint32_t WPT = TILE_SLOTS / SPW;  // waves per tile
+    constexpr int NR = NWS > 0 ? NWS : 1;
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (wave >= (uint64_t)A.ntiles * WPT) return;  // wave-uniform
+    const uint32_t tile = (uint32_t)(wave / WPT), sub0 = (uint32_t)(wave % WPT) * SPW;
+    const uint32_t c = A.stile_contig[tile];
+    const AnchorDesc sa = A.sad[c];
+    const uint32_t wo = (A.n_old + 7) / 8, wn = (A.n_new + 7) / 8;
+    const uint32_t p0 = (tile - sa.tile0) * PROBE_TILE + sub0 * 64 + lane;  // this lane's position in the wave's first slot
+    const uint8_t *sbase = A.src + sa.out_off;
+    uint8_t *dbase = A.dst + A.dad[A.dst_c0 + c].out_off;
+    auto load_old = [&](uint32_t s, uint32_t d) -> uint32_t {  // word d of the source row of slot s
+        const uint32_t p = p0 + 64u * s;
+        return (p < sa.nkmers && 4u * d < wo) ? reinterpret_cast<const U32 *>(sbase + (uint64_t)p * wo + 4u * d)->v : 0u;
+    };
+    auto store_word = [&](uint32_t s, uint32_t d, uint32_t w) {
+        const uint32_t p = p0 + 64u * s;
+        if (p >= sa.nkmers) return;
+        uint8_t *o = dbase + (uint64_t)p * wn + 4u * d;
+        const uint32_t n = min(4u, wn - 4u * d);  // (uniform)
+        if (n == 4) {
+            reinterpret_cast<U32 *>(o)->v = w;
+        } else {
+            if (n >= 2) reinterpret_cast<U16 *>(o)->v = (uint16_t)w;
+            if (n & 1) o[n - 1] = (uint8_t)(w >> (8 * (n - 1)));
+        }
+    };
+    uint32_t oldw[SPW][NR];
+    if constexpr (NWS > 0) {
+#pragma unroll
+        for (int s = 0; s < SPW; ++s)
+#pragma unroll
+            for (int d = 0; d < NWS; ++d) oldw[s][d] = ((A.need >> d) & 1u) ? load_old(s, d) : 0u;  // (uniform)
+    }
+    // NWS = 0: the two source words fetched last (numbers ia < ib; the next segment of a selection that keeps its order wants
+    // ib again, with ib + 1: each word is then fetched once)
+    uint32_t ca[SPW], cb[SPW], ia = 0xFFFFFFFFu, ib = 0xFFFFFFFFu;
+    auto fetch = [&](uint32_t lo, uint32_t two) {  // (uniform)
+        if ((lo == ia || lo == ib) && (!two || lo + 1 == ib)) return;
+        if (two && ib != lo) {
+            ia = lo;
+#pragma unroll
+            for (int s = 0; s < SPW; ++s) ca[s] = load_old(s, lo);
+        } else {  // what was fetched last stays
+            ia = ib;
+#pragma unroll
+            for (int s = 0; s < SPW; ++s) ca[s] = cb[s];
+        }
+        ib = lo + two;
+#pragma unroll
+        for (int s = 0; s < SPW; ++s) cb[s] = load_old(s, ib);
+    };
+    auto word = [&](uint32_t s, uint32_t j) -> uint32_t {  // source word j (uniform) of slot s
+        if constexpr (NWS > 0) {
+            uint32_t r = 0;
+#pragma unroll
+            for (int d = 0; d < NWS; ++d) r = j == (uint32_t)d ? oldw[s][d] : r;
+            return r;
+        } else {
+            return j == ia ? ca[s] : cb[s];
+        }
+    };
+    uint32_t i = 0;
+    for (uint32_t d = 0; 4u * d < wn; ++d) {  // (uniform, as is the loop inside: every destination word has a segment)
+        uint32_t w[SPW];
+#pragma unroll
+        for (int s = 0; s < SPW; ++s) w[s] = 0;
+        for (; i < A.nseg; ++i) {
+            const SelSeg g = A.segs[i];
+            if ((g.words >> 16) != d) break;
+            const uint32_t sw = g.words & 0xFFFFu, sh = g.shifts & 0xFFu, dsh = (g.shifts >> 8) & 0xFFu, two = (g.shifts >> 16) & 1u;
+            if constexpr (NWS == 0) fetch(sw, two);
+#pragma unroll
+            for (int s = 0; s < SPW; ++s) {
+                const uint32_t lo = word(s, sw), hi = two ? word(s, sw + 1) : 0u;
+                w[s] |= ((uint32_t)((((unsigned long long)hi << 32) | lo) >> sh) & g.mask) << dsh;
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < SPW; ++s) store_word(s, d, w[s]);
+    }
+}
+
 // every step-th row of bitmap.1 -> the low-resolution bitmap, for steps other than the 100 the statistics
 // kernels fuse (index.py:101-106 lowres_step): one wave per tile, a handful of rows each
 __global__ __launch_bounds__(64) void k_lowres(uint32_t N, const AnchorDesc *__restrict__ ad,
@@ -2039,6 +2212,35 @@ hipError_t launch_rows_append(hipStream_t st, uint32_t n_old, uint32_t n_new, co
     else if (nw == 4) hipLaunchKernelGGL((k_rows_append<4, 4>), grid(4), dim3(256), 0, st, A);
     else if (nw == 5) hipLaunchKernelGGL((k_rows_append<5, 4>), grid(4), dim3(256), 0, st, A);
     else hipLaunchKernelGGL((k_rows_append<0, 4>), grid(4), dim3(256), 0, st, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_rows_select(hipStream_t st, uint32_t n_old, uint32_t n_new, const AnchorDesc *src_ad, const uint32_t *src_tile_contig,
+                              uint32_t ntiles, const uint8_t *src_rows, const AnchorDesc *dst_ad, uint32_t dst_first_contig,
+                              uint8_t *dst_rows, const SelSeg *segs, uint32_t nseg, uint32_t need) {
+    if (ntiles == 0) return hipSuccess;
+    SelectArgs A;
+    A.sad = src_ad;
+    A.stile_contig = src_tile_contig;
+    A.src = src_rows;
+    A.dad = dst_ad;
+    A.dst = dst_rows;
+    A.segs = segs;
+    A.nseg = nseg;
+    A.need = need;
+    A.ntiles = ntiles;
+    A.dst_c0 = dst_first_contig;
+    A.n_old = n_old;
+    A.n_new = n_new;
+    const uint32_t nws = ((n_old + 7) / 8 + 3) / 4;  // words per source row
+    auto grid = [&](uint32_t spw) { return dim3((unsigned)(((uint64_t)ntiles * (TILE_SLOTS / spw) + 3) / 4)); };
+    if (n_old <= 8) hipLaunchKernelGGL(k_rows_select_b1, dim3((unsigned)(((uint64_t)ntiles + 4 * COLS_TPW - 1) / (4 * COLS_TPW))), dim3(256), 0, st, A);
+    else if (nws == 1) hipLaunchKernelGGL((k_rows_select<1, 8>), grid(8), dim3(256), 0, st, A);
+    else if (nws == 2) hipLaunchKernelGGL((k_rows_select<2, 8>), grid(8), dim3(256), 0, st, A);
+    else if (nws == 3) hipLaunchKernelGGL((k_rows_select<3, 4>), grid(4), dim3(256), 0, st, A);
+    else if (nws == 4) hipLaunchKernelGGL((k_rows_select<4, 4>), grid(4), dim3(256), 0, st, A);
+    else if (nws == 5) hipLaunchKernelGGL((k_rows_select<5, 4>), grid(4), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((k_rows_select<0, 4>), grid(4), dim3(256), 0, st, A);
     return hipGetLastError();
 }
 

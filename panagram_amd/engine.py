@@ -1436,6 +1436,13 @@ class AnchorResult:
         check(self._lib.pg_result_append_columns_range(self._h, first_contig, src._h, C.c_void_p(dev_ptr), nparts, per,
                                                        part_stride_bytes))
 
+    def select_columns(self, src: "AnchorResult", sel, first_contig: int = 0) -> None:
+        """``src``'s finished rows (its contigs 0..n-1 are this result's from ``first_contig`` on, with the same k-mer counts)
+        -> this result's rows, written whole in one pass (async): bit j is ``src``'s bit ``sel[j]``.  ``sel``: this result's
+        ``ngenomes`` distinct column numbers of ``src``, in any order.  ``rows_epilogue`` finishes them."""
+        sel = np.ascontiguousarray(sel, np.uint32)
+        check(self._lib.pg_result_select_columns_range(self._h, first_contig, src._h, _ptr(sel), len(sel)))
+
     def rows_tensor(self):
         """Zero-copy torch uint8 view of the device bitmap.1 buffer (for RCCL collectives)."""
         import torch

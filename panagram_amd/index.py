@@ -1121,6 +1121,22 @@ class Index:
         from . import add as _add
         return _add.add(self, new_samples)
 
+    def subset(self, out_dir, keep=None, drop=None, anchors=None, sequence_files: bool = True) -> List[str]:
+        """Write an index of chosen samples of this finished index into the new directory ``out_dir`` (subset.py; no reference
+        counterpart).  ``keep``: the samples to keep, in the order given (``"A,B"`` or a sequence: this is how columns are
+        reordered); or ``drop``: the samples to leave out, the rest keeping the index's order.  Ids are renumbered.  Every kept
+        anchor (``anchors``: only these of them) gets its rows read back from bitmap.1.gz and narrowed in one kernel pass
+        (``AnchorResult.select_columns``), and all of its files written by the code that writes them in ``run``: the tree equals
+        ``run`` over the kept samples.  No FASTA is read — unless this index holds kmc/bitvec*, genome_dist.tsv or the k-mer
+        statistics, which are refreshed from the kept samples' sequences (``sequence_files=False``: left out instead).  This
+        index is never touched (read-only is enough).  Refused before ``out_dir`` is created (ValueError): an unknown or repeated
+        name, both or neither of ``keep`` and ``drop``, nothing kept, ``anchors`` naming no kept anchor, a non-empty ``out_dir``
+        or one inside this index, a kept anchor without bitmap.1.gz, .gzi or chrs.tsv, more than one process.  A failure midway
+        removes ``out_dir``.  Returns one line per anchor of this index, rewritten or left behind; afterwards this object is
+        ``close()``d, as ``add`` leaves it."""
+        from . import subset as _subset
+        return _subset.subset(self, out_dir, keep, drop, anchors, sequence_files)
+
     def _ensure_process_group(self) -> bool:
         """Under a launcher that set up a rendezvous (torchrun: MASTER_ADDR / MASTER_PORT, RANK, WORLD_SIZE) a run with
         several ranks joins the process group itself — backend "nccl" (= RCCL over xGMI), this rank's GPU — so that the

@@ -39,6 +39,7 @@ extern "C" {
 #define PG_E_FORMAT (-3)    /* ill-formed KMC database */
 #define PG_E_CAPACITY (-4)  /* table cannot grow further */
 #define PG_E_IO (-5)        /* file I/O (BGZF writer) */
+#define PG_E_INTERNAL (-6)  /* the library contradicts itself (a bounded walk did not end): a bug, never the caller's fault */
 
 typedef struct pg_ctx pg_ctx;
 typedef struct pg_table pg_table;
@@ -894,6 +895,41 @@ int pg_novel_runs(pg_table *tbl, const pg_seqset *seqs, uint64_t cap, uint32_t *
  * pg_novel_add_seqset (0: it did not grow, or grew an empty table), k_novel_scan of the last pg_novel_result or pg_novel_keys (both
  * passes), k_novel_runs of the last pg_novel_runs (both passes) — what tools/novel_rate.py reports. */
 int pg_novel_last_timing(float *ms_out);
+/* unitigs: the solid novel k-mers compacted into sequences on the GPU (pg_unitigs.hip).  Over a handle and a min_count, 2 <= k <= 32:
+ *   node             a solid novel key.  Keys below min_count and k-mers the pan table holds are not nodes: they cut paths.
+ *   oriented k-mer   w: a node's k-mer x or its reverse complement; canon(w) is its node
+ *   out(w)           the bases b for which canon(w[1:] + b) is a node;  in(w) = out(rc(w)), complemented
+ *   link byte        of node x in the canonical orientation (first base most significant, A < C < G < T): bit b (b < 4) is set when
+ *                    canon(x[1:] + b) is a node, bit 4 + b when canon(b + x[:-1]) is a node
+ *   compactable edge w -> w': out(w) = {the base that gives w'}, in(w') holds exactly one base, canon(w) != canon(w') (no self-loop,
+ *                    no hairpin w -> rc(w)), and neither node is its own reverse complement
+ *   unitig           a maximal path w1 .. wn along compactable edges: w1 plus the last base of each further wi, n + k - 1 bases.
+ *                    Every node lies in exactly one unitig; a node that is its own reverse complement is a unitig of n = 1.
+ *   circular unitig  a component in which every node has a compactable edge on both sides: emitted once, from its smallest key in
+ *                    that key's canonical orientation to the right, n nodes and n + k - 1 bases (the last k - 1 repeat the first)
+ *   linear unitig    emitted once, by the walk from the end with the smaller key (n = 1: in the canonical orientation): the
+ *                    sequence or its reverse complement, whichever that walk spells
+ *   depth_sum        the sum of the nodes' depths
+ * pg_novel_links: the solid keys and their link bytes, in slot order, under the capacity protocol of pg_novel_keys.
+ * pg_novel_unitigs: unitig u < min(cap_unitigs, *nunitigs) has kmers[u] nodes, depth_sum[u], circular[u] (0 / 1) and the bases
+ * bases[offsets[u] .. offsets[u] + kmers[u] + k - 1), ASCII; bases at or past cap_bases and entries at or past cap_unitigs are never
+ * written (a unitig's bases may be cut).  *nunitigs, *nbases and *ncircular are the full numbers always; caps of 0: only counted.  The
+ * linear unitigs stand first, each kind in slot order of its starting node: the same on every call between two adds.  The handle
+ * keeps two byte planes of its slots and the walks' counts for the last min_count between a counting and a filling call;
+ * pg_novel_add_seqset and pg_novel_clear drop them.  One lane walks one unitig: a unitig of L k-mers costs L dependent memory round
+ * trips, a circular one L^2 probes spread over L lanes.  PG_E_INVALID: min_count == 0, k < 2, a stale handle, a NULL argument;
+ * PG_E_CAPACITY: no memory for the two planes or the outputs; PG_E_INTERNAL: a walk reached its bound (every walk is bounded by
+ * the solid keys, every lookup by the table's probe limit: a wrong plane is an error, never a hang). */
+int pg_novel_links(pg_novel *nv, uint32_t min_count, uint64_t cap, uint64_t *keys, uint8_t *links, uint64_t *n);
+int pg_novel_unitigs(pg_novel *nv, uint32_t min_count, uint64_t cap_unitigs, uint64_t cap_bases, uint64_t *offsets, uint32_t *kmers,
+                     uint64_t *depth_sum, uint8_t *circular, uint8_t *bases, uint64_t *nunitigs, uint64_t *nbases, uint64_t *ncircular);
+/* ms_out[3] = the HIP-event times, in milliseconds, of k_unitig_links, of k_unitig_walk's linear round (all its passes) and of its
+ * circular round (0: not run), as the handle of this host thread's last pg_novel_links / pg_novel_unitigs call has summed them
+ * since its planes were built — the sums are the handle's, two handles used in turn do not mix: a call that builds the planes
+ * (another min_count, or the first after an add or a clear) starts from zero, a call that finds them kept adds its passes — a
+ * counting call and the filling call behind it read as one.  All 0 behind a call that found no solid key.  What
+ * tools/novel_unitigs_rate.py reports. */
+int pg_novel_unitigs_last_timing(float *ms_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

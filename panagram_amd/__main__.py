@@ -37,8 +37,9 @@ of the indexed genomes a sample from outside the index holds and how much of eac
 through the table of every sample's k-mers and counted per k-mer, and one pass over the table joins the counts with the presence
 masks on the GPU; and
 `novel <index_dir> <sample.fq|sample.fa> [more ...] [--min-count N] [--spectrum FILE] [--kmers FILE] [--regions FILE] [--min-bases B]
-[--summary FILE]` says the reverse: the distinct k-mers of the sample that NO indexed genome holds, their depth spectrum, and for an
-assembly where they lie — the sample's windows that miss the table are counted in a key table of their own that grows on the GPU; and
+[--unitigs FILE] [--min-unitig-bases B] [--summary FILE]` says the reverse: the distinct k-mers of the sample that NO indexed genome
+holds, their depth spectrum, for an assembly where they lie, and with --unitigs the novel sequences themselves, the solid k-mers
+compacted into unitigs — the sample's windows that miss the table are counted in a key table of their own that grows on the GPU; and
 `add <index_dir> <new_samples.tsv>` appends samples to a finished index without re-anchoring it: every anchor already there is probed
 against the new samples' k-mers alone, its rows come back from bitmap.1.gz, and one kernel pass writes the wider rows; new anchors are
 anchored the ordinary way, and the tree is staged and renamed at the end, samples.tsv last; and
@@ -267,6 +268,10 @@ def main(argv=None):
     nvl.add_argument("--regions", metavar="FILE", default=None,
                      help="also write file contig start end kmers bases left_held right_held: the runs of novel k-mers along an assembly (no FASTQ)")
     nvl.add_argument("--min-bases", type=int, default=0, metavar="B", help="regions of at least B bases that lie in novel k-mers only (default 0)")
+    nvl.add_argument("--unitigs", metavar="FILE", default=None,
+                     help="also write FASTA: the solid novel k-mers compacted on the GPU into unitigs, the non-branching paths of their de Bruijn "
+                          "graph (>u1 bases= kmers= depth= circular=), longest first; prints unitigs, unitig_bases, unitig_n50, ... behind the statistics")
+    nvl.add_argument("--min-unitig-bases", type=int, default=None, metavar="B", help="unitigs of at least B bases (default 0; needs --unitigs)")
     nvl.add_argument("--summary", metavar="FILE", default=None, help="also write the statistics to FILE")
     nvl.add_argument("--batch-bytes", type=int, default=None, metavar="N", help="FASTQ text bytes joined at a time (default 2^28)")
     nvl.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
@@ -599,6 +604,10 @@ def main(argv=None):
                 ap.error(f"novel: no sample file {r!r}")
         if (a.min_count is not None and not 1 <= a.min_count <= 0xFFFFFFFF) or (a.batch_bytes is not None and a.batch_bytes < 1) or a.min_bases < 0:
             ap.error("novel: --min-count is 1 to 2^32 - 1, --batch-bytes positive, --min-bases not negative")
+        if a.min_unitig_bases is not None and not a.unitigs:
+            ap.error("novel: --min-unitig-bases needs --unitigs FILE")
+        if a.min_unitig_bases is not None and a.min_unitig_bases < 0:
+            ap.error("novel: --min-unitig-bases not negative")
         from .index import Index, is_fastq
         from . import novel
         if a.regions and any(is_fastq(r) for r in a.samples):
@@ -614,8 +623,9 @@ def main(argv=None):
                 if pd.isna(fa) or not os.path.isfile(str(fa)):
                     ap.error(f"novel: sample {n!r} of {a.index_dir} has no sequence file to take k-mers of ({fa})")
             try:
-                stats, spectrum, kmers, regions = idx.novel(a.samples, a.min_count, a.batch_bytes, kmers=bool(a.kmers), regions=bool(a.regions),
-                                                            min_bases=a.min_bases)
+                stats, spectrum, kmers, regions, *unitigs = idx.novel(a.samples, a.min_count, a.batch_bytes, kmers=bool(a.kmers),
+                                                                      regions=bool(a.regions), min_bases=a.min_bases, unitigs=bool(a.unitigs),
+                                                                      min_unitig_bases=a.min_unitig_bases or 0)
             except ValueError as e:
                 ap.error(f"novel: {e}")
         finally:
@@ -629,6 +639,9 @@ def main(argv=None):
         if a.summary:
             novel.write_summary(stats, a.summary)
         novel.write_stats(stats, sys.stdout)
+        if a.unitigs:
+            novel.write_unitigs(unitigs[0], a.unitigs)
+            sys.stdout.writelines(line + "\n" for line in novel.unitig_stat_lines(novel.unitig_stats(unitigs[0])))
         return 0
     if a.cmd == "locate":
         if (a.queries is None) == (a.genes is None):

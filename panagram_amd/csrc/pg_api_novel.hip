@@ -1,5 +1,6 @@
 // pg_api_novel.hip — host side of the C-ABI: what a sample holds that the pan table does not (pg_novel.hip): the novel key table
-// that sequence sets are counted into and that grows in front of them, the pass over its slots, and the novel runs of an assembly.
+// that sequence sets are counted into and that grows in front of them, the pass over its slots, the novel runs of an assembly, and
+// the solid keys compacted into unitigs (pg_unitigs.hip).
 #include "pg_host.h"
 
 #include "pg_keytable_host.h"
@@ -21,15 +22,35 @@ struct pg_novel {
     const uint8_t *buckets;
     uint64_t nbuckets, count;
     uint32_t slots, layout;
+    // what pg_novel_links and pg_novel_unitigs keep between a counting call and a filling call, for ONE min_count: the two byte
+    // planes and the walks' counts.  An add and a clear drop it (unitig_drop): the slots it speaks of are other slots then
+    struct Unitigs {
+        uint32_t min_count = 0;  // 0: nothing kept
+        uint8_t *d_links = nullptr, *d_marks = nullptr;
+        bool walked = false;                   // the counts below stand and `marks` holds the winners of both rounds
+        std::vector<ulonglong2> lin, circ;     // per block of the scan: {winners, their nodes} of the linear / the circular round
+        uint64_t nlin = 0, lin_nodes = 0, ncirc = 0, circ_nodes = 0;
+        float ms[3] = {0, 0, 0};  // the kernels' times since the planes were built: what pg_novel_unitigs_last_timing reads behind a call on this handle
+    } ut;
 };
 
 namespace {
 
 thread_local float g_novel_ms[4] = {0, 0, 0, 0};  // k_novel_count, k_novel_grow, k_novel_scan (both passes), k_novel_runs (both passes)
 
+thread_local float g_unitig_ms[3] = {0, 0, 0};  // k_unitig_links, k_unitig_walk of the linear round (all passes), of the circular round
+
+// (behind a synchronise of the handle's stream: no kernel reads the planes)
+void unitig_drop(pg_novel *nv) {
+    if (nv->ut.d_links) hipFree(nv->ut.d_links);
+    if (nv->ut.d_marks) hipFree(nv->ut.d_marks);
+    nv->ut = pg_novel::Unitigs();
+}
+
 void novel_free(pg_novel *nv) {
     hipSetDevice(nv->ctx->device);
     hipStreamSynchronize(nv->ctx->stream);
+    unitig_drop(nv);
     if (nv->d_depth) hipFree(nv->d_depth);
     if (nv->d_keys) hipFree(nv->d_keys);
     pg_table *t = nv->tbl;
@@ -166,6 +187,7 @@ int novel_add(pg_novel *nv, const pg_seqset *sq, uint64_t *windows, uint64_t *hi
     *windows = *hits = *new_keys = 0;
     g_novel_ms[0] = g_novel_ms[1] = 0;
     if (w.jobs.empty()) return PG_OK;
+    unitig_drop(nv);  // (every call of this unit leaves the stream synchronised)
     if (int r = novel_reserve(nv, w.nkmers, fn)) return r;
     hipStream_t stream = nv->ctx->stream;
     unsigned long long ctr[4] = {0, 0, 0, 0};
@@ -371,6 +393,228 @@ int novel_runs(pg_table *t, const pg_seqset *sq, uint64_t cap, uint32_t *run_con
     return PG_OK;
 }
 
+// the link plane of `min_count` behind a pass of the scan: h = its NOVEL_SCAN_WORDS words (h[1]: the solid keys), block_solid the
+// solid keys of every block.  Nothing is launched beyond the scan, and nothing kept, over a table without a solid key
+int unitig_planes(pg_novel *nv, const char *fn, uint32_t min_count, uint64_t *h, std::vector<uint32_t> &block_solid) {
+    const int k = nv->tbl->k;
+    if (k < 2 || k > 32) return fail(PG_E_INVALID, "%s: a table of k = %d (unitigs: 2 to 32)", fn, k);
+    float ms_scan = 0;
+    if (int r = novel_scan_count(nv, fn, min_count, h, &block_solid, &ms_scan)) return r;
+    if (h[1] != 0 && nv->ut.min_count == min_count) {  // (the planes kept: this handle's times go on adding up)
+        std::copy(nv->ut.ms, nv->ut.ms + 3, g_unitig_ms);
+        return PG_OK;
+    }
+    g_unitig_ms[0] = g_unitig_ms[1] = g_unitig_ms[2] = 0;
+    if (h[1] == 0) return PG_OK;
+    unitig_drop(nv);
+    hipStream_t st = nv->ctx->stream;
+    const size_t bytes = (size_t)std::max<uint64_t>(nv->nslots, 4);  // (the marks are set through 32-bit words)
+    DevBuf<uint8_t> links, marks;
+    float ms_links = 0;
+    LaunchTimer tm(&ms_links);
+    hipError_t e = links.alloc(bytes);
+    if (e == hipSuccess) e = marks.alloc(bytes);
+    if (e == hipErrorOutOfMemory) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_CAPACITY, "%s: no memory for two byte planes of %llu slots", fn, (unsigned long long)nv->nslots);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(marks.get(), 0, bytes, st);
+    if (e == hipSuccess) e = tm.start(st);
+    if (e == hipSuccess) e = launch_unitig_links(st, nv->d_keys, nv->d_depth, nv->nslots, nv->max_probe, min_count, k, links.get());
+    if (e == hipSuccess) e = tm.stop(st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    tm.read();
+    std::swap(nv->ut.d_links, links.p);
+    std::swap(nv->ut.d_marks, marks.p);
+    nv->ut.min_count = min_count;
+    nv->ut.ms[0] = g_unitig_ms[0] = ms_links;
+    return PG_OK;
+}
+
+int novel_links(pg_novel *nv, uint32_t min_count, uint64_t cap, uint64_t *keys_out, uint8_t *links_out, uint64_t *n) {
+    const char *fn = "pg_novel_links";
+    uint64_t h[NOVEL_SCAN_WORDS];
+    std::vector<uint32_t> block_solid;
+    if (int r = unitig_planes(nv, fn, min_count, h, block_solid)) return r;
+    *n = h[1];
+    const uint64_t take = std::min<uint64_t>(h[1], cap);
+    if (take == 0) return PG_OK;
+    std::vector<uint64_t> offs(block_solid.size());
+    uint64_t sum = 0;
+    for (size_t b = 0; b < block_solid.size(); ++b) {
+        offs[b] = sum;
+        sum += block_solid[b];
+    }
+    if (sum != h[1]) return fail(PG_E_HIP, "%s: %llu solid keys by block, %llu in all", fn, (unsigned long long)sum, (unsigned long long)h[1]);
+    hipStream_t st = nv->ctx->stream;
+    DevBuf<uint64_t> d_offs;
+    DevBuf<unsigned long long> d_k;
+    DevBuf<uint8_t> d_l;
+    hipError_t e = d_offs.upload(offs, st);
+    if (e == hipSuccess) e = d_k.alloc(take);
+    if (e == hipSuccess) e = d_l.alloc(take);
+    if (e == hipErrorOutOfMemory) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_CAPACITY, "%s: no memory for %llu keys", fn, (unsigned long long)take);
+    }
+    if (e == hipSuccess)
+        e = launch_unitig_links_emit(st, nv->d_keys, nv->d_depth, nv->ut.d_links, nv->nslots, min_count, d_offs.get(), take, d_k.get(), d_l.get());
+    if (e == hipSuccess) e = hipMemcpyAsync(keys_out, d_k.get(), take * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(links_out, d_l.get(), take, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    return PG_OK;
+}
+
+// where a round's unitigs go: on the device, cut at the caller's capacities
+struct UnitigOut {
+    uint64_t cap_u = 0, cap_b = 0;
+    DevBuf<uint64_t> offsets, depth_sum;
+    DevBuf<uint32_t> kmers;
+    DevBuf<uint8_t> circular, bases;
+};
+
+// one pass of k_unitig_walk over the table.  Count (offs == NULL): counts = {winners, their nodes} per block.  Emit: offs = {unitigs,
+// bases} in front of every block's, out (NULL: the marks only) takes them.  which: the handle's time (1 linear, 2 circular) the pass's is added to
+int unitig_pass(pg_novel *nv, const char *fn, bool circular, uint64_t bound, std::vector<ulonglong2> *counts, const std::vector<ulonglong2> *offs,
+                UnitigOut *out, int which) {
+    hipStream_t st = nv->ctx->stream;
+    const uint32_t blocks = novel_scan_blocks(nv->nslots);
+    DevBuf<ulonglong2> d_counts, d_offs;
+    DevBuf<uint32_t> d_flag;
+    uint32_t flag = 0;
+    float t = 0;
+    LaunchTimer tm(&t);
+    hipError_t e = d_flag.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag.get(), 0, 4, st);
+    if (e == hipSuccess) e = offs ? d_offs.upload(*offs, st) : d_counts.alloc(blocks);
+    if (e == hipSuccess) e = tm.start(st);
+    if (e == hipSuccess)
+        e = launch_unitig_walk(st, nv->d_keys, nv->d_depth, nv->nslots, nv->max_probe, nv->ut.min_count, nv->tbl->k, nv->ut.d_links, nv->ut.d_marks,
+                               circular, bound, d_counts.get(), d_offs.get(), out ? out->cap_u : 0, out ? out->cap_b : 0,
+                               out ? out->offsets.get() : nullptr, out ? out->kmers.get() : nullptr, out ? out->depth_sum.get() : nullptr,
+                               out ? out->circular.get() : nullptr, out ? out->bases.get() : nullptr, d_flag.get());
+    if (e == hipSuccess) e = tm.stop(st);
+    if (e == hipSuccess && counts) {
+        counts->assign(blocks, make_ulonglong2(0, 0));
+        e = hipMemcpyAsync(counts->data(), d_counts.get(), (size_t)blocks * sizeof(ulonglong2), hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag.get(), 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);  // (the upload's source and the copies' targets go with this scope)
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    tm.read();
+    nv->ut.ms[which] += t;
+    g_unitig_ms[which] = nv->ut.ms[which];
+    if (flag)
+        return fail(PG_E_INTERNAL, "%s: a walk of the %s round did not end within %llu nodes, or the link plane contradicts the table", fn,
+                    circular ? "circular" : "linear", (unsigned long long)bound);
+    return PG_OK;
+}
+
+// {unitigs, bases} in front of every block's, from {u0, b0} on; a unitig of n nodes holds n + k - 1 bases
+std::vector<ulonglong2> unitig_offsets(const std::vector<ulonglong2> &counts, int k, uint64_t u0, uint64_t b0) {
+    std::vector<ulonglong2> offs(counts.size());
+    for (size_t b = 0; b < counts.size(); ++b) {
+        offs[b] = make_ulonglong2(u0, b0);
+        u0 += counts[b].x;
+        b0 += counts[b].y + (uint64_t)(k - 1) * counts[b].x;
+    }
+    return offs;
+}
+
+int novel_unitigs(pg_novel *nv, uint32_t min_count, uint64_t cap_u, uint64_t cap_b, uint64_t *offsets, uint32_t *kmers, uint64_t *depth_sum,
+                  uint8_t *circular, uint8_t *bases, uint64_t *nunitigs, uint64_t *nbases, uint64_t *ncircular) {
+    const char *fn = "pg_novel_unitigs";
+    uint64_t h[NOVEL_SCAN_WORDS];
+    std::vector<uint32_t> block_solid;
+    if (int r = unitig_planes(nv, fn, min_count, h, block_solid)) return r;
+    *nunitigs = *nbases = *ncircular = 0;
+    const uint64_t solid = h[1];
+    if (solid == 0) return PG_OK;
+    pg_novel::Unitigs &u = nv->ut;
+    const int k = nv->tbl->k;
+    if (!u.walked) {
+        // the linear round counted; when its winners' nodes are fewer than the solid keys, its emit pass for the marks alone and the
+        // circular round counted over the nodes without one
+        if (int r = unitig_pass(nv, fn, false, solid, &u.lin, nullptr, nullptr, 1)) return r;
+        u.nlin = u.lin_nodes = u.ncirc = u.circ_nodes = 0;
+        for (const ulonglong2 &c : u.lin) {
+            u.nlin += c.x;
+            u.lin_nodes += c.y;
+        }
+        if (u.lin_nodes > solid)
+            return fail(PG_E_INTERNAL, "%s: the linear unitigs hold %llu nodes of %llu", fn, (unsigned long long)u.lin_nodes, (unsigned long long)solid);
+        u.circ.clear();
+        if (u.lin_nodes < solid) {
+            const std::vector<ulonglong2> offs = unitig_offsets(u.lin, k, 0, 0);
+            if (int r = unitig_pass(nv, fn, false, solid, nullptr, &offs, nullptr, 1)) return r;
+            if (int r = unitig_pass(nv, fn, true, solid - u.lin_nodes, &u.circ, nullptr, nullptr, 2)) return r;
+            for (const ulonglong2 &c : u.circ) {
+                u.ncirc += c.x;
+                u.circ_nodes += c.y;
+            }
+            if (u.lin_nodes + u.circ_nodes != solid)
+                return fail(PG_E_INTERNAL, "%s: %llu nodes in linear and %llu in circular unitigs, %llu solid keys", fn,
+                            (unsigned long long)u.lin_nodes, (unsigned long long)u.circ_nodes, (unsigned long long)solid);
+        }
+        u.walked = true;
+    } else if (u.lin_nodes + u.circ_nodes != solid) {
+        return fail(PG_E_INTERNAL, "%s: the counts kept speak of %llu nodes, the table holds %llu solid keys", fn,
+                    (unsigned long long)(u.lin_nodes + u.circ_nodes), (unsigned long long)solid);
+    }
+    const uint64_t lin_bases = u.lin_nodes + (uint64_t)(k - 1) * u.nlin;
+    *nunitigs = u.nlin + u.ncirc;
+    *nbases = lin_bases + u.circ_nodes + (uint64_t)(k - 1) * u.ncirc;
+    *ncircular = u.ncirc;
+    UnitigOut out;
+    out.cap_u = std::min<uint64_t>(cap_u, *nunitigs);
+    out.cap_b = std::min<uint64_t>(cap_b, *nbases);
+    if (out.cap_u == 0 && out.cap_b == 0) return PG_OK;
+    hipStream_t st = nv->ctx->stream;
+    hipError_t e = hipSuccess;
+    if (out.cap_u) {
+        e = out.offsets.alloc(out.cap_u);
+        if (e == hipSuccess) e = out.depth_sum.alloc(out.cap_u);
+        if (e == hipSuccess) e = out.kmers.alloc(out.cap_u);
+        if (e == hipSuccess) e = out.circular.alloc(out.cap_u);
+    }
+    if (e == hipSuccess && out.cap_b) e = out.bases.alloc(out.cap_b);
+    if (e == hipErrorOutOfMemory)
+        return fail(PG_E_CAPACITY, "%s: no memory for %llu unitigs of %llu bases", fn, (unsigned long long)out.cap_u, (unsigned long long)out.cap_b);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    if (u.nlin) {
+        const std::vector<ulonglong2> offs = unitig_offsets(u.lin, k, 0, 0);
+        if (int r = unitig_pass(nv, fn, false, solid, nullptr, &offs, &out, 1)) return r;
+    }
+    if (u.ncirc && (out.cap_u > u.nlin || out.cap_b > lin_bases)) {  // (the circular ones stand behind the linear ones)
+        const std::vector<ulonglong2> offs = unitig_offsets(u.circ, k, u.nlin, lin_bases);
+        if (int r = unitig_pass(nv, fn, true, solid - u.lin_nodes, nullptr, &offs, &out, 2)) return r;
+    }
+    if (out.cap_u) {
+        e = hipMemcpyAsync(offsets, out.offsets.get(), out.cap_u * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(depth_sum, out.depth_sum.get(), out.cap_u * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(kmers, out.kmers.get(), out.cap_u * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(circular, out.circular.get(), out.cap_u, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess && out.cap_b) e = hipMemcpyAsync(bases, out.bases.get(), out.cap_b, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    return PG_OK;
+}
+
 }  // namespace
 
 extern "C" int pg_novel_create(pg_table *tbl, uint64_t capacity_keys, pg_novel **out) {
@@ -394,6 +638,7 @@ extern "C" int pg_novel_clear(pg_novel *nv) {
     HIP_TRY(hipMemsetAsync(nv->d_keys, 0xFF, nv->nslots * 8, nv->ctx->stream));
     HIP_TRY(hipMemsetAsync(nv->d_depth, 0, nv->nslots * 4, nv->ctx->stream));
     HIP_TRY(hipStreamSynchronize(nv->ctx->stream));
+    unitig_drop(nv);
     nv->nkeys = nv->windows = 0;
     nv->overflowed = false;  // (nothing short is left)
     return PG_OK;
@@ -444,6 +689,30 @@ extern "C" int pg_novel_last_timing(float *ms_out) {
     PG_API_BEGIN
     if (!ms_out) return fail(PG_E_INVALID, "pg_novel_last_timing: NULL argument");
     std::copy(g_novel_ms, g_novel_ms + 4, ms_out);
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_novel_links(pg_novel *nv, uint32_t min_count, uint64_t cap, uint64_t *keys, uint8_t *links, uint64_t *n) {
+    PG_API_BEGIN
+    if (!nv || !n || (cap && (!keys || !links))) return fail(PG_E_INVALID, "pg_novel_links: NULL argument");
+    return novel_links(nv, min_count, cap, keys, links, n);
+    PG_API_END
+}
+
+extern "C" int pg_novel_unitigs(pg_novel *nv, uint32_t min_count, uint64_t cap_unitigs, uint64_t cap_bases, uint64_t *offsets, uint32_t *kmers,
+                                uint64_t *depth_sum, uint8_t *circular, uint8_t *bases, uint64_t *nunitigs, uint64_t *nbases, uint64_t *ncircular) {
+    PG_API_BEGIN
+    if (!nv || !nunitigs || !nbases || !ncircular || (cap_unitigs && (!offsets || !kmers || !depth_sum || !circular)) || (cap_bases && !bases))
+        return fail(PG_E_INVALID, "pg_novel_unitigs: NULL argument");
+    return novel_unitigs(nv, min_count, cap_unitigs, cap_bases, offsets, kmers, depth_sum, circular, bases, nunitigs, nbases, ncircular);
+    PG_API_END
+}
+
+extern "C" int pg_novel_unitigs_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_novel_unitigs_last_timing: NULL argument");
+    std::copy(g_unitig_ms, g_unitig_ms + 3, ms_out);
     return PG_OK;
     PG_API_END
 }

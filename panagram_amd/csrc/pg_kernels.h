@@ -454,6 +454,26 @@ hipError_t launch_novel_scan(hipStream_t st, const unsigned long long *keys, con
 hipError_t launch_novel_runs(hipStream_t st, const SubTable &t, const SeqDesc *sd, const uint2 *chunks, uint32_t nchunks, const uint64_t *seqw,
                              const uint32_t *nmw, const uint32_t *has_n, uint4 *counts, const ulonglong2 *offs, uint64_t total,
                              uint32_t *run_start, uint32_t *run_end, uint8_t *left_held, uint8_t *right_held);
+// the solid keys of a novel table compacted into unitigs (pg_unitigs.hip; the definitions are there).  links and marks: two byte
+// planes of max(nslots, 4) bytes beside the table, which is only read; 2 <= k <= 32; the blocks are those of the scan.
+//   links       links[s] = the link byte of a solid slot, 0 of every other
+//   links_emit  offs[b] = the solid keys of all blocks before b (the scan's count pass): the solid keys and their link bytes in slot
+//               order to out_keys / out_links (entries at or past cap are never written)
+//   walk        circular false: the linear round; true: the circular one, over the nodes that the linear round's emit pass left
+//               without a mark.  bound: the nodes a walk may pass (the solid keys; the nodes not covered).  flag[0] (zeroed)
+//               becomes nonzero when a walk reached its bound or the planes contradict the table.
+//               offs == NULL  count: counts[b] = {the block's winners, their nodes}; marks takes the winning sides
+//               offs != NULL  emit: offs[b] = {the unitigs, the bases} in front of the block's; offsets, kmers, depth_sum and
+//                             circular of unitig u < cap_unitigs, base i < cap_bases (ASCII) — nothing at or past a cap is written;
+//                             the linear round marks the nodes its winners pass
+hipError_t launch_unitig_links(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t max_probe,
+                               uint32_t min_count, int k, uint8_t *links);
+hipError_t launch_unitig_links_emit(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, const uint8_t *links, uint64_t nslots,
+                                    uint32_t min_count, const uint64_t *offs, uint64_t cap, unsigned long long *out_keys, uint8_t *out_links);
+hipError_t launch_unitig_walk(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t max_probe,
+                              uint32_t min_count, int k, const uint8_t *links, uint8_t *marks, bool circular, uint64_t bound, ulonglong2 *counts,
+                              const ulonglong2 *offs, uint64_t cap_unitigs, uint64_t cap_bases, uint64_t *offsets, uint32_t *kmers,
+                              uint64_t *depth_sum, uint8_t *circ_out, uint8_t *bases, uint32_t *flag);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

@@ -1189,6 +1189,55 @@ class NovelTable:
         order = np.argsort(k, kind="stable")
         return k[order], d[order]
 
+    def links(self, min_count: int = 1, cap: Optional[int] = None):
+        """(keys [uint64], links [uint8]) of the solid k-mers, sorted by key: the link byte of a key, in its canonical orientation,
+        has bit b (A C G T = 0 1 2 3) set when the k-mer that follows it with base b is solid too, bit 4 + b when the one in front
+        of it with base b is (pg_unitigs.hip: k_unitig_links).  ``cap`` as ``keys`` takes it."""
+        if not 1 <= int(min_count) <= 0xFFFFFFFF:
+            raise ValueError(f"min_count {min_count} (1 to 2^32 - 1)")
+        n = C.c_uint64()
+
+        def call(m):
+            k, l = np.zeros(m, np.uint64), np.zeros(m, np.uint8)
+            check(self._lib.pg_novel_links(self._h, int(min_count), m, _ptr(k) if m else None, _ptr(l) if m else None, C.byref(n)))
+            return k, l
+        if cap is not None:
+            k, l = call(int(cap))
+            return k, l, int(n.value)
+        call(0)
+        k, l = call(int(n.value))
+        order = np.argsort(k, kind="stable")
+        return k[order], l[order]
+
+    def unitigs(self, min_count: int = 1, cap_unitigs: Optional[int] = None, cap_bases: Optional[int] = None, fill=None) -> dict:
+        """the solid k-mers compacted into unitigs — the non-branching paths of their de Bruijn graph (pg_unitigs.hip) — as arrays:
+        ``offsets`` [uint64], ``kmers`` [uint32], ``depth_sum`` [uint64], ``circular`` [uint8] per unitig and ``bases`` [uint8,
+        ASCII]: unitig u spells ``bases[offsets[u] : offsets[u] + kmers[u] + k - 1]``.  A linear unitig comes in one of its two
+        orientations (``novel.canonical_unitig`` picks one), a circular one from its smallest k-mer on, its last k - 1 bases
+        repeating its first.  Two calls: one that counts, one that fills.  ``cap_unitigs`` / ``cap_bases`` (tests of the capacity
+        protocol): ONE call with arrays of that many entries, filled with the byte ``fill`` first, and ``nunitigs``, ``nbases``,
+        ``ncircular`` — the full numbers — beside them."""
+        if not 1 <= int(min_count) <= 0xFFFFFFFF:
+            raise ValueError(f"min_count {min_count} (1 to 2^32 - 1)")
+        nu, nb, nc = C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+        def call(mu, mb):
+            a = {"offsets": np.zeros(mu, np.uint64), "kmers": np.zeros(mu, np.uint32), "depth_sum": np.zeros(mu, np.uint64),
+                 "circular": np.zeros(mu, np.uint8), "bases": np.zeros(mb, np.uint8)}
+            if fill is not None:
+                for v in a.values():
+                    v.view(np.uint8)[:] = int(fill)
+            check(self._lib.pg_novel_unitigs(self._h, int(min_count), mu, mb, *[_ptr(a[f]) if len(a[f]) else None for f in
+                                                                                   ("offsets", "kmers", "depth_sum", "circular", "bases")],
+                                             C.byref(nu), C.byref(nb), C.byref(nc)))
+            return a
+        if cap_unitigs is not None or cap_bases is not None:
+            a = call(int(cap_unitigs or 0), int(cap_bases or 0))
+            a.update(nunitigs=int(nu.value), nbases=int(nb.value), ncircular=int(nc.value))
+            return a
+        call(0, 0)
+        return call(int(nu.value), int(nb.value))
+
     def stats(self) -> dict:
         """``nkeys`` (the novel k-mers held), ``nslots``, ``grown`` (the times the table has grown)"""
         v = [C.c_uint64() for _ in range(3)]
@@ -1238,6 +1287,16 @@ def novel_last_timing() -> dict:
     ms = (C.c_float * 4)()
     check(_lib.load().pg_novel_last_timing(ms))
     return dict(zip(("count_ms", "grow_ms", "scan_ms", "runs_ms"), (float(x) for x in ms)))
+
+
+def novel_unitigs_last_timing() -> dict:
+    """HIP-event milliseconds of k_unitig_links and of k_unitig_walk's linear and circular rounds (every pass of each; 0: not run)
+    as the ``NovelTable`` of this thread's last ``.links`` or ``.unitigs`` call has summed them since its planes were built (the sums
+    are the table's own): a counting call and the filling call behind it read as one; a call at another ``min_count``, or the first
+    after an ``add`` or a ``clear``, starts from zero"""
+    ms = (C.c_float * 3)()
+    check(_lib.load().pg_novel_unitigs_last_timing(ms))
+    return dict(zip(("links_ms", "walk_ms", "circular_ms"), (float(x) for x in ms)))
 
 
 def homology_classes(name_lists: Sequence[Sequence[str]]) -> np.ndarray:

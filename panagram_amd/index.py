@@ -1590,16 +1590,19 @@ class Index:
         return scr.frames(counts, names, int(self.k), min_count, tot["windows"], tot["hits"], tot["reads"], tot["read_bases"], genomes)
 
     def novel(self, samples, min_count: Optional[int] = None, batch_bytes: Optional[int] = None, kmers: bool = False,
-              regions: bool = False, min_bases: int = 0):
+              regions: bool = False, min_bases: int = 0, unitigs: bool = False, min_unitig_bases: int = 0):
         """(stats, spectrum, kmers, regions) — ``novel.stats``, ``novel.spectrum_frame``, ``novel.kmers_frame`` (None unless
         ``kmers``), ``novel.regions_frame`` filtered by ``min_bases`` (None unless ``regions``) — of ONE sample from outside the
         index: the distinct k-mers it holds that NO indexed genome does, their depth spectrum, and for an assembly where they
         lie.  ``samples``, ``batch_bytes`` and the default of ``min_count`` as ``screen`` takes them; the sample is streamed once
         through the table of every sample's k-mers and its missing windows are counted in a table of their own that grows on the
         GPU (``engine.NovelTable``).  A k-mer is solid when the sample holds it at least ``min_count`` times — the only error
-        filter.  ValueError: a missing file, a torn last record, ``min_count`` outside 1..2^32 - 1, a negative ``min_bases``,
-        ``regions`` with a FASTQ file (regions need an assembly); RuntimeError: the cached table holds some anchors' k-mers
-        only."""
+        filter.  With ``unitigs`` a fifth value follows: ``novel.unitigs_frame`` — the solid k-mers compacted on the GPU into the
+        non-branching paths of their de Bruijn graph (``engine.NovelTable.unitigs``: an insertion is one unitig, a plasmid a
+        circular one), those of at least ``min_unitig_bases`` bases — from the same novel table, the sample still streamed once.
+        ValueError: a missing file, a torn last record, ``min_count`` outside 1..2^32 - 1, a negative ``min_bases`` or
+        ``min_unitig_bases``, ``regions`` with a FASTQ file (regions need an assembly); RuntimeError: the cached table holds some
+        anchors' k-mers only."""
         from . import novel as nov, place as pl
         samples = [samples] if isinstance(samples, (str, os.PathLike)) else list(samples)
         paths = [os.fspath(p) for p in samples]
@@ -1610,6 +1613,8 @@ class Index:
             raise ValueError("novel: regions need an assembly: " + ", ".join(repr(p) for p in paths if is_fastq(p)) + " is FASTQ")
         if int(min_bases) < 0:
             raise ValueError(f"novel: min_bases={min_bases} must not be negative")
+        if int(min_unitig_bases) < 0:
+            raise ValueError(f"novel: min_unitig_bases={min_unitig_bases} must not be negative")
         min_count = nov.check_min_count(nov.default_min_count(any(is_fastq(p) for p in paths)) if min_count is None else min_count)
         batch_bytes = pl.DEFAULT_BATCH_BYTES if batch_bytes is None else int(batch_bytes)
         if batch_bytes < 1:
@@ -1645,10 +1650,15 @@ class Index:
                         ss.close()
             counts = nt.result(min_count)
             kmers_df = nov.kmers_frame(*nt.keys(min_count), k) if kmers else None
+            if unitigs:
+                u = nt.unitigs(min_count)
+                unitigs_df = nov.unitigs_frame(u["offsets"], u["kmers"], u["depth_sum"], u["circular"], u["bases"], k, min_unitig_bases)
         finally:
             nt.close()
         regions_df = nov.filter_regions(pd.concat(found, ignore_index=True) if found else nov.no_regions(), min_bases) if regions else None
         st = nov.stats(counts, min_count, tot["windows"], tot["hits"], tot["reads"], tot["read_bases"], regions_df)
+        if unitigs:
+            return st, nov.spectrum_frame(counts["depth_hist"]), kmers_df, regions_df, unitigs_df
         return st, nov.spectrum_frame(counts["depth_hist"]), kmers_df, regions_df
 
     def locate(self, queries, genomes=None, k=None, min_run: int = 1, max_gap: int = 1000, max_shift: int = 100, min_kmers: int = 1,

@@ -131,3 +131,69 @@ def write_kmers(kmers: pd.DataFrame, path) -> None:
 
 def write_regions(regions: pd.DataFrame, path) -> None:
     regions.to_csv(path, sep="\t", index=False)
+
+
+# ---------------------------------------------------------------------------
+# unitigs: the solid novel k-mers compacted into sequences (pg_unitigs.hip; ``engine.NovelTable.unitigs``)
+# ---------------------------------------------------------------------------
+UNITIG_COLUMNS = ["unitig", "bases", "kmers", "depth", "circular", "sequence"]
+UNITIG_STAT_NAMES = ["unitigs", "unitig_bases", "unitig_n50", "longest_unitig", "circular_unitigs"]
+FASTA_WIDTH = 80
+_COMPLEMENT = str.maketrans("ACGT", "TGCA")
+
+
+def canonical_unitig(seq: str) -> str:
+    """the smaller of a sequence and its reverse complement: what a linear unitig reads as, whichever end its walk began at"""
+    rc = seq.translate(_COMPLEMENT)[::-1]
+    return min(seq, rc)
+
+
+def unitigs_frame(offsets, kmers, depth_sum, circular, bases, k: int, min_unitig_bases: int = 0) -> pd.DataFrame:
+    """UNITIG_COLUMNS of ``engine.NovelTable.unitigs``' arrays: ``bases`` = kmers + k - 1, ``depth`` = the mean depth of the
+    unitig's k-mers to two decimals, linear sequences canonicalised (a circular one starts at its smallest k-mer as it came),
+    those of fewer than ``min_unitig_bases`` bases dropped, sorted by (-bases, sequence) and named u1, u2, ... in that order"""
+    if int(min_unitig_bases) < 0:
+        raise ValueError(f"novel: min_unitig_bases={min_unitig_bases} must not be negative")
+    off, n = np.asarray(offsets, np.int64).ravel(), np.asarray(kmers, np.int64).ravel()
+    ds, circ = np.asarray(depth_sum, np.uint64).ravel(), np.asarray(circular, np.int64).ravel()
+    text = np.asarray(bases, np.uint8).tobytes().decode("ascii")
+    length = n + int(k) - 1
+    seqs = [text[o:o + l] if c else canonical_unitig(text[o:o + l]) for o, l, c in zip(off.tolist(), length.tolist(), circ.tolist())]
+    keep = [i for i in range(len(seqs)) if length[i] >= int(min_unitig_bases)]
+    keep.sort(key=lambda i: (-int(length[i]), seqs[i]))
+    depth = [round(int(ds[i]) / int(n[i]), 2) for i in keep]
+    return pd.DataFrame({"unitig": [f"u{j + 1}" for j in range(len(keep))], "bases": length[keep], "kmers": n[keep],
+                         "depth": np.asarray(depth, np.float64), "circular": circ[keep], "sequence": [seqs[i] for i in keep]},
+                        columns=UNITIG_COLUMNS)
+
+
+def unitig_header(row) -> str:
+    return f">{row.unitig} bases={int(row.bases)} kmers={int(row.kmers)} depth={float(row.depth):.2f} circular={int(row.circular)}"
+
+
+def unitig_fasta(frame: pd.DataFrame) -> str:
+    """FASTA text: ``>u7 bases=… kmers=… depth=… circular=0|1``, the sequence in lines of FASTA_WIDTH"""
+    out = []
+    for row in frame.itertuples(index=False):
+        out.append(unitig_header(row))
+        out.extend(row.sequence[i:i + FASTA_WIDTH] for i in range(0, len(row.sequence), FASTA_WIDTH))
+    return "".join(line + "\n" for line in out)
+
+
+def write_unitigs(frame: pd.DataFrame, path) -> None:
+    with open(path, "w") as f:
+        f.write(unitig_fasta(frame))
+
+
+def unitig_stats(frame: pd.DataFrame) -> dict:
+    """UNITIG_STAT_NAMES: ``unitig_n50`` = the length L at which the unitigs of at least L bases hold half of all bases or more
+    (0: no unitig)"""
+    lens = np.sort(np.asarray(frame["bases"], np.int64))[::-1]
+    total = int(lens.sum())
+    n50 = int(lens[np.searchsorted(np.cumsum(lens), (total + 1) // 2)]) if len(lens) else 0
+    return {"unitigs": int(len(lens)), "unitig_bases": total, "unitig_n50": n50, "longest_unitig": int(lens[0]) if len(lens) else 0,
+            "circular_unitigs": int(np.asarray(frame["circular"], np.int64).sum())}
+
+
+def unitig_stat_lines(st: dict) -> List[str]:
+    return [f"{n}\t{int(st[n])}" for n in UNITIG_STAT_NAMES]

@@ -930,6 +930,30 @@ int pg_novel_unitigs(pg_novel *nv, uint32_t min_count, uint64_t cap_unitigs, uin
  * counting call and the filling call behind it read as one.  All 0 behind a call that found no solid key.  What
  * tools/novel_unitigs_rate.py reports. */
 int pg_novel_unitigs_last_timing(float *ms_out);
+/* Error tips clipped and bubbles popped on the graph of the solid keys at min_count, before it is compacted (pg_unitigs.hip:
+ * k_unitig_clean; the header of that file states the rule in full).  With the vocabulary above, over the graph G of the current nodes:
+ *   side    the right side of a linear unitig U = w1 .. wn is out(wn), the left side in(w1): DEAD when empty, ATTACHED BY v when it
+ *           holds one base and the oriented k-mer v it names is a node outside U that is not its own reverse complement
+ *   tip     n <= tip_kmers, one side dead, the other attached by v; S = the other oriented k-mers with an edge into v on that side;
+ *           clipped iff S is not empty and depth(attached end node) * 1000 <= ratio_milli * max over S of depth(s).  A unitig dead
+ *           on both sides, and a fork whose only sibling is a k-mer the table holds, are never tips.
+ *   bubble  n <= bubble_kmers, attached by p on the left and by q on the right; a parallel U' of n' <= bubble_kmers nodes leaves p
+ *           by another successor and is attached by the same p and q; with e(X) = min(depth of X's two end nodes), U is popped iff
+ *           some parallel U' has e(U) * 1000 <= ratio_milli * e(U').  ratio_milli < 1000: two branches never remove each other, and
+ *           an even (heterozygous) bubble stays.
+ *   rounds  every round decides on the graph the round before left and drops what it found at once; the rounds stop at the first
+ *           that drops nothing, or after max_rounds.  Each is one k_unitig_links pass and one k_unitig_clean pass.
+ * stats[5] = {tips clipped, their k-mers, bubbles popped, their k-mers, rounds that dropped something}.  Behind it pg_novel_links and
+ * pg_novel_unitigs with the same min_count answer for the cleaned graph — a dropped key is no node: absent from the links, no part
+ * of any unitig, a cut in its neighbours' link bytes.  The raw graph comes back with max_rounds == 0, another min_count,
+ * pg_novel_add_seqset or pg_novel_clear.  1 <= tip_kmers, bubble_kmers <= 1024; 1 <= ratio_milli <= 999; max_rounds <= 64.
+ * PG_E_INVALID: a parameter out of range, min_count == 0, k < 2, a stale handle, a NULL argument; PG_E_CAPACITY: no memory for the
+ * three byte planes; PG_E_INTERNAL: the planes contradict the table (every walk is bounded by tip_kmers or bubble_kmers). */
+int pg_novel_clean(pg_novel *nv, uint32_t min_count, uint32_t tip_kmers, uint32_t bubble_kmers, uint32_t ratio_milli, uint32_t max_rounds,
+                   uint64_t *stats);
+/* ms_out[2] = the HIP-event milliseconds of the k_unitig_links passes and of the k_unitig_clean passes of this host thread's last
+ * pg_novel_clean (0: not run). */
+int pg_novel_clean_last_timing(float *ms_out);
 /* exact k nearest neighbours among the rows of a dense float32 matrix, under squared Euclidean distance: the neighbour
  * graph that umap.UMAP(n_neighbors, ...).fit_transform(paircounts) builds first (panagram/index.py:1131-1137: run_umap, on the
  * bins x genomes pair-count matrix of a chromosome or of the whole genome).  X is n x ncols, row-major, a host pointer (a

@@ -37,9 +37,10 @@ of the indexed genomes a sample from outside the index holds and how much of eac
 through the table of every sample's k-mers and counted per k-mer, and one pass over the table joins the counts with the presence
 masks on the GPU; and
 `novel <index_dir> <sample.fq|sample.fa> [more ...] [--min-count N] [--spectrum FILE] [--kmers FILE] [--regions FILE] [--min-bases B]
-[--unitigs FILE] [--min-unitig-bases B] [--summary FILE]` says the reverse: the distinct k-mers of the sample that NO indexed genome
+[--unitigs FILE] [--min-unitig-bases B] [--clean [--tip-kmers T] [--bubble-kmers B] [--clean-ratio R] [--clean-rounds N]]
+[--summary FILE]` says the reverse: the distinct k-mers of the sample that NO indexed genome
 holds, their depth spectrum, for an assembly where they lie, and with --unitigs the novel sequences themselves, the solid k-mers
-compacted into unitigs — the sample's windows that miss the table are counted in a key table of their own that grows on the GPU; and
+compacted into unitigs, with --clean after error tips were clipped and bubbles popped — the sample's windows that miss the table are counted in a key table of their own that grows on the GPU; and
 `add <index_dir> <new_samples.tsv>` appends samples to a finished index without re-anchoring it: every anchor already there is probed
 against the new samples' k-mers alone, its rows come back from bitmap.1.gz, and one kernel pass writes the wider rows; new anchors are
 anchored the ordinary way, and the tree is staged and renamed at the end, samples.tsv last; and
@@ -272,6 +273,14 @@ def main(argv=None):
                      help="also write FASTA: the solid novel k-mers compacted on the GPU into unitigs, the non-branching paths of their de Bruijn "
                           "graph (>u1 bases= kmers= depth= circular=), longest first; prints unitigs, unitig_bases, unitig_n50, ... behind the statistics")
     nvl.add_argument("--min-unitig-bases", type=int, default=None, metavar="B", help="unitigs of at least B bases (default 0; needs --unitigs)")
+    nvl.add_argument("--clean", action="store_true",
+                     help="clip error tips and pop bubbles on the GPU before the compaction (needs --unitigs): a dead-end branch, or the weaker "
+                          "of two parallel branches, is dropped when a sibling is deeper by 1 / R or more; prints clipped_tips, clipped_kmers, "
+                          "popped_bubbles, popped_kmers, clean_rounds behind the unitig statistics")
+    nvl.add_argument("--tip-kmers", type=int, default=None, metavar="T", help="tips of at most T k-mers (1 to 1024; default 2 k; needs --clean)")
+    nvl.add_argument("--bubble-kmers", type=int, default=None, metavar="B", help="bubble branches of at most B k-mers (1 to 1024; default 2 k; needs --clean)")
+    nvl.add_argument("--clean-ratio", type=float, default=None, metavar="R", help="above 0 and below 1 (default 0.25; needs --clean)")
+    nvl.add_argument("--clean-rounds", type=int, default=None, metavar="N", help="rounds at the most, 0 to 64 (default 4; needs --clean)")
     nvl.add_argument("--summary", metavar="FILE", default=None, help="also write the statistics to FILE")
     nvl.add_argument("--batch-bytes", type=int, default=None, metavar="N", help="FASTQ text bytes joined at a time (default 2^28)")
     nvl.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
@@ -608,6 +617,16 @@ def main(argv=None):
             ap.error("novel: --min-unitig-bases needs --unitigs FILE")
         if a.min_unitig_bases is not None and a.min_unitig_bases < 0:
             ap.error("novel: --min-unitig-bases not negative")
+        clean_flags = {"--tip-kmers": a.tip_kmers, "--bubble-kmers": a.bubble_kmers, "--clean-ratio": a.clean_ratio, "--clean-rounds": a.clean_rounds}
+        if a.clean and not a.unitigs:
+            ap.error("novel: --clean needs --unitigs FILE")
+        for flag, v in clean_flags.items():
+            if v is not None and not a.clean:
+                ap.error(f"novel: {flag} needs --clean")
+        if a.clean_ratio is not None and not 0.0 < a.clean_ratio < 1.0:
+            ap.error("novel: --clean-ratio is above 0 and below 1")
+        if any(v is not None and not 1 <= v <= 1024 for v in (a.tip_kmers, a.bubble_kmers)) or (a.clean_rounds is not None and not 0 <= a.clean_rounds <= 64):
+            ap.error("novel: --tip-kmers and --bubble-kmers are 1 to 1024, --clean-rounds 0 to 64")
         from .index import Index, is_fastq
         from . import novel
         if a.regions and any(is_fastq(r) for r in a.samples):
@@ -625,7 +644,9 @@ def main(argv=None):
             try:
                 stats, spectrum, kmers, regions, *unitigs = idx.novel(a.samples, a.min_count, a.batch_bytes, kmers=bool(a.kmers),
                                                                       regions=bool(a.regions), min_bases=a.min_bases, unitigs=bool(a.unitigs),
-                                                                      min_unitig_bases=a.min_unitig_bases or 0)
+                                                                      min_unitig_bases=a.min_unitig_bases or 0,
+                                                                      clean={"tip_kmers": a.tip_kmers, "bubble_kmers": a.bubble_kmers,
+                                                                             "ratio": a.clean_ratio, "rounds": a.clean_rounds} if a.clean else None)
             except ValueError as e:
                 ap.error(f"novel: {e}")
         finally:
@@ -642,6 +663,8 @@ def main(argv=None):
         if a.unitigs:
             novel.write_unitigs(unitigs[0], a.unitigs)
             sys.stdout.writelines(line + "\n" for line in novel.unitig_stat_lines(novel.unitig_stats(unitigs[0])))
+            if a.clean:
+                sys.stdout.writelines(line + "\n" for line in novel.clean_stat_lines(unitigs[1]))
         return 0
     if a.cmd == "locate":
         if (a.queries is None) == (a.genes is None):

@@ -180,6 +180,8 @@ PROTOTYPES = {
     "pg_novel_links": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, _vp, _u64p]),
     "pg_novel_unitigs": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _u64p, _u64p, _u64p]),
     "pg_novel_unitigs_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
+    "pg_novel_clean": (C.c_int, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
+    "pg_novel_clean_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
     "pg_knn_rows": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "pg_result_write_bgzf": (C.c_int, [_vp, C.c_int, C.c_char_p, C.c_char_p, C.c_int, C.c_int]),
     "pg_bgzf_inflate": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, C.c_uint64, _u64p]),

@@ -27,6 +27,11 @@ struct pg_novel {
     struct Unitigs {
         uint32_t min_count = 0;  // 0: nothing kept
         uint8_t *d_links = nullptr, *d_marks = nullptr;
+        // pg_novel_clean ran for this min_count: d_drop is the third plane (a set byte: no node any more), the two planes above are
+        // those of the cleaned graph, and its nodes — all and per block of the scan — stand where the scan's solid keys stood
+        uint8_t *d_drop = nullptr;
+        uint64_t nodes = 0;
+        std::vector<uint32_t> block_nodes;
         bool walked = false;                   // the counts below stand and `marks` holds the winners of both rounds
         std::vector<ulonglong2> lin, circ;     // per block of the scan: {winners, their nodes} of the linear / the circular round
         uint64_t nlin = 0, lin_nodes = 0, ncirc = 0, circ_nodes = 0;
@@ -39,11 +44,13 @@ namespace {
 thread_local float g_novel_ms[4] = {0, 0, 0, 0};  // k_novel_count, k_novel_grow, k_novel_scan (both passes), k_novel_runs (both passes)
 
 thread_local float g_unitig_ms[3] = {0, 0, 0};  // k_unitig_links, k_unitig_walk of the linear round (all passes), of the circular round
+thread_local float g_clean_ms[2] = {0, 0};      // the k_unitig_links passes and the k_unitig_clean passes of the last pg_novel_clean
 
 // (behind a synchronise of the handle's stream: no kernel reads the planes)
 void unitig_drop(pg_novel *nv) {
     if (nv->ut.d_links) hipFree(nv->ut.d_links);
     if (nv->ut.d_marks) hipFree(nv->ut.d_marks);
+    if (nv->ut.d_drop) hipFree(nv->ut.d_drop);
     nv->ut = pg_novel::Unitigs();
 }
 
@@ -402,6 +409,10 @@ int unitig_planes(pg_novel *nv, const char *fn, uint32_t min_count, uint64_t *h,
     if (int r = novel_scan_count(nv, fn, min_count, h, &block_solid, &ms_scan)) return r;
     if (h[1] != 0 && nv->ut.min_count == min_count) {  // (the planes kept: this handle's times go on adding up)
         std::copy(nv->ut.ms, nv->ut.ms + 3, g_unitig_ms);
+        if (nv->ut.d_drop) {  // (cleaned: the surviving nodes are the graph)
+            h[1] = nv->ut.nodes;
+            block_solid = nv->ut.block_nodes;
+        }
         return PG_OK;
     }
     g_unitig_ms[0] = g_unitig_ms[1] = g_unitig_ms[2] = 0;
@@ -462,7 +473,8 @@ int novel_links(pg_novel *nv, uint32_t min_count, uint64_t cap, uint64_t *keys_o
         return fail(PG_E_CAPACITY, "%s: no memory for %llu keys", fn, (unsigned long long)take);
     }
     if (e == hipSuccess)
-        e = launch_unitig_links_emit(st, nv->d_keys, nv->d_depth, nv->ut.d_links, nv->nslots, min_count, d_offs.get(), take, d_k.get(), d_l.get());
+        e = launch_unitig_links_emit(st, nv->d_keys, nv->d_depth, nv->ut.d_links, nv->nslots, min_count, d_offs.get(), take, d_k.get(), d_l.get(),
+                                     nv->ut.d_drop);
     if (e == hipSuccess) e = hipMemcpyAsync(keys_out, d_k.get(), take * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipMemcpyAsync(links_out, d_l.get(), take, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -470,6 +482,99 @@ int novel_links(pg_novel *nv, uint32_t min_count, uint64_t cap, uint64_t *keys_o
         hipStreamSynchronize(st);
         return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     }
+    return PG_OK;
+}
+
+// the rounds of pg_novel_clean: links, clean, a read of the counts; a last links pass behind the last round that dropped something.
+// The handle keeps the three planes of the cleaned graph for `min_count`; max_rounds == 0 and a table without a solid key keep nothing
+int novel_clean(pg_novel *nv, uint32_t min_count, uint32_t tip_kmers, uint32_t bubble_kmers, uint32_t ratio_milli, uint32_t max_rounds,
+                uint64_t *stats) {
+    const char *fn = "pg_novel_clean";
+    const int k = nv->tbl->k;
+    if (k < 2 || k > 32) return fail(PG_E_INVALID, "%s: a table of k = %d (unitigs: 2 to 32)", fn, k);
+    if (tip_kmers < 1 || tip_kmers > UNITIG_CLEAN_MAX_KMERS || bubble_kmers < 1 || bubble_kmers > UNITIG_CLEAN_MAX_KMERS)
+        return fail(PG_E_INVALID, "%s: tip_kmers = %u, bubble_kmers = %u (1 to %u)", fn, tip_kmers, bubble_kmers, UNITIG_CLEAN_MAX_KMERS);
+    if (ratio_milli < 1 || ratio_milli > 999) return fail(PG_E_INVALID, "%s: ratio_milli = %u (1 to 999)", fn, ratio_milli);
+    if (max_rounds > UNITIG_CLEAN_MAX_ROUNDS) return fail(PG_E_INVALID, "%s: max_rounds = %u (0 to %u)", fn, max_rounds, UNITIG_CLEAN_MAX_ROUNDS);
+    uint64_t h[NOVEL_SCAN_WORDS];
+    std::vector<uint32_t> block_solid;
+    float ms_scan = 0;
+    if (int r = novel_scan_count(nv, fn, min_count, h, &block_solid, &ms_scan)) return r;
+    std::fill(stats, stats + 5, 0);
+    g_clean_ms[0] = g_clean_ms[1] = 0;
+    unitig_drop(nv);  // (the raw graph's planes are built again by whoever asks next)
+    if (h[1] == 0 || max_rounds == 0) return PG_OK;
+    hipStream_t st = nv->ctx->stream;
+    const uint32_t blocks = novel_scan_blocks(nv->nslots);
+    const size_t bytes = (size_t)std::max<uint64_t>(nv->nslots, 4);  // (marks and drop bytes are set through 32-bit words)
+    DevBuf<uint8_t> links, marks, drop;
+    DevBuf<uint32_t> d_nodes, d_flag;
+    DevBuf<uint64_t> d_counts;
+    hipError_t e = links.alloc(bytes);
+    if (e == hipSuccess) e = marks.alloc(bytes);
+    if (e == hipSuccess) e = drop.alloc(bytes);
+    if (e == hipSuccess) e = d_nodes.alloc(blocks);
+    if (e == hipSuccess) e = d_counts.alloc((size_t)blocks * 4);
+    if (e == hipSuccess) e = d_flag.alloc(1);
+    if (e == hipErrorOutOfMemory) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_CAPACITY, "%s: no memory for three byte planes of %llu slots", fn, (unsigned long long)nv->nslots);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(marks.get(), 0, bytes, st);
+    if (e == hipSuccess) e = hipMemsetAsync(drop.get(), 0, bytes, st);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag.get(), 0, 4, st);
+    std::vector<uint32_t> block_nodes(blocks);
+    std::vector<uint64_t> counts((size_t)blocks * 4);
+    uint32_t flag = 0;
+    for (uint32_t round = 0; e == hipSuccess; ++round) {
+        float ms_links = 0, ms_clean = 0;
+        LaunchTimer tl(&ms_links), tc(&ms_clean);
+        const bool last = round == max_rounds;
+        e = tl.start(st);
+        if (e == hipSuccess)
+            e = launch_unitig_links(st, nv->d_keys, nv->d_depth, nv->nslots, nv->max_probe, min_count, k, links.get(), drop.get(), d_nodes.get());
+        if (e == hipSuccess) e = tl.stop(st);
+        if (e == hipSuccess && !last) {
+            e = tc.start(st);
+            if (e == hipSuccess)
+                e = launch_unitig_clean(st, nv->d_keys, nv->d_depth, nv->nslots, nv->max_probe, min_count, k, links.get(), drop.get(), tip_kmers,
+                                        bubble_kmers, ratio_milli, d_counts.get(), d_flag.get());
+            if (e == hipSuccess) e = tc.stop(st);
+            if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), counts.size() * 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(&flag, d_flag.get(), 4, hipMemcpyDeviceToHost, st);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(block_nodes.data(), d_nodes.get(), (size_t)blocks * 4, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+        tl.read();
+        g_clean_ms[0] += ms_links;
+        if (last) break;
+        tc.read();
+        g_clean_ms[1] += ms_clean;
+        if (flag) return fail(PG_E_INTERNAL, "%s: the link plane contradicts the table in round %u", fn, round + 1);
+        uint64_t got[4] = {0, 0, 0, 0};
+        for (uint32_t b = 0; b < blocks; ++b)
+            for (int i = 0; i < 4; ++i) got[i] += counts[(size_t)b * 4 + i];
+        if (got[0] + got[2] == 0) break;  // (nothing dropped: the link plane is the final graph's)
+        for (int i = 0; i < 4; ++i) stats[i] += got[i];
+        ++stats[4];
+    }
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);
+        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    uint64_t nodes = 0;
+    for (uint32_t n : block_nodes) nodes += n;
+    if (nodes + stats[1] + stats[3] != h[1])
+        return fail(PG_E_INTERNAL, "%s: %llu nodes left and %llu dropped of %llu solid keys", fn, (unsigned long long)nodes,
+                    (unsigned long long)(stats[1] + stats[3]), (unsigned long long)h[1]);
+    std::swap(nv->ut.d_links, links.p);
+    std::swap(nv->ut.d_marks, marks.p);
+    std::swap(nv->ut.d_drop, drop.p);
+    nv->ut.min_count = min_count;
+    nv->ut.nodes = nodes;
+    nv->ut.block_nodes = block_nodes;
+    nv->ut.ms[0] = g_clean_ms[0];
     return PG_OK;
 }
 
@@ -500,7 +605,7 @@ int unitig_pass(pg_novel *nv, const char *fn, bool circular, uint64_t bound, std
         e = launch_unitig_walk(st, nv->d_keys, nv->d_depth, nv->nslots, nv->max_probe, nv->ut.min_count, nv->tbl->k, nv->ut.d_links, nv->ut.d_marks,
                                circular, bound, d_counts.get(), d_offs.get(), out ? out->cap_u : 0, out ? out->cap_b : 0,
                                out ? out->offsets.get() : nullptr, out ? out->kmers.get() : nullptr, out ? out->depth_sum.get() : nullptr,
-                               out ? out->circular.get() : nullptr, out ? out->bases.get() : nullptr, d_flag.get());
+                               out ? out->circular.get() : nullptr, out ? out->bases.get() : nullptr, d_flag.get(), nv->ut.d_drop);
     if (e == hipSuccess) e = tm.stop(st);
     if (e == hipSuccess && counts) {
         counts->assign(blocks, make_ulonglong2(0, 0));
@@ -706,6 +811,22 @@ extern "C" int pg_novel_unitigs(pg_novel *nv, uint32_t min_count, uint64_t cap_u
     if (!nv || !nunitigs || !nbases || !ncircular || (cap_unitigs && (!offsets || !kmers || !depth_sum || !circular)) || (cap_bases && !bases))
         return fail(PG_E_INVALID, "pg_novel_unitigs: NULL argument");
     return novel_unitigs(nv, min_count, cap_unitigs, cap_bases, offsets, kmers, depth_sum, circular, bases, nunitigs, nbases, ncircular);
+    PG_API_END
+}
+
+extern "C" int pg_novel_clean(pg_novel *nv, uint32_t min_count, uint32_t tip_kmers, uint32_t bubble_kmers, uint32_t ratio_milli, uint32_t max_rounds,
+                              uint64_t *stats) {
+    PG_API_BEGIN
+    if (!nv || !stats) return fail(PG_E_INVALID, "pg_novel_clean: NULL argument");
+    return novel_clean(nv, min_count, tip_kmers, bubble_kmers, ratio_milli, max_rounds, stats);
+    PG_API_END
+}
+
+extern "C" int pg_novel_clean_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_novel_clean_last_timing: NULL argument");
+    std::copy(g_clean_ms, g_clean_ms + 2, ms_out);
+    return PG_OK;
     PG_API_END
 }
 

@@ -466,14 +466,24 @@ hipError_t launch_novel_runs(hipStream_t st, const SubTable &t, const SeqDesc *s
 //               offs != NULL  emit: offs[b] = {the unitigs, the bases} in front of the block's; offsets, kmers, depth_sum and
 //                             circular of unitig u < cap_unitigs, base i < cap_bases (ASCII) — nothing at or past a cap is written;
 //                             the linear round marks the nodes its winners pass
+//   drop        NULL, or a third byte plane of max(nslots, 4) bytes: a slot whose byte is set is no node for any of these.  links:
+//               block_nodes (NULL: not wanted) takes every block's nodes.
+//   clean       one round of tip clipping and bubble popping over the link plane of the current nodes: sets the drop bytes of what
+//               it drops (by 32-bit atomic OR) and counts[4 b ..] = block b's {tips, their nodes, bubbles, their nodes};
+//               1 <= tip_kmers, bubble_kmers <= UNITIG_CLEAN_MAX_KMERS, 1 <= ratio_milli <= 999
+constexpr uint32_t UNITIG_CLEAN_MAX_KMERS = 1024, UNITIG_CLEAN_MAX_ROUNDS = 64;
 hipError_t launch_unitig_links(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t max_probe,
-                               uint32_t min_count, int k, uint8_t *links);
+                               uint32_t min_count, int k, uint8_t *links, const uint8_t *drop = nullptr, uint32_t *block_nodes = nullptr);
+hipError_t launch_unitig_clean(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t max_probe,
+                               uint32_t min_count, int k, const uint8_t *links, uint8_t *drop, uint32_t tip_kmers, uint32_t bubble_kmers,
+                               uint32_t ratio_milli, uint64_t *counts, uint32_t *flag);
 hipError_t launch_unitig_links_emit(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, const uint8_t *links, uint64_t nslots,
-                                    uint32_t min_count, const uint64_t *offs, uint64_t cap, unsigned long long *out_keys, uint8_t *out_links);
+                                    uint32_t min_count, const uint64_t *offs, uint64_t cap, unsigned long long *out_keys, uint8_t *out_links,
+                                    const uint8_t *drop = nullptr);
 hipError_t launch_unitig_walk(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t max_probe,
                               uint32_t min_count, int k, const uint8_t *links, uint8_t *marks, bool circular, uint64_t bound, ulonglong2 *counts,
                               const ulonglong2 *offs, uint64_t cap_unitigs, uint64_t cap_bases, uint64_t *offsets, uint32_t *kmers,
-                              uint64_t *depth_sum, uint8_t *circ_out, uint8_t *bases, uint32_t *flag);
+                              uint64_t *depth_sum, uint8_t *circ_out, uint8_t *bases, uint32_t *flag, const uint8_t *drop = nullptr);
 // exact k nearest neighbours among the rows of X (n x D float32, row-major; pg_knn.hip): tile i = four words {row0, nrows,
 // lo, hi} — query rows [row0, row0 + nrows), nrows <= threads, search rows [lo, hi) — and a block of `threads` (64 or 256)
 // threads takes one tile.  idx / d2 ([n][K]) get every query row's K entries sorted by (d2, row), (-1, +inf) where the

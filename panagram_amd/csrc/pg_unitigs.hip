@@ -44,6 +44,35 @@
 // the host answers PG_E_INTERNAL.  The walk is serial per lane by design — one key lookup and one byte per step, each an HBM miss —
 // and lanes diverge in length: no wave-collective stands inside a walk loop.
 // Every write to HBM is a vector store or a vector atomic.
+//
+// Cleaning (opt-in; tests/unitigs_clean_ref.py is the same over a dict): error tips clipped and bubbles popped before the compaction.
+// Over the graph G of the current nodes, with tip_kmers T and bubble_kmers B (1 to 1024), a ratio Rm in per mille (1 to 999: strictly
+// below 1, so two branches never remove each other) and a number of rounds (0 to 64):
+//   side        the right side of a linear unitig U = w1 .. wn is out(wn), the left side in(w1).  A side is DEAD when that set is
+//               empty, ATTACHED BY v when it holds exactly one base and the oriented k-mer v it names is a node that is none of U's
+//               nodes on either strand (tested outright: the walk compares every node of U with canon(v)) and not its own reverse
+//               complement; every other side is open.
+//   tip         n <= T, one side dead, the other attached by v.  S = the other oriented k-mers with an edge into v on that side (a
+//               held k-mer is no node: a fork whose only sibling is held has no S).  U is clipped iff S is not empty and
+//               depth(attached end node) * 1000 <= Rm * max over S of depth(s), in 64 bits.  A unitig dead on both sides stays.
+//   bubble      n <= B, the left side attached by p, the right side by q.  A parallel U' starts at another oriented successor
+//               s != w1 of p with in(s) = {p's base}, walks to the right along compactable edges for n' <= B nodes, none of them
+//               canon(p) or canon(q), and its right side is attached by the same oriented q: U' is asked of on its left side what
+//               it is asked of on its right, so the rule reads the same from either end of U.  With e(X) = min(depth of X's two end
+//               nodes), U is popped iff some parallel U' has e(U) * 1000 <= Rm * e(U').  p = q is nothing special; a unitig
+//               parallel to its own reverse complement has equal e and stays.
+//   rounds      Jacobi: every decision of round r is taken on G_r, D_r is what it drops, G_{r+1} = G_r minus D_r; the rounds stop
+//               at the first empty D_r or after `rounds` of them.  The final graph is compacted as any other.
+// A dropped node is no node: a third byte plane `drop` (NULL: nothing was cleaned, and every kernel does what it did without it)
+// that the solid predicate of k_unitig_links (own slot and the eight neighbours), k_unitig_links_emit and k_unitig_walk honours.
+//   k_unitig_clean  one lane per slot, cut as above.  READS the table, the depths and the link plane of G_r alone — a dropped node's
+//                   link byte is 0 and no byte names it, so it is never a start that matters and never met — and WRITES drop bytes
+//                   alone, which only the next k_unitig_links reads: a round has no race and no order.  A side that starts a unitig
+//                   walks at most max(T, B) nodes and abandons beyond; the end with the smaller key decides (n = 1: side 0), as in
+//                   the count pass; it classifies the two sides from the link bytes, looks up a tip's siblings (at most 3
+//                   key_find) or walks a bubble's at most 3 siblings for at most B nodes each, and then walks once more to set the
+//                   drop byte of U's nodes by a 32-bit atomic OR, one writer per node.  counts[4 b ..] = the block's {tips, their
+//                   nodes, bubbles, their nodes}.  A contradiction between planes and table raises flag[0].
 #include "pg_kernels.h"
 #include "pg_keytable_dev.h"  // key_find
 
@@ -59,6 +88,7 @@ struct UnitigTable {
     uint64_t smask, kmask;
     uint32_t max_probe, min_count;
     int k;
+    const uint8_t *drop;  // NULL: nothing was cleaned
 };
 
 // the reverse complement of an oriented k-mer (first base most significant)
@@ -93,18 +123,35 @@ __device__ __forceinline__ int unitig_step(const UnitigTable &t, uint64_t w, uin
     return __popc(in2) == 1 ? STEP_OK : STEP_NONE;
 }
 
+// the sum of v over the block's lanes (every lane reaches this; lds: 4 words; all lanes get the sum)
+__device__ __forceinline__ uint64_t block_sum64(uint64_t v, unsigned long long *lds) {
+    for (int off = 32; off; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)v, off), hi = (uint32_t)__shfl_down((int)(uint32_t)(v >> 32), off);
+        v += (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    __syncthreads();  // (lds of an earlier call has been read)
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return lds[0] + lds[1] + lds[2] + lds[3];
+}
+
 // ---- the link plane ----
 // block b: slots [b * per, (b + 1) * per), per = novel_scan_per_block(nslots), cut at nslots.  links[s] = the link byte of a solid
-// slot, 0 of every other.
+// slot, 0 of every other.  drop != NULL: a slot whose drop byte is set is no node, as a slot and as a neighbour; block_nodes != NULL:
+// block_nodes[b] = the nodes of block b.
 __global__ __launch_bounds__(256) void k_unitig_links(const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ depth,
                                                       uint64_t nslots, uint32_t max_probe, uint32_t min_count, int k,
-                                                      uint8_t *__restrict__ links) {
+                                                      uint8_t *__restrict__ links, const uint8_t *__restrict__ drop,
+                                                      uint32_t *__restrict__ block_nodes) {
+    __shared__ unsigned long long sum_s[4];
+    uint64_t mine = 0;
     const uint64_t per = novel_scan_per_block(nslots), s0 = (uint64_t)blockIdx.x * per, s1 = min(nslots, s0 + per);
     const uint64_t smask = nslots - 1, kmask = kmer_mask(k);
     for (uint64_t s = s0 + threadIdx.x; s < s1; s += 256) {
         const unsigned long long x = keys[s];
         uint32_t link = 0;
-        if (x != EMPTY_KEY && depth[s] >= min_count) {
+        if (x != EMPTY_KEY && depth[s] >= min_count && !(drop && drop[s])) {
+            ++mine;
             // the eight neighbours' keys, their home slots loaded together; a home that holds another key walks on (key_find)
             uint64_t nb[8], home[8];
             unsigned long long at_home[8];
@@ -126,11 +173,15 @@ __global__ __launch_bounds__(256) void k_unitig_links(const unsigned long long *
                                                     : key_find<uint32_t>(keys, smask, max_probe, nb[i], SLOT_ABSENT);
             }
 #pragma unroll
-            for (uint32_t i = 0; i < 8; ++i) d[i] = slot[i] != SLOT_ABSENT ? depth[slot[i]] : 0u;
+            for (uint32_t i = 0; i < 8; ++i) d[i] = slot[i] != SLOT_ABSENT && !(drop && drop[slot[i]]) ? depth[slot[i]] : 0u;
 #pragma unroll
             for (uint32_t i = 0; i < 8; ++i) link |= (d[i] >= min_count ? 1u : 0u) << i;  // (min_count >= 1: an absent key's 0 is below it)
         }
         links[s] = (uint8_t)link;
+    }
+    if (block_nodes) {  // (uniform over the grid: every lane reaches the barriers)
+        const uint64_t all = block_sum64(mine, sum_s);
+        if (threadIdx.x == 0) block_nodes[blockIdx.x] = (uint32_t)all;
     }
 }
 
@@ -139,7 +190,8 @@ __global__ __launch_bounds__(256) void k_unitig_links(const unsigned long long *
 __global__ __launch_bounds__(256) void k_unitig_links_emit(const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ depth,
                                                            const uint8_t *__restrict__ links, uint64_t nslots, uint32_t min_count,
                                                            const uint64_t *__restrict__ offs, uint64_t cap,
-                                                           unsigned long long *__restrict__ out_keys, uint8_t *__restrict__ out_links) {
+                                                           unsigned long long *__restrict__ out_keys, uint8_t *__restrict__ out_links,
+                                                           const uint8_t *__restrict__ drop) {
     __shared__ uint32_t wsolid[4];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint64_t per = novel_scan_per_block(nslots), s0 = (uint64_t)blockIdx.x * per, s1 = min(nslots, s0 + per);
@@ -147,7 +199,7 @@ __global__ __launch_bounds__(256) void k_unitig_links_emit(const unsigned long l
     for (uint64_t g = s0; g < s1; g += 256) {  // (bounds uniform over the block: every lane reaches the barriers)
         const uint64_t s = g + tid;
         const unsigned long long key = s < s1 ? keys[s] : EMPTY_KEY;
-        const bool solid = key != EMPTY_KEY && depth[s] >= min_count;
+        const bool solid = key != EMPTY_KEY && depth[s] >= min_count && !(drop && drop[s]);
         const uint64_t sm = __ballot(solid);
         if (lane == 0) wsolid[wave] = (uint32_t)__popcll(sm);
         __syncthreads();
@@ -205,18 +257,6 @@ __device__ __forceinline__ bool unitig_walk(const UnitigTable &t, uint64_t w, ui
     }
 }
 
-// the sum of v over the block's lanes (every lane reaches this; lds: 4 words; all lanes get the sum)
-__device__ __forceinline__ uint64_t block_sum64(uint64_t v, unsigned long long *lds) {
-    for (int off = 32; off; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_down((int)(uint32_t)v, off), hi = (uint32_t)__shfl_down((int)(uint32_t)(v >> 32), off);
-        v += (uint64_t)lo | ((uint64_t)hi << 32);
-    }
-    __syncthreads();  // (lds of an earlier call has been read)
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return lds[0] + lds[1] + lds[2] + lds[3];
-}
-
 // block b: slots [b * per, (b + 1) * per) as above, a tile of 256 at a time, one lane per slot.
 //   EMIT false  counts[b] = {the block's winners, their nodes}; the winning side of every slot goes into its mark byte (linear round:
 //               the byte written whole, MARK_COVERED cleared; circular round: MARK_WINC added to it)
@@ -247,7 +287,7 @@ __global__ __launch_bounds__(256) void k_unitig_walk(UnitigTable t, uint64_t nsl
         const uint64_t s = g + tid;
         const bool act = s < s1;
         const unsigned long long x = act ? t.keys[s] : EMPTY_KEY;
-        const bool solid = x != EMPTY_KEY && t.depth[s] >= t.min_count;
+        const bool solid = x != EMPTY_KEY && t.depth[s] >= t.min_count && !(t.drop && t.drop[s]);
         const uint32_t link = solid ? t.links[s] : 0u;
         const uint32_t mark = act && (EMIT || circ) ? marks8[s] : 0u;
         const uint64_t xr = rc_kmer(x, t.k, t.kmask);
@@ -333,34 +373,215 @@ __global__ __launch_bounds__(256) void k_unitig_walk(UnitigTable t, uint64_t nsl
     }
 }
 
+// ---- cleaning ----
+constexpr uint64_t NO_KEY = ~0ull;  // (no canonical key: a key is at most its reverse complement, and these two add up to all ones)
+
+// from the oriented k-mer w of slot `slot` (link: its byte) to the right along compactable edges, at most `limit` nodes: 1 with n and
+// the far end (its oriented k-mer, slot and link byte), 0 when the unitig holds more, -1 when the planes are broken.  met: a node
+// on the way is a1 or a2 (canonical keys, NO_KEY: none).  drop32 != NULL: every node's drop byte is set
+__device__ __forceinline__ int clean_walk(const UnitigTable &t, uint64_t w, uint32_t slot, uint32_t link, uint32_t limit, uint64_t a1, uint64_t a2,
+                                          uint32_t *drop32, uint32_t &n, uint64_t &wf, uint32_t &slotf, uint32_t &linkf, bool &met) {
+    n = 1;
+    met = false;
+    for (;;) {  // (no wave-collective in here)
+        const uint64_t c = min(w, rc_kmer(w, t.k, t.kmask));
+        if (c == a1 || c == a2) met = true;
+        if (drop32) atomicOr(&drop32[slot >> 2], 1u << (8 * (slot & 3u)));
+        uint64_t w2 = 0;
+        uint32_t slot2 = 0, link2 = 0;
+        const int r = unitig_step(t, w, link, w2, slot2, link2);
+        if (r == STEP_BROKEN) return -1;
+        if (r == STEP_NONE) {
+            wf = w;
+            slotf = slot;
+            linkf = link;
+            return 1;
+        }
+        if (n >= limit) return 0;
+        w = w2;
+        slot = slot2;
+        link = link2;
+        ++n;
+    }
+}
+
+// the right side of the oriented end e (link: the byte of canon(e)): 0 dead, 1 one successor v that is not its own reverse
+// complement (attached, if v lies outside the unitig), 2 open
+__device__ __forceinline__ uint32_t clean_side(const UnitigTable &t, uint64_t e, uint32_t link, uint64_t &v) {
+    const uint32_t out = out_of(link, e < rc_kmer(e, t.k, t.kmask));
+    if (!out) return 0;
+    if (__popc(out) != 1) return 2;
+    v = ((e << 2) | (uint32_t)__builtin_ctz(out)) & t.kmask;
+    return rc_kmer(v, t.k, t.kmask) == v ? 2u : 1u;
+}
+
+// the tip whose attached end node is e (slot slot_e), attached by v on e's right: 1 clipped, 0 stays, -1 broken planes
+__device__ __forceinline__ int clean_tip(const UnitigTable &t, uint64_t e, uint32_t slot_e, uint64_t v, uint32_t rm) {
+    const uint64_t rv = rc_kmer(v, t.k, t.kmask);
+    const uint32_t sv = key_find<uint32_t>(t.keys, t.smask, t.max_probe, min(v, rv), SLOT_ABSENT);
+    if (sv == SLOT_ABSENT) return -1;
+    const uint32_t in = in_of(t.links[sv], v < rv);
+    if (!((in >> (uint32_t)(e >> (2 * (t.k - 1)))) & 1u)) return -1;
+    uint32_t deepest = 0;
+    bool any = false;
+#pragma unroll 1
+    for (uint32_t b = 0; b < 4; ++b) {
+        if (!((in >> b) & 1u)) continue;
+        const uint64_t s = (v >> 2) | ((uint64_t)b << (2 * (t.k - 1)));
+        if (s == e) continue;
+        const uint32_t ss = key_find<uint32_t>(t.keys, t.smask, t.max_probe, min(s, rc_kmer(s, t.k, t.kmask)), SLOT_ABSENT);
+        if (ss == SLOT_ABSENT) return -1;
+        deepest = max(deepest, t.depth[ss]);
+        any = true;
+    }
+    return any && (uint64_t)t.depth[slot_e] * 1000ull <= (uint64_t)rm * deepest ? 1 : 0;
+}
+
+// the bubble w1 (first node, oriented) .. between p and q with e(U) = e_u: 1 popped, 0 stays, -1 broken planes
+__device__ __forceinline__ int clean_bubble(const UnitigTable &t, uint64_t w1, uint64_t p, uint64_t q, uint64_t e_u, uint32_t limit, uint32_t rm) {
+    const uint64_t rp = rc_kmer(p, t.k, t.kmask), cp = min(p, rp), cq = min(q, rc_kmer(q, t.k, t.kmask));
+    const uint32_t sp = key_find<uint32_t>(t.keys, t.smask, t.max_probe, cp, SLOT_ABSENT);
+    if (sp == SLOT_ABSENT) return -1;
+    const uint32_t out = out_of(t.links[sp], p < rp);
+    if (!((out >> ((uint32_t)w1 & 3u)) & 1u)) return -1;
+#pragma unroll 1
+    for (uint32_t b = 0; b < 4; ++b) {
+        if (!((out >> b) & 1u)) continue;
+        const uint64_t s = ((p << 2) | b) & t.kmask;
+        if (s == w1) continue;
+        const uint64_t rs = rc_kmer(s, t.k, t.kmask);
+        const uint32_t ss = key_find<uint32_t>(t.keys, t.smask, t.max_probe, min(s, rs), SLOT_ABSENT);
+        if (ss == SLOT_ABSENT) return -1;
+        const uint32_t ls = t.links[ss];
+        if (__popc(in_of(ls, s < rs)) != 1) continue;
+        uint32_t n2 = 0, slotf = 0, linkf = 0;
+        uint64_t wf = 0, v2 = 0;
+        bool met = false;
+        const int r = clean_walk(t, s, ss, ls, limit, cp, cq, nullptr, n2, wf, slotf, linkf, met);
+        if (r < 0) return -1;
+        if (r == 0 || met) continue;
+        if (clean_side(t, wf, linkf, v2) != 1 || v2 != q) continue;
+        const uint64_t e_o = min(t.depth[ss], t.depth[slotf]);
+        if (e_u * 1000ull <= (uint64_t)rm * e_o) return 1;
+    }
+    return 0;
+}
+
+// block b: slots [b * per, (b + 1) * per) as above, one lane per slot.  counts[4 b ..] = {tips, their nodes, bubbles, their nodes}
+__global__ __launch_bounds__(256) void k_unitig_clean(UnitigTable t, uint64_t nslots, uint32_t tip_kmers, uint32_t bubble_kmers, uint32_t rm,
+                                                      uint8_t *drop8, uint64_t *__restrict__ counts, uint32_t *flag) {
+    __shared__ unsigned long long sum_s[4];
+    const uint64_t per = novel_scan_per_block(nslots), s0 = (uint64_t)blockIdx.x * per, s1 = min(nslots, s0 + per);
+    uint32_t *drop32 = reinterpret_cast<uint32_t *>(drop8);
+    const uint32_t longest = max(tip_kmers, bubble_kmers);
+    uint64_t tips = 0, tip_nodes = 0, bubbles = 0, bubble_nodes = 0;
+    bool broken = false;
+    for (uint64_t s = s0 + threadIdx.x; s < s1; s += 256) {
+        const uint32_t link = t.links[s];
+        if (!link) continue;  // (no node, a dropped node, or a node dead on both sides: never dropped)
+        const unsigned long long x = t.keys[s];
+        const uint64_t xr = rc_kmer(x, t.k, t.kmask);
+#pragma unroll 1
+        for (uint32_t side = 0; side < 2; ++side) {
+            const uint64_t w = side ? xr : x, wl = side ? x : xr;  // (wl: the orientation that walks off w's left side)
+            uint64_t w2, vl = 0, vr = 0, wf = 0;
+            uint32_t slot2, link2, n = 0, slotf = 0, linkf = 0;
+            bool met = false;
+            const int left = unitig_step(t, wl, link, w2, slot2, link2);
+            if (left == STEP_BROKEN) broken = true;
+            if (left != STEP_NONE) continue;
+            uint32_t kl = clean_side(t, wl, link, vl);  // (vl: the reverse complement of p)
+            int r = clean_walk(t, w, (uint32_t)s, link, longest, kl == 1 ? min(vl, rc_kmer(vl, t.k, t.kmask)) : NO_KEY, NO_KEY, nullptr, n, wf, slotf,
+                               linkf, met);
+            if (r < 0) broken = true;
+            if (r <= 0) continue;
+            if (!(n == 1 ? side == 0 : x < min(wf, rc_kmer(wf, t.k, t.kmask)))) continue;  // (the other end decides)
+            if (kl == 1 && met) kl = 2;
+            uint32_t kr = clean_side(t, wf, linkf, vr);
+            if (kl == 2 || kr == 2 || kl + kr == 0) continue;
+            if (kr == 1) {  // q outside U, outright
+                uint32_t n1, sf1, lf1;
+                uint64_t wf1;
+                r = clean_walk(t, w, (uint32_t)s, link, n, min(vr, rc_kmer(vr, t.k, t.kmask)), NO_KEY, nullptr, n1, wf1, sf1, lf1, met);
+                if (r <= 0) broken = true;
+                if (r <= 0 || met) continue;
+            }
+            int hit = 0;
+            const bool tip = kl + kr == 1;
+            if (tip) {
+                if (n > tip_kmers) continue;
+                hit = kr == 1 ? clean_tip(t, wf, slotf, vr, rm) : clean_tip(t, wl, (uint32_t)s, vl, rm);
+            } else {
+                if (n > bubble_kmers) continue;
+                hit = clean_bubble(t, w, rc_kmer(vl, t.k, t.kmask), vr, min(t.depth[s], t.depth[slotf]), bubble_kmers, rm);
+            }
+            if (hit < 0) broken = true;
+            if (hit <= 0) continue;
+            uint32_t n1, sf1, lf1;
+            uint64_t wf1;
+            if (clean_walk(t, w, (uint32_t)s, link, n, NO_KEY, NO_KEY, drop32, n1, wf1, sf1, lf1, met) <= 0) broken = true;
+            if (tip) {
+                ++tips;
+                tip_nodes += n;
+            } else {
+                ++bubbles;
+                bubble_nodes += n;
+            }
+        }
+    }
+    if (broken) atomicOr(flag, 1u);
+    const uint64_t a = block_sum64(tips, sum_s), b = block_sum64(tip_nodes, sum_s), c = block_sum64(bubbles, sum_s),
+                   d = block_sum64(bubble_nodes, sum_s);
+    if (threadIdx.x == 0) {
+        counts[4 * (uint64_t)blockIdx.x] = a;
+        counts[4 * (uint64_t)blockIdx.x + 1] = b;
+        counts[4 * (uint64_t)blockIdx.x + 2] = c;
+        counts[4 * (uint64_t)blockIdx.x + 3] = d;
+    }
+}
+
 static bool unitig_ok(const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t min_count, int k) {
     return keys && depth && nslots >= 2 && !(nslots & (nslots - 1)) && nslots <= COPIES_MAX_SLOTS && min_count >= 1 && k >= 2 && k <= 32;
 }
 
 hipError_t launch_unitig_links(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t max_probe,
-                               uint32_t min_count, int k, uint8_t *links) {
+                               uint32_t min_count, int k, uint8_t *links, const uint8_t *drop, uint32_t *block_nodes) {
     if (!unitig_ok(keys, depth, nslots, min_count, k) || !links) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_unitig_links, dim3(novel_scan_blocks(nslots)), dim3(256), 0, st, keys, depth, nslots, max_probe, min_count, k, links);
+    hipLaunchKernelGGL(k_unitig_links, dim3(novel_scan_blocks(nslots)), dim3(256), 0, st, keys, depth, nslots, max_probe, min_count, k, links, drop,
+                       block_nodes);
     return hipGetLastError();
 }
 
 hipError_t launch_unitig_links_emit(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, const uint8_t *links, uint64_t nslots,
-                                    uint32_t min_count, const uint64_t *offs, uint64_t cap, unsigned long long *out_keys, uint8_t *out_links) {
+                                    uint32_t min_count, const uint64_t *offs, uint64_t cap, unsigned long long *out_keys, uint8_t *out_links,
+                                    const uint8_t *drop) {
     if (!unitig_ok(keys, depth, nslots, min_count, 2) || !links || !offs || !out_keys || !out_links) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_unitig_links_emit, dim3(novel_scan_blocks(nslots)), dim3(256), 0, st, keys, depth, links, nslots, min_count, offs, cap,
-                       out_keys, out_links);
+                       out_keys, out_links, drop);
+    return hipGetLastError();
+}
+
+hipError_t launch_unitig_clean(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t max_probe,
+                               uint32_t min_count, int k, const uint8_t *links, uint8_t *drop, uint32_t tip_kmers, uint32_t bubble_kmers,
+                               uint32_t ratio_milli, uint64_t *counts, uint32_t *flag) {
+    if (!unitig_ok(keys, depth, nslots, min_count, k) || !links || !drop || !counts || !flag || tip_kmers < 1 ||
+        tip_kmers > UNITIG_CLEAN_MAX_KMERS || bubble_kmers < 1 || bubble_kmers > UNITIG_CLEAN_MAX_KMERS || ratio_milli < 1 || ratio_milli > 999)
+        return hipErrorInvalidValue;
+    const UnitigTable t = {keys, depth, links, nslots - 1, k == 32 ? ~0ull : ((1ull << (2 * k)) - 1), max_probe, min_count, k, nullptr};
+    hipLaunchKernelGGL(k_unitig_clean, dim3(novel_scan_blocks(nslots)), dim3(256), 0, st, t, nslots, tip_kmers, bubble_kmers, ratio_milli, drop,
+                       counts, flag);
     return hipGetLastError();
 }
 
 hipError_t launch_unitig_walk(hipStream_t st, const unsigned long long *keys, const uint32_t *depth, uint64_t nslots, uint32_t max_probe,
                               uint32_t min_count, int k, const uint8_t *links, uint8_t *marks, bool circular, uint64_t bound, ulonglong2 *counts,
                               const ulonglong2 *offs, uint64_t cap_unitigs, uint64_t cap_bases, uint64_t *offsets, uint32_t *kmers,
-                              uint64_t *depth_sum, uint8_t *circ_out, uint8_t *bases, uint32_t *flag) {
+                              uint64_t *depth_sum, uint8_t *circ_out, uint8_t *bases, uint32_t *flag, const uint8_t *drop) {
     const bool emit = offs != nullptr;
     if (!unitig_ok(keys, depth, nslots, min_count, k) || !links || !marks || !flag || bound < 1 || (emit ? false : !counts))
         return hipErrorInvalidValue;
     if (emit && ((cap_unitigs && (!offsets || !kmers || !depth_sum || !circ_out)) || (cap_bases && !bases))) return hipErrorInvalidValue;
-    const UnitigTable t = {keys, depth, links, nslots - 1, k == 32 ? ~0ull : ((1ull << (2 * k)) - 1), max_probe, min_count, k};
+    const UnitigTable t = {keys, depth, links, nslots - 1, k == 32 ? ~0ull : ((1ull << (2 * k)) - 1), max_probe, min_count, k, drop};
     const uint32_t blocks = novel_scan_blocks(nslots);
     if (emit)
         hipLaunchKernelGGL(k_unitig_walk<true>, dim3(blocks), dim3(256), 0, st, t, nslots, circular ? 1u : 0u, bound, marks, counts, offs,

@@ -1238,6 +1238,23 @@ class NovelTable:
         call(0, 0)
         return call(int(nu.value), int(nb.value))
 
+    def clean(self, min_count: int = 1, tip_kmers: Optional[int] = None, bubble_kmers: Optional[int] = None, ratio: float = 0.25,
+              rounds: int = 4) -> dict:
+        """error tips clipped and bubbles popped on the graph of the solid k-mers (pg_unitigs.hip: k_unitig_clean; the rule stands in
+        that file's header): a dead-end branch of at most ``tip_kmers`` k-mers is dropped when a sibling at its fork is deeper by
+        1 / ``ratio`` or more, the weaker of two parallel branches of at most ``bubble_kmers`` k-mers likewise (both default to
+        2 k); ``rounds`` rounds at the most, each on what the round before left.  ``links`` and ``unitigs`` at the same
+        ``min_count`` answer for the cleaned graph from then on; ``rounds=0``, another ``min_count``, an ``add`` or a ``clear``
+        bring the raw graph back.  Returns ``clipped_tips``, ``clipped_kmers``, ``popped_bubbles``, ``popped_kmers`` and
+        ``clean_rounds`` (the rounds that dropped something)."""
+        if not 1 <= int(min_count) <= 0xFFFFFFFF:
+            raise ValueError(f"min_count {min_count} (1 to 2^32 - 1)")
+        k = int(self.table.k)
+        st = (C.c_uint64 * 5)()
+        check(self._lib.pg_novel_clean(self._h, int(min_count), clean_kmers(tip_kmers, k, "tip_kmers"), clean_kmers(bubble_kmers, k, "bubble_kmers"),
+                                       clean_ratio_milli(ratio), clean_rounds(rounds), st))
+        return dict(zip(CLEAN_STAT_NAMES, (int(x) for x in st)))
+
     def stats(self) -> dict:
         """``nkeys`` (the novel k-mers held), ``nslots``, ``grown`` (the times the table has grown)"""
         v = [C.c_uint64() for _ in range(3)]
@@ -1287,6 +1304,39 @@ def novel_last_timing() -> dict:
     ms = (C.c_float * 4)()
     check(_lib.load().pg_novel_last_timing(ms))
     return dict(zip(("count_ms", "grow_ms", "scan_ms", "runs_ms"), (float(x) for x in ms)))
+
+
+CLEAN_STAT_NAMES = ("clipped_tips", "clipped_kmers", "popped_bubbles", "popped_kmers", "clean_rounds")
+CLEAN_MAX_KMERS, CLEAN_MAX_ROUNDS = 1024, 64
+
+
+def clean_kmers(n: Optional[int], k: int, name: str) -> int:
+    """``tip_kmers`` / ``bubble_kmers`` of ``NovelTable.clean`` checked: None is 2 k"""
+    n = 2 * int(k) if n is None else int(n)
+    if not 1 <= n <= CLEAN_MAX_KMERS:
+        raise ValueError(f"{name} {n} (1 to {CLEAN_MAX_KMERS})")
+    return n
+
+
+def clean_ratio_milli(ratio: float) -> int:
+    """the ratio of ``NovelTable.clean`` in per mille, rounded; ValueError unless 0 < ratio < 1 and the per mille lie in 1 to 999"""
+    r = float(ratio)
+    if not 0.0 < r < 1.0 or not 1 <= int(round(r * 1000)) <= 999:
+        raise ValueError(f"ratio {ratio} (above 0 and below 1, in steps of 0.001)")
+    return int(round(r * 1000))
+
+
+def clean_rounds(rounds: int) -> int:
+    if not 0 <= int(rounds) <= CLEAN_MAX_ROUNDS:
+        raise ValueError(f"rounds {rounds} (0 to {CLEAN_MAX_ROUNDS})")
+    return int(rounds)
+
+
+def novel_clean_last_timing() -> dict:
+    """HIP-event milliseconds of the k_unitig_links passes and the k_unitig_clean passes of this thread's last ``NovelTable.clean``"""
+    ms = (C.c_float * 2)()
+    check(_lib.load().pg_novel_clean_last_timing(ms))
+    return dict(zip(("links_ms", "clean_ms"), (float(x) for x in ms)))
 
 
 def novel_unitigs_last_timing() -> dict:

@@ -1590,7 +1590,7 @@ class Index:
         return scr.frames(counts, names, int(self.k), min_count, tot["windows"], tot["hits"], tot["reads"], tot["read_bases"], genomes)
 
     def novel(self, samples, min_count: Optional[int] = None, batch_bytes: Optional[int] = None, kmers: bool = False,
-              regions: bool = False, min_bases: int = 0, unitigs: bool = False, min_unitig_bases: int = 0):
+              regions: bool = False, min_bases: int = 0, unitigs: bool = False, min_unitig_bases: int = 0, clean: Optional[dict] = None):
         """(stats, spectrum, kmers, regions) — ``novel.stats``, ``novel.spectrum_frame``, ``novel.kmers_frame`` (None unless
         ``kmers``), ``novel.regions_frame`` filtered by ``min_bases`` (None unless ``regions``) — of ONE sample from outside the
         index: the distinct k-mers it holds that NO indexed genome does, their depth spectrum, and for an assembly where they
@@ -1600,6 +1600,9 @@ class Index:
         filter.  With ``unitigs`` a fifth value follows: ``novel.unitigs_frame`` — the solid k-mers compacted on the GPU into the
         non-branching paths of their de Bruijn graph (``engine.NovelTable.unitigs``: an insertion is one unitig, a plasmid a
         circular one), those of at least ``min_unitig_bases`` bases — from the same novel table, the sample still streamed once.
+        ``clean`` (needs ``unitigs``; a dict of ``tip_kmers``, ``bubble_kmers``, ``ratio``, ``rounds``, each optional): error tips
+        are clipped and bubbles popped on the GPU before the compaction (``engine.NovelTable.clean``), and a sixth value follows:
+        its statistics, ``novel.CLEAN_STAT_NAMES``.
         ValueError: a missing file, a torn last record, ``min_count`` outside 1..2^32 - 1, a negative ``min_bases`` or
         ``min_unitig_bases``, ``regions`` with a FASTQ file (regions need an assembly); RuntimeError: the cached table holds some
         anchors' k-mers only."""
@@ -1615,6 +1618,13 @@ class Index:
             raise ValueError(f"novel: min_bases={min_bases} must not be negative")
         if int(min_unitig_bases) < 0:
             raise ValueError(f"novel: min_unitig_bases={min_unitig_bases} must not be negative")
+        if clean is not None:
+            if not unitigs:
+                raise ValueError("novel: clean needs unitigs")
+            try:
+                clean = nov.clean_options(int(self.k), **clean)
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"novel: clean: {e}") from None
         min_count = nov.check_min_count(nov.default_min_count(any(is_fastq(p) for p in paths)) if min_count is None else min_count)
         batch_bytes = pl.DEFAULT_BATCH_BYTES if batch_bytes is None else int(batch_bytes)
         if batch_bytes < 1:
@@ -1651,12 +1661,16 @@ class Index:
             counts = nt.result(min_count)
             kmers_df = nov.kmers_frame(*nt.keys(min_count), k) if kmers else None
             if unitigs:
+                if clean is not None:
+                    clean_stats = nt.clean(min_count, **clean)
                 u = nt.unitigs(min_count)
                 unitigs_df = nov.unitigs_frame(u["offsets"], u["kmers"], u["depth_sum"], u["circular"], u["bases"], k, min_unitig_bases)
         finally:
             nt.close()
         regions_df = nov.filter_regions(pd.concat(found, ignore_index=True) if found else nov.no_regions(), min_bases) if regions else None
         st = nov.stats(counts, min_count, tot["windows"], tot["hits"], tot["reads"], tot["read_bases"], regions_df)
+        if unitigs and clean is not None:
+            return st, nov.spectrum_frame(counts["depth_hist"]), kmers_df, regions_df, unitigs_df, clean_stats
         if unitigs:
             return st, nov.spectrum_frame(counts["depth_hist"]), kmers_df, regions_df, unitigs_df
         return st, nov.spectrum_frame(counts["depth_hist"]), kmers_df, regions_df

@@ -197,3 +197,21 @@ def unitig_stats(frame: pd.DataFrame) -> dict:
 
 def unitig_stat_lines(st: dict) -> List[str]:
     return [f"{n}\t{int(st[n])}" for n in UNITIG_STAT_NAMES]
+
+
+# cleaning the graph before it is compacted (``engine.NovelTable.clean``): what `novel --unitigs --clean` prints behind the unitig statistics
+CLEAN_STAT_NAMES = ["clipped_tips", "clipped_kmers", "popped_bubbles", "popped_kmers", "clean_rounds"]
+
+
+def clean_options(k: int, tip_kmers=None, bubble_kmers=None, ratio=None, rounds=None) -> dict:
+    """the arguments of ``engine.NovelTable.clean`` checked, the defaults filled in (2 k, 2 k, 0.25, 4): ValueError for a k-mer limit
+    outside 1 to 1024, a ratio outside (0, 1) or rounds outside 0 to 64"""
+    from . import engine
+    ratio = 0.25 if ratio is None else float(ratio)
+    engine.clean_ratio_milli(ratio)
+    return {"tip_kmers": engine.clean_kmers(tip_kmers, k, "tip_kmers"), "bubble_kmers": engine.clean_kmers(bubble_kmers, k, "bubble_kmers"),
+            "ratio": ratio, "rounds": engine.clean_rounds(4 if rounds is None else rounds)}
+
+
+def clean_stat_lines(st: dict) -> List[str]:
+    return [f"{n}\t{int(st[n])}" for n in CLEAN_STAT_NAMES]

@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, "libpanagram_hip.so")
 OBJ = os.path.join(HERE, "build")
 SOURCES = ["pg_kernels.hip", "pg_anchor.hip", "pg_rows.hip", "pg_deflate.hip", "pg_inflate.hip", "pg_minhash.hip", "pg_bins.hip", "pg_pairs.hip", "pg_find.hip", "pg_patterns.hip", "pg_gaps.hip", "pg_profile.hip", "pg_knn.hip", "pg_tablestats.hip", "pg_synteny.hip", "pg_blocks.hip", "pg_variants.hip", "pg_copies.hip", "pg_locate.hip", "pg_fastq.hip", "pg_place.hip", "pg_screen.hip", "pg_novel.hip", "pg_unitigs.hip", "pg_api.hip", "pg_api_kmc.hip", "pg_api_sketch.hip",
            "pg_api_seqset.hip", "pg_api_bgzf.hip", "pg_api_query.hip", "pg_api_patterns.hip", "pg_api_gaps.hip", "pg_api_profile.hip", "pg_api_tablestats.hip", "pg_api_synteny.hip", "pg_api_copies.hip", "pg_api_fastq.hip", "pg_api_screen.hip", "pg_api_novel.hip", "pg_bgzf.cpp"]
-HEADERS = ["pg_device.h", "pg_kernels.h", "pg_planes.h", "pg_rowread.h", "pg_pairblocks.h", "pg_tablescan.h", "pg_guard.h", "pg_host.h", "pg_gaps_host.h", "pg_select_host.h", "pg_profile_host.h", "pg_blocks_link.h", "pg_blocks_host.h", "pg_blocks_pred.h", "pg_copies_host.h", "pg_keytable_dev.h", "pg_keytable_host.h", "pg_postable_dev.h", os.path.join("..", "..", "include", "panagram_hip.h")]
+HEADERS = ["pg_device.h", "pg_kernels.h", "pg_planes.h", "pg_rowread.h", "pg_pairblocks.h", "pg_tablescan.h", "pg_guard.h", "pg_host.h", "pg_gaps_host.h", "pg_select_host.h", "pg_profile_host.h", "pg_blocks_link.h", "pg_blocks_host.h", "pg_blocks_pred.h", "pg_copies_host.h", "pg_keytable_dev.h", "pg_keytable_host.h", "pg_postable_dev.h", "pg_runscan.h", "pg_runs_host.h", os.path.join("..", "..", "include", "panagram_hip.h")]
 # (source, extra defines, object name): the units of one build
 UNITS = [("pg_anchor.hip", ["PG_ANCHOR_PART=2"], "pg_anchor_p2.o"), ("pg_anchor.hip", ["PG_ANCHOR_PART=1"], "pg_anchor_p1.o"),
          ("pg_anchor.hip", ["PG_ANCHOR_PART=0"], "pg_anchor_p0.o"), ("pg_rows.hip", [], "pg_rows.o"), ("pg_api.hip", [], "pg_api.o"),

@@ -4,6 +4,7 @@
 #include "pg_host.h"
 
 #include "pg_keytable_host.h"
+#include "pg_runs_host.h"  // RunsOut, runs_two_pass
 
 static constexpr uint64_t NOVEL_MAX_KEYS = COPIES_MAX_SLOTS / 2;  // (table_slots: the power of two at or above 2 * keys)
 static constexpr uint64_t NOVEL_MAX_WINDOWS = 0xFFFFFFFFull;      // of one handle: a depth is 32 bits
@@ -327,77 +328,28 @@ int novel_runs(pg_table *t, const pg_seqset *sq, uint64_t cap, uint32_t *run_con
     const uint32_t nchunks = (uint32_t)w.jobs.size();
     hipStream_t st = t->ctx->stream;
     DevBuf<uint2> d_chunks;
-    DevBuf<uint4> d_counts;
-    std::vector<uint4> counts(nchunks);
-    float ms_count = 0, ms_emit = 0;
-    LaunchTimer tc(&ms_count), te(&ms_emit);
-    hipError_t e = d_chunks.upload(w.jobs, st);
-    if (e == hipSuccess) e = d_counts.alloc(nchunks);
-    if (e == hipSuccess) e = tc.start(st);
-    if (e == hipSuccess)
-        e = launch_novel_runs(st, *pan, sq->d_desc, d_chunks.get(), nchunks, sq->d_seqw, sq->d_nmw, sq->d_has_n, d_counts.get(), nullptr, 0, nullptr,
-                              nullptr, nullptr, nullptr);
-    if (e == hipSuccess) e = tc.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    const hipError_t e = d_chunks.upload(w.jobs, st);
     if (e != hipSuccess) {
-        hipStreamSynchronize(st);  // (the upload's source and the copy's target go with this scope)
+        hipStreamSynchronize(st);  // (the upload's source goes with this scope)
         return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     }
-    tc.read();
-    g_novel_ms[3] = ms_count;
-    // per chunk: the starts and the ends of all chunks before it; per contig: its runs
-    std::vector<ulonglong2> offs(nchunks);
+    const auto launch = [&](uint4 *counts, const ulonglong2 *offs, uint64_t n, uint32_t *words, uint8_t *bytes) {
+        return launch_novel_runs(st, *pan, sq->d_desc, d_chunks.get(), nchunks, sq->d_seqw, sq->d_nmw, sq->d_has_n, counts, offs, n, words,
+                                 words + n, bytes, bytes + n);
+    };
+    RunsOut out;  // the first min(runs, cap) runs in (contig, start) order: start, end and the two held flags
+    out.nwords = out.nbytes = 2;
+    out.cap = cap, out.prefix = true, out.contig = run_contig;
+    out.words[0] = run_start, out.words[1] = run_end;
+    out.bytes[0] = left_held, out.bytes[1] = right_held;
     std::vector<uint64_t> per(sq->n, 0);
-    uint64_t nstarts = 0, nends = 0, nvalid = 0, nnovel = 0;
-    for (uint32_t c = 0; c < sq->n; ++c) {
-        const uint64_t s0 = nstarts;
-        for (uint64_t i = w.first[c]; i < w.first[c + 1]; ++i) {
-            offs[i] = make_ulonglong2(nstarts, nends);
-            nstarts += counts[i].x;
-            nends += counts[i].y;
-            nvalid += counts[i].z;
-            nnovel += counts[i].w;
-        }
-        per[c] = nstarts - s0;
-        if (nstarts != nends)  // (every run of a contig starts and ends inside it)
-            return fail(PG_E_HIP, "%s: contig %u: %llu run starts, %llu run ends", fn, c, (unsigned long long)nstarts, (unsigned long long)nends);
-    }
-    *nruns = nstarts;
-    *windows = nvalid;
-    *novel_windows = nnovel;
-    const uint64_t take = std::min<uint64_t>(nstarts, cap);  // (the first `take` runs in (contig, start) order)
-    if (take == 0) return PG_OK;
-    DevBuf<ulonglong2> d_offs;
-    DevBuf<uint32_t> d_se;  // starts, then ends
-    DevBuf<uint8_t> d_lr;   // left_held, then right_held
-    e = d_offs.upload(offs, st);
-    if (e == hipSuccess) e = d_se.alloc(2 * take);
-    if (e == hipSuccess) e = d_lr.alloc(2 * take);
-    if (e == hipErrorOutOfMemory) {
-        hipStreamSynchronize(st);
-        return fail(PG_E_CAPACITY, "%s: no memory for %llu runs", fn, (unsigned long long)take);
-    }
-    if (e == hipSuccess) e = te.start(st);
-    if (e == hipSuccess)
-        e = launch_novel_runs(st, *pan, sq->d_desc, d_chunks.get(), nchunks, sq->d_seqw, sq->d_nmw, sq->d_has_n, nullptr, d_offs.get(), take,
-                              d_se.get(), d_se.get() + take, d_lr.get(), d_lr.get() + take);
-    if (e == hipSuccess) e = te.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(run_start, d_se.get(), take * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(run_end, d_se.get() + take, take * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(left_held, d_lr.get(), take, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(right_held, d_lr.get() + take, take, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        hipStreamSynchronize(st);
-        return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    }
-    te.read();
-    g_novel_ms[3] = ms_count + ms_emit;
-    uint64_t at = 0;
-    for (uint32_t c = 0; c < sq->n && at < take; ++c)
-        for (uint64_t i = 0; i < per[c] && at < take; ++i) run_contig[at++] = c;
-    return PG_OK;
+    uint64_t sums[2] = {0, 0};  // the valid windows, the novel ones
+    float ms[2] = {0, 0};
+    const int r = runs_two_pass(t->ctx, fn, "contig", sq->n, w.first.data(), nchunks, launch, out, per.data(), nullptr, nruns, sums, ms);
+    g_novel_ms[3] = ms[0] + ms[1];
+    *windows = sums[0];
+    *novel_windows = sums[1];
+    return r;
 }
 
 // the link plane of `min_count` behind a pass of the scan: h = its NOVEL_SCAN_WORDS words (h[1]: the solid keys), block_solid the

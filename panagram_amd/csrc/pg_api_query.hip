@@ -1,6 +1,8 @@
 // pg_api_query.hip — host side of the C-ABI: window queries over a result's finished rows, k-NN of rows.
 #include "pg_host.h"
 
+#include "pg_runs_host.h"  // RunsOut, runs_two_pass
+
 // What the window queries (here and in pg_api_patterns.hip) share, beside check_step (pg_api.hip): one wording of every refusal,
 // whoever asks.  A call opens with check_window_call, makes its own checks, and goes on with gather_windows.
 // the step, the stride and the number n of windows ("bins", "windows") of entry point fn
@@ -225,49 +227,23 @@ extern "C" int pg_result_find_runs(pg_result *r, int step, uint32_t stride, uint
     const uint8_t *rows = step == 1 ? r->d_out1 : r->d_out100;
     DevBuf<uint32_t> d_mw;
     DevBuf<uint2> d_chunks;
-    DevBuf<uint4> d_counts;
-    std::vector<uint4> counts(nchunks);
     hipError_t e = w.upload(st);
     if (e == hipSuccess) e = d_mw.upload(mw, st);
     if (e == hipSuccess) e = d_chunks.upload(chunks, st);
-    if (e == hipSuccess) e = d_counts.alloc(nchunks);
-    if (e == hipSuccess)
-        e = launch_find_runs(st, N, rows, stride, w.base(), w.starts(), w.ends(), d_chunks.get(), nchunks, d_mw.get(),
-                             d_mw.get() + ndw, min_have, max_lack, d_counts.get(), nullptr, 0, nullptr, nullptr);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_find_runs: %s", hipGetErrorString(e));
-    // per window: the sums; per chunk: the starts and the ends of all chunks before it
-    std::vector<ulonglong2> offs(nchunks);
-    uint64_t nstarts = 0, nends = 0;
-    for (uint32_t i = 0; i < nwin; ++i) {
-        const uint64_t s0 = nstarts;
-        for (uint64_t c = first[i]; c < first[i + 1]; ++c) {
-            offs[c] = make_ulonglong2(nstarts, nends);
-            matched_out[i] += counts[c].x;
-            nstarts += counts[c].y;
-            nends += counts[c].z;
-        }
-        nruns_out[i] = nstarts - s0;
-        if (nstarts != nends)  // (every run of a window starts and ends inside it)
-            return fail(PG_E_HIP, "pg_result_find_runs: window %u: %llu run starts, %llu run ends", i, (unsigned long long)nstarts,
-                        (unsigned long long)nends);
+    if (e != hipSuccess) {
+        hipStreamSynchronize(st);  // (the uploads' sources go with this scope)
+        return fail(PG_E_HIP, "pg_result_find_runs: %s", hipGetErrorString(e));
     }
-    const uint64_t total = nstarts;
-    *total_out = total;
-    if (total == 0 || cap == 0 || total > cap) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
-    DevBuf<ulonglong2> d_offs;
-    DevBuf<uint32_t> d_runs;
-    e = d_offs.upload(offs, st);
-    if (e == hipSuccess) e = d_runs.alloc((size_t)2 * total);
-    if (e == hipSuccess)
-        e = launch_find_runs(st, N, rows, stride, w.base(), w.starts(), w.ends(), d_chunks.get(), nchunks, d_mw.get(),
-                             d_mw.get() + ndw, min_have, max_lack, nullptr, d_offs.get(), total, d_runs.get(), d_runs.get() + total);
-    if (e == hipSuccess) e = hipMemcpyAsync(run_start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(run_end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(PG_E_HIP, "pg_result_find_runs: %s", hipGetErrorString(e));
-    return PG_OK;
+    const auto launch = [&](uint4 *counts, const ulonglong2 *offs, uint64_t n, uint32_t *words, uint8_t *) {
+        return launch_find_runs(st, N, rows, stride, w.base(), w.starts(), w.ends(), d_chunks.get(), nchunks, d_mw.get(), d_mw.get() + ndw,
+                                min_have, max_lack, counts, offs, n, words, words + n);
+    };
+    RunsOut out;  // all runs or none: start and end (a run's window is told by nruns_out)
+    out.nwords = 2, out.cap = cap;
+    out.words[0] = run_start, out.words[1] = run_end;
+    uint64_t sums[2];
+    return runs_two_pass(r->ctx, "pg_result_find_runs", "window", nwin, first.data(), nchunks, launch, out, nruns_out, matched_out, total_out,
+                         sums, nullptr);
     PG_API_END
 }
 

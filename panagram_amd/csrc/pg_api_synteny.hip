@@ -5,6 +5,7 @@
 
 #include "pg_blocks_host.h"
 #include "pg_keytable_host.h"
+#include "pg_runs_host.h"  // RunsOut, runs_two_pass
 
 static constexpr uint64_t POS_MAX_BASES = 0x7FFFFFFFull;  // a side's bases: the word pos << 1 | rc stays below POS_MULTI
 static constexpr uint64_t POS_MAX_KEYS = 1ull << 32;      // two sides of 2^31 k-mers
@@ -145,76 +146,6 @@ int postable_mates(pg_postable *pt, const pg_seqset *sq, uint32_t *mates_out, ui
     return PG_OK;
 }
 
-// where the runs of mate_runs_dev go: the caller's four host arrays of `cap` entries under the capacity protocol, or — keep set —
-// all of them into *keep, three planes of the total's words (start, end, mate), which stay in HBM with nothing downloaded
-struct RunsOut {
-    uint64_t cap = 0;
-    uint32_t *contig = nullptr, *start = nullptr, *end = nullptr, *mate = nullptr;
-    DevBuf<uint32_t> *keep = nullptr;
-};
-
-// the two passes of a run kernel over its chunks (k_mate_runs, k_hit_runs): count, the host's exclusive scans of the chunks' run starts
-// and run ends, emit.  launch(counts, offs, total, run_start, run_end, run_word) enqueues one pass — offs NULL: the count pass —
-// over nchunks chunks, the chunks of contig c being first[c] .. first[c + 1].  nruns[c], marked[c] (the contig's marked positions,
-// when given), *total_out and *nmarked always; the runs under `out`; ms[0] the count launch, ms[1] the emit launch
-template <class Launch>
-int runs_two_pass(pg_ctx *ctx, const char *fn, uint32_t ncontigs, const std::vector<uint64_t> &first, uint32_t nchunks, Launch launch,
-                  const RunsOut &out, uint64_t *nruns, uint64_t *marked, uint64_t *total_out, uint64_t *nmarked, float *ms) {
-    hipStream_t st = ctx->stream;
-    DevBuf<uint4> d_counts;
-    std::vector<uint4> counts(nchunks);
-    LaunchTimer tc(ms), te(ms ? ms + 1 : nullptr);
-    hipError_t e = d_counts.alloc(nchunks);
-    if (e == hipSuccess) e = tc.start(st);
-    if (e == hipSuccess) e = launch(d_counts.get(), nullptr, 0, nullptr, nullptr, nullptr);
-    if (e == hipSuccess) e = tc.stop(st);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts.data(), d_counts.get(), (size_t)nchunks * sizeof(uint4), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    tc.read();
-    // per contig: the sums; per chunk: the starts and the ends of all chunks before it
-    std::vector<ulonglong2> offs(nchunks);
-    uint64_t nstarts = 0, nends = 0, nm = 0;
-    for (uint32_t c = 0; c < ncontigs; ++c) {
-        const uint64_t s0 = nstarts, m0 = nm;
-        for (uint64_t i = first[c]; i < first[c + 1]; ++i) {
-            offs[i] = make_ulonglong2(nstarts, nends);
-            nm += counts[i].x;
-            nstarts += counts[i].y;
-            nends += counts[i].z;
-        }
-        nruns[c] = nstarts - s0;
-        if (marked) marked[c] = nm - m0;
-        if (nstarts != nends)  // (every run of a contig starts and ends inside it)
-            return fail(PG_E_HIP, "%s: contig %u: %llu run starts, %llu run ends", fn, c, (unsigned long long)nstarts, (unsigned long long)nends);
-    }
-    const uint64_t total = nstarts;
-    *total_out = total;
-    if (nmarked) *nmarked = nm;
-    if (total == 0 || (!out.keep && (out.cap == 0 || total > out.cap))) return PG_OK;  // (nothing to emit / the caller's arrays are too short)
-    DevBuf<ulonglong2> d_offs;
-    DevBuf<uint32_t> d_runs;
-    e = d_offs.upload(offs, st);
-    if (e == hipSuccess) e = d_runs.alloc((size_t)3 * total);
-    if (e == hipSuccess) e = te.start(st);
-    if (e == hipSuccess) e = launch(nullptr, d_offs.get(), total, d_runs.get(), d_runs.get() + total, d_runs.get() + 2 * total);
-    if (e == hipSuccess) e = te.stop(st);
-    if (e == hipSuccess && !out.keep) e = hipMemcpyAsync(out.start, d_runs.get(), (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && !out.keep) e = hipMemcpyAsync(out.end, d_runs.get() + total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && !out.keep) e = hipMemcpyAsync(out.mate, d_runs.get() + 2 * total, (size_t)total * 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
-    te.read();
-    if (out.keep) {
-        std::swap(out.keep->p, d_runs.p);
-        return PG_OK;
-    }
-    uint64_t at = 0;
-    for (uint32_t c = 0; c < ncontigs; ++c)
-        for (uint64_t i = 0; i < nruns[c]; ++i) out.contig[at++] = c;
-    return PG_OK;
-}
-
 // the runs of a mates array in HBM (ncontigs contigs of nkmers[c] entries, back to back); nruns[c] and *total_out always,
 // *mated: the mated positions counted
 int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t ncontigs, const uint64_t *nkmers, const RunsOut &out,
@@ -245,10 +176,21 @@ int mate_runs_dev(pg_ctx *ctx, const char *fn, const uint32_t *d_mates, uint32_t
         hipStreamSynchronize(st);  // (the uploads' sources go with this scope)
         return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     }
-    const auto launch = [&](uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *rs, uint32_t *re, uint32_t *rm) {
-        return launch_mate_runs(st, d_mates, d_contigs.get(), d_chunks.get(), nchunks, counts, offs, total, rs, re, rm);
+    const auto launch = [&](uint4 *counts, const ulonglong2 *offs, uint64_t n, uint32_t *words, uint8_t *) {
+        return launch_mate_runs(st, d_mates, d_contigs.get(), d_chunks.get(), nchunks, counts, offs, n, words, words + n, words + 2 * n);
     };
-    return runs_two_pass(ctx, fn, ncontigs, first, nchunks, launch, out, nruns, nullptr, total_out, mated, ms);
+    uint64_t sums[2] = {0, 0};  // the mated positions, nothing
+    const int r = runs_two_pass(ctx, fn, "contig", ncontigs, first.data(), nchunks, launch, out, nruns, nullptr, total_out, sums, ms);
+    if (mated) *mated = sums[0];
+    return r;
+}
+
+// the caller's four host arrays of `cap` entries, under the all-or-nothing capacity protocol
+RunsOut host_runs(uint64_t cap, uint32_t *run_contig, uint32_t *run_start, uint32_t *run_end, uint32_t *run_word) {
+    RunsOut out;
+    out.cap = cap, out.contig = run_contig;
+    out.words[0] = run_start, out.words[1] = run_end, out.words[2] = run_word;
+    return out;
 }
 
 bool runs_args_ok(uint32_t ncontigs, uint64_t cap, const uint32_t *run_contig, const uint32_t *run_start, const uint32_t *run_end,
@@ -550,11 +492,14 @@ int hit_runs_dev(pg_postable *pt, const char *fn, const pg_seqset *sq, const Kme
         hipStreamSynchronize(st);  // (the upload's source is the caller's)
         return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     }
-    const auto launch = [&](uint4 *counts, const ulonglong2 *offs, uint64_t total, uint32_t *rs, uint32_t *re, uint32_t *rh) {
+    const auto launch = [&](uint4 *counts, const ulonglong2 *offs, uint64_t n, uint32_t *words, uint8_t *) {
         return launch_hit_runs(st, pt->k, sq->d_desc, d_chunks.get(), nchunks, sq->d_seqw, sq->d_nmw, sq->d_has_n, pt->d_slots, pt->nslots,
-                               pt->max_probe, counts, offs, total, rs, re, rh);
+                               pt->max_probe, counts, offs, n, words, words + n, words + 2 * n);
     };
-    return runs_two_pass(pt->ctx, fn, sq->n, w.first, nchunks, launch, out, nruns, hits, total_out, nhits, ms);
+    uint64_t sums[2] = {0, 0};  // the hits, nothing
+    const int r = runs_two_pass(pt->ctx, fn, "contig", sq->n, w.first.data(), nchunks, launch, out, nruns, hits, total_out, sums, ms);
+    *nhits = sums[0];
+    return r;
 }
 
 }  // namespace
@@ -610,7 +555,7 @@ extern "C" int pg_mate_runs(pg_ctx *ctx, const uint32_t *mates, uint32_t ncontig
         if (e == hipSuccess) e = hipMemcpyAsync(d_mates.get(), mates, n * 4, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return fail(PG_E_HIP, "pg_mate_runs: %s", hipGetErrorString(e));
     }
-    const RunsOut out{cap, run_contig, run_start, run_end, run_mate, nullptr};
+    const RunsOut out = host_runs(cap, run_contig, run_start, run_end, run_mate);
     const int r = mate_runs_dev(ctx, "pg_mate_runs", d_mates.get(), ncontigs, nkmers, out, nruns_per_contig, total, nullptr);
     if (n) hipStreamSynchronize(ctx->stream);  // (the upload's source is the caller's; the buffer goes with the scope)
     return r;
@@ -640,7 +585,7 @@ extern "C" int pg_synteny_segments(pg_ctx *ctx, int k, const pg_seqset *seqsA, c
     float *ms = g_last_ms;
     if (int r = mated_table(ctx, k, seqsA, seqsB, a.nkmers + b.nkmers, pt, nmated, ms)) return r;
     uint64_t mated = 0;
-    const RunsOut out{cap, run_contig, run_start, run_end, run_mate, nullptr};
+    const RunsOut out = host_runs(cap, run_contig, run_start, run_end, run_mate);
     if (int r = mate_runs_dev(ctx, "pg_synteny_segments", pt.p->d_mates, seqsA->n, nk.data(), out, nruns_per_contig, total, &mated, ms + 3))
         return r;
     if (mated != *nmated)  // (two kernels counted the same array)
@@ -861,7 +806,7 @@ extern "C" int pg_postable_hit_runs(pg_postable *pt, const pg_seqset *seqsG, uin
     KmerWalk w;
     if (int r = hit_walk(pt, seqsG, "pg_postable_hit_runs", w)) return r;
     std::fill(g_locate_ms, g_locate_ms + 4, 0.0f);
-    const RunsOut out{cap, run_contig, run_start, run_end, run_hit, nullptr};
+    const RunsOut out = host_runs(cap, run_contig, run_start, run_end, run_hit);
     return hit_runs_dev(pt, "pg_postable_hit_runs", seqsG, w, out, nruns_per_contig, hits_per_contig, total, nhits, g_locate_ms);
     PG_API_END
 }

@@ -21,26 +21,23 @@
 //                   newly claimed are counted: a ballot per wave, one atomic per block (ctr[1]).
 //   k_copy_count    the same walk over a whole genome, the table read-only: a valid window looks its key up (no target's key:
 //                   nothing to do) and adds 1 to the plane's counter of its slot.  Integer atomic adds:
-//                   the result is exact whatever order and contention.  Equal slots are folded inside a wave first, in up to
-//                   COPY_FOLD_TURNS turns: the first lane with a hit takes every lane that has its slot — a homopolymer puts all 64
-//                   on one, a satellite of period p on at most p — and adds their number in ONE atomic; a turn that finds its lane
-//                   alone ends the folding, and the lanes left add 1 each.  A wave without a hit skips all of it.  Measured
-//                   (profiles/copies_rate.txt): 100 Mb with a fifth in repeats 1.81 ms, against 56.6 ms with one atomic per lane
-//                   and 29.0 ms when only runs of neighbouring lanes are folded; no cost where every hit has a slot of its own.
+//                   the result is exact whatever order and contention.  Equal slots are folded inside a wave first
+//                   (wave_fold_add, pg_keytable_dev.h).  Measured (profiles/copies_rate.txt): 100 Mb with a fifth in repeats
+//                   1.81 ms, against 56.6 ms with one atomic per lane and 29.0 ms when only runs of neighbouring lanes are
+//                   folded; no cost where every hit has a slot of its own.
 //                   Hits: a ballot per wave, one atomic per block, as k_pos_mates counts mates.
 //   k_copy_profile  the structure of k_presence_profile: one block per chunk of COPIES_CHUNK positions of one target contig, no
 //                   block waits for another, no global atomic.  A lane resolves the slot of its 16 positions once (LDS: a slot
 //                   number, or the marks INVALID / ABSENT — a key that is not in the table reads depth 0).  Then per plane: the
 //                   depths from the plane, the 64-bin histogram in LDS — per wave, one plain add by lane 0 per distinct bin among
-//                   the wave's lanes (ballot match: depths along a gene are few) — the four waves' sums to partial[], and the u16
+//                   the wave's lanes (wave_fold_bins, pg_keytable_dev.h) — the four waves' sums to partial[], and the u16
 //                   depths to the track when one is asked for.  The host sums a contig's chunks (pg_copies_host.h).
 // Every write to HBM is a vector store or a vector atomic.
 #include "pg_kernels.h"
-#include "pg_keytable_dev.h"  // the walk, copy_key, copy_lookup and the slot marks
+#include "pg_keytable_dev.h"  // the walk, copy_key, copy_lookup, the slot marks, the wave folds and block_add
 
 namespace pg {
 
-constexpr uint32_t COPY_FOLD_TURNS = 8;  // slots a wave folds before its lanes add for themselves (a satellite of period p: at most p)
 static_assert(COPIES_CHUNK % 256 == 0, "a chunk is a whole number of tiles");
 static_assert(COPIES_BINS == 64, "one bin per lane of a wave");
 
@@ -79,22 +76,8 @@ __global__ __launch_bounds__(256) void k_copy_count(int k, const SeqDesc *__rest
         uint32_t slot = SLOT_ABSENT;
         if (p < p1 && window_valid(v, p, k)) slot = copy_lookup(keys, smask, max_probe, copy_key(v.seqw, p, k));
         const bool hit = slot != SLOT_ABSENT;
-        const uint64_t hm = __ballot(hit);
-        found += (uint32_t)__popcll(hm);
-        if (hm == 0) continue;  // (wave-uniform)
-        // turns: the first lane left takes every lane that has its slot and adds their number.  A turn that finds the lane alone —
-        // hits scattered over the table — ends the folding, as the last turn does: the lanes left add for themselves
-        uint64_t todo = hm;
-        for (uint32_t turn = 0; turn < COPY_FOLD_TURNS && todo; ++turn) {
-            const uint32_t first = (uint32_t)__builtin_ctzll(todo);
-            const uint32_t s0 = (uint32_t)__shfl((int)slot, (int)first);
-            const uint64_t m = __ballot(hit && slot == s0);
-            const uint32_t n = (uint32_t)__popcll(m);
-            if (lane == first) atomicAdd(&plane[s0], n);
-            todo &= ~m;
-            if (n == 1) break;
-        }
-        if ((todo >> lane) & 1ull) atomicAdd(&plane[slot], 1u);
+        found += (uint32_t)__popcll(__ballot(hit));
+        wave_fold_add(hit, slot, lane, [&](uint32_t s, uint32_t n) { atomicAdd(&plane[s], n); });
     }
     block_add(found, hits);
 }
@@ -138,13 +121,9 @@ __global__ __launch_bounds__(256) void k_copy_profile(int k, const SeqDesc *__re
             const uint32_t dp = valid && s != SLOT_ABSENT ? pl[s] : 0u;
             if (track && c0 + i < ce) track[(uint64_t)g * depth_stride + i] = (uint16_t)(valid ? min(dp, COPIES_DEPTH_MAX) : COPIES_DEPTH_INVALID);
             const uint32_t bin = min(dp, COPIES_BINS - 1);
-            uint64_t todo = __ballot(valid);
-            while (todo) {  // (wave-uniform: one turn per distinct bin among the wave's valid lanes, 64 at the most)
-                const uint32_t b = (uint32_t)__shfl((int)bin, (int)__builtin_ctzll(todo));
-                const uint64_t m = __ballot(valid && bin == b);
+            wave_fold_bins(valid, bin, [&](uint32_t b, uint64_t m) {
                 if (lane == 0) whist[wave][b] += (uint32_t)__popcll(m);
-                todo &= ~m;
-            }
+            });
         }
         __syncthreads();
         if (tid < COPIES_BINS)

@@ -425,7 +425,7 @@ hipError_t launch_table_screen(hipStream_t st, const SubTable &t, uint32_t ngeno
 //                        out_keys / out_depth (entries at or past cap are never written)
 //   runs   chunk = {contig, first position}: the NOVEL_CHUNK k-mer positions from there, cut at the contig's end, a contig's
 //          chunks consecutive and in order; every contig named holds at least t.k bases and at most 2^32 - 1 k-mer positions.
-//          offs == NULL  count: counts[c] = {run starts, run ends, valid windows, novel windows} of chunk c
+//          offs == NULL  count: counts[c] = {valid windows, run starts, run ends, novel windows} of chunk c
 //          offs != NULL  emit: offs[c] = {starts, ends} of all chunks before c; the contig-relative positions of the run starts
 //                        (with left_held) / the exclusive run ends (with right_held) from there on (entries at or past `total`
 //                        are never written)

@@ -10,7 +10,8 @@
 // One reader keeps key_find's walk written out, for its speed: hit_word of pg_locate.hip.  A change of the policy goes there too.
 //
 // Beside the walk, what the kernels over a seqset's k-mer positions share: the view of one contig with the validity of a window,
-// and the sum of per-wave counts that a block adds to a counter in HBM.
+// the two folds a wave takes over its lanes before it touches a counter (equal slots, equal bins), and the sums of per-wave counts
+// that a block adds to counters in HBM.
 #pragma once
 #include "pg_kernels.h"
 
@@ -91,16 +92,67 @@ __device__ __forceinline__ uint32_t copy_lookup(const unsigned long long *__rest
     return key_find<uint32_t>(keys, smask, max_probe, key, SLOT_ABSENT);
 }
 
-// ---- a block's count: *dst += the sum of the four waves' n (every lane of a wave passes its wave's sum).  EVERY lane of the
-// block must reach this call (a barrier), and a kernel calls it once (one static LDS array) ----
-__device__ __forceinline__ void block_add(uint32_t n_per_wave, unsigned long long *dst) {
-    __shared__ uint32_t wsum[4];
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n_per_wave;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t n = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (n) atomicAdd(dst, (unsigned long long)n);
+// ---- the folds of one wave.  Both are loops with wave-uniform bounds: every lane of the wave reaches the call, whatever its flag ----
+// one value of lane `src`, in every lane (a 64-bit one takes two shuffles)
+__device__ __forceinline__ uint32_t wave_read(uint32_t v, int src) { return (uint32_t)__shfl((int)v, src); }
+__device__ __forceinline__ uint64_t wave_read(uint64_t v, int src) {
+    return (uint64_t)wave_read((uint32_t)v, src) | ((uint64_t)wave_read((uint32_t)(v >> 32), src) << 32);
+}
+
+// slots a wave folds before its lanes add for themselves (a satellite of period p: at most p)
+constexpr uint32_t FOLD_TURNS = 8;
+
+// add(id, n) for every distinct `id` among the lanes that are `on`, n the lanes that have it — the counter of a slot that many lanes
+// hit gets ONE atomic, not one per lane (a homopolymer puts all 64 lanes on one slot, a satellite of period p on at most p:
+// profiles/copies_rate.txt).  Turns: the first lane left takes every lane that has its id and adds their number.  A turn that finds
+// its lane alone — ids scattered over the table — ends the folding, as turn TURNS does: the lanes left add 1 each.  A wave with no
+// lane on does nothing.  id: 32 or 64 bits.
+template <uint32_t TURNS = FOLD_TURNS, class Id, class Add>
+__device__ __forceinline__ void wave_fold_add(bool on, Id id, uint32_t lane, Add add) {
+    uint64_t todo = __ballot(on);
+    for (uint32_t turn = 0; turn < TURNS && todo; ++turn) {
+        const uint32_t first = (uint32_t)__builtin_ctzll(todo);
+        const Id i0 = wave_read(id, (int)first);
+        const uint64_t m = __ballot(on && id == i0);
+        const uint32_t n = (uint32_t)__popcll(m);
+        if (lane == first) add(i0, n);
+        todo &= ~m;
+        if (n == 1) break;
     }
+    if ((todo >> lane) & 1ull) add(id, 1u);
+}
+
+// each(b, m) once per distinct `bin` among the wave's `act` lanes, m the ballot of the lanes that have it: one turn per bin, 64 at
+// the most (depths along a gene are few).  each is called by the whole wave with the same (b, m) in every lane: it may take
+// ballots of its own, and leaves its add to one lane.
+template <class Each>
+__device__ __forceinline__ void wave_fold_bins(bool act, uint32_t bin, Each each) {
+    uint64_t todo = __ballot(act);
+    while (todo) {
+        const uint32_t b = wave_read(bin, (int)__builtin_ctzll(todo));
+        const uint64_t m = __ballot(act && bin == b);
+        each(b, m);
+        todo &= ~m;
+    }
+}
+
+// ---- a block's counts: dst[i] += the sum of the four waves' n[i] (every lane of a wave passes its wave's sums).  EVERY lane of
+// the block must reach this call (a barrier), and a kernel calls it once (one static LDS array): its counters go in one call ----
+template <uint32_t N>
+__device__ __forceinline__ void block_add(const uint32_t (&n_per_wave)[N], unsigned long long *dst) {
+    static_assert(N >= 1 && N <= 64, "thread i of the block adds counter i");
+    __shared__ uint32_t wsum[N][4];
+    if ((threadIdx.x & 63) == 0)
+        for (uint32_t i = 0; i < N; ++i) wsum[i][threadIdx.x >> 6] = n_per_wave[i];
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const uint32_t n = wsum[threadIdx.x][0] + wsum[threadIdx.x][1] + wsum[threadIdx.x][2] + wsum[threadIdx.x][3];
+        if (n) atomicAdd(dst + threadIdx.x, (unsigned long long)n);
+    }
+}
+__device__ __forceinline__ void block_add(uint32_t n_per_wave, unsigned long long *dst) {
+    const uint32_t n[1] = {n_per_wave};
+    block_add(n, dst);
 }
 
 }  // namespace pg

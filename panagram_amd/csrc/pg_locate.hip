@@ -12,24 +12,19 @@
 //              runs.  For k >= 2 a run lies inside one query: the global Q positions of two neighbouring contigs' k-mers differ
 //              by at least k.
 // Positions of G are contig-relative everywhere: G's total is unlimited, one contig holds at most 2^32 - 1 k-mer positions.
-//   k_hit_runs  the structure of k_mate_runs with the mate load replaced by the probe (the walk of k_pos_mates without its
-//               condition on side 0): chunks of LOCATE_CHUNK positions of one contig, tiles of 256, the predecessor's word from
-//               the lane below, the wave below (LDS), the tile before, and at a chunk's first position from ONE extra probe of
-//               position c0 - 1 — none at a contig's first.  With H = hit, P = predecessor hit, C = continues:
+//   k_hit_runs  the run scan of pg_runscan.h over chunks of LOCATE_CHUNK positions of one contig; a position's value is its hit
+//               word, from a probe (the walk of k_pos_mates without its condition on side 0), the halo ONE extra probe of
+//               position c0 - 1.  With H = hit, P = predecessor hit, C = continues:
 //                 run starts  H & ~C        run ends (exclusive)  P & ~C, and one at the contig's end when its last is a hit
-//               count (EMIT = false): counts[chunk] = {hits, starts, ends, 0}; the host takes exclusive scans.
-//               emit: starts and ends are numbered separately (the i-th start and the i-th end of a contig are one run), so the
-//               output is sorted by (contig, start) by construction and the same on every call.
+//               counts[chunk] = {hits, starts, ends, 0}; beside a start goes its hit word.
 // Both passes probe: the table is only read, so both see the same words.  The table's policy stands in pg_keytable_dev.h; the
 // walk here is key_find's, kept as a copy of its own in hit_word for its speed.  No atomics; every write to HBM is a vector store.
 #include "pg_kernels.h"
 
 #include "pg_postable_dev.h"  // PosSlot, kmer_key_rc, mate_continues; with it pg_keytable_dev.h
+#include "pg_runscan.h"
 
 namespace pg {
-
-constexpr uint32_t LOCATE_TILE = 256;
-static_assert(LOCATE_CHUNK % LOCATE_TILE == 0, "a chunk is a whole number of tiles");
 
 // the hit word of position p of a contig (p below its k-mer positions).  (The view by value: by reference the kernel comes out
 // a few instructions different.)
@@ -60,81 +55,28 @@ __global__ __launch_bounds__(256) void k_hit_runs(int k, const SeqDesc *__restri
                                                   uint4 *__restrict__ counts, const ulonglong2 *__restrict__ offs, uint64_t total,
                                                   uint32_t *__restrict__ run_start, uint32_t *__restrict__ run_end,
                                                   uint32_t *__restrict__ run_hit) {
-    __shared__ uint32_t lasth[4];  // the hit word of every wave's last lane
-    __shared__ uint4 wcnt[4];      // {starts, ends, hits, 0} of every wave
-    __shared__ uint32_t tailh;     // the hit word of the chunk's last position
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint2 ck = chunks[blockIdx.x];
     const ContigView v = contig_view(sd, ck.x, seqw_all, nmw_all, has_n, k);
     const uint64_t smask = nslots - 1;
-    // this chunk: positions [c0, ce), 0 <= c0 < ce <= nk <= 2^32 - 1 (64-bit: c0 + LOCATE_CHUNK may pass 2^32)
-    const uint64_t nk = v.nkmers, c0 = ck.y, ce = min(c0 + LOCATE_CHUNK, nk);
+    // positions in 64 bits: nk <= 2^32 - 1, but c0 + LOCATE_CHUNK may pass 2^32
+    const uint64_t c0 = ck.y;
     // the chunk's halo: the hit word of position c0 - 1 (every lane the same probe: broadcast loads)
-    uint32_t carry = c0 > 0 ? hit_word(k, v, c0 - 1, slots, smask, max_probe) : NO_MATE;
-    uint32_t nhits = 0, nstarts = 0, nends = 0;
-    uint64_t soff = 0, eoff = 0;
-    if (EMIT) {
-        const ulonglong2 o = offs[blockIdx.x];
-        soff = o.x;
-        eoff = o.y;
-    }
-    for (uint64_t t0 = c0; t0 < ce; t0 += LOCATE_TILE) {  // (bounds uniform over the block: every lane reaches the barriers)
-        const uint64_t j = t0 + tid;
-        const bool act = j < ce;
-        const uint32_t h = act ? hit_word(k, v, j, slots, smask, max_probe) : NO_MATE;
-        if (lane == 63) lasth[wave] = h;
-        if (j == ce - 1) tailh = h;
-        __syncthreads();
-        uint32_t prev = (uint32_t)__shfl_up((int)h, 1);
-        if (lane == 0) prev = wave ? lasth[wave - 1] : carry;
-        carry = lasth[3];
-        const bool cont = act && mate_continues(prev, h);
-        const uint64_t sm = __ballot(act && h != NO_MATE && !cont);
-        const uint64_t em = __ballot(act && prev != NO_MATE && !cont);
-        const uint64_t hm = __ballot(act && h != NO_MATE);
-        if (lane == 0) wcnt[wave] = make_uint4((uint32_t)__popcll(sm), (uint32_t)__popcll(em), (uint32_t)__popcll(hm), 0u);
-        __syncthreads();
-        // (one buffer each: lasth is read between the two barriers and written again behind the second, wcnt is read behind
-        // the second and written again behind the next tile's first)
-        uint32_t sbelow = 0, ebelow = 0, stile = 0, etile = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 4; ++w) {
-            const uint4 c = wcnt[w];
-            if (w == wave) {
-                sbelow = stile;
-                ebelow = etile;
-            }
-            stile += c.x;
-            etile += c.y;
-            nhits += c.z;
-        }
-        if (EMIT) {
-            const uint64_t below = (1ull << lane) - 1ull;
-            if ((sm >> lane) & 1ull) {
-                const uint64_t at = soff + nstarts + sbelow + (uint32_t)__popcll(sm & below);
-                if (at < total) {
-                    run_start[at] = (uint32_t)j;
-                    run_hit[at] = h;
-                }
-            }
-            if ((em >> lane) & 1ull) {
-                const uint64_t at = eoff + nends + ebelow + (uint32_t)__popcll(em & below);
-                if (at < total) run_end[at] = (uint32_t)j;
-            }
-        }
-        nstarts += stile;
-        nends += etile;
-    }
-    // the contig's last chunk: a run that reaches the contig's last position ends at nk (tailh: written in front of the last
-    // tile's first barrier, which every lane has passed)
-    if (ce == nk && tailh != NO_MATE) {
-        if (EMIT && tid == 0) {
-            const uint64_t at = eoff + nends;
-            if (at < total) run_end[at] = (uint32_t)nk;
-        }
-        nends += 1;
-    }
-    if (!EMIT && tid == 0) counts[blockIdx.x] = make_uint4(nhits, nstarts, nends, 0u);
+    const uint32_t halo = c0 > 0 ? hit_word(k, v, c0 - 1, slots, smask, max_probe) : NO_MATE;
+    const ulonglong2 off = EMIT ? offs[blockIdx.x] : make_ulonglong2(0, 0);
+    const uint4 c = chunk_runs<EMIT, LOCATE_CHUNK>(
+        c0, v.nkmers, NO_MATE, halo, off, total, [&](uint64_t j) { return hit_word(k, v, j, slots, smask, max_probe); },
+        [](bool act, uint32_t prev, uint32_t h, bool &starts, bool &ends) {
+            const bool cont = act && mate_continues(prev, h);
+            starts = act && h != NO_MATE && !cont;
+            ends = act && prev != NO_MATE && !cont;
+        },
+        [](uint32_t tail) { return tail != NO_MATE; }, [](uint32_t h) { return h != NO_MATE; }, no_tally(),
+        [&](uint64_t at, uint64_t j, uint32_t, uint32_t h) {
+            run_start[at] = (uint32_t)j;
+            run_hit[at] = h;
+        },
+        [&](uint64_t at, uint64_t j, uint32_t, uint32_t) { run_end[at] = (uint32_t)j; });
+    if (!EMIT && threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
 hipError_t launch_hit_runs(hipStream_t st, int k, const SeqDesc *sd, const uint2 *chunks, uint32_t nchunks, const uint64_t *seqw,

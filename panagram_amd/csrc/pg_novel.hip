@@ -18,34 +18,31 @@
 // launch, so no claim runs out of probes; one that does raises the overflow flag all the same.
 //   k_novel_count  one launch over the (contig, piece) jobs of a sequence set, the pan table read-only.  A valid window probes the
 //                  pan table (lane_find); a miss claims its key's slot in the novel table (key_claim) and adds 1 to the slot's
-//                  depth.  Equal slots are folded inside the wave first, as in k_copy_count: the first lane left takes every
-//                  lane that has its slot and adds their number in ONE atomic, in up to NOVEL_FOLD_TURNS turns; a turn that
-//                  finds its lane alone ends the folding, and the lanes left add 1 each.  A wave without a miss skips all of it.
-//                  ctr: the valid windows, the pan hits, the keys newly claimed, the claims that gave up — a ballot per wave,
-//                  one atomic per block each.
+//                  depth.  Equal slots are folded inside the wave first (wave_fold_add, pg_keytable_dev.h).  A wave without a
+//                  miss skips the claim and the fold.  ctr: the valid windows, the pan hits, the keys newly claimed, the claims
+//                  that gave up — a ballot per wave, one atomic per block each (one block_add of four counters).
 //   k_novel_grow   one lane per slot of the old table: its key claimed in the new one (twice the slots or more), its depth copied
 //                  by a plain store — a key stands once in the old table, so every new slot has one writer.
 //   k_novel_scan   one pass over the slots and their depths, a run of consecutive slots per block (novel_scan_per_block).  Count: nkeys, solid,
 //                  solid_windows (the sum of the solid depths, 64 bits) and depth_hist[64] by min(d, 63) — the histogram folded
-//                  per wave, one add per distinct bin, into the block's counters in LDS, which are flushed once per block, as
-//                  k_table_screen does — and the solid keys of every block's slots.  Emit, after the host's exclusive scan of
+//                  per wave (wave_fold_bins, pg_keytable_dev.h) into the block's counters in LDS, which are flushed once per
+//                  block — and the solid keys of every block's slots.  Emit, after the host's exclusive scan of
 //                  those: the solid keys and their depths in slot order, the same on every call.
-//   k_novel_runs   the structure of k_hit_runs: chunks of NOVEL_CHUNK positions of one contig, tiles of 256; the state of a
-//                  position is one of invalid, held, novel (a probe of the pan table; the novel table is not touched); the
-//                  predecessor's state comes from the lane below, the wave below (LDS), the tile before, and at a chunk's first
-//                  position from ONE extra probe of position c0 - 1 — none at a contig's first.  With V = novel, P = predecessor
-//                  novel:  run starts  V & ~P  (left_held: the predecessor is held)     run ends (exclusive)  P & ~V
-//                  (right_held: this position is held), and one at the contig's end when its last is novel.  Count, then emit
-//                  with starts and ends numbered separately: sorted by (contig, start) by construction.
+//   k_novel_runs   the run scan that pg_runscan.h describes (its loop written out here, for its speed) over chunks of NOVEL_CHUNK
+//                  positions of one contig; a position's value is its state, one of invalid, held, novel (a probe of the pan
+//                  table; the novel table is not touched), the halo ONE extra probe of position c0 - 1.  With V = novel, P =
+//                  predecessor novel:
+//                    run starts  V & ~P  (left_held: the predecessor is held)     run ends (exclusive)  P & ~V  (right_held:
+//                    this position is held), and one at the contig's end when its last is novel
+//                  counts[chunk] = {valid, starts, ends, novel}.
 // Every write to HBM is a vector store or a vector atomic.
 #include "pg_kernels.h"
-#include "pg_keytable_dev.h"  // contig_view, window_valid, copy_key, key_claim, block_add
+#include "pg_keytable_dev.h"  // contig_view, window_valid, copy_key, key_claim, the wave folds, block_add
+#include "pg_runscan.h"  // what k_novel_runs' loop is a copy of; RUNSCAN_TILE
 
 namespace pg {
 
-constexpr uint32_t NOVEL_FOLD_TURNS = 8;  // slots a wave folds before its lanes add for themselves (a satellite of period p: at most p)
-constexpr uint32_t NOVEL_TILE = 256;
-static_assert(NOVEL_CHUNK % NOVEL_TILE == 0, "a chunk is a whole number of tiles");
+static_assert(NOVEL_CHUNK % RUNSCAN_TILE == 0, "a chunk is a whole number of tiles");
 constexpr uint32_t NOVEL_SCAN_UNROLL = 8;  // tiles of k_novel_scan whose loads are in flight together
 static_assert(NOVEL_SCAN_SLOTS % (256 * NOVEL_SCAN_UNROLL) == 0, "a block's slots are a whole number of tile groups");
 static_assert(NOVEL_BINS == 64, "one bin per lane of a wave");
@@ -77,31 +74,10 @@ __global__ __launch_bounds__(256) void k_novel_count(SubTable st, int k, const S
         const uint32_t slot = (uint32_t)s64;  // (below 2^31: COPIES_MAX_SLOTS)
         nclaimed += (uint32_t)__popcll(__ballot(claimed));
         ngaveup += (uint32_t)__popcll(__ballot(miss && !ok));
-        // turns: the first lane left takes every lane that has its slot and adds their number.  A turn that finds the lane alone —
-        // sequencing errors scattered over the table — ends the folding, as the last turn does: the lanes left add for themselves
-        uint64_t todo = __ballot(ok);
-        for (uint32_t turn = 0; turn < NOVEL_FOLD_TURNS && todo; ++turn) {
-            const uint32_t first = (uint32_t)__builtin_ctzll(todo);
-            const uint32_t s0 = (uint32_t)__shfl((int)slot, (int)first);
-            const uint64_t m = __ballot(ok && slot == s0);
-            const uint32_t n = (uint32_t)__popcll(m);
-            if (lane == first) atomicAdd(&depth[s0], n);
-            todo &= ~m;
-            if (n == 1) break;
-        }
-        if ((todo >> lane) & 1ull) atomicAdd(&depth[slot], 1u);
+        wave_fold_add(ok, slot, lane, [&](uint32_t s, uint32_t n) { atomicAdd(&depth[s], n); });
     }
-    // Four counters, four calls of block_add.  pg_keytable_dev.h says a kernel calls it once, because all calls share ONE static LDS
-    // array of four sums: a second call could overwrite a sum that thread 0 of the first has not read yet.  The exception, as in
-    // k_table_mark: a barrier between two calls, which every lane reaches (no lane leaves this kernel early) — thread 0 reads the
-    // sums in front of it, the next call writes them behind it.
-    block_add(nvalid, ctr);
-    __syncthreads();
-    block_add(found, ctr + 1);
-    __syncthreads();
-    block_add(nclaimed, ctr + 2);
-    __syncthreads();
-    block_add(ngaveup, ctr + 3);
+    const uint32_t sums[4] = {nvalid, found, nclaimed, ngaveup};
+    block_add(sums, ctr);
 }
 
 // slot i of the old table into the new one; flag[0] becomes nonzero when a claim gave up
@@ -194,13 +170,9 @@ __global__ __launch_bounds__(256) void k_novel_scan(const unsigned long long *__
                 if (solid) sw += d;
                 // the depth bins: one turn per distinct bin among the wave's keys, 64 at the most
                 const uint32_t bin = min(d, NOVEL_BINS - 1);
-                uint64_t todo = am;
-                while (todo) {  // (wave-uniform)
-                    const uint32_t b = (uint32_t)__shfl((int)bin, (int)__builtin_ctzll(todo));
-                    const uint64_t m = __ballot(act && bin == b);
+                wave_fold_bins(act, bin, [&](uint32_t b, uint64_t m) {
                     if (lane == 0) atomicAdd(&hist_s[b], (uint32_t)__popcll(m));
-                    todo &= ~m;
-                }
+                });
             }
         }
     }
@@ -234,7 +206,10 @@ __device__ __forceinline__ uint32_t novel_state(const SubTable &st, int k, const
     return lane_find(st, copy_key(v.seqw, p, k), line, slot) ? NS_HELD : NS_NOVEL;
 }
 
-// chunk = {contig, first position}: a contig of at least k bases, 0 <= first position < its k-mer positions
+// chunk = {contig, first position}: a contig of at least k bases, 0 <= first position < its k-mer positions.
+// chunk_runs' loop (pg_runscan.h), written out: through chunk_runs this kernel took 1.794 ms against 1.747 ms over an assembly of
+// 100 Mb on the MI355X (profiles/stream_refactor_ab.txt: the probe's scalar registers are at their limit, and the inlined functors
+// spill more of them).  A change to the run scan comes here too.
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_novel_runs(SubTable st, int k, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ chunks,
                                                     const uint64_t *seqw_all, const uint32_t *nmw_all, const uint32_t *has_n,
@@ -258,7 +233,7 @@ __global__ __launch_bounds__(256) void k_novel_runs(SubTable st, int k, const Se
         soff = o.x;
         eoff = o.y;
     }
-    for (uint64_t t0 = c0; t0 < ce; t0 += NOVEL_TILE) {  // (bounds uniform over the block: every lane reaches the barriers)
+    for (uint64_t t0 = c0; t0 < ce; t0 += RUNSCAN_TILE) {  // (bounds uniform over the block: every lane reaches the barriers)
         const uint64_t j = t0 + tid;
         const bool act = j < ce;
         const uint32_t s = act ? novel_state(st, k, v, j) : NS_INVALID;
@@ -273,8 +248,6 @@ __global__ __launch_bounds__(256) void k_novel_runs(SubTable st, int k, const Se
         const uint64_t vm = __ballot(act && s != NS_INVALID), nm = __ballot(act && s == NS_NOVEL);
         if (lane == 0) wcnt[wave] = make_uint4((uint32_t)__popcll(sm), (uint32_t)__popcll(em), (uint32_t)__popcll(vm), (uint32_t)__popcll(nm));
         __syncthreads();
-        // (one buffer each: lasts is read between the two barriers and written again behind the second, wcnt is read behind
-        // the second and written again behind the next tile's first)
         uint32_t sbelow = 0, ebelow = 0, stile = 0, etile = 0;
 #pragma unroll
         for (uint32_t w = 0; w < 4; ++w) {
@@ -308,8 +281,7 @@ __global__ __launch_bounds__(256) void k_novel_runs(SubTable st, int k, const Se
         nstarts += stile;
         nends += etile;
     }
-    // the contig's last chunk: a run that reaches the contig's last position ends at nk (tails: written in front of the last
-    // tile's first barrier, which every lane has passed)
+    // the contig's last chunk: a run that reaches the contig's last position ends at nk
     if (ce == nk && tails == NS_NOVEL) {
         if (EMIT && tid == 0) {
             const uint64_t at = eoff + nends;
@@ -320,7 +292,7 @@ __global__ __launch_bounds__(256) void k_novel_runs(SubTable st, int k, const Se
         }
         nends += 1;
     }
-    if (!EMIT && tid == 0) counts[blockIdx.x] = make_uint4(nstarts, nends, nvalid, nnovel);
+    if (!EMIT && tid == 0) counts[blockIdx.x] = make_uint4(nvalid, nstarts, nends, nnovel);
 }
 
 static bool pan_ok(const SubTable &t) { return t.k >= 1 && t.k <= 32 && t.nbuckets != 0 && t.slots >= 1 && t.slots <= 64 && t.buckets; }

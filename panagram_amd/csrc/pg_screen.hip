@@ -13,8 +13,7 @@
 //
 //   k_table_mark    one launch over the (contig, piece) jobs of a sequence set, the table read-only.  A valid window finds its
 //                   slot (lane_find: the walk of lane_lookup) and adds 1 to the slot's byte.  Equal slots are folded inside the
-//                   wave first, as in k_copy_count: the first lane with a hit takes every lane that has its slot and adds their
-//                   number, in up to SCREEN_FOLD_TURNS turns; a turn that finds its lane alone ends the folding.  The add is a
+//                   wave first (wave_fold_add, pg_keytable_dev.h, over the 64-bit index of the byte).  The add is a
 //                   saturating add on the byte by a compare-and-swap on its aligned dword: the three neighbouring bytes are
 //                   other slots' and go back as they were read, so no carry ever reaches them; a byte that reads 255 is left
 //                   alone without an atomic.  Neighbouring positions of a read share their minimizer and so their home line:
@@ -26,19 +25,18 @@
 //                   queue in LDS and the wave works on 64 KEYS at a time, as that kernel does.  Per 64 keys: the ballot of bit
 //                   c is column c's word (pg_pairblocks.h), the ballot of depth >= min_count the seen word; two popcounts per
 //                   column give distinct and seen; a lane's popcount gives occ and seen_occ, a lone bit's lane private and
-//                   private_seen; the depth bins are folded as k_copy_profile folds its histogram (one add per distinct bin
-//                   among the wave's keys).  All of it into the BLOCK's 32-bit counters in LDS, flushed once with 64-bit
+//                   private_seen; the depth bins are folded per wave (wave_fold_bins, pg_keytable_dev.h: one add per distinct
+//                   bin among the wave's keys).  All of it into the BLOCK's 32-bit counters in LDS, flushed once with 64-bit
 //                   atomics: no block waits for another.  The grid keeps a block below 2^32 slots (tablescan_blocks).
 // Every write to HBM is a vector store or a vector atomic.
 #include "pg_kernels.h"
-#include "pg_keytable_dev.h"  // contig_view, window_valid, copy_key, block_add
+#include "pg_keytable_dev.h"  // contig_view, window_valid, copy_key, the wave folds, block_add
 #include "pg_rowread.h"       // valid_bits
 #include "pg_pairblocks.h"
 #include "pg_tablescan.h"
 
 namespace pg {
 
-constexpr uint32_t SCREEN_FOLD_TURNS = 8;  // slots a wave folds before its lanes add for themselves (a satellite of period p: at most p)
 static_assert(SCREEN_BINS == 64, "one bin per lane of a wave");
 
 // byte `idx` of the plane += n, saturating at SCREEN_DEPTH_MAX
@@ -74,26 +72,11 @@ __global__ __launch_bounds__(256) void k_table_mark(SubTable st, int k, const Se
         const bool hit = valid && lane_find(st, copy_key(v.seqw, p, k), line, slot);
         const uint64_t idx = (uint64_t)line * st.slots + slot;
         nvalid += (uint32_t)__popcll(__ballot(valid));
-        const uint64_t hm = __ballot(hit);
-        found += (uint32_t)__popcll(hm);
-        if (hm == 0) continue;  // (wave-uniform)
-        // turns: the first lane left takes every lane that has its slot and adds their number.  A turn that finds the lane alone —
-        // hits scattered over the table — ends the folding, as the last turn does: the lanes left add for themselves
-        uint64_t todo = hm;
-        for (uint32_t turn = 0; turn < SCREEN_FOLD_TURNS && todo; ++turn) {
-            const int first = (int)__builtin_ctzll(todo);
-            const uint64_t i0 = (uint64_t)(uint32_t)__shfl((int)(uint32_t)idx, first) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(idx >> 32), first) << 32);
-            const uint64_t m = __ballot(hit && idx == i0);
-            const uint32_t n = (uint32_t)__popcll(m);
-            if ((int)lane == first) plane_add(plane, i0, n);
-            todo &= ~m;
-            if (n == 1) break;
-        }
-        if ((todo >> lane) & 1ull) plane_add(plane, idx, 1u);
+        found += (uint32_t)__popcll(__ballot(hit));
+        wave_fold_add(hit, idx, lane, [&](uint64_t i, uint32_t n) { plane_add(plane, i, n); });
     }
-    block_add(nvalid, ctr);
-    __syncthreads();  // (block_add's one LDS array: the first sum is read before the second is written)
-    block_add(found, ctr + 1);
+    const uint32_t sums[2] = {nvalid, found};
+    block_add(sums, ctr);
 }
 
 // LDS of one block of k_table_screen, in 32-bit words: the block's counters, then the four waves' queues of W mask words and a depth
@@ -175,14 +158,11 @@ __global__ __launch_bounds__(256) void k_table_screen(SubTable st, uint32_t N, u
         // the depth bins: one turn per distinct bin among the wave's keys, 64 at the most
         const uint32_t bin = min(dep, SCREEN_BINS - 1);
         const bool core = act && pc == N;
-        uint64_t todo = __ballot(act);
-        while (todo) {  // (wave-uniform)
-            const uint32_t b = (uint32_t)__shfl((int)bin, (int)__builtin_ctzll(todo));
-            const uint64_t m = __ballot(act && bin == b), mc = __ballot(core && bin == b);
+        wave_fold_bins(act, bin, [&](uint32_t b, uint64_t m) {
+            const uint64_t mc = __ballot(core && bin == b);
             if (lane == 0) atomicAdd(&dh_s[b], (uint32_t)__popcll(m));
             if (lane == 0 && mc) atomicAdd(&ch_s[b], (uint32_t)__popcll(mc));
-            todo &= ~m;
-        }
+        });
         nk += take;
         qh = (qh + take) & (TS_QCAP - 1);
         qn -= take;

@@ -21,22 +21,17 @@
 //                  the single occurrence's word or MULTI, whatever the order the lanes ran in.
 //   k_pos_mates    the same walk over A; mates[koff[c] + p] for k-mer position p of contig c (contigs back to back), and the
 //                  number of mated positions: a ballot per wave, one atomic per block.
-//   k_mate_runs    the structure of k_find_runs (pg_find.hip): chunks of MATE_CHUNK positions of one contig, tiles of 256, the
-//                  predecessor's mate from the lane below, the wave below (LDS), the tile before, and ONE halo element at a
-//                  chunk's first position — none at a contig's first.  With M = mated, P = predecessor mated, C = continues:
+//   k_mate_runs    the run scan of pg_runscan.h over chunks of MATE_CHUNK positions of one contig; a position's value is its
+//                  mate, the halo one load.  With M = mated, P = predecessor mated, C = continues:
 //                    run starts  M & ~C        run ends (exclusive)  P & ~C, and one at the contig's end when its last is mated
-//                  count (EMIT = false): counts[chunk] = {mated, starts, ends, 0}; the host takes exclusive scans.
-//                  emit: starts and ends are numbered separately (the i-th start and the i-th end of a contig are one run), so
-//                  the output is sorted by (contig, start) by construction and the same on every call.
+//                  counts[chunk] = {mated, starts, ends, 0}; beside a start goes its mate.
 // Every write to HBM is a vector store or a vector atomic.
 #include "pg_kernels.h"
 
 #include "pg_postable_dev.h"  // PosSlot, kmer_key_rc, mate_continues; with it pg_keytable_dev.h
+#include "pg_runscan.h"
 
 namespace pg {
-
-constexpr uint32_t MATE_TILE = 256;
-static_assert(MATE_CHUNK % MATE_TILE == 0, "a chunk is a whole number of tiles");
 
 // job = positions [y * SYNTENY_JOB, (y + 1) * SYNTENY_JOB) of contig x, which holds at least k bases
 __global__ __launch_bounds__(256) void k_pos_insert(int k, uint32_t side, const SeqDesc *__restrict__ sd, const uint2 *__restrict__ jobs,
@@ -103,80 +98,26 @@ __global__ __launch_bounds__(256) void k_mate_runs(const uint32_t *__restrict__ 
                                                    const ulonglong2 *__restrict__ offs, uint64_t total,
                                                    uint32_t *__restrict__ run_start, uint32_t *__restrict__ run_end,
                                                    uint32_t *__restrict__ run_mate) {
-    __shared__ uint32_t lastm[4];  // the mate of every wave's last lane
-    __shared__ uint4 wcnt[4];      // {starts, ends, mated, 0} of every wave
-    __shared__ uint32_t tailm;     // the mate of the chunk's last position
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint2 ck = chunks[blockIdx.x];
     const uint2 cd = contigs[ck.x];
     const uint32_t *cm = mates + cd.x;
-    const uint32_t nk = cd.y, c0 = ck.y, ce = min(c0 + MATE_CHUNK, nk);  // this chunk: positions [c0, ce), 0 <= c0 < ce <= nk
     // the chunk's halo: the mate of position c0 - 1 (every lane the same entry: one broadcast load)
-    uint32_t carry = c0 > 0 ? cm[c0 - 1] : NO_MATE;
-    uint32_t matched = 0, nstarts = 0, nends = 0;
-    uint64_t soff = 0, eoff = 0;
-    if (EMIT) {
-        const ulonglong2 o = offs[blockIdx.x];
-        soff = o.x;
-        eoff = o.y;
-    }
-    for (uint32_t t0 = c0; t0 < ce; t0 += MATE_TILE) {
-        const uint32_t j = t0 + tid;
-        const uint32_t m = j < ce ? cm[j] : NO_MATE;
-        if (lane == 63) lastm[wave] = m;
-        if (j == ce - 1) tailm = m;
-        __syncthreads();
-        uint32_t prev = (uint32_t)__shfl_up((int)m, 1);
-        if (lane == 0) prev = wave ? lastm[wave - 1] : carry;
-        carry = lastm[3];
-        const bool act = j < ce;
-        const bool cont = act && mate_continues(prev, m);
-        const uint64_t sm = __ballot(act && m != NO_MATE && !cont);
-        const uint64_t em = __ballot(act && prev != NO_MATE && !cont);
-        const uint64_t mm = __ballot(act && m != NO_MATE);
-        if (lane == 0) wcnt[wave] = make_uint4((uint32_t)__popcll(sm), (uint32_t)__popcll(em), (uint32_t)__popcll(mm), 0u);
-        __syncthreads();
-        // (one buffer each: lastm is read between the two barriers and written again behind the second, wcnt is read behind
-        // the second and written again behind the next tile's first)
-        uint32_t sbelow = 0, ebelow = 0, stile = 0, etile = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 4; ++w) {
-            const uint4 c = wcnt[w];
-            if (w == wave) {
-                sbelow = stile;
-                ebelow = etile;
-            }
-            stile += c.x;
-            etile += c.y;
-            matched += c.z;
-        }
-        if (EMIT) {
-            const uint64_t below = (1ull << lane) - 1ull;
-            if ((sm >> lane) & 1ull) {
-                const uint64_t at = soff + nstarts + sbelow + (uint32_t)__popcll(sm & below);
-                if (at < total) {
-                    run_start[at] = j;
-                    run_mate[at] = m;
-                }
-            }
-            if ((em >> lane) & 1ull) {
-                const uint64_t at = eoff + nends + ebelow + (uint32_t)__popcll(em & below);
-                if (at < total) run_end[at] = j;
-            }
-        }
-        nstarts += stile;
-        nends += etile;
-    }
-    // the contig's last chunk: a run that reaches the contig's last position ends at nk (tailm: written in front of the last
-    // tile's first barrier, which every lane has passed)
-    if (ce == nk && tailm != NO_MATE) {
-        if (EMIT && tid == 0) {
-            const uint64_t at = eoff + nends;
-            if (at < total) run_end[at] = nk;
-        }
-        nends += 1;
-    }
-    if (!EMIT && tid == 0) counts[blockIdx.x] = make_uint4(matched, nstarts, nends, 0u);
+    const uint32_t halo = ck.y > 0 ? cm[ck.y - 1] : NO_MATE;
+    const ulonglong2 off = EMIT ? offs[blockIdx.x] : make_ulonglong2(0, 0);
+    const uint4 c = chunk_runs<EMIT, MATE_CHUNK>(
+        ck.y, cd.y, NO_MATE, halo, off, total, [&](uint32_t j) { return cm[j]; },
+        [](bool act, uint32_t prev, uint32_t m, bool &starts, bool &ends) {
+            const bool cont = act && mate_continues(prev, m);
+            starts = act && m != NO_MATE && !cont;
+            ends = act && prev != NO_MATE && !cont;
+        },
+        [](uint32_t tail) { return tail != NO_MATE; }, [](uint32_t m) { return m != NO_MATE; }, no_tally(),
+        [&](uint64_t at, uint32_t j, uint32_t, uint32_t m) {
+            run_start[at] = j;
+            run_mate[at] = m;
+        },
+        [&](uint64_t at, uint32_t j, uint32_t, uint32_t) { run_end[at] = j; });
+    if (!EMIT && threadIdx.x == 0) counts[blockIdx.x] = c;
 }
 
 hipError_t launch_pos_insert(hipStream_t st, int k, uint32_t side, const SeqDesc *sd, const uint2 *jobs, uint32_t njobs,

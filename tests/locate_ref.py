@@ -152,7 +152,7 @@ def crafted():
     dele = query("del", _rand(rng, 300))
     query("absent", _rand(rng, 500))
     single = query("single", _rand(rng, 64))
-    for i in range(16):  # bystanders, of which G holds every fourth
+    for i in range(16):  # bystanders, of which G holds every fourth (contig 6) and the first three others (contig 7)
         query(f"extra{i}", _rand(rng, 30 + 61 * i))
     promises = {}
 
@@ -220,7 +220,15 @@ def crafted():
     c6.put(4096, chunk_start)
     promises["starts at a chunk's start"] = [("none", 6, 4096 - k, 4096), ("hits", 6, 4096, 150 - k + 1, name["chunk_start"], 0, 0)]
     promises["absent query"] = name["absent"]
-    g = [bytes(c0.b), bytes(c1.b)] + small + [bytes(c6.b)]
+
+    # contig 7: 768 k-mer positions, three tiles exactly.  Three more bystanders: a run that STARTS at position 64 (its predecessor
+    # is the wave's below), one that starts at 256 (the tile's before), one that reaches the contig's end at a tile's end
+    c7 = _Contig(rng, 3 * TILE + k - 1)
+    for tag, at, i in (("starts at a wave's start", WAVE, 1), ("starts at a tile's start", TILE, 2), ("ends with the last tile", None, 3)):
+        seq = q[name[f"extra{i}"]]
+        at = c7.put(len(c7.b) - len(seq) if at is None else at, seq)
+        promises[tag] = [("none", 7, at - 1, at), ("hits", 7, at, len(seq) - k + 1, name[f"extra{i}"], 0, 0)]
+    g = [bytes(c0.b), bytes(c1.b)] + small + [bytes(c6.b), bytes(c7.b)]
     return dict(k=k, q=q, g=g, params=dict(CRAFTED_PARAMS), promises=promises, names=name)
 
 

@@ -21,6 +21,7 @@ BINS = 64
 JOB = 1 << 14   # k-mer positions per block of k_novel_count
 CHUNK = 4096    # ... per block of k_novel_runs
 TILE = 256      # ... per step of a block
+WAVE = 64       # ... per wave of a step
 
 
 # ---------------------------------------------------------------------------
@@ -144,6 +145,7 @@ LONG_POSITIONS = 2 * JOB + 300 + 57  # the period-11 contig: three jobs, the sam
 UNIT = 211                         # the period of the backbone the run contigs are cut from: its k-mers are the table's
 BACKBONE = CHUNK + 900
 INSERTION = 37
+EDGES_POSITIONS = 2 * CHUNK + TILE  # the ``edges`` contig: two chunks and one tile, exactly
 EXACT_FROM_K = 21                  # from this k on no chance hit splits a planted run or deepens a planted key
 
 
@@ -193,7 +195,9 @@ def crafted(k, min_count=2, seed=0):
     ``sub`` (a substitution: bases 1), ``ins`` (INSERTION random bases: bases INSERTION), ``del`` (a deletion: bases 0), ``tile`` /
     ``chunk`` (the homopolymer inserted so that its run crosses position TILE / CHUNK at any k), ``cut`` (an insertion with an N in it: two runs), ``all``
     (a wholly novel contig: bases = its length), ``short`` (k - 1 bases), ``homo`` (ten positions of the homopolymer: held on neither side at any k), ``start_a`` / ``end_a`` (the
-    homopolymer at a contig's start / end: a run from the first / to the last position at any k).  promises["runs"]: name -> contig number."""
+    homopolymer at a contig's start / end: a run from the first / to the last position at any k), ``edges`` (substitutions placed so
+    that runs start at a wave's, a tile's and a chunk's first position, end with a chunk's last, and reach the end of a contig that
+    is a whole number of tiles).  promises["runs"]: name -> contig number."""
     rng = np.random.default_rng(1000 * k + seed)
     drawn = SR.table_keys(rng, table_size(k), k)
     homo = int(drawn[0])
@@ -254,6 +258,13 @@ def crafted(k, min_count=2, seed=0):
     add("homo", b"A" * (k + 9))
     add("start_a", b"A" * (k + 10) + backbone[50:300])
     add("end_a", backbone[300:600] + b"A" * (k + 10))
+    # ``edges``: EDGES_POSITIONS positions of the backbone, a whole number of tiles, with five substitutions — each makes the k
+    # positions whose windows hold it novel: runs that START at positions WAVE, TILE and 2 CHUNK, a run whose last position is
+    # CHUNK - 1, and a run that reaches the contig's end
+    edges = _periodic(backbone[:UNIT], EDGES_POSITIONS + k - 1)
+    for at in (WAVE + k - 1, TILE + k - 1, CHUNK - 1, 2 * CHUNK + k - 1, EDGES_POSITIONS - 1):
+        edges = sub(edges, at)
+    add("edges", edges)
     promises = dict(homo=homo, sat3=sorted(_window_keys(sat3, k)), sat11=sorted(_window_keys(long_c, k)), twice=twice, edge=edge,
                     broken=broken, lower=lower, exact=exact, held=plain[:200], del_at=del_at, runs={n: i for i, n in enumerate(names)})
     return table, [a, b], R, promises

@@ -180,6 +180,16 @@ def test_crafted_holds_every_edge_of_the_kernel(crafted):
     w = words[koff[0]:koff[1]].astype(np.int64)
     assert w[4096] == w[4095] + 2 and w[8192] == w[8191] + 2
     assert (s == 0).any() and (e == nk).any() and ((s == 0) & (e == nk) & (nk == 1)).any()  # first, last, the only position
+    # what the run scan decides from a neighbour that is not the lane below: a run whose last position is 4095 with the next one
+    # starting at 4096 (end and start both from the halo), runs starting at a wave's and at a tile's first lane behind no hit, and
+    # a run closed at the contig's end where the contig is a whole number of tiles, and where it is not
+    at = {(int(ci), int(si)) for ci, si in zip(c, s)}
+    assert any((int(ci), 4096) in at for ci, ei in zip(c, e) if ei == 4096)
+    for first_lane in (64, 256):
+        mine = s == first_lane
+        assert mine.any() and (words[koff[c[mine]] + first_lane - 1] == NO).all(), first_lane
+    assert crafted["nk"][7] <= 2 * 4096 + 300
+    assert ((e == nk) & (nk % 256 == 0)).any() and ((e == nk) & (nk % 256 != 0) & (nk > 1)).any()
     assert (runs[:, 3] & 1).any()                                                    # a minus-strand run
     # pg_postable_mates would give the three copies nothing: their keys are not unique in G
     triple = crafted["promises"]["once in Q, three times in G"]

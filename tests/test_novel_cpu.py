@@ -79,6 +79,13 @@ def test_the_crafted_sample_keeps_its_promises(k):
         assert by["all"] == [(0, 333 - k + 1, 0, 0, 333)]
         assert by["start"] == [(0, 50, 0, 1, 50)] and by["end"] == [(600 - k + 1, n_end, 1, 0, 45)]
         assert [(l, r) for _, _, l, r, _ in by["cut"]] == [(1, 0), (0, 1)] and sum(n for *_, n in by["cut"]) == 60
+        # what the run scan decides from a neighbour that is not the lane below: runs starting at a wave's, a tile's and a chunk's
+        # first position, a run whose last position is a chunk's last, and a run closed at the contig's end — where the contig is
+        # a whole number of tiles (edges) and where it is not (end_a)
+        n_edges = len(R[p["runs"]["edges"]]) - k + 1
+        assert n_edges == NR.EDGES_POSITIONS <= 2 * NR.CHUNK + 300 and n_edges % NR.TILE == 0 and n_end % NR.TILE != 0
+        assert [r[:4] for r in by["edges"]] == [(NR.WAVE, NR.WAVE + k, 1, 1), (NR.TILE, NR.TILE + k, 1, 1), (NR.CHUNK - k, NR.CHUNK, 1, 1),
+                                                (2 * NR.CHUNK, 2 * NR.CHUNK + k, 1, 1), (n_edges - k, n_edges, 1, 0)]
 
 
 def test_bases_on_the_four_edge_pairs():

@@ -810,6 +810,36 @@ int pg_place_last_timing(float *ms_out);
 /* the HIP-event times, in milliseconds, of this host thread's last calls: ms_out[3] = k_copy_insert of the last insert, k_copy_count
  * of the last count, k_copy_profile (all its launches) of the last profile — what tools/copies_rate.py reports. */
 int pg_copies_last_timing(float *ms_out);
+/* genotype: WHICH ALLELE of a variant does a sample carry?  The two calls work on allele ranges of a sequence set instead of whole
+ * contigs (pg_genotype.hip).  With k the table's k:
+ *   allele range    (contig[i], start[i], len[i]): bases [s, s + l) of that contig, s + l <= the contig's length L; l = 0 is the
+ *                   junction between base s - 1 and base s
+ *   allele windows  the k-mer positions p of the contig with max(0, s - k + 1) <= p < min(L - k + 1, s + l): every window that
+ *                   overlaps the allele — for l = 0 the k - 1 windows that hold both neighbours of the junction; none when L < k,
+ *                   none for a junction at s = 0 or s = L; a window holding a non-ACGT base does not exist
+ *   informative     an allele window with canonical key K is informative when own[K] == 1 && other[K] == 0 in the planes named:
+ *                   the k-mer occurs once in the genome the allele comes from and nowhere in the other; it is seen when also
+ *                   sample[K] >= min_count.  A key the table does not hold reads 0 in every plane and is never informative.
+ * pg_copytable_insert_ranges puts the keys of the ranges' allele windows into the table: keys accumulate as with
+ * pg_copytable_insert_seqset, *distinct = the keys this call added, the same sticky PG_E_CAPACITY, and planes counted before it
+ * have missed its keys.  pg_copytable_allele_support reduces three planes along every range: windows_out[i] = the allele windows
+ * that exist, inf_out[i] = the informative ones, seen_out[i] = the seen ones, depth_out[i] = the sum of sample[K] over the
+ * informative ones, in 64 bits.
+ * PG_E_INVALID before anything is launched: a NULL argument with n > 0, a sequence set of another context, a contig number out of
+ * range, start + len beyond the contig, a plane >= nplanes, min_count == 0, own_plane == other_plane, more than 2^31 - 1 pieces.
+ * n == 0 launches nothing and returns PG_OK.  The host cuts every range's windows into pieces of at most 64, one wave's work
+ * (k_allele_insert, k_allele_support: no wave loops over an allele, no block waits for another, the support without atomics); the
+ * pieces' partials are summed per range on the host in 64 bits, the piece list going out in slices when the partials exceed the
+ * 256 MiB pg_copytable_profile caps itself at.  Both calls synchronise. */
+int pg_copytable_insert_ranges(pg_copytable *ct, const pg_seqset *seqs, uint64_t n, const uint32_t *contig, const uint64_t *start,
+                               const uint64_t *len, uint64_t *distinct);
+int pg_copytable_allele_support(pg_copytable *ct, const pg_seqset *seqs, uint64_t n, const uint32_t *contig, const uint64_t *start,
+                                const uint64_t *len, uint32_t own_plane, uint32_t other_plane, uint32_t sample_plane,
+                                uint32_t min_count, uint64_t *windows_out, uint64_t *inf_out, uint64_t *seen_out, uint64_t *depth_out);
+/* the HIP-event times, in milliseconds, of this host thread's last calls: ms_out[2] = k_allele_insert of the last
+ * pg_copytable_insert_ranges, k_allele_support (all its launches) of the last pg_copytable_allele_support — what
+ * tools/genotype_rate.py reports. */
+int pg_genotype_last_timing(float *ms_out);
 /* screen: WHICH of the indexed genomes does a sample hold, and how much of each?  The sample — read sets joined by
  * pg_seqset_from_fastq, or the contigs of an assembly — is streamed through the pan table itself and counted per slot; one pass over
  * the slots joins the counts with the presence masks (pg_screen.hip).  With k the table's k (a sequence set carries none: its

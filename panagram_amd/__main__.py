@@ -46,7 +46,14 @@ against the new samples' k-mers alone, its rows come back from bitmap.1.gz, and 
 anchored the ordinary way, and the tree is staged and renamed at the end, samples.tsv last; and
 `subset <index_dir> -o <out_dir> (--keep A,B,... | --drop C,D,...) [--anchors A,B] [--no-sequence-files]` writes an index of the
 chosen samples into a new directory: the kept anchors' rows come back from bitmap.1.gz and one kernel pass takes the kept columns
-out of them, in the order asked for; no sequence is read."""
+out of them, in the order asked for; no sequence is read; and
+`genotype <index_dir> <A> <B> <sample.fq|sample.fa> [more ...] [--chroms-a X,Y] [--chroms-b X,Y] [-k K] [--min-run N] [--max-gap G]
+[--max-shift S] [--min-count C] [--min-frac F] [--vcf] [--sample NAME] [--summary FILE]` joins the two sides: at every variant of B
+against A that `synteny --variants` calls, which allele does a third, unassembled sample carry?  The k-mers that span either allele go
+into a count table on the GPU, the whole assemblies of A and B and the sample's reads are streamed through it, and per variant and
+allele the k-mers that occur once in the allele's genome and never in the other are counted with those the sample holds: `0/0`, `0/1`,
+`1/1` or `./.`, as a table or as a VCF with a sample column.  Limits: variants closer than k share windows, `--min-count` is the only
+error filter, depths are not modelled (`0/1` is also what a mixture gives), four-line FASTQ, k <= 32, 2^30 keys."""
 import argparse
 import os
 import sys
@@ -183,6 +190,31 @@ def main(argv=None):
                     "basesA basesB per class of variant, then the links without a difference and all links")
     sy.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
     sy.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
+    ge = sub.add_parser("genotype", help="which allele a sample from outside the index carries at every variant of genome B against genome "
+                                         "A: the k-mers that span either allele counted in A, in B and in the sample's reads (or assembly) on "
+                                         "the GPU: tab-separated, with a header, chrA posA refLen chrB posB altLen strand class ref alt "
+                                         "ref_kmers ref_seen ref_depth alt_kmers alt_seen alt_depth GT flag")
+    ge.add_argument("index_dir")
+    ge.add_argument("genome_a", metavar="A")
+    ge.add_argument("genome_b", metavar="B")
+    ge.add_argument("samples", metavar="sample.fq|sample.fa", nargs="+", help="the sample's files: FASTQ (four lines per record) or FASTA, plain or .gz")
+    ge.add_argument("--chroms-a", default="", metavar="X,Y", help="variants on these chromosomes of A only (default: all of them)")
+    ge.add_argument("--chroms-b", default="", metavar="X,Y", help="variants on these chromosomes of B only (default: all of them)")
+    ge.add_argument("-k", type=int, default=None, help="1 to 32 (default: the index's k)")
+    ge.add_argument("--min-run", type=int, default=1, metavar="N", help="as synteny --variants (default 1)")
+    ge.add_argument("--max-gap", type=int, default=1000, metavar="G", help="as synteny --variants (default 1000)")
+    ge.add_argument("--max-shift", type=int, default=100, metavar="S", help="as synteny --variants (default 100)")
+    ge.add_argument("--min-count", type=int, default=None, metavar="C",
+                    help="the sample holds a k-mer it holds at least C times: the only error filter (default: 2 when a file is FASTQ, else 1)")
+    ge.add_argument("--min-frac", type=float, default=0.5, metavar="F",
+                    help="an allele is present when the sample holds at least F of its informative k-mers, above 0 to 1 (default 0.5)")
+    ge.add_argument("--vcf", action="store_true", help="VCF 4.2 lines of synteny --variants --vcf with one sample column GT:RK:AK in place of the table")
+    ge.add_argument("--sample", metavar="NAME", default=None, help="with --vcf: the sample column's name (default: the first sample file's base name)")
+    ge.add_argument("--summary", metavar="FILE", default=None, help="also write class GT count; in front, as # lines, reads, windows, hits, "
+                    "sites, callable sites, min_count and min_frac")
+    ge.add_argument("--batch-bytes", type=int, default=None, metavar="N", help="FASTQ text bytes joined at a time (default 2^28)")
+    ge.add_argument("-o", "--output", metavar="FILE", default=None, help="default: stdout")
+    ge.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")))
     se = sub.add_parser("search", help="which genomes carry each query sequence, and how completely: the queries' k-mers probed against "
                                        "the table of every sample's k-mers and reduced per query and genome on the GPU: tab-separated, with "
                                        "a header, query length kmers genome hits frac covered cov_frac runs longest first end")
@@ -760,6 +792,62 @@ def main(argv=None):
         if a.variants:
             out = out.replace({"ref": {"": "-"}, "alt": {"": "-"}})  # (an empty allele: no empty field in the table)
         out.to_csv(a.output if a.output else sys.stdout, sep="\t", header=False, index=False)
+        return 0
+    if a.cmd == "genotype":
+        if not os.path.isdir(a.index_dir):
+            ap.error(f"genotype: {a.index_dir!r} is not an index directory")
+        if a.genome_a == a.genome_b:
+            ap.error(f"genotype: {a.genome_a!r} against itself has no variants")
+        for r in a.samples:
+            if not os.path.isfile(r):
+                ap.error(f"genotype: no sample file {r!r}")
+        if not 0.0 < a.min_frac <= 1.0:
+            ap.error("genotype: --min-frac is above 0 and at most 1")
+        if a.min_count is not None and a.min_count < 1:
+            ap.error("genotype: --min-count must be at least 1")
+        if a.k is not None and not 1 <= a.k <= 32:
+            ap.error("genotype: -k is 1 to 32")
+        if a.sample is not None and not a.vcf:
+            ap.error("genotype: --sample needs --vcf")
+        if a.batch_bytes is not None and a.batch_bytes < 1:
+            ap.error("genotype: --batch-bytes must be positive")
+        from .index import Index, is_fastq
+        from . import genotype
+        try:
+            idx = Index(a.index_dir, mode="r", device=a.device)
+        except (ValueError, OSError) as e:
+            ap.error(f"genotype: {e}")
+        try:
+            import pandas as pd
+            for g in (a.genome_a, a.genome_b):
+                if g not in idx.genomes:
+                    ap.error(f"genotype: unknown genome {g!r} (the index has {', '.join(idx.genome_names)})")
+                fa = idx[g].fasta
+                if pd.isna(fa) or is_fastq(str(fa)) or not os.path.isfile(str(fa)):
+                    ap.error(f"genotype: genome {g!r} of {a.index_dir} has no assembly FASTA ({fa})")
+            chroms = [[c for c in s.split(",") if c] or None for s in (a.chroms_a, a.chroms_b)]
+            try:
+                table, summary, stats = idx.genotype(a.genome_a, a.genome_b, a.samples, chroms[0], chroms[1], a.k, a.min_run, a.max_gap,
+                                                     a.max_shift, a.min_count, a.min_frac, a.batch_bytes)
+                lens_a = dict(zip(idx.seqset_for(a.genome_a).names, (int(n) for n in idx.seqset_for(a.genome_a).lens)))
+            except (ValueError, KeyError) as e:
+                ap.error(f"genotype: {e}")
+        finally:
+            idx.close()
+        if a.summary:
+            genotype.write_summary(summary, stats, a.summary)
+        if a.vcf:
+            if chroms[0] is not None:
+                lens_a = {n: v for n, v in lens_a.items() if n in chroms[0]}
+            name = a.sample if a.sample is not None else os.path.basename(a.samples[0])
+            f = open(a.output, "w") if a.output else sys.stdout
+            try:
+                f.writelines(line + "\n" for line in genotype.vcf_lines(table, lens_a, name))
+            finally:
+                if a.output:
+                    f.close()
+            return 0
+        genotype.write_main(table, a.output if a.output else sys.stdout)
         return 0
     if a.cmd == "patterns":
         if a.whole == (a.chrom is not None):

@@ -162,6 +162,9 @@ PROTOTYPES = {
     "pg_copies_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
     "pg_copytable_sample_agree": (C.c_int, [_vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pg_place_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
+    "pg_copytable_insert_ranges": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, _u64p]),
+    "pg_copytable_allele_support": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "pg_genotype_last_timing": (C.c_int, [C.POINTER(C.c_float)]),
     "pg_screen_create": (C.c_int, [_vp, _vpp]),
     "pg_screen_destroy": (C.c_int, [_vp]),
     "pg_screen_add_seqset": (C.c_int, [_vp, _vp, _u64p, _u64p]),

@@ -15,9 +15,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpanagram_hip.so")
 OBJ = os.path.join(HERE, "build")
-SOURCES = ["pg_kernels.hip", "pg_anchor.hip", "pg_rows.hip", "pg_deflate.hip", "pg_inflate.hip", "pg_minhash.hip", "pg_bins.hip", "pg_pairs.hip", "pg_find.hip", "pg_patterns.hip", "pg_gaps.hip", "pg_profile.hip", "pg_knn.hip", "pg_tablestats.hip", "pg_synteny.hip", "pg_blocks.hip", "pg_variants.hip", "pg_copies.hip", "pg_locate.hip", "pg_fastq.hip", "pg_place.hip", "pg_screen.hip", "pg_novel.hip", "pg_unitigs.hip", "pg_api.hip", "pg_api_kmc.hip", "pg_api_sketch.hip",
+SOURCES = ["pg_kernels.hip", "pg_anchor.hip", "pg_rows.hip", "pg_deflate.hip", "pg_inflate.hip", "pg_minhash.hip", "pg_bins.hip", "pg_pairs.hip", "pg_find.hip", "pg_patterns.hip", "pg_gaps.hip", "pg_profile.hip", "pg_knn.hip", "pg_tablestats.hip", "pg_synteny.hip", "pg_blocks.hip", "pg_variants.hip", "pg_copies.hip", "pg_genotype.hip", "pg_locate.hip", "pg_fastq.hip", "pg_place.hip", "pg_screen.hip", "pg_novel.hip", "pg_unitigs.hip", "pg_api.hip", "pg_api_kmc.hip", "pg_api_sketch.hip",
            "pg_api_seqset.hip", "pg_api_bgzf.hip", "pg_api_query.hip", "pg_api_patterns.hip", "pg_api_gaps.hip", "pg_api_profile.hip", "pg_api_tablestats.hip", "pg_api_synteny.hip", "pg_api_copies.hip", "pg_api_fastq.hip", "pg_api_screen.hip", "pg_api_novel.hip", "pg_bgzf.cpp"]
-HEADERS = ["pg_device.h", "pg_kernels.h", "pg_planes.h", "pg_rowread.h", "pg_pairblocks.h", "pg_tablescan.h", "pg_guard.h", "pg_host.h", "pg_gaps_host.h", "pg_select_host.h", "pg_profile_host.h", "pg_blocks_link.h", "pg_blocks_host.h", "pg_blocks_pred.h", "pg_copies_host.h", "pg_keytable_dev.h", "pg_keytable_host.h", "pg_postable_dev.h", "pg_runscan.h", "pg_runs_host.h", os.path.join("..", "..", "include", "panagram_hip.h")]
+HEADERS = ["pg_device.h", "pg_kernels.h", "pg_planes.h", "pg_rowread.h", "pg_pairblocks.h", "pg_tablescan.h", "pg_guard.h", "pg_host.h", "pg_gaps_host.h", "pg_select_host.h", "pg_profile_host.h", "pg_blocks_link.h", "pg_blocks_host.h", "pg_blocks_pred.h", "pg_copies_host.h", "pg_genotype_host.h", "pg_keytable_dev.h", "pg_keytable_host.h", "pg_postable_dev.h", "pg_runscan.h", "pg_runs_host.h", os.path.join("..", "..", "include", "panagram_hip.h")]
 # (source, extra defines, object name): the units of one build
 UNITS = [("pg_anchor.hip", ["PG_ANCHOR_PART=2"], "pg_anchor_p2.o"), ("pg_anchor.hip", ["PG_ANCHOR_PART=1"], "pg_anchor_p1.o"),
          ("pg_anchor.hip", ["PG_ANCHOR_PART=0"], "pg_anchor_p0.o"), ("pg_rows.hip", [], "pg_rows.o"), ("pg_api.hip", [], "pg_api.o"),
@@ -29,7 +29,7 @@ UNITS = [("pg_anchor.hip", ["PG_ANCHOR_PART=2"], "pg_anchor_p2.o"), ("pg_anchor.
          ("pg_bins.hip", [], "pg_bins.o"), ("pg_pairs.hip", [], "pg_pairs.o"), ("pg_find.hip", [], "pg_find.o"), ("pg_patterns.hip", [], "pg_patterns.o"), ("pg_gaps.hip", [], "pg_gaps.o"),
          ("pg_knn.hip", [], "pg_knn.o"), ("pg_tablestats.hip", [], "pg_tablestats.o"), ("pg_api_tablestats.hip", [], "pg_api_tablestats.o"),
          ("pg_synteny.hip", [], "pg_synteny.o"), ("pg_blocks.hip", [], "pg_blocks.o"), ("pg_variants.hip", [], "pg_variants.o"),
-         ("pg_api_synteny.hip", [], "pg_api_synteny.o"), ("pg_copies.hip", [], "pg_copies.o"), ("pg_locate.hip", [], "pg_locate.o"), ("pg_api_copies.hip", [], "pg_api_copies.o"),
+         ("pg_api_synteny.hip", [], "pg_api_synteny.o"), ("pg_copies.hip", [], "pg_copies.o"), ("pg_genotype.hip", [], "pg_genotype.o"), ("pg_locate.hip", [], "pg_locate.o"), ("pg_api_copies.hip", [], "pg_api_copies.o"),
          ("pg_fastq.hip", [], "pg_fastq.o"), ("pg_place.hip", [], "pg_place.o"), ("pg_api_fastq.hip", [], "pg_api_fastq.o"),
          ("pg_screen.hip", [], "pg_screen.o"), ("pg_api_screen.hip", [], "pg_api_screen.o"),
          ("pg_novel.hip", [], "pg_novel.o"), ("pg_unitigs.hip", [], "pg_unitigs.o"), ("pg_api_novel.hip", [], "pg_api_novel.o"),

@@ -1,6 +1,6 @@
 // pg_api_copies.hip — host side of the C-ABI: the count table of target k-mers, a genome counted into one of its planes, and the
 // depth histograms of sequences along the planes (pg_copies.hip, pg_copies_host.h); one plane joined with finished bitmap rows
-// (pg_place.hip).
+// (pg_place.hip); allele ranges inserted into the table and three planes reduced along them (pg_genotype.hip, pg_genotype_host.h).
 #include "pg_host.h"
 
 #include "pg_copies_host.h"
@@ -28,6 +28,7 @@ struct pg_copytable {
 namespace {
 
 thread_local float g_copies_ms[3] = {0, 0, 0};  // k_copy_insert, k_copy_count, k_copy_profile of this thread's last calls
+thread_local float g_genotype_ms[2] = {0, 0};   // k_allele_insert, k_allele_support of this thread's last calls
 
 void copytable_free(pg_copytable *ct) {
     hipSetDevice(ct->ctx->device);
@@ -254,6 +255,123 @@ int copytable_sample_agree(pg_copytable *ct, uint32_t plane, uint32_t min_count,
     return PG_OK;
 }
 
+// the ranges of an allele call checked and cut into pieces: range i's pieces are [first[i], first[i + 1])
+int allele_pieces(const char *fn, const pg_copytable *ct, const pg_seqset *sq, uint64_t n, const uint32_t *contig, const uint64_t *start,
+                  const uint64_t *len, std::vector<AllelePiece> &pieces, std::vector<uint64_t> &first) {
+    if (ct->ctx != sq->ctx) return fail(PG_E_INVALID, "%s: table and seqset belong to different contexts", fn);
+    first.assign((size_t)n + 1, 0);
+    uint64_t npieces = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (contig[i] >= sq->n) return fail(PG_E_INVALID, "%s: range %llu names contig %u of %u", fn, (unsigned long long)i, contig[i], sq->n);
+        const uint64_t L = sq->desc[contig[i]].len;
+        if (start[i] > L || len[i] > L - start[i])
+            return fail(PG_E_INVALID, "%s: range %llu, bases [%llu, %llu + %llu) of a contig of %llu", fn, (unsigned long long)i,
+                        (unsigned long long)start[i], (unsigned long long)start[i], (unsigned long long)len[i], (unsigned long long)L);
+        uint64_t p0, p1;
+        allele_windows(L, (uint32_t)ct->k, start[i], len[i], &p0, &p1);
+        first[i] = npieces;
+        npieces += allele_piece_count(p1 - p0);
+        if (npieces > 0x7FFFFFFFull) return fail(PG_E_INVALID, "%s: more than 2^31 - 1 pieces of %u windows", fn, ALLELE_PIECE);
+    }
+    first[n] = npieces;
+    pieces.clear();
+    pieces.reserve(npieces);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint64_t p0, p1;
+        allele_windows(sq->desc[contig[i]].len, (uint32_t)ct->k, start[i], len[i], &p0, &p1);
+        allele_cut(contig[i], p0, p1, pieces);
+    }
+    return PG_OK;
+}
+
+int copytable_insert_ranges(pg_copytable *ct, const pg_seqset *sq, uint64_t n, const uint32_t *contig, const uint64_t *start,
+                            const uint64_t *len, uint64_t *distinct) {
+    const char *fn = "pg_copytable_insert_ranges";
+    std::vector<AllelePiece> pieces;
+    std::vector<uint64_t> first;
+    if (int r = allele_pieces(fn, ct, sq, n, contig, start, len, pieces, first)) return r;
+    if (ct->overflowed) return fail(PG_E_CAPACITY, "%s: the table overflowed before", fn);
+    if (int r = use_device(ct->ctx)) return r;
+    *distinct = 0;
+    g_genotype_ms[0] = 0;
+    if (pieces.empty()) return PG_OK;
+    hipStream_t st = ct->ctx->stream;
+    DevBuf<AllelePiece> d_pieces;
+    DevBuf<unsigned long long> d_ctr;
+    unsigned long long ctr[2] = {0, 0};
+    LaunchTimer tm(&g_genotype_ms[0]);
+    hipError_t e = d_pieces.upload(pieces, st);
+    if (e == hipSuccess) e = d_ctr.alloc(2);
+    if (e == hipErrorOutOfMemory) return fail(PG_E_CAPACITY, "%s: no memory for %zu pieces", fn, pieces.size());
+    if (e == hipSuccess) e = hipMemsetAsync(d_ctr.get(), 0, sizeof ctr, st);
+    if (e == hipSuccess) e = tm.start(st);
+    if (e == hipSuccess)
+        e = launch_allele_insert(st, ct->k, sq->d_desc, d_pieces.get(), (uint32_t)pieces.size(), sq->d_seqw, sq->d_nmw, sq->d_has_n, ct->d_keys,
+                                 ct->nslots, ct->max_probe, d_ctr.get());
+    if (e == hipSuccess) e = tm.stop(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, d_ctr.get(), sizeof ctr, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    tm.read();
+    *distinct = ctr[1];
+    if (ctr[0]) {
+        ct->overflowed = true;
+        return fail(PG_E_CAPACITY, "%s: %llu slots (created for %llu keys) do not hold the ranges' k-mers", fn,
+                    (unsigned long long)ct->nslots, (unsigned long long)ct->capacity);
+    }
+    return PG_OK;
+}
+
+int copytable_allele_support(pg_copytable *ct, const pg_seqset *sq, uint64_t n, const uint32_t *contig, const uint64_t *start,
+                             const uint64_t *len, uint32_t own, uint32_t other, uint32_t sample, uint32_t min_count, uint64_t *windows_out,
+                             uint64_t *inf_out, uint64_t *seen_out, uint64_t *depth_out) {
+    const char *fn = "pg_copytable_allele_support";
+    if (own >= ct->nplanes || other >= ct->nplanes || sample >= ct->nplanes)
+        return fail(PG_E_INVALID, "%s: planes %u, %u, %u of %u", fn, own, other, sample, ct->nplanes);
+    if (own == other) return fail(PG_E_INVALID, "%s: own and other are both plane %u", fn, own);
+    if (min_count == 0) return fail(PG_E_INVALID, "%s: min_count must be >= 1", fn);
+    std::vector<AllelePiece> pieces;
+    std::vector<uint64_t> first;
+    if (int r = allele_pieces(fn, ct, sq, n, contig, start, len, pieces, first)) return r;
+    if (ct->overflowed) return fail(PG_E_CAPACITY, "%s: the table overflowed", fn);
+    if (int r = use_device(ct->ctx)) return r;
+    g_genotype_ms[1] = 0;
+    if (n == 0) return PG_OK;
+    for (uint64_t *out : {windows_out, inf_out, seen_out, depth_out}) std::fill(out, out + n, 0ull);
+    if (pieces.empty()) return PG_OK;  // (no range has a window: zeros)
+    const size_t npieces = pieces.size();
+    const size_t per = std::min(npieces, COPIES_PARTIAL_BYTES / sizeof(AllelePartial));  // pieces per launch
+    hipStream_t st = ct->ctx->stream;
+    DevBuf<AllelePiece> d_pieces;
+    DevBuf<AllelePartial> d_part;
+    std::vector<AllelePartial> part(per);
+    hipError_t e = d_pieces.upload(pieces, st);
+    if (e == hipSuccess) e = d_part.alloc(per);
+    if (e == hipErrorOutOfMemory) return fail(PG_E_CAPACITY, "%s: no memory for %zu pieces", fn, npieces);
+    float total_ms = 0;
+    for (size_t c0 = 0; c0 < npieces && e == hipSuccess; c0 += per) {
+        const size_t m = std::min(per, npieces - c0);
+        float ms = 0;
+        LaunchTimer tm(&ms);
+        e = tm.start(st);
+        if (e == hipSuccess)
+            e = launch_allele_support(st, ct->k, sq->d_desc, d_pieces.get() + c0, (uint32_t)m, sq->d_seqw, sq->d_nmw, sq->d_has_n, ct->d_keys,
+                                      ct->nslots, ct->max_probe, ct->d_planes + (size_t)own * ct->nslots,
+                                      ct->d_planes + (size_t)other * ct->nslots, ct->d_planes + (size_t)sample * ct->nslots, min_count,
+                                      d_part.get());
+        if (e == hipSuccess) e = tm.stop(st);
+        if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_part.get(), m * sizeof(AllelePartial), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) break;
+        tm.read();
+        total_ms += ms;
+        allele_stitch(n, first.data(), part.data(), c0, m, windows_out, inf_out, seen_out, depth_out);
+    }
+    if (e != hipSuccess) return fail(PG_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+    g_genotype_ms[1] = total_ms;
+    return PG_OK;
+}
+
 }  // namespace
 
 extern "C" int pg_copytable_create(pg_ctx *ctx, int k, uint64_t capacity_keys, uint32_t nplanes, pg_copytable **out) {
@@ -325,6 +443,34 @@ extern "C" int pg_copies_last_timing(float *ms_out) {
     PG_API_BEGIN
     if (!ms_out) return fail(PG_E_INVALID, "pg_copies_last_timing: NULL argument");
     std::copy(g_copies_ms, g_copies_ms + 3, ms_out);
+    return PG_OK;
+    PG_API_END
+}
+
+extern "C" int pg_copytable_insert_ranges(pg_copytable *ct, const pg_seqset *seqs, uint64_t n, const uint32_t *contig, const uint64_t *start,
+                                          const uint64_t *len, uint64_t *distinct) {
+    PG_API_BEGIN
+    if (!ct || !seqs || !distinct || (n && (!contig || !start || !len))) return fail(PG_E_INVALID, "pg_copytable_insert_ranges: NULL argument");
+    return copytable_insert_ranges(ct, seqs, n, contig, start, len, distinct);
+    PG_API_END
+}
+
+extern "C" int pg_copytable_allele_support(pg_copytable *ct, const pg_seqset *seqs, uint64_t n, const uint32_t *contig,
+                                           const uint64_t *start, const uint64_t *len, uint32_t own_plane, uint32_t other_plane,
+                                           uint32_t sample_plane, uint32_t min_count, uint64_t *windows_out, uint64_t *inf_out,
+                                           uint64_t *seen_out, uint64_t *depth_out) {
+    PG_API_BEGIN
+    if (!ct || !seqs || (n && (!contig || !start || !len || !windows_out || !inf_out || !seen_out || !depth_out)))
+        return fail(PG_E_INVALID, "pg_copytable_allele_support: NULL argument");
+    return copytable_allele_support(ct, seqs, n, contig, start, len, own_plane, other_plane, sample_plane, min_count, windows_out, inf_out,
+                                    seen_out, depth_out);
+    PG_API_END
+}
+
+extern "C" int pg_genotype_last_timing(float *ms_out) {
+    PG_API_BEGIN
+    if (!ms_out) return fail(PG_E_INVALID, "pg_genotype_last_timing: NULL argument");
+    std::copy(g_genotype_ms, g_genotype_ms + 2, ms_out);
     return PG_OK;
     PG_API_END
 }

@@ -3,6 +3,7 @@
 #include "pg_device.h"
 
 #include "pg_blocks_link.h"
+#include "pg_genotype_host.h"
 #include "pg_select_host.h"
 
 namespace pg {
@@ -369,6 +370,19 @@ hipError_t launch_copy_profile(hipStream_t st, int k, const SeqDesc *sd, const u
                                const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n, const unsigned long long *keys,
                                uint64_t nslots, uint32_t max_probe, const uint32_t *planes, uint32_t nplanes, uint32_t *partial,
                                uint32_t *valid_partial, uint16_t *depth, uint64_t depth_stride);
+// allele ranges against the count table (pg_genotype.hip; the definitions are there).  pieces[i] = windows [p0, p0 + n) of a contig
+// of sd, 1 <= n <= ALLELE_PIECE, all below the contig's len - k + 1 (pg_genotype_host.h cuts them); at most 2^31 - 1 pieces, four
+// to a block.  The count table as launch_copy_insert / launch_copy_profile take it.
+//   insert   claims a slot for the key of every piece window that exists; ctr as launch_copy_insert's
+//   support  own, other, sample: three planes of nslots counters; partial[i] = piece i's {windows | inf << 16 | seen << 32, depth};
+//            min_count >= 1.  No atomics.
+hipError_t launch_allele_insert(hipStream_t st, int k, const SeqDesc *sd, const AllelePiece *pieces, uint32_t npieces, const uint64_t *seqw,
+                                const uint32_t *nmw, const uint32_t *has_n, unsigned long long *keys, uint64_t nslots,
+                                uint32_t max_probe, unsigned long long *ctr);
+hipError_t launch_allele_support(hipStream_t st, int k, const SeqDesc *sd, const AllelePiece *pieces, uint32_t npieces,
+                                 const uint64_t *seqw, const uint32_t *nmw, const uint32_t *has_n, const unsigned long long *keys,
+                                 uint64_t nslots, uint32_t max_probe, const uint32_t *own, const uint32_t *other, const uint32_t *sample,
+                                 uint32_t min_count, AllelePartial *partial);
 // FASTQ text to the ASCII of one contig (pg_fastq.hip; the definitions are there): `text` is readable, and zero past nbytes, up to
 // ntiles * FASTQ_TILE + 16 bytes, ntiles = ceil(nbytes / FASTQ_TILE).
 //   scan  sums[tile] per tile (k_fastq_scan), then bases[tile] = {first output byte, first line number} and summary[3] = {line

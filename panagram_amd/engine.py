@@ -850,6 +850,34 @@ class CopyTable:
                                                   _ptr(ends), _ptr(valid), _ptr(held), _ptr(col), _ptr(both)))
         return valid, held, col, both
 
+    def insert_ranges(self, seqs: SeqSet, contigs, starts, lens) -> int:
+        """the keys of the allele windows of ranges ``(contigs[i], starts[i], lens[i])`` of ``seqs`` into the table — every k-mer
+        window that overlaps bases ``[start, start + len)`` of that contig; ``len == 0`` is the junction in front of base
+        ``start``, whose windows hold both its neighbours (pg_genotype.hip) — as ``insert`` puts whole contigs in, without a
+        contig cut per range; the keys this call added"""
+        contigs, starts, lens = _windows(contigs, starts, lens, "range")
+        n = C.c_uint64()
+        check(self._lib.pg_copytable_insert_ranges(self._h, seqs._h, len(contigs), _ptr(contigs), _ptr(starts), _ptr(lens), C.byref(n)))
+        return int(n.value)
+
+    def allele_support(self, seqs: SeqSet, contigs, starts, lens, own: int, other: int, sample: int, min_count: int):
+        """(windows, inf, seen, depth) uint64 per range ``(contigs[i], starts[i], lens[i])`` of ``seqs``: its allele windows that
+        exist; the informative ones, whose k-mer plane ``own`` counted exactly once and plane ``other`` never; those of them plane
+        ``sample`` counted at least ``min_count`` times; and the sum of ``sample``'s counts over the informative ones (one launch
+        family, four integers per range come back: pg_genotype.hip).  A k-mer the table does not hold is never informative."""
+        if min(own, other, sample) < 0 or min_count < 0:
+            raise ValueError(f"planes {own}, {other}, {sample}, min_count {min_count}")
+        contigs, starts, lens = _windows(contigs, starts, lens, "range")
+        n = len(contigs)
+        out = [np.zeros(n, np.uint64) for _ in range(4)]
+        check(self._lib.pg_copytable_allele_support(self._h, seqs._h, n, _ptr(contigs), _ptr(starts), _ptr(lens), int(own), int(other),
+                                                    int(sample), int(min_count), *[_ptr(x) for x in out]))
+        return tuple(out)
+
+    @staticmethod
+    def genotype_last_timing() -> dict:
+        return genotype_last_timing()
+
     def close(self) -> None:
         if self._h:
             self._lib.pg_copytable_destroy(self._h)
@@ -867,6 +895,14 @@ def copies_last_timing() -> dict:
     ms = (C.c_float * 3)()
     check(_lib.load().pg_copies_last_timing(ms))
     return dict(zip(("insert_ms", "count_ms", "profile_ms"), (float(x) for x in ms)))
+
+
+def genotype_last_timing() -> dict:
+    """HIP-event milliseconds of k_allele_insert and k_allele_support in this thread's last ``CopyTable.insert_ranges`` and
+    ``CopyTable.allele_support``"""
+    ms = (C.c_float * 2)()
+    check(_lib.load().pg_genotype_last_timing(ms))
+    return dict(zip(("insert_ms", "support_ms"), (float(x) for x in ms)))
 
 
 def place_last_timing() -> dict:

@@ -1833,6 +1833,82 @@ class Index:
         alignment: a single mismatch ends a segment; ``synteny_blocks_tables`` chains the segments into blocks."""
         return self.synteny_tables(a, b, chroms_a, chroms_b, k, min_len)[0]
 
+    def genotype(self, a, b, samples, chroms_a=None, chroms_b=None, k=None, min_run=1, max_gap=1000, max_shift=100, min_count=None,
+                 min_frac=0.5, batch_bytes: Optional[int] = None):
+        """(table, summary, stats) — ``genotype.frames`` and ``genotype.stats`` — of ONE sample from outside the index at every
+        variant of genome ``b`` against genome ``a``: which allele it carries.  The variants are those of
+        ``synteny_variants_tables`` with the same arguments.  The k-mers that span either allele of every variant go into a count
+        table of three planes (``engine.CopyTable.insert_ranges``: no contig is cut per variant); plane 0 is counted from the
+        WHOLE assembly of ``a`` and plane 1 from the whole assembly of ``b``, also when ``chroms_a`` / ``chroms_b`` narrowed the
+        variant calling — the sample's reads come from the whole genome, so uniqueness is judged against all of it; the sample
+        is streamed into plane 2 as ``screen`` streams it (``samples``, ``batch_bytes`` and the default of ``min_count`` as
+        there); and ``engine.CopyTable.allele_support`` reduces the planes along A's alleles and along B's to four integers per
+        variant and side.  The call rule with ``min_frac`` is ``genotype.call``'s.  ValueError: ``a == b``, a genome without an
+        assembly FASTA, a missing sample file, ``min_frac`` outside (0, 1], ``min_count`` below 1, what ``synteny_variants_tables``
+        refuses; KeyError: an unknown genome."""
+        from . import genotype as gt, place as pl, screen as scr
+        for g in (a, b):
+            if g not in self.genomes:
+                raise KeyError(f"genotype: unknown genome {g!r} (the index has {', '.join(self.genome_names)})")
+        if a == b:
+            raise ValueError(f"genotype: {a!r} against itself has no variants")
+        for g in (a, b):
+            fa = self.genomes[g].fasta
+            if pd.isna(fa) or is_fastq(str(fa)) or not os.path.isfile(str(fa)):
+                raise ValueError(f"genotype: genome {g!r} has no assembly FASTA ({fa})")
+        samples = [samples] if isinstance(samples, (str, os.PathLike)) else list(samples)
+        paths = [os.fspath(p) for p in samples]
+        for p in paths:
+            if not os.path.isfile(p):
+                raise ValueError(f"genotype: no sample file {p!r}")
+        min_frac = gt.check_min_frac(min_frac)
+        min_count = gt.check_min_count(scr.default_min_count(any(is_fastq(p) for p in paths)) if min_count is None else min_count)
+        batch_bytes = pl.DEFAULT_BATCH_BYTES if batch_bytes is None else int(batch_bytes)
+        if batch_bytes < 1:
+            raise ValueError(f"genotype: batch_bytes must be positive, got {batch_bytes}")
+        variants = self.synteny_variants_tables(a, b, chroms_a, chroms_b, k, min_run, max_gap, max_shift)[0]
+        k = int(self.k) if k is None else int(k)
+        ctx = self.context
+        ss_a, ss_b = self.seqset_for(a), self.seqset_for(b)
+        ranges_a, ranges_b = gt.allele_ranges(variants, list(ss_a.names), list(ss_b.names))
+        zero = tuple(np.zeros(0, np.uint64) for _ in range(4))
+        reads = hits = 0
+        if len(variants):
+            # a range of l bases has at most l + k - 1 windows: enough for the distinct keys of both sides
+            capacity = sum(int(r[2].sum()) + (k - 1) * len(variants) for r in (ranges_a, ranges_b))
+            table = engine.CopyTable(ctx, k, max(capacity, 1), 3)
+            try:
+                table.insert_ranges(ss_a, *ranges_a)
+                table.insert_ranges(ss_b, *ranges_b)
+                table.count(0, ss_a)
+                table.count(1, ss_b)
+                for p in paths:
+                    if is_fastq(p):
+                        fb = pl.FastqBatches(p, batch_bytes)
+                        for buf in fb:
+                            rs, n, used = engine.SeqSet.from_fastq(ctx, buf)
+                            try:
+                                hits += table.count(2, rs)
+                                reads += int(n)
+                            finally:
+                                rs.close()
+                            fb.advance(used)
+                    else:
+                        ss = engine.SeqSet.from_fasta(ctx, p)
+                        try:
+                            hits += table.count(2, ss)
+                            reads += len(ss.lens)
+                        finally:
+                            ss.close()
+                sup_a = table.allele_support(ss_a, *ranges_a, 0, 1, 2, min_count)
+                sup_b = table.allele_support(ss_b, *ranges_b, 1, 0, 2, min_count)
+            finally:
+                table.close()
+        else:
+            sup_a = sup_b = zero
+        out, summary = gt.frames(variants, sup_a, sup_b, min_frac)
+        return out, summary, gt.stats(out, sup_a, sup_b, reads, hits, min_count, min_frac)
+
     def region_tree(self, genome, chrom, start=None, end=None, step=None) -> "RegionTree":
         """The tree of the genomes over a region, as the viewer draws it (view.py:751-764: create_tree) — but from the pair
         counts of EVERY row of the region at ``step`` (default: the low-resolution step), not from a random sample of

@@ -26,6 +26,7 @@ def _check(ctx, text, tag):
         if got != want:
             at = next(i for i, (a, b) in enumerate(zip(got, want)) if a != b)
             raise AssertionError(f"{tag}: base {at} of {len(want)}: {got[at - 5:at + 5]!r} != {want[at - 5:at + 5]!r}")
+        return got
     finally:
         ss.close()
 
